@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """Headline benchmark: ADMM iterations/s of the tall Lasso lambda path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
+
+A plain run sets up, runs W warm-up steps, times K steps and prints one JSON line (`ms_per_step` = milliseconds per timed
+step).  `--full` adds everything else described below: the steady-state setup (`setup_s`, `sec_to_eps`), `cpu_baseline`, the
+other BASELINE configs (`configs`) and the side measurements.  `--dump-outputs DIR` writes what the last timed step returned
+(lambda.npy, beta.npy, niter.npy; see dump_outputs) so that two builds can be compared output for output.
 
 Workload (BASELINE.json configs[1], SURVEY.md section 8d "C2"): admm_lasso tall, n=100000,
 p=10000, fp32 solver arithmetic, automatic 100-lambda grid (lambda_min_ratio 1e-4), warm-started,
@@ -11,8 +16,9 @@ HBM (X ~ N(0, 2^2), beta* = U(0,1) on the first 1000 coordinates, y = X beta* + 
 A "step" is one pass of the hot path: the complete warm-started lambda path (the loop of
 Lasso.cpp:97-124 -> FADMMBase::solve) from a cold start on the resident data.  The one-time
 preparation the reference does before that loop (convert, DataStd, X'y, Gram, Spectra, Cholesky)
-runs once before the timed region and is reported separately as `setup_s`; `sec_to_eps` =
-setup + one path.  value = sum of ADMM iterations of the K timed steps (over all ranks) divided
+runs once before the timed region and is reported separately as `setup_s_cold` (with --full a
+second time, steady state, as `setup_s`); `sec_to_eps[_cold]` = that setup + one path.
+value = sum of ADMM iterations of the K timed steps (over all ranks) divided
 by the max-over-ranks wall time of the timed region.
 
 N > 1 (one process per GPU; `python bench.py --gpus N` started WITHOUT a launcher re-executes itself under
@@ -25,7 +31,7 @@ disagrees with --gpus is refused -- a line saying n_gpus: 1 can not come out of 
     lambda converged; otherwise the line falls back to the replica figure and says so (`parallelism`).
   * `replicas_weak`: N independent replicas of the single-GPU solver (what the reference's serial solver offers,
     SURVEY.md 8e "replicas only"), no data-path collective.
-  * side objects, each from time-limited child processes with their own rendezvous so that a failing exchange can
+  * with --full, side objects, each from time-limited child processes with their own rendezvous so that a failing exchange can
     never take the primary line down: `exchange_self_check` (both back-ends against a closed-form sum, first),
     `consensus` (BASELINE configs[3]: 8 row blocks spread over the ranks, one grouped all-reduce of p floats per
     iteration), `wide_column_sharded` (configs[2] with its columns spread over the ranks, all-reduce of n floats).
@@ -33,7 +39,7 @@ disagrees with --gpus is refused -- a line saying n_gpus: 1 can not come out of 
 Extra objects on the JSON line: `roofline` for the dominant kernel (the x-update mat-vec: 2*p^2
 algorithmic bytes per launch for the symmetric lower-triangle kernel, 4*p^2 for the full-matrix
 one; durations from kernel-exact HIP start/stop events recorded by the library on its own stream
-inside the timed region) and `cpu_baseline` (the compiled C restatement of the same loop,
+inside the timed region) and, with --full, `cpu_baseline` (the compiled C restatement of the same loop,
 oracle/c, timed on the host cores on a bounded sample: the reference's one-core configuration,
 and a best-effort all-core cached-inverse variant beside it).
 """
@@ -90,6 +96,11 @@ def parse():
     ap.add_argument("--m", type=int, default=1000, help="non-zeros in beta*")
     ap.add_argument("--nlambda", type=int, default=100)
     ap.add_argument("--seed", type=int, default=123)
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the steady-state setup, cpu_baseline, the other BASELINE configs "
+                         "and the side measurements (without it: setup, warm-up, the timed steps and the result line only)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step returned (lambda, beta, niter) to DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline loop (0 disables)")
     ap.add_argument("--profile-stride", type=int, default=32, help="time every k-th x-update launch with HIP events")
     ap.add_argument("--consensus-seconds", type=float, default=180.0,
@@ -104,8 +115,34 @@ def parse():
     ap.add_argument("--side-shapes", default="", help=argparse.SUPPRESS)      # test hook: "n,p" of the consensus child and "n,p,nl" of the wide child, ";"-separated (tests/test_gpu_bench_children.py)
     ap.add_argument("--child", default="", help=argparse.SUPPRESS)
     if os.environ.get("ADMM_BENCH_ARGV") and "--child" not in sys.argv:      # a self-spawned rank (self_spawn): the original argument list
-        return ap.parse_args(json.loads(os.environ["ADMM_BENCH_ARGV"]))
-    return ap.parse_args()
+        a = ap.parse_args(json.loads(os.environ["ADMM_BENCH_ARGV"]))
+    else:
+        a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return a
+
+
+DUMP_BUDGET_BYTES = 64 * 10**6
+
+
+def dump_outputs(fit, out_dir):
+    """--dump-outputs: what LassoPlan.run() handed its caller in the last timed step -- the lambda grid, the (p+1) x nlambda
+    coefficients (intercept first) and the iteration counts -- as DIR/lambda.npy (float64), DIR/beta.npy (float32) and DIR/niter.npy
+    (float64).  Above 64 MB in all, beta.npy holds a fixed seeded sample of its rows and DIR/beta_rows.npy (float64) says which."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"lambda": np.asarray(fit.lambda_, dtype=np.float64), "niter": np.asarray(fit.niter, dtype=np.float64)}
+    beta = np.ascontiguousarray(fit.beta_dense, dtype=np.float32)
+    room = DUMP_BUDGET_BYTES - 4096 - sum(v.nbytes for v in arrays.values())      # 4096: the .npy headers
+    if beta.nbytes > room:
+        row_bytes = beta.shape[1] * beta.itemsize + 8                # a kept row: its floats plus its index in beta_rows.npy
+        rows = np.sort(np.random.default_rng(0).choice(beta.shape[0], room // row_bytes, replace=False))
+        beta = np.ascontiguousarray(beta[rows])
+        arrays["beta_rows"] = rows.astype(np.float64)
+    arrays["beta"] = beta
+    for name, v in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), v)
 
 
 def cpu_baseline(p, nlambda, budget_s, seed, n_full=None):
@@ -864,19 +901,21 @@ def main():
     y = beta_true @ xt + torch.randn(n, generator=g, device=dev, dtype=torch.float64)
     torch.cuda.synchronize()
 
-    # ---- one-time preparation (outside the timed region), done twice: the first call of a process also pays the lazy
-    # loading of the library's code objects and the first large allocations (what a fresh R session's first $fit() pays),
-    # the second is the steady-state cost.
+    # ---- one-time preparation (outside the timed region).  The first call of a process also pays the lazy loading of the
+    # library's code objects and the first large allocations (what a fresh R session's first $fit() pays); with --full it is
+    # done a second time for the steady-state cost (`setup_s`).
     model = admm_lasso(DevicePtr(xt.data_ptr()), DevicePtr(y.data_ptr()), n=n, p=p).penalty(nlambda=a.nlambda)
     t0 = time.time()
     plan = LassoPlan(model)
     lib.admm_hip_device_synchronize()
     setup_s_cold = time.time() - t0
-    plan.close()
-    t0 = time.time()
-    plan = LassoPlan(model)
-    lib.admm_hip_device_synchronize()
-    setup_s = time.time() - t0
+    setup_s = None
+    if a.full:
+        plan.close()
+        t0 = time.time()
+        plan = LassoPlan(model)
+        lib.admm_hip_device_synchronize()
+        setup_s = time.time() - t0
     del xt
     torch.cuda.empty_cache()
 
@@ -908,12 +947,15 @@ def main():
         elapsed_max, iters_all = float(tmax[0]), float(tsum[1])
     else:
         elapsed_max, iters_all = elapsed, float(iters)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(fit, a.dump_outputs)
 
-    # ---- side measurements in child processes (own rendezvous, time-limited): the paths with a real exchange step
+    # ---- side measurements in child processes (own rendezvous, time-limited): the paths with a real exchange step.  At N > 1 the
+    # sharded run of the headline workload is the primary figure; everything else runs with --full only.
     consensus, shard = [], []
     exch = []
     backends = tuple(b for b in a.exchanges.split(",") if b in ("rccl", "peer"))
-    if multi:
+    if multi and a.full:
         for k, backend in enumerate(backends):
             exch.append(run_side_measurement(a, rank, world, "exchcheck", backend, 120.0, 5 + 6 * k))
             barrier()
@@ -924,7 +966,7 @@ def main():
                     sys.stderr.write("[bench] exchange self-check over %s FAILED at %d ranks: %s -- the measurements over it are kept apart as `rejected` / `error`; "
                                      "continuing with %s\n" % (c["exchange"], world, c.get("error", "sums differ from the closed form (relative error %.2e)" % c.get("worst_relative_error_rank0", float("nan"))),
                                                                  ", ".join(good) if good else "the replica figure only"))
-    if a.consensus_seconds > 0:
+    if a.full and a.consensus_seconds > 0:
         for k, backend in enumerate(backends if multi else ("rccl",)):
             consensus.append(run_side_measurement(a, rank, world, "consensus", backend, a.consensus_seconds, 17 + 12 * k))
             barrier()
@@ -933,11 +975,12 @@ def main():
         for k, backend in enumerate(backends):
             shard.append(run_side_measurement(a, rank, world, "tallshard", backend, a.shard_seconds, 41 + 12 * k))
             barrier()
-        for k, backend in enumerate(backends):
-            widecols.append(run_side_measurement(a, rank, world, "widecols", backend, a.shard_seconds, 71 + 12 * k))
-            barrier()
+        if a.full:
+            for k, backend in enumerate(backends):
+                widecols.append(run_side_measurement(a, rank, world, "widecols", backend, a.shard_seconds, 71 + 12 * k))
+                barrier()
     cfg_results = {}
-    if world == 1 and not FORCE_DIST and a.config_seconds > 0:
+    if a.full and world == 1 and not FORCE_DIST and a.config_seconds > 0:
         # the headline plan's 400 MB inverse stays resident; the children need up to ~20 GB each (fp64 inputs + fp32 / fp64 copies)
         for k, name in enumerate(CONFIGS):
             cfg_results[name] = run_side_measurement(a, rank, world, "config", name, a.config_seconds, 101 + k)
@@ -982,9 +1025,7 @@ def main():
                        "standardize": True, "intercept": True, "eps_abs": 1e-5, "eps_rel": 1e-5,
                        "parallelism": "replicas x%d" % world if world > 1 else "single GPU",
                        "iters_per_step": iters / a.steps, "step": "one cold-started warm-chained lambda path"},
-            "setup_s": setup_s,
             "setup_s_cold": setup_s_cold,
-            "sec_to_eps": setup_s + elapsed / a.steps,
             "sec_to_eps_cold": setup_s_cold + elapsed / a.steps,
             "setup_breakdown_s": {k: fit.stats[k] for k in ("t_h2d", "t_standardize", "t_gram", "t_eigs", "t_factor")},
             "loop_ms_events_per_step": loop_ms / a.steps,
@@ -996,6 +1037,9 @@ def main():
                          "algorithmic_bytes_per_launch": alg_bytes, "avg_launch_ms": x_ms, "launches_timed": xsamp,
                          "survey_4p2_equivalent_GBps": 4.0 * p * p / (x_ms * 1e-3) / 1e9 if x_ms > 0 else 0.0},
         }
+        if setup_s is not None:
+            out["setup_s"] = setup_s
+            out["sec_to_eps"] = setup_s + elapsed / a.steps
         consensus = [c for c in consensus if c]
         shard = [c for c in shard if c]
         if exch:
@@ -1046,7 +1090,7 @@ def main():
                 out["setup_s"] = best["setup_s"]
                 out["sec_to_eps"] = best["setup_s"] + best["elapsed_s"] / best["steps"]
                 out["roofline"]["note"] = "single-GPU replica kernel; the sharded run's share is in `sharded`"
-        if a.cpu_seconds > 0 and world == 1:                # the CPU leg is timed on rank 0 at N = 1 only
+        if a.full and a.cpu_seconds > 0 and world == 1:     # the CPU leg is timed on rank 0 at N = 1 only
             try:
                 out["cpu_baseline"] = cpu_baseline(p, a.nlambda, a.cpu_seconds, a.seed, n_full=n)
             except Exception as e:                          # noqa: BLE001 -- never lose the GPU line to the CPU leg

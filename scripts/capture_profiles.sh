@@ -14,7 +14,7 @@ grep '^{"metric"' $OUT/trace_bench.log | tail -1 > $OUT/tall_c2_kernel_stats_ben
 rocprofv3 --pmc FETCH_SIZE --kernel-trace -d $OUT/pmc_fetch -o c2 -- python bench.py --steps 1 --warmup 0 --cpu-seconds 0 --consensus-seconds 0 --config-seconds 0 --nlambda 10 > $OUT/pmc_fetch.log 2>&1
 rocprofv3 --pmc WRITE_SIZE --kernel-trace -d $OUT/pmc_write -o c2 -- python bench.py --steps 1 --warmup 0 --cpu-seconds 0 --consensus-seconds 0 --config-seconds 0 --nlambda 10 > $OUT/pmc_write.log 2>&1
 python scripts/rocpd_pmc.py $OUT/pmc_fetch/c2_results.db $OUT/pmc_write/c2_results.db $OUT/tall_c2_pmc_hbm_bytes.md
-python bench.py > $OUT/bench_default.log 2>&1
+python bench.py --full > $OUT/bench_default.log 2>&1
 grep '^{"metric"' $OUT/bench_default.log | tail -1 > $OUT/bench_all_configs.json
 python scripts/bench_configs.py c3 c4 c5lad c5bp c5parbp dantzig > $OUT/bench_configs.jsonl 2> $OUT/bench_configs.err
 for c in c3 c4 c5lad c5bp c5parbp dantzig; do

@@ -87,7 +87,7 @@ def test_bench_gpus2_without_a_launcher_spawns_its_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(ADMM_BENCH_OVERSUBSCRIBE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--n", "24000", "--p", "2304", "--m", "100", "--nlambda", "12", "--steps", "1",
-           "--warmup", "1", "--exchanges", "peer", "--consensus-seconds", "0", "--shard-seconds", "240", "--cpu-seconds", "0",
+           "--warmup", "1", "--full", "--exchanges", "peer", "--consensus-seconds", "0", "--shard-seconds", "240", "--cpu-seconds", "0",
            "--side-shapes", "2000,20000;600,30000,8"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
