@@ -25,7 +25,8 @@ class AdmmHipOptions(ctypes.Structure):
     _fields_ = [(k, ctypes.c_int) for k in (
         "struct_size", "gram_backend", "gram_split", "factor_backend", "inverse_precision", "tall_xupdate", "tall_refine",
         "consensus_two_pass", "consensus_unfused", "bp_two_pass", "lad_no_hat", "wide_no_persist", "wide_unfused", "wide_gram_sprad",
-        "sharing_bp_direct", "cv_downdate", "peer_exchange", "batch_iters", "profile_stride", "pool_mb", "screen", "lad_two_pass")] + [("reserved", ctypes.c_int * 10)]
+        "sharing_bp_direct", "cv_downdate", "peer_exchange", "batch_iters", "profile_stride", "pool_mb", "screen", "lad_two_pass",
+        "par_devices")] + [("reserved", ctypes.c_int * 9)]
 
 
 class AdmmStats(ctypes.Structure):
@@ -71,7 +72,8 @@ EXPORTS = ["admm_hip_lasso", "admm_hip_enet", "admm_hip_parlasso", "admm_hip_lad
            "admm_hip_lasso_plan_create_dist_cols", "admm_hip_lasso_cv", "admm_hip_lasso_multi",
            "admm_hip_parbp", "admm_hip_parbp_traced", "admm_hip_parbp_dist", "admm_hip_dantzig", "admm_hip_dantzig_traced",
            "admm_hip_lad_state", "admm_hip_bp_state", "admm_hip_lasso_plan_data_read", "admm_hip_trim_memory", "admm_hip_test_gather",
-           "admm_hip_options_default", "admm_hip_options_set", "admm_hip_option_set", "admm_hip_options_reset", "admm_hip_option_get"]
+           "admm_hip_options_default", "admm_hip_options_set", "admm_hip_option_set", "admm_hip_options_reset", "admm_hip_option_get",
+           "admm_hip_last_parallel_layout", "admm_hip_parallel_assign"]
 
 TRACE_FIELDS = 12
 TRACE_COLD, TRACE_CONVERGED, TRACE_ACCELERATE, TRACE_RESTART = -1, 0, 1, 2
@@ -222,6 +224,10 @@ def load():
     lib.admm_hip_host_lanczos.restype = ctypes.c_int
     lib.admm_hip_test_gather.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, _c_double_p]
     lib.admm_hip_test_gather.restype = ctypes.c_int
+    lib.admm_hip_last_parallel_layout.argtypes = [_c_int_p, _c_int_p, ctypes.c_int]
+    lib.admm_hip_last_parallel_layout.restype = ctypes.c_int
+    lib.admm_hip_parallel_assign.argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.c_int, _c_int_p, _c_int_p, ctypes.c_int]
+    lib.admm_hip_parallel_assign.restype = ctypes.c_int
     lib.admm_hip_trim_memory.argtypes = []
     lib.admm_hip_trim_memory.restype = ctypes.c_int
     _lib = lib
@@ -264,10 +270,14 @@ class options:
 
     def __enter__(self):
         lib = load()
-        for k, v in self.kw.items():
-            cur = lib.admm_hip_option_get(k.encode())
-            self.old[k] = cur.decode() if cur is not None else None
-            check(lib.admm_hip_option_set(k.encode(), None if v is None else v.encode()))
+        try:
+            for k, v in self.kw.items():
+                cur = lib.admm_hip_option_get(k.encode())
+                self.old[k] = cur.decode() if cur is not None else None
+                check(lib.admm_hip_option_set(k.encode(), None if v is None else v.encode()))
+        except BaseException:
+            self.__exit__(None, None, None)          # a failure part-way: what was already set goes back
+            raise
         return self
 
     def __exit__(self, *exc):
@@ -295,3 +305,24 @@ class options:
             setattr(o, k, int(v))
         check(lib.admm_hip_options_set(ctypes.byref(o)))
         return o
+
+
+def last_parallel_layout():
+    """Devices of the ranks of the calling thread's last admm_hip_parlasso / admm_hip_parbp call (admm_hip_last_parallel_layout):
+    one entry for the single-device path, one per rank with PAR_DEVICES, [] before any such call."""
+    lib = load()
+    nr = ctypes.c_int(0)
+    devs = (ctypes.c_int * 64)()
+    check(lib.admm_hip_last_parallel_layout(ctypes.byref(nr), devs, 64))
+    return [int(devs[r]) for r in range(min(nr.value, 64))]
+
+
+def parallel_assign(nblocks, par_devices, device_count):
+    """Host-only (admm_hip_parallel_assign): the devices of the ranks a PAR_DEVICES call with `nblocks` blocks would run, [] when it
+    runs the single-device path."""
+    lib = load()
+    nr = ctypes.c_int(0)
+    devs = (ctypes.c_int * 64)()
+    check(lib.admm_hip_parallel_assign(int(nblocks), None if par_devices is None else str(par_devices).encode(), int(device_count),
+                                       ctypes.byref(nr), devs, 64))
+    return [int(devs[r]) for r in range(nr.value)] if nr.value > 1 else []

@@ -36,6 +36,21 @@ def _shape(x, n, p):
     return a.shape
 
 
+def _devices_option(devices):
+    """PAR_DEVICES value of $parallel(devices=...): None, "all", "0,1" or a sequence of device numbers."""
+    if devices is None:
+        return None
+    if isinstance(devices, str):
+        return devices
+    return ",".join(str(int(d)) for d in devices)
+
+
+def _par_devices(model):
+    """The calling thread's PAR_DEVICES for the duration of one parallel fit (restored afterwards, also on error)."""
+    dev = getattr(model, "devices", None)
+    return _lib.options(PAR_DEVICES=dev) if dev is not None else _lib.options()
+
+
 def _beta_to_csc(beta_dense):
     """(p+1) x nlambda dense -> CSC holding row 0 always plus the non-zeros (Lasso.cpp:22-30)."""
     p1, nl = beta_dense.shape
@@ -136,13 +151,17 @@ class ADMM_Lasso:
         self.lambda_min_ratio = lmr
         return self
 
-    def parallel(self, nthread=2):
+    def parallel(self, nthread=2, devices=None):
+        """devices (not in R): spread the nthread blocks over devices in this process -- "all", a list such as [0, 1] or "0,1"
+        (repeats put several ranks on one device: a test / diagnostic form), None = the single-device default.  Sets the option
+        PAR_DEVICES around the fit only (include/admm_hip.h, admm_hip_parlasso)."""
         nt = int(nthread)
         if nt < 1:
             nt = 1
         if nt >= self.p / 5:
             _stop("nthread cannot exceed ncol(x)/5")                             # R/30_admm_lasso.R:105-106
         self.nthread = nt
+        self.devices = _devices_option(devices)
         return self
 
     def opts(self, maxit=10000, eps_abs=1e-5, eps_rel=1e-5, rho=None):
@@ -241,7 +260,8 @@ class ADMM_Lasso:
         if self.nthread <= 1:
             check(lib.admm_hip_lasso(*head, *tail))                              # .Call("admm_lasso", ...)
         else:
-            check(lib.admm_hip_parlasso(*head, self.nthread, *tail))             # .Call("admm_parlasso", ...)
+            with _par_devices(self):
+                check(lib.admm_hip_parlasso(*head, self.nthread, *tail))         # .Call("admm_parlasso", ...)
         return ADMM_Lasso_fit(lam_out, beta, niter, stats.as_dict())
 
 
@@ -350,13 +370,15 @@ class ADMM_BP:
         self.eps_rel = 1e-4
         self.rho = 1.0
 
-    def parallel(self, nthread=2):
+    def parallel(self, nthread=2, devices=None):
         """ADMM_BP$parallel (R/10_admm_bp.R:65-76) only stores nthread; $fit() with nthread > 1 then calls the C symbol
         `admm_parbp`, which the reference never builds (it lives in src/TODO/ParBP.cppp) -- the R call fails there; here it
         runs the column-block sharing solver (admm_hip_parbp).  The setter clamps to >= 1 and stores, exactly like R (no
         ncol(x)/5 check here: only ADMM_Lasso$parallel has one, R/30_admm_lasso.R:119-124).  ADMM_LAD inherits this method
-        as in R (`contains = "ADMM_BP"`, R/20_admm_lad.R:4) and, as in R, its fit() ignores nthread."""
+        as in R (`contains = "ADMM_BP"`, R/20_admm_lad.R:4) and, as in R, its fit() ignores nthread.  devices: as for
+        ADMM_Lasso.parallel (PAR_DEVICES around the admm_hip_parbp call)."""
         self.nthread = max(1, int(nthread))
+        self.devices = _devices_option(devices)
         return self
 
     def opts(self, maxit=10000, eps_abs=1e-4, eps_rel=1e-4, rho=1.0):
@@ -387,9 +409,10 @@ class ADMM_BP:
         if getattr(self, "nthread", 1) > 1:
             # .Call("admm_parbp", x, y, nthread, list(maxit, eps_abs, eps_rel, rho_ratio = rho)), R/10_admm_bp.R:111-116 -- the
             # symbol the reference never builds; here the column-block sharing solver of admm_amd/csrc/sharing_bp.hip
-            check(lib.admm_hip_parbp_traced(xp, yp, self.n, self.p, xmem, int(self.nthread), ctypes.byref(o),
-                                            beta.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                            niter.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), ctypes.byref(stats), *_trace_args(tr, ntr)))
+            with _par_devices(self):
+                check(lib.admm_hip_parbp_traced(xp, yp, self.n, self.p, xmem, int(self.nthread), ctypes.byref(o),
+                                                beta.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                                                niter.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), ctypes.byref(stats), *_trace_args(tr, ntr)))
         else:
             sbuf, nst = _state_buffers(state if trace else 0, self.p)
             check(lib.admm_hip_bp_state(xp, yp, self.n, self.p, xmem, ctypes.byref(o),

@@ -11,6 +11,7 @@
 #include <vector>
 #include <stdexcept>
 #include <chrono>
+#include <exception>
 
 #include "../../include/admm_hip.h"
 
@@ -69,6 +70,10 @@ struct TraceRange {
 // ADMM_HIP_POOL_MB megabytes in all, default 24576; 0 switches the cache off) and handed to the next allocation they fit (size <=
 // block <= 1.25 size).  A failed hipMalloc empties the cache and tries again; pool_cached_bytes() is what a caller adds to
 // hipMemGetInfo's free figure; admm_hip_trim_memory() returns everything to the driver.  Thread-safe (one mutex).
+// A rank thread of an in-process group (api.hip) does not free device or pinned memory during its call: hipFree / hipHostFree wait for
+// every stream of the device, a device may hold several ranks, and another rank's kernel may be waiting for an exchange this rank
+// has yet to enqueue.  Its releases are collected and carried out by the calling thread once every rank has returned.
+void pinned_free(void* p);                                          // hipHostFree, or deferred as above
 void* pool_alloc(size_t bytes, size_t* granted);
 void pool_free(void* p, size_t granted);
 size_t pool_cached_bytes();
@@ -103,6 +108,9 @@ struct DevBuf {
     T* get() const { return p; }
 };
 
+// Raises the abort word of the calling thread's in-process exchange group, if it has one (comm.hip; otherwise nothing).
+void comm_unwinding();
+
 // A non-blocking stream borrowed from a per-thread, per-device pool: creating a HIP stream costs 4-20 ms and
 // destroying one 3 ms on this runtime (measured), more than a whole small solve, so streams are created once per
 // thread and device and handed back idle (the borrower synchronises before it returns one).
@@ -122,6 +130,7 @@ struct Stream {
     }
     ~Stream() {
         if (!s) return;
+        if (std::uncaught_exceptions() > 0) comm_unwinding();      // a failing rank of an in-process group: release the others first
         if (hipStreamSynchronize(s) == hipSuccess) pool().push_back({dev, s});
         else (void)hipStreamDestroy(s);                  // a stream that saw an error is not reused
     }
@@ -178,6 +187,8 @@ inline void read_back(void* dst, const void* src, size_t bytes, hipStream_t st) 
 // silent, so large inputs do not go through it at all.  Returns with the bytes in device memory.
 // ADMM_HIP_H2D=pageable: plain hipMemcpy (A/B).
 void write_device(void* dst, const void* src, size_t bytes);
+// The same for `ncols` column pieces of `rows` doubles, `ld` doubles apart in the caller's memory, packed into dst (rows x ncols).
+void write_device_cols(double* dst, const double* src, size_t rows, size_t ld, size_t ncols);
 
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 inline size_t round_up_sz(size_t v, size_t m) { return (v + m - 1) / m * m; }

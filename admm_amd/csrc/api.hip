@@ -3,7 +3,10 @@
 #include <unordered_map>
 #include "solvers.h"
 #include "comm.h"
+#include <condition_variable>
+#include <functional>
 #include <mutex>
+#include <thread>
 
 namespace admm {
 const std::string& last_error_ref();
@@ -123,8 +126,19 @@ void* pool_alloc(size_t bytes, size_t* granted) {
     return p;
 }
 
+namespace {
+struct DeferredFree { void* p; size_t granted; bool pinned; };
+thread_local std::vector<DeferredFree>* t_defer = nullptr;          // set while this thread is a rank of an in-process call
+}  // namespace
+void pinned_free(void* p) {
+    if (!p) return;
+    if (t_defer) { t_defer->push_back({p, 0, true}); return; }
+    (void)hipHostFree(p);
+}
+
 void pool_free(void* p, size_t granted) {
     if (!p) return;
+    if (t_defer) { t_defer->push_back({p, granted, false}); return; }
     if (granted >= kPoolMinBytes && pool_cap_bytes() > 0) {
         int dev = 0;
         if (hipGetDevice(&dev) == hipSuccess) {
@@ -237,7 +251,7 @@ static LassoProblem make_problem(const double* lambda_in, int nlambda_in, int nl
 static PlanHandle* create_plan(const double* x, const double* y, int n, int p, int mem,
                                const double* lambda_in, int nlambda_in, int nlambda_auto, double lmin_ratio,
                                int standardize, int intercept, bool enet, double alpha, int nworkers,
-                               const admm_opts* opts, long long n_total = 0) {
+                               const admm_opts* opts, long long n_total = 0, long long ldx = 0) {
     check_common(x, y, n, p, mem, opts);
     ADMM_REQUIRE(nlambda_in >= 0, "nlambda_in must be >= 0");
     ADMM_REQUIRE(nlambda_in > 0 ? lambda_in != nullptr : nlambda_auto > 0, "need a lambda grid or nlambda_auto > 0");
@@ -260,7 +274,7 @@ static PlanHandle* create_plan(const double* x, const double* y, int n, int p, i
     const bool pipelined = mem == ADMM_MEM_HOST && !dist && nworkers <= 0 && n > p && p >= 4096 &&
                            !(eg && (std::string(eg) == "rocblas" || std::string(eg) == "oneshot"));
     if (pipelined) upload_standardize_gram_f32(d, x, y, n, p, standardize != 0, intercept != 0, h->st.s);
-    else upload_standardize<float>(d, x, y, n, p, mem, standardize != 0, intercept != 0, h->st.s, dist ? n_total : 0);
+    else upload_standardize<float>(d, x, y, n, p, mem, standardize != 0, intercept != 0, h->st.s, dist ? n_total : 0, ldx);
     if (nworkers > 0) h->plan = make_par_plan(std::move(d), pb, h->st.s);
     else if ((dist ? n_total : (long long)n) > p) h->plan = make_tall_plan(std::move(d), pb, h->st.s);      // Lasso.cpp:73
     else h->plan = make_wide_plan(std::move(d), pb, h->st.s);
@@ -577,6 +591,208 @@ static void lasso_multi(const double* x, const double* Y, int n, int p, int m, i
 }
 
 }  // namespace admm
+extern "C" int admm_hip_device_count(void);
+namespace admm {
+
+// ---- in-process multi-device mode of admm_hip_parlasso / admm_hip_parbp (PAR_DEVICES)
+namespace {
+// "0" / "" / unset: off (empty list).  "all": devices 0 .. device_count - 1.  Else a comma-separated list of device numbers
+// (repeats allowed: several ranks on one device -- the test / diagnostic form).
+std::vector<int> parse_par_devices(const char* v, int device_count) {
+    std::vector<int> out;
+    if (!v) return out;
+    const std::string s(v);
+    if (s.empty() || s == "0") return out;
+    if (s == "all") {
+        ADMM_REQUIRE(device_count >= 1, "PAR_DEVICES=all: no device");
+        for (int d = 0; d < device_count && d < 64; ++d) out.push_back(d);
+        return out;
+    }
+    size_t i = 0;
+    while (i <= s.size()) {
+        const size_t j = std::min(s.find(',', i), s.size());
+        const std::string item = s.substr(i, j - i);
+        ADMM_REQUIRE(!item.empty() && item.size() <= 4 && item.find_first_not_of("0123456789") == std::string::npos,
+                     "PAR_DEVICES must be 0, all, or a comma-separated list of device numbers (got '" + s + "')");
+        const int d = std::atoi(item.c_str());
+        ADMM_REQUIRE(d < device_count, "PAR_DEVICES lists device " + item + " but there are " + std::to_string(device_count) + " devices");
+        out.push_back(d);
+        ADMM_REQUIRE(out.size() <= 64, "PAR_DEVICES lists more than 64 ranks");
+        i = j + 1;
+    }
+    return out;
+}
+// rank r runs on devices[r] for r < the largest divisor of nblocks that is <= the number of listed devices (whole blocks per rank)
+std::vector<int> par_layout(int nblocks, const std::vector<int>& listed) {
+    int nr = 1;
+    for (int d = std::min<int>((int)listed.size(), nblocks); d >= 1; --d) if (nblocks % d == 0) { nr = d; break; }
+    return std::vector<int>(listed.begin(), listed.begin() + (listed.empty() ? 0 : nr));
+}
+thread_local std::vector<int> t_last_layout;                       // admm_hip_last_parallel_layout (empty: no call yet)
+void record_single_layout() {
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) { (void)hipGetLastError(); dev = 0; }
+    t_last_layout.assign(1, dev);
+}
+
+// One persistent host thread per rank index, re-used by every in-process call of the process: a rank's thread keeps its pooled
+// streams, pinned staging ring and BLAS handle from one call to the next (creating them costs more than a small solve), and nothing
+// is left behind per call.  Never destroyed (the runtime may be gone at process exit).
+struct RankWorker {
+    std::mutex mu;
+    std::condition_variable cv;
+    std::function<void()> task;
+    bool busy = false;
+    RankWorker() { std::thread([this] { loop(); }).detach(); }
+    void loop() {
+        for (;;) {
+            std::function<void()> t;
+            {
+                std::unique_lock<std::mutex> lk(mu);
+                cv.wait(lk, [&] { return (bool)task; });
+                t = std::move(task);
+                task = nullptr;
+            }
+            t();
+            { std::lock_guard<std::mutex> lk(mu); busy = false; }
+            cv.notify_all();
+        }
+    }
+    void start(std::function<void()> f) {
+        { std::lock_guard<std::mutex> lk(mu); task = std::move(f); busy = true; }
+        cv.notify_all();
+    }
+    void wait() {
+        std::unique_lock<std::mutex> lk(mu);
+        cv.wait(lk, [&] { return !busy; });
+    }
+};
+std::mutex& inproc_mu() { static std::mutex* m = new std::mutex(); return *m; }     // one in-process call at a time per process
+RankWorker& rank_worker(int r) {
+    static std::vector<RankWorker*>* w = new std::vector<RankWorker*>();
+    while ((int)w->size() <= r) w->push_back(new RankWorker());
+    return *(*w)[r];
+}
+
+struct RankOutcome { int code = ADMM_OK; std::string msg; bool abandoned = false; std::vector<DeferredFree> frees; };
+
+// Runs body(rank, nranks) on one thread per rank, rank r on devices[r], as the ranks of an in-process PEER group.  The caller's
+// thread options go with every rank; a device that holds more than one rank takes the two-launch PEER form (several ranks' launches
+// must never depend on being resident together).  src_device >= 0: the caller's input lives on that device -- every rank device
+// must reach it over peer access.  Throws the first failing rank's error (a rank's own failure before another's ADMM_ERR_COMM).
+void run_inproc(const std::vector<int>& devices, int src_device, const std::function<void(int, int)>& body) {
+    ADMM_REQUIRE(!comm_process_attached(), "PAR_DEVICES (in-process ranks) cannot be combined with an attached process-wide communicator "
+                                           "(admm_hip_comm_init*): use the *_dist entry points there, or finalize it first");
+    std::lock_guard<std::mutex> call_lock(inproc_mu());
+    const int nranks = (int)devices.size();
+    int cur = 0;
+    ADMM_HIP_CHECK(hipGetDevice(&cur));
+    if (src_device >= 0) {
+        for (int d : devices) {
+            if (d == src_device) continue;
+            int can = 0;
+            ADMM_HIP_CHECK(hipDeviceCanAccessPeer(&can, d, src_device));
+            ADMM_REQUIRE(can, "PAR_DEVICES with device input: device " + std::to_string(d) + " cannot read device " + std::to_string(src_device) +
+                              "'s memory (no peer access); pass the input in host memory instead");
+            ADMM_HIP_CHECK(hipSetDevice(d));
+            const hipError_t pe = hipDeviceEnablePeerAccess(src_device, 0);
+            (void)hipSetDevice(cur);
+            if (pe == hipErrorPeerAccessAlreadyEnabled) (void)hipGetLastError();
+            else ADMM_HIP_CHECK(pe);
+        }
+    }
+    std::vector<int> sorted(devices);
+    std::sort(sorted.begin(), sorted.end());
+    const bool shared = std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end();
+    const OptMap opts = option_thread();
+    InprocGroup* g = comm_group_create(devices);
+    std::vector<RankOutcome> out(nranks);
+    for (int r = 0; r < nranks; ++r) {
+        rank_worker(r).start([&, r]() {
+            option_thread() = opts;
+            if (shared) { option_set_thread("PEER_FUSED", "2"); option_set_thread("PAR_FUSE_PZ", "0"); }
+            RankOutcome& o = out[r];
+            t_defer = &o.frees;
+            try {
+                ADMM_HIP_CHECK(hipSetDevice(devices[r]));
+                comm_group_attach(g, r);
+                const char* inj = option("TEST_PAR_FAIL_RANK");          // test hook: this rank fails on the host before its first exchange
+                if (inj && std::atoi(inj) == r) throw Error(ADMM_ERR_INTERNAL, "test: injected failure of rank " + std::to_string(r));
+                body(r, nranks);
+            } catch (const Error& e) {
+                o.code = e.code; o.msg = e.what();
+            } catch (const std::bad_alloc&) {
+                o.code = ADMM_ERR_INTERNAL; o.msg = "host allocation failed";
+            } catch (const std::exception& e) {
+                o.code = ADMM_ERR_INTERNAL; o.msg = e.what();
+            }
+            if (o.code != ADMM_OK) {
+                o.abandoned = o.code == ADMM_ERR_COMM && o.msg.rfind("exchange abandoned", 0) == 0;
+                o.msg = "rank " + std::to_string(r) + " (device " + std::to_string(devices[r]) + "): " + o.msg;
+                comm_group_abort(g);
+            }
+            comm_group_detach();
+            t_defer = nullptr;
+            options_reset_thread();
+        });
+    }
+    for (int r = 0; r < nranks; ++r) rank_worker(r).wait();
+    for (int r = 0; r < nranks; ++r) {                  // every rank has returned: its releases are safe now
+        (void)hipSetDevice(devices[r]);
+        for (const DeferredFree& f : out[r].frees) { if (f.pinned) (void)hipHostFree(f.p); else pool_free(f.p, f.granted); }
+    }
+    comm_group_destroy(g);
+    (void)hipSetDevice(cur);
+    t_last_layout = devices;
+    int first = -1;
+    for (int r = 0; r < nranks && first < 0; ++r) if (out[r].code != ADMM_OK && !out[r].abandoned) first = r;
+    for (int r = 0; r < nranks && first < 0; ++r) if (out[r].code != ADMM_OK) first = r;
+    if (first >= 0) throw Error(out[first].code, out[first].msg);
+}
+
+// the ranks of a PAR_DEVICES call with `nblocks` blocks; empty: the single-device path
+std::vector<int> par_devices_for(int nblocks) {
+    const std::vector<int> listed = parse_par_devices(option("PAR_DEVICES"), admm_hip_device_count());
+    std::vector<int> lay = par_layout(nblocks, listed);
+    if (lay.size() <= 1) lay.clear();
+    return lay;
+}
+int input_device(const void* x, int mem) {
+    if (mem != ADMM_MEM_DEVICE) return -1;
+    hipPointerAttribute_t at;
+    ADMM_HIP_CHECK(hipPointerGetAttributes(&at, x));
+    return at.device;
+}
+}  // namespace
+
+// admm_hip_parlasso over in-process ranks: rank r holds the rows of its K / N whole blocks (admm_amd/dist.py row_partition)
+static void parlasso_inproc(const std::vector<int>& devs, const double* x, const double* y, int n, int p, int mem,
+                            const double* lambda_in, int nlambda_in, int nlambda_auto, double lmin_ratio,
+                            int standardize, int intercept, int nthread, const admm_opts* opts,
+                            double* lambda_out, float* beta_out, int* niter_out, admm_stats* stats) {
+    ADMM_REQUIRE(lambda_out && beta_out && niter_out, "output pointers must not be NULL");
+    check_common(x, y, n, p, mem, opts);
+    ADMM_REQUIRE(nthread <= n, "more row blocks than rows");
+    const int nl = nlambda_in > 0 ? nlambda_in : nlambda_auto;
+    ADMM_REQUIRE(nl > 0, "need a lambda grid or nlambda_auto > 0");
+    run_inproc(devs, input_device(x, mem), [&](int rank, int nranks) {
+        const long long chunk = n / nthread, per = nthread / nranks;
+        const long long lo = rank * per * chunk, hi = rank == nranks - 1 ? n : (rank + 1) * per * chunk;
+        std::vector<double> lam_own; std::vector<float> beta_own; std::vector<int> nit_own;
+        double* lam = lambda_out; float* beta = beta_out; int* nit = niter_out;
+        admm_stats st_own;
+        if (rank != 0) {                                  // every rank computes the full result; the caller gets rank 0's
+            lam_own.resize(nl); beta_own.resize((size_t)(p + 1) * nl); nit_own.resize(nl);
+            lam = lam_own.data(); beta = beta_own.data(); nit = nit_own.data();
+        }
+        std::unique_ptr<PlanHandle> h(create_plan(x + lo, y + lo, (int)(hi - lo), p, mem, lambda_in, nlambda_in, nlambda_auto, lmin_ratio,
+                                                  standardize, intercept, false, 1.0, nthread, opts, n, n));
+        run_plan(h.get(), lam, beta, nit, rank == 0 ? stats : &st_own, h->t_create);
+    });
+}
+
+
+}  // namespace admm
 
 using namespace admm;
 
@@ -632,6 +848,13 @@ int admm_hip_parlasso(const double* x, const double* y, int n, int p, int mem,
         set_last_error("nthread must be >= 1");
         return ADMM_ERR_INVALID_ARG;
     }
+    std::vector<int> devs;
+    const int rc = guarded([&] { devs = par_devices_for(nthread); });
+    if (rc != ADMM_OK) return rc;
+    if (!devs.empty())
+        return guarded([&] { parlasso_inproc(devs, x, y, n, p, mem, lambda_in, nlambda_in, nlambda_auto, lmin_ratio, standardize, intercept,
+                                             nthread, opts, lambda_out, beta_out, niter_out, stats); });
+    record_single_layout();
     return lasso_family(x, y, n, p, mem, lambda_in, nlambda_in, nlambda_auto, lmin_ratio, standardize, intercept,
                         false, 1.0, nthread, opts, lambda_out, beta_out, niter_out, stats);
 }
@@ -793,14 +1016,43 @@ static void parbp_common(const double* x_cols, const double* y, int n, int p_loc
     if (stats) *stats = res.stats;
 }
 
+// admm_hip_parbp(_traced) over in-process ranks: rank r holds its whole blocks of columns (admm_amd/dist.py parbp_partition)
+static void parbp_inproc(const std::vector<int>& devs, const double* x, const double* y, int n, int p, int mem, int nthread, const admm_opts* opts,
+                         double* beta_out, int* niter_out, admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out) {
+    ADMM_REQUIRE(x != nullptr && beta_out && niter_out, "x and the output pointers must not be NULL");
+    ADMM_REQUIRE(n > 0 && p > 0, "n and p must be positive");
+    ADMM_REQUIRE(nthread >= 1 && nthread <= p, "nthread must be within [1, ncol(x)]");
+    run_inproc(devs, input_device(x, mem), [&](int rank, int nranks) {
+        const long long chunk = p / nthread, per = nthread / nranks;
+        const long long lo = rank * per * chunk, hi = rank == nranks - 1 ? p : (rank + 1) * per * chunk;
+        int nit = 0;
+        admm_stats st_own;
+        std::vector<double> tr_own;
+        long long ntr_own = 0;
+        const bool traced = rank == 0 && trace_cap > 0;
+        parbp_common(x + (size_t)lo * n, y, n, (int)(hi - lo), p, lo, mem, nthread, opts, beta_out + lo, &nit, rank == 0 ? stats : &st_own,
+                     traced ? trace_out : nullptr, traced ? trace_cap : 0, traced ? ntrace_out : &ntr_own);
+        if (rank == 0) niter_out[0] = nit;
+    });
+}
+
 int admm_hip_parbp(const double* x, const double* y, int n, int p, int mem, int nthread, const admm_opts* opts,
                    double* beta_out, int* niter_out, admm_stats* stats) {
-    return guarded([&] { parbp_common(x, y, n, p, p, 0, mem, nthread, opts, beta_out, niter_out, stats, nullptr, 0, nullptr); });
+    return admm_hip_parbp_traced(x, y, n, p, mem, nthread, opts, beta_out, niter_out, stats, nullptr, 0, nullptr);
 }
 
 int admm_hip_parbp_traced(const double* x, const double* y, int n, int p, int mem, int nthread, const admm_opts* opts,
                           double* beta_out, int* niter_out, admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out) {
-    return guarded([&] { parbp_common(x, y, n, p, p, 0, mem, nthread, opts, beta_out, niter_out, stats, trace_out, trace_cap, ntrace_out); });
+    return guarded([&] {
+        const std::vector<int> devs = nthread >= 1 ? par_devices_for(nthread) : std::vector<int>();
+        if (!devs.empty()) {
+            ADMM_REQUIRE(trace_cap == 0 || (trace_out != nullptr && ntrace_out != nullptr && trace_cap > 0), "bad trace arguments");
+            parbp_inproc(devs, x, y, n, p, mem, nthread, opts, beta_out, niter_out, stats, trace_out, trace_cap, ntrace_out);
+            return;
+        }
+        record_single_layout();
+        parbp_common(x, y, n, p, p, 0, mem, nthread, opts, beta_out, niter_out, stats, trace_out, trace_cap, ntrace_out);
+    });
 }
 
 int admm_hip_parbp_dist(const double* x_cols, const double* y, int n, int p_local, long long p_total, long long col_offset, int mem, int nthread,
@@ -956,6 +1208,12 @@ int admm_hip_options_set(const admm_hip_options* o) {
         if (v.profile_stride > 0) num("PROFILE_STRIDE", v.profile_stride);
         if (v.pool_mb) num("POOL_MB", v.pool_mb < 0 ? 0 : v.pool_mb);
         if (v.lad_two_pass) set("LAD_ONEPASS", "0");
+        if (v.par_devices) {
+            ADMM_REQUIRE(v.par_devices >= -1 && v.par_devices <= 64, "options: par_devices");
+            std::string l;
+            for (int d = 0; d < v.par_devices; ++d) l += (d ? "," : "") + std::to_string(d);
+            set("PAR_DEVICES", v.par_devices == -1 ? "all" : l.c_str());
+        }
         if (v.screen) {
             ADMM_REQUIRE(v.screen >= 1 && v.screen <= 3, "options: screen");
             set("WIDE_SCREEN", v.screen == 1 ? "16" : (v.screen == 3 ? "8" : "0"));
@@ -1088,6 +1346,25 @@ int admm_hip_lasso_plan_system_read(admm_hip_plan* plan, float* out, long long l
         PlanHandle* h = reinterpret_cast<PlanHandle*>(plan);
         ADMM_REQUIRE(h != nullptr && h->plan, "plan is NULL");
         h->plan->read_system(out, ld);
+    });
+}
+
+int admm_hip_last_parallel_layout(int* nranks, int* devices, int cap) {
+    return guarded([&] {
+        ADMM_REQUIRE(nranks != nullptr && cap >= 0 && (cap == 0 || devices != nullptr), "bad layout arguments");
+        *nranks = (int)t_last_layout.size();
+        for (int r = 0; r < std::min(cap, *nranks); ++r) devices[r] = t_last_layout[r];
+    });
+}
+
+int admm_hip_parallel_assign(int nblocks, const char* par_devices, int device_count, int* nranks, int* devices, int cap) {
+    return guarded([&] {
+        ADMM_REQUIRE(nblocks >= 1 && device_count >= 0, "nblocks must be >= 1 and device_count >= 0");
+        ADMM_REQUIRE(nranks != nullptr && cap >= 0 && (cap == 0 || devices != nullptr), "bad layout arguments");
+        std::vector<int> lay = par_layout(nblocks, parse_par_devices(par_devices, device_count));
+        if (lay.size() <= 1) lay.clear();
+        *nranks = lay.empty() ? 1 : (int)lay.size();
+        for (int r = 0; r < std::min(cap, (int)lay.size()); ++r) devices[r] = lay[r];
     });
 }
 

@@ -12,6 +12,10 @@
 //   SHM    through POSIX shared memory on the host (D2H, a host function in stream order, H2D).  Slow; exists so that
 //          the multi-rank code paths run as separate processes on ONE GPU / without RCCL (tests), bit-identical to PEER.
 // Every call is a no-op when no communicator is attached.
+//
+// In-process form (admm_hip_parlasso / admm_hip_parbp with PAR_DEVICES): the ranks are threads of ONE process, each on its own
+// device (or several on one device: the test form).  The state of a rank lives in a context of its own; a thread-local "current
+// context" selects it and falls back to the process-wide one, so every function below works unchanged in either form.
 #pragma once
 #include "admm_internal.h"
 
@@ -58,5 +62,22 @@ PeerExchange comm_peer_begin(size_t payload_bytes);
 // PEER backend only: the AUX region (peer_device.h) for a kernel that exchanges many times inside ONE launch.
 struct PeerAux;
 PeerAux comm_peer_aux();
+
+// True while a process-wide communicator is attached (admm_hip_comm_init*), whatever the calling thread's current context.
+bool comm_process_attached();
+// In-process group: PEER over device pointers swapped in host memory (peer access enabled between the listed devices, no hipIpc).
+//   comm_group_create   calling thread: enables peer access, allocates the group's abort word; throws if two listed devices
+//                       cannot reach each other
+//   comm_group_attach   rank thread, on its device: its exchange buffer, the pointer swap (a host barrier that ends on the
+//                       abort word), then installs its context as the thread's current one
+//   comm_group_abort    a rank failed: every wait of every rank (host and device) ends early, the calls return ADMM_ERR_COMM
+//   comm_group_detach   rank thread: back to the process-wide context
+//   comm_group_destroy  calling thread, after every rank thread returned: frees every rank's buffers (success and error alike)
+struct InprocGroup;
+InprocGroup* comm_group_create(const std::vector<int>& devices);
+void comm_group_attach(InprocGroup* g, int rank);
+void comm_group_abort(InprocGroup* g);
+void comm_group_detach();
+void comm_group_destroy(InprocGroup* g);
 
 }  // namespace admm

@@ -3,7 +3,8 @@
 // Replaces the shared-memory "collectives" of the reference's OpenMP master/worker loop:
 //   sum_i (x_i + y_i / rho)           /root/reference/src/PADMMLasso.h:99-108 (add_xu_to :65-68)
 //   sum_i ||x_i||^2, ||y_i||^2, ||r_i||^2   /root/reference/src/PADMMBase.h:117-138,200-214
-// The reference reads the workers' vectors directly (threads of one process); here each rank is a process on its own GPU.
+// The reference reads the workers' vectors directly (threads of one process); here each rank is a process on its own GPU, or a
+// thread of one process on its own GPU (the in-process group at the end of this file).
 //
 // Bootstrap is caller-driven (the library never opens sockets): RCCL needs rank 0's 128-byte unique id on every rank,
 // PEER needs every rank's 64-byte hipIpc handle on every rank, SHM needs a name all ranks agree on.  The Python harness
@@ -11,7 +12,9 @@
 #include "comm.h"
 #include "peer_device.h"
 #include <rccl/rccl.h>
+#include <algorithm>
 #include <atomic>
+#include <memory>
 #include <cerrno>
 #include <mutex>
 #include <fcntl.h>
@@ -39,17 +42,39 @@ double env_seconds(const char* name, double dflt) {
 }
 double wait_seconds_lockstep() { return env_seconds("COMM_TIMEOUT_S", 20.0); }
 double wait_seconds_patient() { return env_seconds("COMM_PATIENT_TIMEOUT_S", 3600.0); }
-std::atomic<int> g_lockstep{0};
-double wait_seconds_now() { return g_lockstep.load(std::memory_order_relaxed) > 0 ? wait_seconds_lockstep() : wait_seconds_patient(); }
+
+struct PeerState {
+    unsigned char* local = nullptr;                      // this rank's buffer
+    unsigned char* remote[kMaxRanks] = {};               // every rank's buffer as mapped here (remote[rank] == local)
+    bool opened[kMaxRanks] = {};                         // remote[r] came from hipIpcOpenMemHandle (closed by peer_close)
+    size_t bytes = 0, flags_off = 0;
+    size_t aux_data_off = 0, aux_flags_off = 0;          // the AUX region (peer_device.h): exchanges numbered on the device
+    unsigned long long* aux_seq = nullptr;               // device word
+    unsigned int* count = nullptr;                       // [nranks] workgroup arrival counters of the push (device)
+    unsigned char** d_remote = nullptr;                  // device copy of remote[]
+};
+
+// The state of ONE rank.  A process-wide communicator (one process per GPU) is g_ctx; an in-process group (admm_hip_parlasso /
+// admm_hip_parbp with PAR_DEVICES) gives each of its rank threads a context of its own, installed as that thread's current one.
+// A thread without one uses g_ctx -- so a caller who attaches on one thread and calls from another sees what it always did.
+struct CommCtx {
+    CommInfo info;
+    PeerState peer;
+    size_t slot = kDefaultSlotBytes;
+    uint64_t seq = 0;                                 // exchanges enqueued so far (all ranks enqueue the same sequence)
+    int* err = nullptr;                               // pinned host word: set by a timed-out wait of the SHM host function
+    int* derr = nullptr;                              // device word: set by a timed-out wait of a PEER kernel (a pinned host word
+                                                      // would cost every workgroup a PCIe round trip: 30 us per exchange, measured)
+    std::atomic<int> lockstep{0};
+    int* abort = nullptr;                             // in-process group only: its shared abort word (fine-grained host memory)
+};
+CommCtx g_ctx;
+thread_local CommCtx* t_ctx = nullptr;
+CommCtx& C() { return t_ctx ? *t_ctx : g_ctx; }
+double wait_seconds_now() { return C().lockstep.load(std::memory_order_relaxed) > 0 ? wait_seconds_lockstep() : wait_seconds_patient(); }
 
 std::mutex g_mu;
-CommInfo g_info;
 ncclComm_t g_comm = nullptr;
-size_t g_slot = kDefaultSlotBytes;
-uint64_t g_seq = 0;                                   // exchanges enqueued so far (all ranks enqueue the same sequence)
-int* g_err = nullptr;                                 // pinned host word: set by a timed-out wait of the SHM host function
-int* g_derr = nullptr;                                // device word: set by a timed-out wait of a PEER kernel (a pinned host word
-                                                      // would cost every workgroup a PCIe round trip: 30 us per exchange, measured)
 
 #define ADMM_NCCL_CHECK(expr)                                                                     \
     do {                                                                                          \
@@ -67,9 +92,9 @@ size_t slot_bytes_from_env() {
 }
 
 void alloc_err_word() {
-    if (!g_err) {
-        ADMM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&g_err), sizeof(int), hipHostMallocMapped));
-        *g_err = 0;
+    if (!C().err) {
+        ADMM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&C().err), sizeof(int), hipHostMallocMapped));
+        *C().err = 0;
     }
 }
 
@@ -100,7 +125,7 @@ struct ShmState {
 } g_shm;
 
 unsigned char* shm_slot(uint64_t seq, int rank) {
-    return g_shm.data + ((size_t)(seq & 1) * g_info.nranks + (size_t)rank) * g_slot;
+    return g_shm.data + ((size_t)(seq & 1) * g_ctx.info.nranks + (size_t)rank) * g_ctx.slot;
 }
 
 // Runs on a runtime thread when the stream reaches it: the payload is in stage_in, the result goes to stage_out.
@@ -109,18 +134,18 @@ void shm_host_fn(void* user) {
     const size_t off_d = round_up_sz(op.nf * sizeof(float), 16);
     const size_t bytes = off_d + op.nd * sizeof(double);
     ShmHeader* h = g_shm.hdr;
-    if (h->failed.load(std::memory_order_acquire) || (g_err && *g_err)) { std::memset(g_shm.stage_out, 0, bytes); return; }
-    std::memcpy(shm_slot(op.seq, g_info.rank), g_shm.stage_in, bytes);
-    h->posted[g_info.rank].store(op.seq, std::memory_order_release);
+    if (h->failed.load(std::memory_order_acquire) || (g_ctx.err && *g_ctx.err)) { std::memset(g_shm.stage_out, 0, bytes); return; }
+    std::memcpy(shm_slot(op.seq, g_ctx.info.rank), g_shm.stage_in, bytes);
+    h->posted[g_ctx.info.rank].store(op.seq, std::memory_order_release);
     const double t0 = now_s();
-    for (int r = 0; r < g_info.nranks; ++r) {
+    for (int r = 0; r < g_ctx.info.nranks; ++r) {
         int spins = 0;
         while (h->posted[r].load(std::memory_order_acquire) < op.seq) {
             if ((++spins & 1023) == 0) {
                 sched_yield();
                 if (h->failed.load(std::memory_order_acquire) || now_s() - t0 > op.wait_s) {
                     h->failed.store(1, std::memory_order_release);
-                    if (g_err) *g_err = 1;
+                    if (g_ctx.err) *g_ctx.err = 1;
                     std::memset(g_shm.stage_out, 0, bytes);
                     return;
                 }
@@ -129,7 +154,7 @@ void shm_host_fn(void* user) {
     }
     float* of = reinterpret_cast<float*>(g_shm.stage_out);
     double* od = reinterpret_cast<double*>(g_shm.stage_out + off_d);
-    for (int r = 0; r < g_info.nranks; ++r) {             // fixed rank order: every rank computes the identical sum
+    for (int r = 0; r < g_ctx.info.nranks; ++r) {             // fixed rank order: every rank computes the identical sum
         const float* sf = reinterpret_cast<const float*>(shm_slot(op.seq, r));
         const double* sd = reinterpret_cast<const double*>(shm_slot(op.seq, r) + off_d);
         if (r == 0) {
@@ -144,9 +169,9 @@ void shm_host_fn(void* user) {
 
 void shm_exchange(float* fbuf, size_t nf, double* dbuf, size_t nd, hipStream_t st) {
     const size_t off_d = round_up_sz(nf * sizeof(float), 16);
-    ADMM_REQUIRE(off_d + round_up_sz(nd * sizeof(double), 16) <= g_slot, "exchange payload exceeds the slot size");
+    ADMM_REQUIRE(off_d + round_up_sz(nd * sizeof(double), 16) <= C().slot, "exchange payload exceeds the slot size");
     ShmOp* op = &g_shm.ring[g_shm.ring_pos++ % g_shm.ring.size()];
-    op->seq = ++g_seq; op->nf = nf; op->nd = nd; op->wait_s = wait_seconds_now();
+    op->seq = ++C().seq; op->nf = nf; op->nd = nd; op->wait_s = wait_seconds_now();
     if (nf) ADMM_HIP_CHECK(hipMemcpyAsync(g_shm.stage_in, fbuf, nf * sizeof(float), hipMemcpyDeviceToHost, st));
     if (nd) ADMM_HIP_CHECK(hipMemcpyAsync(g_shm.stage_in + off_d, dbuf, nd * sizeof(double), hipMemcpyDeviceToHost, st));
     ADMM_HIP_CHECK(hipLaunchHostFunc(st, shm_host_fn, op));
@@ -172,16 +197,6 @@ void shm_close() {
 //   sum    every workgroup first waits (lane r spins, acquire, system scope, bounded) until its own flags[s & 1][r] reads s,
 //          then out[i] = sum over r = 0 .. nranks-1 of data[s & 1][r][i], in rank order, written back in place.
 // The buffer is fine-grained device memory (peer_alloc_local), so a peer's stores are never shadowed by a stale L2 line here.
-struct PeerState {
-    unsigned char* local = nullptr;                      // this rank's buffer
-    unsigned char* remote[kMaxRanks] = {};               // every rank's buffer as mapped here (remote[rank] == local)
-    bool opened[kMaxRanks] = {};
-    size_t bytes = 0, flags_off = 0;
-    size_t aux_data_off = 0, aux_flags_off = 0;          // the AUX region (peer_device.h): exchanges numbered on the device
-    unsigned long long* aux_seq = nullptr;               // device word
-    unsigned int* count = nullptr;                       // [nranks] workgroup arrival counters of the push (device)
-    unsigned char** d_remote = nullptr;                  // device copy of remote[]
-} g_peer;
 
 constexpr int kPushGroups = 4;                           // workgroups per destination rank
 constexpr int kSumGroups = 128;                          // most workgroups of a consuming launch (they all wait for the flags)
@@ -290,9 +305,9 @@ __global__ void __launch_bounds__(256) peer_sum_kernel(PeerArgs a) {
 }
 
 void peer_fill(PeerExchange& a) {
-    a.remote = g_peer.d_remote; a.local = g_peer.local; a.slot = g_slot; a.flags_off = g_peer.flags_off;
-    a.nranks = g_info.nranks; a.rank = g_info.rank; a.seq = ++g_seq;
-    a.count = g_peer.count; a.err = g_derr;
+    a.remote = C().peer.d_remote; a.local = C().peer.local; a.slot = C().slot; a.flags_off = C().peer.flags_off;
+    a.nranks = C().info.nranks; a.rank = C().info.rank; a.seq = ++C().seq;
+    a.count = C().peer.count; a.err = C().derr; a.abort = C().abort ? C().abort : C().derr;
     a.timeout_ticks = (long long)(wait_seconds_now() * 100e6);          // wall_clock64: constant 100 MHz
 }
 
@@ -307,31 +322,31 @@ void peer_exchange(float* fbuf, size_t nf, double* dbuf, size_t nd, hipStream_t 
     a.rs_stride = rs_stride;
     a.groups = bcast_root >= 0 ? 32 : kPushGroups;        // bulk payload: more workgroups per destination
     a.off_d = round_up_sz(nf * sizeof(float), 16);
-    ADMM_REQUIRE(a.off_d + round_up_sz(nd * sizeof(double), 16) <= (bcast_root >= 0 ? g_slot * (size_t)g_info.nranks : g_slot), "exchange payload exceeds the slot size");
+    ADMM_REQUIRE(a.off_d + round_up_sz(nd * sizeof(double), 16) <= (bcast_root >= 0 ? C().slot * (size_t)C().info.nranks : C().slot), "exchange payload exceeds the slot size");
     ADMM_REQUIRE((reinterpret_cast<uintptr_t>(fbuf) & 15) == 0 && (reinterpret_cast<uintptr_t>(dbuf) & 15) == 0, "exchange buffers must be 16-byte aligned");
     a.fsrc = rs_send ? rs_send : fbuf; a.nf = nf; a.dsrc = dbuf; a.nd = nd; a.fdst = fbuf; a.ddst = dbuf;
     ADMM_REQUIRE((reinterpret_cast<uintptr_t>(a.fsrc) & 15) == 0 && (rs_stride % 4) == 0, "reduce-scatter chunks must be 16-byte aligned");
     const size_t units = a.off_d / 16 + (nd + 1) / 2;
-    hipLaunchKernelGGL(peer_push_kernel, dim3(g_info.nranks * a.groups), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(peer_push_kernel, dim3(C().info.nranks * a.groups), dim3(256), 0, st, a);
     hipLaunchKernelGGL(peer_sum_kernel, dim3((unsigned)std::min<size_t>((units + 255) / 256, (size_t)kSumGroups)), dim3(256), 0, st, a);
 }
 
 void peer_close() {
     for (int r = 0; r < kMaxRanks; ++r)
-        if (g_peer.opened[r] && g_peer.remote[r]) (void)hipIpcCloseMemHandle(g_peer.remote[r]);
-    if (g_peer.local) (void)hipFree(g_peer.local);
-    if (g_peer.count) (void)hipFree(g_peer.count);
-    if (g_peer.aux_seq) (void)hipFree(g_peer.aux_seq);
-    if (g_peer.d_remote) (void)hipFree(g_peer.d_remote);
-    g_peer = PeerState();
+        if (C().peer.opened[r] && C().peer.remote[r]) (void)hipIpcCloseMemHandle(C().peer.remote[r]);
+    if (C().peer.local) (void)hipFree(C().peer.local);
+    if (C().peer.count) (void)hipFree(C().peer.count);
+    if (C().peer.aux_seq) (void)hipFree(C().peer.aux_seq);
+    if (C().peer.d_remote) (void)hipFree(C().peer.d_remote);
+    C().peer = PeerState();
 }
 
 void peer_alloc_local(int nranks) {
-    g_slot = slot_bytes_from_env();
-    g_peer.flags_off = (size_t)2 * nranks * g_slot;
-    g_peer.aux_data_off = g_peer.flags_off + (size_t)2 * nranks * 64;
-    g_peer.aux_flags_off = g_peer.aux_data_off + (size_t)2 * nranks * kAuxSlotBytes;
-    g_peer.bytes = g_peer.aux_flags_off + (size_t)2 * nranks * (kAuxGroups + 1) * 64;
+    C().slot = slot_bytes_from_env();
+    C().peer.flags_off = (size_t)2 * nranks * C().slot;
+    C().peer.aux_data_off = C().peer.flags_off + (size_t)2 * nranks * 64;
+    C().peer.aux_flags_off = C().peer.aux_data_off + (size_t)2 * nranks * kAuxSlotBytes;
+    C().peer.bytes = C().peer.aux_flags_off + (size_t)2 * nranks * (kAuxGroups + 1) * 64;
     void* ptr = nullptr;
     // Fine-grained device memory: the HIP memory model makes system-scope release / acquire pairs (the flag protocol
     // below) order and publish plain accesses to it across agents, so stores arriving from a peer are never shadowed by
@@ -339,19 +354,19 @@ void peer_alloc_local(int nranks) {
     // transaction of its own: measured 3-10x slower for the 80 KB payload; kept as the conservative fallback).
     const char* pm = option("PEER_MEM");
     const bool uncached = pm && std::string(pm) == "uncached";
-    if (hipExtMallocWithFlags(&ptr, g_peer.bytes, uncached ? hipDeviceMallocUncached : hipDeviceMallocFinegrained) != hipSuccess) {
+    if (hipExtMallocWithFlags(&ptr, C().peer.bytes, uncached ? hipDeviceMallocUncached : hipDeviceMallocFinegrained) != hipSuccess) {
         (void)hipGetLastError();
         pool_trim();                                          // the cache of released device blocks must never starve this allocation
-        ADMM_HIP_CHECK(hipExtMallocWithFlags(&ptr, g_peer.bytes, uncached ? hipDeviceMallocFinegrained : hipDeviceMallocUncached));
+        ADMM_HIP_CHECK(hipExtMallocWithFlags(&ptr, C().peer.bytes, uncached ? hipDeviceMallocFinegrained : hipDeviceMallocUncached));
     }
-    g_peer.local = static_cast<unsigned char*>(ptr);
-    ADMM_HIP_CHECK(hipMemset(g_peer.local, 0, g_peer.bytes));
+    C().peer.local = static_cast<unsigned char*>(ptr);
+    ADMM_HIP_CHECK(hipMemset(C().peer.local, 0, C().peer.bytes));
     ADMM_HIP_CHECK(hipDeviceSynchronize());
 }
 
 // ================================================================================================ dispatch
 void exchange(float* fbuf, size_t nf, double* dbuf, size_t nd, hipStream_t st) {
-    switch (g_info.backend) {
+    switch (C().info.backend) {
         case COMM_RCCL:
             if (nf && nd) ADMM_NCCL_CHECK(ncclGroupStart());
             if (nf) ADMM_NCCL_CHECK(ncclAllReduce(fbuf, fbuf, nf, ncclFloat, ncclSum, g_comm, st));
@@ -365,7 +380,7 @@ void exchange(float* fbuf, size_t nf, double* dbuf, size_t nd, hipStream_t st) {
 }
 
 void require_free() {
-    if (g_info.active) throw Error(ADMM_ERR_COMM, "communicator already initialised");
+    if (C().info.active) throw Error(ADMM_ERR_COMM, "communicator already initialised");
 }
 void check_ranks(int nranks, int rank) {
     ADMM_REQUIRE(nranks >= 1 && nranks <= kMaxRanks && rank >= 0 && rank < nranks, "bad rank / nranks");
@@ -375,36 +390,41 @@ void check_ranks(int nranks, int rank) {
 
 // The next exchange of the PEER backend for a solver whose own kernels produce / consume it (peer_device.h).
 PeerExchange comm_peer_begin(size_t payload_bytes) {
-    if (g_info.backend != COMM_PEER) throw Error(ADMM_ERR_COMM, "the PEER exchange is not attached");
-    ADMM_REQUIRE(payload_bytes <= g_slot, "exchange payload exceeds the slot size");
+    if (C().info.backend != COMM_PEER) throw Error(ADMM_ERR_COMM, "the PEER exchange is not attached");
+    ADMM_REQUIRE(payload_bytes <= C().slot, "exchange payload exceeds the slot size");
     PeerExchange e;
     peer_fill(e);
     return e;
 }
 
 PeerAux comm_peer_aux() {
-    if (g_info.backend != COMM_PEER) throw Error(ADMM_ERR_COMM, "the PEER exchange is not attached");
+    if (C().info.backend != COMM_PEER) throw Error(ADMM_ERR_COMM, "the PEER exchange is not attached");
     PeerAux a;
-    a.remote = g_peer.d_remote; a.local = g_peer.local; a.data_off = g_peer.aux_data_off; a.flags_off = g_peer.aux_flags_off;
-    a.nranks = g_info.nranks; a.rank = g_info.rank; a.seq = g_peer.aux_seq; a.err = g_derr;
+    a.remote = C().peer.d_remote; a.local = C().peer.local; a.data_off = C().peer.aux_data_off; a.flags_off = C().peer.aux_flags_off;
+    a.nranks = C().info.nranks; a.rank = C().info.rank; a.seq = C().peer.aux_seq; a.err = C().derr; a.abort = C().abort ? C().abort : C().derr;
     a.timeout_ticks = (long long)(wait_seconds_now() * 100e6);
     return a;
 }
 
 CommInfo comm_info() {
     std::lock_guard<std::mutex> lk(g_mu);
-    return g_info;
+    return C().info;
+}
+bool comm_process_attached() {
+    std::lock_guard<std::mutex> lk(g_mu);
+    return g_ctx.info.active;
 }
 
-CommLockstep::CommLockstep() { g_lockstep.fetch_add(1, std::memory_order_relaxed); }
-CommLockstep::~CommLockstep() { g_lockstep.fetch_sub(1, std::memory_order_relaxed); }
+CommLockstep::CommLockstep() { C().lockstep.fetch_add(1, std::memory_order_relaxed); }
+CommLockstep::~CommLockstep() { C().lockstep.fetch_sub(1, std::memory_order_relaxed); }
 
 void comm_check() {
-    if (g_info.backend == COMM_PEER && g_derr) {          // called at the solvers' polls (after an event sync) only
+    if (C().info.backend == COMM_PEER && C().derr) {          // called at the solvers' polls (after an event sync) only
         int h = 0;
-        if (hipMemcpy(&h, g_derr, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess && h && g_err) *g_err = 1;
+        if (hipMemcpy(&h, C().derr, sizeof(int), hipMemcpyDeviceToHost) == hipSuccess && h && C().err) *C().err = 1;
     }
-    if (g_err && *g_err) throw Error(ADMM_ERR_COMM, "exchange failed: a rank did not arrive within the time limit (or a peer reported failure)");
+    if (C().err && *C().err) throw Error(ADMM_ERR_COMM, "exchange failed: a rank did not arrive within the time limit (or a peer reported failure)");
+    if (C().abort && *reinterpret_cast<volatile int*>(C().abort)) throw Error(ADMM_ERR_COMM, "exchange abandoned: another rank of this in-process call failed");
 }
 
 namespace {
@@ -413,8 +433,8 @@ namespace {
     {
         std::lock_guard<std::mutex> lk(g_mu);
         if (g_comm) { (void)ncclCommAbort(g_comm); g_comm = nullptr; }
-        g_info = CommInfo();
-        g_seq = 0;
+        C().info = CommInfo();
+        C().seq = 0;
     }
     throw Error(ADMM_ERR_COMM, "RCCL exchange failed: " + why + " (communicator aborted; call admm_hip_comm_finalize and re-attach)");
 }
@@ -440,17 +460,35 @@ void rccl_watched_wait(Q&& query) {
 }
 }  // namespace
 
+namespace {
+// In-process group: the device waits end on the abort word by themselves; the host stops waiting as soon as it is up.
+template <typename Q>
+void inproc_watched_wait(Q&& query) {
+    const volatile int* abort = C().abort;
+    const double t0 = now_s();
+    for (;;) {
+        const hipError_t q = query();
+        if (q == hipSuccess) return;
+        if (q != hipErrorNotReady) ADMM_HIP_CHECK(q);
+        if (*abort) throw Error(ADMM_ERR_COMM, "exchange abandoned: another rank of this in-process call failed");
+        if (now_s() - t0 > 100e-6) sched_yield();
+    }
+}
+}  // namespace
+
 void comm_stream_sync(hipStream_t st) {
-    if (g_info.backend != COMM_RCCL || !g_comm) { ADMM_HIP_CHECK(hipStreamSynchronize(st)); return; }
+    if (C().abort) { inproc_watched_wait([&] { return hipStreamQuery(st); }); return; }
+    if (C().info.backend != COMM_RCCL || !g_comm) { ADMM_HIP_CHECK(hipStreamSynchronize(st)); return; }
     rccl_watched_wait([&] { return hipStreamQuery(st); });
 }
 void comm_event_sync(hipEvent_t ev) {
-    if (g_info.backend != COMM_RCCL || !g_comm) { ADMM_HIP_CHECK(hipEventSynchronize(ev)); return; }
+    if (C().abort) { inproc_watched_wait([&] { return hipEventQuery(ev); }); return; }
+    if (C().info.backend != COMM_RCCL || !g_comm) { ADMM_HIP_CHECK(hipEventSynchronize(ev)); return; }
     rccl_watched_wait([&] { return hipEventQuery(ev); });
 }
 CommInfo comm_info_live() {
     std::lock_guard<std::mutex> lk(g_mu);
-    CommInfo ci = g_info;
+    CommInfo ci = C().info;
     if (ci.backend == COMM_RCCL && g_comm) {
         int n = 0, r = -1;
         ADMM_NCCL_CHECK(ncclCommCount(g_comm, &n));
@@ -460,59 +498,59 @@ CommInfo comm_info_live() {
         ci.nranks = (int)g_shm.hdr->attached.load(std::memory_order_acquire);
     } else if (ci.backend == COMM_PEER) {
         int n = 0;
-        for (int r = 0; r < kMaxRanks; ++r) n += (g_peer.remote[r] != nullptr);
+        for (int r = 0; r < kMaxRanks; ++r) n += (C().peer.remote[r] != nullptr);
         ci.nranks = n;
     }
     return ci;
 }
 
 void allreduce_sum_f32(float* buf, size_t n, hipStream_t st) {
-    if (!g_info.active || n == 0) return;
-    if (g_info.backend == COMM_RCCL) { exchange(buf, n, nullptr, 0, st); return; }
-    const size_t per = g_slot / sizeof(float);
+    if (!C().info.active || n == 0) return;
+    if (C().info.backend == COMM_RCCL) { exchange(buf, n, nullptr, 0, st); return; }
+    const size_t per = C().slot / sizeof(float);
     for (size_t o = 0; o < n; o += per) exchange(buf + o, std::min(per, n - o), nullptr, 0, st);
 }
 void allreduce_sum_f64(double* buf, size_t n, hipStream_t st) {
-    if (!g_info.active || n == 0) return;
-    if (g_info.backend == COMM_RCCL) { exchange(nullptr, 0, buf, n, st); return; }
-    const size_t per = g_slot / sizeof(double);
+    if (!C().info.active || n == 0) return;
+    if (C().info.backend == COMM_RCCL) { exchange(nullptr, 0, buf, n, st); return; }
+    const size_t per = C().slot / sizeof(double);
     for (size_t o = 0; o < n; o += per) exchange(nullptr, 0, buf + o, std::min(per, n - o), st);
 }
 void broadcast_f32(float* buf, size_t n, int root, hipStream_t st) {
-    if (!g_info.active || n == 0 || g_info.nranks == 1) return;
-    if (g_info.backend == COMM_RCCL) { ADMM_NCCL_CHECK(ncclBroadcast(buf, buf, n, ncclFloat, root, g_comm, st)); return; }
-    if (g_info.backend == COMM_PEER) {
-        const size_t per = g_slot * (size_t)g_info.nranks / sizeof(float);
+    if (!C().info.active || n == 0 || C().info.nranks == 1) return;
+    if (C().info.backend == COMM_RCCL) { ADMM_NCCL_CHECK(ncclBroadcast(buf, buf, n, ncclFloat, root, g_comm, st)); return; }
+    if (C().info.backend == COMM_PEER) {
+        const size_t per = C().slot * (size_t)C().info.nranks / sizeof(float);
         for (size_t o = 0; o < n; o += per) peer_exchange(buf + o, std::min(per, n - o), nullptr, 0, st, root);
         return;
     }
-    if (g_info.rank != root) ADMM_HIP_CHECK(hipMemsetAsync(buf, 0, n * sizeof(float), st));      // SHM (tests): x + 0 + ... + 0 is x bit for bit
+    if (C().info.rank != root) ADMM_HIP_CHECK(hipMemsetAsync(buf, 0, n * sizeof(float), st));      // SHM (tests): x + 0 + ... + 0 is x bit for bit
     allreduce_sum_f32(buf, n, st);
 }
 void reduce_scatter_sum_f32(const float* send, float* recv, size_t count, hipStream_t st) {
     if (count == 0) return;
-    if (!g_info.active || g_info.nranks == 1) {
+    if (!C().info.active || C().info.nranks == 1) {
         ADMM_HIP_CHECK(hipMemcpyAsync(recv, send, count * sizeof(float), hipMemcpyDeviceToDevice, st));
         return;
     }
-    if (g_info.backend == COMM_RCCL) { ADMM_NCCL_CHECK(ncclReduceScatter(send, recv, count, ncclFloat, ncclSum, g_comm, st)); return; }
-    if (g_info.backend == COMM_PEER) {
+    if (C().info.backend == COMM_RCCL) { ADMM_NCCL_CHECK(ncclReduceScatter(send, recv, count, ncclFloat, ncclSum, g_comm, st)); return; }
+    if (C().info.backend == COMM_PEER) {
         // every rank pushes chunk q of its send buffer into rank q's slot and sums the nranks slots it received, in rank order:
         // (nranks - 1) / nranks of an all-reduce's traffic, 1 / nranks of its additions
-        const size_t per = g_slot / sizeof(float);
+        const size_t per = C().slot / sizeof(float);
         for (size_t o = 0; o < count; o += per) peer_exchange(recv + o, std::min(per, count - o), nullptr, 0, st, -1, send + o, count);
         return;
     }
     // SHM (tests): an all-reduce of a copy of the whole send buffer, then this rank's chunk -- the same sums in the same order
-    DevBuf<float> tmp((size_t)g_info.nranks * count);
-    ADMM_HIP_CHECK(hipMemcpyAsync(tmp.get(), send, (size_t)g_info.nranks * count * sizeof(float), hipMemcpyDeviceToDevice, st));
-    allreduce_sum_f32(tmp.get(), (size_t)g_info.nranks * count, st);
-    ADMM_HIP_CHECK(hipMemcpyAsync(recv, tmp.get() + (size_t)g_info.rank * count, count * sizeof(float), hipMemcpyDeviceToDevice, st));
+    DevBuf<float> tmp((size_t)C().info.nranks * count);
+    ADMM_HIP_CHECK(hipMemcpyAsync(tmp.get(), send, (size_t)C().info.nranks * count * sizeof(float), hipMemcpyDeviceToDevice, st));
+    allreduce_sum_f32(tmp.get(), (size_t)C().info.nranks * count, st);
+    ADMM_HIP_CHECK(hipMemcpyAsync(recv, tmp.get() + (size_t)C().info.rank * count, count * sizeof(float), hipMemcpyDeviceToDevice, st));
     ADMM_HIP_CHECK(hipStreamSynchronize(st));             // tmp is freed on return
 }
 void allreduce_sum_f32_f64(float* fbuf, size_t nf, double* dbuf, size_t nd, hipStream_t st) {
-    if (!g_info.active) return;
-    if (g_info.backend != COMM_RCCL && round_up_sz(nf * sizeof(float), 16) + round_up_sz(nd * sizeof(double), 16) > g_slot) {
+    if (!C().info.active) return;
+    if (C().info.backend != COMM_RCCL && round_up_sz(nf * sizeof(float), 16) + round_up_sz(nd * sizeof(double), 16) > C().slot) {
         allreduce_sum_f32(fbuf, nf, st);
         allreduce_sum_f64(dbuf, nd, st);
         return;
@@ -534,8 +572,8 @@ void comm_init(int nranks, int rank, const void* idbytes) {
     ncclUniqueId id;
     std::memcpy(&id, idbytes, sizeof(id));
     ADMM_NCCL_CHECK(ncclCommInitRank(&g_comm, nranks, id, rank));
-    g_info.nranks = nranks; g_info.rank = rank; g_info.active = true; g_info.backend = COMM_RCCL;
-    g_seq = 0;
+    C().info.nranks = nranks; C().info.rank = rank; C().info.active = true; C().info.backend = COMM_RCCL;
+    C().seq = 0;
 }
 
 // `token`: a job-unique non-zero number every rank received over the caller's channel (like RCCL's unique id).  Rank 0
@@ -550,9 +588,9 @@ void comm_init_shm(int nranks, int rank, const char* name, unsigned long long to
     ADMM_REQUIRE(name != nullptr && name[0] == '/' && std::strlen(name) < 200, "shm name must start with '/'");
     ADMM_REQUIRE(token != 0, "the shared-memory token must be non-zero (a job-unique number all ranks agree on)");
     alloc_err_word();
-    g_slot = slot_bytes_from_env();
+    C().slot = slot_bytes_from_env();
     const size_t hdr_bytes = round_up_sz(sizeof(ShmHeader), 4096);
-    const size_t total = hdr_bytes + (size_t)2 * nranks * g_slot;
+    const size_t total = hdr_bytes + (size_t)2 * nranks * C().slot;
     g_shm.name = name;
     const double t0 = now_s();
     const double patience = std::min(wait_seconds_patient(), 60.0);
@@ -572,7 +610,7 @@ void comm_init_shm(int nranks, int rank, const char* name, unsigned long long to
         if (g_shm.fd < 0 || ftruncate(g_shm.fd, (off_t)total) != 0) { shm_close(); throw Error(ADMM_ERR_COMM, "cannot create the shared-memory segment"); }
         g_shm.owner = true;
         map_segment();                                                      // fresh pages read zero: posted[], attached, failed
-        g_shm.hdr->slot = g_slot; g_shm.hdr->nranks = (uint32_t)nranks;
+        g_shm.hdr->slot = C().slot; g_shm.hdr->nranks = (uint32_t)nranks;
         g_shm.hdr->token.store(token, std::memory_order_release);
     } else {
         for (;;) {                                                          // until the segment of THIS job is there
@@ -589,21 +627,21 @@ void comm_init_shm(int nranks, int rank, const char* name, unsigned long long to
             usleep(2000);
         }
     }
-    ADMM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&g_shm.stage_in), g_slot, hipHostMallocDefault));
-    ADMM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&g_shm.stage_out), g_slot, hipHostMallocDefault));
+    ADMM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&g_shm.stage_in), C().slot, hipHostMallocDefault));
+    ADMM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&g_shm.stage_out), C().slot, hipHostMallocDefault));
     g_shm.ring.assign(8192, ShmOp());
     g_shm.hdr->attached.fetch_add(1, std::memory_order_acq_rel);
     while (g_shm.hdr->attached.load(std::memory_order_acquire) < (uint32_t)nranks) {       // everybody is mapped before anyone posts
         if (now_s() - t0 > patience) { shm_close(); throw Error(ADMM_ERR_COMM, "not every rank attached to the shared-memory segment"); }
         usleep(1000);
     }
-    if (g_shm.hdr->attached.load(std::memory_order_acquire) > (uint32_t)nranks || g_shm.hdr->slot != g_slot || g_shm.hdr->nranks != (uint32_t)nranks) {
+    if (g_shm.hdr->attached.load(std::memory_order_acquire) > (uint32_t)nranks || g_shm.hdr->slot != C().slot || g_shm.hdr->nranks != (uint32_t)nranks) {
         shm_close();
         throw Error(ADMM_ERR_COMM, "ranks disagree on slot size / rank count (or more ranks attached than the job has)");
     }
     if (rank == 0) { shm_unlink(name); g_shm.owner = false; }              // everybody holds a mapping: the name is not needed any more and cannot leak
-    g_info.nranks = nranks; g_info.rank = rank; g_info.active = true; g_info.backend = COMM_SHM;
-    g_seq = 0;
+    C().info.nranks = nranks; C().info.rank = rank; C().info.active = true; C().info.backend = COMM_SHM;
+    C().seq = 0;
 }
 
 // PEER, step 1: allocate this rank's exchange buffer and export it.
@@ -611,10 +649,10 @@ void comm_peer_prepare(int nranks, void* handle_out) {
     std::lock_guard<std::mutex> lk(g_mu);
     require_free();
     ADMM_REQUIRE(nranks >= 1 && nranks <= kMaxRanks, "bad nranks");
-    if (g_peer.local) peer_close();
+    if (C().peer.local) peer_close();
     peer_alloc_local(nranks);
     hipIpcMemHandle_t h;
-    ADMM_HIP_CHECK(hipIpcGetMemHandle(&h, g_peer.local));
+    ADMM_HIP_CHECK(hipIpcGetMemHandle(&h, C().peer.local));
     static_assert(sizeof(hipIpcMemHandle_t) == ADMM_HIP_PEER_HANDLE_BYTES, "hipIpcMemHandle_t size");
     std::memcpy(handle_out, &h, sizeof(h));
 }
@@ -623,41 +661,155 @@ void comm_init_peer(int nranks, int rank, const void* handles) {
     std::lock_guard<std::mutex> lk(g_mu);
     require_free();
     check_ranks(nranks, rank);
-    if (!g_peer.local) throw Error(ADMM_ERR_COMM, "call admm_hip_comm_peer_prepare first");
-    ADMM_REQUIRE(g_peer.flags_off == (size_t)2 * nranks * g_slot, "nranks differs from the prepared buffer");
+    if (!C().peer.local) throw Error(ADMM_ERR_COMM, "call admm_hip_comm_peer_prepare first");
+    ADMM_REQUIRE(C().peer.flags_off == (size_t)2 * nranks * C().slot, "nranks differs from the prepared buffer");
     alloc_err_word();
     for (int r = 0; r < nranks; ++r) {
-        if (r == rank) { g_peer.remote[r] = g_peer.local; continue; }
+        if (r == rank) { C().peer.remote[r] = C().peer.local; continue; }
         hipIpcMemHandle_t h;
         std::memcpy(&h, static_cast<const unsigned char*>(handles) + (size_t)r * sizeof(h), sizeof(h));
         void* ptr = nullptr;
         ADMM_HIP_CHECK(hipIpcOpenMemHandle(&ptr, h, hipIpcMemLazyEnablePeerAccess));
-        g_peer.remote[r] = static_cast<unsigned char*>(ptr);
-        g_peer.opened[r] = true;
+        C().peer.remote[r] = static_cast<unsigned char*>(ptr);
+        C().peer.opened[r] = true;
     }
-    if (!g_derr) ADMM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&g_derr), sizeof(int)));
-    ADMM_HIP_CHECK(hipMemset(g_derr, 0, sizeof(int)));
-    ADMM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&g_peer.count), (nranks + 1) * sizeof(unsigned int)));
-    ADMM_HIP_CHECK(hipMemset(g_peer.count, 0, (nranks + 1) * sizeof(unsigned int)));
-    ADMM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&g_peer.aux_seq), sizeof(unsigned long long)));
-    ADMM_HIP_CHECK(hipMemset(g_peer.aux_seq, 0, sizeof(unsigned long long)));
-    ADMM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&g_peer.d_remote), nranks * sizeof(unsigned char*)));
-    ADMM_HIP_CHECK(hipMemcpy(g_peer.d_remote, g_peer.remote, nranks * sizeof(unsigned char*), hipMemcpyHostToDevice));
+    if (!C().derr) ADMM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&C().derr), sizeof(int)));
+    ADMM_HIP_CHECK(hipMemset(C().derr, 0, sizeof(int)));
+    ADMM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&C().peer.count), (nranks + 1) * sizeof(unsigned int)));
+    ADMM_HIP_CHECK(hipMemset(C().peer.count, 0, (nranks + 1) * sizeof(unsigned int)));
+    ADMM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&C().peer.aux_seq), sizeof(unsigned long long)));
+    ADMM_HIP_CHECK(hipMemset(C().peer.aux_seq, 0, sizeof(unsigned long long)));
+    ADMM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&C().peer.d_remote), nranks * sizeof(unsigned char*)));
+    ADMM_HIP_CHECK(hipMemcpy(C().peer.d_remote, C().peer.remote, nranks * sizeof(unsigned char*), hipMemcpyHostToDevice));
     ADMM_HIP_CHECK(hipDeviceSynchronize());
-    g_info.nranks = nranks; g_info.rank = rank; g_info.active = true; g_info.backend = COMM_PEER;
-    g_seq = 0;
+    C().info.nranks = nranks; C().info.rank = rank; C().info.active = true; C().info.backend = COMM_PEER;
+    C().seq = 0;
 }
 
 void comm_finalize() {
     std::lock_guard<std::mutex> lk(g_mu);
     (void)hipDeviceSynchronize();
     if (g_comm) { (void)ncclCommDestroy(g_comm); g_comm = nullptr; }
-    if (g_info.backend == COMM_SHM) shm_close();
-    if (g_peer.local) peer_close();
-    if (g_err) *g_err = 0;
-    if (g_derr) (void)hipMemset(g_derr, 0, sizeof(int));
-    g_info = CommInfo();
-    g_seq = 0;
+    if (C().info.backend == COMM_SHM) shm_close();
+    if (C().peer.local) peer_close();
+    if (C().err) *C().err = 0;
+    if (C().derr) (void)hipMemset(C().derr, 0, sizeof(int));
+    C().info = CommInfo();
+    C().seq = 0;
+}
+
+// ---------------------------------------------------------------------------------------------- in-process group (api.hip)
+// The PEER backend with its bootstrap inside one process: every rank thread allocates its exchange buffer on its own device
+// (fine-grained, peer_alloc_local) and the threads swap the plain device pointers through host memory -- peer access was
+// enabled between the listed devices when the group was created, so no hipIpc handle is needed.  The kernels and the slot
+// protocol are those of the process-wide PEER backend.  Failure rule: a rank that fails raises the group's abort word
+// (fine-grained host memory, read by the host waits above and by the device waits of peer_device.h inside their spin), and
+// every other rank ends its call with ADMM_ERR_COMM at its next wait.
+struct InprocGroup {
+    int nranks = 0;
+    std::vector<int> devices;
+    int* abort = nullptr;
+    std::vector<CommCtx*> ctx;                        // owned; freed by comm_group_destroy after the rank threads have returned
+    std::atomic<int> arrived{0};
+};
+
+InprocGroup* comm_group_create(const std::vector<int>& devices) {
+    ADMM_REQUIRE(!devices.empty() && (int)devices.size() <= kMaxRanks, "bad number of in-process ranks");
+    std::unique_ptr<InprocGroup> g(new InprocGroup());
+    g->nranks = (int)devices.size();
+    g->devices = devices;
+    int cur = 0;
+    ADMM_HIP_CHECK(hipGetDevice(&cur));
+    std::vector<int> distinct(devices);
+    std::sort(distinct.begin(), distinct.end());
+    distinct.erase(std::unique(distinct.begin(), distinct.end()), distinct.end());
+    try {
+        for (int d : distinct) {
+            for (int e : distinct) {
+                if (d == e) continue;
+                int can = 0;
+                ADMM_HIP_CHECK(hipDeviceCanAccessPeer(&can, d, e));
+                if (!can) throw Error(ADMM_ERR_COMM, "in-process ranks: device " + std::to_string(d) + " cannot access device " + std::to_string(e) +
+                                                         " (no peer access; the PEER exchange needs it)");
+                ADMM_HIP_CHECK(hipSetDevice(d));
+                const hipError_t pe = hipDeviceEnablePeerAccess(e, 0);
+                if (pe == hipErrorPeerAccessAlreadyEnabled) (void)hipGetLastError();
+                else ADMM_HIP_CHECK(pe);
+            }
+        }
+        (void)hipSetDevice(cur);
+    } catch (...) {
+        (void)hipSetDevice(cur);
+        throw;
+    }
+    ADMM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&g->abort), 64, hipHostMallocCoherent | hipHostMallocMapped | hipHostMallocPortable));
+    *reinterpret_cast<volatile int*>(g->abort) = 0;
+    for (int r = 0; r < g->nranks; ++r) g->ctx.push_back(new CommCtx());
+    return g.release();
+}
+
+void comm_group_abort(InprocGroup* g) {
+    if (g && g->abort) __atomic_store_n(g->abort, 1, __ATOMIC_SEQ_CST);
+}
+
+// In rank `rank`'s thread, on its device: allocate, swap pointers with the other ranks, install the context.
+void comm_group_attach(InprocGroup* g, int rank) {
+    CommCtx& c = *g->ctx[rank];
+    c.abort = g->abort;
+    t_ctx = &c;                                        // from here on every allocation below is this rank's (freed by comm_group_destroy)
+    peer_alloc_local(g->nranks);
+    ADMM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&c.err), sizeof(int), hipHostMallocMapped));
+    *c.err = 0;
+    ADMM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c.derr), sizeof(int)));
+    ADMM_HIP_CHECK(hipMemset(c.derr, 0, sizeof(int)));
+    ADMM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c.peer.count), (g->nranks + 1) * sizeof(unsigned int)));
+    ADMM_HIP_CHECK(hipMemset(c.peer.count, 0, (g->nranks + 1) * sizeof(unsigned int)));
+    ADMM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c.peer.aux_seq), sizeof(unsigned long long)));
+    ADMM_HIP_CHECK(hipMemset(c.peer.aux_seq, 0, sizeof(unsigned long long)));
+    ADMM_HIP_CHECK(hipMalloc(reinterpret_cast<void**>(&c.peer.d_remote), g->nranks * sizeof(unsigned char*)));
+    ADMM_HIP_CHECK(hipDeviceSynchronize());
+    // every rank's buffer is allocated and cleared before anyone reads the pointers (the release of `arrived` publishes them)
+    g->arrived.fetch_add(1, std::memory_order_acq_rel);
+    const double t0 = now_s(), patience = std::min(wait_seconds_patient(), 60.0);
+    while (g->arrived.load(std::memory_order_acquire) < g->nranks) {
+        if (*reinterpret_cast<volatile int*>(g->abort)) throw Error(ADMM_ERR_COMM, "exchange abandoned: another rank of this in-process call failed during setup");
+        if (now_s() - t0 > patience) throw Error(ADMM_ERR_COMM, "in-process ranks: not every rank reached the exchange setup");
+        usleep(200);
+    }
+    for (int r = 0; r < g->nranks; ++r) c.peer.remote[r] = g->ctx[r]->peer.local;
+    ADMM_HIP_CHECK(hipMemcpy(c.peer.d_remote, c.peer.remote, g->nranks * sizeof(unsigned char*), hipMemcpyHostToDevice));
+    c.info.nranks = g->nranks; c.info.rank = rank; c.info.active = true; c.info.backend = COMM_PEER;
+    c.seq = 0;
+}
+
+void comm_group_detach() { t_ctx = nullptr; }
+
+// Calling thread, after every rank thread has returned (their streams are idle): free every rank's buffers on its device.
+void comm_group_destroy(InprocGroup* g) {
+    if (!g) return;
+    int cur = 0;
+    (void)hipGetDevice(&cur);
+    for (int r = 0; r < g->nranks; ++r) {
+        CommCtx* c = g->ctx[r];
+        (void)hipSetDevice(g->devices[r]);
+        (void)hipDeviceSynchronize();
+        if (c->peer.local) (void)hipFree(c->peer.local);
+        if (c->peer.count) (void)hipFree(c->peer.count);
+        if (c->peer.aux_seq) (void)hipFree(c->peer.aux_seq);
+        if (c->peer.d_remote) (void)hipFree(c->peer.d_remote);
+        if (c->derr) (void)hipFree(c->derr);
+        if (c->err) (void)hipHostFree(c->err);
+        delete c;
+    }
+    (void)hipSetDevice(cur);
+    if (g->abort) (void)hipHostFree(g->abort);
+    delete g;
+}
+
+// Stream destructor during unwinding (admm_internal.h): raise the abort word FIRST, so that this rank's own waiting kernels and
+// the other ranks' end at once instead of after their time limit.
+void comm_unwinding() {
+    if (t_ctx && t_ctx->abort) __atomic_store_n(t_ctx->abort, 1, __ATOMIC_SEQ_CST);
 }
 
 }  // namespace admm

@@ -17,7 +17,7 @@ struct LoopTimes {
 struct PinnedFlag {
     int* p = nullptr;
     PinnedFlag() { ADMM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&p), sizeof(int), hipHostMallocDefault)); *p = 0; }
-    ~PinnedFlag() { if (p) (void)hipHostFree(p); }
+    ~PinnedFlag() { if (p) pinned_free(p); }
     PinnedFlag(const PinnedFlag&) = delete;
     PinnedFlag& operator=(const PinnedFlag&) = delete;
 };
@@ -36,7 +36,7 @@ inline LoopTimes run_until_done(hipStream_t st, const int* d_done, int batch, lo
     const TraceRange trace_range("admm:loop");
     int* h_done = nullptr;
     ADMM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h_done), 2 * sizeof(int), hipHostMallocDefault));
-    struct HostFree { void* p; ~HostFree() { (void)hipHostFree(p); } } hf{h_done};
+    struct HostFree { void* p; ~HostFree() { pinned_free(p); } } hf{h_done};
     h_done[0] = h_done[1] = 0;
     const CommLockstep lockstep;                       // exchanges enqueued from here are per-iteration: short wait bound
     const int batch0 = batch;

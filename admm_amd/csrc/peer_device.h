@@ -21,6 +21,8 @@ struct PeerExchange {
     unsigned int* count;                // [nranks + 1] arrival counters of the producing launch (device memory)
     int* err;                           // device word: non-zero after a timed-out wait
     long long timeout_ticks;            // wall_clock64 ticks (100 MHz)
+    const int* abort;                   // read inside the waits only: the abort word of an in-process group (comm.hip; fine-grained
+                                        // host memory every rank's device reads), else this rank's own err word
 };
 
 __device__ __forceinline__ unsigned long long* peer_flag(unsigned char* buf, size_t flags_off, unsigned long long seq, int nranks, int src) {
@@ -70,7 +72,7 @@ __device__ __forceinline__ bool peer_wait_relaxed(const PeerExchange& e) {
         const long long t0 = wall_clock64();
         while (__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) < e.seq) {
             __builtin_amdgcn_s_sleep(1);
-            if (wall_clock64() - t0 > e.timeout_ticks) {
+            if (wall_clock64() - t0 > e.timeout_ticks || *reinterpret_cast<const volatile int*>(e.abort)) {
                 __hip_atomic_store(e.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 ok = false;
                 break;
@@ -106,6 +108,7 @@ struct PeerAux {
     int nranks, rank;
     unsigned long long* seq;            // device word: exchanges made through the region so far
     int* err; long long timeout_ticks;
+    const int* abort;                   // as PeerExchange::abort
 };
 __device__ __forceinline__ float* aux_slot(unsigned char* buf, const PeerAux& a, unsigned long long e, int src) {
     return reinterpret_cast<float*>(buf + a.data_off + ((size_t)(e & 1) * a.nranks + src) * kAuxSlotBytes);
@@ -122,7 +125,7 @@ __device__ __forceinline__ bool aux_wait(const PeerAux& a, unsigned long long e,
         const long long t0 = wall_clock64();
         while (__hip_atomic_load(f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) < e) {
             __builtin_amdgcn_s_sleep(1);
-            if (wall_clock64() - t0 > a.timeout_ticks) { __hip_atomic_store(a.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); ok = false; break; }
+            if (wall_clock64() - t0 > a.timeout_ticks || *reinterpret_cast<const volatile int*>(a.abort)) { __hip_atomic_store(a.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); ok = false; break; }
         }
     }
     return __all(ok) != 0;
@@ -144,7 +147,7 @@ __device__ __forceinline__ bool peer_wait(const PeerExchange& e) {
         const long long t0 = wall_clock64();
         while (__hip_atomic_load(f, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) < e.seq) {
             __builtin_amdgcn_s_sleep(2);
-            if (wall_clock64() - t0 > e.timeout_ticks || *reinterpret_cast<volatile int*>(e.err)) {
+            if (wall_clock64() - t0 > e.timeout_ticks || *reinterpret_cast<volatile int*>(e.err) || *reinterpret_cast<const volatile int*>(e.abort)) {
                 *reinterpret_cast<volatile int*>(e.err) = 1;
                 break;
             }

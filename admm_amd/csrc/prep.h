@@ -33,7 +33,10 @@ struct DeviceData {
 // DataStd::standardize (DataStd.h:89-155) there.  mem: ADMM_MEM_HOST / ADMM_MEM_DEVICE.
 template <typename T>
 void upload_standardize(DeviceData<T>& d, const double* x, const double* y, int n, int p, int mem,
-                        bool standardize, bool intercept, hipStream_t st, long long n_total = 0);
+                        bool standardize, bool intercept, hipStream_t st, long long n_total = 0, long long ldx_in = 0);
+// ldx_in > n: x is a row slice of a taller column-major matrix (leading dimension ldx_in) -- a rank of an in-process
+// admm_hip_parlasso.  Host input then travels as one contiguous column piece at a time through the pinned ring (the caller's
+// matrix is never repacked); device input is read in place.
 
 // Host-input variant for the tall fp32 path: the same conversion and standardisation, column chunk by column chunk,
 // with the Gram block row of every chunk (it only needs the chunks that have already arrived) enqueued behind it, so

@@ -367,9 +367,59 @@ void write_device(void* dst, const void* src, size_t bytes) {
     }
 }
 
+void write_device_cols(double* dst, const double* src, size_t rows, size_t ld, size_t ncols) {
+    const size_t col_bytes = rows * sizeof(double);
+    if (ld == rows) { write_device(dst, src, col_bytes * ncols); return; }
+    const char* h2d = option("H2D");
+    const bool pageable = h2d && std::string(h2d) == "pageable";
+    if (pageable || col_bytes * ncols < (size_t(4) << 20)) {
+        ADMM_HIP_CHECK(hipMemcpy2D(dst, col_bytes, src, ld * sizeof(double), col_bytes, ncols, hipMemcpyHostToDevice));
+        return;
+    }
+    if (col_bytes > H2DRing::kSlot) {                    // (a column piece longer than a slot: each piece is a transfer of its own)
+        for (size_t j = 0; j < ncols; ++j) write_device(dst + j * rows, src + j * ld, col_bytes);
+        return;
+    }
+    H2DRing& r = h2d_ring();
+    const int nt = h2d_threads();
+    const size_t per_slot = H2DRing::kSlot / col_bytes;
+    int i = 0;
+    bool used[H2DRing::kSlots] = {false, false, false};
+    try {
+        for (size_t j0 = 0; j0 < ncols; j0 += per_slot, i = (i + 1) % H2DRing::kSlots) {
+            const size_t nc = std::min(per_slot, ncols - j0);
+            if (used[i]) ADMM_HIP_CHECK(hipEventSynchronize(r.ev[i]));
+            char* slot = static_cast<char*>(r.slot[i]);
+            auto copy_cols = [&](size_t a, size_t b) {
+                for (size_t j = a; j < b; ++j) std::memcpy(slot + j * col_bytes, src + (j0 + j) * ld, col_bytes);
+            };
+            const int use = (int)std::min<size_t>((size_t)nt, std::max<size_t>(1, nc * col_bytes / (size_t(1) << 20)));
+            if (use <= 1) copy_cols(0, nc);
+            else {
+                std::vector<std::thread> th;
+                const size_t step = (nc + use - 1) / use;
+                for (int t = 1; t < use; ++t) {
+                    const size_t a = step * t, b = std::min(nc, a + step);
+                    if (a < b) th.emplace_back(copy_cols, a, b);
+                }
+                copy_cols(0, std::min(nc, step));
+                for (std::thread& t : th) t.join();
+            }
+            ADMM_HIP_CHECK(hipMemcpyAsync(dst + j0 * rows, slot, nc * col_bytes, hipMemcpyHostToDevice, r.st));
+            ADMM_HIP_CHECK(hipEventRecord(r.ev[i], r.st));
+            used[i] = true;
+        }
+        ADMM_HIP_CHECK(hipStreamSynchronize(r.st));
+    } catch (...) {
+        (void)hipStreamSynchronize(r.st);
+        throw;
+    }
+}
+
 template <typename T>
 void upload_standardize(DeviceData<T>& d, const double* x, const double* y, int n, int p, int mem,
-                        bool standardize, bool intercept, hipStream_t st, long long n_total) {
+                        bool standardize, bool intercept, hipStream_t st, long long n_total, long long ldx_in) {
+    if (ldx_in < n) ldx_in = n;
     const TraceRange trace_range("admm:convert+standardize");
     const bool dist = n_total > 0;          // only the multi-process entry points pass n_total: all ranks are in this call
     if (n_total <= 0) n_total = n;
@@ -387,10 +437,11 @@ void upload_standardize(DeviceData<T>& d, const double* x, const double* y, int 
     const int ny = std::max(1, std::min(64, (n + 255) / 256));
     double t0 = now_s();
     double th = 0;
+    long long ldsrc = n;                                                // leading dimension of what convert_block reads
     auto convert_block = [&](const double* src, int c0, int nc) {       // columns [c0, c0 + nc) from a device block of nc columns
-        if (fused) hipLaunchKernelGGL((convert_standardize_kernel<T>), dim3(nc), dim3(256), 0, st, src, (const double*)nullptr, (long long)n, n, p, c0,
+        if (fused) hipLaunchKernelGGL((convert_standardize_kernel<T>), dim3(nc), dim3(256), 0, st, src, (const double*)nullptr, ldsrc, n, p, c0,
                                       d.X.get(), d.Y.get(), d.ldx, d.flag, (double)n_total, fmean.get(), fscale.get());
-        else hipLaunchKernelGGL((convert_cols_kernel<T>), dim3(nc, ny), dim3(256), 0, st, src, (long long)n, n, d.X.get() + (size_t)c0 * d.ldx, d.ldx);
+        else hipLaunchKernelGGL((convert_cols_kernel<T>), dim3(nc, ny), dim3(256), 0, st, src, ldsrc, n, d.X.get() + (size_t)c0 * d.ldx, d.ldx);
     };
     auto convert_y = [&](const double* src) {
         if (fused) hipLaunchKernelGGL((convert_standardize_kernel<T>), dim3(1), dim3(256), 0, st, (const double*)nullptr, src, (long long)n, n, p, 0,
@@ -399,7 +450,9 @@ void upload_standardize(DeviceData<T>& d, const double* x, const double* y, int 
     };
     // ---- pass 0: narrow to T on the device
     if (mem == ADMM_MEM_DEVICE) {
+        ldsrc = ldx_in;
         convert_block(x, 0, p);
+        ldsrc = n;
         convert_y(y);
     } else {
         // Host input (what R hands over): stream column chunks through two device staging buffers.
@@ -416,7 +469,7 @@ void upload_standardize(DeviceData<T>& d, const double* x, const double* y, int 
             const int nc = std::min(cols_per_chunk, p - c0);
             if (used[b]) ADMM_HIP_CHECK(hipEventSynchronize(ev[b].e));
             double t1 = now_s();
-            write_device(stage[b].get(), x + (size_t)c0 * n, (size_t)nc * n * sizeof(double));
+            write_device_cols(stage[b].get(), x + (size_t)c0 * ldx_in, (size_t)n, (size_t)ldx_in, (size_t)nc);
             th += now_s() - t1;
             convert_block(stage[b].get(), c0, nc);
             ADMM_HIP_CHECK(hipEventRecord(ev[b].e, st));
@@ -465,7 +518,7 @@ void upload_standardize(DeviceData<T>& d, const double* x, const double* y, int 
     d.t_h2d = th;
     d.t_std = now_s() - t0 - th;
 }
-template void upload_standardize<float>(DeviceData<float>&, const double*, const double*, int, int, int, bool, bool, hipStream_t, long long);
+template void upload_standardize<float>(DeviceData<float>&, const double*, const double*, int, int, int, bool, bool, hipStream_t, long long, long long);
 // Multi-response fits (admm_hip_lasso_multi): a DeviceData for another response y of the SAME x.  X, its column statistics
 // and (if present) the Gram matrix are copied device to device from `base`; y (device doubles) is converted and
 // standardised by the kernels upload_standardize runs on column p with the same flag -- column by column they do not depend
@@ -516,7 +569,7 @@ void clone_with_response_f32(DeviceData<float>& d, const DeviceData<float>& base
     comm_stream_sync(st);
 }
 
-template void upload_standardize<double>(DeviceData<double>&, const double*, const double*, int, int, int, bool, bool, hipStream_t, long long);
+template void upload_standardize<double>(DeviceData<double>&, const double*, const double*, int, int, int, bool, bool, hipStream_t, long long, long long);
 
 void gram_rows_mfma_f32(const float* Z, long long ldz, int r0, int nr, int K, float* C, long long ldc, hipStream_t st);   // syrk_mfma.hip
 

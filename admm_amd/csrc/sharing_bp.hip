@@ -1364,7 +1364,7 @@ static void sbp_sprad_batch(const double* A, long long lda, int n, const std::ve
     struct Pinned {
         double* p = nullptr;
         explicit Pinned(size_t n_) { ADMM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&p), n_ * sizeof(double), hipHostMallocDefault)); }
-        ~Pinned() { if (p) (void)hipHostFree(p); }
+        ~Pinned() { if (p) pinned_free(p); }
         Pinned(const Pinned&) = delete;
         Pinned& operator=(const Pinned&) = delete;
     } hal((size_t)mmax * B), hb2((size_t)mmax * B);

@@ -165,7 +165,14 @@ ADMM_HIP_API int admm_hip_lasso_multi(const double* x, const double* Y, int n, i
                          double* lambda_out, float* beta_out, int* niter_out, admm_stats* stats);
 
 /* Row-block consensus ADMM with `nthread` blocks (ParLasso.cpp:33-36,71-72: nthread only sets the
- * number of blocks K).  All K blocks run on the current device. */
+ * number of blocks K).  By default all K blocks run on the current device.
+ * In-process multi-device mode (option PAR_DEVICES / admm_hip_options.par_devices, off by default): with D devices listed the call
+ * runs N = the largest divisor of K that is <= D ranks, one host thread per rank, rank r on the r-th listed device.  Each rank
+ * uploads only its row slice of x (admm_hip_parlasso_dist's partition: K / N whole blocks per rank) and runs the distributed
+ * consensus solver; the ranks exchange through the PEER one-shot all-reduce over device pointers (peer access between the listed
+ * devices is enabled by the call).  The outputs are rank 0's (every rank holds the full result).  N = 1: the default path.  Refused
+ * (ADMM_ERR_INVALID_ARG) while a process-wide communicator is attached.  mem = ADMM_MEM_DEVICE: ranks on other devices read their
+ * slice over peer access (refused when there is none).  A failing rank ends every rank's call (ADMM_ERR_COMM or its own code). */
 ADMM_HIP_API int admm_hip_parlasso(const double* x, const double* y, int n, int p, int mem,
                       const double* lambda_in, int nlambda_in, int nlambda_auto, double lmin_ratio,
                       int standardize, int intercept, int nthread, const admm_opts* opts,
@@ -209,6 +216,9 @@ ADMM_HIP_API int admm_hip_dantzig_traced(const double* x, const double* y, int n
  * _dist: the blocks spread over the ranks of the attached communicator -- this rank passes columns
  * [col_offset, col_offset + p_local) of the p_total, whole blocks of the partition above, and gets their coefficients back;
  * one sum all-reduce of n + O(n / 32) doubles per iteration (the "all-reduce of X_i beta_i" of SURVEY.md section 8f row n2). */
+/* admm_hip_parbp / _traced with PAR_DEVICES (as admm_hip_parlasso above): N = the largest divisor of nthread that is <= the number of
+ * listed devices; rank r runs admm_hip_parbp_dist on its whole blocks of columns on its own device; beta_out is assembled from the
+ * ranks' column blocks, niter_out / stats / the trace are rank 0's (the decisions are replicated on every rank). */
 ADMM_HIP_API int admm_hip_parbp(const double* x, const double* y, int n, int p, int mem, int nthread, const admm_opts* opts,
                                 double* beta_out, int* niter_out, admm_stats* stats);
 ADMM_HIP_API int admm_hip_parbp_traced(const double* x, const double* y, int n, int p, int mem, int nthread, const admm_opts* opts,
@@ -330,7 +340,9 @@ typedef struct admm_hip_options {
                                  picks the 8-bit code where its bounds are tight enough, else fp16), 1 always (fp16), 2 never, 3 always, wide
                                  solver with the 8-bit code */
     int lad_two_pass;         /* 1: LAD with the reference's two products per iteration (default: one pass over the rows of X, p <= 6144) */
-    int reserved[10];
+    int par_devices;          /* admm_hip_parlasso / admm_hip_parbp in-process over several devices (named option PAR_DEVICES):
+                                 0 off (default), -1 every device (PAR_DEVICES=all), k > 0 devices 0 .. k-1 */
+    int reserved[9];
 } admm_hip_options;
 ADMM_HIP_API int admm_hip_options_default(admm_hip_options* o);               /* zero-fills and sets struct_size */
 ADMM_HIP_API int admm_hip_options_set(const admm_hip_options* o);             /* NULL: back to the defaults (keeps nothing of the thread's earlier settings) */
@@ -426,6 +438,16 @@ ADMM_HIP_API int admm_hip_lasso_plan_create_dist_cols(const double* x_cols, cons
                                          const double* lambda_in, int nlambda_in, int nlambda_auto, double lmin_ratio,
                                          int standardize, int intercept, double alpha, const admm_opts* opts,
                                          admm_hip_plan** plan_out, int* nlambda_out);
+
+/* In-process multi-device mode (admm_hip_parlasso / admm_hip_parbp with PAR_DEVICES):
+ * admm_hip_last_parallel_layout: the rank-to-device layout of the CALLING THREAD's last admm_hip_parlasso / admm_hip_parbp call
+ *   (thread-local): *nranks = its number of ranks (1: the single-device path, 0: no such call yet), devices[r] = rank r's device
+ *   for r < min(*nranks, cap).
+ * admm_hip_parallel_assign: the same layout for `nblocks` blocks and a PAR_DEVICES value, computed on the host without touching a
+ *   device ("all" means device_count devices).  Returns ADMM_ERR_INVALID_ARG for a malformed list or a device >= device_count.
+ *   *nranks = 1 when the mode is off ("0", "" or NULL) or only one rank fits. */
+ADMM_HIP_API int admm_hip_last_parallel_layout(int* nranks, int* devices, int cap);
+ADMM_HIP_API int admm_hip_parallel_assign(int nblocks, const char* par_devices, int device_count, int* nranks, int* devices, int cap);
 
 ADMM_HIP_API const char* admm_hip_last_error(void);
 ADMM_HIP_API const char* admm_hip_version(void);
