@@ -24,43 +24,6 @@ void comm_init_shm(int nranks, int rank, const char* name, unsigned long long to
 void cv_gather(const double* x, long long ldx, const double* y, const int* d_idx, int m, int p, double* xo, double* yo, hipStream_t st);
 std::vector<double> cv_score(const double* xt, const double* yt, int m, int p, const float* beta_host, int nlam, hipStream_t st);
 
-// ---- variant selectors / tuning values (admm_internal.h: option)
-}  // namespace admm
-extern char** environ;
-namespace admm {
-namespace {
-using OptMap = std::unordered_map<std::string, std::string>;
-// the ADMM_HIP_* variables of the environment the library was first used in -- read once, never again
-const OptMap& option_overlay() {
-    static const OptMap* m = []() {
-        OptMap* o = new OptMap();
-        for (char** e = environ; e && *e; ++e) {
-            if (std::strncmp(*e, "ADMM_HIP_", 9) != 0) continue;
-            const char* eq = std::strchr(*e, '=');
-            if (eq && eq > *e + 9) (*o)[std::string(*e + 9, (size_t)(eq - (*e + 9)))] = std::string(eq + 1);
-        }
-        return o;
-    }();
-    return *m;
-}
-OptMap& option_thread() { static thread_local OptMap m; return m; }
-}  // namespace
-const char* option(const char* name) {
-    const OptMap& t = option_thread();
-    if (!t.empty()) { auto it = t.find(name); if (it != t.end()) return it->second.c_str(); }
-    const OptMap& o = option_overlay();
-    auto it = o.find(name);
-    return it != o.end() ? it->second.c_str() : nullptr;
-}
-int option_int(const char* name, int dflt) {
-    const char* v = option(name);
-    return v ? std::atoi(v) : dflt;
-}
-void option_set_thread(const char* name, const char* value) {
-    if (value) option_thread()[name] = value; else option_thread().erase(name);
-}
-void options_reset_thread() { option_thread().clear(); }
-
 // ---- cache of large device blocks (admm_internal.h, DevBuf)
 namespace {
 struct PoolBlock { void* p; size_t bytes; int dev; };
@@ -76,7 +39,7 @@ constexpr size_t kPoolMinBytes = size_t(32) << 20;
 // C2 setup re-uses is ~10 GB).  Allocators of this library that bypass DevBuf (the PEER exchange buffer) trim the cache and retry on
 // out-of-memory themselves; admm_hip_trim_memory() hands everything back on request.
 size_t pool_cap_bytes() {
-    if (const char* e = option("POOL_MB")) { const long long mb = std::atoll(e); return mb > 0 ? (size_t)mb << 20 : size_t(0); }
+    if (opt_set(Opt::POOL_MB)) return (size_t)opt_int(Opt::POOL_MB, 0) << 20;
     static const size_t dflt = []() {
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) { (void)hipGetLastError(); total_b = size_t(128) << 30; }
@@ -202,6 +165,7 @@ std::vector<double> make_lambda_grid(const LassoProblem& pb, double lambda0, int
 template <typename F>
 static int guarded(F&& f) {
     try {
+        check_option_overlay();
         f();
         return ADMM_OK;
     } catch (const Error& e) {
@@ -243,8 +207,8 @@ static LassoProblem make_problem(const double* lambda_in, int nlambda_in, int nl
     pb.alpha = alpha;
     pb.nworkers = nworkers;
     pb.dist = dist;
-    pb.batch_iters = option_int("BATCH_ITERS", 0);
-    pb.profile_stride = option_int("PROFILE_STRIDE", 0);
+    pb.batch_iters = (int)opt_int(Opt::BATCH_ITERS, 0);
+    pb.profile_stride = (int)opt_int(Opt::PROFILE_STRIDE, 0);
     return pb;
 }
 
@@ -270,9 +234,7 @@ static PlanHandle* create_plan(const double* x, const double* y, int n, int p, i
     const LassoProblem pb = make_problem(lambda_in, nlambda_in, nlambda_auto, lmin_ratio, enet, alpha, nworkers, dist, opts);
     DeviceData<float> d;
     // Host input of a large tall problem: standardisation and X'X run under the PCIe transfer (bit-identical result).
-    const char* eg = option("GRAM");
-    const bool pipelined = mem == ADMM_MEM_HOST && !dist && nworkers <= 0 && n > p && p >= 4096 &&
-                           !(eg && (std::string(eg) == "rocblas" || std::string(eg) == "oneshot"));
+    const bool pipelined = mem == ADMM_MEM_HOST && !dist && nworkers <= 0 && n > p && p >= 4096 && !opt_set(Opt::GRAM);
     if (pipelined) upload_standardize_gram_f32(d, x, y, n, p, standardize != 0, intercept != 0, h->st.s);
     else upload_standardize<float>(d, x, y, n, p, mem, standardize != 0, intercept != 0, h->st.s, dist ? n_total : 0, ldx);
     if (nworkers > 0) h->plan = make_par_plan(std::move(d), pb, h->st.s);
@@ -309,7 +271,7 @@ static PlanHandle* create_plan_cols(const double* x_cols, const double* y, int n
     pb.alpha = alpha;
     pb.p_total = p_total;
     pb.col_offset = col_offset;
-    pb.batch_iters = option_int("BATCH_ITERS", 0);
+    pb.batch_iters = (int)opt_int(Opt::BATCH_ITERS, 0);
     DeviceData<float> d;
     upload_standardize<float>(d, x_cols, y, n, p_local, mem, standardize != 0, intercept != 0, h->st.s, 0);   // column moments are local, y is replicated
     h->plan = make_wide_plan(std::move(d), pb, h->st.s);
@@ -387,7 +349,7 @@ static void lasso_cv(const double* x, const double* y, int n, int p, int mem, co
     int min_tr = n;
     for (int f = 0; f < nfolds; ++f) min_tr = std::min(min_tr, n - cnt[f]);
     bool downdate = min_tr > p && p >= 1024;
-    if (const char* e = option("CV_DOWNDATE")) downdate = min_tr > p && std::string(e) == "1";
+    if (opt_set(Opt::CV_DOWNDATE)) downdate = min_tr > p && opt_on(Opt::CV_DOWNDATE);
     CvBase base;
     if (downdate) {
         ADMM_REQUIRE(nlambda_in >= 0, "nlambda_in must be >= 0");
@@ -537,7 +499,7 @@ static void lasso_multi(const double* x, const double* Y, int n, int p, int m, i
     pb.lmin_ratio = lmin_ratio;
     pb.enet = enet;
     pb.alpha = enet ? alpha : 1.0;
-    pb.batch_iters = option_int("BATCH_ITERS", 0);
+    pb.batch_iters = (int)opt_int(Opt::BATCH_ITERS, 0);
     pb.profile_stride = 0;
     if (nlambda_in == 0) ADMM_REQUIRE(lmin_ratio > 0 && lmin_ratio < 1, "lambda_min_ratio must be within (0, 1)");
     for (int i = 0; i < nlambda_in; ++i) ADMM_REQUIRE(lambda_in[i] > 0, "lambda must be positive");
@@ -596,32 +558,6 @@ namespace admm {
 
 // ---- in-process multi-device mode of admm_hip_parlasso / admm_hip_parbp (PAR_DEVICES)
 namespace {
-// "0" / "" / unset: off (empty list).  "all": devices 0 .. device_count - 1.  Else a comma-separated list of device numbers
-// (repeats allowed: several ranks on one device -- the test / diagnostic form).
-std::vector<int> parse_par_devices(const char* v, int device_count) {
-    std::vector<int> out;
-    if (!v) return out;
-    const std::string s(v);
-    if (s.empty() || s == "0") return out;
-    if (s == "all") {
-        ADMM_REQUIRE(device_count >= 1, "PAR_DEVICES=all: no device");
-        for (int d = 0; d < device_count && d < 64; ++d) out.push_back(d);
-        return out;
-    }
-    size_t i = 0;
-    while (i <= s.size()) {
-        const size_t j = std::min(s.find(',', i), s.size());
-        const std::string item = s.substr(i, j - i);
-        ADMM_REQUIRE(!item.empty() && item.size() <= 4 && item.find_first_not_of("0123456789") == std::string::npos,
-                     "PAR_DEVICES must be 0, all, or a comma-separated list of device numbers (got '" + s + "')");
-        const int d = std::atoi(item.c_str());
-        ADMM_REQUIRE(d < device_count, "PAR_DEVICES lists device " + item + " but there are " + std::to_string(device_count) + " devices");
-        out.push_back(d);
-        ADMM_REQUIRE(out.size() <= 64, "PAR_DEVICES lists more than 64 ranks");
-        i = j + 1;
-    }
-    return out;
-}
 // rank r runs on devices[r] for r < the largest divisor of nblocks that is <= the number of listed devices (whole blocks per rank)
 std::vector<int> par_layout(int nblocks, const std::vector<int>& listed) {
     int nr = 1;
@@ -704,20 +640,20 @@ void run_inproc(const std::vector<int>& devices, int src_device, const std::func
     std::vector<int> sorted(devices);
     std::sort(sorted.begin(), sorted.end());
     const bool shared = std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end();
-    const OptMap opts = option_thread();
+    const ThreadOptions opts = thread_options();
     InprocGroup* g = comm_group_create(devices);
     std::vector<RankOutcome> out(nranks);
     for (int r = 0; r < nranks; ++r) {
         rank_worker(r).start([&, r]() {
-            option_thread() = opts;
-            if (shared) { option_set_thread("PEER_FUSED", "2"); option_set_thread("PAR_FUSE_PZ", "0"); }
+            thread_options() = opts;
+            if (shared) { opt_set_thread(Opt::PEER_FUSED, "2"); opt_set_thread(Opt::PAR_FUSE_PZ, "0"); }
             RankOutcome& o = out[r];
             t_defer = &o.frees;
             try {
                 ADMM_HIP_CHECK(hipSetDevice(devices[r]));
                 comm_group_attach(g, r);
-                const char* inj = option("TEST_PAR_FAIL_RANK");          // test hook: this rank fails on the host before its first exchange
-                if (inj && std::atoi(inj) == r) throw Error(ADMM_ERR_INTERNAL, "test: injected failure of rank " + std::to_string(r));
+                if (opt_int(Opt::TEST_PAR_FAIL_RANK, -1) == r)           // test hook: this rank fails on the host before its first exchange
+                    throw Error(ADMM_ERR_INTERNAL, "test: injected failure of rank " + std::to_string(r));
                 body(r, nranks);
             } catch (const Error& e) {
                 o.code = e.code; o.msg = e.what();
@@ -733,7 +669,7 @@ void run_inproc(const std::vector<int>& devices, int src_device, const std::func
             }
             comm_group_detach();
             t_defer = nullptr;
-            options_reset_thread();
+            thread_options() = ThreadOptions();
         });
     }
     for (int r = 0; r < nranks; ++r) rank_worker(r).wait();
@@ -752,7 +688,7 @@ void run_inproc(const std::vector<int>& devices, int src_device, const std::func
 
 // the ranks of a PAR_DEVICES call with `nblocks` blocks; empty: the single-device path
 std::vector<int> par_devices_for(int nblocks) {
-    const std::vector<int> listed = parse_par_devices(option("PAR_DEVICES"), admm_hip_device_count());
+    const std::vector<int> listed = parse_par_devices(opt_text(Opt::PAR_DEVICES), admm_hip_device_count());
     std::vector<int> lay = par_layout(nblocks, listed);
     if (lay.size() <= 1) lay.clear();
     return lay;
@@ -1159,66 +1095,63 @@ int admm_hip_options_default(admm_hip_options* o) {
         o->struct_size = (int)sizeof(*o);
     });
 }
-int admm_hip_options_reset(void) { return guarded([&] { options_reset_thread(); }); }
+int admm_hip_options_reset(void) { return guarded([&] { thread_options() = ThreadOptions(); }); }
 int admm_hip_option_set(const char* name, const char* value) {
     return guarded([&] {
         ADMM_REQUIRE(name != nullptr && name[0] != 0, "option name must not be empty");
-        std::string n(name);
-        if (n.rfind("ADMM_HIP_", 0) == 0) n = n.substr(9);
-        for (char& c : n) c = (char)std::toupper((unsigned char)c);
-        option_set_thread(n.c_str(), value);
+        Opt id;
+        ADMM_REQUIRE(opt_find(name, &id), std::string("unknown option '") + name + "' (INTEGRATION.md section 5 lists the names)");
+        opt_set_thread(id, value);
     });
 }
 const char* admm_hip_option_get(const char* name) {
-    if (!name) return nullptr;
-    std::string n(name);
-    if (n.rfind("ADMM_HIP_", 0) == 0) n = n.substr(9);
-    for (char& c : n) c = (char)std::toupper((unsigned char)c);
-    return option(n.c_str());
+    Opt id;
+    return name && opt_find(name, &id) ? opt_text(id) : nullptr;
 }
 int admm_hip_options_set(const admm_hip_options* o) {
     return guarded([&] {
-        options_reset_thread();
-        if (o == nullptr) return;
+        ThreadOptions n;                          // built aside: a refused field leaves the thread's settings as they were
+        if (o == nullptr) { thread_options() = n; return; }
         ADMM_REQUIRE(o->struct_size >= (int)(2 * sizeof(int)) && o->struct_size <= (int)sizeof(admm_hip_options), "options: bad struct_size");
         admm_hip_options v;
         std::memset(&v, 0, sizeof(v));
         std::memcpy(&v, o, (size_t)o->struct_size);
-        auto set = [](const char* k, const char* val) { option_set_thread(k, val); };
-        auto num = [](const char* k, int val) { option_set_thread(k, std::to_string(val).c_str()); };
-        if (v.gram_backend == 1) set("GRAM", "rocblas");
-        if (v.gram_split) { ADMM_REQUIRE(v.gram_split >= 1 && v.gram_split <= 3, "options: gram_split"); set("GRAM_SPLIT", v.gram_split == 1 ? "0" : (v.gram_split == 2 ? "f16x2" : "bf16x3")); }
-        if (v.factor_backend == 1) set("FACTOR", "rocsolver");
-        if (v.inverse_precision) { ADMM_REQUIRE(v.inverse_precision == 1 || v.inverse_precision == 2, "options: inverse_precision"); set("INVERSE", v.inverse_precision == 1 ? "f32" : "f64"); }
-        if (v.tall_xupdate) { ADMM_REQUIRE(v.tall_xupdate == 1 || v.tall_xupdate == 2, "options: tall_xupdate"); set("XUPDATE", v.tall_xupdate == 1 ? "gemv" : "sym"); }
-        if (v.tall_refine) set("REFINE", "1");
-        if (v.consensus_two_pass) set("PAR_ONEPASS", "0");
-        if (v.consensus_unfused >= 1) set("PAR_FUSE_PZ", "0");
-        if (v.consensus_unfused >= 2) set("PAR_BATCH", "0");
-        if (v.bp_two_pass) set("BP_ONEPASS", "0");
-        if (v.lad_no_hat) set("LAD_HAT", "0");
-        if (v.wide_no_persist == 1) set("WIDE_PERSIST", "0");
-        if (v.wide_no_persist == 2) set("WIDE_PERSIST_COLS", "0");
-        if (v.wide_unfused) set("WIDE_FUSE", "0");
-        if (v.wide_gram_sprad) set("WIDE_SPRAD", "gram");
-        if (v.sharing_bp_direct) set("SBP_GRAM", "0");
-        if (v.cv_downdate) set("CV_DOWNDATE", v.cv_downdate == 1 ? "1" : "0");
-        if (v.peer_exchange) set("PEER_FUSED", v.peer_exchange == 1 ? "2" : "0");
-        if (v.batch_iters > 0) num("BATCH_ITERS", v.batch_iters);
-        if (v.profile_stride > 0) num("PROFILE_STRIDE", v.profile_stride);
-        if (v.pool_mb) num("POOL_MB", v.pool_mb < 0 ? 0 : v.pool_mb);
-        if (v.lad_two_pass) set("LAD_ONEPASS", "0");
+        auto set = [&](Opt k, const char* val) { opt_parse(k, val, &n.v[(int)k]); n.has[(int)k] = true; };
+        auto num = [&](Opt k, int val) { set(k, std::to_string(val).c_str()); };
+        if (v.gram_backend == 1) set(Opt::GRAM, "rocblas");
+        if (v.gram_split) { ADMM_REQUIRE(v.gram_split >= 1 && v.gram_split <= 3, "options: gram_split"); set(Opt::GRAM_SPLIT, v.gram_split == 1 ? "0" : (v.gram_split == 2 ? "f16x2" : "bf16x3")); }
+        if (v.factor_backend == 1) set(Opt::FACTOR, "rocsolver");
+        if (v.inverse_precision) { ADMM_REQUIRE(v.inverse_precision == 1 || v.inverse_precision == 2, "options: inverse_precision"); set(Opt::INVERSE, v.inverse_precision == 1 ? "f32" : "f64"); }
+        if (v.tall_xupdate) { ADMM_REQUIRE(v.tall_xupdate == 1 || v.tall_xupdate == 2, "options: tall_xupdate"); set(Opt::XUPDATE, v.tall_xupdate == 1 ? "gemv" : "sym"); }
+        if (v.tall_refine) set(Opt::REFINE, "1");
+        if (v.consensus_two_pass) set(Opt::PAR_ONEPASS, "0");
+        if (v.consensus_unfused >= 1) set(Opt::PAR_FUSE_PZ, "0");
+        if (v.consensus_unfused >= 2) set(Opt::PAR_BATCH, "0");
+        if (v.bp_two_pass) set(Opt::BP_ONEPASS, "0");
+        if (v.lad_no_hat) set(Opt::LAD_HAT, "0");
+        if (v.wide_no_persist == 1) set(Opt::WIDE_PERSIST, "0");
+        if (v.wide_no_persist == 2) set(Opt::WIDE_PERSIST_COLS, "0");
+        if (v.wide_unfused) set(Opt::WIDE_FUSE, "0");
+        if (v.wide_gram_sprad) set(Opt::WIDE_SPRAD, "gram");
+        if (v.sharing_bp_direct) set(Opt::SBP_GRAM, "0");
+        if (v.cv_downdate) set(Opt::CV_DOWNDATE, v.cv_downdate == 1 ? "1" : "0");
+        if (v.peer_exchange) set(Opt::PEER_FUSED, v.peer_exchange == 1 ? "2" : "0");
+        if (v.batch_iters > 0) num(Opt::BATCH_ITERS, v.batch_iters);
+        if (v.profile_stride > 0) num(Opt::PROFILE_STRIDE, v.profile_stride);
+        if (v.pool_mb) num(Opt::POOL_MB, v.pool_mb < 0 ? 0 : v.pool_mb);
+        if (v.lad_two_pass) set(Opt::LAD_ONEPASS, "0");
         if (v.par_devices) {
             ADMM_REQUIRE(v.par_devices >= -1 && v.par_devices <= 64, "options: par_devices");
             std::string l;
             for (int d = 0; d < v.par_devices; ++d) l += (d ? "," : "") + std::to_string(d);
-            set("PAR_DEVICES", v.par_devices == -1 ? "all" : l.c_str());
+            set(Opt::PAR_DEVICES, v.par_devices == -1 ? "all" : l.c_str());
         }
         if (v.screen) {
             ADMM_REQUIRE(v.screen >= 1 && v.screen <= 3, "options: screen");
-            set("WIDE_SCREEN", v.screen == 1 ? "16" : (v.screen == 3 ? "8" : "0"));
-            set("SBP_SCREEN", v.screen == 2 ? "0" : "1");
+            set(Opt::WIDE_SCREEN, v.screen == 1 ? "16" : (v.screen == 3 ? "8" : "0"));
+            set(Opt::SBP_SCREEN, v.screen == 2 ? "0" : "1");
         }
+        thread_options() = n;
     });
 }
 int admm_hip_comm_unique_id(void* id_out) {

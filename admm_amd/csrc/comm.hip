@@ -36,12 +36,8 @@ constexpr size_t kDefaultSlotBytes = 4u << 20;        // payload capacity of one
 //              fits of imbalance BY DESIGN): RCCL would wait for ever there, so SHM / PEER wait long.
 //              ADMM_HIP_COMM_PATIENT_TIMEOUT_S (default one hour).
 // An exchange takes the bound in force when it is ENQUEUED (CommLockstep, comm.h).
-double env_seconds(const char* name, double dflt) {
-    if (const char* e = option(name)) { const double v = std::atof(e); if (v > 0.0) return v; }
-    return dflt;
-}
-double wait_seconds_lockstep() { return env_seconds("COMM_TIMEOUT_S", 20.0); }
-double wait_seconds_patient() { return env_seconds("COMM_PATIENT_TIMEOUT_S", 3600.0); }
+double wait_seconds_lockstep() { return opt_real(Opt::COMM_TIMEOUT_S, 20.0); }
+double wait_seconds_patient() { return opt_real(Opt::COMM_PATIENT_TIMEOUT_S, 3600.0); }
 
 struct PeerState {
     unsigned char* local = nullptr;                      // this rank's buffer
@@ -84,10 +80,7 @@ ncclComm_t g_comm = nullptr;
     } while (0)
 
 size_t slot_bytes_from_env() {
-    if (const char* e = option("COMM_SLOT_BYTES")) {
-        const long long v = std::atoll(e);
-        if (v >= 4096) return (size_t)v / 16 * 16;
-    }
+    if (opt_set(Opt::COMM_SLOT_BYTES)) return (size_t)opt_int(Opt::COMM_SLOT_BYTES, 0) / 16 * 16;
     return kDefaultSlotBytes;
 }
 
@@ -352,8 +345,7 @@ void peer_alloc_local(int nranks) {
     // below) order and publish plain accesses to it across agents, so stores arriving from a peer are never shadowed by
     // a stale line of this device's L2.  ADMM_HIP_PEER_MEM=uncached selects MTYPE UC instead (every access a memory
     // transaction of its own: measured 3-10x slower for the 80 KB payload; kept as the conservative fallback).
-    const char* pm = option("PEER_MEM");
-    const bool uncached = pm && std::string(pm) == "uncached";
+    const bool uncached = opt_is(Opt::PEER_MEM, "uncached");
     if (hipExtMallocWithFlags(&ptr, C().peer.bytes, uncached ? hipDeviceMallocUncached : hipDeviceMallocFinegrained) != hipSuccess) {
         (void)hipGetLastError();
         pool_trim();                                          // the cache of released device blocks must never starve this allocation

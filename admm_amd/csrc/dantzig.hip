@@ -161,12 +161,6 @@ dz_tail_kernel(DzParams q, int par) {
     }
 }
 
-static int dz_batch() {
-    const char* e = option("BATCH_ITERS");
-    const int v = e ? std::atoi(e) : 0;
-    return v > 0 ? (v + 1) / 2 * 2 : 16;
-}
-
 // d: the standardised data (DataStd<double>, Dantzig.cpp:52-55).  pb: lambda grid / options.  res.beta: (p + 1) x nlambda doubles.
 void solve_dantzig(DeviceData<double>& d, const LassoProblem& pb, DantzigResult& res, hipStream_t st) {
     const int n = d.n, p = d.p;
@@ -254,7 +248,7 @@ void solve_dantzig(DeviceData<double>& d, const LassoProblem& pb, DantzigResult&
 
     ADMM_HIP_CHECK(hipStreamSynchronize(st));
     const int* skip = ddone.get();
-    LoopTimes lt = run_until_done(st, ddone.get(), dz_batch(), (long long)pb.opts.maxit * nlam + 2 * nlam + 2, [&](long long g) {
+    LoopTimes lt = run_until_done(st, ddone.get(), batch_iters((int)opt_int(Opt::BATCH_ITERS, 0), 16), (long long)pb.opts.maxit * nlam + 2 * nlam + 2, [&](long long g) {
         const int par = (int)(g & 1);
         hipLaunchKernelGGL(dz_head_kernel, dim3(nwg), dim3(kDzThreads), 0, st, q, par);
         amult(rhs.get(), vec.get(), skip);

@@ -463,12 +463,6 @@ struct DenseLoop {
     }
 };
 
-int env_batch(int dflt) {
-    const char* v = option("BATCH_ITERS");
-    int b = v ? std::atoi(v) : dflt;
-    if (b <= 0) b = dflt;
-    return (b + 1) / 2 * 2;
-}
 
 }  // namespace
 
@@ -490,21 +484,6 @@ static void dense_collect_trace(DenseLoop& L, const DenseCtl& fc, DenseResult& r
         res.state_dim = L.q.dim;
         res.state.resize((size_t)ns * 5 * L.q.dim);
         if (ns > 0) read_back(res.state.data(), L.state.get(), res.state.size() * sizeof(double), st);
-        if (ns > 0 && option("DEBUG_REREAD")) {
-            // diagnosis of profiles/r04_transient_stale_lines.md: the dump above came through read_back()'s pinned bounce buffer.  Read the
-            // same device memory again through the pinned path and through the runtime's pageable hipMemcpy, and report which differs.
-            std::vector<double> pinned2(res.state.size()), pageable(res.state.size());
-            read_back(pinned2.data(), L.state.get(), pinned2.size() * sizeof(double), st);
-            ADMM_HIP_CHECK(hipMemcpy(pageable.data(), L.state.get(), pageable.size() * sizeof(double), hipMemcpyDeviceToHost));
-            size_t d12 = 0, d13 = 0, first12 = 0, first13 = 0;
-            for (size_t i = 0; i < pinned2.size(); ++i) {
-                if (std::memcmp(&pinned2[i], &res.state[i], 8) != 0) { if (!d12) first12 = i; ++d12; }
-                if (std::memcmp(&pageable[i], &res.state[i], 8) != 0) { if (!d13) first13 = i; ++d13; }
-            }
-            if (d12 || d13)
-                std::fprintf(stderr, "[admm_hip reread] dump of %zu doubles (dim %d): second pinned read differs in %zu entries (first at %zu), pageable hipMemcpy differs in %zu (first at %zu)\n",
-                             pinned2.size(), L.q.dim, d12, first12, d13, first13);
-        }
     }
 }
 
@@ -522,7 +501,7 @@ void solve_lad(const DeviceData<double>& d, const admm_opts& opts, DenseResult& 
     t0 = now_s();
     // n <= 2000: the hat-matrix branch below also needs the Cholesky factor of the same Gram matrix: keep a copy
     bool hat = n <= 2000;
-    if (const char* e = option("LAD_HAT")) hat = hat && std::string(e) != "0";
+    if (opt_off(Opt::LAD_HAT)) hat = false;
     DevBuf<double> G2;
     if (hat) {
         G2.alloc((size_t)ldp * ldp);
@@ -544,7 +523,7 @@ void solve_lad(const DeviceData<double>& d, const admm_opts& opts, DenseResult& 
     // general branch, one-pass form (DenseParams::lp): X streamed once per iteration by rows.  LAD_ONEPASS=0: the reference's two products.
     constexpr int kLadMaxCols = 2 * kLadThreads * 6;             // 6144 columns: six double2 per thread and row (more would spill)
     bool onepass = !hat && p <= kLadMaxCols;
-    if (const char* e = option("LAD_ONEPASS")) onepass = onepass && std::string(e) != "0";
+    if (opt_off(Opt::LAD_ONEPASS)) onepass = false;
     const int lad_nwg = std::max(1, std::min(device_info().num_cu, (n + 2 * kLadRows - 1) / (2 * kLadRows)));
     const int lad_rows = (int)round_up((n + lad_nwg - 1) / lad_nwg, kLadRows);
 
@@ -610,7 +589,7 @@ void solve_lad(const DeviceData<double>& d, const admm_opts& opts, DenseResult& 
     };
 
     const int* skip = L.done.get();
-    LoopTimes lt = run_until_done(st, skip, env_batch(8), (long long)opts.maxit + 2, [&](long long g) {
+    LoopTimes lt = run_until_done(st, skip, batch_iters((int)opt_int(Opt::BATCH_ITERS, 0), 8), (long long)opts.maxit + 2, [&](long long g) {
         L.head(g, st);
         if (hat) {
             gH.run_partials(L.vec.get(), skip, st);          // dsymv(H, vec)
@@ -664,8 +643,7 @@ void solve_bp(const DeviceData<double>& d, const admm_opts& opts, DenseResult& r
     DevBuf<double> w0(d.ldx); w0.zero(st);
     const long long ldbt = round_up(p, 32);
     DevBuf<double> Bt((size_t)ldbt * n); Bt.zero(st);
-    const char* efac = option("FACTOR");
-    if (efac && std::string(efac) == "rocsolver") {
+    if (opt_is(Opt::FACTOR, "rocsolver")) {
         cholesky_lower<double>(G.get(), ldn, n, st);
         ADMM_HIP_CHECK(hipMemcpyAsync(B.get(), d.X.get(), (size_t)d.ldx * p * sizeof(double), hipMemcpyDeviceToDevice, st));
         trsm_left_lower<double>(G.get(), ldn, n, B.get(), d.ldx, p, st);
@@ -696,8 +674,7 @@ void solve_bp(const DeviceData<double>& d, const admm_opts& opts, DenseResult& r
     // One-pass form (default; ADMM_HIP_BP_ONEPASS=0 keeps the two streaming products of ADMMBP.h:65-66): only B' w streams per
     // iteration, B vec comes from n-sized recurrences + a gather over the non-zeros of z (DenseParams), and the second stored
     // layout of B (its transpose, another 8np bytes) is a setup temporary.
-    bool onepass = true;
-    if (const char* e = option("BP_ONEPASS")) onepass = std::string(e) != "0";
+    const bool onepass = !opt_off(Opt::BP_ONEPASS);
     GemvT<double> gB, gBt;                       // t = B' w (p outputs) ; w = B vec (n outputs, via the stored transpose)
     gB.init(B.get(), d.ldx, n, p);
     if (!onepass) gBt.init(Bt.get(), ldbt, p, n);
@@ -727,7 +704,7 @@ void solve_bp(const DeviceData<double>& d, const admm_opts& opts, DenseResult& r
     }
 
     const int* skip = L.done.get();
-    LoopTimes lt = run_until_done(st, skip, env_batch(8), (long long)opts.maxit + 2, [&](long long g) {
+    LoopTimes lt = run_until_done(st, skip, batch_iters((int)opt_int(Opt::BATCH_ITERS, 0), 8), (long long)opts.maxit + 2, [&](long long g) {
         L.head(g, st);
         if (onepass) {
             gB.run_partials(L.q.w, skip, st);               // B' w, w = B vec from the recurrences   (mat_vec_tprod, ADMMBP.h:66)

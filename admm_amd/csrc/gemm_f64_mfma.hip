@@ -288,7 +288,6 @@ void gram_mfma_f64(const double* A, long long lda, int rows, int cols, bool atA,
         const double cost = (double)((tiles * c + slots - 1) / slots) / c;
         if (cost < best * 0.93) { best = cost; S = c; }
     }
-    if (const char* e = option("GRAM64_KSPLIT")) { const int v = std::atoi(e); if (v >= 1 && v <= 8) S = v; }
     if (S == 1) {
         launch_gemm_nt_f64(true, Z.get(), ldz, Z.get(), ldz, C, ldc, M, M, K, 1.0, 0.0, true, false, st, false);
     } else {

@@ -516,11 +516,8 @@ colscale_kernel(const float* __restrict__ X, long long ldx, int rows, float* __r
 }
 
 int gram_split_mode() {
-    const char* e = option("GRAM_SPLIT");       // read per call (the A/B tests flip it inside one process)
-    if (e == nullptr) return 2;
-    const std::string v(e);
-    if (v == "0" || v == "fp32") return 0;
-    if (v == "bf16x3") return 3;
+    if (opt_is(Opt::GRAM_SPLIT, "0")) return 0;       // read per call (the A/B tests flip it inside one process)
+    if (opt_is(Opt::GRAM_SPLIT, "bf16x3")) return 3;
     return 2;
 }
 
@@ -565,8 +562,7 @@ static void launch_gram_b3(const GramSplit3& z, int ioff, int joff, float* C, lo
     // apart in K inside one long launch -- at 2.7 x the fp32 kernel's pace the operand over-fetch (57-fold there) is what the launch
     // waits for -- and start together again with every launch.  ADMM_HIP_GRAM_B3_KTILES=<K tiles per launch> (A/B; 0 = one launch).
     const int nkt = g.K / GB_BK;
-    int per_launch = 516;
-    if (const char* e = option("GRAM_B3_KTILES")) per_launch = std::atoi(e);
+    int per_launch = (int)opt_int(Opt::GRAM_B3_KTILES, 516);
     if (per_launch <= 0) per_launch = nkt;
     per_launch = (per_launch + 5) / 6 * 6;
     for (int kt = 0; kt < nkt; kt += per_launch) {

@@ -502,11 +502,11 @@ struct TallPlan final : LassoPlan {
             size_t free_b = 0, total_b = 0;
             ADMM_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
             free_b += pool_cached_bytes();                        // blocks this library holds for re-use are free for it
-            if (const char* e = option("TEST_FREE_BYTES")) free_b = (size_t)std::atoll(e);
+            if (opt_set(Opt::TEST_FREE_BYTES)) free_b = (size_t)opt_int(Opt::TEST_FREE_BYTES, 0);
             const bool have_gram = d.gram.get() && d.ldgram == ldp;
-            const bool inv64_wanted = p < 4096 || (option("INVERSE") && std::string(option("INVERSE")) == "f64");
+            const bool inv64_wanted = p < 4096 || opt_is(Opt::INVERSE, "f64");
             const double mat = (double)ldp * (double)ldp * 4.0;
-            const double need = (have_gram ? 0.0 : mat) + (inv64_wanted ? 2.0 * mat : 0.5 * mat) + (option("REFINE") ? mat : 0.0) +
+            const double need = (have_gram ? 0.0 : mat) + (inv64_wanted ? 2.0 * mat : 0.5 * mat) + (opt_on(Opt::REFINE) ? mat : 0.0) +
                                 (shard && ci.nranks > 1 ? mat + mat / ci.nranks : 0.0);      // packed send / receive buffers of the Gram's reduce-scatter
             if (need > 0.97 * (double)free_b) {
                 char msg[320];
@@ -529,9 +529,9 @@ struct TallPlan final : LassoPlan {
         }
         // Row-sharded solver: decided here because it chooses how the split-K Gram is reduced (below)
         bool inv64 = p < 4096;
-        if (const char* e = option("INVERSE")) inv64 = std::string(e) == "f64";
+        if (opt_set(Opt::INVERSE)) inv64 = opt_is(Opt::INVERSE, "f64");
         bool dist_factor = shard && ci.nranks > 1 && !inv64 && (p + 127) / 128 >= 2 * ci.nranks && p >= 256;
-        if (const char* e = option("DIST_FACTOR")) dist_factor = dist_factor && std::string(e) != "0";
+        if (opt_off(Opt::DIST_FACTOR)) dist_factor = false;
 
         // rho (ADMMLassoTall.h:194-202)
         rho = pb.opts.rho;
@@ -601,7 +601,7 @@ struct TallPlan final : LassoPlan {
         // from the float system M = X'X + rho I (the reference's: XX.diagonal() += rho in float, ADMMLassoTall.h:204) -- the
         // x-update's error against the exact solve of that system drops from cond(M) ulps to about one ulp, i.e. onto what
         // oracle/variants.py calls the `exact` variant, at three passes over the triangle per iteration instead of one.
-        if (const char* e = option("REFINE")) refine = std::string(e) == "1" && !shard;
+        refine = opt_on(Opt::REFINE) && !shard;
         if (refine) {
             Mg.alloc((size_t)ldp * ldp);
             ADMM_HIP_CHECK(hipMemcpyAsync(Mg.get(), M.get(), (size_t)ldp * ldp * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -641,9 +641,9 @@ struct TallPlan final : LassoPlan {
 
         // ---- loop state
         // x-update variant: lower-triangle symmetric mat-vec (2p^2 bytes) for large p, full-matrix
-        // gemv_t (4p^2 bytes, fewer and larger workgroups) for small p.  ADMM_HIP_XUPDATE=full|sym overrides.
+        // gemv_t (4p^2 bytes, fewer and larger workgroups) for small p.  ADMM_HIP_XUPDATE=sym|gemv|full overrides.
         use_sym = p >= 2048;
-        if (const char* e = option("XUPDATE")) use_sym = std::string(e) == "sym";
+        if (opt_set(Opt::XUPDATE)) use_sym = opt_is(Opt::XUPDATE, "sym");
         if (refine) use_sym = true;                      // the refinement is built on the symmetric kernel's partial layout
         if (shard) use_sym = true;                       // the sharded x-update is the tile list of the symmetric kernel dealt out to the ranks
         pl = plan_gemv_t<float>(p, p, 2, 4);
@@ -661,14 +661,14 @@ struct TallPlan final : LassoPlan {
         else if (!use_sym) { a_part.alloc((size_t)pl.nseg * ldp); b_part.alloc((size_t)pl.nseg * ldp); a_part.zero(st); b_part.zero(st); }
         // ADMM_HIP_PEER_FUSED=0: go through the generic all-reduce of the exchange layer also on the PEER backend
         peer_fused = shard && ci.backend == COMM_PEER;
-        if (const char* e = option("PEER_FUSED")) { if (std::string(e) == "0") peer_fused = false; }
+        if (opt_is(Opt::PEER_FUSED, "0")) peer_fused = false;
         if (peer_fused) {
             // one launch only when the whole grid is resident with room to spare (its workgroups wait for one another)
             int occ = 0;
             ADMM_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void*>(tall_tail_kernel<TAIL_PEER1>), kTailThreads, 0));
             const int nwg_tail = (p + kTailElems - 1) / kTailElems;
             peer_one = (long long)nwg_tail * 2 <= resident_workgroups(occ);
-            if (const char* e = option("PEER_FUSED")) { if (std::string(e) == "2") peer_one = false; }
+            if (opt_is(Opt::PEER_FUSED, "2")) peer_one = false;
         }
         // (A single-launch iteration -- tail, decision and tiles in one launch -- and a hipGraph replay of the batch were built, measured
         // bit-identical and SLOWER on C2 in rounds 4 / 5 (44.5 and 46.9 us per iteration against 42.1 / 46.6): removed in round 6,
@@ -737,20 +737,8 @@ struct TallPlan final : LassoPlan {
         ADMM_HIP_CHECK(hipMemcpy2D(out, (size_t)ld * sizeof(float), Mg.get(), (size_t)ldp * sizeof(float), (size_t)p * sizeof(float), (size_t)p, hipMemcpyDeviceToHost));
     }
 
-    void debug_dump(const char* tag, const float* dptr, size_t n) {
-        std::vector<float> h(n);
-        ADMM_HIP_CHECK(hipMemcpy(h.data(), dptr, n * sizeof(float), hipMemcpyDeviceToHost));
-        size_t bad = 0; double mx = 0;
-        for (size_t k = 0; k < n; ++k) { const float v = h[k]; if (!(v == v) || std::fabs(v) > 1e30f) { if (bad < 4) fprintf(stderr, "[dbg]   %s[%zu] = %g\n", tag, k, (double)v); ++bad; } else mx = std::max(mx, (double)std::fabs(v)); }
-        fprintf(stderr, "[dbg] %-8s n=%zu nonfinite=%zu max|.|=%g\n", tag, n, bad, mx);
-    }
-
     // One warm-started lambda path from a cold start (init at the first lambda, init_warm after).
     void run(LassoResult& res) override {
-        if (option("DEBUG_DUMP")) {
-            if (M.get()) debug_dump("M", M.get(), (size_t)ldp * ldp);
-            debug_dump("XY", XY.get(), ldp);
-        }
         admm_stats S = setup_stats;
         S.xupdate_variant = shard ? 2 : (use_sym ? 1 : 0);
         S.exchange_variant = !shard ? 0 : (!peer_fused ? 1 : (peer_one ? 3 : 2));
@@ -768,7 +756,7 @@ struct TallPlan final : LassoPlan {
         sy.probe_idx = 0;
 #endif
 
-        const int batch = pb.batch_iters > 0 ? (pb.batch_iters + 1) / 2 * 2 : 32;    // even
+        const int batch = batch_iters(pb.batch_iters, 32);
         const int stride = pb.profile_stride;                          // sample every stride-th x-update with events
         size_t nev = 0;                                                // events of ev_pool used by this run
         Event ev_loop0, ev_loop1, ev_poll[2];
@@ -861,7 +849,7 @@ struct TallPlan final : LassoPlan {
         S.t_loop = now_s() - tl0;
         ADMM_HIP_CHECK(hipMemcpy(hctl, ctl.get(), 2 * sizeof(TallCtl), hipMemcpyDeviceToHost));      // both slots: decisions taken
 #ifdef ADMM_HIP_PROBE
-        if (const char* f = option("PROBE_OUT")) {
+        if (const char* f = opt_text(Opt::PROBE_OUT)) {
             std::vector<long long> hp((size_t)4096 * 4 * 8);
             ADMM_HIP_CHECK(hipMemcpy(hp.data(), probe.get(), hp.size() * sizeof(long long), hipMemcpyDeviceToHost));
             if (FILE* fp = std::fopen(f, "wb")) { std::fwrite(hp.data(), sizeof(long long), hp.size(), fp); std::fclose(fp); }
@@ -880,16 +868,6 @@ struct TallPlan final : LassoPlan {
             }
             S.xupdate_samples = (long long)(nev / 2);
             S.xupdate_ms_avg = tot / (double)(nev / 2);
-        }
-
-        if (option("DEBUG_DUMP")) {
-            debug_dump("x", x.get(), ldv); debug_dump("u", u.get(), ldv); debug_dump("w", w.get(), ldv);
-            debug_dump("z0", z0.get(), ldv); debug_dump("y0", y0.get(), ldv);
-            if (!use_sym) { debug_dump("a_part", a_part.get(), (size_t)pl.nseg * ldp); debug_dump("b_part", b_part.get(), (size_t)pl.nseg * ldp); }
-            std::vector<double> hp((size_t)2 * nwg * 8);
-            ADMM_HIP_CHECK(hipMemcpy(hp.data(), P.get(), hp.size() * sizeof(double), hipMemcpyDeviceToHost));
-            for (size_t k = 0; k < hp.size() && k < 16; ++k) fprintf(stderr, "[dbg] P[%zu]=%g\n", k, hp[k]);
-            fprintf(stderr, "[dbg] nseg=%d nwg=%d ldp=%lld ldv=%lld\n", pl.nseg, nwg, ldp, ldv);
         }
 
         // ---- results: niter, beta on the original scale (DataStd::recover, Lasso.cpp:108-111)

@@ -1912,7 +1912,7 @@ struct WidePlan final : LassoPlan {
         cshard = pb.p_total > 0;
         ci = cshard ? comm_info() : CommInfo();
         peer_fused = cshard && ci.backend == COMM_PEER;
-        if (const char* e = option("PEER_FUSED")) { if (std::string(e) == "0") peer_fused = false; }
+        if (opt_is(Opt::PEER_FUSED, "0")) peer_fused = false;
         p_total = cshard ? pb.p_total : p; col_offset = cshard ? pb.col_offset : 0;
         admm_stats& S = setup_stats;
         S.branch = 1; S.t_h2d = d.t_h2d; S.t_standardize = d.t_std;
@@ -1942,7 +1942,7 @@ struct WidePlan final : LassoPlan {
         // n x n matrix once instead of exchanging a p-vector per product).
         double t0 = now_s();
         bool gram_free = !cshard;
-        if (const char* e = option("WIDE_SPRAD")) gram_free = !cshard && std::string(e) != "gram";
+        if (opt_is(Opt::WIDE_SPRAD, "gram")) gram_free = false;
         if (gram_free) {
             GramFreeWideOp op(d.X.get(), d.ldx, n, p, st);
             comm_stream_sync(st);
@@ -1978,13 +1978,13 @@ struct WidePlan final : LassoPlan {
             int occ = 0;
             ADMM_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void*>(wide_tail_kernel<2>), kWideThreads, 0));
             peer_one = (long long)nwg_tail * 2 <= resident_workgroups(occ);
-            if (const char* e = option("PEER_FUSED")) { if (std::string(e) == "2") peer_one = false; }
+            if (opt_is(Opt::PEER_FUSED, "2")) peer_one = false;
         }
         x.alloc(ldp); x.zero(st);
         for (DevBuf<float>* b : {&Ax, &z, &y}) { b->alloc(std::max<long long>(ldn, 8192)); b->zero(st); }   // the fused x-update reads up to 32 x 256 entries unconditionally
         // ADMM_HIP_WIDE_FUSE=0: always three launches per iteration
         fuse_rt = n <= 1024 ? 4 : (n <= 2048 ? 8 : (n <= 4096 ? 16 : (n <= 6144 ? 24 : (n <= 8192 ? 32 : 0))));
-        if (const char* e = option("WIDE_FUSE")) if (std::string(e) == "0") fuse_rt = 0;
+        if (opt_off(Opt::WIDE_FUSE)) fuse_rt = 0;
         lds_x = std::max((size_t)((n + 255) / 256 * 256) * 2 * sizeof(float), (size_t)std::min(std::max(fuse_rt, 4), 8) * kWideThreads * sizeof(float4));
         // The x-update stages t and t / gamma (2 n floats) in dynamic LDS: up to 64 KB by default, up to the device's
         // opt-in limit (160 KB on gfx950) after raising the kernel's attribute; beyond that (n > ~20 000) t goes through
@@ -1997,11 +1997,11 @@ struct WidePlan final : LassoPlan {
                 t_global = true;
             }
         }
-        if (const char* e = option("WIDE_TGLOBAL")) if (std::string(e) == "1") t_global = true;
+        if (opt_on(Opt::WIDE_TGLOBAL)) t_global = true;
         if (t_global) { fuse_rt = 0; lds_x = 0; tbuf.alloc(ldn); tbuf.zero(st); }
         // grid of the x-update launch: exactly ONE resident round of workgroups (a regular step streams all of X; a
         // partial second round runs at a fraction of the occupancy: 342 us instead of 280 us at C3 with 4 per CU
-        // when 3 fit).  ADMM_HIP_WIDE_WGX overrides the workgroups per CU.
+        // when 3 fit).
         int wgx = 0;
         {
             const void* fn = fuse_rt == 4 ? reinterpret_cast<const void*>(wide_x_kernel<4>)
@@ -2014,7 +2014,6 @@ struct WidePlan final : LassoPlan {
             ADMM_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgx, fn, kWideThreads, lds_x));
             wgx = std::max(1, std::min(wgx, 4));
         }
-        if (const char* e = option("WIDE_WGX")) wgx = std::max(1, std::atoi(e));
         nwg_x = std::max(wgx * device_info().num_cu, kActWG);
         axpart.alloc((size_t)(fuse_rt ? nwg_x : kAxWG) * ldn); axpart.zero(st);
         beta.alloc((size_t)nlam * p); niter.alloc(nlam); done.alloc(1); dlam.alloc(nlam);
@@ -2043,14 +2042,14 @@ struct WidePlan final : LassoPlan {
     }
 
     // Safe screening of the regular steps (wide_x_kernel): worth its copy when X is a stream from HBM at all (beyond the Infinity Cache
-    // the regular step is bandwidth, below it launch latency).  WIDE_SCREEN = 0 never, 1 / 16 the fp16 copy, 8 the 8-bit code, auto = the default's choice at any size (tests);
+    // the regular step is bandwidth, below it launch latency).  WIDE_SCREEN = 0 never, 16 the fp16 copy, 8 the 8-bit code, auto = the default's choice at any size (tests);
     // default: the 8-bit code when its bounds are tight enough on these columns (wide_screen_rate8_kernel: mean r_j <= 0.6), else
     // fp16.  When the copy does not fit the device the solver simply runs unscreened.
     void setup_screen() {
         const size_t xbytes = (size_t)d.ldx * (size_t)p * sizeof(float);
         if (fuse_rt == 0) return;
         int fmt = xbytes >= ((size_t)256 << 20) ? -1 : 0;                // -1: choose
-        if (const char* e = option("WIDE_SCREEN")) { const int v = std::atoi(e); fmt = std::string(e) == "auto" ? -1 : (v == 0 ? 0 : (v == 8 ? 8 : 16)); }
+        if (opt_set(Opt::WIDE_SCREEN)) fmt = opt_is(Opt::WIDE_SCREEN, "auto") ? -1 : std::atoi(opt_text(Opt::WIDE_SCREEN));
         if (fmt == 0 || d.ldx % 16 != 0) return;
         if (fmt < 0) {
             const int nb = (p + 3) / 4;
@@ -2076,8 +2075,7 @@ struct WidePlan final : LassoPlan {
             return;
         }
         scr_s.zero(st);
-        double loosen = 1.0;                                          // WIDE_SCREEN_SLACK >= 1: bounds that much looser (what a coarser copy would cost in exact steps; diagnosis)
-        if (const char* e = option("WIDE_SCREEN_SLACK")) loosen = std::max(1.0, std::atof(e));
+        const double loosen = 1.0;                                    // factor on every bound (the kernels' argument)
         if (fmt == 8) {
             scr_scale.zero(st);
             hipLaunchKernelGGL(wide_screen_prep8_kernel, dim3((unsigned)((p + 3) / 4)), dim3(256), 0, st, d.X.get(), d.ldx, n, p,
@@ -2087,7 +2085,7 @@ struct WidePlan final : LassoPlan {
                                reinterpret_cast<unsigned short*>(Xh.get()), ldh, scr_s.get(), NW, S, loosen);
         }
         q.Xh = Xh.get(); q.ldh = ldh; q.scr_fmt = fmt; q.scr_s = scr_s.get(); q.scr_S = S; q.scr_scale = scr_scale.get();
-        if (option("WIDE_SCREEN_STATS")) { scr_stat.alloc(2); scr_stat.zero(st); q.scr_stat = scr_stat.get(); }
+        if (opt_on(Opt::WIDE_SCREEN_STATS)) { scr_stat.alloc(2); scr_stat.zero(st); q.scr_stat = scr_stat.get(); }
         screened = true; screen_fmt = fmt;
     }
 
@@ -2105,12 +2103,12 @@ struct WidePlan final : LassoPlan {
         // and the host shared-memory back-end cannot do); ADMM_HIP_WIDE_PERSIST_COLS=0 switches it off there alone
         persist_rows = (!cshard || (peer_fused && ci.nranks <= 64)) && n <= kRRS * kRG && (long long)p <= 262144;
         static_assert(kRRS * kRG <= kAuxRows && kRG <= kAuxGroups, "the AUX region carries one float per row, one flag per row group");
-        if (cshard) if (const char* e = option("WIDE_PERSIST_COLS")) if (std::string(e) == "0") persist_rows = false;
-        if (const char* e = option("WIDE_PERSIST")) if (std::string(e) == "0") persist_rows = false;
+        if (cshard && opt_off(Opt::WIDE_PERSIST_COLS)) persist_rows = false;
+        if (opt_off(Opt::WIDE_PERSIST)) persist_rows = false;
         if (!persist_rows) return;
         rows_R = (n + kRRS - 1) / kRRS;                                     // row groups of 256 rows
         rows_C = std::max(1, kRG / rows_R);                                 // column groups: R C <= 32 workgroups (one XCD)
-        if (const char* e = option("WIDE_ROWS_C")) { const int c = std::atoi(e); if (c >= 1 && c * rows_R <= kRG) rows_C = c; }
+        if (const int c = (int)opt_int(Opt::WIDE_ROWS_C, 0)) { if (c * rows_R <= kRG) rows_C = c; }
         rows_G = rows_R * rows_C;
         rflags.alloc((size_t)3 * kRG * 8); rflags.zero(st);
         rpd.alloc((size_t)2 * rows_G * kRCMAX); rpd.zero(st);
@@ -2125,7 +2123,7 @@ struct WidePlan final : LassoPlan {
         WideRows ps;
         ps.flag = rflags.get(); ps.flagX = rflags.get() + (size_t)kRG * 8; ps.flagS = rflags.get() + (size_t)2 * kRG * 8;
         ps.pd = rpd.get(); ps.np = rnp.get(); ps.err = rerr.get(); ps.seq = ++rseq; ps.stat = rstat.get(); ps.hint = rhint.get();
-        ps.G = rows_G; ps.R = rows_R; ps.C = rows_C; ps.pa = rpa.get(); ps.diag = option("WIDE_PERSIST_STATS") ? 1 : 0;
+        ps.G = rows_G; ps.R = rows_R; ps.C = rows_C; ps.pa = rpa.get(); ps.diag = opt_on(Opt::WIDE_PERSIST_STATS) ? 1 : 0;
         ps.lst_idx = rli.get(); ps.lst_x = rlx.get(); ps.lcount = rlc.get();
         if (cshard) hipLaunchKernelGGL(wide_rows_persist_kernel<true>, dim3(8 * rows_G), dim3(kRNW * 64), 0, st, q, cpar, ps, comm_peer_aux());
         else hipLaunchKernelGGL(wide_rows_persist_kernel<false>, dim3(8 * rows_G), dim3(kRNW * 64), 0, st, q, cpar, ps, PeerAux{});
@@ -2142,7 +2140,7 @@ struct WidePlan final : LassoPlan {
         if (q.state != nullptr) ADMM_HIP_CHECK(hipMemsetAsync(state.get(), 0, state.n * sizeof(float), st));
         const int init_n = std::max(std::max(n, p), nwg_tail * 8);
         hipLaunchKernelGGL(wide_init_kernel, dim3((init_n + 255) / 256), dim3(256), 0, st, q, rho0, lam_int[0]);
-        const int batch = pb.batch_iters > 0 ? (pb.batch_iters + 1) / 2 * 2 : 16;
+        const int batch = batch_iters(pb.batch_iters, 16);
         LoopTimes lt = run_until_done(st, done.get(), batch, (long long)nlam * ((long long)pb.opts.maxit + 2) + 4, [&](long long g) {
             const int par = (int)(g & 1);
             switch (fuse_rt) {
@@ -2210,7 +2208,7 @@ struct WidePlan final : LassoPlan {
             ADMM_HIP_CHECK(hipMemcpy(hs, rstat.get(), sizeof(hs), hipMemcpyDeviceToHost));
             S.persist_iter = (long long)hs[0];
             rstat.zero(st);
-            if (option("WIDE_PERSIST_STATS"))
+            if (opt_on(Opt::WIDE_PERSIST_STATS))
             {
                 const double it = hs[0] ? (double)hs[0] : 1.0;
                 std::fprintf(stderr, "[wide rows persist] %llu iterations in %llu stretches (%llu not on one XCD, %llu extra hand-overs after a rho change), %.2f us per iteration inside; %d row groups x %d column groups\n"
@@ -2220,7 +2218,7 @@ struct WidePlan final : LassoPlan {
             }
         }
 #ifdef ADMM_HIP_PROBE
-        if (const char* f = option("PROBE_OUT")) {
+        if (const char* f = opt_text(Opt::PROBE_OUT)) {
             std::vector<long long> hp((size_t)4096 * 4 * 8);
             ADMM_HIP_CHECK(hipMemcpy(hp.data(), probe.get(), hp.size() * sizeof(long long), hipMemcpyDeviceToHost));
             if (FILE* fp = std::fopen(f, "wb")) { std::fwrite(hp.data(), sizeof(long long), hp.size(), fp); std::fclose(fp); }

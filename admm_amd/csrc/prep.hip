@@ -47,7 +47,7 @@ TraceRange::TraceRange(const char* name) : on(roctx().push != nullptr) { if (on)
 TraceRange::~TraceRange() { if (on) (void)roctx().pop(); }
 
 long long resident_workgroups(int occupancy_per_cu) {
-    if (const char* e = option("TEST_RESIDENT_WGS")) { const long long v = std::atoll(e); if (v >= 0) return v; }
+    if (opt_set(Opt::TEST_RESIDENT_WGS)) return opt_int(Opt::TEST_RESIDENT_WGS, 0);
     return (long long)occupancy_per_cu * device_info().num_cu;
 }
 
@@ -320,7 +320,6 @@ H2DRing& h2d_ring() {
     return *r;
 }
 int h2d_threads() {
-    if (const char* e = option("H2D_THREADS")) { const int v = std::atoi(e); if (v >= 1) return std::min(v, 32); }
     static const int n = []() {
         const unsigned hw = std::thread::hardware_concurrency();
         return (int)std::max(1u, std::min(16u, hw ? hw / 2 : 4u));      // C2 host input on the 128-thread box: 8 threads 50 GB/s, 16 threads 56 GB/s = the pageable hipMemcpy's rate
@@ -343,9 +342,7 @@ void parallel_memcpy(char* dst, const char* src, size_t bytes, int nthreads) {
 
 void write_device(void* dst, const void* src, size_t bytes) {
     if (!bytes) return;
-    const char* h2d = option("H2D");
-    const bool pageable = h2d && std::string(h2d) == "pageable";
-    if (pageable) { ADMM_HIP_CHECK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice)); return; }
+    if (opt_is(Opt::H2D, "pageable")) { ADMM_HIP_CHECK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice)); return; }
     if (bytes < (size_t(4) << 20)) { ADMM_HIP_CHECK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice)); return; }      // (a y vector, a lambda grid: no ring for those)
     H2DRing& r = h2d_ring();
     const int nt = h2d_threads();
@@ -370,9 +367,7 @@ void write_device(void* dst, const void* src, size_t bytes) {
 void write_device_cols(double* dst, const double* src, size_t rows, size_t ld, size_t ncols) {
     const size_t col_bytes = rows * sizeof(double);
     if (ld == rows) { write_device(dst, src, col_bytes * ncols); return; }
-    const char* h2d = option("H2D");
-    const bool pageable = h2d && std::string(h2d) == "pageable";
-    if (pageable || col_bytes * ncols < (size_t(4) << 20)) {
+    if (opt_is(Opt::H2D, "pageable") || col_bytes * ncols < (size_t(4) << 20)) {
         ADMM_HIP_CHECK(hipMemcpy2D(dst, col_bytes, src, ld * sizeof(double), col_bytes, ncols, hipMemcpyHostToDevice));
         return;
     }
@@ -430,7 +425,7 @@ void upload_standardize(DeviceData<T>& d, const double* x, const double* y, int 
     d.Y.alloc((size_t)d.ldx);
     // one launch per block of columns does everything (convert_standardize_kernel) unless the moments are global (several processes)
     bool fused = !dist;
-    if (const char* e = option("PREP_FUSED")) fused = fused && std::string(e) != "0";
+    if (opt_off(Opt::PREP_FUSED)) fused = false;
     DevBuf<T> fmean, fscale;
     if (fused) { fmean.alloc(p + 1); fscale.alloc(p + 1); }
     if (!fused) { d.X.zero(st); d.Y.zero(st); }
@@ -805,8 +800,7 @@ void gram_full(const T* A, long long lda, int rows, int cols, bool atA, T* C, lo
     // BLAS handle is ever created in a default run (rocBLAS handle creation alone costs 0.1-0.2 s per process);
     // ADMM_HIP_GRAM=rocblas forces the library path (A/B tests)
     {
-        const char* e = option("GRAM");
-        const bool force_lib = e && std::string(e) == "rocblas";
+        const bool force_lib = opt_is(Opt::GRAM, "rocblas");
         if (!force_lib) {
             if constexpr (std::is_same<T, float>::value) gram_mfma_f32(A, lda, rows, cols, atA, C, ldc, st);
             else gram_mfma_f64(A, lda, rows, cols, atA, C, ldc, st);
@@ -930,15 +924,13 @@ void spd_inverse_f32_via_f64(float* A, long long lda, int n, double diag, hipStr
 
 void spd_inverse_f32(float* A, long long lda, int n, hipStream_t st) {
     const TraceRange trace_range("admm:factor+inverse (f32)");
-    const char* e = option("FACTOR");
-    if ((e && std::string(e) == "rocsolver") || lda < round_up(n, 128)) spd_inverse_full<float>(A, lda, n, st);
+    if (opt_is(Opt::FACTOR, "rocsolver") || lda < round_up(n, 128)) spd_inverse_full<float>(A, lda, n, st);
     else spd_inverse_mfma_f32(A, lda, n, st);
 }
 
 void spd_inverse_f64(double* A, long long lda, int n, hipStream_t st) {
     const TraceRange trace_range("admm:factor+inverse (f64)");
-    const char* e = option("FACTOR");
-    if ((e && std::string(e) == "rocsolver") || lda < round_up(n, 128)) spd_inverse_full<double>(A, lda, n, st);
+    if (opt_is(Opt::FACTOR, "rocsolver") || lda < round_up(n, 128)) spd_inverse_full<double>(A, lda, n, st);
     else spd_inverse_mfma_f64(A, lda, n, st);
 }
 template void spd_inverse_full<double>(double*, long long, int, hipStream_t);

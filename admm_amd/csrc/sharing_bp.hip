@@ -1181,10 +1181,6 @@ sbp_gs_tail_kernel(SbpParams q, int par, int nth) {
 }
 
 // ------------------------------------------------------------------------------------------------ setup
-static int env_int(const char* name, int dflt) {          // a positive option value, or the default
-    const int v = option_int(name, 0);
-    return v > 0 ? v : dflt;
-}
 
 
 // Largest eigenvalue of a symmetric tridiagonal matrix (diagonal a[0..m), off-diagonal e[0..m-1)) and the LAST component of
@@ -1455,12 +1451,6 @@ static void sbp_sprad_batch(const double* A, long long lda, int n, const std::ve
     ADMM_HIP_CHECK(hipGetLastError());
 }
 
-static int sbp_batch() {
-    const char* e = option("BATCH_ITERS");
-    const int v = e ? std::atoi(e) : 0;
-    return v > 0 ? (v + 1) / 2 * 2 : 20;                            // even: the parity pattern of the control block
-}
-
 // d: this rank's columns (n x pl).  nblocks: N (global); blk_first / nloc: the global blocks this rank holds; p_total.
 void solve_parbp(const DeviceData<double>& d, const admm_opts& opts, int nblocks, long long p_total, long long col_offset,
                  DenseResult& res, hipStream_t st) {
@@ -1496,10 +1486,9 @@ void solve_parbp(const DeviceData<double>& d, const admm_opts& opts, int nblocks
     std::vector<double> sprad(N, 0.0);
     int lsteps = 0;
     {
-        // as many blocks in lockstep as ~3 GB of Gram matrices and Lanczos bases allow (A/B: ADMM_HIP_SBP_LZ_BATCH)
+        // as many blocks in lockstep as ~3 GB of Gram matrices and Lanczos bases allow
         const double per = (double)round_up(n, 32) * ((double)round_up(n, 32) + (double)std::min(n, 600) + 8.0) * 8.0;
-        int Bmax = std::max(1, std::min(NL, (int)(3.0e9 / per)));
-        Bmax = std::min(Bmax, env_int("SBP_LZ_BATCH", Bmax));
+        const int Bmax = std::max(1, std::min(NL, (int)(3.0e9 / per)));
         for (int b = 0; b < NL; b += Bmax) {
             const int B = std::min(Bmax, NL - b);
             std::vector<int> ns(B, 0);
@@ -1538,7 +1527,7 @@ void solve_parbp(const DeviceData<double>& d, const admm_opts& opts, int nblocks
     int ncu = 256;
     { hipDeviceProp_t prop; int dev = 0; ADMM_HIP_CHECK(hipGetDevice(&dev)); ADMM_HIP_CHECK(hipGetDeviceProperties(&prop, dev)); ncu = prop.multiProcessorCount; }
     // workgroups per block: the same for every local block (block = g / Gb), about two per CU in all, never more than a block has columns
-    int Gb = std::max(1, env_int("SBP_WGS", 2 * ncu) / NL);
+    int Gb = std::max(1, (int)opt_int(Opt::SBP_WGS, 2 * ncu) / NL);
     for (int b = 0; b < NL; ++b) Gb = std::min(Gb, c0[b + 1] - c0[b]);
     const int G = Gb * NL;
     const int nT = npad / 64;
@@ -1575,7 +1564,7 @@ void solve_parbp(const DeviceData<double>& d, const admm_opts& opts, int nblocks
     PinnedFlag hflag;
 
     SbpParams q{};
-    q.min_share = std::max(1, env_int("SBP_SHARE", 4));
+    q.min_share = (int)opt_int(Opt::SBP_SHARE, 4);
     q.n = n; q.npad = npad; q.N = N; q.NL = NL; q.maxit = opts.maxit; q.G = G; q.nT = nT;
     q.eps_abs = opts.eps_abs; q.eps_rel = opts.eps_rel; q.rho = rho;
     q.sqrt_nN = std::sqrt((double)n * (double)N); q.sqrtN = std::sqrt((double)N); q.dN = (double)N;
@@ -1590,8 +1579,8 @@ void solve_parbp(const DeviceData<double>& d, const admm_opts& opts, int nblocks
 
     // ---- Gram space (single process): state, the gather launches that materialise the n-vectors
     bool gram = !dist && NL <= kGsMaxBlocks;
-    if (const char* e = option("SBP_GRAM")) gram = gram && std::atoi(e) != 0;      // 0: the direct launches on every iteration (A/B)
-    const int gcap = std::min(kGsCapMax, std::max(kGsRows, env_int("SBP_GRAM_CAP", kGsCapMax)) / kGsRows * kGsRows);
+    if (opt_off(Opt::SBP_GRAM)) gram = false;      // 0: the direct launches on every iteration (A/B)
+    const int gcap = std::min(kGsCapMax, std::max(kGsRows, (int)opt_int(Opt::SBP_GRAM_CAP, kGsCapMax)) / kGsRows * kGsRows);
     DevBuf<int> g_umap, g_ucol, g_ubid, g_ust;
     DevBuf<double> g_G, g_gz, g_ugp, g_xs, g_hr, g_gy, g_sx, g_sxd, g_Ps, g_sc, g_partP, g_partT;
     DevBuf<GatherArgs<double>> g_args;
@@ -1616,7 +1605,7 @@ void solve_parbp(const DeviceData<double>& d, const admm_opts& opts, int nblocks
         gs.sx = g_sx.get(); gs.sxd = g_sxd.get(); gs.Ps = g_Ps.get(); gs.sc = g_sc.get();
         gs.partP = g_partP.get(); gs.partT = g_partT.get(); gs.ngroups = gp.ngroups; gs.pstride = npad;
         gs.zz = zz;
-        gs.test_delay = 100 * env_int("SBP_TEST_DELAY_US", 0); gs.pad2 = 0;
+        gs.test_delay = 100 * (int)opt_int(Opt::SBP_TEST_DELAY_US, 0); gs.pad2 = 0;
         std::vector<GatherArgs<double>> ha(2 * (size_t)NL);
         for (int k = 0; k < 2 * NL; ++k) {
             const int b = k % NL;
@@ -1655,7 +1644,7 @@ void solve_parbp(const DeviceData<double>& d, const admm_opts& opts, int nblocks
     const bool nt = (double)lda * (double)pl * 8.0 > 220e6;       // as gemv_plan.h: beyond what the 256 MB Infinity Cache keeps
     // the regular iterations' screen (sbp_xreg_screen_kernel): worth its 2 n p bytes when A streams from HBM; SBP_SCREEN = 0 never, 1 always
     bool screen = nt;
-    if (const char* e = option("SBP_SCREEN")) screen = std::atoi(e) != 0;
+    if (opt_set(Opt::SBP_SCREEN)) screen = opt_on(Opt::SBP_SCREEN);
     DevBuf<unsigned short> Ah;
     DevBuf<float> scr_s;
     DevBuf<unsigned long long> scr_stat;
@@ -1669,14 +1658,14 @@ void solve_parbp(const DeviceData<double>& d, const admm_opts& opts, int nblocks
         if (screen) {
             hipLaunchKernelGGL(sbp_screen_prep_kernel, dim3((unsigned)((pl + 3) / 4)), dim3(256), 0, st, A, lda, n, pl, Ah.get(), ldh, scr_s.get());
             q.Ah = Ah.get(); q.ldh = ldh; q.scr_s = scr_s.get();
-            if (option("SBP_SCREEN_STATS")) { scr_stat.alloc(2); scr_stat.zero(st); q.scr_stat = scr_stat.get(); }
+            if (opt_on(Opt::SBP_SCREEN_STATS)) { scr_stat.alloc(2); scr_stat.zero(st); q.scr_stat = scr_stat.get(); }
         }
     }
     comm_stream_sync(st);
     const size_t ldsv = (size_t)npad * sizeof(double);
     const bool gram_on = gram;
     bool carry_on = true;                                          // 0: every Gram-space stretch starts from the direct launches' n-vectors (A/B)
-    if (const char* e = option("SBP_GRAM_CARRY")) carry_on = std::atoi(e) != 0;
+    if (opt_off(Opt::SBP_GRAM_CARRY)) carry_on = false;
     long long gram_from = 0;                                       // the first regular iteration whose stretch may run in Gram space
     long long last_gram = -100;                                    // the regular iteration of the last stretch enqueued in Gram space
     std::vector<char> carried;                                     // per stretch: it started from the previous stretch's Gram-space state
@@ -1739,7 +1728,7 @@ void solve_parbp(const DeviceData<double>& d, const admm_opts& opts, int nblocks
     int gstat[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int halts = 0;
     for (long long g_start = 0;;) {
-        const LoopTimes l1 = run_until_done(st, d_done.get(), sbp_batch(), (long long)opts.maxit + 2, enqueue, dist ? nullptr : hflag.p, g_start);
+        const LoopTimes l1 = run_until_done(st, d_done.get(), batch_iters((int)opt_int(Opt::BATCH_ITERS, 0), 20), (long long)opts.maxit + 2, enqueue, dist ? nullptr : hflag.p, g_start);
         lt.wall_s += l1.wall_s; lt.events_ms += l1.events_ms; lt.launched += l1.launched;
         if (!gram_on) break;
         ADMM_HIP_CHECK(hipGetLastError());

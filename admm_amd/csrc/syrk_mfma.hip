@@ -464,20 +464,18 @@ void gram_mfma_f32(const float* A, long long lda, int rows, int cols, bool atA, 
         GramSplit3 z3;
         z3.alloc(M, Kd, st);
         z3.split_cols(A, lda, rows, 0, cols, st);
-        // fp16 form: 256 x 256 macro-tiles (round 6; option GRAM_B3_TILE=128 keeps the 128 x 128 tiles: the A/B, bit-identical)
-        bool big = z3.npl == 2;
-        if (const char* e = option("GRAM_B3_TILE")) big = big && std::atoi(e) != 128;
+        // fp16 form: 256 x 256 macro-tiles (round 6)
+        const bool big = z3.npl == 2;
         if (big) {
             // One macro-tile workgroup is resident per CU: T macro-tiles take ceil(T / CUs) rounds (p = 10^4: 820 on 256 CUs, the fourth round
             // a fifth full).  Whole rounds of macro-tiles; the rest -- taken evenly from the back of the 8 XCD lists -- as 128 x 128 tiles after
-            // them (four per CU are resident: one short round).  GRAM_B3_TAIL=0: every tile a macro-tile.
+            // them (four per CU are resident: one short round).
             const int nb2 = (M + 255) / 256;
             std::vector<std::vector<int>> q = square_tile_lists(nb2);
             size_t total = 0;
             for (const auto& l : q) total += l.size();
             const size_t slots = (size_t)device_info().num_cu;
             size_t cut = total > slots ? total % slots : 0;
-            if (const char* e = option("GRAM_B3_TAIL")) { if (std::atoi(e) == 0) cut = 0; }
             if (cut * 4 > slots * 3) cut = 0;                     // a last round three quarters full is left alone
             std::vector<int> tail;
             auto longest = [&]() { int x = 0; for (int k = 1; k < 8; ++k) if (q[k].size() > q[x].size()) x = k; return x; };

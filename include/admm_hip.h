@@ -312,8 +312,11 @@ ADMM_HIP_API int admm_hip_lasso_plan_state_read(admm_hip_plan* plan, float* out,
  * created): two threads can run two different variants at the same time, and nothing reads the environment per call.  The typed
  * struct carries the selectors that choose between numerically different (all parity-tested) paths; admm_hip_option_set reaches the
  * long tail of tuning / diagnostic values by name (INTEGRATION.md lists them).  Every field 0 = the library's default.
+ * Values are checked when they are set: an unknown name, or a value outside what the option accepts, is refused with
+ * ADMM_ERR_INVALID_ARG (the message names the option and what it takes) and the thread's settings stay as they were.
  * Debugging aid: ADMM_HIP_<NAME> environment variables present when the library is FIRST used form a process-wide overlay under
- * the thread's own settings (read once; changing the environment afterwards has no effect). */
+ * the thread's own settings (read once; changing the environment afterwards has no effect).  Variables that name no option are
+ * ignored; a known name with a malformed value makes every entry point return ADMM_ERR_INVALID_ARG, naming the variable. */
 typedef struct admm_hip_options {
     int struct_size;          /* sizeof(admm_hip_options): lets the library accept older, shorter structs */
     int gram_backend;         /* 0 hand-written matrix-core kernels, 1 rocBLAS (dlopen) */
@@ -346,7 +349,9 @@ typedef struct admm_hip_options {
 } admm_hip_options;
 ADMM_HIP_API int admm_hip_options_default(admm_hip_options* o);               /* zero-fills and sets struct_size */
 ADMM_HIP_API int admm_hip_options_set(const admm_hip_options* o);             /* NULL: back to the defaults (keeps nothing of the thread's earlier settings) */
-ADMM_HIP_API int admm_hip_option_set(const char* name, const char* value);    /* one value by name ("GRAM_SPLIT", "f16x2"); value NULL: back to the default */
+ADMM_HIP_API int admm_hip_option_set(const char* name, const char* value);    /* one value by name ("GRAM_SPLIT", "f16x2"; case-insensitive,
+                                                                                 ADMM_HIP_ prefix optional); value NULL: back to the default;
+                                                                                 unknown name / malformed value: ADMM_ERR_INVALID_ARG, nothing changed */
 ADMM_HIP_API int admm_hip_options_reset(void);
 ADMM_HIP_API const char* admm_hip_option_get(const char* name);               /* value in force for this thread, or NULL (library default) */
 

@@ -19,4 +19,4 @@ plan.run()
 for i in range(5):
     t0 = time.time(); fit = plan.run(); w = time.time() - t0
     s = fit.stats
-    print(f"stride={os.environ['ADMM_HIP_PROFILE_STRIDE']} layout={os.environ.get('ADMM_HIP_SYMV_LAYOUT','packed')} wall {w*1e3:.2f} ms  t_total {s['t_total']*1e3:.2f}  t_loop(wall) {s['t_loop']*1e3:.2f}  loop_events {s['loop_ms_events']:.2f}  iters {s['total_iter']} launches {s['xupdate_launches']} xms {s['xupdate_ms_avg']*1e3:.2f}us")
+    print(f"stride={os.environ['ADMM_HIP_PROFILE_STRIDE']} wall {w*1e3:.2f} ms  t_total {s['t_total']*1e3:.2f}  t_loop(wall) {s['t_loop']*1e3:.2f}  loop_events {s['loop_ms_events']:.2f}  iters {s['total_iter']} launches {s['xupdate_launches']} xms {s['xupdate_ms_avg']*1e3:.2f}us")

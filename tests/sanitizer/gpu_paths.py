@@ -26,9 +26,8 @@ f = admm_amd.admm_enet(xw, yw).penalty(nlambda=5, alpha=0.3).fit()
 m = admm_amd.admm_lasso(x, y).penalty(nlambda=4); m.parallel(3); f = m.fit()         # consensus, Cholesky blocks
 m = admm_amd.admm_lasso(xw, yw).penalty(nlambda=3).opts(maxit=200); m.nthread = 4; f = m.fit()   # Woodbury blocks
 cv = admm_amd.admm_lasso(x, y).penalty(nlambda=6).cv(nfolds=3, keep_fold_beta=True)
-os.environ["ADMM_HIP_CV_DOWNDATE"] = "1"
-cv = admm_amd.admm_lasso(x, y).penalty(nlambda=6).cv(nfolds=3)
-os.environ.pop("ADMM_HIP_CV_DOWNDATE")
+with admm_amd.options(CV_DOWNDATE="1"):
+    cv = admm_amd.admm_lasso(x, y).penalty(nlambda=6).cv(nfolds=3)
 fits = admm_amd.admm_lasso(x, y).penalty(nlambda=4).fit_responses(np.stack([y, y[::-1]], axis=1)); assert len(fits) == 2
 rng = np.random.default_rng(4)
 xl = rng.standard_normal((400, 30)); yl = xl @ rng.standard_normal(30) + rng.standard_cauchy(400) * 0.1

@@ -161,23 +161,44 @@ def test_fit_objects_mirror_show_and_plot_data():
         dz.fit_responses(np.zeros((30, 2)))
 
 
-def test_every_option_the_library_reads_is_in_the_integration_guide_and_nothing_reads_the_environment():
-    """INTEGRATION.md's option table is the only place a maintainer learns what the named options do: every name the sources pass
-    to option() / option_int() must appear there.  And the sources must not call getenv at all (round 6: variant selectors belong to
-    the calling thread, admm_hip_options / admm_hip_option_set; ADMM_HIP_* variables are an overlay captured once from `environ`)."""
-    import glob, os, re
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    names, getenvs = set(), 0
-    for f in glob.glob(os.path.join(root, "admm_amd", "csrc", "*")):
+def _option_table():
+    """The names of admm_amd/csrc/options.h's table (ADMM_OPTIONS), with what each accepts as written there."""
+    src = open(os.path.join(ROOT, "admm_amd", "csrc", "options.h")).read()
+    table = src[src.index("#define ADMM_OPTIONS(X)"):src.index("enum class Opt :")]
+    return dict(re.findall(r"\bX\(([A-Z0-9_]+), (\w+\([^)]*\))", table))
+
+
+def _integration_section5():
+    guide = open(os.path.join(ROOT, "INTEGRATION.md")).read()
+    return guide[guide.index("## 5. Options"):]
+
+
+def test_every_option_of_the_table_is_in_the_integration_guide_and_nothing_reads_the_environment():
+    """INTEGRATION.md's option table is the only place a maintainer learns what the named options do: every name of the library's
+    table (options.h) must have its row there, and every ADMM_HIP_<NAME> row there must be a name of the table or one of the two
+    variables that are not the library's (the Python loader's LIB, the build's EXTRA_CXXFLAGS).  The sources must not call getenv
+    at all (round 6: variant selectors belong to the calling thread, admm_hip_options / admm_hip_option_set; ADMM_HIP_* variables
+    are an overlay captured once from `environ`), and nothing outside the options module looks an option up by a string."""
+    import glob
+    names = set(_option_table())
+    assert len(names) > 40
+    getenvs, lookups = 0, []
+    for f in glob.glob(os.path.join(ROOT, "admm_amd", "csrc", "*")):
         if f.endswith((".hip", ".h")):
             src = open(f).read()
-            names |= set(re.findall(r'\b(?:option|option_int|env_int|env_seconds)\("([A-Z0-9_]+)"', src))
-            getenvs += len(re.findall(r'\bgetenv\s*\(', src))
+            getenvs += len(re.findall(r"\bgetenv\s*\(", src))
+            if os.path.basename(f) not in ("options.h", "options.hip"):
+                lookups += [(os.path.basename(f), m) for m in re.findall(r'\b(?:option|option_int)\("[^"]*"', src)]
     assert getenvs == 0, f"{getenvs} getenv calls in admm_amd/csrc"
-    guide = open(os.path.join(root, "INTEGRATION.md")).read()
-    missing = sorted(n for n in names if n not in guide)
-    assert len(names) > 20 and not missing, missing
-
+    assert not lookups, lookups
+    rows = set()
+    for line in _integration_section5().splitlines():
+        if line.startswith("| `ADMM_HIP_"):
+            rows |= set(re.findall(r"ADMM_HIP_([A-Z0-9_]+)", line.split("|")[1]))
+    missing = sorted(names - rows)
+    assert not missing, missing
+    unknown = sorted(rows - names - {"LIB", "EXTRA_CXXFLAGS"})
+    assert not unknown, unknown
 
 
 def test_options_are_per_thread_and_the_typed_struct_maps_onto_the_named_ones():
@@ -207,6 +228,53 @@ def test_options_are_per_thread_and_the_typed_struct_maps_onto_the_named_ones():
     assert b"gram_split" in lib.admm_hip_last_error()
     _lib.check(lib.admm_hip_options_set(None))
     assert lib.admm_hip_option_get(b"INVERSE") is None
+    # names and values are checked when they are set; a refusal names the option and leaves the thread's settings as they were
+    _lib.check(lib.admm_hip_option_set(b"GRAM_SPLIT", b"bf16x3"))
+    _lib.check(lib.admm_hip_option_set(b"wide_screen", b"8"))
+    for name, value in ((b"GRAM_SPLT", b"0"), (b"WIDE_SCREEN", b"fp16"), (b"GRAM_SPLIT", b"f16x3"), (b"BATCH_ITERS", b"abc"),
+                        (b"BATCH_ITERS", b"0"), (b"REFINE", b"2"), (b"SYMV_SCHED", b"100,64,0"), (b"PAR_DEVICES", b"0,x")):
+        assert lib.admm_hip_option_set(name, value) == 1, (name, value)          # ADMM_ERR_INVALID_ARG
+        assert name.upper() in lib.admm_hip_last_error(), lib.admm_hip_last_error()
+        assert lib.admm_hip_option_get(b"GRAM_SPLIT") == b"bf16x3" and lib.admm_hip_option_get(b"WIDE_SCREEN") == b"8"
+        assert lib.admm_hip_option_get(b"BATCH_ITERS") is None and lib.admm_hip_option_get(b"REFINE") is None
+    assert lib.admm_hip_option_set(b"WIDE_SCREEN", b"fp16") == 1 and b"0|8|16|auto" in lib.admm_hip_last_error()     # what it accepts
+    # every accepted value of every choice option survives a set / get round trip (XUPDATE: full and gemv mean the same)
+    choices = {k: v[len('Choice("'):-2].split("|") for k, v in _option_table().items() if v.startswith("Choice(")}
+    assert choices["XUPDATE"] == ["sym", "gemv", "full"] and choices["GRAM_SPLIT"] == ["0", "f16x2", "bf16x3"]
+    assert choices["WIDE_SCREEN"] == ["0", "8", "16", "auto"]
+    for name, values in choices.items():
+        for v in values:
+            _lib.check(lib.admm_hip_option_set(name.encode(), v.encode()))
+            assert lib.admm_hip_option_get(name.encode()) == v.encode(), (name, v)
+    _lib.check(lib.admm_hip_options_reset())
+    assert lib.admm_hip_option_get(b"GRAM_SPLIT") is None
+
+
+_OVERLAY_CHILD = """
+import sys
+sys.path.insert(0, sys.argv[1])
+from admm_amd import _lib
+lib = _lib.load()
+rc = lib.admm_hip_option_set(b"GRAM_SPLIT", b"0")
+print(rc, lib.admm_hip_last_error().decode() if rc else "")
+"""
+
+
+@pytest.mark.parametrize("env,refused", [({"ADMM_HIP_WIDE_SCREEN": "fp16"}, True), ({"ADMM_HIP_EXTRA_CXXFLAGS": "-O3"}, False)])
+def test_environment_overlay_goes_through_the_same_parser(env, refused):
+    """ADMM_HIP_<NAME> variables are read once from the environment and parsed like admm_hip_option_set's values: a known name
+    with a malformed value makes every entry point refuse, naming the variable; names that are not the library's options (the
+    build's and the Python loader's) are ignored."""
+    import subprocess, sys
+    full = {k: v for k, v in os.environ.items() if not k.startswith("ADMM_HIP_") or k == "ADMM_HIP_LIB"}
+    full.update(env)
+    r = subprocess.run([sys.executable, "-c", _OVERLAY_CHILD, ROOT], env=full, capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0, r.stderr
+    rc, _, msg = r.stdout.strip().partition(" ")
+    if refused:
+        assert int(rc) == 1 and "WIDE_SCREEN" in msg, r.stdout           # ADMM_ERR_INVALID_ARG
+    else:
+        assert int(rc) == 0, r.stdout
 
 
 def test_bench_refuses_a_world_size_that_disagrees_with_gpus_without_a_gpu():

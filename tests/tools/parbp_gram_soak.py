@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Soak of admm_hip_parbp's Gram-space active-set iterations against the oracle (oracle/solvers.py SharingBP), decision by
 decision, on randomised problems -- the drawing of tests/test_gpu_fuzz_new.py with more seeds, larger shapes and, per case, a
-random capacity of the Gram matrix (ADMM_HIP_SBP_GRAM_CAP) so that halts (support larger than the matrix), re-entries and
+random capacity of the Gram matrix (option SBP_GRAM_CAP) so that halts (support larger than the matrix), re-entries and
 rebuilds of the column set are exercised as well as the plain path.  Prints one line per seed and a summary (markdown).
 
     python tests/tools/parbp_gram_soak.py [first_seed [n_seeds [cases_per_seed [shape_factor]]]]
@@ -45,8 +45,8 @@ def main():
             maxit = int(rng.choice([60, 400, 3000]))
             ratio = float(rng.choice([0.5, 1.0, 1.0, 3.0]))
             cap = int(rng.choice([8, 16, 32, 64, 128, 1024, 1024])) if sf == 1 else int(rng.choice([256, 512, 1024, 1024]))
-            os.environ["ADMM_HIP_SBP_GRAM_CAP"] = str(cap)
-            fit = admm_amd.admm_bp(A, b).parallel(N).opts(maxit=maxit, eps_abs=eps, eps_rel=eps, rho=ratio).fit(trace=True)
+            with admm_amd.options(SBP_GRAM_CAP=cap):
+                fit = admm_amd.admm_bp(A, b).parallel(N).opts(maxit=maxit, eps_abs=eps, eps_rel=eps, rho=ratio).fit(trace=True)
             d = {"trace": []}
             ref = entry.admm_parbp(A, b, N, dict(maxit=maxit, eps_abs=eps, eps_rel=eps, rho_ratio=ratio), d)
             tr = np.asarray(d["trace"], dtype=np.float64)
