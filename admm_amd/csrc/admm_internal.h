@@ -25,6 +25,7 @@ struct Error : std::runtime_error {
 };
 
 void set_last_error(const std::string& m);
+const std::string& last_error_ref();
 
 #define ADMM_HIP_CHECK(expr)                                                                       \
     do {                                                                                           \
@@ -55,16 +56,20 @@ struct TraceRange {
     bool on;
 };
 
-// Cache of large device blocks (api.hip).  hipMalloc / hipFree of multi-GB buffers are synchronous page-table operations whose cost
+// Cache of large device blocks (pool.hip).  hipMalloc / hipFree of multi-GB buffers are synchronous page-table operations whose cost
 // varies by box and by what the process freed before (measured on C2, second plan creation of a process: 0.07 s of kernels inside
 // 0.07 .. 0.31 s of wall, the difference all in hipFree / hipMalloc of the 4 GB operands) -- a resident server or an R session that
 // calls $fit() repeatedly should not pay it per call.  Blocks of at least 32 MB that a DevBuf releases are kept (per device, at most
-// ADMM_HIP_POOL_MB megabytes in all, default 24576; 0 switches the cache off) and handed to the next allocation they fit (size <=
+// ADMM_HIP_POOL_MB megabytes in all, default the smaller of 16 GB and an eighth of the device's memory; 0 switches the cache off)
+// and handed to the next allocation they fit (size <=
 // block <= 1.25 size).  A failed hipMalloc empties the cache and tries again; pool_cached_bytes() is what a caller adds to
 // hipMemGetInfo's free figure; admm_hip_trim_memory() returns everything to the driver.  Thread-safe (one mutex).
-// A rank thread of an in-process group (api.hip) does not free device or pinned memory during its call: hipFree / hipHostFree wait for
-// every stream of the device, a device may hold several ranks, and another rank's kernel may be waiting for an exchange this rank
+// A rank thread of an in-process group (inproc.hip) does not free device or pinned memory during its call: hipFree / hipHostFree wait
+// for every stream of the device, a device may hold several ranks, and another rank's kernel may be waiting for an exchange this rank
 // has yet to enqueue.  Its releases are collected and carried out by the calling thread once every rank has returned.
+struct DeferredFree { void* p; size_t granted; bool pinned; };
+void defer_frees(std::vector<DeferredFree>* sink);                  // the calling thread's releases go to `sink` from now on (nullptr: freed at once)
+void release_deferred(const std::vector<DeferredFree>& frees);
 void pinned_free(void* p);                                          // hipHostFree, or deferred as above
 void* pool_alloc(size_t bytes, size_t* granted);
 void pool_free(void* p, size_t granted);

@@ -1,0 +1,65 @@
+// What a lambda-path call asks for and where its results go: built once by each extern "C" function (api.hip) from its arguments and
+// handed down as they are.  The solvers keep taking LassoProblem (solvers.h), which PathSpec::problem() fills.
+#pragma once
+#include "solvers.h"
+
+namespace admm {
+
+struct PathSpec {
+    const double* lambda_in = nullptr;   // the caller's grid (nlambda_in entries), or an automatic one of nlambda_auto values
+    int nlambda_in = 0, nlambda_auto = 0;
+    double lmin_ratio = 0;
+    int standardize = 0, intercept = 0;
+    double alpha = -1.0;                 // as the ABI passes it: >= 0 means elastic net (and then <= 1), anything else the plain Lasso
+    const admm_opts* opts = nullptr;
+    bool enet_only = false;              // admm_hip_enet has no Lasso form: it refuses a negative alpha too (R/40_admm_enet.R:38-39)
+
+    bool enet() const { return alpha >= 0.0; }
+    double alpha_eff() const { return enet() ? alpha : 1.0; }
+    int nlam() const { return nlambda_in > 0 ? nlambda_in : nlambda_auto; }
+    void check() const {
+        ADMM_REQUIRE(enet() ? alpha <= 1.0 : !enet_only, "alpha must be within [0, 1]");
+        ADMM_REQUIRE(nlambda_in >= 0, "nlambda_in must be >= 0");
+        ADMM_REQUIRE(nlambda_in > 0 ? lambda_in != nullptr : nlambda_auto > 0, "need a lambda grid or nlambda_auto > 0");
+        if (nlambda_in == 0) ADMM_REQUIRE(lmin_ratio > 0 && lmin_ratio < 1, "lambda_min_ratio must be within (0, 1)");
+        for (int i = 0; i < nlambda_in; ++i) ADMM_REQUIRE(lambda_in[i] > 0, "lambda must be positive");
+    }
+    LassoProblem problem(int nworkers, bool dist) const {
+        LassoProblem pb;
+        pb.opts = *opts;
+        pb.lambda_in.assign(lambda_in, lambda_in + nlambda_in);
+        pb.nlambda_auto = nlambda_auto;
+        pb.lmin_ratio = lmin_ratio;
+        pb.enet = enet();
+        pb.alpha = alpha_eff();
+        pb.nworkers = nworkers;
+        pb.dist = dist;
+        pb.batch_iters = (int)opt_int(Opt::BATCH_ITERS, 0);
+        pb.profile_stride = (int)opt_int(Opt::PROFILE_STRIDE, 0);
+        return pb;
+    }
+    PathSpec on_grid(const std::vector<double>& lam) const {      // the same call on a grid that an earlier fit fixed
+        PathSpec s = *this;
+        s.lambda_in = lam.data(); s.nlambda_in = (int)lam.size(); s.nlambda_auto = 0;
+        return s;
+    }
+};
+
+template <typename B>
+struct PathOutT {
+    double* lambda_out; B* beta_out; int* niter_out; admm_stats* stats;
+    void require() const { ADMM_REQUIRE(lambda_out && beta_out && niter_out, "output pointers must not be NULL"); }
+};
+using PathOut = PathOutT<float>;
+
+struct TraceOut {
+    double* out = nullptr; long long cap = 0; long long* n_out = nullptr;
+    void check() const { ADMM_REQUIRE(cap == 0 || (out != nullptr && n_out != nullptr && cap > 0), "bad trace arguments"); }
+    void store(const std::vector<double>& trace) const {
+        if (cap <= 0) return;
+        std::memcpy(out, trace.data(), trace.size() * sizeof(double));
+        *n_out = (long long)(trace.size() / ADMM_TRACE_FIELDS);
+    }
+};
+
+}  // namespace admm

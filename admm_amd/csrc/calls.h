@@ -1,0 +1,64 @@
+// What the C boundary (api.hip) calls: plan creation and path runs, the replica drivers (multi-response here, cross-validation in
+// cv.hip), the dense solvers and the Dantzig selector.  Everything takes the call as call_args.h describes it and throws Error.
+#pragma once
+#include "call_args.h"
+
+namespace admm {
+
+void check_common(const double* x, const double* y, int n, int p, int mem, const admm_opts* opts);
+
+// How the caller's data are spread over the ranks of the attached communicator (or of an in-process group).
+struct Shard {
+    enum Kind { NONE, ROWS, COLS } kind = NONE;
+    long long n_total = 0, ldx = 0;            // ROWS: rows of the whole problem; ldx > n: x is a row slice of a matrix with this leading dimension
+    long long p_total = 0, col_offset = 0;     // COLS: this rank holds columns [col_offset, col_offset + p) of p_total (the wide solver)
+    static Shard rows(long long n_total, long long ldx = 0) { Shard s; s.kind = ROWS; s.n_total = n_total; s.ldx = ldx; return s; }
+    static Shard cols(long long p_total, long long col_offset) { Shard s; s.kind = COLS; s.p_total = p_total; s.col_offset = col_offset; return s; }
+};
+
+struct PlanHandle {
+    Stream st;
+    std::unique_ptr<LassoPlan> plan;
+    int p = 0, nlam = 0;
+    double t_create = 0;
+};
+// nworkers > 0: the row-block consensus solver; otherwise the tall or the wide one by shape (Lasso.cpp:73)
+PlanHandle* create_plan(const double* x, const double* y, int n, int p, int mem, const PathSpec& spec, int nworkers, const Shard& shard = Shard());
+void run_plan(PlanHandle* h, const PathOut& out, double t_extra);
+// create_plan + run_plan: admm_hip_lasso / _enet and the _dist entry points
+void lasso_family(const double* x, const double* y, int n, int p, int mem, const PathSpec& spec, int nworkers, const Shard& shard, const PathOut& out);
+// admm_hip_parlasso: over in-process ranks when PAR_DEVICES lists several devices, else lasso_family
+void parlasso(const double* x, const double* y, int n, int p, int mem, const PathSpec& spec, int nthread, const PathOut& out);
+
+// The replica drivers (cross-validation folds, responses) keep one resident double copy of host input; device input is used in place.
+struct Resident {
+    DevBuf<double> own;
+    const double* p;
+    Resident(const double* src, size_t count, int mem) : p(src) {
+        if (mem != ADMM_MEM_HOST) return;
+        own.alloc(count);
+        write_device(own.get(), src, count * sizeof(double));
+        p = own.get();
+    }
+};
+// ... and deal their units out to the ranks (unit u on rank u mod nranks, zeroed tables elsewhere): the results are the sums over
+// the ranks of the double tables a and b (equal length) and of the nf host floats at f (may be NULL).  One rank: nothing to do.
+void sum_over_ranks(std::vector<double>& a, std::vector<double>& b, float* f, size_t nf, hipStream_t st);
+
+void lasso_multi(const double* x, const double* Y, int n, int p, int m, int mem, const PathSpec& spec, const PathOut& out);
+struct CvOut { double* cv_mean; double* cv_se; double* fold_mse; int* fold_niter; float* fold_beta; int* idx_min; int* idx_1se; };
+void lasso_cv(const double* x, const double* y, int n, int p, int mem, const int* fold_id, int nfolds, const PathSpec& spec,
+              const PathOut& out, const CvOut& cv);
+
+// Iterate dump of a LAD / BP run (admm_hip_lad_state / admm_hip_bp_state)
+struct StateOut { double* out = nullptr; long long cap = 0; long long* n_out = nullptr; };
+struct DenseOut { double* beta_out; int* niter_out; admm_stats* stats; TraceOut trace = {}; StateOut state = {}; };
+void lad(const double* x, const double* y, int n, int p, int mem, int intercept, const admm_opts* opts, const DenseOut& out);
+void bp(const double* x, const double* y, int n, int p, int mem, const admm_opts* opts, const DenseOut& out);
+// admm_hip_parbp(_traced): over in-process ranks when PAR_DEVICES lists several devices; parbp_dist: this rank's columns of p_total
+void parbp(const double* x, const double* y, int n, int p, int mem, int nthread, const admm_opts* opts, const DenseOut& out);
+void parbp_dist(const double* x_cols, const double* y, int n, int p_local, long long p_total, long long col_offset, int mem, int nthread,
+                const admm_opts* opts, const DenseOut& out);
+void dantzig(const double* x, const double* y, int n, int p, int mem, const PathSpec& spec, const PathOutT<double>& out, const TraceOut& trace);
+
+}  // namespace admm

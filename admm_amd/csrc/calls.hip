@@ -1,0 +1,318 @@
+// The calls behind the C boundary (calls.h): lambda grid, plan creation and runs, the multi-response driver, the dense solvers.
+#include "calls.h"
+#include "comm.h"
+#include "inproc.h"
+
+namespace admm {
+
+std::vector<double> make_lambda_grid(const LassoProblem& pb, double lambda0, int n, double scaleY) {
+    if (!pb.lambda_in.empty()) return pb.lambda_in;
+    // Lasso.cpp:78-89: lmax = lambda0 / n * scaleY; log-spaced down to lmin_ratio * lmax
+    const int nl = pb.nlambda_auto;
+    const double lmax = lambda0 / n * scaleY;
+    const double lmin = pb.lmin_ratio * lmax;
+    std::vector<double> lam(nl);
+    const double lo = std::log(lmax), hi = std::log(lmin);
+    for (int i = 0; i < nl; ++i) {
+        const double t = nl > 1 ? lo + (hi - lo) * ((double)i / (double)(nl - 1)) : lo;
+        lam[i] = std::exp(i == nl - 1 && nl > 1 ? hi : t);
+    }
+    return lam;
+}
+
+void check_common(const double* x, const double* y, int n, int p, int mem, const admm_opts* opts) {
+    ADMM_REQUIRE(x != nullptr && y != nullptr, "x and y must not be NULL");
+    ADMM_REQUIRE(n > 0 && p > 0, "n and p must be positive");
+    ADMM_REQUIRE(mem == ADMM_MEM_HOST || mem == ADMM_MEM_DEVICE, "mem must be ADMM_MEM_HOST or ADMM_MEM_DEVICE");
+    ADMM_REQUIRE(opts != nullptr, "opts must not be NULL");
+    ADMM_REQUIRE(opts->maxit > 0, "maxit should be positive");                                  // R/30_admm_lasso.R:119-120
+    ADMM_REQUIRE(opts->eps_abs >= 0 && opts->eps_rel >= 0, "eps_abs and eps_rel should be nonnegative");
+}
+
+PlanHandle* create_plan(const double* x, const double* y, int n, int p, int mem, const PathSpec& spec, int nworkers, const Shard& shard) {
+    const bool rows = shard.kind == Shard::ROWS, cols = shard.kind == Shard::COLS;
+    if (rows) ADMM_REQUIRE(shard.n_total >= n && n > 0, "n_total must be >= n_local > 0");
+    check_common(x, y, n, p, mem, spec.opts);
+    spec.check();
+    if (cols) {
+        ADMM_REQUIRE(shard.p_total >= p && shard.col_offset >= 0 && shard.col_offset + p <= shard.p_total, "column block outside [0, p_total)");
+        ADMM_REQUIRE(shard.p_total < (1ll << 31) - 1, "p_total too large");
+        ADMM_REQUIRE((long long)n <= shard.p_total, "the column-sharded solver is the wide one: it needs n <= p_total (Lasso.cpp:73)");
+        ADMM_REQUIRE(comm_info().active, "no communicator: call admm_hip_comm_init first");
+    } else if (rows) {
+        ADMM_REQUIRE(nworkers >= 0, "nthread must be >= 0");
+        ADMM_REQUIRE(comm_info().active, "no communicator: call admm_hip_comm_init first");
+        if (nworkers == 0) ADMM_REQUIRE(shard.n_total > p, "the row-sharded serial solver is the tall one: it needs n_total > p");
+    } else if (nworkers > 0) {
+        ADMM_REQUIRE(nworkers <= n, "more row blocks than rows");
+    }
+    require_device();
+    const double t0 = now_s();
+    std::unique_ptr<PlanHandle> h(new PlanHandle());
+    LassoProblem pb = spec.problem(cols ? 0 : nworkers, rows);
+    if (cols) { pb.p_total = shard.p_total; pb.col_offset = shard.col_offset; pb.profile_stride = 0; }
+    DeviceData<float> d;
+    const bool std_x = spec.standardize != 0, icpt = spec.intercept != 0;
+    // Host input of a large tall problem: standardisation and X'X run under the PCIe transfer (bit-identical result).
+    const bool pipelined = mem == ADMM_MEM_HOST && shard.kind == Shard::NONE && nworkers <= 0 && n > p && p >= 4096 && !opt_set(Opt::GRAM);
+    if (pipelined) upload_standardize_gram_f32(d, x, y, n, p, std_x, icpt, h->st.s);
+    else upload_standardize<float>(d, x, y, n, p, mem, std_x, icpt, h->st.s, shard.n_total, shard.ldx);   // COLS: column moments are local, y is replicated
+    if (cols) h->plan = make_wide_plan(std::move(d), pb, h->st.s);
+    else if (nworkers > 0) h->plan = make_par_plan(std::move(d), pb, h->st.s);
+    else if ((rows ? shard.n_total : (long long)n) > p) h->plan = make_tall_plan(std::move(d), pb, h->st.s);      // Lasso.cpp:73
+    else h->plan = make_wide_plan(std::move(d), pb, h->st.s);
+    h->p = cols ? (int)shard.p_total : p;
+    h->nlam = spec.nlam();
+    h->t_create = now_s() - t0;
+    return h.release();
+}
+
+void run_plan(PlanHandle* h, const PathOut& out, double t_extra) {
+    ADMM_REQUIRE(h != nullptr && h->plan, "plan is NULL");
+    out.require();
+    const double t0 = now_s();
+    LassoResult res;
+    res.beta_dst = out.beta_out;
+    h->plan->run(res);
+    const int nl = (int)res.lambda.size();
+    for (int i = 0; i < nl; ++i) { out.lambda_out[i] = res.lambda[i]; out.niter_out[i] = res.niter[i]; }
+    if (!res.beta_written) std::memcpy(out.beta_out, res.beta.data(), sizeof(float) * (size_t)(h->p + 1) * nl);
+    res.stats.t_total = now_s() - t0 + t_extra;
+    if (out.stats) *out.stats = res.stats;
+}
+
+void lasso_family(const double* x, const double* y, int n, int p, int mem, const PathSpec& spec, int nworkers, const Shard& shard, const PathOut& out) {
+    out.require();
+    std::unique_ptr<PlanHandle> h(create_plan(x, y, n, p, mem, spec, nworkers, shard));
+    run_plan(h.get(), out, h->t_create);
+}
+
+void parlasso(const double* x, const double* y, int n, int p, int mem, const PathSpec& spec, int nthread, const PathOut& out) {
+    ADMM_REQUIRE(nthread >= 1, "nthread must be >= 1");
+    const std::vector<int> devs = par_devices_for(nthread);
+    if (devs.empty()) {
+        record_single_layout();
+        lasso_family(x, y, n, p, mem, spec, nthread, Shard(), out);
+        return;
+    }
+    // in-process ranks: rank r holds the rows of its K / N whole blocks (admm_amd/dist.py row_partition)
+    out.require();
+    check_common(x, y, n, p, mem, spec.opts);
+    spec.check();
+    ADMM_REQUIRE(nthread <= n, "more row blocks than rows");
+    const int nl = spec.nlam();
+    run_inproc(devs, input_device(x, mem), [&](int rank, int nranks) {
+        const long long chunk = n / nthread, per = nthread / nranks;
+        const long long lo = rank * per * chunk, hi = rank == nranks - 1 ? n : (rank + 1) * per * chunk;
+        std::vector<double> lam_own; std::vector<float> beta_own; std::vector<int> nit_own;
+        admm_stats st_own;
+        PathOut mine = out;
+        if (rank != 0) {                                  // every rank computes the full result; the caller gets rank 0's
+            lam_own.resize(nl); beta_own.resize((size_t)(p + 1) * nl); nit_own.resize(nl);
+            mine = PathOut{lam_own.data(), beta_own.data(), nit_own.data(), &st_own};
+        }
+        lasso_family(x + lo, y + lo, (int)(hi - lo), p, mem, spec, nthread, Shard::rows(n, n), mine);
+    });
+}
+
+void sum_over_ranks(std::vector<double>& a, std::vector<double>& b, float* f, size_t nf, hipStream_t st) {
+    const CommInfo ci = comm_info();
+    if (!ci.active || ci.nranks <= 1) return;
+    const size_t na = a.size();
+    DevBuf<double> t(2 * na);
+    ADMM_HIP_CHECK(hipMemcpyAsync(t.get(), a.data(), na * sizeof(double), hipMemcpyHostToDevice, st));
+    ADMM_HIP_CHECK(hipMemcpyAsync(t.get() + na, b.data(), na * sizeof(double), hipMemcpyHostToDevice, st));
+    allreduce_sum_f64(t.get(), 2 * na, st);
+    ADMM_HIP_CHECK(hipMemcpyAsync(a.data(), t.get(), na * sizeof(double), hipMemcpyDeviceToHost, st));
+    ADMM_HIP_CHECK(hipMemcpyAsync(b.data(), t.get() + na, na * sizeof(double), hipMemcpyDeviceToHost, st));
+    comm_stream_sync(st);
+    comm_check();
+    if (!f) return;
+    DevBuf<float> fb(nf);
+    ADMM_HIP_CHECK(hipMemcpyAsync(fb.get(), f, nf * sizeof(float), hipMemcpyHostToDevice, st));
+    allreduce_sum_f32(fb.get(), nf, st);
+    read_back(f, fb.get(), nf * sizeof(float), st);
+    comm_stream_sync(st);
+    comm_check();
+}
+
+// Several responses of one design matrix ("batched / multi-response"): response j is the ordinary
+// fit of (x, Y[:, j]) -- bit-identical to admm_hip_lasso / admm_hip_enet on that pair -- but x is uploaded, converted and
+// standardised once, and for the tall solver X'X is formed once (it does not depend on y; the cached inverse does, through
+// rho, and is rebuilt per response).  With a communicator the responses are dealt out to the ranks (response j on rank
+// j mod nranks, independent replicas) and the outputs are summed over the ranks at the end.
+void lasso_multi(const double* x, const double* Y, int n, int p, int m, int mem, const PathSpec& spec, const PathOut& out) {
+    check_common(x, Y, n, p, mem, spec.opts);
+    ADMM_REQUIRE(m >= 1, "the number of responses must be >= 1");
+    out.require();
+    spec.check();
+    require_device();
+    const int nlam = spec.nlam();
+    const size_t bsz = (size_t)(p + 1) * nlam;
+    Stream st;
+    const Resident xr(x, (size_t)n * p, mem), yr(Y, (size_t)n * m, mem);
+    if (mem == ADMM_MEM_HOST) comm_stream_sync(st.s);
+    const double* xd = xr.p; const double* yd = yr.p;
+    const CommInfo ci = comm_info();
+    const int nranks = ci.active ? ci.nranks : 1, rank = ci.active ? ci.rank : 0;
+    std::vector<double> lam((size_t)m * nlam, 0.0), nit((size_t)m * nlam, 0.0);
+    std::memset(out.beta_out, 0, sizeof(float) * bsz * m);
+    if (out.stats) std::memset(out.stats, 0, sizeof(admm_stats) * (size_t)m);
+    LassoProblem pb = spec.problem(0, false);
+    pb.profile_stride = 0;
+
+    const bool tall = n > p;                                           // Lasso.cpp:73
+    DeviceData<float> base;
+    DevBuf<float> G;
+    long long ldg = 0;
+    double t_shared = 0;
+    int first = -1;
+    for (int j = 0; j < m; ++j) if (j % nranks == rank) { first = j; break; }
+    if (first >= 0) {
+        const double t0 = now_s();
+        upload_standardize<float>(base, xd, yd + (size_t)first * n, n, p, ADMM_MEM_DEVICE, spec.standardize != 0, spec.intercept != 0, st.s, 0);
+        if (tall) {
+            ldg = round_up(p, 128);
+            G.alloc((size_t)ldg * ldg); G.zero(st.s);
+            gram_full<float>(base.X.get(), base.ldx, n, p, true, G.get(), ldg, st.s);
+            comm_stream_sync(st.s);
+        }
+        t_shared = now_s() - t0;
+    }
+    for (int j = 0; j < m; ++j) {
+        if (j % nranks != rank) continue;
+        const double t0 = now_s();
+        DeviceData<float> d;
+        clone_with_response_f32(d, base, tall ? G.get() : nullptr, ldg, yd + (size_t)j * n, st.s);
+        std::unique_ptr<LassoPlan> plan = tall ? make_tall_plan(std::move(d), pb, st.s) : make_wide_plan(std::move(d), pb, st.s);
+        LassoResult res;
+        plan->run(res);
+        ADMM_REQUIRE((int)res.lambda.size() == nlam, "internal: unexpected path length");
+        for (int l = 0; l < nlam; ++l) { lam[(size_t)j * nlam + l] = res.lambda[l]; nit[(size_t)j * nlam + l] = res.niter[l]; }
+        std::memcpy(out.beta_out + (size_t)j * bsz, res.beta.data(), sizeof(float) * bsz);
+        if (out.stats) { out.stats[j] = res.stats; out.stats[j].t_total = now_s() - t0 + (j == first ? t_shared : 0.0); }
+    }
+    sum_over_ranks(lam, nit, out.beta_out, bsz * m, st.s);             // the other ranks' responses
+    for (size_t k = 0; k < lam.size(); ++k) { out.lambda_out[k] = lam[k]; out.niter_out[k] = (int)std::llround(nit[k]); }
+}
+
+// ---- the dense solvers (LAD, BP, ParBP) and the Dantzig selector: double precision, one solve per call
+namespace {
+template <typename R>
+void begin_result(R& res, const DeviceData<double>& d, const TraceOut& trace) {
+    res.trace_cap = trace.cap;
+    res.stats.t_h2d = d.t_h2d;
+    res.stats.t_standardize = d.t_std;
+}
+template <typename R>
+void finish_result(R& res, double t0, const TraceOut& trace, admm_stats* stats) {
+    trace.store(res.trace);
+    res.stats.t_total = now_s() - t0;
+    if (stats) *stats = res.stats;
+}
+
+// What LAD, BP and ParBP share.  The standardise flags are fixed by the reference per solver; shape_ok / shape_msg is the solver's
+// precondition on the shape, blocks_ok ParBP's on nthread; `solve` fills res.beta with ncoef coefficients.
+using DenseSolve = std::function<void(const DeviceData<double>&, DenseResult&, hipStream_t)>;
+void run_dense(const double* x, const double* y, int n, int p, int mem, const admm_opts* opts, bool standardize, bool intercept,
+               bool shape_ok, const char* shape_msg, bool blocks_ok, int ncoef, const DenseSolve& solve, const DenseOut& out) {
+    const StateOut& so = out.state;
+    out.trace.check();
+    ADMM_REQUIRE(so.cap == 0 || (so.out != nullptr && so.n_out != nullptr && so.cap > 0 && out.trace.cap > 0), "bad state arguments (the iterate dump needs the trace)");
+    check_common(x, y, n, p, mem, opts);
+    ADMM_REQUIRE(out.beta_out && out.niter_out, "output pointers must not be NULL");
+    ADMM_REQUIRE(shape_ok, shape_msg);
+    ADMM_REQUIRE(opts->rho > 0, "rho should be positive");
+    ADMM_REQUIRE(blocks_ok, "nthread must be within [1, ncol(x)]");
+    require_device();
+    const double t0 = now_s();
+    Stream st;
+    DeviceData<double> d;
+    upload_standardize<double>(d, x, y, n, p, mem, standardize, intercept, st.s);
+    DenseResult res;
+    begin_result(res, d, out.trace);
+    res.state_cap = so.cap;
+    solve(d, res, st.s);
+    for (int i = 0; i < ncoef; ++i) out.beta_out[i] = res.beta[i];
+    out.niter_out[0] = res.niter;
+    if (so.cap > 0) {
+        std::memcpy(so.out, res.state.data(), res.state.size() * sizeof(double));
+        *so.n_out = res.state_dim > 0 ? (long long)(res.state.size() / (5 * (size_t)res.state_dim)) : 0;
+    }
+    finish_result(res, t0, out.trace, out.stats);
+}
+}  // namespace
+
+void lad(const double* x, const double* y, int n, int p, int mem, int intercept, const admm_opts* opts, const DenseOut& out) {
+    run_dense(x, y, n, p, mem, opts, true, intercept != 0,                           // LAD.cpp:34: standardize always TRUE
+              n > p, "nrow(x) must be greater than ncol(x)", true, p + 1,            // R/20_admm_lad.R:21-22
+              [&](const DeviceData<double>& d, DenseResult& res, hipStream_t st) { solve_lad(d, *opts, res, st); }, out);
+}
+
+void bp(const double* x, const double* y, int n, int p, int mem, const admm_opts* opts, const DenseOut& out) {
+    run_dense(x, y, n, p, mem, opts, false, false,                                   // BP.cpp:24-27: no standardisation
+              p > n, "ncol(x) must be greater than nrow(x)", true, p,                // R/10_admm_bp.R:30-31
+              [&](const DeviceData<double>& d, DenseResult& res, hipStream_t st) { solve_bp(d, *opts, res, st); }, out);
+}
+
+// admm_parbp (R/10_admm_bp.R:111-116; TODO/ParBP.cppp:26-71): opts->rho carries rho_ratio.
+static void parbp_cols(const double* x_cols, const double* y, int n, int p_local, long long p_total, long long col_offset, int mem, int nthread,
+                       const admm_opts* opts, const DenseOut& out) {
+    run_dense(x_cols, y, n, p_local, mem, opts, false, false,                        // ParBP.cppp:36-37: no standardisation
+              p_total > n, "ncol(x) must be greater than nrow(x)", nthread >= 1 && nthread <= p_total, p_local,
+              [&](const DeviceData<double>& d, DenseResult& res, hipStream_t st) { solve_parbp(d, *opts, nthread, p_total, col_offset, res, st); }, out);
+}
+
+void parbp(const double* x, const double* y, int n, int p, int mem, int nthread, const admm_opts* opts, const DenseOut& out) {
+    const std::vector<int> devs = nthread >= 1 ? par_devices_for(nthread) : std::vector<int>();
+    if (devs.empty()) {
+        record_single_layout();
+        parbp_cols(x, y, n, p, p, 0, mem, nthread, opts, out);
+        return;
+    }
+    // in-process ranks: rank r holds its whole blocks of columns (admm_amd/dist.py parbp_partition)
+    out.trace.check();
+    ADMM_REQUIRE(x != nullptr && out.beta_out && out.niter_out, "x and the output pointers must not be NULL");
+    ADMM_REQUIRE(n > 0 && p > 0, "n and p must be positive");
+    ADMM_REQUIRE(nthread >= 1 && nthread <= p, "nthread must be within [1, ncol(x)]");
+    run_inproc(devs, input_device(x, mem), [&](int rank, int nranks) {
+        const long long chunk = p / nthread, per = nthread / nranks;
+        const long long lo = rank * per * chunk, hi = rank == nranks - 1 ? p : (rank + 1) * per * chunk;
+        int nit = 0;
+        admm_stats st_own;
+        const DenseOut mine = {out.beta_out + lo, &nit, rank == 0 ? out.stats : &st_own, rank == 0 ? out.trace : TraceOut{}, out.state};
+        parbp_cols(x + (size_t)lo * n, y, n, (int)(hi - lo), p, lo, mem, nthread, opts, mine);
+        if (rank == 0) out.niter_out[0] = nit;
+    });
+}
+
+void parbp_dist(const double* x_cols, const double* y, int n, int p_local, long long p_total, long long col_offset, int mem, int nthread,
+                const admm_opts* opts, const DenseOut& out) {
+    ADMM_REQUIRE(comm_info().active, "no communicator: call admm_hip_comm_init first");
+    ADMM_REQUIRE(p_total >= p_local && col_offset >= 0 && col_offset + p_local <= p_total, "column block outside [0, p_total)");
+    parbp_cols(x_cols, y, n, p_local, p_total, col_offset, mem, nthread, opts, out);
+}
+
+// admm_dantzig (R/50_admm_dantzig.R:30-46; TODO/Dantzig.cpp:32-99)
+void dantzig(const double* x, const double* y, int n, int p, int mem, const PathSpec& spec, const PathOutT<double>& out, const TraceOut& trace) {
+    trace.check();
+    check_common(x, y, n, p, mem, spec.opts);
+    out.require();
+    spec.check();
+    ADMM_REQUIRE(p >= 3, "the spectral-radius estimate needs at least 3 columns");
+    require_device();
+    const double t0 = now_s();
+    Stream st;
+    DeviceData<double> d;
+    upload_standardize<double>(d, x, y, n, p, mem, spec.standardize != 0, spec.intercept != 0, st.s);     // Dantzig.cpp:52-55
+    const LassoProblem pb = spec.problem(0, false);
+    DantzigResult res;
+    begin_result(res, d, trace);
+    solve_dantzig(d, pb, res, st.s);
+    const int nl = (int)res.lambda.size();
+    for (int i = 0; i < nl; ++i) { out.lambda_out[i] = res.lambda[i]; out.niter_out[i] = res.niter[i]; }
+    std::memcpy(out.beta_out, res.beta.data(), sizeof(double) * (size_t)(p + 1) * nl);
+    finish_result(res, t0, trace, out.stats);
+}
+
+}  // namespace admm

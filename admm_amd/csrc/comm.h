@@ -63,6 +63,14 @@ PeerExchange comm_peer_begin(size_t payload_bytes);
 struct PeerAux;
 PeerAux comm_peer_aux();
 
+// Bootstrap of the process-wide communicator (admm_hip_comm_*): RCCL from a unique id, SHM from a named segment, PEER in two steps.
+int comm_unique_id(void* out);
+void comm_init(int nranks, int rank, const void* idbytes);
+void comm_init_shm(int nranks, int rank, const char* name, unsigned long long token);
+void comm_peer_prepare(int nranks, void* handle_out);
+void comm_init_peer(int nranks, int rank, const void* handles);
+void comm_finalize();
+
 // True while a process-wide communicator is attached (admm_hip_comm_init*), whatever the calling thread's current context.
 bool comm_process_attached();
 // In-process group: PEER over device pointers swapped in host memory (peer access enabled between the listed devices, no hipIpc).

@@ -690,7 +690,7 @@ void comm_finalize() {
     C().seq = 0;
 }
 
-// ---------------------------------------------------------------------------------------------- in-process group (api.hip)
+// ---------------------------------------------------------------------------------------------- in-process group (inproc.hip)
 // The PEER backend with its bootstrap inside one process: every rank thread allocates its exchange buffer on its own device
 // (fine-grained, peer_alloc_local) and the threads swap the plain device pointers through host memory -- peer access was
 // enabled between the listed devices when the group was created, so no hipIpc handle is needed.  The kernels and the slot

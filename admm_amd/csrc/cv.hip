@@ -4,7 +4,8 @@
 // bit-identical to a user-side call on that row subset (unless the folds are formed as down-dates of the full-data Gram,
 // second half of this file) -- plus two small kernels: a row gather that builds the training /
 // held-out matrices on the device from one resident copy of X, and the held-out squared prediction error for every lambda.
-#include "solvers.h"
+#include "calls.h"
+#include "test_hooks.h"
 #include "comm.h"
 #include "device_utils.h"
 #include "prep.h"
@@ -256,6 +257,144 @@ void cv_downdate_fold(DeviceData<float>& d, const CvBase& b, const double* yd, c
     ADMM_HIP_CHECK(hipGetLastError());
     comm_stream_sync(st);
     d.t_gram_tail = now_s() - t0;
+}
+
+// ================================================================================================ the driver
+// The full-data fit fixes the lambda grid; fold f is the ordinary plan on the rows with fold_id != f, scored on the rows with
+// fold_id == f.  With a communicator the folds are dealt out to the ranks (fold f on rank f mod nranks: independent replicas,
+// nothing exchanged on the data path) and the score / iteration tables are summed over the ranks at the end.
+void lasso_cv(const double* x, const double* y, int n, int p, int mem, const int* fold_id, int nfolds, const PathSpec& spec,
+              const PathOut& out, const CvOut& cv) {
+    check_common(x, y, n, p, mem, spec.opts);
+    ADMM_REQUIRE(nfolds >= 2 && nfolds <= n, "nfolds must be within [2, n]");
+    ADMM_REQUIRE(out.lambda_out && cv.cv_mean && cv.cv_se, "lambda_out, cv_mean and cv_se must not be NULL");
+    spec.check();
+    std::vector<int> fid(n);
+    for (int i = 0; i < n; ++i) {
+        fid[i] = fold_id ? fold_id[i] : i % nfolds;
+        ADMM_REQUIRE(fid[i] >= 0 && fid[i] < nfolds, "fold_id entries must be within [0, nfolds)");
+    }
+    std::vector<int> cnt(nfolds, 0);
+    for (int i = 0; i < n; ++i) ++cnt[fid[i]];
+    for (int f = 0; f < nfolds; ++f) ADMM_REQUIRE(cnt[f] > 0 && cnt[f] < n, "every fold needs at least one held-out row and one training row");
+    require_device();
+    const double t0 = now_s();
+    Stream st;
+    const Resident xr(x, (size_t)n * p, mem), yr(y, n, mem);       // folds are gathered from it on the device
+    if (mem == ADMM_MEM_HOST) comm_stream_sync(st.s);
+    const double* xd = xr.p; const double* yd = yr.p;
+    // Folds as down-dates of the full-data Gram (above): when every fit of the call is the tall solver's and the Gram is
+    // what setup costs (p >= 1024; ADMM_HIP_CV_DOWNDATE=1 / 0 forces it on for any tall call / off).
+    int min_tr = n;
+    for (int f = 0; f < nfolds; ++f) min_tr = std::min(min_tr, n - cnt[f]);
+    bool downdate = min_tr > p && p >= 1024;
+    if (opt_set(Opt::CV_DOWNDATE)) downdate = min_tr > p && opt_on(Opt::CV_DOWNDATE);
+    CvBase base;
+    if (downdate) cv_downdate_prepare(base, xd, yd, n, p, spec.standardize != 0, spec.intercept != 0, st.s);
+    // a fit of the call: the down-dated Gram form `d` when there is one, else the ordinary plan on the rows given
+    auto fit = [&](const PathSpec& s, DeviceData<float>* d, const double* xr_, const double* yr_, int rows, LassoResult& res) {
+        std::unique_ptr<PlanHandle> h;
+        if (d) {
+            h.reset(new PlanHandle());
+            h->plan = make_tall_plan(std::move(*d), s.problem(0, false), h->st.s);
+        } else {
+            h.reset(create_plan(xr_, yr_, rows, p, ADMM_MEM_DEVICE, s, 0));
+        }
+        h->plan->run(res);
+    };
+    // ---- full-data fit: the lambda grid (and, if asked for, the coefficients)
+    LassoResult full;
+    {
+        DeviceData<float> d;
+        if (downdate) cv_downdate_full(d, base, st.s);
+        fit(spec, downdate ? &d : nullptr, xd, yd, n, full);
+    }
+    const std::vector<double>& lam = full.lambda;
+    const int nlam = (int)lam.size();
+    for (int l = 0; l < nlam; ++l) out.lambda_out[l] = lam[l];
+    if (out.beta_out) std::memcpy(out.beta_out, full.beta.data(), sizeof(float) * (size_t)(p + 1) * nlam);
+    if (out.niter_out) for (int l = 0; l < nlam; ++l) out.niter_out[l] = full.niter[l];
+    if (out.stats) *out.stats = full.stats;
+    // ---- folds
+    const PathSpec fold_spec = spec.on_grid(lam);
+    const CommInfo ci = comm_info();
+    const int nranks = ci.active ? ci.nranks : 1, rank = ci.active ? ci.rank : 0;
+    const size_t bsz = (size_t)(p + 1) * nlam;
+    std::vector<double> mse((size_t)nfolds * nlam, 0.0);
+    std::vector<double> nit((size_t)nfolds * nlam, 0.0);         // as doubles: summed over ranks with the scores
+    if (cv.fold_beta) std::memset(cv.fold_beta, 0, sizeof(float) * bsz * nfolds);
+    DevBuf<int> didx(n);
+    for (int f = 0; f < nfolds; ++f) {
+        if (f % nranks != rank) continue;
+        std::vector<int> tr, te;
+        for (int i = 0; i < n; ++i) (fid[i] == f ? te : tr).push_back(i);
+        const int ntr = (int)tr.size(), nte = (int)te.size();
+        std::vector<int> both(tr);
+        both.insert(both.end(), te.begin(), te.end());
+        ADMM_HIP_CHECK(hipMemcpyAsync(didx.get(), both.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, st.s));
+        DevBuf<double> xtr, ytr, xte((size_t)nte * p), yte(nte);
+        cv_gather(xd, n, yd, didx.get() + ntr, nte, p, xte.get(), yte.get(), st.s);
+        LassoResult res;
+        if (downdate) {
+            DeviceData<float> d;
+            cv_downdate_fold(d, base, yd, didx.get(), ntr, didx.get() + ntr, nte, st.s);
+            fit(fold_spec, &d, nullptr, nullptr, 0, res);
+        } else {
+            xtr.alloc((size_t)ntr * p); ytr.alloc(ntr);
+            cv_gather(xd, n, yd, didx.get(), ntr, p, xtr.get(), ytr.get(), st.s);
+            comm_stream_sync(st.s);
+            fit(fold_spec, nullptr, xtr.get(), ytr.get(), ntr, res);
+        }
+        const std::vector<double> sse = cv_score(xte.get(), yte.get(), nte, p, res.beta.data(), nlam, st.s);
+        for (int l = 0; l < nlam; ++l) { mse[(size_t)f * nlam + l] = sse[l] / nte; nit[(size_t)f * nlam + l] = res.niter[l]; }
+        if (cv.fold_beta) std::memcpy(cv.fold_beta + (size_t)f * bsz, res.beta.data(), sizeof(float) * bsz);
+    }
+    sum_over_ranks(mse, nit, cv.fold_beta, bsz * nfolds, st.s);    // folds of the other ranks
+    // ---- summary: mean over folds, standard error sd / sqrt(K) (sample sd over the folds), minimum and one-standard-error rule
+    int imin = 0;
+    for (int l = 0; l < nlam; ++l) {
+        double m = 0;
+        for (int f = 0; f < nfolds; ++f) m += mse[(size_t)f * nlam + l];
+        m /= nfolds;
+        double v = 0;
+        for (int f = 0; f < nfolds; ++f) { const double d = mse[(size_t)f * nlam + l] - m; v += d * d; }
+        cv.cv_mean[l] = m;
+        cv.cv_se[l] = std::sqrt(v / (nfolds - 1) / nfolds);
+        if (cv.cv_mean[l] < cv.cv_mean[imin]) imin = l;
+    }
+    int i1se = imin;
+    for (int l = 0; l < nlam; ++l) if (lam[l] > lam[i1se] && cv.cv_mean[l] <= cv.cv_mean[imin] + cv.cv_se[imin]) i1se = l;   // largest lambda within one standard error
+    if (cv.idx_min) *cv.idx_min = imin;
+    if (cv.idx_1se) *cv.idx_1se = i1se;
+    if (cv.fold_mse) std::memcpy(cv.fold_mse, mse.data(), mse.size() * sizeof(double));
+    if (cv.fold_niter) for (size_t k = 0; k < nit.size(); ++k) cv.fold_niter[k] = (int)std::llround(nit[k]);
+    if (out.stats) out.stats->t_total = now_s() - t0;
+}
+
+// admm_hip_test_cv_fold_system: the down-dated system of one fold, read back
+void test_cv_fold_system(const double* x, const double* y, int n, int p, const int* fold_id, int nfolds, int fold,
+                         int standardize, int intercept, float* gram, float* xy, float* mean_x, float* scale_x, float* mean_scale_y) {
+    ADMM_REQUIRE(x && y && gram && xy && mean_x && scale_x && mean_scale_y && n > 0 && p > 0, "bad arguments");
+    ADMM_REQUIRE(nfolds >= 2 && fold >= 0 && fold < nfolds, "fold must be within [0, nfolds)");
+    require_device();
+    Stream st;
+    const Resident xd(x, (size_t)n * p, ADMM_MEM_HOST), yd(y, n, ADMM_MEM_HOST);
+    std::vector<int> tr, te;
+    for (int i = 0; i < n; ++i) ((fold_id ? fold_id[i] : i % nfolds) == fold ? te : tr).push_back(i);
+    const int ntr = (int)tr.size(), nte = (int)te.size();
+    ADMM_REQUIRE(ntr > p && nte > 0, "the fold needs held-out rows and more training rows than columns");
+    std::vector<int> both(tr);
+    both.insert(both.end(), te.begin(), te.end());
+    DevBuf<int> didx(n);
+    ADMM_HIP_CHECK(hipMemcpyAsync(didx.get(), both.data(), (size_t)n * sizeof(int), hipMemcpyHostToDevice, st.s));
+    CvBase base;
+    cv_downdate_prepare(base, xd.p, yd.p, n, p, standardize != 0, intercept != 0, st.s);
+    DeviceData<float> d;
+    cv_downdate_fold(d, base, yd.p, didx.get(), ntr, didx.get() + ntr, nte, st.s);
+    ADMM_HIP_CHECK(hipMemcpy2D(gram, (size_t)p * sizeof(float), d.gram.get(), (size_t)d.ldgram * sizeof(float), (size_t)p * sizeof(float), p, hipMemcpyDeviceToHost));
+    ADMM_HIP_CHECK(hipMemcpy(xy, d.xy.get(), (size_t)p * sizeof(float), hipMemcpyDeviceToHost));
+    for (int j = 0; j < p; ++j) { mean_x[j] = d.meanX[j]; scale_x[j] = d.scaleX[j]; }
+    mean_scale_y[0] = d.meanY; mean_scale_y[1] = d.scaleY;
 }
 
 }  // namespace admm

@@ -1,0 +1,14 @@
+// The test hooks behind the C ABI (include/admm_hip.h, "test hooks"): test_hooks.hip, and cv.hip for the fold system.
+#pragma once
+
+namespace admm {
+
+void test_symv(const float* A, int p, const float* v0, const float* v1, float* y0, float* y1);
+template <typename T> void test_gram(const T* A, int rows, int cols, bool atA, T* G);
+template <typename T> void test_spd_inverse(const T* A, int n, T* Ainv, bool via64);
+template <typename T> void test_gemv_t(const T* A, int rows, int cols, const T* v, T* y);
+template <typename T> void test_gather(const T* A, int rows, int cols, const T* v, double* y);
+void test_cv_fold_system(const double* x, const double* y, int n, int p, const int* fold_id, int nfolds, int fold,
+                         int standardize, int intercept, float* gram, float* xy, float* mean_x, float* scale_x, float* mean_scale_y);
+
+}  // namespace admm

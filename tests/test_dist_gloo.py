@@ -346,7 +346,7 @@ def test_two_rank_column_sharded_wide_protocol_matches_serial_oracle(tmp_path):
 
 # ------------------------------------------------------------------------------------------------------------------
 # Replicas with a final exchange (admm_hip_lasso_cv, admm_hip_lasso_multi): world_size-2 model of the dealing rule of
-# api.hip -- unit u (fold / response) runs on rank u mod world, every rank starts from zeroed tables, ONE sum all-reduce at
+# cv.hip / calls.hip -- unit u (fold / response) runs on rank u mod world, every rank starts from zeroed tables, ONE sum all-reduce at
 # the end -- with the oracle as the fit.  Every rank must end with the tables a single process computes.
 def _replica_rank_main(rank, world, port, x, y, nfolds, lam, out_path):
     from oracle import entry
