@@ -27,6 +27,7 @@
 #include "gemv_kernels.h"
 #include "solvers.h"
 #include "loop_driver.h"
+#include "plan_host.h"
 
 namespace admm {
 
@@ -176,10 +177,8 @@ void solve_dantzig(DeviceData<double>& d, const LassoProblem& pb, DantzigResult&
     double lambda0 = 0, xyn = 0;
     for (int j = 0; j < p; ++j) { lambda0 = std::max(lambda0, std::fabs(hxy[j])); xyn += hxy[j] * hxy[j]; }
     xyn = std::sqrt(xyn);
-    res.lambda = make_lambda_grid(pb, lambda0, n, (double)d.scaleY);
-    const int nlam = (int)res.lambda.size();
-    std::vector<double> lam_int(nlam);
-    for (int i = 0; i < nlam; ++i) lam_int[i] = res.lambda[i] * (double)n / (double)d.scaleY;
+    std::vector<double> lam_int;
+    const int nlam = make_path_grid<double>(pb, lambda0, n, (double)d.scaleY, res.lambda, lam_int);
 
     // ---- the operator A = X'X: explicit for small tall problems, two streaming products otherwise (ADMMDantzig.h:222-224)
     const bool use_xx = n > p && p <= 1000;
@@ -255,30 +254,13 @@ void solve_dantzig(DeviceData<double>& d, const LassoProblem& pb, DantzigResult&
         hipLaunchKernelGGL(dz_mid_kernel, dim3(nwg), dim3(kDzThreads), 0, st, q, par ^ 1);
         amult(x.get(), Ax.get(), skip);
         hipLaunchKernelGGL(dz_tail_kernel, dim3(nwg), dim3(kDzThreads), 0, st, q, par ^ 1);
-    }, hflag.p);
+    }, LoopOpts{hflag.p});
 
     // ---- results: recover every column (Dantzig.cpp:88-93)
     std::vector<double> hb((size_t)nlam * p);
-    std::vector<int> hn(nlam);
     read_back(hb.data(), beta.get(), hb.size() * sizeof(double), st);
-    ADMM_HIP_CHECK(hipMemcpy(hn.data(), dniter.get(), (size_t)nlam * sizeof(int), hipMemcpyDeviceToHost));
-    res.beta.assign((size_t)(p + 1) * nlam, 0.0);
-    res.niter = hn;
-    long long tot = 0;
-    for (int i = 0; i < nlam; ++i) {
-        double b0 = 0;
-        recover_coef<double>(d, hb.data() + (size_t)i * p, &b0, res.beta.data() + (size_t)i * (p + 1) + 1);
-        res.beta[(size_t)i * (p + 1)] = b0;
-        tot += std::min(hn[i], pb.opts.maxit);
-    }
-    if (res.trace_cap > 0) {
-        DzCtl hc[2];
-        ADMM_HIP_CHECK(hipMemcpy(hc, ctl.get(), sizeof(hc), hipMemcpyDeviceToHost));
-        const long long nrec = std::min<long long>(std::max(hc[0].total, hc[1].total), res.trace_cap);
-        res.trace.assign((size_t)nrec * ADMM_TRACE_FIELDS, 0.0);
-        if (nrec > 0) read_back(res.trace.data(), trace.get(), res.trace.size() * sizeof(double), st);
-    }
-    S.total_iter = tot;
+    S.total_iter = read_out_path<double>(d, hb.data(), nlam, dniter.get(), (size_t)p + 1, 0, res.niter, res.beta, pb.opts.maxit);
+    if (res.trace_cap > 0) collect_records(res.trace, trace.get(), ADMM_TRACE_FIELDS, read_ctl(ctl.get()).total(), res.trace_cap, st);
     S.t_loop = lt.wall_s;
     S.loop_ms_events = lt.events_ms;
     S.xupdate_variant = use_xx ? 0 : 1;

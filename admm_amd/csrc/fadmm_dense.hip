@@ -476,14 +476,11 @@ __global__ void __launch_bounds__(256) copy_cols_f64_kernel(const double* __rest
 // copies the decision records of a finished loop into the result
 static void dense_collect_trace(DenseLoop& L, const DenseCtl& fc, DenseResult& res, hipStream_t st) {
     if (res.trace_cap <= 0) return;
-    const long long nrec = std::min<long long>(fc.total + (fc.done ? 1 : 0), res.trace_cap);      // the finishing decision does not advance `total`
-    res.trace.resize((size_t)nrec * ADMM_TRACE_FIELDS);
-    if (nrec > 0) read_back(res.trace.data(), L.trace.get(), res.trace.size() * sizeof(double), st);
+    const long long taken = fc.total + (fc.done ? 1 : 0);      // the finishing decision does not advance `total`
+    collect_records(res.trace, L.trace.get(), ADMM_TRACE_FIELDS, taken, res.trace_cap, st);
     if (res.state_cap > 0) {                                   // one record per decision, same numbering as the trace
-        const long long ns = std::min<long long>(fc.total + (fc.done ? 1 : 0), res.state_cap);
         res.state_dim = L.q.dim;
-        res.state.resize((size_t)ns * 5 * L.q.dim);
-        if (ns > 0) read_back(res.state.data(), L.state.get(), res.state.size() * sizeof(double), st);
+        collect_records(res.state, L.state.get(), 5ll * L.q.dim, taken, res.state_cap, st);
     }
 }
 

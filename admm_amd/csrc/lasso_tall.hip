@@ -37,6 +37,7 @@
 #include "solvers.h"
 #include "comm.h"
 #include "loop_driver.h"
+#include "plan_host.h"
 #include "peer_device.h"
 #include "probe.h"
 
@@ -430,6 +431,7 @@ struct TallPlan final : LassoPlan {
     bool shard = false;                                 // x-update spread over the ranks of the attached communicator
     bool peer_fused = false;                            // ... with the exchange done by the solver's own kernels (PEER backend)
     bool peer_one = false;                              // ... producer and consumer in one launch (tall_tail_kernel<TAIL_PEER1>)
+    int exchange_code = 0;                              // ... as admm_stats.exchange_variant reports it
     CommInfo ci;
     DevBuf<float> ab;                                   // [2][ldp] this rank's share of (a, b), all-reduced in place
     double dist_flops = 0;                              // distributed factorisation: flops this rank performed (0: replicated)
@@ -439,15 +441,10 @@ struct TallPlan final : LassoPlan {
     DevBuf<double> P, dlam;
     DevBuf<TallCtl> ctl;
     TallParams q{};
-    DevBuf<double> trace;
-    long long trace_cap = 0, trace_n = 0;
-    DevBuf<float> state;
-    long long state_cap = 0;
     // mixed-precision refinement of the x-update (ADMM_HIP_REFINE=1)
     bool refine = false;
     DevBuf<float> Mg, rab, ruw;                          // the float system X'X + rho I; first solve a | b; residuals r_u | r_w
     DevBuf<double> dD0, dD1, xD0, xD1;                   // double partial arrays of M x1
-    TallCtl* hctl = nullptr;
     PinnedFlag hflag;
 #ifdef ADMM_HIP_PROBE
     DevBuf<long long> probe;
@@ -457,7 +454,6 @@ struct TallPlan final : LassoPlan {
     std::vector<hipEvent_t> ev_pool;                    // start/stop events of sampled x-update launches, reused by every run()
 
     ~TallPlan() override {
-        if (hctl) (void)hipHostFree(hctl);
         if (hbeta) (void)hipHostFree(hbeta);
         for (auto e : ev_pool) (void)hipEventDestroy(e);
     }
@@ -490,10 +486,7 @@ struct TallPlan final : LassoPlan {
         if (pb.enet) lambda0 = (float)(lambda0 / ((double)(float)pb.alpha + 0.0001));
 
         // lambda grid (Lasso.cpp:78-89) and internal lambdas (Lasso.cpp:99), stored as float like `Scalar lambda`
-        lam_user = make_lambda_grid(pb, lambda0, (int)nt, (double)d.scaleY);
-        nlam = (int)lam_user.size();
-        lam_int.resize(nlam);
-        for (int i = 0; i < nlam; ++i) lam_int[i] = (double)(float)(lam_user[i] * (double)nt / (double)d.scaleY);
+        nlam = make_path_grid<float>(pb, lambda0, nt, (double)d.scaleY, lam_user, lam_int);
 
         // Memory wall: this solver keeps (X'X + rho I)^-1, ldp^2 floats, next to X (until the loop starts), the Gram and -- below
         // p = 4096 or with ADMM_HIP_INVERSE=f64 -- a double copy during the factorisation.  Refuse clearly instead of failing
@@ -659,17 +652,8 @@ struct TallPlan final : LassoPlan {
         }
         if (shard) { ab.alloc((size_t)2 * ldp); ab.zero(st); }
         else if (!use_sym) { a_part.alloc((size_t)pl.nseg * ldp); b_part.alloc((size_t)pl.nseg * ldp); a_part.zero(st); b_part.zero(st); }
-        // ADMM_HIP_PEER_FUSED=0: go through the generic all-reduce of the exchange layer also on the PEER backend
-        peer_fused = shard && ci.backend == COMM_PEER;
-        if (opt_is(Opt::PEER_FUSED, "0")) peer_fused = false;
-        if (peer_fused) {
-            // one launch only when the whole grid is resident with room to spare (its workgroups wait for one another)
-            int occ = 0;
-            ADMM_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void*>(tall_tail_kernel<TAIL_PEER1>), kTailThreads, 0));
-            const int nwg_tail = (p + kTailElems - 1) / kTailElems;
-            peer_one = (long long)nwg_tail * 2 <= resident_workgroups(occ);
-            if (opt_is(Opt::PEER_FUSED, "2")) peer_one = false;
-        }
+        const ExchangeForm xf = peer_exchange_form(shard, ci, reinterpret_cast<const void*>(tall_tail_kernel<TAIL_PEER1>), kTailThreads, nwg);
+        peer_fused = xf.fused; peer_one = xf.one; exchange_code = xf.variant;
         // (A single-launch iteration -- tail, decision and tiles in one launch -- and a hipGraph replay of the batch were built, measured
         // bit-identical and SLOWER on C2 in rounds 4 / 5 (44.5 and 46.9 us per iteration against 42.1 / 46.6): removed in round 6,
         // profiles/HISTORY.md.)
@@ -698,38 +682,11 @@ struct TallPlan final : LassoPlan {
         sy.probe = probe.get();
 #endif
 
-        // Pinned mirror of the control block for asynchronous polling.
-        ADMM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&hctl), 2 * sizeof(TallCtl), hipHostMallocDefault));
         ADMM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&hbeta), (size_t)nlam * p * sizeof(float), hipHostMallocDefault));
         comm_stream_sync(st);
     }
 
-    void enable_trace(long long cap) override {
-        trace.alloc((size_t)cap * ADMM_TRACE_FIELDS);
-        trace_cap = cap; trace_n = 0;
-        q.trace = trace.get(); q.trace_cap = cap;
-    }
-    long long read_trace(double* out, long long cap) override {
-        const long long nrec = std::min(std::min(trace_n, trace_cap), cap);
-        if (nrec > 0) read_back(out, trace.get(), (size_t)nrec * ADMM_TRACE_FIELDS * sizeof(double), st);
-        return nrec;
-    }
-
-    void enable_state(long long cap) override {
-        state.alloc((size_t)cap * 5 * p);
-        // on the solver's own (non-blocking) stream: a null-stream memset is not ordered against it and, on a busy device, landed
-        // AFTER run() had copied record 0 into the dump (suspected cause of the one unreadable record 0 of the 40-process soak, case 546:23)
-        ADMM_HIP_CHECK(hipMemsetAsync(state.get(), 0, (size_t)cap * 5 * p * sizeof(float), st));
-        state_cap = cap;
-        q.state = state.get(); q.state_cap = cap;
-    }
-    long long read_state(float* out, long long cap, long long* rec_floats) override {
-        if (rec_floats) *rec_floats = 5ll * p;
-        if (!out) return std::min(trace_n, state_cap);                             // size query
-        const long long nrec = std::min(std::min(trace_n, state_cap), cap);       // one record per decision, same numbering as the trace
-        if (nrec > 0 && out) read_back(out, state.get(), (size_t)nrec * 5 * p * sizeof(float), st);
-        return nrec;
-    }
+    Records records() override { return {st, 5ll * p, &q.trace, &q.trace_cap, &q.state, &q.state_cap}; }
 
     void read_system(float* out, long long ld) override {
         if (!refine) throw Error(ADMM_ERR_INVALID_ARG, "the system matrix is only kept with ADMM_HIP_REFINE=1");
@@ -741,7 +698,7 @@ struct TallPlan final : LassoPlan {
     void run(LassoResult& res) override {
         admm_stats S = setup_stats;
         S.xupdate_variant = shard ? 2 : (use_sym ? 1 : 0);
-        S.exchange_variant = !shard ? 0 : (!peer_fused ? 1 : (peer_one ? 3 : 2));
+        S.exchange_variant = exchange_code;
         S.refine = refine ? 1 : 0;
         S.factor_flops = dist_flops;
         res.lambda = lam_user;
@@ -750,7 +707,6 @@ struct TallPlan final : LassoPlan {
         hipLaunchKernelGGL(tall_init_kernel, dim3((init_n + 255) / 256), dim3(256), 0, st, q, rho, lam_int[0]);
         if (q.state != nullptr)      // record 0 of the iterate dump (the cold start has no iterates): X'y as this solver holds it, in the x slot
             ADMM_HIP_CHECK(hipMemcpyAsync(q.state, XY.get(), (size_t)p * sizeof(float), hipMemcpyDeviceToDevice, st));
-        hctl[0].done = hctl[1].done = 0;
         *hflag.p = 0;
 #ifdef ADMM_HIP_PROBE
         sy.probe_idx = 0;
@@ -759,106 +715,69 @@ struct TallPlan final : LassoPlan {
         const int batch = batch_iters(pb.batch_iters, 32);
         const int stride = pb.profile_stride;                          // sample every stride-th x-update with events
         size_t nev = 0;                                                // events of ev_pool used by this run
-        Event ev_loop0, ev_loop1, ev_poll[2];
-
-        comm_stream_sync(st);
-        const CommLockstep lockstep;                                   // per-iteration exchanges: the short wait bound (comm.h)
-        const TraceRange trace_range("admm:loop");
-        const double tl0 = now_s();
-        ADMM_HIP_CHECK(hipEventRecord(ev_loop0.e, st));
-        long long g = 0, launches = 0;
-        const long long max_total = (long long)nlam * ((long long)pb.opts.maxit + 2) + 4 + 2 * batch;
-        auto enqueue_batch = [&](int slot) {
-            for (int k = 0; k < batch; ++k, ++g) {
-                const int par = (int)(g & 1);
-                const bool sample = stride > 0 && (g % stride) == stride / 2 && nev < 8192;      // mid-batch: not the launch right behind the poll event
-                hipEvent_t e0 = nullptr, e1 = nullptr;
-                if (sample) {
-                    while (ev_pool.size() < nev + 2) {
-                        hipEvent_t e; ADMM_HIP_CHECK(hipEventCreate(&e));
-                        ev_pool.push_back(e);
-                    }
-                    e0 = ev_pool[nev]; e1 = ev_pool[nev + 1];
-                    nev += 2;
+        // Single rank: no copy per poll, the deciding workgroup sets the pinned flag itself when the path has finished.
+        // Sharded over ranks: every rank must enqueue the SAME number of exchanges, so the stop decision has to be a
+        // deterministic function of the stream position -- the `done` word of the control block sampled in stream order after
+        // each batch -- not of when a flag store happens to become visible to this host.  (No batch growth on this path.)
+        const auto done_at = [&](long long g) -> const int* { return &ctl.get()[(int)(g & 1)].done; };
+        const LoopTimes lt = run_until_done(st, done_at, batch, (long long)nlam * ((long long)pb.opts.maxit + 2) + 4, [&](long long g) {
+            const int par = (int)(g & 1);
+            const bool sample = stride > 0 && (g % stride) == stride / 2 && nev < 8192;      // mid-batch: not the launch right behind the poll event
+            hipEvent_t e0 = nullptr, e1 = nullptr;
+            if (sample) {
+                while (ev_pool.size() < nev + 2) {
+                    hipEvent_t e; ADMM_HIP_CHECK(hipEventCreate(&e));
+                    ev_pool.push_back(e);
                 }
-                // sampled launches carry start/stop events that time exactly the x-update kernel on this stream
-                // the decision of this iteration rides along as one extra workgroup of the x-update launch
-                const TallDecideExtra dec{q, par};
-                if (shard && peer_fused) {
-                    // this rank's tiles -> its share of (a, b) written into every rank's exchange slot by the reduction
-                    // launch itself -> the (replicated) tail waits for the K flags and sums the K slots: three launches,
-                    // none of them the exchange layer's
-                    sy.launch(M.get(), ldp, u.get(), w.get(), &ctl.get()[par].done, st, dec, e0, e1);
-                    const PeerExchange ex = comm_peer_begin((size_t)2 * ldp * sizeof(float));
-                    if (peer_one) {
-                        hipLaunchKernelGGL(tall_tail_kernel<TAIL_PEER1>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, ex);
-                    } else {
-                        hipLaunchKernelGGL(tall_shard_push_kernel, dim3(nwg), dim3(kTailThreads), 0, st, q, ex, ldp, &ctl.get()[par].done);
-                        hipLaunchKernelGGL(tall_tail_kernel<TAIL_PEER>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, ex);
-                    }
-                } else if (shard) {
-                    // this rank's tiles -> its share of (a, b) -> ONE all-reduce of 2 ldp floats -> the (replicated) tail
-                    sy.launch(M.get(), ldp, u.get(), w.get(), &ctl.get()[par].done, st, dec, e0, e1);
-                    hipLaunchKernelGGL(tall_shard_reduce_kernel, dim3(nwg), dim3(kTailThreads), 0, st, q, ab.get(), ldp, &ctl.get()[par].done);
-                    allreduce_sum_f32(ab.get(), (size_t)2 * ldp, st);
-                    hipLaunchKernelGGL(tall_tail_kernel<TAIL_GEMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, PeerExchange{});
-                } else if (use_sym && refine) {
-                    // x1 = Minv rhs (both candidates) -> vectors; r = rhs - M x1 in double; correction Minv r -> partials; the tail adds
-                    const int* skip = &ctl.get()[par].done;
-                    sy.launch(M.get(), ldp, u.get(), w.get(), skip, st, dec, e0, e1);
-                    hipLaunchKernelGGL(tall_shard_reduce_kernel, dim3(nwg), dim3(kTailThreads), 0, st, q, rab.get(), ldv, skip);
-                    SymvArgsD ad;
-                    ad.A = Mg.get(); ad.lda = ldp; ad.p = p; ad.v0 = rab.get(); ad.v1 = rab.get() + ldv;
-                    ad.dot0 = dD0.get(); ad.dot1 = dD1.get(); ad.axp0 = xD0.get(); ad.axp1 = xD1.get(); ad.ldo = sy.ldo; ad.tiles = sy.tiles.get(); ad.skip = skip;
-                    hipLaunchKernelGGL(symv2_lower_f64acc_kernel, dim3(sy.ntiles), dim3(kSyThreads), 0, st, ad);
-                    hipLaunchKernelGGL(tall_refine_resid_kernel, dim3(nwg), dim3(kTailThreads), 0, st, q, dD0.get(), dD1.get(), xD0.get(), xD1.get(),
-                                       ruw.get(), ruw.get() + ldv, skip);
-                    sy.launch(M.get(), ldp, ruw.get(), ruw.get() + ldv, skip, st, SymvNoExtra());
-                    hipLaunchKernelGGL(tall_tail_kernel<TAIL_SYMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, PeerExchange{});
-                } else if (use_sym) {
-                    sy.launch(M.get(), ldp, u.get(), w.get(), &ctl.get()[par].done, st, dec, e0, e1);
-                    hipLaunchKernelGGL(tall_tail_kernel<TAIL_SYMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, PeerExchange{});
-                } else {
-                    launch_gemv_t<float, 2, 4, TallDecideExtra>(pl, M.get(), ldp, p, p, u.get(), w.get(), a_part.get(), b_part.get(), ldp,
-                                                                &ctl.get()[par].done, st, dec, e0, e1);
-                    hipLaunchKernelGGL(tall_tail_kernel<TAIL_GEMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, PeerExchange{});
-                }
-                ++launches;
+                e0 = ev_pool[nev]; e1 = ev_pool[nev + 1];
+                nev += 2;
             }
-            // Single rank: no copy per poll, the deciding workgroup sets the pinned flag itself when the path has finished.
-            // Sharded over ranks: every rank must enqueue the SAME number of exchanges, so the stop decision has to be a
-            // deterministic function of the stream position -- the control block sampled in stream order after each
-            // batch -- not of when a flag store happens to become visible to this host.
-            if (shard) ADMM_HIP_CHECK(hipMemcpyAsync(&hctl[slot], &ctl.get()[(int)(g & 1)], sizeof(TallCtl), hipMemcpyDeviceToHost, st));
-            ADMM_HIP_CHECK(hipEventRecord(ev_poll[slot].e, st));
-        };
-        int slot = 0;
-        enqueue_batch(slot);
-        ADMM_HIP_CHECK(hipGetLastError());                 // launch failures surface here
-        bool done = false;
-        while (!done) {
-            enqueue_batch(slot ^ 1);      // keep one batch in flight while polling the previous one
-            comm_event_sync(ev_poll[slot].e);
-            comm_check();
-            done = shard ? hctl[slot].done != 0 : *static_cast<volatile int*>(hflag.p) != 0;
-            slot ^= 1;
-            if (!done && g > max_total) throw Error(ADMM_ERR_INTERNAL, "tall path: iteration bound exceeded without completion");
-        }
-        ADMM_HIP_CHECK(hipEventRecord(ev_loop1.e, st));
-        comm_stream_sync(st);
-        S.t_loop = now_s() - tl0;
-        ADMM_HIP_CHECK(hipMemcpy(hctl, ctl.get(), 2 * sizeof(TallCtl), hipMemcpyDeviceToHost));      // both slots: decisions taken
-#ifdef ADMM_HIP_PROBE
-        if (const char* f = opt_text(Opt::PROBE_OUT)) {
-            std::vector<long long> hp((size_t)4096 * 4 * 8);
-            ADMM_HIP_CHECK(hipMemcpy(hp.data(), probe.get(), hp.size() * sizeof(long long), hipMemcpyDeviceToHost));
-            if (FILE* fp = std::fopen(f, "wb")) { std::fwrite(hp.data(), sizeof(long long), hp.size(), fp); std::fclose(fp); }
-        }
-#endif
-        float ms = 0.f;
-        ADMM_HIP_CHECK(hipEventElapsedTime(&ms, ev_loop0.e, ev_loop1.e));
-        S.loop_ms_events = ms;
-        S.xupdate_launches = launches;
+            // sampled launches carry start/stop events that time exactly the x-update kernel on this stream
+            // the decision of this iteration rides along as one extra workgroup of the x-update launch
+            const TallDecideExtra dec{q, par};
+            if (shard && peer_fused) {
+                // this rank's tiles -> its share of (a, b) written into every rank's exchange slot by the reduction
+                // launch itself -> the (replicated) tail waits for the K flags and sums the K slots: three launches,
+                // none of them the exchange layer's
+                sy.launch(M.get(), ldp, u.get(), w.get(), &ctl.get()[par].done, st, dec, e0, e1);
+                const PeerExchange ex = comm_peer_begin((size_t)2 * ldp * sizeof(float));
+                if (peer_one) {
+                    hipLaunchKernelGGL(tall_tail_kernel<TAIL_PEER1>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, ex);
+                } else {
+                    hipLaunchKernelGGL(tall_shard_push_kernel, dim3(nwg), dim3(kTailThreads), 0, st, q, ex, ldp, &ctl.get()[par].done);
+                    hipLaunchKernelGGL(tall_tail_kernel<TAIL_PEER>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, ex);
+                }
+            } else if (shard) {
+                // this rank's tiles -> its share of (a, b) -> ONE all-reduce of 2 ldp floats -> the (replicated) tail
+                sy.launch(M.get(), ldp, u.get(), w.get(), &ctl.get()[par].done, st, dec, e0, e1);
+                hipLaunchKernelGGL(tall_shard_reduce_kernel, dim3(nwg), dim3(kTailThreads), 0, st, q, ab.get(), ldp, &ctl.get()[par].done);
+                allreduce_sum_f32(ab.get(), (size_t)2 * ldp, st);
+                hipLaunchKernelGGL(tall_tail_kernel<TAIL_GEMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, PeerExchange{});
+            } else if (use_sym && refine) {
+                // x1 = Minv rhs (both candidates) -> vectors; r = rhs - M x1 in double; correction Minv r -> partials; the tail adds
+                const int* skip = &ctl.get()[par].done;
+                sy.launch(M.get(), ldp, u.get(), w.get(), skip, st, dec, e0, e1);
+                hipLaunchKernelGGL(tall_shard_reduce_kernel, dim3(nwg), dim3(kTailThreads), 0, st, q, rab.get(), ldv, skip);
+                SymvArgsD ad;
+                ad.A = Mg.get(); ad.lda = ldp; ad.p = p; ad.v0 = rab.get(); ad.v1 = rab.get() + ldv;
+                ad.dot0 = dD0.get(); ad.dot1 = dD1.get(); ad.axp0 = xD0.get(); ad.axp1 = xD1.get(); ad.ldo = sy.ldo; ad.tiles = sy.tiles.get(); ad.skip = skip;
+                hipLaunchKernelGGL(symv2_lower_f64acc_kernel, dim3(sy.ntiles), dim3(kSyThreads), 0, st, ad);
+                hipLaunchKernelGGL(tall_refine_resid_kernel, dim3(nwg), dim3(kTailThreads), 0, st, q, dD0.get(), dD1.get(), xD0.get(), xD1.get(),
+                                   ruw.get(), ruw.get() + ldv, skip);
+                sy.launch(M.get(), ldp, ruw.get(), ruw.get() + ldv, skip, st, SymvNoExtra());
+                hipLaunchKernelGGL(tall_tail_kernel<TAIL_SYMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, PeerExchange{});
+            } else if (use_sym) {
+                sy.launch(M.get(), ldp, u.get(), w.get(), &ctl.get()[par].done, st, dec, e0, e1);
+                hipLaunchKernelGGL(tall_tail_kernel<TAIL_SYMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, PeerExchange{});
+            } else {
+                launch_gemv_t<float, 2, 4, TallDecideExtra>(pl, M.get(), ldp, p, p, u.get(), w.get(), a_part.get(), b_part.get(), ldp,
+                                                            &ctl.get()[par].done, st, dec, e0, e1);
+                hipLaunchKernelGGL(tall_tail_kernel<TAIL_GEMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, PeerExchange{});
+            }
+        }, LoopOpts{shard ? nullptr : hflag.p, 0, false});
+        S.t_loop = lt.wall_s; S.loop_ms_events = lt.events_ms; S.xupdate_launches = lt.launched;
+        const CtlPair<TallCtl> hctl = read_ctl(ctl.get());      // both slots: decisions taken
+        WIDE_PROBE_DUMP(probe);
         if (nev > 0) {
             double tot = 0;
             for (size_t k = 0; k + 1 < nev; k += 2) {
@@ -871,20 +790,10 @@ struct TallPlan final : LassoPlan {
         }
 
         // ---- results: niter, beta on the original scale (DataStd::recover, Lasso.cpp:108-111)
-        res.niter.assign(nlam, 0);
-        ADMM_HIP_CHECK(hipMemcpy(res.niter.data(), niter.get(), nlam * sizeof(int), hipMemcpyDeviceToHost));
         ADMM_HIP_CHECK(hipMemcpyAsync(hbeta, beta.get(), (size_t)nlam * p * sizeof(float), hipMemcpyDeviceToHost, st));
         comm_stream_sync(st);
-        res.beta.assign((size_t)(p + 1) * nlam, 0.f);
-        long long tot_it = 0;
-        for (int l = 0; l < nlam; ++l) {
-            float b0 = 0.f;
-            recover_coef<float>(d, hbeta + (size_t)l * p, &b0, res.beta.data() + (size_t)l * (p + 1) + 1);
-            res.beta[(size_t)l * (p + 1)] = b0;
-            tot_it += res.niter[l];
-        }
-        S.total_iter = tot_it;
-        trace_n = hctl[0].done ? std::max(hctl[0].total, hctl[1].total) : 0;      // decisions taken (the sticky no-op decisions after `done` do not write)
+        S.total_iter = read_out_path<float>(d, hbeta, nlam, niter.get(), (size_t)p + 1, 0, res.niter, res.beta);
+        decisions = hctl.c[0].done ? hctl.total() : 0;      // (the sticky no-op decisions after `done` do not write)
         res.stats = S;
     }
 };

@@ -30,6 +30,7 @@
 #include "gemv_kernels.h"
 #include "solvers.h"
 #include "loop_driver.h"
+#include "plan_host.h"
 #include "comm.h"
 #include "probe.h"
 #include "peer_device.h"
@@ -1839,6 +1840,7 @@ struct WidePlan final : LassoPlan {
     bool cshard = false;                 // columns spread over the ranks: per iteration one all-reduce of Ax (n floats)
     bool peer_fused = false;             // ... done by the solver's own kernels over the PEER exchange (no launches of the exchange layer)
     bool peer_one = false;               // ... producer and consumer in one launch (wide_tail_kernel<2>)
+    int exchange_code = 0;               // ... as admm_stats.exchange_variant reports it
     CommInfo ci;
     long long p_total = 0, col_offset = 0;
     DevBuf<float> axl;                   // [ldn] this rank's share of Ax, all-reduced in place
@@ -1862,38 +1864,8 @@ struct WidePlan final : LassoPlan {
     DevBuf<long long> probe;
 #endif
     WideParams q{};
-    DevBuf<double> trace;
-    long long trace_cap = 0, trace_n = 0;
-
-    void enable_trace(long long cap) override {
-        trace.alloc((size_t)cap * ADMM_TRACE_FIELDS);
-        trace_cap = cap; trace_n = 0;
-        q.trace = trace.get(); q.trace_cap = cap;
-    }
-    long long read_trace(double* out, long long cap) override {
-        const long long nrec = std::min(std::min(trace_n, trace_cap), cap);
-        if (nrec > 0) read_back(out, trace.get(), (size_t)nrec * ADMM_TRACE_FIELDS * sizeof(double), st);
-        return nrec;
-    }
-
     // iterate dump (test facility): record s = x | A x | z | y (p + 3 n floats; column-sharded: x of this rank's p columns) the decision of trace record s judged
-    DevBuf<float> state;
-    long long state_cap = 0;
-    void enable_state(long long cap) override {
-        const size_t rec = (size_t)p + 3 * (size_t)n;
-        state.alloc((size_t)cap * rec);
-        ADMM_HIP_CHECK(hipMemsetAsync(state.get(), 0, (size_t)cap * rec * sizeof(float), st));
-        state_cap = cap;
-        q.state = state.get(); q.state_cap = cap;
-    }
-    long long read_state(float* out, long long cap, long long* rec_floats) override {
-        const size_t rec = (size_t)p + 3 * (size_t)n;
-        if (rec_floats) *rec_floats = (long long)rec;
-        if (!out) return std::min(trace_n, state_cap);                             // size query
-        const long long nrec = std::min(std::min(trace_n, state_cap), cap);
-        if (nrec > 0) read_back(out, state.get(), (size_t)nrec * rec * sizeof(float), st);
-        return nrec;
-    }
+    Records records() override { return {st, (long long)p + 3ll * n, &q.trace, &q.trace_cap, &q.state, &q.state_cap}; }
     // the standardised data as this solver holds them (test hook admm_hip_lasso_plan_data_read)
     void read_data(float* x_out, long long ld, float* y_out) override {
         comm_stream_sync(st);
@@ -1911,8 +1883,6 @@ struct WidePlan final : LassoPlan {
         // X X' = sum_i X_i X_i' (one all-reduce), the Lanczos value replicated.
         cshard = pb.p_total > 0;
         ci = cshard ? comm_info() : CommInfo();
-        peer_fused = cshard && ci.backend == COMM_PEER;
-        if (opt_is(Opt::PEER_FUSED, "0")) peer_fused = false;
         p_total = cshard ? pb.p_total : p; col_offset = cshard ? pb.col_offset : 0;
         admm_stats& S = setup_stats;
         S.branch = 1; S.t_h2d = d.t_h2d; S.t_standardize = d.t_std;
@@ -1965,21 +1935,14 @@ struct WidePlan final : LassoPlan {
         }
         if (pb.enet) lambda0 = (float)((double)lambda0 / ((double)(float)pb.alpha + 0.0001));
 
-        lam_user = make_lambda_grid(pb, lambda0, n, (double)d.scaleY);
-        nlam = (int)lam_user.size();
-        lam_int.resize(nlam);
-        for (int i = 0; i < nlam; ++i) lam_int[i] = (float)(lam_user[i] * n / (double)d.scaleY);
+        nlam = make_path_grid<float>(pb, lambda0, n, (double)d.scaleY, lam_user, lam_int);
         rho0 = pb.opts.rho;
         if (rho0 <= 0) rho0 = std::pow((double)lam_int[0] / (double)sprad, 1.0 / 3);       // :227-228
         S.rho = rho0;
 
         nwg_tail = (n + kWtElems - 1) / kWtElems;                    // 32 elements per workgroup (8 lanes each)
-        if (peer_fused) {
-            int occ = 0;
-            ADMM_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, reinterpret_cast<const void*>(wide_tail_kernel<2>), kWideThreads, 0));
-            peer_one = (long long)nwg_tail * 2 <= resident_workgroups(occ);
-            if (opt_is(Opt::PEER_FUSED, "2")) peer_one = false;
-        }
+        const ExchangeForm xf = peer_exchange_form(cshard, ci, reinterpret_cast<const void*>(wide_tail_kernel<2>), kWideThreads, nwg_tail);
+        peer_fused = xf.fused; peer_one = xf.one; exchange_code = xf.variant;
         x.alloc(ldp); x.zero(st);
         for (DevBuf<float>* b : {&Ax, &z, &y}) { b->alloc(std::max<long long>(ldn, 8192)); b->zero(st); }   // the fused x-update reads up to 32 x 256 entries unconditionally
         // ADMM_HIP_WIDE_FUSE=0: always three launches per iteration
@@ -2003,17 +1966,8 @@ struct WidePlan final : LassoPlan {
         // partial second round runs at a fraction of the occupancy: 342 us instead of 280 us at C3 with 4 per CU
         // when 3 fit).
         int wgx = 0;
-        {
-            const void* fn = fuse_rt == 4 ? reinterpret_cast<const void*>(wide_x_kernel<4>)
-                           : fuse_rt == 8 ? reinterpret_cast<const void*>(wide_x_kernel<8>)
-                           : fuse_rt == 16 ? reinterpret_cast<const void*>(wide_x_kernel<16>)
-                           : fuse_rt == 24 ? reinterpret_cast<const void*>(wide_x_kernel<24>)
-                           : fuse_rt == 32 ? reinterpret_cast<const void*>(wide_x_kernel<32>)
-                           : t_global ? reinterpret_cast<const void*>(wide_x_kernel<0, true>)
-                                      : reinterpret_cast<const void*>(wide_x_kernel<0, false>);
-            ADMM_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgx, fn, kWideThreads, lds_x));
-            wgx = std::max(1, std::min(wgx, 4));
-        }
+        ADMM_HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&wgx, reinterpret_cast<const void*>(x_kernel()), kWideThreads, lds_x));
+        wgx = std::max(1, std::min(wgx, 4));
         nwg_x = std::max(wgx * device_info().num_cu, kActWG);
         axpart.alloc((size_t)(fuse_rt ? nwg_x : kAxWG) * ldn); axpart.zero(st);
         beta.alloc((size_t)nlam * p); niter.alloc(nlam); done.alloc(1); dlam.alloc(nlam);
@@ -2039,6 +1993,20 @@ struct WidePlan final : LassoPlan {
         setup_screen();
         setup_persist_rows();
         comm_stream_sync(st);
+    }
+
+    // The x-update kernel of this plan: rows per thread of the fused form (fuse_rt), or the unfused form with t staged in the LDS or
+    // read from global memory.  Launched with lds_x bytes of dynamic LDS (0 for the t_global form).
+    using XKernel = void (*)(WideParams, int);
+    XKernel x_kernel() const {
+        switch (fuse_rt) {
+            case 4: return wide_x_kernel<4>;
+            case 8: return wide_x_kernel<8>;
+            case 16: return wide_x_kernel<16>;
+            case 24: return wide_x_kernel<24>;
+            case 32: return wide_x_kernel<32>;
+            default: return t_global ? wide_x_kernel<0, true> : wide_x_kernel<0, false>;
+        }
     }
 
     // Safe screening of the regular steps (wide_x_kernel): worth its copy when X is a stream from HBM at all (beyond the Infinity Cache
@@ -2137,28 +2105,17 @@ struct WidePlan final : LassoPlan {
         if (persist_rows) { rhint.zero(st); rerr.zero(st); }
         // records written inside a persistent stretch store x for the listed columns only ("zeros elsewhere"): a second run() on the
         // same plan must not see the previous run's entries
-        if (q.state != nullptr) ADMM_HIP_CHECK(hipMemsetAsync(state.get(), 0, state.n * sizeof(float), st));
+        state_buf.zero(st);
         const int init_n = std::max(std::max(n, p), nwg_tail * 8);
         hipLaunchKernelGGL(wide_init_kernel, dim3((init_n + 255) / 256), dim3(256), 0, st, q, rho0, lam_int[0]);
         const int batch = batch_iters(pb.batch_iters, 16);
+        const XKernel xk = x_kernel();
         LoopTimes lt = run_until_done(st, done.get(), batch, (long long)nlam * ((long long)pb.opts.maxit + 2) + 4, [&](long long g) {
             const int par = (int)(g & 1);
-            switch (fuse_rt) {
-                case 4: hipLaunchKernelGGL(wide_x_kernel<4>, dim3(nwg_x), dim3(kWideThreads), lds_x, st, q, par); break;
-                case 8: hipLaunchKernelGGL(wide_x_kernel<8>, dim3(nwg_x), dim3(kWideThreads), lds_x, st, q, par); break;
-                case 16: hipLaunchKernelGGL(wide_x_kernel<16>, dim3(nwg_x), dim3(kWideThreads), lds_x, st, q, par); break;
-                case 24: hipLaunchKernelGGL(wide_x_kernel<24>, dim3(nwg_x), dim3(kWideThreads), lds_x, st, q, par); break;
-                case 32: hipLaunchKernelGGL(wide_x_kernel<32>, dim3(nwg_x), dim3(kWideThreads), lds_x, st, q, par); break;
-                default:
-                    if (t_global) {
-                        hipLaunchKernelGGL(wide_t_kernel, dim3((unsigned)((ldn + kWideThreads - 1) / kWideThreads)), dim3(kWideThreads), 0, st, q, par);
-                        hipLaunchKernelGGL((wide_x_kernel<0, true>), dim3(nwg_x), dim3(kWideThreads), 0, st, q, par);
-                    } else {
-                        hipLaunchKernelGGL((wide_x_kernel<0, false>), dim3(nwg_x), dim3(kWideThreads), lds_x, st, q, par);
-                    }
-                    hipLaunchKernelGGL(wide_ax_kernel, dim3(kAxWG), dim3(kWideThreads), 0, st, q);
-            }
-            if (cshard && peer_fused) {                                // the only exchange, produced and consumed by the solver's own kernels
+            if (t_global) hipLaunchKernelGGL(wide_t_kernel, dim3((unsigned)((ldn + kWideThreads - 1) / kWideThreads)), dim3(kWideThreads), 0, st, q, par);
+            hipLaunchKernelGGL(xk, dim3(nwg_x), dim3(kWideThreads), lds_x, st, q, par);
+            if (!fuse_rt) hipLaunchKernelGGL(wide_ax_kernel, dim3(kAxWG), dim3(kWideThreads), 0, st, q);
+            if (cshard && peer_fused) {                                  // the only exchange, produced and consumed by the solver's own kernels
                 const PeerExchange ex = comm_peer_begin((size_t)ldn * sizeof(float));
                 if (peer_one) {
                     hipLaunchKernelGGL(wide_tail_kernel<2>, dim3(nwg_tail), dim3(kWideThreads), 0, st, q, par, ex);
@@ -2166,20 +2123,20 @@ struct WidePlan final : LassoPlan {
                     hipLaunchKernelGGL(wide_ax_push_kernel, dim3((unsigned)((ldn + kWtElems - 1) / kWtElems)), dim3(kWideThreads), 0, st, q, par, ex);
                     hipLaunchKernelGGL(wide_tail_kernel<1>, dim3(nwg_tail), dim3(kWideThreads), 0, st, q, par, ex);
                 }
-                if (q.state != nullptr) hipLaunchKernelGGL(wide_state_kernel, dim3(std::min(1024, (std::max(n, p) + kWideThreads - 1) / kWideThreads)), dim3(kWideThreads), 0, st, q, par);
-                if (persist_rows) launch_persist_rows(par ^ 1);          // the stretch on this rank's column block, its A x summed over the ranks inside the launch
-                return;
+            } else {
+                if (cshard) {                                          // the only exchange: A x summed over the ranks' column blocks
+                    hipLaunchKernelGGL(wide_ax_local_kernel, dim3((unsigned)((ldn + kWtElems - 1) / kWtElems)), dim3(kWideThreads), 0, st, q, par, axl.get());
+                    allreduce_sum_f32(axl.get(), (size_t)n, st);
+                }
+                hipLaunchKernelGGL(wide_tail_kernel<0>, dim3(nwg_tail), dim3(kWideThreads), 0, st, q, par, PeerExchange{});
             }
-            if (cshard) {                                              // the only exchange: A x summed over the ranks' column blocks
-                hipLaunchKernelGGL(wide_ax_local_kernel, dim3((unsigned)((ldn + kWtElems - 1) / kWtElems)), dim3(kWideThreads), 0, st, q, par, axl.get());
-                allreduce_sum_f32(axl.get(), (size_t)n, st);
-            }
-            hipLaunchKernelGGL(wide_tail_kernel<0>, dim3(nwg_tail), dim3(kWideThreads), 0, st, q, par, PeerExchange{});
             if (q.state != nullptr) hipLaunchKernelGGL(wide_state_kernel, dim3(std::min(1024, (std::max(n, p) + kWideThreads - 1) / kWideThreads)), dim3(kWideThreads), 0, st, q, par);
-            if (persist_rows) launch_persist_rows(par ^ 1);             // takes over from the state the next x-update launch would start from
-        }, cshard ? nullptr : hflag.p);       // column-sharded: every rank must enqueue the same number of exchanges -> stream-ordered sampling of `done`
+            // the stretch takes over from the state the next x-update launch would start from (column-sharded: on this rank's column
+            // block, its A x summed over the ranks inside the launch)
+            if (persist_rows) launch_persist_rows(par ^ 1);
+        }, LoopOpts{cshard ? nullptr : hflag.p});       // column-sharded: every rank must enqueue the same number of exchanges -> stream-ordered sampling of `done`
         S.t_loop = lt.wall_s; S.loop_ms_events = lt.events_ms; S.xupdate_launches = lt.launched;
-        S.exchange_variant = !cshard ? 0 : (!peer_fused ? 1 : (peer_one ? 3 : 2));
+        S.exchange_variant = exchange_code;
         S.xupdate_variant = !screened ? 0 : (screen_fmt == 8 ? 2 : 1);
         if (q.scr_stat != nullptr) {
             unsigned long long hs[2] = {0, 0};
@@ -2217,21 +2174,13 @@ struct WidePlan final : LassoPlan {
                              0.01 * hs[6] / it, 0.01 * hs[7] / it, 0.01 * hs[8] / it, 0.01 * hs[9] / it, 0.01 * hs[10] / it, 0.01 * hs[11] / it, 0.01 * hs[12] / it, 0.01 * hs[13] / it);
             }
         }
-#ifdef ADMM_HIP_PROBE
-        if (const char* f = opt_text(Opt::PROBE_OUT)) {
-            std::vector<long long> hp((size_t)4096 * 4 * 8);
-            ADMM_HIP_CHECK(hipMemcpy(hp.data(), probe.get(), hp.size() * sizeof(long long), hipMemcpyDeviceToHost));
-            if (FILE* fp = std::fopen(f, "wb")) { std::fwrite(hp.data(), sizeof(long long), hp.size(), fp); std::fclose(fp); }
-        }
-#endif
+        WIDE_PROBE_DUMP(probe);
 
-        res.niter.assign(nlam, 0);
-        ADMM_HIP_CHECK(hipMemcpy(res.niter.data(), niter.get(), nlam * sizeof(int), hipMemcpyDeviceToHost));
         const size_t pt1 = (size_t)p_total + 1;
-        std::vector<double> icpt(nlam, 0.0);                          // sum_j beta_j meanX_j over this rank's columns
-        long long tot = 0;
         if (!cshard && res.beta_dst != nullptr) {
             // sparse read-back straight into the caller's buffer (kernels above)
+            res.niter.assign(nlam, 0);
+            ADMM_HIP_CHECK(hipMemcpy(res.niter.data(), niter.get(), nlam * sizeof(int), hipMemcpyDeviceToHost));
             DevBuf<int> dcnt(nlam);
             hipLaunchKernelGGL(wide_beta_count_kernel, dim3(nlam), dim3(256), 0, st, beta.get(), p, dcnt.get());
             std::vector<int> hcnt(nlam);
@@ -2257,28 +2206,22 @@ struct WidePlan final : LassoPlan {
                 float b0 = 0.f;
                 recover_coef_sparse<float>(d, hidx.data() + hoff[l], hval.data() + hoff[l], hcnt[l], &b0, res.beta_dst + (size_t)l * pt1 + 1);
                 res.beta_dst[(size_t)l * pt1] = b0;
-                tot += res.niter[l];
+                S.total_iter += res.niter[l];
             }
             res.beta_written = true;
             res.beta.clear();
         } else {
-        std::vector<float> hb((size_t)nlam * p);
-        read_back(hb.data(), beta.get(), hb.size() * sizeof(float), st);
-        res.beta.assign(pt1 * nlam, 0.f);
-        for (int l = 0; l < nlam; ++l) {
-            float b0 = 0.f;
-            recover_coef<float>(d, hb.data() + (size_t)l * p, &b0, res.beta.data() + (size_t)l * pt1 + 1 + col_offset);
-            res.beta[(size_t)l * pt1] = b0;
-            icpt[l] = (double)d.meanY - (double)b0;
-            tot += res.niter[l];
-        }
+            std::vector<float> hb((size_t)nlam * p);
+            read_back(hb.data(), beta.get(), hb.size() * sizeof(float), st);
+            S.total_iter = read_out_path<float>(d, hb.data(), nlam, niter.get(), pt1, col_offset, res.niter, res.beta);
         }
         if (cshard) {
             // every rank returns the full coefficient matrix: blocks summed into a zero-padded copy, the intercept
             // beta_0 = meanY - sum over ALL columns (DataStd::recover) from the ranks' partial sums
             const bool has_icpt = (d.flag & 2) != 0;
             DevBuf<float> db(res.beta.size()); DevBuf<double> di(nlam);
-            for (int l = 0; l < nlam; ++l) res.beta[(size_t)l * pt1] = 0.f;
+            std::vector<double> icpt(nlam);                           // sum_j beta_j meanX_j over this rank's columns
+            for (int l = 0; l < nlam; ++l) { icpt[l] = (double)d.meanY - (double)res.beta[(size_t)l * pt1]; res.beta[(size_t)l * pt1] = 0.f; }
             ADMM_HIP_CHECK(hipMemcpyAsync(db.get(), res.beta.data(), res.beta.size() * sizeof(float), hipMemcpyHostToDevice, st));
             ADMM_HIP_CHECK(hipMemcpyAsync(di.get(), icpt.data(), nlam * sizeof(double), hipMemcpyHostToDevice, st));
             allreduce_sum_f32(db.get(), res.beta.size(), st);
@@ -2289,12 +2232,7 @@ struct WidePlan final : LassoPlan {
             comm_check();
             for (int l = 0; l < nlam; ++l) res.beta[(size_t)l * pt1] = has_icpt ? (float)((double)d.meanY - icpt[l]) : 0.f;
         }
-        S.total_iter = tot;
-        {   // decisions taken = the cold-start one + one per ADMM iteration
-            WideCtl hc[2];
-            ADMM_HIP_CHECK(hipMemcpy(hc, ctl.get(), sizeof(hc), hipMemcpyDeviceToHost));
-            trace_n = std::max(hc[0].total, hc[1].total);
-        }
+        decisions = read_ctl(ctl.get()).total();
         res.stats = S;
     }
 };

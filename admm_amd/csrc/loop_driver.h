@@ -22,34 +22,49 @@ struct PinnedFlag {
     PinnedFlag& operator=(const PinnedFlag&) = delete;
 };
 
+// What a caller may set beyond the defaults.
+// h_flag (SINGLE-RANK solves only: when a flag store becomes visible to the host is not a function of the stream position, and ranks
+// that exchange data per iteration must all stop after the same number of enqueued iterations): a PinnedFlag word the kernels set
+// together with the device word -- then no copy is enqueued per poll (a 4-byte device-to-host copy is a blit launch plus a
+// system-scope release: ~14 us of stream time per batch, measured on the wide path), no pinned poll words are allocated, and with
+// `grow` the batch goes from `batch` to 4 x `batch` as the solve gets long.
+struct LoopOpts {
+    const volatile int* h_flag = nullptr;
+    long long g_start = 0;                             // (a solver that resumes a halted loop continues its own count)
+    bool grow = true;
+};
+
+// The device word to sample after the batch that ends before iteration g: one word for most solvers, a function of g for a
+// double-buffered control block.
+inline const int* poll_word(const int* w, long long) { return w; }
+template <typename P> auto poll_word(P& at, long long g) -> decltype(at(g)) { return at(g); }
+
 // enqueue(g): enqueue every kernel of iteration g (g = 0, 1, 2, ...) on `st`.
-// d_done: device int that the iteration kernels set to non-zero once the solve is finished; all
+// d_done: device int (or g -> device int) that the iteration kernels set to non-zero once the solve is finished; all
 // kernels must be no-ops afterwards.  `batch` iterations are enqueued between two polls.
-// h_flag (optional, SINGLE-RANK solves only: when a flag store becomes visible to the host is not a function of the stream
-// position, and ranks that exchange data per iteration must all stop after the same number of enqueued iterations):
-// a PinnedFlag word the kernels set together with d_done -- then no copy is enqueued per poll (a
-// 4-byte device-to-host copy is a blit launch plus a system-scope release: ~14 us of stream time per batch, measured on
-// the wide path), and the batch grows from `batch` to 4 x `batch` as the solve gets long.
-template <typename F>
-inline LoopTimes run_until_done(hipStream_t st, const int* d_done, int batch, long long max_iters, F&& enqueue,
-                                const volatile int* h_flag = nullptr, long long g_start = 0) {
+template <typename P, typename F>
+inline LoopTimes run_until_done(hipStream_t st, P d_done, int batch, long long max_iters, F&& enqueue, const LoopOpts& o = LoopOpts()) {
     const TraceRange trace_range("admm:loop");
-    int* h_done = nullptr;
-    ADMM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h_done), 2 * sizeof(int), hipHostMallocDefault));
-    struct HostFree { void* p; ~HostFree() { pinned_free(p); } } hf{h_done};
-    h_done[0] = h_done[1] = 0;
+    const volatile int* h_flag = o.h_flag;
+    const long long g_start = o.g_start;
+    int* h_done = nullptr;                             // pinned poll words: only where the copies below are enqueued
+    if (h_flag == nullptr) {
+        ADMM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&h_done), 2 * sizeof(int), hipHostMallocDefault));
+        h_done[0] = h_done[1] = 0;
+    }
+    struct HostFree { void* p; ~HostFree() { if (p) pinned_free(p); } } hf{h_done};
     const CommLockstep lockstep;                       // exchanges enqueued from here are per-iteration: short wait bound
     const int batch0 = batch;
     int npoll = 0;
     Event ev0, ev1, poll[2];
     LoopTimes t;
-    ADMM_HIP_CHECK(hipStreamSynchronize(st));
+    comm_stream_sync(st);
     const double t0 = now_s();
     ADMM_HIP_CHECK(hipEventRecord(ev0.e, st));
-    long long g = g_start;                             // (a solver that resumes a halted loop continues its own count)
+    long long g = g_start;
     auto enqueue_batch = [&](int slot) {
         for (int k = 0; k < batch; ++k, ++g) enqueue(g);
-        if (h_flag == nullptr) ADMM_HIP_CHECK(hipMemcpyAsync(&h_done[slot], d_done, sizeof(int), hipMemcpyDeviceToHost, st));
+        if (h_flag == nullptr) ADMM_HIP_CHECK(hipMemcpyAsync(&h_done[slot], poll_word(d_done, g), sizeof(int), hipMemcpyDeviceToHost, st));
         ADMM_HIP_CHECK(hipEventRecord(poll[slot].e, st));
     };
     int slot = 0;
@@ -62,7 +77,7 @@ inline LoopTimes run_until_done(hipStream_t st, const int* d_done, int batch, lo
         comm_check();                                  // a timed-out exchange ends the solve with ADMM_ERR_COMM
         done = h_flag ? (*h_flag != 0) : (h_done[slot] != 0);
         slot ^= 1;
-        if (h_flag && (++npoll & 3) == 0 && batch < 4 * batch0) batch *= 2;      // stays even: the parity pattern of g is kept
+        if (o.grow && h_flag && (++npoll & 3) == 0 && batch < 4 * batch0) batch *= 2;      // stays even: the parity pattern of g is kept
         if (!done && g - g_start > max_iters + 2 * batch)
             throw Error(ADMM_ERR_INTERNAL, "ADMM loop: iteration bound exceeded without completion");
     }

@@ -19,6 +19,7 @@
 #include "gather_kernels.h"
 #include "solvers.h"
 #include "loop_driver.h"
+#include "plan_host.h"
 #include "comm.h"
 #include "peer_device.h"
 #include "probe.h"
@@ -608,19 +609,8 @@ struct ParPlan final : LassoPlan {
     DevBuf<long long> probe;
 #endif
     ParParams q{};
-    DevBuf<double> trace;
-    long long trace_cap = 0, trace_n = 0;
-
-    void enable_trace(long long cap) override {
-        trace.alloc((size_t)cap * ADMM_TRACE_FIELDS);
-        trace_cap = cap; trace_n = 0;
-        q.trace = trace.get(); q.trace_cap = cap;
-    }
-    long long read_trace(double* out, long long cap) override {
-        const long long nrec = std::min(std::min(trace_n, trace_cap), cap);
-        if (nrec > 0) read_back(out, trace.get(), (size_t)nrec * ADMM_TRACE_FIELDS * sizeof(double), st);
-        return nrec;
-    }
+    // iterate dump: record s = z | x_0 .. x_{Kl-1} | y_0 .. y_{Kl-1} the decision of trace record s judged
+    Records records() override { return {st, (1ll + 2 * Kl) * p, &q.trace, &q.trace_cap, &q.state, &q.state_cap}; }
 
     // several row blocks in this process, all of one branch: the workers' products of one kind go out as ONE launch each
     bool batched = false, bt_wide = false, bt_nt = false;
@@ -643,25 +633,6 @@ struct ParPlan final : LassoPlan {
     bool fuse_pz = false;             // pack + z in one launch (single process; PEER: when the grid is resident with room to spare)
     DevBuf<GatherArgs<float>> bG, bGd;
     long long fallback_passes = 0;
-    DevBuf<float> state;
-    long long state_cap = 0;
-    void enable_state(long long cap) override {
-        const size_t rec = (size_t)(1 + 2 * Kl) * p;
-        state.alloc((size_t)cap * rec);
-        // on the solver's own (non-blocking) stream: a null-stream memset is not ordered against it and, on a busy device, landed
-        // AFTER run() had copied record 0 into the dump (suspected cause of the one unreadable record 0 of the 40-process soak, case 546:23)
-        ADMM_HIP_CHECK(hipMemsetAsync(state.get(), 0, (size_t)cap * rec * sizeof(float), st));
-        state_cap = cap;
-        q.state = state.get(); q.state_cap = cap;
-    }
-    long long read_state(float* out, long long cap, long long* rec_floats) override {
-        const size_t rec = (size_t)(1 + 2 * Kl) * p;
-        if (rec_floats) *rec_floats = (long long)rec;
-        if (!out) return std::min(trace_n, state_cap);                             // size query
-        const long long nrec = std::min(std::min(trace_n, state_cap), cap);
-        if (nrec > 0 && out) read_back(out, state.get(), (size_t)nrec * rec * sizeof(float), st);
-        return nrec;
-    }
 
     ParPlan(DeviceData<float>&& data, const LassoProblem& prob, hipStream_t stream) : d(std::move(data)), pb(prob), st(stream) {
         const int n = d.n;
@@ -686,10 +657,7 @@ struct ParPlan final : LassoPlan {
         gemv_t_simple<float>(d.X.get(), d.ldx, n, p, d.Y.get(), XY.get(), st);
         if (pb.dist) { allreduce_sum_f32(XY.get(), p, st); comm_stream_sync(st); }
         const float lambda0 = device_absmax<float>(XY.get(), p, st);
-        lam_user = make_lambda_grid(pb, lambda0, (int)nt, (double)d.scaleY);
-        nlam = (int)lam_user.size();
-        lam_int.resize(nlam);
-        for (int i = 0; i < nlam; ++i) lam_int[i] = lam_user[i] * (double)nt / (double)d.scaleY;   // `double lambda` in the master
+        nlam = make_path_grid<double>(pb, lambda0, nt, (double)d.scaleY, lam_user, lam_int);      // `double lambda` in the master
         rho = pb.opts.rho;
         if (rho <= 0) rho = lam_int[0] / K;                                                // PADMMLasso.h:199-200
         S.rho = rho;
@@ -955,7 +923,7 @@ struct ParPlan final : LassoPlan {
             if (onepass) hipLaunchKernelGGL((gather_batch_kernel<float>), dim3(gather_tiles, gp.ngroups, Kl), dim3(kGatherThreads), 0, st, bG.get());      // A_k z_new over the non-zeros of z
         });
         S.t_loop = lt.wall_s; S.loop_ms_events = lt.events_ms; S.xupdate_launches = lt.launched;
-        S.exchange_variant = !pb.dist ? 0 : (peer_fused ? (fuse_pz ? 3 : 2) : 1);      // 3: `pack` and `z` as ONE launch, producer and consumer of the exchange
+        S.exchange_variant = exchange_variant(pb.dist, peer_fused, fuse_pz);      // 3: `pack` and `z` as ONE launch, producer and consumer of the exchange
         if (onepass) {
             unsigned long long hc = 0;
             ADMM_HIP_CHECK(hipMemcpy(&hc, wbcount.get(), sizeof(hc), hipMemcpyDeviceToHost));
@@ -964,32 +932,12 @@ struct ParPlan final : LassoPlan {
             if (opt_on(Opt::PAR_ONEPASS_STATS))
                 std::fprintf(stderr, "[consensus one-pass] %lld worker-iterations took the dense fall-back pass (cancellation guard) of %lld x %d\n", fallback_passes, (long long)lt.launched, Kl);
         }
-#ifdef ADMM_HIP_PROBE
-        if (const char* f = opt_text(Opt::PROBE_OUT)) {
-            std::vector<long long> hp((size_t)4096 * 4 * 8);
-            ADMM_HIP_CHECK(hipMemcpy(hp.data(), probe.get(), hp.size() * sizeof(long long), hipMemcpyDeviceToHost));
-            if (FILE* fp = std::fopen(f, "wb")) { std::fwrite(hp.data(), sizeof(long long), hp.size(), fp); std::fclose(fp); }
-        }
-#endif
+        WIDE_PROBE_DUMP(probe);
 
-        res.niter.assign(nlam, 0);
-        ADMM_HIP_CHECK(hipMemcpy(res.niter.data(), niter.get(), nlam * sizeof(int), hipMemcpyDeviceToHost));
         std::vector<float> hb((size_t)nlam * p);
         read_back(hb.data(), beta.get(), hb.size() * sizeof(float), st);
-        res.beta.assign((size_t)(p + 1) * nlam, 0.f);
-        long long tot = 0;
-        for (int l = 0; l < nlam; ++l) {
-            float b0 = 0.f;
-            recover_coef<float>(d, hb.data() + (size_t)l * p, &b0, res.beta.data() + (size_t)l * (p + 1) + 1);
-            res.beta[(size_t)l * (p + 1)] = b0;
-            tot += res.niter[l];
-        }
-        S.total_iter = tot;
-        {   // decisions taken = the cold-start one + one per ADMM iteration
-            ParCtl hc[2];
-            ADMM_HIP_CHECK(hipMemcpy(hc, ctl.get(), sizeof(hc), hipMemcpyDeviceToHost));
-            trace_n = std::max(hc[0].total, hc[1].total);
-        }
+        S.total_iter = read_out_path<float>(d, hb.data(), nlam, niter.get(), (size_t)p + 1, 0, res.niter, res.beta);
+        decisions = read_ctl(ctl.get()).total();
         res.stats = S;
     }
 };

@@ -34,6 +34,7 @@
 #include "gemv_kernels.h"
 #include "solvers.h"
 #include "loop_driver.h"
+#include "plan_host.h"
 #include "comm.h"
 #include "device_utils.h"
 #include "gather_kernels.h"
@@ -1728,7 +1729,7 @@ void solve_parbp(const DeviceData<double>& d, const admm_opts& opts, int nblocks
     int gstat[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     int halts = 0;
     for (long long g_start = 0;;) {
-        const LoopTimes l1 = run_until_done(st, d_done.get(), batch_iters((int)opt_int(Opt::BATCH_ITERS, 0), 20), (long long)opts.maxit + 2, enqueue, dist ? nullptr : hflag.p, g_start);
+        const LoopTimes l1 = run_until_done(st, d_done.get(), batch_iters((int)opt_int(Opt::BATCH_ITERS, 0), 20), (long long)opts.maxit + 2, enqueue, LoopOpts{dist ? nullptr : hflag.p, g_start});
         lt.wall_s += l1.wall_s; lt.events_ms += l1.events_ms; lt.launched += l1.launched;
         if (!gram_on) break;
         ADMM_HIP_CHECK(hipGetLastError());
@@ -1751,18 +1752,13 @@ void solve_parbp(const DeviceData<double>& d, const admm_opts& opts, int nblocks
         ++halts;
     }
     ADMM_HIP_CHECK(hipGetLastError());                             // a refused launch (LDS request, grid) is an error, not a silent no-op
-    SbpCtl hc[2];
-    ADMM_HIP_CHECK(hipMemcpy(hc, ctl.get(), sizeof(hc), hipMemcpyDeviceToHost));
-    const SbpCtl& fin = hc[0].done ? hc[0] : hc[1];
+    const CtlPair<SbpCtl> hc = read_ctl(ctl.get());
+    const SbpCtl& fin = hc.finished();
     ADMM_REQUIRE(fin.done, "admm_parbp: the loop ended without a decision");
     res.niter = fin.niter;
     res.beta.assign(pl, 0.0);
     read_back(res.beta.data(), x.get(), (size_t)pl * sizeof(double), st);
-    if (res.trace_cap > 0) {
-        const long long nrec = std::min<long long>(fin.total, res.trace_cap);
-        res.trace.assign((size_t)nrec * ADMM_TRACE_FIELDS, 0.0);
-        if (nrec > 0) read_back(res.trace.data(), trace.get(), res.trace.size() * sizeof(double), st);
-    }
+    if (res.trace_cap > 0) collect_records(res.trace, trace.get(), ADMM_TRACE_FIELDS, fin.total, res.trace_cap, st);
     S.total_iter = fin.niter > opts.maxit ? opts.maxit : fin.niter;
     S.t_loop = lt.wall_s;
     S.loop_ms_events = lt.events_ms;

@@ -1,6 +1,7 @@
 // Solver entry points behind the C ABI (one per reference problem class).
 #pragma once
 #include "prep.h"
+#include <algorithm>
 #include <memory>
 
 namespace admm {
@@ -34,22 +35,64 @@ struct LassoResult {
 // Lasso.cpp:78-89
 std::vector<double> make_lambda_grid(const LassoProblem& pb, double lambda0, int n, double scaleY);
 
+// Read-out of a device-side recorder (decision trace or iterate dump, `rec_len` values per record): the first min(taken, capacity, cap)
+// records, where `taken` is the number of decisions the loop took and `capacity` what the recorder was given.  Returns how many.
+template <typename T>
+long long read_records(T* out, long long cap, const T* dev, long long rec_len, long long taken, long long capacity, hipStream_t st) {
+    const long long nrec = std::min(std::min(taken, capacity), cap);
+    if (nrec > 0) read_back(out, dev, (size_t)nrec * rec_len * sizeof(T), st);
+    return nrec;
+}
+template <typename T>      // ... into a result's vector, sized to what was recorded
+void collect_records(std::vector<T>& out, const T* dev, long long rec_len, long long taken, long long capacity, hipStream_t st) {
+    out.assign((size_t)(std::max(std::min(taken, capacity), 0ll) * rec_len), T(0));
+    read_records(out.data(), capacity, dev, rec_len, taken, capacity, st);
+}
+
 // A prepared problem: construction does the one-time work (X'y, Gram, rho, factorisation ...),
 // run() executes one cold-started warm-chained lambda path and may be called repeatedly.
 struct LassoPlan {
     virtual ~LassoPlan() = default;
     virtual void run(LassoResult& res) = 0;
-    // per-decision trace of the iteration control (admm_hip_lasso_plan_trace_*); solvers without one refuse
-    virtual void enable_trace(long long) { throw Error(ADMM_ERR_INVALID_ARG, "this solver records no decision trace"); }
-    virtual long long read_trace(double*, long long) { return 0; }
-    // per-iteration iterate dump (admm_hip_lasso_plan_state_*): tall and consensus solvers
-    virtual void enable_state(long long) { throw Error(ADMM_ERR_INVALID_ARG, "this solver records no iterate dump"); }
-    virtual long long read_state(float*, long long, long long*) { return 0; }
+    // The recorders, written once for every plan: the per-decision trace of the iteration control (admm_hip_lasso_plan_trace_*) and the
+    // per-iteration iterate dump (admm_hip_lasso_plan_state_*), record s = the iterates trace record s judged.  A plan supplies its
+    // stream, the floats of one iterate record and where its parameter block takes the buffers and their capacities (records()), and
+    // sets `decisions` at the end of run() by its own rule.
+    struct Records { hipStream_t st; long long rec_floats; double** trace; long long* trace_cap; float** state; long long* state_cap; };
+    virtual Records records() = 0;
+    void enable_trace(long long cap) {
+        const Records r = records();
+        trace_buf.alloc((size_t)cap * ADMM_TRACE_FIELDS);
+        decisions = 0;
+        *r.trace = trace_buf.get(); *r.trace_cap = cap;
+    }
+    long long read_trace(double* out, long long cap) {
+        const Records r = records();
+        return read_records(out, cap, trace_buf.get(), ADMM_TRACE_FIELDS, decisions, *r.trace_cap, r.st);
+    }
+    void enable_state(long long cap) {
+        const Records r = records();
+        state_buf.alloc((size_t)cap * r.rec_floats);
+        // on the solver's own (non-blocking) stream: a null-stream memset is not ordered against it and, on a busy device, landed
+        // AFTER run() had copied record 0 into the dump (suspected cause of the one unreadable record 0 of the 40-process soak, case 546:23)
+        state_buf.zero(r.st);
+        *r.state = state_buf.get(); *r.state_cap = cap;
+    }
+    long long read_state(float* out, long long cap, long long* rec_floats) {
+        const Records r = records();
+        if (rec_floats) *rec_floats = r.rec_floats;
+        if (!out) return std::min(decisions, *r.state_cap);                          // size query
+        return read_records(out, cap, state_buf.get(), r.rec_floats, decisions, *r.state_cap, r.st);      // one record per decision, same numbering as the trace
+    }
     // the float system matrix X'X + rho I the x-update solves, p x p column-major (admm_hip_lasso_plan_system_read): only
     // the tall solver with ADMM_HIP_REFINE=1 keeps it
     // the standardised data (X n x p column-major with leading dimension ld, Y) as the solver holds them (admm_hip_lasso_plan_data_read): wide solver
     virtual void read_data(float*, long long, float*) { throw Error(ADMM_ERR_INVALID_ARG, "this plan does not keep its standardised data (wide solver only)"); }
     virtual void read_system(float*, long long) { throw Error(ADMM_ERR_INVALID_ARG, "this plan does not keep its system matrix (tall solver with ADMM_HIP_REFINE=1 only)"); }
+protected:
+    long long decisions = 0;         // decisions the last run() took: records of the trace and the dump that are valid
+    DevBuf<double> trace_buf;
+    DevBuf<float> state_buf;
 };
 std::unique_ptr<LassoPlan> make_tall_plan(DeviceData<float>&& d, const LassoProblem& pb, hipStream_t st);
 std::unique_ptr<LassoPlan> make_wide_plan(DeviceData<float>&& d, const LassoProblem& pb, hipStream_t st);
