@@ -73,7 +73,9 @@ EXPORTS = ["admm_hip_lasso", "admm_hip_enet", "admm_hip_parlasso", "admm_hip_lad
            "admm_hip_parbp", "admm_hip_parbp_traced", "admm_hip_parbp_dist", "admm_hip_dantzig", "admm_hip_dantzig_traced",
            "admm_hip_lad_state", "admm_hip_bp_state", "admm_hip_lasso_plan_data_read", "admm_hip_trim_memory", "admm_hip_test_gather",
            "admm_hip_options_default", "admm_hip_options_set", "admm_hip_option_set", "admm_hip_options_reset", "admm_hip_option_get",
-           "admm_hip_last_parallel_layout", "admm_hip_parallel_assign"]
+           "admm_hip_last_parallel_layout", "admm_hip_parallel_assign", "admm_hip_grplasso", "admm_hip_grplasso_plan_create"]
+
+GROUP_MAX = 1024          # ADMM_HIP_GROUP_MAX
 
 TRACE_FIELDS = 12
 TRACE_COLD, TRACE_CONVERGED, TRACE_ACCELERATE, TRACE_RESTART = -1, 0, 1, 2
@@ -148,6 +150,11 @@ def load():
     lib.admm_hip_lasso_plan_create.argtypes = lasso_args + [ctypes.c_double, ctypes.c_int, ctypes.POINTER(AdmmOpts),
                                                ctypes.POINTER(ctypes.c_void_p), _c_int_p]
     lib.admm_hip_lasso_plan_create.restype = ctypes.c_int
+    grp_args = lasso_args[:5] + [_c_int_p, _c_double_p, ctypes.c_int] + lasso_args[5:]
+    lib.admm_hip_grplasso.argtypes = grp_args + tail
+    lib.admm_hip_grplasso.restype = ctypes.c_int
+    lib.admm_hip_grplasso_plan_create.argtypes = grp_args + [ctypes.POINTER(AdmmOpts), ctypes.POINTER(ctypes.c_void_p), _c_int_p]
+    lib.admm_hip_grplasso_plan_create.restype = ctypes.c_int
     lib.admm_hip_lasso_plan_run.argtypes = [ctypes.c_void_p, _c_double_p, _c_float_p, _c_int_p, ctypes.POINTER(AdmmStats)]
     lib.admm_hip_lasso_plan_run.restype = ctypes.c_int
     lib.admm_hip_lasso_plan_destroy.argtypes = [ctypes.c_void_p]

@@ -7,6 +7,7 @@ the same names, argument meaning, defaults and error behaviour:
     admm_enet(x, y)$penalty(..., alpha)$opts(...)$fit()             R/40_admm_enet.R
     admm_lad(x, y, intercept)$opts(...)$fit()                       R/20_admm_lad.R
     admm_bp(x, y)$opts(...)$fit()                                   R/10_admm_bp.R
+    admm_grplasso(x, y, group)$penalty(..., group_weights)$opts(...)$fit()      (not in the reference: admm_hip_grplasso)
 
 `fit()` forwards to the C ABI of libadmm_hip.so exactly where the R `$fit()` does its
 `.Call("admm_*", ...)` (R/30_admm_lasso.R:136-160 etc.).  All numerics run in the HIP library;
@@ -495,10 +496,14 @@ class LassoPlan:
         alpha = float(model.alpha) if isinstance(model, ADMM_Enet) else -1.0
         h = ctypes.c_void_p()
         nl = ctypes.c_int()
-        check(lib.admm_hip_lasso_plan_create(
-            xp, yp, model.n, model.p, xmem, ctypes.c_void_p(lam_in.ctypes.data if lam_in.size else 0), int(lam_in.size),
-            model.nlambda, model.lambda_min_ratio, int(model.standardize), int(model.intercept), alpha,
-            int(model.nthread), ctypes.byref(o), ctypes.byref(h), ctypes.byref(nl)))
+        path = (ctypes.c_void_p(lam_in.ctypes.data if lam_in.size else 0), int(lam_in.size),
+                model.nlambda, model.lambda_min_ratio, int(model.standardize), int(model.intercept))
+        if isinstance(model, ADMM_GrpLasso):
+            check(lib.admm_hip_grplasso_plan_create(xp, yp, model.n, model.p, xmem, *model._group_args(), *path,
+                                                    ctypes.byref(o), ctypes.byref(h), ctypes.byref(nl)))
+        else:
+            check(lib.admm_hip_lasso_plan_create(xp, yp, model.n, model.p, xmem, *path, alpha,
+                                                 int(model.nthread), ctypes.byref(o), ctypes.byref(h), ctypes.byref(nl)))
         self._h = h
         self.nlambda = nl.value
 
@@ -511,6 +516,8 @@ class LassoPlan:
         check(self._lib.admm_hip_lasso_plan_run(self._h, lam_out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
                                                 beta.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
                                                 niter.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), ctypes.byref(stats)))
+        if isinstance(m, ADMM_GrpLasso):
+            beta = m._restore(beta)
         return ADMM_Lasso_fit(lam_out, beta, niter, stats.as_dict())
 
     def enable_trace(self, capacity=1 << 18):
@@ -620,3 +627,91 @@ class ADMM_Dantzig(ADMM_Lasso):
 
 def admm_dantzig(x, y, intercept=True, standardize=True, **kw):
     return ADMM_Dantzig(x, y, intercept, standardize, **kw)
+
+
+class ADMM_GrpLasso(ADMM_Lasso):
+    """Group lasso on the tall path (admm_hip_grplasso; n > p only, one device): `group` gives one label per column, columns with
+    the same label enter or leave the model together.  Labels are arbitrary; the groups are numbered in order of first appearance
+    (`group_labels`), and that is the order of `group_weights`.  The library wants the columns of a group adjacent: host input
+    with scattered groups is reordered here and the coefficients are put back in the caller's column order; a DevicePtr is used in
+    place, so scattered groups are refused for it."""
+    _name = "ADMM Group Lasso model"
+    _missing = "not available for the group lasso (single-device tall solver only)"
+
+    def __init__(self, x, y, group, intercept=True, standardize=True, n=None, p=None):
+        super().__init__(x, y, intercept, standardize, n, p)
+        if self.n <= self.p:
+            _stop("nrow(x) must be greater than ncol(x): the group lasso is built for n > p only")
+        g = np.asarray(group).ravel()
+        if g.size != self.p:
+            _stop("group should have length ncol(x)")
+        labels, first, inverse = np.unique(g, return_index=True, return_inverse=True)
+        order = np.argsort(first, kind="stable")                    # groups in order of first appearance
+        rank = np.empty(order.size, dtype=np.int64)
+        rank[order] = np.arange(order.size)
+        ids = rank[np.asarray(inverse).ravel()]
+        self.group_labels = labels[order]
+        self.ngroups = int(order.size)
+        self._perm = None
+        if np.any(np.diff(ids) < 0):
+            if isinstance(x, DevicePtr):
+                _stop("the columns of a group must be adjacent with a DevicePtr (host input is reordered automatically)")
+            self._perm = np.argsort(ids, kind="stable")              # library column k = caller's column _perm[k]
+            self.x = np.asfortranarray(np.asarray(x, dtype=np.float64)[:, self._perm])
+            ids = ids[self._perm]
+        self.group = np.ascontiguousarray(ids, dtype=np.int32)
+        self.group_sizes = np.bincount(self.group, minlength=self.ngroups)
+        if self.group_sizes.max() > _lib.GROUP_MAX:
+            _stop(f"a group has more than {_lib.GROUP_MAX} columns")
+        self.group_weights = None                                    # library default: sqrt(group size)
+
+    def penalty(self, lambda_=None, nlambda=100, lambda_min_ratio=None, group_weights=None, **kw):
+        super().penalty(lambda_, nlambda, lambda_min_ratio, **kw)
+        if group_weights is not None:
+            w = np.ascontiguousarray(np.asarray(group_weights, dtype=np.float64).ravel())
+            if w.size != self.ngroups:
+                _stop("group_weights should have one entry per group (in order of first appearance)")
+            if not np.all(np.isfinite(w)) or np.any(w < 0):
+                _stop("group_weights must be finite and non-negative")
+            if not np.any(w > 0):
+                _stop("at least one group weight must be positive")
+            group_weights = w
+        self.group_weights = group_weights
+        return self
+
+    def effective_weights(self):
+        return np.sqrt(self.group_sizes.astype(np.float64)) if self.group_weights is None else self.group_weights
+
+    def parallel(self, *a, **kw):
+        _stop(self._missing)
+
+    def cv(self, *a, **kw):
+        _stop(self._missing)
+
+    def fit_responses(self, *a, **kw):
+        _stop(self._missing)
+
+    def _group_args(self):
+        w = self.group_weights
+        return (self.group.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                w.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if w is not None else None, self.ngroups)
+
+    def _restore(self, beta):
+        """Coefficient rows back into the caller's column order (row 0 is the intercept)."""
+        if self._perm is None:
+            return beta
+        out = np.zeros_like(beta)
+        out[0] = beta[0]
+        out[1 + self._perm] = beta[1:]
+        return out
+
+    def fit(self):
+        lib, head, tail, lam_out, beta, niter, stats, keep = self._common()
+        check(lib.admm_hip_grplasso(*head[:5], *self._group_args(), *head[5:], *tail))
+        fit = ADMM_Lasso_fit(lam_out, self._restore(beta), niter, stats.as_dict())
+        fit._title = "ADMM Group Lasso fitting result"
+        return fit
+
+
+def admm_grplasso(x, y, group, intercept=True, standardize=True, **kw):
+    return ADMM_GrpLasso(x, y, group, intercept, standardize, **kw)

@@ -206,6 +206,28 @@ int admm_hip_lasso_plan_create_dist_cols(const double* x_cols, const double* y, 
     });
 }
 
+// admm_hip_grplasso: the Lasso's path arguments plus the grouping of the columns
+#define GROUP_SPEC [&] { PathSpec s = PATH_SPEC(-1.0); s.grouped = true; s.group = group; s.group_weight = group_weight; s.ngroups = ngroups; s.group_cols = p; return s; }()
+
+int admm_hip_grplasso(const double* x, const double* y, int n, int p, int mem,
+                      const int* group, const double* group_weight, int ngroups,
+                      const double* lambda_in, int nlambda_in, int nlambda_auto, double lmin_ratio,
+                      int standardize, int intercept, const admm_opts* opts,
+                      double* lambda_out, float* beta_out, int* niter_out, admm_stats* stats) {
+    return guarded([&] { lasso_family(x, y, n, p, mem, GROUP_SPEC, 0, Shard(), PATH_OUT); });
+}
+
+int admm_hip_grplasso_plan_create(const double* x, const double* y, int n, int p, int mem,
+                                  const int* group, const double* group_weight, int ngroups,
+                                  const double* lambda_in, int nlambda_in, int nlambda_auto, double lmin_ratio,
+                                  int standardize, int intercept, const admm_opts* opts,
+                                  admm_hip_plan** plan_out, int* nlambda_out) {
+    return guarded([&] {
+        ADMM_REQUIRE(plan_out != nullptr, "plan_out must not be NULL");
+        plan_out_set(create_plan(x, y, n, p, mem, GROUP_SPEC, 0), plan_out, nlambda_out);
+    });
+}
+
 int admm_hip_options_default(admm_hip_options* o) {
     return guarded([&] {
         ADMM_REQUIRE(o != nullptr, "options must not be NULL");

@@ -13,6 +13,10 @@ struct PathSpec {
     double alpha = -1.0;                 // as the ABI passes it: >= 0 means elastic net (and then <= 1), anything else the plain Lasso
     const admm_opts* opts = nullptr;
     bool enet_only = false;              // admm_hip_enet has no Lasso form: it refuses a negative alpha too (R/40_admm_enet.R:38-39)
+    // group lasso (admm_hip_grplasso): the group id of every column and the groups' weights as the ABI passes them
+    bool grouped = false;
+    const int* group = nullptr; const double* group_weight = nullptr; int ngroups = 0;
+    int group_cols = 0;                  // p, the length of `group`
 
     bool enet() const { return alpha >= 0.0; }
     double alpha_eff() const { return enet() ? alpha : 1.0; }
@@ -23,6 +27,26 @@ struct PathSpec {
         ADMM_REQUIRE(nlambda_in > 0 ? lambda_in != nullptr : nlambda_auto > 0, "need a lambda grid or nlambda_auto > 0");
         if (nlambda_in == 0) ADMM_REQUIRE(lmin_ratio > 0 && lmin_ratio < 1, "lambda_min_ratio must be within (0, 1)");
         for (int i = 0; i < nlambda_in; ++i) ADMM_REQUIRE(lambda_in[i] > 0, "lambda must be positive");
+    }
+    // ... of a group-lasso call, once check_common has passed (p > 0): ids 0 .. ngroups - 1 in runs, usable weights, n > p
+    void check_groups(int n, int p) const {
+        ADMM_REQUIRE(group != nullptr, "group must not be NULL");
+        ADMM_REQUIRE(group[0] == 0, "group ids must start at 0");
+        int run = 1;
+        for (int j = 1; j < p; ++j) {
+            ADMM_REQUIRE(group[j] >= group[j - 1], "group ids must be non-decreasing (the columns of a group are adjacent)");
+            ADMM_REQUIRE(group[j] <= group[j - 1] + 1, "group ids must have no gaps");
+            run = group[j] == group[j - 1] ? run + 1 : 1;
+            ADMM_REQUIRE(run <= ADMM_HIP_GROUP_MAX, "a group has more than ADMM_HIP_GROUP_MAX (1024) columns");
+        }
+        ADMM_REQUIRE(ngroups == group[p - 1] + 1, "ngroups does not match the group ids");
+        bool any = group_weight == nullptr;
+        for (int g = 0; group_weight != nullptr && g < ngroups; ++g) {
+            ADMM_REQUIRE(std::isfinite(group_weight[g]) && group_weight[g] >= 0, "group weights must be finite and non-negative");
+            any = any || group_weight[g] > 0;
+        }
+        ADMM_REQUIRE(any, "at least one group weight must be positive");
+        ADMM_REQUIRE(n > p, "the group lasso is built for n > p only");
     }
     LassoProblem problem(int nworkers, bool dist) const {
         LassoProblem pb;
@@ -36,6 +60,13 @@ struct PathSpec {
         pb.dist = dist;
         pb.batch_iters = (int)opt_int(Opt::BATCH_ITERS, 0);
         pb.profile_stride = (int)opt_int(Opt::PROFILE_STRIDE, 0);
+        if (grouped) {                      // (checked: check_groups)
+            for (int j = 0; j < group_cols; ++j)
+                if (j == 0 || group[j] != group[j - 1]) pb.group_start.push_back(j);
+            pb.group_start.push_back(group_cols);
+            for (int g = 0; g < ngroups; ++g)
+                pb.group_weight.push_back(group_weight ? group_weight[g] : std::sqrt((double)(pb.group_start[g + 1] - pb.group_start[g])));
+        }
         return pb;
     }
     PathSpec on_grid(const std::vector<double>& lam) const {      // the same call on a grid that an earlier fit fixed

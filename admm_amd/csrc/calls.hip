@@ -46,6 +46,11 @@ PlanHandle* create_plan(const double* x, const double* y, int n, int p, int mem,
     } else if (nworkers > 0) {
         ADMM_REQUIRE(nworkers <= n, "more row blocks than rows");
     }
+    if (spec.grouped) {                                     // admm_hip_grplasso: the tall solver on one device, nothing else
+        ADMM_REQUIRE(shard.kind == Shard::NONE && nworkers <= 0 && !spec.enet(), "the group lasso has no sharded, consensus or elastic-net form");
+        spec.check_groups(n, p);
+        ADMM_REQUIRE(!opt_on(Opt::REFINE), "the group lasso has no refined x-update: unset REFINE");
+    }
     require_device();
     const double t0 = now_s();
     std::unique_ptr<PlanHandle> h(new PlanHandle());

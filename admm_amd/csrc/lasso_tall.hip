@@ -351,6 +351,141 @@ tall_tail_kernel(TallParams q, int par, PeerExchange ex) {
     WIDE_PROBE_FLUSH(blockIdx.x == 0 ? 0 : (blockIdx.x == gridDim.x - 1 ? 1 : -1), c.total - 1);
 }
 
+// ---- group lasso (admm_hip_grplasso): the same iteration with a block soft-threshold as next_z
+//     z_g = v_g max(0, 1 - pen_g / ||v_g||_2),  v = x + adj_y / rho,  pen_g = lambda w_g / rho
+// A coordinate needs the norm of its whole group before it can be written, which tall_tail_kernel (one owner lane per coordinate,
+// no coordinate sees another) cannot express.  This tail does everything that one does for its coordinates plus the norms, in the
+// same launch: the host packs whole groups into TILES -- a run of consecutive groups of at most kTailElems coordinates in all,
+// one workgroup, one pass; a group larger than that gets a workgroup of its own, which walks it in passes of kTailElems -- and the
+// coordinates' v go through LDS.  Norms are sums of (double) v^2 in a fixed order: no atomics, the same bits from run to run.
+// A group of ONE column takes the Lasso's scalar soft-threshold (tall_update_elem) bit for bit, so singleton groups of weight 1
+// reproduce admm_hip_lasso exactly (the tiles are then tall_tail_kernel's workgroups, the norm partials P the same sums).
+struct GroupCoord { int gs, gn; double w; };      // per coordinate: first column, size and weight of its group
+struct GroupTailParams {
+    const int2* tiles;                            // [TallParams.nwg]  (first coordinate, number of coordinates)
+    const GroupCoord* coord;                      // [p]
+};
+constexpr int kGroupMax = ADMM_HIP_GROUP_MAX;
+
+template <int MODE>
+__global__ void __launch_bounds__(kTailThreads)
+tall_group_tail_kernel(TallParams q, int par, GroupTailParams gp) {
+#pragma clang fp contract(off)
+    static_assert(MODE == TAIL_GEMV || MODE == TAIL_SYMV, "single device");
+    __shared__ double scratch[6 * (kTailThreads / 64)];
+    __shared__ double snrm[kTailElems];
+    // the tile's coordinates between the two halves of the update: x, adj_z, adj_y, v and what the second half still needs of the loads
+    __shared__ float sx[kGroupMax], sadjz[kGroupMax], sadjy[kGroupMax], sv[kGroupMax], szc[kGroupMax], syc[kGroupMax], sxy[kGroupMax];
+    const TallCtl c = q.ctl[par ^ 1];
+    const int2 tile = gp.tiles[blockIdx.x];
+    const int i0 = tile.x, cnt = tile.y;
+    const int sub = threadIdx.x & (kTailLanes - 1), e = threadIdx.x / kTailLanes;
+    const int npass = (cnt + kTailElems - 1) / kTailElems;
+    const bool big = cnt > kTailElems;                                   // one group walked in passes; otherwise whole small groups, one pass
+    const GroupCoord gc = gp.coord[i0 + min(e, cnt - 1)];                // (big: every coordinate of the tile has the same)
+    float* zo_ = par ? q.z0 : q.z1; float* yo_ = par ? q.y0 : q.y1;
+    const float rho_f = (float)c.rho;
+
+    // ---- first half: x-update results, extrapolation, v = x + adj_y / rho
+    for (int k = 0; k < npass; ++k) {
+        const int s = k * kTailElems + e, i = i0 + s;
+        const bool valid = s < cnt, owner = valid && sub == 0;
+        TallElem el = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (owner) el = tall_load_elem(q, par, i);
+        float a = 0.f, b = 0.f;
+        if (MODE == TAIL_SYMV) {
+            symv_sum_partials<kTailLanes>(q.dot0, q.dot1, q.axp0, q.axp1, q.ldo, q.nrb, q.sched, q.p32, i, sub, valid, a, b);
+        } else {
+            if (valid) {
+                for (int m = sub; m < q.nseg; m += kTailLanes) {
+                    const size_t o = (size_t)m * q.part_stride + i;
+                    a += q.a_part[o]; b += q.b_part[o];
+                }
+            }
+#pragma unroll
+            for (int m = 1; m < kTailLanes; m <<= 1) { a += __shfl_xor(a, m, 64); b += __shfl_xor(b, m, 64); }
+        }
+        if (c.done && c.fin_idx < 0) return;
+        if (owner) {
+            if (c.fin_idx >= 0) q.beta[(size_t)c.fin_idx * q.p + i] = el.zc;     // get_z() snapshot (Lasso.cpp:108)
+            if (!c.done) {
+                float adjz, adjy, x;
+                if (c.mode) {
+                    if (c.restart) { adjz = el.zo; adjy = el.yo; x = b; }
+                    else {
+                        const float t = (float)c.tau, t1 = (float)(1.0 + c.tau);
+                        adjz = tall_extrapolate(t1, t, el.zc, el.zo);
+                        adjy = tall_extrapolate(t1, t, el.yc, el.yo);
+                        x = a;
+                    }
+                } else { adjz = el.adjz; adjy = el.adjy; x = el.x; }
+                sx[s] = x; sadjz[s] = adjz; sadjy[s] = adjy; sv[s] = x + adjy / rho_f;
+                szc[s] = el.zc; syc[s] = el.yc; sxy[s] = el.xy;
+            }
+        }
+    }
+    if (c.done) return;
+    __syncthreads();
+
+    // ---- squared norm of this lane's group, in double, in a fixed order
+    double nrm2 = 0.0;
+    if (big) {
+        if (sub == 0) {
+            double part = 0.0;
+            for (int s = e; s < cnt; s += kTailElems) { const double v = (double)sv[s]; part += v * v; }
+            snrm[e] = part;
+        }
+        __syncthreads();
+        for (int m = 0; m < kTailElems; ++m) nrm2 += snrm[m];
+    } else if (sub == 0 && e < cnt && gc.gn > 1) {
+        const int s0 = gc.gs - i0;
+        for (int m = 0; m < gc.gn; ++m) { const double v = (double)sv[s0 + m]; nrm2 += v * v; }
+    }
+    const double pen = c.lam * gc.w / c.rho;
+    double shrink = 0.0;                                                // max(0, 1 - pen / ||v_g||)
+    if (gc.gn > 1) { const double nrm = sqrt(nrm2); shrink = nrm > pen ? 1.0 - pen / nrm : 0.0; }
+
+    // ---- second half: next_z, residual, dual update, norms, the right-hand sides of the next x-update (as tall_update_elem)
+    double acc[6] = {0, 0, 0, 0, 0, 0};
+    const float tn = (float)c.tau_next, tn1 = (float)(1.0 + c.tau_next);
+    for (int k = 0; k < npass; ++k) {
+        const int s = k * kTailElems + e, i = i0 + s;
+        if (!(s < cnt && sub == 0)) continue;
+        const float x = sx[s], adjz = sadjz[s], adjy = sadjy[s], vec = sv[s], zc = szc[s], yc = syc[s], xy = sxy[s];
+        const double v = (double)vec;
+        float zn;
+        if (gc.gn == 1) zn = v > pen ? (float)(v - pen) : (v < -pen ? (float)(v + pen) : 0.f);      // the Lasso's soft_threshold, double compare
+        else zn = (float)(v * shrink);
+        const float r = x - zn;
+        const float yn = adjy + rho_f * r;
+        const float dz = zn - zc, daz = zn - adjz;
+        acc[0] += (double)r * r; acc[1] += (double)dz * dz; acc[2] += (double)daz * daz;
+        acc[3] += (double)x * x; acc[4] += (double)zn * zn; acc[5] += (double)yn * yn;
+        q.x[i] = x; zo_[i] = zn; yo_[i] = yn; q.adj_z[i] = adjz; q.adj_y[i] = adjy;
+        if (q.state != nullptr && c.total < q.state_cap) {
+            float* st = q.state + (size_t)c.total * 5 * q.p;
+            st[i] = x; st[q.p + i] = zn; st[2 * (size_t)q.p + i] = yn; st[3 * (size_t)q.p + i] = adjz; st[4 * (size_t)q.p + i] = adjy;
+        }
+        const float adjz_a = tall_extrapolate(tn1, tn, zn, zc), adjy_a = tall_extrapolate(tn1, tn, yn, yc);
+        q.u[i] = (float)((double)(xy - adjy_a) + c.rho * (double)adjz_a);
+        q.w[i] = (float)((double)(xy - yc) + c.rho * (double)zc);
+    }
+    // block sum of the six norms: tall_tail_kernel's, value for value
+    static_assert(kTailLanes == 8, "owner lanes are the multiples of 8");
+    {
+        const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+        const double v8[8] = {acc[0], acc[1], acc[2], acc[3], acc[4], acc[5], 0.0, 0.0};
+        const double tot = halving_sum8_top(v8, lane);
+        if ((lane & 7) == 0 && lane < 48) scratch[(lane >> 3) * (kTailThreads / 64) + wid] = tot;
+        __syncthreads();
+        if (threadIdx.x < 6) {
+            double sum = 0;
+            for (int ww = 0; ww < kTailThreads / 64; ++ww) sum += scratch[threadIdx.x * (kTailThreads / 64) + ww];
+            q.P[((size_t)(par ^ 1) * q.nwg + blockIdx.x) * 8 + threadIdx.x] = sum;
+        }
+    }
+}
+
 // Round 4 also built the whole path as ONE persistent launch with a third of the inverse's triangle resident in registers (two
 // grid barriers per iteration, decision off the critical path; bit-identical): 66.7 us per iteration against 39.25 at C2 -- the
 // barriers + an in-launch tail cost 16.6 us where the kernel boundaries cost 5.6, residency saves at most 10.8 us of the stream, and
@@ -445,6 +580,11 @@ struct TallPlan final : LassoPlan {
     bool refine = false;
     DevBuf<float> Mg, rab, ruw;                          // the float system X'X + rho I; first solve a | b; residuals r_u | r_w
     DevBuf<double> dD0, dD1, xD0, xD1;                   // double partial arrays of M x1
+    // group lasso (LassoProblem.group_start): the tail is tall_group_tail_kernel over tiles of whole groups, nwg = their number
+    bool grouped = false;
+    DevBuf<int2> gtiles;
+    DevBuf<GroupCoord> gcoord;
+    GroupTailParams gq{};
     PinnedFlag hflag;
 #ifdef ADMM_HIP_PROBE
     DevBuf<long long> probe;
@@ -482,7 +622,10 @@ struct TallPlan final : LassoPlan {
             gemv_t_simple<float>(d.X.get(), d.ldx, n, p, d.Y.get(), XY.get(), st);
             if (shard) allreduce_sum_f32(XY.get(), (size_t)p, st);
         }
-        float lambda0 = device_absmax<float>(XY.get(), p, st);
+        grouped = !pb.group_start.empty();
+        ADMM_REQUIRE(!grouped || (!shard && !pb.enet && !opt_on(Opt::REFINE) && (int)pb.group_start.size() == (int)pb.group_weight.size() + 1 &&
+                                  pb.group_start.back() == p), "internal: the group lasso is the plain single-device tall solver");
+        float lambda0 = grouped ? group_lambda0() : device_absmax<float>(XY.get(), p, st);
         if (pb.enet) lambda0 = (float)(lambda0 / ((double)(float)pb.alpha + 0.0001));
 
         // lambda grid (Lasso.cpp:78-89) and internal lambdas (Lasso.cpp:99), stored as float like `Scalar lambda`
@@ -641,6 +784,7 @@ struct TallPlan final : LassoPlan {
         if (shard) use_sym = true;                       // the sharded x-update is the tile list of the symmetric kernel dealt out to the ranks
         pl = plan_gemv_t<float>(p, p, 2, 4);
         nwg = (p + kTailElems - 1) / kTailElems;
+        if (grouped) nwg = pack_group_tiles();
         ldv = round_up(p, 256);                         // symv reads the right-hand vectors in 256-row blocks
         if (use_sym) sy.init(p, st, shard ? ci.rank : 0, shard ? ci.nranks : 1);
         if (refine) {
@@ -684,6 +828,45 @@ struct TallPlan final : LassoPlan {
 
         ADMM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&hbeta), (size_t)nlam * p * sizeof(float), hipHostMallocDefault));
         comm_stream_sync(st);
+    }
+
+    // lambda_0 of the group lasso: the largest ||(X'y)_g||_2 / w_g over the penalised groups, the norm in double from the float X'y,
+    // rounded to float like the Lasso's `Scalar lambda0` (singleton groups of weight 1: exactly device_absmax)
+    float group_lambda0() {
+        std::vector<float> h(p);
+        read_back(h.data(), XY.get(), (size_t)p * sizeof(float), st);
+        double best = 0.0;
+        for (size_t g = 0; g + 1 < pb.group_start.size(); ++g) {
+            if (!(pb.group_weight[g] > 0)) continue;
+            double s2 = 0.0;
+            for (int j = pb.group_start[g]; j < pb.group_start[g + 1]; ++j) s2 += (double)h[j] * (double)h[j];
+            best = std::max(best, std::sqrt(s2) / pb.group_weight[g]);
+        }
+        return (float)best;
+    }
+
+    // Whole groups into tiles for tall_group_tail_kernel: consecutive groups while they total at most kTailElems coordinates; a
+    // larger group alone.  Returns the number of tiles (workgroups of the tail).
+    int pack_group_tiles() {
+        std::vector<int2> tiles;
+        std::vector<GroupCoord> coord(p);
+        int first = 0, count = 0;
+        const auto flush = [&] { if (count > 0) tiles.push_back(make_int2(first, count)); first += count; count = 0; };
+        for (size_t g = 0; g + 1 < pb.group_start.size(); ++g) {
+            const int gs = pb.group_start[g], gn = pb.group_start[g + 1] - gs;
+            ADMM_REQUIRE(gn >= 1 && gn <= kGroupMax && gs == first + count, "internal: bad group partition");
+            for (int j = gs; j < gs + gn; ++j) coord[j] = GroupCoord{gs, gn, pb.group_weight[g]};
+            if (count + gn > kTailElems) flush();
+            count += gn;
+            if (gn > kTailElems) flush();
+        }
+        flush();
+        gtiles.alloc(tiles.size()); gcoord.alloc(coord.size());
+        ADMM_HIP_CHECK(hipMemcpyAsync(gtiles.get(), tiles.data(), tiles.size() * sizeof(int2), hipMemcpyHostToDevice, st));
+        ADMM_HIP_CHECK(hipMemcpyAsync(gcoord.get(), coord.data(), coord.size() * sizeof(GroupCoord), hipMemcpyHostToDevice, st));
+        comm_stream_sync(st);                           // (the host vectors go out of scope)
+        gq.tiles = gtiles.get(); gq.coord = gcoord.get();
+        return (int)tiles.size();
     }
 
     Records records() override { return {st, 5ll * p, &q.trace, &q.trace_cap, &q.state, &q.state_cap}; }
@@ -735,7 +918,16 @@ struct TallPlan final : LassoPlan {
             // sampled launches carry start/stop events that time exactly the x-update kernel on this stream
             // the decision of this iteration rides along as one extra workgroup of the x-update launch
             const TallDecideExtra dec{q, par};
-            if (shard && peer_fused) {
+            if (grouped) {                             // two launches, as the Lasso: the x-update with the decision, the group tail
+                if (use_sym) {
+                    sy.launch(M.get(), ldp, u.get(), w.get(), &ctl.get()[par].done, st, dec, e0, e1);
+                    hipLaunchKernelGGL(tall_group_tail_kernel<TAIL_SYMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, gq);
+                } else {
+                    launch_gemv_t<float, 2, 4, TallDecideExtra>(pl, M.get(), ldp, p, p, u.get(), w.get(), a_part.get(), b_part.get(), ldp,
+                                                                &ctl.get()[par].done, st, dec, e0, e1);
+                    hipLaunchKernelGGL(tall_group_tail_kernel<TAIL_GEMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, gq);
+                }
+            } else if (shard && peer_fused) {
                 // this rank's tiles -> its share of (a, b) written into every rank's exchange slot by the reduction
                 // launch itself -> the (replicated) tail waits for the K flags and sums the K slots: three launches,
                 // none of them the exchange layer's

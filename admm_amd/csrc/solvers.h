@@ -19,6 +19,10 @@ struct LassoProblem {
     long long col_offset = 0;
     int batch_iters = 0;             // iterations enqueued per host poll (0 = default)
     int profile_stride = 0;          // > 0: time every stride-th x-update launch with HIP events
+    // group lasso (admm_hip_grplasso, tall solver only): group g holds columns [group_start[g], group_start[g + 1]) and is
+    // penalised by group_weight[g] * its Euclidean norm; empty = no groups
+    std::vector<int> group_start;
+    std::vector<double> group_weight;
 };
 
 struct LassoResult {

@@ -263,6 +263,32 @@ ADMM_HIP_API int admm_hip_lasso_plan_create(const double* x, const double* y, in
 ADMM_HIP_API int admm_hip_lasso_plan_run(admm_hip_plan* plan, double* lambda_out, float* beta_out, int* niter_out, admm_stats* stats);
 ADMM_HIP_API int admm_hip_lasso_plan_destroy(admm_hip_plan* plan);
 
+/* Group lasso on the tall path (n > p only; not in the reference package):
+ *     minimise 1/2 ||y_s - X_s b||^2 + lambda_int sum_g w_g ||b_g||_2
+ * in the solver's internal units (standardised data, lambda_int = lambda n / scaleY as for admm_hip_lasso).  The iteration is the
+ * tall solver's fast ADMM with the z-update replaced by a block soft-threshold (lasso_tall.hip, tall_group_tail_kernel); the lambda
+ * path, the stopping rule, niter (maxit + 1 on exhaustion) and the outputs are admm_hip_lasso's.
+ * group[p]: the group id of every column -- 0 .. ngroups - 1, non-decreasing, starting at 0, without gaps (groups are runs of
+ * adjacent columns).  group_weight[ngroups] >= 0, at least one > 0; NULL selects sqrt(group size).  A group of one column with weight
+ * w is a Lasso coefficient with penalty factor w; weight 0 leaves a group unpenalised.  A group holds at most ADMM_HIP_GROUP_MAX
+ * columns; larger groups are refused.  Single device; the row-sharded, refined (REFINE), cross-validated and multi-response forms of
+ * the Lasso do not exist for it (REFINE set: refused).
+ * Automatic grid: lambda_0 = max over the groups with w_g > 0 of ||(X_s'y_s)_g||_2 / w_g.  With unpenalised groups present the
+ * first lambda of that grid is NOT guaranteed to give an empty penalised model (the unpenalised columns have not been fitted
+ * when lambda_0 is taken): pass a grid of your own there.
+ * The plan is an ordinary admm_hip_plan: admm_hip_lasso_plan_run / _trace_* / _state_* / _destroy work on it. */
+#define ADMM_HIP_GROUP_MAX 1024
+ADMM_HIP_API int admm_hip_grplasso(const double* x, const double* y, int n, int p, int mem,
+                                   const int* group, const double* group_weight, int ngroups,
+                                   const double* lambda_in, int nlambda_in, int nlambda_auto, double lmin_ratio,
+                                   int standardize, int intercept, const admm_opts* opts,
+                                   double* lambda_out, float* beta_out, int* niter_out, admm_stats* stats);
+ADMM_HIP_API int admm_hip_grplasso_plan_create(const double* x, const double* y, int n, int p, int mem,
+                                               const int* group, const double* group_weight, int ngroups,
+                                               const double* lambda_in, int nlambda_in, int nlambda_auto, double lmin_ratio,
+                                               int standardize, int intercept, const admm_opts* opts,
+                                               admm_hip_plan** plan_out, int* nlambda_out);
+
 /* Decision trace of a prepared Lasso-family problem (tall, wide and consensus solvers): what the reference's commented-out iteration table
  * (print_row, FADMMBase.h:135-170, ADMMBase.h:111-146) would print, recorded on the device by the iteration control itself, one record
  * per decision (the cold-start decision first, then one per ADMM iteration, over all lambdas of a run in order).

@@ -98,6 +98,32 @@ BEGIN_RCPP
 END_RCPP
 }
 
+// Group lasso (not in the reference; include/admm_hip.h, admm_hip_grplasso): the arguments of admm_lasso plus `group`, the 0-based
+// group id of every column (non-decreasing, no gaps: the columns of a group adjacent), and `group_weight`, one weight per group or
+// numeric(0) for sqrt(group size).  n > p only.
+RcppExport SEXP admm_grplasso(SEXP x_, SEXP y_, SEXP lambda_, SEXP nlambda_, SEXP lmin_ratio_,
+                              SEXP standardize_, SEXP intercept_, SEXP group_, SEXP group_weight_, SEXP opts_) {
+BEGIN_RCPP
+    NumericMatrix x(x_);
+    NumericVector y(y_), lambda(lambda_), group_weight(group_weight_);
+    IntegerVector group(group_);
+    const int n = x.nrow(), p = x.ncol();
+    if (group.size() != p) Rcpp::stop("group should have length ncol(x)");
+    const int ngroups = p > 0 ? group[p - 1] + 1 : 0;
+    if (group_weight.size() != 0 && group_weight.size() != ngroups) Rcpp::stop("group_weight should have one entry per group");
+    const int nl_in = lambda.size();
+    const int nl = nl_in > 0 ? nl_in : as<int>(nlambda_);
+    admm_opts o = unpack_opts(opts_);
+    NumericVector lambda_out(nl);
+    IntegerVector niter(nl);
+    std::vector<float> beta((size_t)(p + 1) * nl);
+    check(admm_hip_grplasso(x.begin(), y.begin(), n, p, ADMM_MEM_HOST, group.begin(), group_weight.size() ? group_weight.begin() : nullptr, ngroups,
+                            nl_in > 0 ? lambda.begin() : nullptr, nl_in, as<int>(nlambda_), as<double>(lmin_ratio_),
+                            as<bool>(standardize_), as<bool>(intercept_), &o, lambda_out.begin(), beta.data(), niter.begin(), nullptr));
+    return List::create(Named("lambda") = lambda_out, Named("beta") = to_dgCMatrix(beta, p + 1, nl), Named("niter") = niter);
+END_RCPP
+}
+
 RcppExport SEXP admm_lad(SEXP x_, SEXP y_, SEXP intercept_, SEXP opts_) {
 BEGIN_RCPP
     NumericMatrix x(x_);
