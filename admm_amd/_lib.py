@@ -73,7 +73,8 @@ EXPORTS = ["admm_hip_lasso", "admm_hip_enet", "admm_hip_parlasso", "admm_hip_lad
            "admm_hip_parbp", "admm_hip_parbp_traced", "admm_hip_parbp_dist", "admm_hip_dantzig", "admm_hip_dantzig_traced",
            "admm_hip_lad_state", "admm_hip_bp_state", "admm_hip_lasso_plan_data_read", "admm_hip_trim_memory", "admm_hip_test_gather",
            "admm_hip_options_default", "admm_hip_options_set", "admm_hip_option_set", "admm_hip_options_reset", "admm_hip_option_get",
-           "admm_hip_last_parallel_layout", "admm_hip_parallel_assign", "admm_hip_grplasso", "admm_hip_grplasso_plan_create"]
+           "admm_hip_last_parallel_layout", "admm_hip_parallel_assign", "admm_hip_grplasso", "admm_hip_grplasso_plan_create",
+           "admm_hip_quantreg", "admm_hip_quantreg_state"]
 
 GROUP_MAX = 1024          # ADMM_HIP_GROUP_MAX
 
@@ -126,6 +127,13 @@ def load():
     lib.admm_hip_bp_traced.restype = ctypes.c_int
     lib.admm_hip_lad_state.argtypes = lib.admm_hip_lad_traced.argtypes + [_c_double_p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]
     lib.admm_hip_lad_state.restype = ctypes.c_int
+    lib.admm_hip_quantreg.argtypes = [_DP, _DP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_double_p, ctypes.c_int,
+                                      ctypes.POINTER(AdmmOpts), _c_double_p, _c_int_p, ctypes.POINTER(AdmmStats)]
+    lib.admm_hip_quantreg.restype = ctypes.c_int
+    lib.admm_hip_quantreg_state.argtypes = ([_DP, _DP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
+                                             ctypes.POINTER(AdmmOpts), _c_double_p, _c_int_p, ctypes.POINTER(AdmmStats)]
+                                            + [_c_double_p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)] * 2)
+    lib.admm_hip_quantreg_state.restype = ctypes.c_int
     lib.admm_hip_bp_state.argtypes = lib.admm_hip_bp_traced.argtypes + [_c_double_p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]
     lib.admm_hip_bp_state.restype = ctypes.c_int
     lib.admm_hip_dantzig.argtypes = [_DP, _DP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _DP, ctypes.c_int, ctypes.c_int, ctypes.c_double,

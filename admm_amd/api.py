@@ -477,6 +477,65 @@ class ADMM_LAD(ADMM_BP):
         return fit
 
 
+class ADMM_QuantReg_fit:
+    def __init__(self, tau, beta, niter, stats):
+        self.tau = tau              # numeric ntau
+        self.beta = beta            # (p + 1) x ntau, column k = tau[k], intercept first
+        self.niter = niter          # integer ntau
+        self.stats = stats
+
+    def __repr__(self):
+        return f"ADMM quantile regression fitting result\n\n$tau\n{self.tau}\n\n$beta\n<{self.beta.shape[0]} x {self.beta.shape[1]}> matrix\n\n$niter\n{self.niter}"
+
+    def show(self):
+        print(repr(self))
+
+
+class ADMM_QuantReg(ADMM_LAD):
+    """Quantile regression on LAD's loop (admm_hip_quantreg): one fit per entry of `tau`, the setup paid once.  Unlike ADMM_LAD the
+    intercept is fitted (a column of ones), so nrow(x) must exceed ncol(x) + intercept."""
+
+    def __init__(self, x, y, tau=0.5, intercept=True, n=None, p=None):
+        n_, p_ = _shape(x, n, p)
+        if n_ <= p_ + (1 if intercept else 0):
+            _stop("nrow(x) must be greater than ncol(x) + 1 (the intercept is fitted)" if intercept else "nrow(x) must be greater than ncol(x)")
+        ADMM_LAD.__init__(self, x, y, intercept, n, p)
+        t = np.atleast_1d(np.asarray(tau, dtype=np.float64))
+        if t.ndim != 1 or t.size < 1 or t.size > 4096:
+            _stop("tau must hold between 1 and 4096 values")
+        if not (np.all(np.isfinite(t)) and np.all(t > 0) and np.all(t < 1)):
+            _stop("every tau must lie strictly between 0 and 1")
+        self.tau = np.ascontiguousarray(t)
+
+    def fit(self, trace=False, state=0):
+        """-> ADMM_QuantReg_fit.  trace / state (as ADMM_LAD.fit, admm_hip_quantreg_state) for a single tau only."""
+        lib = _lib.load()
+        xp, xmem, xk = as_input(self.x)
+        yp, ymem, yk = as_input(self.y)
+        if xmem != ymem:
+            _stop("x and y must live in the same memory space")
+        ntau = int(self.tau.size)
+        if (trace or state) and ntau != 1:
+            _stop("trace and state are recorded for a single tau")
+        o = AdmmOpts(self.maxit, self.eps_abs, self.eps_rel, self.rho)
+        beta = np.zeros((self.p + 1) * ntau, dtype=np.float64)
+        niter = np.zeros(ntau, dtype=np.int32)
+        stats = AdmmStats()
+        bp, np_ = beta.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), niter.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+        if trace:
+            tr, ntr = _trace_buffers(self.maxit)
+            sbuf, nst = _state_buffers(state, self.n)
+            check(lib.admm_hip_quantreg_state(xp, yp, self.n, self.p, xmem, int(self.intercept), float(self.tau[0]), ctypes.byref(o),
+                                              bp, np_, ctypes.byref(stats), *_trace_args(tr, ntr), *_state_args(sbuf, nst)))
+        else:
+            check(lib.admm_hip_quantreg(xp, yp, self.n, self.p, xmem, int(self.intercept),
+                                        self.tau.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ntau, ctypes.byref(o), bp, np_, ctypes.byref(stats)))
+        fit = ADMM_QuantReg_fit(self.tau.copy(), beta.reshape(ntau, self.p + 1).T.copy(), niter.copy(), stats.as_dict())
+        fit.trace = tr[:ntr.value].copy() if trace else None
+        fit.state = sbuf[:nst.value].copy() if (trace and state) else None
+        return fit
+
+
 class LassoPlan:
     """Prepared problem (admm_hip_lasso_plan_*): setup once, run the lambda path repeatedly.
 
@@ -587,6 +646,10 @@ def admm_enet(x, y, intercept=True, standardize=True, **kw):
 
 def admm_lad(x, y, intercept=True, **kw):
     return ADMM_LAD(x, y, intercept, **kw)
+
+
+def admm_quantreg(x, y, tau=0.5, intercept=True, **kw):
+    return ADMM_QuantReg(x, y, tau, intercept, **kw)
 
 
 def admm_bp(x, y, **kw):

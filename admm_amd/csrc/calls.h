@@ -54,6 +54,8 @@ void lasso_cv(const double* x, const double* y, int n, int p, int mem, const int
 struct StateOut { double* out = nullptr; long long cap = 0; long long* n_out = nullptr; };
 struct DenseOut { double* beta_out; int* niter_out; admm_stats* stats; TraceOut trace = {}; StateOut state = {}; };
 void lad(const double* x, const double* y, int n, int p, int mem, int intercept, const admm_opts* opts, const DenseOut& out);
+// out.beta_out: (p + 1) x ntau, out.niter_out: ntau; trace / state for ntau = 1 only
+void quantreg(const double* x, const double* y, int n, int p, int mem, int intercept, const double* tau, int ntau, const admm_opts* opts, const DenseOut& out);
 void bp(const double* x, const double* y, int n, int p, int mem, const admm_opts* opts, const DenseOut& out);
 // admm_hip_parbp(_traced): over in-process ranks when PAR_DEVICES lists several devices; parbp_dist: this rank's columns of p_total
 void parbp(const double* x, const double* y, int n, int p, int mem, int nthread, const admm_opts* opts, const DenseOut& out);

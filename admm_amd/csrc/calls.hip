@@ -2,6 +2,7 @@
 #include "calls.h"
 #include "comm.h"
 #include "inproc.h"
+#include <cmath>
 
 namespace admm {
 
@@ -219,8 +220,8 @@ void finish_result(R& res, double t0, const TraceOut& trace, admm_stats* stats) 
 // What LAD, BP and ParBP share.  The standardise flags are fixed by the reference per solver; shape_ok / shape_msg is the solver's
 // precondition on the shape, blocks_ok ParBP's on nthread; `solve` fills res.beta with ncoef coefficients.
 using DenseSolve = std::function<void(const DeviceData<double>&, DenseResult&, hipStream_t)>;
-void run_dense(const double* x, const double* y, int n, int p, int mem, const admm_opts* opts, bool standardize, bool intercept,
-               bool shape_ok, const char* shape_msg, bool blocks_ok, int ncoef, const DenseSolve& solve, const DenseOut& out) {
+void check_dense(const double* x, const double* y, int n, int p, int mem, const admm_opts* opts, bool shape_ok, const char* shape_msg, bool blocks_ok,
+                 const DenseOut& out) {
     const StateOut& so = out.state;
     out.trace.check();
     ADMM_REQUIRE(so.cap == 0 || (so.out != nullptr && so.n_out != nullptr && so.cap > 0 && out.trace.cap > 0), "bad state arguments (the iterate dump needs the trace)");
@@ -229,6 +230,16 @@ void run_dense(const double* x, const double* y, int n, int p, int mem, const ad
     ADMM_REQUIRE(shape_ok, shape_msg);
     ADMM_REQUIRE(opts->rho > 0, "rho should be positive");
     ADMM_REQUIRE(blocks_ok, "nthread must be within [1, ncol(x)]");
+}
+void store_state(const DenseResult& res, const StateOut& so) {
+    if (so.cap <= 0) return;
+    std::memcpy(so.out, res.state.data(), res.state.size() * sizeof(double));
+    *so.n_out = res.state_dim > 0 ? (long long)(res.state.size() / (5 * (size_t)res.state_dim)) : 0;
+}
+void run_dense(const double* x, const double* y, int n, int p, int mem, const admm_opts* opts, bool standardize, bool intercept,
+               bool shape_ok, const char* shape_msg, bool blocks_ok, int ncoef, const DenseSolve& solve, const DenseOut& out) {
+    const StateOut& so = out.state;
+    check_dense(x, y, n, p, mem, opts, shape_ok, shape_msg, blocks_ok, out);
     require_device();
     const double t0 = now_s();
     Stream st;
@@ -240,10 +251,7 @@ void run_dense(const double* x, const double* y, int n, int p, int mem, const ad
     solve(d, res, st.s);
     for (int i = 0; i < ncoef; ++i) out.beta_out[i] = res.beta[i];
     out.niter_out[0] = res.niter;
-    if (so.cap > 0) {
-        std::memcpy(so.out, res.state.data(), res.state.size() * sizeof(double));
-        *so.n_out = res.state_dim > 0 ? (long long)(res.state.size() / (5 * (size_t)res.state_dim)) : 0;
-    }
+    store_state(res, so);
     finish_result(res, t0, out.trace, out.stats);
 }
 }  // namespace
@@ -252,6 +260,31 @@ void lad(const double* x, const double* y, int n, int p, int mem, int intercept,
     run_dense(x, y, n, p, mem, opts, true, intercept != 0,                           // LAD.cpp:34: standardize always TRUE
               n > p, "nrow(x) must be greater than ncol(x)", true, p + 1,            // R/20_admm_lad.R:21-22
               [&](const DeviceData<double>& d, DenseResult& res, hipStream_t st) { solve_lad(d, *opts, res, st); }, out);
+}
+
+// admm_hip_quantreg: LAD's checks and standardisation (always TRUE), one loop per quantile on one setup (solve_quantreg).  The
+// intercept is FITTED (a column of ones behind the standardised X), not recovered from the means as LAD's: n > p + intercept.
+void quantreg(const double* x, const double* y, int n, int p, int mem, int intercept, const double* tau, int ntau, const admm_opts* opts, const DenseOut& out) {
+    ADMM_REQUIRE(tau != nullptr, "tau must not be NULL");
+    ADMM_REQUIRE(ntau >= 1 && ntau <= 4096, "the number of quantiles must be within [1, 4096]");
+    for (int k = 0; k < ntau; ++k) ADMM_REQUIRE(std::isfinite(tau[k]) && tau[k] > 0.0 && tau[k] < 1.0, "every tau must lie strictly between 0 and 1");
+    ADMM_REQUIRE(ntau == 1 || out.trace.cap == 0, "the decision trace is recorded for a single tau");
+    const bool icpt = intercept != 0;
+    check_dense(x, y, n, p, mem, opts, (long long)n > (long long)p + (icpt ? 1 : 0),
+                icpt ? "nrow(x) must be greater than ncol(x) + 1 (the intercept is fitted)" : "nrow(x) must be greater than ncol(x)", true, out);
+    require_device();
+    const double t0 = now_s();
+    Stream st;
+    DeviceData<double> d;
+    upload_standardize<double>(d, x, y, n, p, mem, true, icpt, st.s);
+    QuantResult res;
+    begin_result(res.dense, d, out.trace);
+    res.dense.state_cap = out.state.cap;
+    solve_quantreg(d, icpt, *opts, tau, ntau, res, st.s);
+    std::memcpy(out.beta_out, res.beta.data(), res.beta.size() * sizeof(double));
+    for (int k = 0; k < ntau; ++k) out.niter_out[k] = res.niter[k];
+    store_state(res.dense, out.state);
+    finish_result(res.dense, t0, out.trace, out.stats);
 }
 
 void bp(const double* x, const double* y, int n, int p, int mem, const admm_opts* opts, const DenseOut& out) {

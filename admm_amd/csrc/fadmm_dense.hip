@@ -59,24 +59,20 @@ struct DenseParams {
     double *Xz0, *Xz1, *Xy0, *Xy1;            // X'z, X'y in the slots of z0 / z1, y0 / y1
     double* u;                                // X'vec of this iteration
     const double* cpart; int cnwg; long long cstride;      // the rows launch's partials: [cnwg][2][cstride] (X'z_new | X'y_new)
+    // the prox of g(z) = 2 sum rho_tau(-z_i) (quantile regression, admm_hip_quantreg): thresholds c_hi / rho above, c_lo / rho below,
+    // c_hi = 2 (1 - tau), c_lo = 2 tau.  LAD (tau = 0.5) and BP: both 1.0 -- the symmetric soft-threshold with 1 / rho.
+    double c_hi, c_lo;
 };
 
 constexpr int kDenseThreads = 256;
+constexpr int kQuantAutoSlots = 1;         // what QUANT_SLOTS=0 picks on the one-pass branch (decided by scripts/bench_quantreg.py)
 
-__device__ __forceinline__ double soft1(double v, double pen) {
-    return v > pen ? v - pen : (v < -pen ? v + pen : 0.0);
+__device__ __forceinline__ double soft2(double v, double hi, double lo) {
+    return v > hi ? v - hi : (v < -lo ? v + lo : 0.0);
 }
 
-__global__ void __launch_bounds__(kDenseThreads)
-dense_head_kernel(DenseParams q, int par) {
-    __shared__ double sums[8];
-    extern __shared__ __attribute__((aligned(16))) double pstage[];
-    const DenseCtl in = load_ctl_vector(q.ctl + par);
-    DenseCtl* outp = &q.ctl[par ^ 1];
-    if (in.done) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) *outp = in;
-        return;
-    }
+// The six squared norms of the previous iteration: the tail's (rows launch's) partials summed in workgroup order.  pstage: nwg_tail * 8 doubles.
+__device__ __forceinline__ void dense_head_sums(const DenseParams& q, double* pstage, double (&sums)[8]) {
     const int np = q.nwg_tail * 8;
     for (int k = threadIdx.x; k < np; k += kDenseThreads) pstage[k] = q.P[k];
     __syncthreads();
@@ -86,22 +82,34 @@ dense_head_kernel(DenseParams q, int par) {
         sums[threadIdx.x] = s;
     }
     __syncthreads();
+}
+
+// The decision on the previous iteration (FADMMBase.h:213-259): the control block the iteration runs with, whether the extrapolated
+// pair is formed, and what the decision trace records.
+struct DenseDecision {
+    DenseCtl out;
+    bool write_adj;
+    double tr_rp, tr_rd, tr_c, tr_code;
+};
+__device__ __forceinline__ DenseDecision dense_decide(const DenseParams& q, const DenseCtl& in, const double* sums) {
     const double r2 = sums[0], dz2 = sums[1], daz2 = sums[2], x2 = sums[3], z2 = sums[4], y2 = sums[5];
-    DenseCtl out = in;
+    DenseDecision D;
+    DenseCtl& out = D.out;
+    out = in;
     out.first = 0;
-    bool write_adj = true;
-    double tr_rp = 0, tr_rd = 0, tr_c = 0, tr_code = ADMM_TRACE_COLD;
+    D.write_adj = true;
+    D.tr_rp = 0; D.tr_rd = 0; D.tr_c = 0; D.tr_code = ADMM_TRACE_COLD;
     if (!in.first) {
         const double rp = sqrt(r2), rd = in.rho * sqrt(dz2);
-        tr_rp = rp; tr_rd = rd;
+        D.tr_rp = rp; D.tr_rd = rd;
         if (rp < in.eps_primal && rd < in.eps_dual) {          // converged(): adj_z/adj_y/rho stay as they are
             out.done = 1; out.conv = 1; out.niter = in.iter + 1;
-            write_adj = false;
-            tr_code = ADMM_TRACE_CONVERGED;
+            D.write_adj = false;
+            D.tr_code = ADMM_TRACE_CONVERGED;
         } else {
             const double old_c = in.adj_c;
             const double c = in.rho * rp * rp + in.rho * daz2;
-            tr_c = c; tr_code = c < 0.999 * old_c ? ADMM_TRACE_ACCELERATE : ADMM_TRACE_RESTART;
+            D.tr_c = c; D.tr_code = c < 0.999 * old_c ? ADMM_TRACE_ACCELERATE : ADMM_TRACE_RESTART;
             if (c < 0.999 * old_c) {
                 const double old_a = in.adj_a;
                 const double a = 0.5 + 0.5 * sqrt(1.0 + 4.0 * old_a * old_a);
@@ -126,17 +134,12 @@ dense_head_kernel(DenseParams q, int par) {
     out.eps_primal = fmax(fmax(sqrt(x2), sqrt(z2)), q.extra_norm) * q.eps_rel + q.sqrt_dim * q.eps_abs;
     out.eps_dual = sqrt(y2) * q.eps_rel + q.sqrt_dim * q.eps_abs;
     out.total = out.done ? in.total : in.total + 1;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        *outp = out;
-        if (out.done) *q.done = 1;
-        if (q.trace != nullptr && in.total < q.trace_cap) {      // what FADMMBase.h:135-170 (print_row, commented out there) would print
-            double* t = q.trace + (size_t)in.total * ADMM_TRACE_FIELDS;
-            t[0] = 0.0; t[1] = in.iter; t[2] = in.eps_primal; t[3] = in.eps_dual; t[4] = tr_rp; t[5] = tr_rd;
-            t[6] = tr_c; t[7] = in.adj_c; t[8] = tr_code; t[9] = in.rho; t[10] = out.rho; t[11] = 0.0;
-        }
-    }
-    if (!write_adj) return;
+    return D;
+}
 
+// The vectors the iteration starts from: adj_z / adj_y (accelerate / restart combination of the two latest z / y), the vector the
+// projection is applied to, and the same step for the one-pass forms' recurrences.  Every workgroup takes its share.
+__device__ __forceinline__ void dense_head_vectors(const DenseParams& q, const DenseCtl& in, const DenseCtl& out) {
     const int cur = in.total & 1;
     const double* zc_ = cur ? q.z1 : q.z0; const double* yc_ = cur ? q.y1 : q.y0;
     const double* zo_ = cur ? q.z0 : q.z1; const double* yo_ = cur ? q.y0 : q.y1;
@@ -213,6 +216,122 @@ dense_head_kernel(DenseParams q, int par) {
     }
 }
 
+__global__ void __launch_bounds__(kDenseThreads)
+dense_head_kernel(DenseParams q, int par) {
+    __shared__ double sums[8];
+    extern __shared__ __attribute__((aligned(16))) double pstage[];
+    const DenseCtl in = load_ctl_vector(q.ctl + par);
+    DenseCtl* outp = &q.ctl[par ^ 1];
+    if (in.done) {
+        if (blockIdx.x == 0 && threadIdx.x == 0) *outp = in;
+        return;
+    }
+    dense_head_sums(q, pstage, sums);
+    const DenseDecision D = dense_decide(q, in, sums);
+    const DenseCtl& out = D.out;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        *outp = out;
+        if (out.done) *q.done = 1;
+        if (q.trace != nullptr && in.total < q.trace_cap) {      // what FADMMBase.h:135-170 (print_row, commented out there) would print
+            double* t = q.trace + (size_t)in.total * ADMM_TRACE_FIELDS;
+            t[0] = 0.0; t[1] = in.iter; t[2] = in.eps_primal; t[3] = in.eps_dual; t[4] = D.tr_rp; t[5] = D.tr_rd;
+            t[6] = D.tr_c; t[7] = in.adj_c; t[8] = D.tr_code; t[9] = in.rho; t[10] = out.rho; t[11] = 0.0;
+        }
+    }
+    if (!D.write_adj) return;
+    dense_head_vectors(q, in, out);
+}
+
+// ---- the slotted loop of admm_hip_quantreg: S independent problems (the quantiles of a grid) advance in the same three launches
+struct QuantGrid {
+    int nslots, ntau;
+    long long slot_stride;                    // doubles between two slots' vectors (see quant_slot_params)
+    double rho0;                              // opts.rho: every quantile starts cold
+    int* next;                                // [2] the first quantile no slot has taken yet, double-buffered like the control blocks
+    int* idle;                                // [nslots] sticky: the slot has run out of quantiles (the skip word of its (X'X)^-1 u product)
+    int* niter; double* rho_fin;              // [ntau] per quantile: iterations (LAD's convention) and final rho
+    double* fin; long long fin_ld;            // [ntau][fin_ld] y - adj_y / rho + adj_z of the finished loop: what get_x needs
+};
+// slot s: every buffer of slot 0 shifted by s * stride doubles, its pair of control blocks behind slot 0's
+__device__ __forceinline__ DenseParams quant_slot_params(DenseParams q, int s, long long stride) {
+    const size_t o = (size_t)s * (size_t)stride;
+    q.x += o; q.z0 += o; q.z1 += o; q.y0 += o; q.y1 += o; q.adj_z += o; q.adj_y += o; q.vec += o; q.P += o;
+    q.Xz0 += o; q.Xz1 += o; q.Xy0 += o; q.Xy1 += o; q.u += o; q.cpart += o;
+    q.ctl += 2 * s;
+    return q;
+}
+__device__ __forceinline__ DenseCtl dense_cold_ctl(double rho, int pad) {
+    DenseCtl c;
+    c.rho = rho; c.eps_primal = 0; c.eps_dual = 0; c.adj_a = 1.0; c.adj_c = 9999.0; c.tau = 0.0;
+    c.restart = 0; c.iter = 0; c.done = 0; c.first = 1; c.total = 0; c.niter = 0; c.conv = 0; c.pad = pad;
+    return c;
+}
+// One head launch for all slots: blockIdx.y = slot.  Every workgroup evaluates the decisions of ALL slots (as dense_head_kernel's
+// workgroups all evaluate the one) and so knows, without atomics and the same on every run, which slots finish in this iteration and
+// which quantile each of them takes next: the unclaimed ones are handed out in slot order.  A finishing slot records its quantile's
+// niter, rho and get_x vector and starts the next quantile cold IN THIS LAUNCH (control block pad = the quantile's index): zero
+// iterates, first = 1, rho = opts.rho.  With no quantile left it goes idle; when all are idle the sticky `done` word is set.
+__global__ void __launch_bounds__(kDenseThreads)
+quant_head_kernel(DenseParams q0, QuantGrid G, int par) {
+    __shared__ double sums[8];
+    extern __shared__ __attribute__((aligned(16))) double pstage[];
+    const int me = blockIdx.y;
+    const bool lead = blockIdx.x == 0 && threadIdx.x == 0;
+    int next = load_flag_vector(G.next + par);
+    DenseCtl in{};
+    DenseDecision D{};
+    int take = -1;
+    bool all_idle = true;
+    for (int s = 0; s < G.nslots; ++s) {
+        const DenseParams qs = quant_slot_params(q0, s, G.slot_stride);
+        const DenseCtl cs = load_ctl_vector(qs.ctl + par);
+        if (s == me) in = cs;
+        if (cs.done) continue;                                   // idle (uniform)
+        dense_head_sums(qs, pstage, sums);
+        const DenseDecision Ds = dense_decide(qs, cs, sums);
+        int tk = -1;
+        if (Ds.out.done && next < G.ntau) tk = next++;
+        if (!Ds.out.done || tk >= 0) all_idle = false;
+        if (s == me) { D = Ds; take = tk; }
+    }
+    if (lead && me == 0) {
+        G.next[par ^ 1] = next;
+        if (all_idle) *q0.done = 1;
+    }
+    const DenseParams q = quant_slot_params(q0, me, G.slot_stride);
+    DenseCtl* outp = &q.ctl[par ^ 1];
+    if (in.done) {
+        if (lead) *outp = in;
+        return;
+    }
+    const DenseCtl& out = D.out;
+    if (!out.done) {
+        if (lead) *outp = out;
+        dense_head_vectors(q, in, out);
+        return;
+    }
+    // the slot's quantile has finished.  Out of iterations: the last extrapolated pair, as the single run's head forms it
+    if (D.write_adj) dense_head_vectors(q, in, out);
+    const int k = in.pad;
+    if (lead) { G.niter[k] = out.niter; G.rho_fin[k] = out.rho; }
+    double* fin = G.fin + (size_t)k * G.fin_ld;
+    for (int i = blockIdx.x * kDenseThreads + threadIdx.x; i < q.dim; i += gridDim.x * kDenseThreads) {      // (the mapping of dense_head_vectors: a thread reads what it wrote)
+        fin[i] = q.data_vec[i] - q.adj_y[i] / out.rho + q.adj_z[i];                                          // lad_final_vec_kernel
+        q.x[i] = 0; q.z0[i] = 0; q.z1[i] = 0; q.y0[i] = 0; q.y1[i] = 0;
+    }
+    if (take < 0) {
+        if (lead) { *outp = out; G.idle[me] = 1; }
+        return;
+    }
+    // the cold start of quantile `take`: what dense_init_kernel + the first head of a single run leave (the stale X'z, X'y of the other
+    // parity and the stale partials are multiplied by zero or skipped under `first`, the norm partials are not read)
+    const DenseCtl c0 = dense_cold_ctl(G.rho0, take);
+    const double zeros[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const DenseDecision D0 = dense_decide(q, c0, zeros);
+    if (lead) *outp = D0.out;
+    dense_head_vectors(q, c0, D0.out);
+}
+
 // LAD one-pass form: the rows of X (the stored transpose: row i is ld contiguous doubles) streamed ONCE.  A workgroup of eight waves
 // owns a run of rows and takes them R at a time: every thread holds its 2 NPT columns of the R rows, the lanes' partial dots go through
 // one halving butterfly per wave and the eight waves' sums through LDS (waves in order: a fixed order), every thread then knows
@@ -221,6 +340,109 @@ dense_head_kernel(DenseParams q, int par) {
 // The next R rows are requested before the current ones are reduced.
 constexpr int kLadThreads = 512;
 constexpr int kLadRows = 4;
+
+// What lad_rows_kernel and quant_rows_kernel (S problems on one load of the rows) share: a problem in a slot is computed by exactly
+// these functions, in the same order, as the same problem alone -- the two are bit-identical.
+// the thread's 2 NPT entries of s = the g2 product's partial rows summed in order; the thread's X'z, X'y columns cleared
+template <int NPT>
+__device__ __forceinline__ void lad_load_s(const double* __restrict__ spart, int snseg, long long sstride, long long ld, int lp, int tid,
+                                           double2 (&sv)[NPT], double2 (&az)[NPT], double2 (&ay)[NPT]) {
+#pragma unroll
+    for (int k = 0; k < NPT; ++k) {
+        const long long col = ((long long)k * kLadThreads + tid) * 2;
+        double2 a = make_double2(0.0, 0.0);
+        if (col < ld) for (int g = 0; g < snseg; ++g) { const double2 v = *reinterpret_cast<const double2*>(spart + (size_t)g * sstride + col); a.x += v.x; a.y += v.y; }
+        if (col >= lp) a.x = 0.0;
+        if (col + 1 >= lp) a.y = 0.0;
+        sv[k] = a; az[k] = make_double2(0.0, 0.0); ay[k] = make_double2(0.0, 0.0);
+    }
+}
+template <int R, int NPT>
+__device__ __forceinline__ void lad_load_rows(const double* __restrict__ Xt, long long ld, int dim, int i0, int tid, double2 (&rv)[R][NPT]) {
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        const double* row = Xt + (size_t)min(i0 + r, dim - 1) * ld;       // clamped: rows beyond the run are weighted with zero below
+#pragma unroll
+        for (int k = 0; k < NPT; ++k) {
+            const long long col = ((long long)k * kLadThreads + tid) * 2;
+            rv[r][k] = col < ld ? load16_nt<double2>(row + col) : make_double2(0.0, 0.0);
+        }
+    }
+}
+// lane 8 r: the wave's sum of row_r . s
+template <int R, int NPT>
+__device__ __forceinline__ double lad_rows_dot(const double2 (&rv)[R][NPT], const double2 (&sv)[NPT], int lane) {
+    double v8[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) v8[r] = 0.0;
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+        double d = 0.0;
+#pragma unroll
+        for (int k = 0; k < NPT; ++k) { d = fma(rv[r][k].x, sv[k].x, d); d = fma(rv[r][k].y, sv[k].y, d); }
+        v8[r] = d;
+    }
+    return halving_sum8(v8, lane);
+}
+// the entries of one problem's vectors a row needs (the same addresses in every lane)
+struct LadRowIn { double ajy, ajz, zc; };
+// row i with x_i = row_i . s known: z_i, y_i as the tail kernel forms them (same expressions, no contraction), thread 0 stores them and
+// adds up the six norms, every thread adds row_i z_i, row_i y_i to its columns of X'z, X'y.  LANE_NORMS (the slotted kernel, to hold
+// one accumulator per slot instead of six): thread k < 6 adds up norm k in nacc[0] -- the same squares added in the same order.
+template <int NPT, bool LANE_NORMS>
+__device__ __forceinline__ void lad_row_step(int i, int tid, double x, double dv, const LadRowIn& in, double rho, double pen_hi, double pen_lo,
+                                             double* __restrict__ xo, double* __restrict__ zn_, double* __restrict__ yn_,
+                                             double* state, long long state_cap, int total, int dim,
+                                             double* nacc, const double2 (&rv)[NPT], double2 (&az)[NPT], double2 (&ay)[NPT]) {
+    double zn, yn;
+    {
+#pragma clang fp contract(off)
+        zn = soft2(x - dv + in.ajy / rho, pen_hi, pen_lo);       // dense_tail_kernel, prob 0 (ADMMLAD.h:94-107)
+        const double rr = x - dv - zn;
+        yn = in.ajy + rho * rr;
+        if (LANE_NORMS && tid < 6) {
+            const double dz = zn - in.zc, daz = zn - in.ajz;
+            const double t = tid == 0 ? rr : (tid == 1 ? dz : (tid == 2 ? daz : (tid == 3 ? x : (tid == 4 ? zn : yn))));
+            nacc[0] += t * t;
+        }
+        if (tid == 0) {
+            if (!LANE_NORMS) {
+                const double dz = zn - in.zc, daz = zn - in.ajz;
+                nacc[0] += rr * rr; nacc[1] += dz * dz; nacc[2] += daz * daz; nacc[3] += x * x; nacc[4] += zn * zn; nacc[5] += yn * yn;
+            }
+            xo[i] = x; zn_[i] = zn; yn_[i] = yn;
+            if (state != nullptr && total < state_cap) {
+                double* s = state + (size_t)total * 5 * dim;
+                s[i] = x; s[(size_t)dim + i] = zn; s[2 * (size_t)dim + i] = yn; s[3 * (size_t)dim + i] = in.ajz; s[4 * (size_t)dim + i] = in.ajy;
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < NPT; ++k) {
+        az[k].x = fma(rv[k].x, zn, az[k].x); az[k].y = fma(rv[k].y, zn, az[k].y);
+        ay[k].x = fma(rv[k].x, yn, ay[k].x); ay[k].y = fma(rv[k].y, yn, ay[k].y);
+    }
+}
+// the workgroup's partial of X'z_new, X'y_new and its row of norm partials
+template <int NPT, bool LANE_NORMS>
+__device__ __forceinline__ void lad_store_partials(double* __restrict__ cpart, long long cstride, double* __restrict__ P, int tid,
+                                                   const double2 (&az)[NPT], const double2 (&ay)[NPT], const double* nacc) {
+    double* cz = cpart + ((size_t)blockIdx.x * 2) * cstride;
+    double* cy = cz + cstride;
+#pragma unroll
+    for (int k = 0; k < NPT; ++k) {
+        const long long col = ((long long)k * kLadThreads + tid) * 2;
+        if (col < cstride) { *reinterpret_cast<double2*>(cz + col) = az[k]; *reinterpret_cast<double2*>(cy + col) = ay[k]; }
+    }
+    double* Pout = P + (size_t)blockIdx.x * 8;
+    if (LANE_NORMS) {
+        if (tid < 6) Pout[tid] = nacc[0];
+    } else if (tid == 0) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) Pout[k] = nacc[k];
+    }
+}
+
 template <int NPT>
 __global__ void __launch_bounds__(kLadThreads)
 lad_rows_kernel(DenseParams q, int par, const double* __restrict__ Xt, long long ld, const double* __restrict__ spart, int snseg, long long sstride,
@@ -232,52 +454,24 @@ lad_rows_kernel(DenseParams q, int par, const double* __restrict__ Xt, long long
     const int cur = (c.total - 1) & 1;
     const double* zc_ = cur ? q.z1 : q.z0;
     double* zn_ = cur ? q.z0 : q.z1; double* yn_ = cur ? q.y0 : q.y1;
-    const double rho = c.rho, pen = 1.0 / rho;
+    const double rho = c.rho, pen_hi = q.c_hi / rho, pen_lo = q.c_lo / rho;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int row_lo = blockIdx.x * rows_per_wg, row_hi = min(q.dim, row_lo + rows_per_wg);
     double2 sv[NPT], az[NPT], ay[NPT];
-#pragma unroll
-    for (int k = 0; k < NPT; ++k) {
-        const long long col = ((long long)k * kLadThreads + tid) * 2;
-        double2 a = make_double2(0.0, 0.0);
-        if (col < ld) for (int g = 0; g < snseg; ++g) { const double2 v = *reinterpret_cast<const double2*>(spart + (size_t)g * sstride + col); a.x += v.x; a.y += v.y; }
-        if (col >= q.lp) a.x = 0.0;
-        if (col + 1 >= q.lp) a.y = 0.0;
-        sv[k] = a; az[k] = make_double2(0.0, 0.0); ay[k] = make_double2(0.0, 0.0);
-    }
-    auto load_rows = [&](int i0, double2 (&rv)[R][NPT]) {
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            const double* row = Xt + (size_t)min(i0 + r, q.dim - 1) * ld;       // clamped: rows beyond the run are weighted with zero below
-#pragma unroll
-            for (int k = 0; k < NPT; ++k) {
-                const long long col = ((long long)k * kLadThreads + tid) * 2;
-                rv[r][k] = col < ld ? load16_nt<double2>(row + col) : make_double2(0.0, 0.0);
-            }
-        }
-    };
+    lad_load_s<NPT>(spart, snseg, sstride, ld, q.lp, tid, sv, az, ay);
     double nacc[6] = {0, 0, 0, 0, 0, 0};
     double2 ra[R][NPT], rb[R][NPT];
     int buf = 0;
     auto group = [&](int i0, const double2 (&rv)[R][NPT]) {
         // the four vectors' entries of the R rows (the same addresses in every lane), requested before the reduction
-        double dv[R], ajy[R], ajz[R], zc[R];
+        double dv[R];
+        LadRowIn in[R];
 #pragma unroll
         for (int r = 0; r < R; ++r) {
             const int i = min(i0 + r, q.dim - 1);
-            dv[r] = q.data_vec[i]; ajy[r] = q.adj_y[i]; ajz[r] = q.adj_z[i]; zc[r] = zc_[i];
+            dv[r] = q.data_vec[i]; in[r].ajy = q.adj_y[i]; in[r].ajz = q.adj_z[i]; in[r].zc = zc_[i];
         }
-        double v8[8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) v8[r] = 0.0;
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            double d = 0.0;
-#pragma unroll
-            for (int k = 0; k < NPT; ++k) { d = fma(rv[r][k].x, sv[k].x, d); d = fma(rv[r][k].y, sv[k].y, d); }
-            v8[r] = d;
-        }
-        const double tot = halving_sum8(v8, lane);                   // lane 8 r: the wave's sum of row r
+        const double tot = lad_rows_dot<R, NPT>(rv, sv, lane);      // lane 8 r: the wave's sum of row r
         if ((lane & 7) == 0 && (lane >> 3) < R) wsum[buf][wid][lane >> 3] = tot;
         __syncthreads();
 #pragma unroll
@@ -287,52 +481,118 @@ lad_rows_kernel(DenseParams q, int par, const double* __restrict__ Xt, long long
             double x = wsum[buf][0][r];
 #pragma unroll
             for (int w = 1; w < NWV; ++w) x += wsum[buf][w][r];
-            double zn, yn;
-            {
-#pragma clang fp contract(off)
-                zn = soft1(x - dv[r] + ajy[r] / rho, pen);           // dense_tail_kernel, prob 0 (ADMMLAD.h:94-107)
-                const double rr = x - dv[r] - zn;
-                yn = ajy[r] + rho * rr;
-                if (tid == 0) {
-                    const double dz = zn - zc[r], daz = zn - ajz[r];
-                    nacc[0] += rr * rr; nacc[1] += dz * dz; nacc[2] += daz * daz; nacc[3] += x * x; nacc[4] += zn * zn; nacc[5] += yn * yn;
-                    q.x[i] = x; zn_[i] = zn; yn_[i] = yn;
-                    if (q.state != nullptr && c.total < q.state_cap) {
-                        double* s = q.state + (size_t)c.total * 5 * q.dim;
-                        s[i] = x; s[(size_t)q.dim + i] = zn; s[2 * (size_t)q.dim + i] = yn; s[3 * (size_t)q.dim + i] = ajz[r]; s[4 * (size_t)q.dim + i] = ajy[r];
-                    }
-                }
-            }
-#pragma unroll
-            for (int k = 0; k < NPT; ++k) {
-                az[k].x = fma(rv[r][k].x, zn, az[k].x); az[k].y = fma(rv[r][k].y, zn, az[k].y);
-                ay[k].x = fma(rv[r][k].x, yn, ay[k].x); ay[k].y = fma(rv[r][k].y, yn, ay[k].y);
-            }
+            lad_row_step<NPT, false>(i, tid, x, dv[r], in[r], rho, pen_hi, pen_lo, q.x, zn_, yn_, q.state, q.state_cap, c.total, q.dim, nacc, rv[r], az, ay);
         }
         buf ^= 1;                                                    // (the next group writes the other half of wsum: one barrier per group)
     };
     if (row_lo < row_hi) {
-        load_rows(row_lo, ra);
+        lad_load_rows<R, NPT>(Xt, ld, q.dim, row_lo, tid, ra);
         for (int i0 = row_lo; i0 < row_hi; i0 += 2 * R) {
-            if (i0 + R < row_hi) load_rows(i0 + R, rb);
+            if (i0 + R < row_hi) lad_load_rows<R, NPT>(Xt, ld, q.dim, i0 + R, tid, rb);
             group(i0, ra);
             if (i0 + R >= row_hi) break;
-            if (i0 + 2 * R < row_hi) load_rows(i0 + 2 * R, ra);
+            if (i0 + 2 * R < row_hi) lad_load_rows<R, NPT>(Xt, ld, q.dim, i0 + 2 * R, tid, ra);
             group(i0 + R, rb);
         }
     }
-    double* cz = cpart + ((size_t)blockIdx.x * 2) * q.cstride;
-    double* cy = cz + q.cstride;
+    lad_store_partials<NPT, false>(cpart, q.cstride, q.P, tid, az, ay, nacc);
+}
+
+// S problems ("slots": the quantiles of admm_hip_quantreg's grid) on ONE load of every row group.  Slot s has its own s, prox constants,
+// rho and control block, its own z / y / x / adj vectors, norm partials and X'z, X'y accumulators: all of slot 0's (q0) shifted by
+// s * slot_stride doubles (control blocks: q0.ctl + 2 s).  A slot whose control block says done (idle: its last quantile has finished
+// and none is left) does no work and stores nothing.
+template <int NPT> struct QuantRowsR { static constexpr int value = NPT <= 2 ? kLadRows : 2; };
+template <int NPT, int S>
+__global__ void __launch_bounds__(kLadThreads)
+quant_rows_kernel(DenseParams q0, long long slot_stride, const double* __restrict__ chi, const double* __restrict__ clo, int par,
+                  const double* __restrict__ Xt, long long ld, const double* __restrict__ spart0, int snseg, long long sstride,
+                  double* __restrict__ cpart0, int rows_per_wg) {
+    constexpr int R = QuantRowsR<NPT>::value, NWV = kLadThreads / 64;
+    constexpr int NU = R * (1 + 3 * S);                   // the vectors' entries a row group needs: d | per slot adj_y, adj_z, z
+    __shared__ double wsum[2][S][NWV][R];
+    __shared__ double uni[2][NU];
+    bool act[S];
+    int cur[S];
+    double rho[S], pen_hi[S], pen_lo[S];
+    bool any = false;
 #pragma unroll
-    for (int k = 0; k < NPT; ++k) {
-        const long long col = ((long long)k * kLadThreads + tid) * 2;
-        if (col < q.cstride) { *reinterpret_cast<double2*>(cz + col) = az[k]; *reinterpret_cast<double2*>(cy + col) = ay[k]; }
+    for (int s = 0; s < S; ++s) {
+        const DenseCtl c = load_ctl_vector(q0.ctl + 2 * s + (par ^ 1));      // written by this iteration's head
+        act[s] = !c.done; any = any || act[s];
+        cur[s] = (c.total - 1) & 1;
+        rho[s] = c.rho;
+        const int k = act[s] ? c.pad : 0;                                    // the slot's place in the grid of quantiles
+        pen_hi[s] = chi[k] / rho[s]; pen_lo[s] = clo[k] / rho[s];
     }
-    if (tid == 0) {
-        double* Pout = q.P + (size_t)blockIdx.x * 8;
+    if (!any) return;
+    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+    const int row_lo = blockIdx.x * rows_per_wg, row_hi = min(q0.dim, row_lo + rows_per_wg);
+    double2 sv[S][NPT], az[S][NPT], ay[S][NPT];
+    double nacc[S][1];
 #pragma unroll
-        for (int k = 0; k < 6; ++k) Pout[k] = nacc[k];
+    for (int s = 0; s < S; ++s) {
+        nacc[s][0] = 0.0;
+        if (act[s]) lad_load_s<NPT>(spart0 + s * slot_stride, snseg, sstride, ld, q0.lp, tid, sv[s], az[s], ay[s]);
     }
+    double2 ra[R][NPT], rb[R][NPT];
+    int buf = 0;
+    auto group = [&](int i0, const double2 (&rv)[R][NPT]) {
+        // the vectors' entries of the R rows: thread t < NU requests ONE of them before the reduction and passes it on through LDS
+        // (held in every lane, as lad_rows_kernel holds its four per row, they would take the registers of a slot)
+        double uval = 0.0;
+        if (tid < NU) {
+            const int kind = tid / R, i = min(i0 + tid % R, q0.dim - 1);
+            const double* src = q0.data_vec;
+            bool live = kind == 0;
+#pragma unroll
+            for (int s = 0; s < S; ++s) {
+                if (kind == 1 + 3 * s) { src = q0.adj_y + (size_t)s * slot_stride; live = act[s]; }
+                if (kind == 2 + 3 * s) { src = q0.adj_z + (size_t)s * slot_stride; live = act[s]; }
+                if (kind == 3 + 3 * s) { src = (cur[s] ? q0.z1 : q0.z0) + (size_t)s * slot_stride; live = act[s]; }
+            }
+            if (live) uval = src[i];
+        }
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            if (!act[s]) continue;
+            const double tot = lad_rows_dot<R, NPT>(rv, sv[s], lane);
+            if ((lane & 7) == 0 && (lane >> 3) < R) wsum[buf][s][wid][lane >> 3] = tot;
+        }
+        if (tid < NU) uni[buf][tid] = uval;
+        __syncthreads();
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            if (!act[s]) continue;
+            const size_t so = (size_t)s * slot_stride;
+            double* zn_ = (cur[s] ? q0.z0 : q0.z1) + so; double* yn_ = (cur[s] ? q0.y0 : q0.y1) + so;
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                const int i = i0 + r;
+                if (i >= row_hi) break;                              // uniform
+                double x = wsum[buf][s][0][r];
+#pragma unroll
+                for (int w = 1; w < NWV; ++w) x += wsum[buf][s][w][r];
+                LadRowIn in;
+                in.ajy = uni[buf][(1 + 3 * s) * R + r]; in.ajz = uni[buf][(2 + 3 * s) * R + r]; in.zc = uni[buf][(3 + 3 * s) * R + r];
+                lad_row_step<NPT, true>(i, tid, x, uni[buf][r], in, rho[s], pen_hi[s], pen_lo[s], q0.x + so, zn_, yn_, nullptr, 0, 0, q0.dim, nacc[s], rv[r], az[s], ay[s]);
+            }
+        }
+        buf ^= 1;
+    };
+    if (row_lo < row_hi) {
+        lad_load_rows<R, NPT>(Xt, ld, q0.dim, row_lo, tid, ra);
+        for (int i0 = row_lo; i0 < row_hi; i0 += 2 * R) {
+            if (i0 + R < row_hi) lad_load_rows<R, NPT>(Xt, ld, q0.dim, i0 + R, tid, rb);
+            group(i0, ra);
+            if (i0 + R >= row_hi) break;
+            if (i0 + 2 * R < row_hi) lad_load_rows<R, NPT>(Xt, ld, q0.dim, i0 + 2 * R, tid, ra);
+            group(i0 + R, rb);
+        }
+    }
+#pragma unroll
+    for (int s = 0; s < S; ++s)
+        if (act[s]) lad_store_partials<NPT, true>(cpart0 + s * slot_stride, q0.cstride, q0.P + s * slot_stride, tid, az[s], ay[s], nacc[s]);
 }
 
 // BP one-pass form: B z_new for the z the tail of this iteration just wrote (gather over its non-zeros)
@@ -353,7 +613,7 @@ dense_tail_kernel(DenseParams q, int par) {
     const int cur = (c.total - 1) & 1;           // head already advanced `total`
     const double* zc_ = cur ? q.z1 : q.z0;
     double* zn_ = cur ? q.z0 : q.z1; double* yn_ = cur ? q.y0 : q.y1;
-    const double rho = c.rho, pen = 1.0 / rho;
+    const double rho = c.rho, pen_hi = q.c_hi / rho, pen_lo = q.c_lo / rho;
     double acc[6] = {0, 0, 0, 0, 0, 0};
     for (int i = blockIdx.x * kDenseThreads + threadIdx.x; i < q.dim; i += gridDim.x * kDenseThreads) {
 #pragma clang fp contract(off)
@@ -361,14 +621,14 @@ dense_tail_kernel(DenseParams q, int par) {
         for (int s = 0; s < q.gout_nseg; ++s) g += q.gout[(size_t)s * q.gout_stride + i];
         const double adjy = q.adj_y[i], adjz = q.adj_z[i], zc = zc_[i];
         double x, zn, r;
-        if (q.prob == 0) {                        // LAD: x = P_X(vec); z = soft(x - y + adj_y/rho, 1/rho); r = x - y - z
+        if (q.prob == 0) {                        // LAD: x = P_X(vec); z = prox(x - y + adj_y/rho; c_hi/rho, c_lo/rho); r = x - y - z
             x = g;
             const double d = q.data_vec[i];
-            zn = soft1(x - d + adjy / rho, pen);
+            zn = soft2(x - d + adjy / rho, pen_hi, pen_lo);
             r = x - d - zn;
         } else {                                  // BP: x = vec + A'(AA')^-1 b - B'(B vec); z = soft(x + adj_y/rho, 1/rho); r = x - z
             x = q.vec[i] + q.data_vec[i] - g;
-            zn = soft1(x + adjy / rho, pen);
+            zn = soft2(x + adjy / rho, pen_hi, pen_lo);
             r = x - zn;
         }
         const double yn = adjy + rho * r;
@@ -436,6 +696,7 @@ struct DenseLoop {
         q.dim = dim; q.prob = prob; q.maxit = o.maxit; q.nwg_tail = nwg_tail;
         q.eps_abs = o.eps_abs; q.eps_rel = o.eps_rel; q.sqrt_dim = std::sqrt((double)dim); q.extra_norm = extra_norm;
         q.data_vec = data_vec;
+        q.c_hi = 1.0; q.c_lo = 1.0;
         q.x = x.get(); q.z0 = z0.get(); q.z1 = z1.get(); q.y0 = y0.get(); q.y1 = y1.get();
         q.adj_z = adj_z.get(); q.adj_y = adj_y.get(); q.vec = vec.get();
         q.ctl = ctl.get(); q.P = P.get(); q.done = done.get();
@@ -484,142 +745,329 @@ static void dense_collect_trace(DenseLoop& L, const DenseCtl& fc, DenseResult& r
     }
 }
 
-void solve_lad(const DeviceData<double>& d, const admm_opts& opts, DenseResult& res, hipStream_t st) {
-    const int n = d.n, p = d.p;
-    admm_stats& S = res.stats;
-    const long long ldp = round_up(p, 128);                // whole 128-blocks for the matrix-core inverse
+namespace {
 
-    // X'X, its inverse (LLT of X'X in the reference, ADMMLAD.h:186-189), X' stored for the X*s product
-    double t0 = now_s();
-    DevBuf<double> M((size_t)ldp * ldp); M.zero(st);
-    gram_full<double>(d.X.get(), d.ldx, n, p, true, M.get(), ldp, st);
-    ADMM_HIP_CHECK(hipStreamSynchronize(st));
-    S.t_gram = now_s() - t0;
-    t0 = now_s();
-    // n <= 2000: the hat-matrix branch below also needs the Cholesky factor of the same Gram matrix: keep a copy
-    bool hat = n <= 2000;
-    if (opt_off(Opt::LAD_HAT)) hat = false;
-    DevBuf<double> G2;
-    if (hat) {
-        G2.alloc((size_t)ldp * ldp);
-        ADMM_HIP_CHECK(hipMemcpyAsync(G2.get(), M.get(), (size_t)ldp * ldp * sizeof(double), hipMemcpyDeviceToDevice, st));
-    }
-    spd_inverse_f64(M.get(), ldp, p, st);
-    const long long ldxt = round_up(p, 32);
-    DevBuf<double> Xt((size_t)ldxt * n); Xt.zero(st);
-    transpose<double>(d.X.get(), d.ldx, n, p, Xt.get(), ldxt, st);
-    ADMM_HIP_CHECK(hipStreamSynchronize(st));
-    S.t_factor = now_s() - t0;
+// columns a thread of the rows kernels holds per row and, by that, how many slots the registers of quant_rows_kernel hold
+inline int lad_npt(long long ldxt) { return (int)((ldxt / 2 + kLadThreads - 1) / kLadThreads); }
+inline int quant_max_slots(int npt) { return npt <= 3 ? 4 : (npt == 4 ? 3 : (npt == 5 ? 2 : 1)); }      // (six double2 per row: two slots would spill)
 
-    DevBuf<double> ynorm_d(1);
-    hipLaunchKernelGGL(norm2_kernel, dim3(1), dim3(1024), 0, st, d.Y.get(), n, ynorm_d.get());
+// Everything of a LAD-type fit that does not depend on the prox constants, formed ONCE (setup), and the loop from a cold start
+// (loop: one quantile; loop_slots: a grid, several quantiles per pass over X).  admm_hip_lad is setup + one loop with c_hi = c_lo = 1.
+struct LadProblem {
+    const DeviceData<double>& d;
+    const admm_opts& opts;
+    hipStream_t st;
+    int n, p;
+    long long ldp, ldxt, ldh = 0;
+    bool hat = false, onepass = false;
+    int lad_nwg = 1, lad_rows = 0;
     double ynorm = 0;
-    ADMM_HIP_CHECK(hipMemcpyAsync(&ynorm, ynorm_d.get(), sizeof(double), hipMemcpyDeviceToHost, st));
-    ADMM_HIP_CHECK(hipStreamSynchronize(st));
-
-    // general branch, one-pass form (DenseParams::lp): X streamed once per iteration by rows.  LAD_ONEPASS=0: the reference's two products.
-    constexpr int kLadMaxCols = 2 * kLadThreads * 6;             // 6144 columns: six double2 per thread and row (more would spill)
-    bool onepass = !hat && p <= kLadMaxCols;
-    if (opt_off(Opt::LAD_ONEPASS)) onepass = false;
-    const int lad_nwg = std::max(1, std::min(device_info().num_cu, (n + 2 * kLadRows - 1) / (2 * kLadRows)));
-    const int lad_rows = (int)round_up((n + lad_nwg - 1) / lad_nwg, kLadRows);
-
-    DenseLoop L;
-    L.init(n, 0, opts, d.Y.get(), ynorm, st, res.trace_cap, res.state_cap, onepass ? lad_nwg : 0);
+    DevBuf<double> M, Xt, H, Xd, tvec, svec;
     GemvT<double> g1, g2, g3, gH;                // t = X' vec ; s = (X'X)^-1 t ; xs = X s ;  or xs = H vec
-    g1.init(d.X.get(), d.ldx, n, p);
-    g2.init(M.get(), ldp, p, p);
-    DevBuf<double> tvec(ldp), svec(ldp);
-    tvec.zero(st); svec.zero(st);
 
-    // n <= 2000: the reference caches the hat matrix H = X (X'X)^-1 X' = T T', T = X L^-T, and projects with one
-    // symmetric product (ADMMLAD.h:67-73,191-203).  Same here: T = X U with U = L^-T from the blocked factorisation,
-    // H = T T' on the fp64 matrix cores, then ONE mat-vec per iteration.  ADMM_HIP_LAD_HAT=0 keeps the general form.
-    DevBuf<double> H;
-    long long ldh = 0;
-    if (hat) {
-        t0 = now_s();
-        const long long ldn = round_up(n, 128);
-        const int pk = (int)round_up(p, 8);
-        DevBuf<double> U = cholesky_linvt_mfma_f64(G2.get(), ldp, p, st);          // U = L^-T (p x p, upper)
-        DevBuf<double> W((size_t)ldp * ldp), Xp((size_t)ldn * pk), T((size_t)ldn * ldp);
-        Xp.zero(st); T.zero(st);
-        transpose<double>(U.get(), ldp, (int)ldp, (int)ldp, W.get(), ldp, st);      // W = L^-1: W[j, k] = U[k, j]
-        hipLaunchKernelGGL(copy_cols_f64_kernel, dim3((n + 255) / 256, p), dim3(256), 0, st, d.X.get(), d.ldx, n, Xp.get(), ldn);
-        gemm_nt_f64(Xp.get(), ldn, W.get(), ldp, T.get(), ldn, n, p, pk, st, true); // T[i, j] = sum_k X[i, k] U[k, j]   (W = U' = L^-1: lower triangular)
-        ldh = ldn;
-        H.alloc((size_t)ldh * ldh); H.zero(st);
-        gram_full<double>(T.get(), ldn, n, p, false, H.get(), ldh, st);             // H = T T' (tcross_prod_lower)
+    LadProblem(const DeviceData<double>& d_, const admm_opts& o, hipStream_t st_) : d(d_), opts(o), st(st_), n(d_.n), p(d_.p) {}
+
+    void setup(admm_stats& S) {
+        ldp = round_up(p, 128);                // whole 128-blocks for the matrix-core inverse
+        // X'X, its inverse (LLT of X'X in the reference, ADMMLAD.h:186-189), X' stored for the X*s product
+        double t0 = now_s();
+        M.alloc((size_t)ldp * ldp); M.zero(st);
+        gram_full<double>(d.X.get(), d.ldx, n, p, true, M.get(), ldp, st);
         ADMM_HIP_CHECK(hipStreamSynchronize(st));
-        S.t_factor += now_s() - t0;
-        gH.init(H.get(), ldh, n, n);
-        gH.set_nt(gemv_stream_nt(gH.bytes()));
-        L.q.gout = gH.part.get(); L.q.gout_nseg = gH.pl.nseg; L.q.gout_stride = gH.stride;
-    } else if (!onepass) {
-        g3.init(Xt.get(), ldxt, p, n);
-        const bool nt = gemv_stream_nt(g1.bytes() + g2.bytes() + g3.bytes());        // per iteration: X', the inverse, X
-        g1.set_nt(nt); g2.set_nt(nt); g3.set_nt(nt);
-        L.q.gout = g3.part.get(); L.q.gout_nseg = g3.pl.nseg; L.q.gout_stride = g3.stride;
-    }
-    DevBuf<double> Xd, Xz0, Xz1, Xy0, Xy1, uvec, cpart;
-    if (onepass) {
-        g2.set_nt(gemv_stream_nt(g1.bytes() + g2.bytes()));
-        for (DevBuf<double>* b : {&Xd, &Xz0, &Xz1, &Xy0, &Xy1, &uvec}) { b->alloc(ldp); b->zero(st); }
-        cpart.alloc((size_t)lad_nwg * 2 * ldp); cpart.zero(st);
-        g1.run(d.Y.get(), Xd.get(), nullptr, st);                // X'd, once
-        L.q.lp = p; L.q.Xd = Xd.get(); L.q.Xz0 = Xz0.get(); L.q.Xz1 = Xz1.get(); L.q.Xy0 = Xy0.get(); L.q.Xy1 = Xy1.get(); L.q.u = uvec.get();
-        L.q.cpart = cpart.get(); L.q.cnwg = lad_nwg; L.q.cstride = ldp;
-    }
-    auto launch_rows = [&](long long g) {
-        const int par = (int)(g & 1);
-        const int npt = (int)((ldxt / 2 + kLadThreads - 1) / kLadThreads);
-#define ADMM_LAD_ROWS(N) hipLaunchKernelGGL((lad_rows_kernel<N>), dim3(lad_nwg), dim3(kLadThreads), 0, st, L.q, par, Xt.get(), ldxt, g2.part.get(), g2.pl.nseg, g2.stride, cpart.get(), lad_rows)
-        switch (npt) {
-            case 1: ADMM_LAD_ROWS(1); break;
-            case 2: ADMM_LAD_ROWS(2); break;
-            case 3: ADMM_LAD_ROWS(3); break;
-            case 4: ADMM_LAD_ROWS(4); break;
-            case 5: ADMM_LAD_ROWS(5); break;
-            default: ADMM_LAD_ROWS(6); break;
-        }
-#undef ADMM_LAD_ROWS
-    };
-
-    const int* skip = L.done.get();
-    LoopTimes lt = run_until_done(st, skip, batch_iters((int)opt_int(Opt::BATCH_ITERS, 0), 8), (long long)opts.maxit + 2, [&](long long g) {
-        L.head(g, st);
+        S.t_gram = now_s() - t0;
+        t0 = now_s();
+        // n <= 2000: the hat-matrix branch below also needs the Cholesky factor of the same Gram matrix: keep a copy
+        hat = n <= 2000;
+        if (opt_off(Opt::LAD_HAT)) hat = false;
+        DevBuf<double> G2;
         if (hat) {
-            gH.run_partials(L.vec.get(), skip, st);          // dsymv(H, vec)
-        } else if (onepass) {
-            g2.run_partials(uvec.get(), skip, st);           // s = (X'X)^-1 u, u = X'vec formed by the head from X'd, X'z, X'y
-            launch_rows(g);                                   // x = X s, z, y, norms, X'z_new, X'y_new: one pass over the rows of X
-            return;
-        } else {
-            g1.run_partials(L.vec.get(), skip, st);          // chained: the next product sums these partial rows while staging
-            g2.run_partials_from(g1, skip, st);
-            g3.run_partials_from(g2, skip, st);
+            G2.alloc((size_t)ldp * ldp);
+            ADMM_HIP_CHECK(hipMemcpyAsync(G2.get(), M.get(), (size_t)ldp * ldp * sizeof(double), hipMemcpyDeviceToDevice, st));
         }
-        L.tail(g, st);
-    });
-    S.t_loop = lt.wall_s; S.loop_ms_events = lt.events_ms; S.xupdate_launches = lt.launched;
+        spd_inverse_f64(M.get(), ldp, p, st);
+        ldxt = round_up(p, 32);
+        Xt.alloc((size_t)ldxt * n); Xt.zero(st);
+        transpose<double>(d.X.get(), d.ldx, n, p, Xt.get(), ldxt, st);
+        ADMM_HIP_CHECK(hipStreamSynchronize(st));
+        S.t_factor = now_s() - t0;
 
-    const DenseCtl fc = L.final_ctl(st);
-    res.niter = fc.niter;
-    S.total_iter = fc.niter; S.rho = fc.rho;
-    S.xupdate_variant = onepass ? 1 : 0;
-    dense_collect_trace(L, fc, res, st);
-    // get_x(): beta = (X'X)^-1 X' (y - adj_y/rho + adj_z) with the final adj and rho (ADMMLAD.h:220-225)
-    hipLaunchKernelGGL(lad_final_vec_kernel, dim3((n + 255) / 256), dim3(256), 0, st, d.Y.get(), L.adj_y.get(), L.adj_z.get(), fc.rho, n, L.vec.get());
-    g1.run(L.vec.get(), tvec.get(), nullptr, st);
-    g2.run(tvec.get(), svec.get(), nullptr, st);
+        DevBuf<double> ynorm_d(1);
+        hipLaunchKernelGGL(norm2_kernel, dim3(1), dim3(1024), 0, st, d.Y.get(), n, ynorm_d.get());
+        ADMM_HIP_CHECK(hipMemcpyAsync(&ynorm, ynorm_d.get(), sizeof(double), hipMemcpyDeviceToHost, st));
+        ADMM_HIP_CHECK(hipStreamSynchronize(st));
+
+        // general branch, one-pass form (DenseParams::lp): X streamed once per iteration by rows.  LAD_ONEPASS=0: the reference's two products.
+        constexpr int kLadMaxCols = 2 * kLadThreads * 6;             // 6144 columns: six double2 per thread and row (more would spill)
+        onepass = !hat && p <= kLadMaxCols;
+        if (opt_off(Opt::LAD_ONEPASS)) onepass = false;
+        lad_nwg = std::max(1, std::min(device_info().num_cu, (n + 2 * kLadRows - 1) / (2 * kLadRows)));
+        lad_rows = (int)round_up((n + lad_nwg - 1) / lad_nwg, kLadRows);
+
+        g1.init(d.X.get(), d.ldx, n, p);
+        g2.init(M.get(), ldp, p, p);
+        tvec.alloc(ldp); svec.alloc(ldp);
+        tvec.zero(st); svec.zero(st);
+
+        // n <= 2000: the reference caches the hat matrix H = X (X'X)^-1 X' = T T', T = X L^-T, and projects with one
+        // symmetric product (ADMMLAD.h:67-73,191-203).  Same here: T = X U with U = L^-T from the blocked factorisation,
+        // H = T T' on the fp64 matrix cores, then ONE mat-vec per iteration.  ADMM_HIP_LAD_HAT=0 keeps the general form.
+        if (hat) {
+            t0 = now_s();
+            const long long ldn = round_up(n, 128);
+            const int pk = (int)round_up(p, 8);
+            DevBuf<double> U = cholesky_linvt_mfma_f64(G2.get(), ldp, p, st);          // U = L^-T (p x p, upper)
+            DevBuf<double> W((size_t)ldp * ldp), Xp((size_t)ldn * pk), T((size_t)ldn * ldp);
+            Xp.zero(st); T.zero(st);
+            transpose<double>(U.get(), ldp, (int)ldp, (int)ldp, W.get(), ldp, st);      // W = L^-1: W[j, k] = U[k, j]
+            hipLaunchKernelGGL(copy_cols_f64_kernel, dim3((n + 255) / 256, p), dim3(256), 0, st, d.X.get(), d.ldx, n, Xp.get(), ldn);
+            gemm_nt_f64(Xp.get(), ldn, W.get(), ldp, T.get(), ldn, n, p, pk, st, true); // T[i, j] = sum_k X[i, k] U[k, j]   (W = U' = L^-1: lower triangular)
+            ldh = ldn;
+            H.alloc((size_t)ldh * ldh); H.zero(st);
+            gram_full<double>(T.get(), ldn, n, p, false, H.get(), ldh, st);             // H = T T' (tcross_prod_lower)
+            ADMM_HIP_CHECK(hipStreamSynchronize(st));
+            S.t_factor += now_s() - t0;
+            gH.init(H.get(), ldh, n, n);
+            gH.set_nt(gemv_stream_nt(gH.bytes()));
+        } else if (!onepass) {
+            g3.init(Xt.get(), ldxt, p, n);
+            const bool nt = gemv_stream_nt(g1.bytes() + g2.bytes() + g3.bytes());        // per iteration: X', the inverse, X
+            g1.set_nt(nt); g2.set_nt(nt); g3.set_nt(nt);
+        }
+        if (onepass) {
+            g2.set_nt(gemv_stream_nt(g1.bytes() + g2.bytes()));
+            Xd.alloc(ldp); Xd.zero(st);
+            g1.run(d.Y.get(), Xd.get(), nullptr, st);                // X'd, once
+        }
+    }
+
+    // get_x(): (X'X)^-1 X' vec for vec = y - adj_y/rho + adj_z with the final adj and rho (ADMMLAD.h:220-225), on the host
+    void coef_of(const double* vec, double* coef) {
+        g1.run(vec, tvec.get(), nullptr, st);
+        g2.run(tvec.get(), svec.get(), nullptr, st);
+        ADMM_HIP_CHECK(hipMemcpyAsync(coef, svec.get(), (size_t)p * sizeof(double), hipMemcpyDeviceToHost, st));
+        ADMM_HIP_CHECK(hipStreamSynchronize(st));
+    }
+
+    // One loop from a cold start with the prox constants c_hi, c_lo; coef: the p coefficients of the standardised problem.  Returns niter.
+    int loop(double c_hi, double c_lo, DenseResult& res, double* coef) {
+        admm_stats& S = res.stats;
+        DenseLoop L;
+        L.init(n, 0, opts, d.Y.get(), ynorm, st, res.trace_cap, res.state_cap, onepass ? lad_nwg : 0);
+        L.q.c_hi = c_hi; L.q.c_lo = c_lo;
+        if (hat) { L.q.gout = gH.part.get(); L.q.gout_nseg = gH.pl.nseg; L.q.gout_stride = gH.stride; }
+        else if (!onepass) { L.q.gout = g3.part.get(); L.q.gout_nseg = g3.pl.nseg; L.q.gout_stride = g3.stride; }
+        DevBuf<double> Xz0, Xz1, Xy0, Xy1, uvec, cpart;
+        if (onepass) {
+            for (DevBuf<double>* b : {&Xz0, &Xz1, &Xy0, &Xy1, &uvec}) { b->alloc(ldp); b->zero(st); }
+            cpart.alloc((size_t)lad_nwg * 2 * ldp); cpart.zero(st);
+            L.q.lp = p; L.q.Xd = Xd.get(); L.q.Xz0 = Xz0.get(); L.q.Xz1 = Xz1.get(); L.q.Xy0 = Xy0.get(); L.q.Xy1 = Xy1.get(); L.q.u = uvec.get();
+            L.q.cpart = cpart.get(); L.q.cnwg = lad_nwg; L.q.cstride = ldp;
+        }
+        auto launch_rows = [&](long long g) {
+            const int par = (int)(g & 1);
+#define ADMM_LAD_ROWS(N) hipLaunchKernelGGL((lad_rows_kernel<N>), dim3(lad_nwg), dim3(kLadThreads), 0, st, L.q, par, Xt.get(), ldxt, g2.part.get(), g2.pl.nseg, g2.stride, cpart.get(), lad_rows)
+            switch (lad_npt(ldxt)) {
+                case 1: ADMM_LAD_ROWS(1); break;
+                case 2: ADMM_LAD_ROWS(2); break;
+                case 3: ADMM_LAD_ROWS(3); break;
+                case 4: ADMM_LAD_ROWS(4); break;
+                case 5: ADMM_LAD_ROWS(5); break;
+                default: ADMM_LAD_ROWS(6); break;
+            }
+#undef ADMM_LAD_ROWS
+        };
+
+        const int* skip = L.done.get();
+        LoopTimes lt = run_until_done(st, skip, batch_iters((int)opt_int(Opt::BATCH_ITERS, 0), 8), (long long)opts.maxit + 2, [&](long long g) {
+            L.head(g, st);
+            if (hat) {
+                gH.run_partials(L.vec.get(), skip, st);          // dsymv(H, vec)
+            } else if (onepass) {
+                g2.run_partials(uvec.get(), skip, st);           // s = (X'X)^-1 u, u = X'vec formed by the head from X'd, X'z, X'y
+                launch_rows(g);                                   // x = X s, z, y, norms, X'z_new, X'y_new: one pass over the rows of X
+                return;
+            } else {
+                g1.run_partials(L.vec.get(), skip, st);          // chained: the next product sums these partial rows while staging
+                g2.run_partials_from(g1, skip, st);
+                g3.run_partials_from(g2, skip, st);
+            }
+            L.tail(g, st);
+        });
+        S.t_loop += lt.wall_s; S.loop_ms_events += lt.events_ms; S.xupdate_launches += lt.launched;
+
+        const DenseCtl fc = L.final_ctl(st);
+        S.total_iter += fc.niter; S.rho = fc.rho;
+        S.xupdate_variant = onepass ? 1 : 0;
+        dense_collect_trace(L, fc, res, st);
+        hipLaunchKernelGGL(lad_final_vec_kernel, dim3((n + 255) / 256), dim3(256), 0, st, d.Y.get(), L.adj_y.get(), L.adj_z.get(), fc.rho, n, L.vec.get());
+        coef_of(L.vec.get(), coef);
+        return fc.niter;
+    }
+
+    // A grid of quantiles, S >= 2 of them per pass over X (one-pass branch only).  Per iteration: quant_head_kernel for all slots, ONE
+    // batched launch of the slots' (X'X)^-1 u products (g2's plan: the partials of the single run), quant_rows_kernel.  The slots refill
+    // on the device; the host polls the one `done` word.  coef: [ntau][p].
+    void loop_slots(int S_, const std::vector<double>& c_hi, const std::vector<double>& c_lo, admm_stats& S, int* niter, double* coef) {
+        const int ntau = (int)c_hi.size(), nslots = S_;
+        const long long ldn = round_up(n, 32);
+        const size_t gpart_sz = (size_t)g2.pl.nseg * g2.stride;
+        // one slot: 8 n-vectors | X'z (2), X'y (2), u | norm partials | the rows launch's partials | the product's partial rows
+        const size_t o_p = 8 * (size_t)ldn, o_P = o_p + 5 * (size_t)ldp, o_c = o_P + (size_t)lad_nwg * 8, o_g = o_c + (size_t)lad_nwg * 2 * ldp;
+        const size_t stride = round_up_sz(o_g + gpart_sz, 32);
+        DevBuf<double> pool(stride * nslots), fin((size_t)ntau * ldn), chi_d(ntau), clo_d(ntau), rho_fin(ntau);
+        DevBuf<DenseCtl> ctl(2 * (size_t)nslots);
+        DevBuf<int> ints(3 + nslots + ntau);                     // done | next[2] | idle[nslots] | niter[ntau]
+        DevBuf<GemvTArgs<double>> batch(nslots);
+        pool.zero(st); fin.zero(st); rho_fin.zero(st);
+        std::vector<int> hi(3 + nslots + ntau, 0);
+        hi[1] = hi[2] = nslots;                                  // slots 0 .. S-1 start with the first S quantiles
+        std::vector<DenseCtl> hc(2 * (size_t)nslots);
+        for (int s = 0; s < nslots; ++s) {
+            DenseCtl c;
+            c.rho = opts.rho; c.eps_primal = 0; c.eps_dual = 0; c.adj_a = 1.0; c.adj_c = 9999.0; c.tau = 0.0;
+            c.restart = 0; c.iter = 0; c.done = 0; c.first = 1; c.total = 0; c.niter = 0; c.conv = 0; c.pad = s;
+            hc[2 * s] = hc[2 * s + 1] = c;
+        }
+        DenseParams q{};
+        double* b = pool.get();
+        q.dim = n; q.prob = 0; q.maxit = opts.maxit; q.nwg_tail = lad_nwg;
+        q.eps_abs = opts.eps_abs; q.eps_rel = opts.eps_rel; q.sqrt_dim = std::sqrt((double)n); q.extra_norm = ynorm;
+        q.data_vec = d.Y.get();
+        q.x = b; q.z0 = b + ldn; q.z1 = b + 2 * ldn; q.y0 = b + 3 * ldn; q.y1 = b + 4 * ldn; q.adj_z = b + 5 * ldn; q.adj_y = b + 6 * ldn; q.vec = b + 7 * ldn;
+        q.ctl = ctl.get(); q.P = b + o_P; q.done = ints.get();
+        q.lp = p; q.Xd = Xd.get(); q.Xz0 = b + o_p; q.Xz1 = b + o_p + ldp; q.Xy0 = b + o_p + 2 * ldp; q.Xy1 = b + o_p + 3 * ldp; q.u = b + o_p + 4 * ldp;
+        q.cpart = b + o_c; q.cnwg = lad_nwg; q.cstride = ldp;
+        q.c_hi = 1.0; q.c_lo = 1.0;                              // (unused: the slots' constants are chi / clo of their quantile)
+        QuantGrid G{};
+        G.nslots = nslots; G.ntau = ntau; G.slot_stride = (long long)stride; G.rho0 = opts.rho;
+        G.next = ints.get() + 1; G.idle = ints.get() + 3; G.niter = ints.get() + 3 + nslots; G.rho_fin = rho_fin.get();
+        G.fin = fin.get(); G.fin_ld = ldn;
+        std::vector<GemvTArgs<double>> hb(nslots);
+        for (int s = 0; s < nslots; ++s) {
+            hb[s] = g2.args_partials(q.u + s * stride, G.idle + s);
+            hb[s].out[0] = b + s * stride + o_g;
+        }
+        ADMM_HIP_CHECK(hipMemcpyAsync(ints.get(), hi.data(), hi.size() * sizeof(int), hipMemcpyHostToDevice, st));
+        ADMM_HIP_CHECK(hipMemcpyAsync(ctl.get(), hc.data(), hc.size() * sizeof(DenseCtl), hipMemcpyHostToDevice, st));
+        ADMM_HIP_CHECK(hipMemcpyAsync(chi_d.get(), c_hi.data(), ntau * sizeof(double), hipMemcpyHostToDevice, st));
+        ADMM_HIP_CHECK(hipMemcpyAsync(clo_d.get(), c_lo.data(), ntau * sizeof(double), hipMemcpyHostToDevice, st));
+        ADMM_HIP_CHECK(hipMemcpyAsync(batch.get(), hb.data(), hb.size() * sizeof(GemvTArgs<double>), hipMemcpyHostToDevice, st));
+        ADMM_HIP_CHECK(hipStreamSynchronize(st));                // (the host vectors above are read by the copies)
+
+        const int nwg_head = std::max(1, std::min(device_info().num_cu, (n + kDenseThreads - 1) / kDenseThreads));
+        const double* spart0 = b + o_g;
+        double* cpart0 = b + o_c;
+        auto launch_rows = [&](int par) {
+#define ADMM_QUANT_ROWS(N, SS) hipLaunchKernelGGL((quant_rows_kernel<N, SS>), dim3(lad_nwg), dim3(kLadThreads), 0, st, q, (long long)stride, chi_d.get(), clo_d.get(), par, \
+                                                  Xt.get(), ldxt, spart0, g2.pl.nseg, g2.stride, cpart0, lad_rows)
+            switch (lad_npt(ldxt) * 10 + nslots) {
+                case 12: ADMM_QUANT_ROWS(1, 2); break;
+                case 13: ADMM_QUANT_ROWS(1, 3); break;
+                case 14: ADMM_QUANT_ROWS(1, 4); break;
+                case 22: ADMM_QUANT_ROWS(2, 2); break;
+                case 23: ADMM_QUANT_ROWS(2, 3); break;
+                case 24: ADMM_QUANT_ROWS(2, 4); break;
+                case 32: ADMM_QUANT_ROWS(3, 2); break;
+                case 33: ADMM_QUANT_ROWS(3, 3); break;
+                case 34: ADMM_QUANT_ROWS(3, 4); break;
+                case 42: ADMM_QUANT_ROWS(4, 2); break;
+                case 43: ADMM_QUANT_ROWS(4, 3); break;
+                case 52: ADMM_QUANT_ROWS(5, 2); break;
+                default: throw Error(ADMM_ERR_INTERNAL, "quantile slots: no rows kernel for this layout");
+            }
+#undef ADMM_QUANT_ROWS
+        };
+        const long long bound = (long long)ntau * ((long long)opts.maxit + 2);      // (all quantiles through one slot)
+        LoopTimes lt = run_until_done(st, (const int*)ints.get(), batch_iters((int)opt_int(Opt::BATCH_ITERS, 0), 8), bound, [&](long long g) {
+            const int par = (int)(g & 1);
+            hipLaunchKernelGGL(quant_head_kernel, dim3(nwg_head, nslots), dim3(kDenseThreads), (size_t)lad_nwg * 8 * sizeof(double), st, q, G, par);
+            launch_gemv_t_batch<double>(batch.get(), nslots, g2.pl.grid, g2.pl.lds_bytes, g2.pl.nt, st);
+            launch_rows(par);
+        });
+        S.t_loop += lt.wall_s; S.loop_ms_events += lt.events_ms; S.xupdate_launches += lt.launched;
+        read_back(hi.data(), ints.get(), hi.size() * sizeof(int), st);
+        std::vector<double> hr(ntau);
+        read_back(hr.data(), rho_fin.get(), ntau * sizeof(double), st);
+        for (int k = 0; k < ntau; ++k) {
+            niter[k] = hi[3 + nslots + k];
+            S.total_iter += niter[k];
+            coef_of(fin.get() + (size_t)k * ldn, coef + (size_t)k * p);
+        }
+        S.rho = hr[ntau - 1];
+        S.xupdate_variant = 8 + nslots;
+    }
+};
+
+}  // namespace
+
+void solve_lad(const DeviceData<double>& d, const admm_opts& opts, DenseResult& res, hipStream_t st) {
+    const int p = d.p;
+    LadProblem P(d, opts, st);
+    P.setup(res.stats);
     std::vector<double> coef(p), out(p);
-    ADMM_HIP_CHECK(hipMemcpyAsync(coef.data(), svec.get(), (size_t)p * sizeof(double), hipMemcpyDeviceToHost, st));
-    ADMM_HIP_CHECK(hipStreamSynchronize(st));
+    res.niter = P.loop(1.0, 1.0, res, coef.data());
     double b0 = 0;
     recover_coef<double>(d, coef.data(), &b0, out.data());      // LAD.cpp:41
     res.beta.assign(p + 1, 0.0);
     res.beta[0] = b0;
     for (int j = 0; j < p; ++j) res.beta[j + 1] = out[j];
+}
+
+// ---------------------------------------------------------------------------------------------- quantile regression
+__global__ void __launch_bounds__(256) ones_column_kernel(double* col, int n, long long ld) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < ld) col[i] = i < n ? 1.0 : 0.0;
+}
+
+// d: the standardised data (DataStd flag 3 with the intercept, 1 without); with the intercept the loop fits one more column of ones.
+void solve_quantreg(DeviceData<double>& d, bool intercept, const admm_opts& opts, const double* tau, int ntau, QuantResult& res, hipStream_t st) {
+    const int n = d.n, p0 = d.p;
+    if (intercept) {                                             // X | 1
+        DevBuf<double> X1((size_t)d.ldx * (p0 + 1));
+        ADMM_HIP_CHECK(hipMemcpyAsync(X1.get(), d.X.get(), (size_t)d.ldx * p0 * sizeof(double), hipMemcpyDeviceToDevice, st));
+        hipLaunchKernelGGL(ones_column_kernel, dim3((unsigned)((d.ldx + 255) / 256)), dim3(256), 0, st, X1.get() + (size_t)d.ldx * p0, n, d.ldx);
+        ADMM_HIP_CHECK(hipStreamSynchronize(st));
+        d.X = std::move(X1);
+        d.p = p0 + 1;
+    }
+    const int p = d.p;
+    DenseResult& dr = res.dense;
+    LadProblem P(d, opts, st);
+    P.setup(dr.stats);
+    std::vector<double> c_hi(ntau), c_lo(ntau);
+    for (int k = 0; k < ntau; ++k) { c_hi[k] = 2.0 * (1.0 - tau[k]); c_lo[k] = 2.0 * tau[k]; }
+
+    // slots: the one-pass branch only; QUANT_SLOTS 0 = automatic, 1 = serial, 2 .. 8 = at most that many, clipped to what the registers
+    // of the shape's layout hold and to the number of quantiles.  The get_x vectors of all quantiles (n x ntau) must fit beside the problem.
+    int slots = 1;
+    if (P.onepass && dr.trace_cap == 0 && ntau >= 2) {
+        const long long want = opt_int(Opt::QUANT_SLOTS, 0);
+        slots = want == 0 ? kQuantAutoSlots : (int)want;
+        slots = std::min(std::min(slots, quant_max_slots(lad_npt(P.ldxt))), ntau);
+        if ((size_t)ntau * (size_t)n * sizeof(double) > (size_t(2) << 30)) slots = 1;
+    }
+    std::vector<double> coef((size_t)ntau * p);
+    res.niter.assign(ntau, 0);
+    if (slots >= 2) {
+        P.loop_slots(slots, c_hi, c_lo, dr.stats, res.niter.data(), coef.data());
+    } else {
+        for (int k = 0; k < ntau; ++k) res.niter[k] = P.loop(c_hi[k], c_lo[k], dr, coef.data() + (size_t)k * p);
+    }
+    dr.niter = res.niter[0];
+    // beta_j = b_j scaleY / scaleX_j;  beta_0 = (meanY - sum beta_j meanX_j) + scaleY b_{p+1}
+    res.beta.assign((size_t)(p0 + 1) * ntau, 0.0);
+    d.p = p0;                                                    // (recover_coef: the user's columns)
+    std::vector<double> out(p0);
+    for (int k = 0; k < ntau; ++k) {
+        const double* b = coef.data() + (size_t)k * p;
+        double b0 = 0;
+        recover_coef<double>(d, b, &b0, out.data());
+        if (intercept) b0 = b0 + d.scaleY * b[p0];
+        double* col = res.beta.data() + (size_t)k * (p0 + 1);
+        col[0] = b0;
+        for (int j = 0; j < p0; ++j) col[j + 1] = out[j];
+    }
+    d.p = p;
 }
 
 // ---------------------------------------------------------------------------------------------- BP

@@ -114,6 +114,16 @@ struct DenseResult {
 };
 void solve_lad(const DeviceData<double>& d, const admm_opts& opts, DenseResult& res, hipStream_t st);
 void solve_bp(const DeviceData<double>& d, const admm_opts& opts, DenseResult& res, hipStream_t st);
+// admm_hip_quantreg (fadmm_dense.hip): LAD's loop with the prox of the check loss, one cold-started loop per quantile on ONE setup;
+// on the one-pass branch several quantiles per pass over X (QUANT_SLOTS).  d: the standardised data (DataStd flag 3 with the
+// intercept, 1 without); with the intercept the loop fits a further column of ones, which solve_quantreg appends to d.X.
+// beta: (p + 1) x ntau column-major, row 0 = intercept.  dense: stats, and for a single quantile the trace / iterate dump.
+struct QuantResult {
+    DenseResult dense;
+    std::vector<double> beta;
+    std::vector<int> niter;
+};
+void solve_quantreg(DeviceData<double>& d, bool intercept, const admm_opts& opts, const double* tau, int ntau, QuantResult& res, hipStream_t st);
 // admm_dantzig (dantzig.hip): the Dantzig selector path in double.  res.beta: (p + 1) x nlambda column-major, row 0 = intercept.
 struct DantzigResult {
     std::vector<double> lambda, beta;

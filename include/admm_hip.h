@@ -247,6 +247,25 @@ ADMM_HIP_API int admm_hip_bp_state(const double* x, const double* y, int n, int 
                       double* beta_out, int* niter_out, admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out,
                       double* state_out, long long state_cap, long long* nstate_out);
 
+/* Quantile regression (no counterpart in the reference): minimise sum_i rho_tau(y_i - b0 - x_i'b), rho_tau(r) = tau r for r >= 0 and
+ * (tau - 1) r below, for every tau[k] of a grid -- admm_hip_lad's loop (ADMMLAD.h with z = X b - y) with the prox of
+ * g(z) = 2 sum rho_tau(-z_i): thresholds 2 (1 - tau) / rho above and 2 tau / rho below; tau = 0.5 without intercept is admm_hip_lad
+ * bit for bit.  The setup (X'X, its inverse, the hat matrix for n <= 2000) is paid once per call; every tau runs from a cold start.
+ * n > 2000 and p + intercept <= 6144: several quantiles advance per pass over X (option QUANT_SLOTS) -- every column is bit-identical
+ * to the same tau fitted alone.
+ * INTERCEPT: unlike admm_hip_lad, which recovers it as mean(y) - mean(x)'b (LAD.cpp:41: right for no tau but by symmetry of the
+ * noise), the intercept is FITTED: x is standardised as LAD's (DataStd flag 3 / 1), a column of ones is appended and the loop fits
+ * p + 1 coefficients.  Hence n > p + intercept.
+ * tau[ntau] (1 <= ntau <= 4096) strictly inside (0, 1), in any order, repeats allowed.  beta_out[(p + 1) * ntau]: column k = tau[k],
+ * intercept first (0 when intercept = 0); niter_out[ntau] as admm_hip_lad's.  stats->xupdate_variant: 0 / 1 as admm_hip_lad when the
+ * quantiles ran one after another, 8 + S when S >= 2 ran per pass.
+ * _state: one tau with the decision trace and (state_cap > 0) the iterate dump, layouts as admm_hip_lad_state (dim = n). */
+ADMM_HIP_API int admm_hip_quantreg(const double* x, const double* y, int n, int p, int mem, int intercept, const double* tau, int ntau,
+                      const admm_opts* opts, double* beta_out, int* niter_out, admm_stats* stats);
+ADMM_HIP_API int admm_hip_quantreg_state(const double* x, const double* y, int n, int p, int mem, int intercept, double tau, const admm_opts* opts,
+                            double* beta_out, int* niter_out, admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out,
+                            double* state_out, long long state_cap, long long* nstate_out);
+
 /* Prepared-problem variant of the Lasso family (the "persistent context" anticipated for a
  * re-fitting caller; the R shim does not need it).  create = everything the reference does
  * before its lambda loop (copy/convert, DataStd, X'y, Gram, Spectra, factorisation:

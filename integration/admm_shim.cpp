@@ -136,6 +136,22 @@ BEGIN_RCPP
 END_RCPP
 }
 
+// Quantile regression (not in the reference): .Call("admm_quantreg", x, y, tau, intercept, opts) -> beta: (p + 1) x length(tau)
+// numeric matrix, column k = tau[k], intercept first; niter: integer vector.  The intercept is fitted, not recovered as admm_lad's.
+RcppExport SEXP admm_quantreg(SEXP x_, SEXP y_, SEXP tau_, SEXP intercept_, SEXP opts_) {
+BEGIN_RCPP
+    NumericMatrix x(x_);
+    NumericVector y(y_), tau(tau_);
+    admm_opts o = unpack_opts(opts_);
+    const int ntau = tau.size();
+    NumericMatrix beta(x.ncol() + 1, ntau);
+    IntegerVector niter(ntau);
+    check(admm_hip_quantreg(x.begin(), y.begin(), x.nrow(), x.ncol(), ADMM_MEM_HOST, as<bool>(intercept_), tau.begin(), ntau, &o,
+                            beta.begin(), niter.begin(), nullptr));
+    return List::create(Named("tau") = tau, Named("beta") = beta, Named("niter") = niter);
+END_RCPP
+}
+
 // The symbol R/50_admm_dantzig.R:38 asks for and the reference never builds (src/TODO/Dantzig.cpp:32-99): doubles throughout.
 RcppExport SEXP admm_dantzig(SEXP x_, SEXP y_, SEXP lambda_, SEXP nlambda_, SEXP lmin_ratio_, SEXP standardize_, SEXP intercept_, SEXP opts_) {
 BEGIN_RCPP
