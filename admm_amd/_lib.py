@@ -74,9 +74,12 @@ EXPORTS = ["admm_hip_lasso", "admm_hip_enet", "admm_hip_parlasso", "admm_hip_lad
            "admm_hip_lad_state", "admm_hip_bp_state", "admm_hip_lasso_plan_data_read", "admm_hip_trim_memory", "admm_hip_test_gather",
            "admm_hip_options_default", "admm_hip_options_set", "admm_hip_option_set", "admm_hip_options_reset", "admm_hip_option_get",
            "admm_hip_last_parallel_layout", "admm_hip_parallel_assign", "admm_hip_grplasso", "admm_hip_grplasso_plan_create",
-           "admm_hip_quantreg", "admm_hip_quantreg_state"]
+           "admm_hip_quantreg", "admm_hip_quantreg_state",
+           "admm_hip_mtlasso", "admm_hip_mtlasso_plan_create", "admm_hip_test_symv_multi"]
 
 GROUP_MAX = 1024          # ADMM_HIP_GROUP_MAX
+MT_MAX = 16               # ADMM_HIP_MT_MAX
+MT_RHS_BUILT = (2, 4, 8, 12)      # right-hand sides per pass the multi-vector kernel is built for (option MT_RHS; 0 = automatic)
 
 TRACE_FIELDS = 12
 TRACE_COLD, TRACE_CONVERGED, TRACE_ACCELERATE, TRACE_RESTART = -1, 0, 1, 2
@@ -163,6 +166,11 @@ def load():
     lib.admm_hip_grplasso.restype = ctypes.c_int
     lib.admm_hip_grplasso_plan_create.argtypes = grp_args + [ctypes.POINTER(AdmmOpts), ctypes.POINTER(ctypes.c_void_p), _c_int_p]
     lib.admm_hip_grplasso_plan_create.restype = ctypes.c_int
+    mt_args = lasso_args[:4] + [ctypes.c_int, ctypes.c_int, _c_double_p] + lasso_args[5:]
+    lib.admm_hip_mtlasso.argtypes = mt_args + tail
+    lib.admm_hip_mtlasso.restype = ctypes.c_int
+    lib.admm_hip_mtlasso_plan_create.argtypes = mt_args + [ctypes.POINTER(AdmmOpts), ctypes.POINTER(ctypes.c_void_p), _c_int_p]
+    lib.admm_hip_mtlasso_plan_create.restype = ctypes.c_int
     lib.admm_hip_lasso_plan_run.argtypes = [ctypes.c_void_p, _c_double_p, _c_float_p, _c_int_p, ctypes.POINTER(AdmmStats)]
     lib.admm_hip_lasso_plan_run.restype = ctypes.c_int
     lib.admm_hip_lasso_plan_destroy.argtypes = [ctypes.c_void_p]
@@ -226,6 +234,8 @@ def load():
     lib.admm_hip_lasso_plan_system_read.restype = ctypes.c_int
     lib.admm_hip_test_symv.argtypes = [_c_float_p, ctypes.c_int, _c_float_p, _c_float_p, _c_float_p, _c_float_p]
     lib.admm_hip_test_symv.restype = ctypes.c_int
+    lib.admm_hip_test_symv_multi.argtypes = [_c_float_p, ctypes.c_int, _c_float_p, ctypes.c_int, ctypes.c_int, _c_float_p]
+    lib.admm_hip_test_symv_multi.restype = ctypes.c_int
     lib.admm_hip_test_gram.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
     lib.admm_hip_test_gram.restype = ctypes.c_int
     lib.admm_hip_test_gemv_t.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]

@@ -8,6 +8,7 @@ the same names, argument meaning, defaults and error behaviour:
     admm_lad(x, y, intercept)$opts(...)$fit()                       R/20_admm_lad.R
     admm_bp(x, y)$opts(...)$fit()                                   R/10_admm_bp.R
     admm_grplasso(x, y, group)$penalty(..., group_weights)$opts(...)$fit()      (not in the reference: admm_hip_grplasso)
+    admm_mtlasso(x, Y)$penalty(..., row_weights)$opts(...)$fit()                (not in the reference: admm_hip_mtlasso)
 
 `fit()` forwards to the C ABI of libadmm_hip.so exactly where the R `$fit()` does its
 `.Call("admm_*", ...)` (R/30_admm_lasso.R:136-160 etc.).  All numerics run in the HIP library;
@@ -557,7 +558,10 @@ class LassoPlan:
         nl = ctypes.c_int()
         path = (ctypes.c_void_p(lam_in.ctypes.data if lam_in.size else 0), int(lam_in.size),
                 model.nlambda, model.lambda_min_ratio, int(model.standardize), int(model.intercept))
-        if isinstance(model, ADMM_GrpLasso):
+        if isinstance(model, ADMM_MTLasso):
+            check(lib.admm_hip_mtlasso_plan_create(xp, yp, model.n, model.p, model.m, xmem, model._weight_arg(), *path,
+                                                   ctypes.byref(o), ctypes.byref(h), ctypes.byref(nl)))
+        elif isinstance(model, ADMM_GrpLasso):
             check(lib.admm_hip_grplasso_plan_create(xp, yp, model.n, model.p, xmem, *model._group_args(), *path,
                                                     ctypes.byref(o), ctypes.byref(h), ctypes.byref(nl)))
         else:
@@ -569,12 +573,15 @@ class LassoPlan:
     def run(self):
         m = self.model
         lam_out = np.zeros(self.nlambda, dtype=np.float64)
-        beta = np.zeros((m.p + 1, self.nlambda), dtype=np.float32, order="F")
+        mt = isinstance(m, ADMM_MTLasso)
+        beta = np.zeros((self.nlambda, m.m, m.p + 1), dtype=np.float32) if mt else np.zeros((m.p + 1, self.nlambda), dtype=np.float32, order="F")
         niter = np.zeros(self.nlambda, dtype=np.int32)
         stats = AdmmStats()
         check(self._lib.admm_hip_lasso_plan_run(self._h, lam_out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
                                                 beta.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
                                                 niter.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), ctypes.byref(stats)))
+        if mt:
+            return ADMM_MTLasso_fit(lam_out, beta, niter, stats.as_dict())
         if isinstance(m, ADMM_GrpLasso):
             beta = m._restore(beta)
         return ADMM_Lasso_fit(lam_out, beta, niter, stats.as_dict())
@@ -778,3 +785,92 @@ class ADMM_GrpLasso(ADMM_Lasso):
 
 def admm_grplasso(x, y, group, intercept=True, standardize=True, **kw):
     return ADMM_GrpLasso(x, y, group, intercept, standardize, **kw)
+
+
+class ADMM_MTLasso_fit:
+    """Fields lambda, beta_dense ((m, p + 1, nlambda): response, intercept + coefficients, lambda), niter (one count per lambda)."""
+
+    def __init__(self, lam, beta_lmp, niter, stats):
+        self.lambda_ = lam
+        self.beta_dense = np.ascontiguousarray(np.transpose(beta_lmp, (1, 2, 0)))      # the library writes [nlambda][m][p + 1]
+        self.niter = niter
+        self.stats = stats
+
+    @property
+    def beta(self):
+        """One dgCMatrix-like CSC ((p + 1) x nlambda) per response."""
+        return [_beta_to_csc(b) for b in self.beta_dense]
+
+    def __repr__(self):
+        m, p1, nl = self.beta_dense.shape
+        return (f"ADMM multi-task Lasso fitting result\n\n$lambda\n{self.lambda_}\n\n$beta\n{m} responses, each <{p1} x {nl}>\n\n$niter\n{self.niter}")
+
+    def show(self):
+        print(repr(self))
+
+
+class ADMM_MTLasso(ADMM_Lasso):
+    """Multi-task lasso on the tall path (admm_hip_mtlasso; n > p only, one device): Y is n x m, one row-wise penalty
+    lambda sum_j w_j ||B_j.||_2 selects a column of x for all responses at once.  All responses share one cached inverse, so an
+    iteration streams it once for several of them (option MT_RHS).  With a DevicePtr for Y pass m."""
+    _name = "ADMM multi-task Lasso model"
+    _missing = "not available for the multi-task lasso (single-device tall solver only)"
+
+    def __init__(self, x, Y, intercept=True, standardize=True, n=None, p=None, m=None):
+        if isinstance(Y, DevicePtr):
+            if m is None:
+                _stop("m (the number of responses) is needed with a device pointer")
+            m = int(m)
+        else:
+            Y = np.asarray(Y, dtype=np.float64)
+            if Y.ndim == 1:
+                Y = Y.reshape(-1, 1)
+            if Y.ndim != 2:
+                _stop("Y should be a matrix with nrow(x) rows")
+            Y = np.asfortranarray(Y)
+            m = Y.shape[1]
+        super().__init__(x, Y, intercept, standardize, n, p)
+        if self.n <= self.p:
+            _stop("nrow(x) must be greater than ncol(x): the multi-task lasso is built for n > p only")
+        if m < 1 or m > _lib.MT_MAX:
+            _stop(f"the number of responses must be within [1, {_lib.MT_MAX}]")
+        self.m = m
+        self.row_weights = None                                      # library default: 1 for every row
+
+    def penalty(self, lambda_=None, nlambda=100, lambda_min_ratio=None, row_weights=None, **kw):
+        super().penalty(lambda_, nlambda, lambda_min_ratio, **kw)
+        if row_weights is not None:
+            w = np.ascontiguousarray(np.asarray(row_weights, dtype=np.float64).ravel())
+            if w.size != self.p:
+                _stop("row_weights should have one entry per column of x")
+            if not np.all(np.isfinite(w)) or np.any(w < 0):
+                _stop("row_weights must be finite and non-negative")
+            if not np.any(w > 0):
+                _stop("at least one row weight must be positive")
+            row_weights = w
+        self.row_weights = row_weights
+        return self
+
+    def parallel(self, *a, **kw):
+        _stop(self._missing)
+
+    def cv(self, *a, **kw):
+        _stop(self._missing)
+
+    def fit_responses(self, *a, **kw):
+        _stop(self._missing)
+
+    def _weight_arg(self):
+        w = self.row_weights
+        return w.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if w is not None else None
+
+    def fit(self):
+        lib, head, tail, lam_out, _, niter, stats, keep = self._common()
+        beta = np.zeros((lam_out.size, self.m, self.p + 1), dtype=np.float32)
+        check(lib.admm_hip_mtlasso(*head[:4], self.m, head[4], self._weight_arg(), *head[5:], tail[0], tail[1],
+                                   beta.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), tail[3], tail[4]))
+        return ADMM_MTLasso_fit(lam_out, beta, niter, stats.as_dict())
+
+
+def admm_mtlasso(x, Y, intercept=True, standardize=True, **kw):
+    return ADMM_MTLasso(x, Y, intercept, standardize, **kw)

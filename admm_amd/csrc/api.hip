@@ -241,6 +241,28 @@ int admm_hip_grplasso_plan_create(const double* x, const double* y, int n, int p
     });
 }
 
+// admm_hip_mtlasso: the Lasso's path arguments plus the number of responses and the row weights
+#define MT_SPEC [&] { PathSpec s = PATH_SPEC(-1.0); s.nresp = m; s.row_weight = row_weight; s.mt_rows = p; if (m == 0) s.nresp = -1; return s; }()
+
+int admm_hip_mtlasso(const double* x, const double* Y, int n, int p, int m, int mem,
+                     const double* row_weight,
+                     const double* lambda_in, int nlambda_in, int nlambda_auto, double lmin_ratio,
+                     int standardize, int intercept, const admm_opts* opts,
+                     double* lambda_out, float* beta_out, int* niter_out, admm_stats* stats) {
+    return guarded([&] { lasso_family(x, Y, n, p, mem, MT_SPEC, 0, Shard(), PATH_OUT); });
+}
+
+int admm_hip_mtlasso_plan_create(const double* x, const double* Y, int n, int p, int m, int mem,
+                                 const double* row_weight,
+                                 const double* lambda_in, int nlambda_in, int nlambda_auto, double lmin_ratio,
+                                 int standardize, int intercept, const admm_opts* opts,
+                                 admm_hip_plan** plan_out, int* nlambda_out) {
+    return guarded([&] {
+        ADMM_REQUIRE(plan_out != nullptr, "plan_out must not be NULL");
+        plan_out_set(create_plan(x, Y, n, p, mem, MT_SPEC, 0), plan_out, nlambda_out);
+    });
+}
+
 int admm_hip_options_default(admm_hip_options* o) {
     return guarded([&] {
         ADMM_REQUIRE(o != nullptr, "options must not be NULL");
@@ -481,6 +503,13 @@ int admm_hip_test_symv(const float* A, int p, const float* v0, const float* v1, 
     return guarded([&] {
         ADMM_REQUIRE(A && v0 && v1 && y0 && y1 && p > 0, "bad arguments");
         test_symv(A, p, v0, v1, y0, y1);
+    });
+}
+
+int admm_hip_test_symv_multi(const float* A, int p, const float* V, int nr, int rhs_per_pass, float* Yout) {
+    return guarded([&] {
+        ADMM_REQUIRE(A && V && Yout && p > 0 && nr >= 1 && nr <= 64, "bad arguments");
+        test_symv_multi(A, p, V, nr, rhs_per_pass, Yout);
     });
 }
 

@@ -17,6 +17,10 @@ struct PathSpec {
     bool grouped = false;
     const int* group = nullptr; const double* group_weight = nullptr; int ngroups = 0;
     int group_cols = 0;                  // p, the length of `group`
+    // multi-task lasso (admm_hip_mtlasso): the number of responses (0: an ordinary call) and the p row weights as the ABI passes them
+    int nresp = 0;
+    const double* row_weight = nullptr;
+    int mt_rows = 0;                     // p, the length of `row_weight`
 
     bool enet() const { return alpha >= 0.0; }
     double alpha_eff() const { return enet() ? alpha : 1.0; }
@@ -48,6 +52,17 @@ struct PathSpec {
         ADMM_REQUIRE(any, "at least one group weight must be positive");
         ADMM_REQUIRE(n > p, "the group lasso is built for n > p only");
     }
+    // ... of a multi-task call, once check_common has passed: 1 <= m <= ADMM_HIP_MT_MAX, usable weights, n > p
+    void check_mt(int n, int p) const {
+        ADMM_REQUIRE(nresp >= 1 && nresp <= ADMM_HIP_MT_MAX, "the number of responses must be within [1, ADMM_HIP_MT_MAX (16)]");
+        bool any = row_weight == nullptr;
+        for (int j = 0; row_weight != nullptr && j < p; ++j) {
+            ADMM_REQUIRE(std::isfinite(row_weight[j]) && row_weight[j] >= 0, "row weights must be finite and non-negative");
+            any = any || row_weight[j] > 0;
+        }
+        ADMM_REQUIRE(any, "at least one row weight must be positive");
+        ADMM_REQUIRE(n > p, "the multi-task lasso is built for n > p only");
+    }
     LassoProblem problem(int nworkers, bool dist) const {
         LassoProblem pb;
         pb.opts = *opts;
@@ -66,6 +81,10 @@ struct PathSpec {
             pb.group_start.push_back(group_cols);
             for (int g = 0; g < ngroups; ++g)
                 pb.group_weight.push_back(group_weight ? group_weight[g] : std::sqrt((double)(pb.group_start[g + 1] - pb.group_start[g])));
+        }
+        if (nresp > 0) {                    // (checked: check_mt)
+            pb.nresp = nresp;
+            for (int j = 0; j < mt_rows; ++j) pb.row_weight.push_back(row_weight ? row_weight[j] : 1.0);
         }
         return pb;
     }

@@ -20,6 +20,7 @@ struct PlanHandle {
     Stream st;
     std::unique_ptr<LassoPlan> plan;
     int p = 0, nlam = 0;
+    int nresp = 1;                             // coefficient columns per lambda (admm_hip_mtlasso: its responses)
     double t_create = 0;
 };
 // nworkers > 0: the row-block consensus solver; otherwise the tall or the wide one by shape (Lasso.cpp:73)

@@ -52,6 +52,13 @@ PlanHandle* create_plan(const double* x, const double* y, int n, int p, int mem,
         spec.check_groups(n, p);
         ADMM_REQUIRE(!opt_on(Opt::REFINE), "the group lasso has no refined x-update: unset REFINE");
     }
+    if (spec.nresp != 0) {                                  // admm_hip_mtlasso: the tall solver on one device, nothing else (y is Y, n x m)
+        ADMM_REQUIRE(shard.kind == Shard::NONE && nworkers <= 0 && !spec.enet() && !spec.grouped,
+                     "the multi-task lasso has no sharded, consensus, elastic-net or grouped form");
+        spec.check_mt(n, p);
+        ADMM_REQUIRE(!opt_on(Opt::REFINE), "the multi-task lasso has no refined x-update: unset REFINE");
+        ADMM_REQUIRE(!comm_info().active, "the multi-task lasso runs on a single device: detach the communicator (admm_hip_comm_finalize)");
+    }
     require_device();
     const double t0 = now_s();
     std::unique_ptr<PlanHandle> h(new PlanHandle());
@@ -60,9 +67,15 @@ PlanHandle* create_plan(const double* x, const double* y, int n, int p, int mem,
     DeviceData<float> d;
     const bool std_x = spec.standardize != 0, icpt = spec.intercept != 0;
     // Host input of a large tall problem: standardisation and X'X run under the PCIe transfer (bit-identical result).
-    const bool pipelined = mem == ADMM_MEM_HOST && shard.kind == Shard::NONE && nworkers <= 0 && n > p && p >= 4096 && !opt_set(Opt::GRAM);
+    const bool pipelined = mem == ADMM_MEM_HOST && shard.kind == Shard::NONE && nworkers <= 0 && n > p && p >= 4096 && !opt_set(Opt::GRAM) && spec.nresp == 0;
     if (pipelined) upload_standardize_gram_f32(d, x, y, n, p, std_x, icpt, h->st.s);
     else upload_standardize<float>(d, x, y, n, p, mem, std_x, icpt, h->st.s, shard.n_total, shard.ldx);   // COLS: column moments are local, y is replicated
+    if (spec.nresp > 0) {                                   // X went up with the first response; now all of them, standardised together
+        const Resident yr(y, (size_t)n * spec.nresp, mem);
+        if (mem == ADMM_MEM_HOST) comm_stream_sync(h->st.s);
+        standardize_responses_f32(d, yr.p, spec.nresp, h->st.s);
+        h->nresp = spec.nresp;
+    }
     if (cols) h->plan = make_wide_plan(std::move(d), pb, h->st.s);
     else if (nworkers > 0) h->plan = make_par_plan(std::move(d), pb, h->st.s);
     else if ((rows ? shard.n_total : (long long)n) > p) h->plan = make_tall_plan(std::move(d), pb, h->st.s);      // Lasso.cpp:73
@@ -82,7 +95,7 @@ void run_plan(PlanHandle* h, const PathOut& out, double t_extra) {
     h->plan->run(res);
     const int nl = (int)res.lambda.size();
     for (int i = 0; i < nl; ++i) { out.lambda_out[i] = res.lambda[i]; out.niter_out[i] = res.niter[i]; }
-    if (!res.beta_written) std::memcpy(out.beta_out, res.beta.data(), sizeof(float) * (size_t)(h->p + 1) * nl);
+    if (!res.beta_written) std::memcpy(out.beta_out, res.beta.data(), sizeof(float) * (size_t)(h->p + 1) * h->nresp * nl);
     res.stats.t_total = now_s() - t0 + t_extra;
     if (out.stats) *out.stats = res.stats;
 }

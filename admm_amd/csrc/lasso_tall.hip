@@ -486,6 +486,141 @@ tall_group_tail_kernel(TallParams q, int par, GroupTailParams gp) {
     }
 }
 
+// ---- multi-task lasso (admm_hip_mtlasso): m responses on ONE cached inverse, a row-wise block soft-threshold
+//     Z_j. = V_j. max(0, 1 - pen_j / ||V_j.||_2),  V = X + adj_Y / rho,  pen_j = lambda w_j / rho
+// The iterates are m planes (x, z, y, adj_z, adj_y: [m][ldv]; the right-hand sides u_k, w_k planes 2k, 2k + 1 of uw), the x-update is
+// ceil(2m / NR) passes of symvn_lower_kernel (symv_kernels.h), each writing one plane of partials per right-hand side.  This tail has
+// tall_tail_kernel<TAIL_SYMV>'s geometry -- 32 coordinates per workgroup, 8 lanes per coordinate summing partials -- and loops over the
+// responses of its coordinate, kMtChunk at a time with the loads of a chunk issued together.  A row's m values belong to one owner lane:
+// the row norm is the sum of (double) v_k^2 in the order k = 0 .. m - 1 in registers -- no LDS tiles, no tile list, no atomics.  m = 1
+// takes the Lasso's scalar soft-threshold, and every sum is then tall_tail_kernel's: admm_hip_lasso bit for bit.
+struct MtTailParams {
+    int m;
+    long long ldv, ldxy;                  // plane strides of the iterates and of X'Y
+    float* uw;                            // [2m][ldv]
+    const float* dot; const float* axp;   // partial planes [2m] of symvn_lower_kernel
+    long long dot_stride, axp_stride;
+    const double* row_w;                  // [p] row weights
+};
+constexpr int kMtMax = ADMM_HIP_MT_MAX;
+constexpr int kMtChunk = 4;
+static_assert(kMtMax % kMtChunk == 0, "whole chunks");
+
+__global__ void __launch_bounds__(kTailThreads)
+tall_mt_tail_kernel(TallParams q, int par, MtTailParams mp) {
+#pragma clang fp contract(off)
+    __shared__ double scratch[6 * (kTailThreads / 64)];
+    const TallCtl c = q.ctl[par ^ 1];
+    const int sub = threadIdx.x & (kTailLanes - 1);
+    const int i = blockIdx.x * kTailElems + threadIdx.x / kTailLanes;
+    const bool valid = i < q.p;
+    const bool owner = valid && sub == 0;
+    const int m = mp.m;
+    const float* zc_ = par ? q.z1 : q.z0; const float* yc_ = par ? q.y1 : q.y0;
+    float* zo_ = par ? q.z0 : q.z1; float* yo_ = par ? q.y0 : q.y1;
+    const double wj = owner ? mp.row_w[i] : 0.0;
+    const float rho_f = (float)c.rho;
+    // the row between the two halves of the update: x, adj_z, adj_y, v and what the second half still needs of the loads (registers: every index below is a constant once unrolled)
+    float sx[kMtMax], sadjz[kMtMax], sadjy[kMtMax], sv[kMtMax], szc[kMtMax], syc[kMtMax], sxy[kMtMax];
+    double nrm2 = 0.0;
+
+    // ---- first half: x-update results, extrapolation, v = x + adj_y / rho, the row norm
+#pragma unroll
+    for (int ch = 0; ch < kMtMax / kMtChunk; ++ch) {
+        const int k0 = ch * kMtChunk;
+        if (k0 < m) {
+            const int nk = min(kMtChunk, m - k0);
+            TallElem e[kMtChunk];
+#pragma unroll
+            for (int kk = 0; kk < kMtChunk; ++kk) {
+                const int kc = min(k0 + kk, m - 1);
+                const size_t o = (size_t)kc * mp.ldv + i;
+                e[kk] = TallElem{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+                if (owner) {
+                    e[kk].zc = zc_[o]; e[kk].yc = yc_[o]; e[kk].zo = zo_[o]; e[kk].yo = yo_[o];
+                    e[kk].adjz = q.adj_z[o]; e[kk].adjy = q.adj_y[o]; e[kk].x = q.x[o]; e[kk].xy = q.XY[(size_t)kc * mp.ldxy + i];
+                }
+            }
+            float a[kMtChunk], b[kMtChunk];
+            symv_sum_partials_n<kTailLanes, kMtChunk>(mp.dot + (size_t)(2 * k0) * mp.dot_stride, mp.dot_stride, mp.axp + (size_t)(2 * k0) * mp.axp_stride, mp.axp_stride,
+                                                      nk, q.ldo, q.nrb, q.sched, q.p32, i, sub, valid, a, b);
+            if (c.done && c.fin_idx < 0) return;
+#pragma unroll
+            for (int kk = 0; kk < kMtChunk; ++kk) {
+                const int k = k0 + kk;
+                if (kk < nk && owner) {
+                    const TallElem el = e[kk];
+                    if (c.fin_idx >= 0) q.beta[((size_t)c.fin_idx * m + k) * q.p + i] = el.zc;     // snapshot beta[fin_idx][k][j]
+                    if (!c.done) {
+                        float adjz, adjy, x;
+                        if (c.mode) {
+                            if (c.restart) { adjz = el.zo; adjy = el.yo; x = b[kk]; }
+                            else {
+                                const float t = (float)c.tau, t1 = (float)(1.0 + c.tau);
+                                adjz = tall_extrapolate(t1, t, el.zc, el.zo);
+                                adjy = tall_extrapolate(t1, t, el.yc, el.yo);
+                                x = a[kk];
+                            }
+                        } else { adjz = el.adjz; adjy = el.adjy; x = el.x; }
+                        const float vec = x + adjy / rho_f;
+                        sx[k] = x; sadjz[k] = adjz; sadjy[k] = adjy; sv[k] = vec; szc[k] = el.zc; syc[k] = el.yc; sxy[k] = el.xy;
+                        const double v = (double)vec;
+                        nrm2 += v * v;
+                    }
+                }
+            }
+        }
+    }
+    if (c.done) return;
+
+    const double pen = c.lam * wj / c.rho;
+    double shrink = 0.0;                                                // max(0, 1 - pen / ||v_j.||)
+    if (m > 1) { const double nrm = sqrt(nrm2); shrink = nrm > pen ? 1.0 - pen / nrm : 0.0; }
+
+    // ---- second half: next_z, residual, dual update, norms, the right-hand sides of the next x-update (as tall_update_elem)
+    double acc[6] = {0, 0, 0, 0, 0, 0};
+    const float tn = (float)c.tau_next, tn1 = (float)(1.0 + c.tau_next);
+    const size_t pm = (size_t)q.p * m;
+#pragma unroll
+    for (int k = 0; k < kMtMax; ++k) {
+        if (k < m && owner) {
+            const float x = sx[k], adjz = sadjz[k], adjy = sadjy[k], vec = sv[k], zc = szc[k], yc = syc[k], xy = sxy[k];
+            const double v = (double)vec;
+            float zn;
+            if (m == 1) zn = v > pen ? (float)(v - pen) : (v < -pen ? (float)(v + pen) : 0.f);      // the Lasso's soft_threshold, double compare
+            else zn = (float)(v * shrink);
+            const float r = x - zn;
+            const float yn = adjy + rho_f * r;
+            const float dz = zn - zc, daz = zn - adjz;
+            acc[0] += (double)r * r; acc[1] += (double)dz * dz; acc[2] += (double)daz * daz;
+            acc[3] += (double)x * x; acc[4] += (double)zn * zn; acc[5] += (double)yn * yn;
+            const size_t o = (size_t)k * mp.ldv + i;
+            q.x[o] = x; zo_[o] = zn; yo_[o] = yn; q.adj_z[o] = adjz; q.adj_y[o] = adjy;
+            if (q.state != nullptr && c.total < q.state_cap) {          // record [5][m][p]
+                float* st = q.state + (size_t)c.total * 5 * pm + (size_t)k * q.p + i;
+                st[0] = x; st[pm] = zn; st[2 * pm] = yn; st[3 * pm] = adjz; st[4 * pm] = adjy;
+            }
+            const float adjz_a = tall_extrapolate(tn1, tn, zn, zc), adjy_a = tall_extrapolate(tn1, tn, yn, yc);
+            mp.uw[(size_t)(2 * k) * mp.ldv + i] = (float)((double)(xy - adjy_a) + c.rho * (double)adjz_a);
+            mp.uw[(size_t)(2 * k + 1) * mp.ldv + i] = (float)((double)(xy - yc) + c.rho * (double)zc);
+        }
+    }
+    // block sum of the six norms: tall_tail_kernel's, value for value
+    static_assert(kTailLanes == 8, "owner lanes are the multiples of 8");
+    {
+        const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+        const double v8[8] = {acc[0], acc[1], acc[2], acc[3], acc[4], acc[5], 0.0, 0.0};
+        const double tot = halving_sum8_top(v8, lane);
+        if ((lane & 7) == 0 && lane < 48) scratch[(lane >> 3) * (kTailThreads / 64) + wid] = tot;
+        __syncthreads();
+        if (threadIdx.x < 6) {
+            double sum = 0;
+            for (int ww = 0; ww < kTailThreads / 64; ++ww) sum += scratch[threadIdx.x * (kTailThreads / 64) + ww];
+            q.P[((size_t)(par ^ 1) * q.nwg + blockIdx.x) * 8 + threadIdx.x] = sum;
+        }
+    }
+}
+
 // Round 4 also built the whole path as ONE persistent launch with a third of the inverse's triangle resident in registers (two
 // grid barriers per iteration, decision off the critical path; bit-identical): 66.7 us per iteration against 39.25 at C2 -- the
 // barriers + an in-launch tail cost 16.6 us where the kernel boundaries cost 5.6, residency saves at most 10.8 us of the stream, and
@@ -585,6 +720,12 @@ struct TallPlan final : LassoPlan {
     DevBuf<int2> gtiles;
     DevBuf<GroupCoord> gcoord;
     GroupTailParams gq{};
+    // multi-task lasso (LassoProblem.nresp): every vector is nresp planes, the x-update passes of symvn_lower_kernel, the tail tall_mt_tail_kernel
+    int mt = 0;                                         // responses (0: not a multi-task problem)
+    int mt_rhs = 2;                                     // right-hand sides per pass (MT_RHS)
+    DevBuf<float> uw, mdot, maxp;                       // [2 mt][ldv] right-hand sides; [2 mt] planes of partials
+    DevBuf<double> roww;
+    MtTailParams mq{};
     PinnedFlag hflag;
 #ifdef ADMM_HIP_PROBE
     DevBuf<long long> probe;
@@ -617,15 +758,22 @@ struct TallPlan final : LassoPlan {
         if (d.xy.get()) {                                  // Gram-form data (a cross-validation fold formed as a down-date, cv.hip)
             ADMM_REQUIRE(!shard && d.gram.get() && d.ldgram == ldp, "Gram-form data needs X'X next to X'y");
             XY = std::move(d.xy);
+        } else if (pb.nresp > 0) {                         // multi-task: X'Y, one plane per response
+            mt = pb.nresp;
+            ADMM_REQUIRE(!shard && !pb.enet && !opt_on(Opt::REFINE) && pb.group_start.empty() && mt <= kMtMax && d.nresp == mt && d.Ymt.get() &&
+                         (int)pb.row_weight.size() == p, "internal: the multi-task lasso is the plain single-device tall solver");
+            XY.alloc((size_t)mt * ldp); XY.zero(st);
+            for (int k = 0; k < mt; ++k) gemv_t_simple<float>(d.X.get(), d.ldx, n, p, d.Ymt.get() + (size_t)k * d.ldx, XY.get() + (size_t)k * ldp, st);
         } else {
             XY.alloc(ldp); XY.zero(st);
             gemv_t_simple<float>(d.X.get(), d.ldx, n, p, d.Y.get(), XY.get(), st);
             if (shard) allreduce_sum_f32(XY.get(), (size_t)p, st);
         }
+        ADMM_REQUIRE(pb.nresp == mt, "internal: the multi-task lasso takes its data as columns, not in Gram form");
         grouped = !pb.group_start.empty();
         ADMM_REQUIRE(!grouped || (!shard && !pb.enet && !opt_on(Opt::REFINE) && (int)pb.group_start.size() == (int)pb.group_weight.size() + 1 &&
                                   pb.group_start.back() == p), "internal: the group lasso is the plain single-device tall solver");
-        float lambda0 = grouped ? group_lambda0() : device_absmax<float>(XY.get(), p, st);
+        float lambda0 = grouped ? group_lambda0() : (mt ? mt_lambda0() : device_absmax<float>(XY.get(), p, st));
         if (pb.enet) lambda0 = (float)(lambda0 / ((double)(float)pb.alpha + 0.0001));
 
         // lambda grid (Lasso.cpp:78-89) and internal lambdas (Lasso.cpp:99), stored as float like `Scalar lambda`
@@ -643,7 +791,8 @@ struct TallPlan final : LassoPlan {
             const bool inv64_wanted = p < 4096 || opt_is(Opt::INVERSE, "f64");
             const double mat = (double)ldp * (double)ldp * 4.0;
             const double need = (have_gram ? 0.0 : mat) + (inv64_wanted ? 2.0 * mat : 0.5 * mat) + (opt_on(Opt::REFINE) ? mat : 0.0) +
-                                (shard && ci.nranks > 1 ? mat + mat / ci.nranks : 0.0);      // packed send / receive buffers of the Gram's reduce-scatter
+                                (shard && ci.nranks > 1 ? mat + mat / ci.nranks : 0.0) +     // packed send / receive buffers of the Gram's reduce-scatter
+                                (mt ? mt_partial_floats() * 4.0 : 0.0);                      // multi-task: a plane of partials per right-hand side
             if (need > 0.97 * (double)free_b) {
                 char msg[320];
                 std::snprintf(msg, sizeof msg, "tall solver: the cached %d x %d inverse and its workspace need %.1f GB, the device has %.1f GB free; "
@@ -782,6 +931,7 @@ struct TallPlan final : LassoPlan {
         if (opt_set(Opt::XUPDATE)) use_sym = opt_is(Opt::XUPDATE, "sym");
         if (refine) use_sym = true;                      // the refinement is built on the symmetric kernel's partial layout
         if (shard) use_sym = true;                       // the sharded x-update is the tile list of the symmetric kernel dealt out to the ranks
+        if (mt) use_sym = true;                          // the multi-vector kernel is the symmetric one at every p: there is no gemv form
         pl = plan_gemv_t<float>(p, p, 2, 4);
         nwg = (p + kTailElems - 1) / kTailElems;
         if (grouped) nwg = pack_group_tiles();
@@ -801,16 +951,17 @@ struct TallPlan final : LassoPlan {
         // (A single-launch iteration -- tail, decision and tiles in one launch -- and a hipGraph replay of the batch were built, measured
         // bit-identical and SLOWER on C2 in rounds 4 / 5 (44.5 and 46.9 us per iteration against 42.1 / 46.6): removed in round 6,
         // profiles/HISTORY.md.)
-        x.alloc(ldv); z0.alloc(ldv); z1.alloc(ldv); y0.alloc(ldv); y1.alloc(ldv);
-        adj_z.alloc(ldv); adj_y.alloc(ldv); u.alloc(ldv); w.alloc(ldv);
-        beta.alloc((size_t)nlam * p); niter.alloc(nlam);
+        const size_t npl = (size_t)std::max(mt, 1);     // planes per vector
+        x.alloc(npl * ldv); z0.alloc(npl * ldv); z1.alloc(npl * ldv); y0.alloc(npl * ldv); y1.alloc(npl * ldv);
+        adj_z.alloc(npl * ldv); adj_y.alloc(npl * ldv); u.alloc(ldv); w.alloc(ldv);
+        beta.alloc((size_t)nlam * p * npl); niter.alloc(nlam);
         P.alloc((size_t)2 * nwg * 8); dlam.alloc(nlam); ctl.alloc(2);
         u.zero(st); w.zero(st);
         ADMM_HIP_CHECK(hipMemcpyAsync(dlam.get(), lam_int.data(), nlam * sizeof(double), hipMemcpyHostToDevice, st));
 
         q.p = p; q.nwg = nwg; q.nseg = pl.nseg; q.maxit = pb.opts.maxit; q.nlam = nlam; q.enet = pb.enet ? 1 : 0;
         q.part_stride = ldp;
-        q.eps_abs = pb.opts.eps_abs; q.eps_rel = pb.opts.eps_rel; q.alpha = (double)(float)pb.alpha; q.sqrt_p = std::sqrt((double)p);
+        q.eps_abs = pb.opts.eps_abs; q.eps_rel = pb.opts.eps_rel; q.alpha = (double)(float)pb.alpha; q.sqrt_p = std::sqrt((double)p * (double)npl);
         q.lambdas = dlam.get(); q.XY = XY.get(); q.a_part = a_part.get(); q.b_part = b_part.get();
         if (shard) { q.a_part = ab.get(); q.b_part = ab.get() + ldp; q.nseg = 1; }      // the tail reads the all-reduced pair (generic exchange)
         q.dot0 = sy.dot0.get(); q.dot1 = sy.dot1.get(); q.axp0 = sy.axp0.get(); q.axp1 = sy.axp1.get();
@@ -826,8 +977,48 @@ struct TallPlan final : LassoPlan {
         sy.probe = probe.get();
 #endif
 
-        ADMM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&hbeta), (size_t)nlam * p * sizeof(float), hipHostMallocDefault));
+        if (mt) {
+            // right-hand sides per pass: MT_RHS, or the automatic value = the fastest measured at p = 10^4 for that m, every m from 1 to
+            // 16 measured (scripts/bench_mtlasso.py, profiles/mtlasso_rhs.md).  A pass costs the same full or partly filled: about 31 us
+            // for 2 or 4 vectors (the stream is the bound), 58 - 60 for 8 and 83 - 87 for 12 (the FMAs are), so the winner is the NR whose
+            // ceil(2m / NR) passes waste the fewest slots -- no monotone rule in m.
+            static const int kAutoRhs[kMtMax] = {2, 4, 8, 8, 12, 12, 8, 8, 4, 4, 12, 12, 4, 4, 8, 8};
+            mt_rhs = kAutoRhs[mt - 1];
+            if (const OptValue* v = opt(Opt::MT_RHS)) { if (v->i > 0) mt_rhs = kSyNR[v->i - 1]; }
+            uw.alloc((size_t)2 * mt * ldv); uw.zero(st);
+            const size_t ds = (size_t)sy.nrb * sy.ldo, as = (size_t)sy.nax_rows * sy.ldo;
+            mdot.alloc((size_t)2 * mt * ds); maxp.alloc((size_t)2 * mt * as);
+            mdot.zero(st); maxp.zero(st);
+            x.zero(st); z0.zero(st); z1.zero(st); y0.zero(st); y1.zero(st); adj_z.zero(st); adj_y.zero(st);      // (the padding of the planes)
+            roww.alloc(p);
+            ADMM_HIP_CHECK(hipMemcpyAsync(roww.get(), pb.row_weight.data(), (size_t)p * sizeof(double), hipMemcpyHostToDevice, st));
+            mq.m = mt; mq.ldv = ldv; mq.ldxy = ldp; mq.uw = uw.get();
+            mq.dot = mdot.get(); mq.axp = maxp.get(); mq.dot_stride = (long long)ds; mq.axp_stride = (long long)as;
+            mq.row_w = roww.get();
+        }
+        ADMM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&hbeta), (size_t)nlam * p * npl * sizeof(float), hipHostMallocDefault));
         comm_stream_sync(st);
+    }
+
+    // lambda_0 of the multi-task lasso: the largest ||(X'Y)_j.||_2 / w_j over the penalised rows, the norm in double from the float X'Y,
+    // rounded to float (m = 1, weight 1: exactly device_absmax)
+    float mt_lambda0() {
+        std::vector<float> h((size_t)mt * ldp);
+        read_back(h.data(), XY.get(), h.size() * sizeof(float), st);
+        double best = 0.0;
+        for (int j = 0; j < p; ++j) {
+            if (!(pb.row_weight[j] > 0)) continue;
+            double s2 = 0.0;
+            for (int k = 0; k < mt; ++k) { const double v = (double)h[(size_t)k * ldp + j]; s2 += v * v; }
+            best = std::max(best, std::sqrt(s2) / pb.row_weight[j]);
+        }
+        return (float)best;
+    }
+    // floats of the multi-task partial planes, 2 m (nrb + nax_rows) ldo, bounded from the shape alone (the schedule is chosen later; its
+    // narrowest segments are 32 columns, so no strip has more than p32 / 32 of them)
+    double mt_partial_floats() const {
+        const double nrb = (double)((p + kSyRB - 1) / kSyRB), ldo = nrb * kSyRB;
+        return 2.0 * mt * (nrb + (double)((p + 31) / 32)) * ldo;
     }
 
     // lambda_0 of the group lasso: the largest ||(X'y)_g||_2 / w_g over the penalised groups, the norm in double from the float X'y,
@@ -869,7 +1060,7 @@ struct TallPlan final : LassoPlan {
         return (int)tiles.size();
     }
 
-    Records records() override { return {st, 5ll * p, &q.trace, &q.trace_cap, &q.state, &q.state_cap}; }
+    Records records() override { return {st, 5ll * p * std::max(mt, 1), &q.trace, &q.trace_cap, &q.state, &q.state_cap}; }      // multi-task: [5][m][p]
 
     void read_system(float* out, long long ld) override {
         if (!refine) throw Error(ADMM_ERR_INVALID_ARG, "the system matrix is only kept with ADMM_HIP_REFINE=1");
@@ -887,8 +1078,19 @@ struct TallPlan final : LassoPlan {
         res.lambda = lam_user;
         beta.zero(st); niter.zero(st);
         const int init_n = std::max(p, 2 * nwg * 8);
-        hipLaunchKernelGGL(tall_init_kernel, dim3((init_n + 255) / 256), dim3(256), 0, st, q, rho, lam_int[0]);
-        if (q.state != nullptr)      // record 0 of the iterate dump (the cold start has no iterates): X'y as this solver holds it, in the x slot
+        for (int k = 0; k < std::max(mt, 1); ++k) {      // multi-task: plane by plane (every launch writes the same control block and norm partials)
+            TallParams qk = q;
+            if (mt) {
+                const size_t o = (size_t)k * ldv;
+                qk.x += o; qk.z0 += o; qk.z1 += o; qk.y0 += o; qk.y1 += o; qk.adj_z += o; qk.adj_y += o;
+                qk.XY += (size_t)k * ldp; qk.u = uw.get() + (size_t)(2 * k) * ldv; qk.w = uw.get() + (size_t)(2 * k + 1) * ldv;
+            }
+            hipLaunchKernelGGL(tall_init_kernel, dim3((init_n + 255) / 256), dim3(256), 0, st, qk, rho, lam_int[0]);
+        }
+        if (q.state != nullptr && mt)      // record 0 of the iterate dump: X'Y, [m][p], in the x slot
+            ADMM_HIP_CHECK(hipMemcpy2DAsync(q.state, (size_t)p * sizeof(float), XY.get(), (size_t)ldp * sizeof(float), (size_t)p * sizeof(float),
+                                            (size_t)mt, hipMemcpyDeviceToDevice, st));
+        else if (q.state != nullptr)      // record 0 of the iterate dump (the cold start has no iterates): X'y as this solver holds it, in the x slot
             ADMM_HIP_CHECK(hipMemcpyAsync(q.state, XY.get(), (size_t)p * sizeof(float), hipMemcpyDeviceToDevice, st));
         *hflag.p = 0;
 #ifdef ADMM_HIP_PROBE
@@ -918,7 +1120,23 @@ struct TallPlan final : LassoPlan {
             // sampled launches carry start/stop events that time exactly the x-update kernel on this stream
             // the decision of this iteration rides along as one extra workgroup of the x-update launch
             const TallDecideExtra dec{q, par};
-            if (grouped) {                             // two launches, as the Lasso: the x-update with the decision, the group tail
+            if (mt) {
+                // ceil(2m / NR) passes over the triangle, NR right-hand sides each (the decision rides on the first), then the row tail
+                const int nvec = 2 * mt;
+                for (int r0 = 0; r0 < nvec; r0 += mt_rhs) {
+                    SymvNArgs a;
+                    a.A = M.get(); a.lda = ldp; a.p = p;
+                    a.v = uw.get() + (size_t)r0 * ldv; a.vstride = ldv;
+                    a.dot = mdot.get() + (size_t)r0 * mq.dot_stride; a.dot_stride = mq.dot_stride;
+                    a.axp = maxp.get() + (size_t)r0 * mq.axp_stride; a.axp_stride = mq.axp_stride;
+                    a.nvec = std::min(mt_rhs, nvec - r0); a.ldo = sy.ldo; a.tiles = sy.tiles.get(); a.skip = &ctl.get()[par].done;
+                    // a sampled iteration is timed from the start of its first pass to the end of its last
+                    hipEvent_t es = r0 == 0 ? e0 : nullptr, ee = r0 + mt_rhs >= nvec ? e1 : nullptr;
+                    if (r0 == 0) symvn_launch(sy, mt_rhs, a, st, dec, es, ee);
+                    else symvn_launch(sy, mt_rhs, a, st, SymvNoExtra(), es, ee);
+                }
+                hipLaunchKernelGGL(tall_mt_tail_kernel, dim3(nwg), dim3(kTailThreads), 0, st, q, par, mq);
+            } else if (grouped) {                      // two launches, as the Lasso: the x-update with the decision, the group tail
                 if (use_sym) {
                     sy.launch(M.get(), ldp, u.get(), w.get(), &ctl.get()[par].done, st, dec, e0, e1);
                     hipLaunchKernelGGL(tall_group_tail_kernel<TAIL_SYMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, gq);
@@ -982,9 +1200,19 @@ struct TallPlan final : LassoPlan {
         }
 
         // ---- results: niter, beta on the original scale (DataStd::recover, Lasso.cpp:108-111)
-        ADMM_HIP_CHECK(hipMemcpyAsync(hbeta, beta.get(), (size_t)nlam * p * sizeof(float), hipMemcpyDeviceToHost, st));
+        ADMM_HIP_CHECK(hipMemcpyAsync(hbeta, beta.get(), (size_t)nlam * p * std::max(mt, 1) * sizeof(float), hipMemcpyDeviceToHost, st));
         comm_stream_sync(st);
-        S.total_iter = read_out_path<float>(d, hbeta, nlam, niter.get(), (size_t)p + 1, 0, res.niter, res.beta);
+        if (mt) {      // per response, with that response's mean: coefficients [nlam][m][p + 1]; niter is one count per lambda
+            const size_t col = (size_t)p + 1;
+            std::vector<float> bk;
+            res.beta.assign(col * mt * nlam, 0.f);
+            for (int k = 0; k < mt; ++k) {
+                S.total_iter = read_out_path<float>(d, hbeta + (size_t)k * p, nlam, niter.get(), col, 0, res.niter, bk, INT_MAX, (size_t)mt * p, &d.meanYs[k]);
+                for (int l = 0; l < nlam; ++l) std::memcpy(res.beta.data() + ((size_t)l * mt + k) * col, bk.data() + (size_t)l * col, col * sizeof(float));
+            }
+        } else {
+            S.total_iter = read_out_path<float>(d, hbeta, nlam, niter.get(), (size_t)p + 1, 0, res.niter, res.beta);
+        }
         decisions = hctl.c[0].done ? hctl.total() : 0;      // (the sticky no-op decisions after `done` do not write)
         res.stats = S;
     }

@@ -64,6 +64,7 @@ constexpr double kPositive = std::numeric_limits<double>::min();  // Real(kPosit
     X(LAD_HAT, Flag(), "LAD: 0 = the general projection also for n <= 2000")                                                            \
     X(LAD_ONEPASS, Flag(), "LAD: 0 = the reference's two products per iteration")                                                      \
     X(QUANT_SLOTS, Int(0, 8), "admm_hip_quantreg: quantiles per pass over X on the one-pass branch: 0 = automatic, 1 = serial, else at most that many") \
+    X(MT_RHS, Choice("0|2|4|8|12"), "admm_hip_mtlasso: right-hand sides per pass over the cached inverse (0: automatic)")               \
     X(BP_ONEPASS, Flag(), "basis pursuit: 0 = the reference's two products per iteration")                                             \
     X(SBP_GRAM, Flag(), "admm_hip_parbp: 0 = the direct launches on every active-set iteration")                                       \
     X(SBP_GRAM_CAP, Int(1, 1024), "admm_hip_parbp: most columns of the Gram-space matrix (rounded to multiples of 8)")                 \

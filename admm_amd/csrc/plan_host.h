@@ -22,17 +22,21 @@ int make_path_grid(const LassoProblem& pb, double lambda0, long long n, double s
 
 // The common tail of a path: the iteration counts from the device, and the coefficient matrix on the original scale (DataStd::recover,
 // Lasso.cpp:108-111) from the host snapshots `snap` (nlam x d.p) -- column l of `beta` is `stride` long, row 0 the intercept, this
-// solver's columns from row 1 + col_offset.  Returns the sum of the counts, each clipped to `niter_clip`.
+// solver's columns from row 1 + col_offset.  Returns the sum of the counts, each clipped to `niter_clip`.  snap_stride: distance between the
+// snapshots of two lambdas (0: d.p; the multi-task plan keeps m of them per lambda and reads them out response by response, each with
+// its own mean `mean_y`; NULL: d.meanY).
 template <typename T>
 long long read_out_path(const DeviceData<T>& d, const T* snap, int nlam, const int* dev_niter, size_t stride, long long col_offset,
-                        std::vector<int>& niter, std::vector<T>& beta, int niter_clip = INT_MAX) {
+                        std::vector<int>& niter, std::vector<T>& beta, int niter_clip = INT_MAX, size_t snap_stride = 0,
+                        const T* mean_y = nullptr) {
+    if (snap_stride == 0) snap_stride = (size_t)d.p;
     niter.assign(nlam, 0);
     ADMM_HIP_CHECK(hipMemcpy(niter.data(), dev_niter, (size_t)nlam * sizeof(int), hipMemcpyDeviceToHost));
     beta.assign(stride * nlam, T(0));
     long long tot = 0;
     for (int l = 0; l < nlam; ++l) {
         T b0 = 0;
-        recover_coef<T>(d, snap + (size_t)l * d.p, &b0, beta.data() + (size_t)l * stride + 1 + col_offset);
+        recover_coef<T>(d, mean_y ? *mean_y : d.meanY, snap + (size_t)l * snap_stride, &b0, beta.data() + (size_t)l * stride + 1 + col_offset);
         beta[(size_t)l * stride] = b0;
         tot += std::min(niter[l], niter_clip);
     }

@@ -27,6 +27,11 @@ struct DeviceData {
     // Gram-form data (cross-validation folds formed as down-dates, cv.hip): X'y of the standardised data, round_up(p, 128)
     // entries, zero padded.  When set the tall solver takes X'y and the Gram from here and X / Y may be empty.
     DevBuf<T> xy;
+    // Multi-task lasso (standardize_responses_f32): nresp > 0 responses, n x nresp column-major with leading dimension ldx (padding rows
+    // zero), each centred by its own mean (meanYs), all divided by ONE scale (scaleY above).
+    int nresp = 0;
+    DevBuf<T> Ymt;
+    std::vector<T> meanYs;
 };
 
 // Convert the caller's double column-major x (n x p, ld n) and y to T on the device and apply
@@ -82,9 +87,18 @@ void cv_downdate_fold(DeviceData<float>& d, const CvBase& b, const double* yd, c
 void standardize_response_f32(const double* y_dev, int n, int flag, long long n_total, float* Yout, long long ld,
                               float* meanY, float* scaleY, hipStream_t st);
 
+// The responses of a multi-task problem (admm_hip_mtlasso): Y_dev (device doubles, n x m column-major) narrowed to float into d.Ymt and
+// standardised by d.flag with the kernels of upload_standardize -- every response centred by its own mean, all of them divided by the
+// common scale sqrt(sum_k ||y_k - mean_k||^2 / (n m)), the sums in double, DataStd's rounding (m = 1: DataStd's scaleY to the bit).
+// d must hold the standardised X of the same call (upload_standardize).
+void standardize_responses_f32(DeviceData<float>& d, const double* Y_dev, int m, hipStream_t st);
+
 // DataStd::recover (DataStd.h:157-207) on a host coefficient vector (length p) in precision T.
 template <typename T>
 void recover_coef(const DeviceData<T>& d, const T* coef, T* beta0, T* out);
+// the same with the response's mean given by the caller (a multi-task plan keeps one per response); d.meanY is not read
+template <typename T>
+void recover_coef(const DeviceData<T>& d, T meanY, const T* coef, T* beta0, T* out);
 // the same for a column given as its non-zeros (ascending indices): writes only those entries of `out` (the caller cleared it).  Same
 // arithmetic in the same order as recover_coef -- the entries skipped there add exact zeros to the intercept's sum.
 template <typename T>

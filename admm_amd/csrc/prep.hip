@@ -544,6 +544,58 @@ void standardize_response_f32(const double* y_dev, int n, int flag, long long n_
     ADMM_HIP_CHECK(hipGetLastError());
 }
 
+__global__ void sum_stats_kernel(const double* in, int count, double* out) {      // fixed order: the same bits from run to run
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        double s = 0.0;
+        for (int k = 0; k < count; ++k) s += in[k];
+        *out = s;
+    }
+}
+
+void standardize_responses_f32(DeviceData<float>& d, const double* Y_dev, int m, hipStream_t st) {
+    typedef float T;
+    const int n = d.n;
+    const long long ld = d.ldx;
+    d.nresp = m;
+    d.Ymt.alloc((size_t)ld * m);
+    d.Ymt.zero(st);
+    const int ny = std::max(1, std::min(64, (n + 255) / 256));
+    hipLaunchKernelGGL((convert_cols_kernel<T>), dim3(m, ny), dim3(256), 0, st, Y_dev, (long long)n, n, d.Ymt.get(), ld);
+    d.meanYs.assign(m, T(0));
+    d.meanY = T(0); d.scaleY = T(1);
+    if (d.flag != 0) {
+        DevBuf<double> stat(m + 1);
+        DevBuf<T> mean(m), scale(1), inv(1);
+        // column by column with p = 0: the only "column" of these launches is that response (standardize_response_f32)
+        for (int k = 0; k < m; ++k) {
+            T* Yk = d.Ymt.get() + (size_t)k * ld;
+            hipLaunchKernelGGL((colstat_kernel<T, 0>), dim3(1), dim3(256), 0, st, Yk, ld, Yk, n, 0, mean.get() + k, stat.get() + k);
+        }
+        hipLaunchKernelGGL((finish_mean_kernel<T>), dim3(1), dim3(256), 0, st, stat.get(), (double)d.n_total, m, mean.get());
+        for (int k = 0; k < m; ++k) {
+            T* Yk = d.Ymt.get() + (size_t)k * ld;
+            hipLaunchKernelGGL((colstat_kernel<T, 1>), dim3(1), dim3(256), 0, st, Yk, ld, Yk, n, 0, mean.get() + k, stat.get() + k);
+        }
+        // one scale for all responses: the centred sums of squares added in double, then DataStd's rounding with n m in the place of n
+        hipLaunchKernelGGL(sum_stats_kernel, dim3(1), dim3(1), 0, st, stat.get(), m, stat.get() + m);
+        hipLaunchKernelGGL((finish_scale_kernel<T>), dim3(1), dim3(256), 0, st, stat.get() + m, (double)d.n_total * (double)m, 1, scale.get(), inv.get());
+        for (int k = 0; k < m; ++k) {
+            T* Yk = d.Ymt.get() + (size_t)k * ld;
+            hipLaunchKernelGGL((apply_std_kernel<T>), dim3(1, ny), dim3(256), 0, st, Yk, ld, Yk, n, 0, d.flag, mean.get() + k, scale.get(), inv.get());
+        }
+        std::vector<T> hm(m);
+        T hs = 1;
+        ADMM_HIP_CHECK(hipMemcpyAsync(hm.data(), mean.get(), (size_t)m * sizeof(T), hipMemcpyDeviceToHost, st));
+        ADMM_HIP_CHECK(hipMemcpyAsync(&hs, scale.get(), sizeof(T), hipMemcpyDeviceToHost, st));
+        comm_stream_sync(st);
+        if (d.flag & 2) d.meanYs = hm;
+        d.scaleY = hs;
+        d.meanY = d.meanYs[0];
+    }
+    ADMM_HIP_CHECK(hipGetLastError());
+    comm_stream_sync(st);
+}
+
 void clone_with_response_f32(DeviceData<float>& d, const DeviceData<float>& base, const float* gram, long long ldgram,
                              const double* y_dev, hipStream_t st) {
     typedef float T;
@@ -679,7 +731,9 @@ void upload_standardize_gram_f32(DeviceData<float>& d, const double* x, const do
 }
 
 template <typename T>
-void recover_coef(const DeviceData<T>& d, const T* coef, T* beta0, T* out) {
+void recover_coef(const DeviceData<T>& d, const T* coef, T* beta0, T* out) { recover_coef<T>(d, d.meanY, coef, beta0, out); }
+template <typename T>
+void recover_coef(const DeviceData<T>& d, T meanY, const T* coef, T* beta0, T* out) {
     const int p = d.p;
     T b0 = T(0);
     switch (d.flag) {
@@ -692,13 +746,13 @@ void recover_coef(const DeviceData<T>& d, const T* coef, T* beta0, T* out) {
         case 2: {
             T acc = T(0);
             for (int j = 0; j < p; ++j) { out[j] = coef[j] * d.scaleY; acc += out[j] * d.meanX[j]; }
-            b0 = d.meanY - acc;
+            b0 = meanY - acc;
             break;
         }
         default: {
             T acc = T(0);
             for (int j = 0; j < p; ++j) { out[j] = (coef[j] / d.scaleX[j]) * d.scaleY; acc += out[j] * d.meanX[j]; }
-            b0 = d.meanY - acc;
+            b0 = meanY - acc;
         }
     }
     *beta0 = b0;
@@ -723,6 +777,8 @@ void recover_coef_sparse(const DeviceData<T>& d, const int* idx, const T* val, l
 template void recover_coef_sparse<float>(const DeviceData<float>&, const int*, const float*, long long, float*, float*);
 template void recover_coef<float>(const DeviceData<float>&, const float*, float*, float*);
 template void recover_coef<double>(const DeviceData<double>&, const double*, double*, double*);
+template void recover_coef<float>(const DeviceData<float>&, float, const float*, float*, float*);
+template void recover_coef<double>(const DeviceData<double>&, double, const double*, double*, double*);
 
 // ------------------------------------------------------------------ small dense helpers
 template <typename T>

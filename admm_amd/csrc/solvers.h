@@ -23,6 +23,10 @@ struct LassoProblem {
     // penalised by group_weight[g] * its Euclidean norm; empty = no groups
     std::vector<int> group_start;
     std::vector<double> group_weight;
+    // multi-task lasso (admm_hip_mtlasso, tall solver only): nresp responses share the design (DeviceData.Ymt), row j of the p x nresp
+    // coefficient matrix is penalised by row_weight[j] * its Euclidean norm; 0 = an ordinary single-response problem
+    int nresp = 0;
+    std::vector<double> row_weight;
 };
 
 struct LassoResult {

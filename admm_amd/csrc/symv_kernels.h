@@ -260,6 +260,146 @@ symv2_lower_kernel(SymvArgs a, Extra extra) {
 #endif
 }
 
+// ---- NR right-hand sides on ONE load of every matrix element (multi-task lasso: lasso_tall.hip, tall_mt_tail_kernel).
+// symv2_lower_kernel streams 2 p^2 bytes for two vectors; with one cached inverse shared by m responses the same bytes can serve
+// all 2 m of them.  Same tile list (SymvPlan, SymvSched), same partial layout, one PLANE of partials per right-hand side.  For every
+// right-hand side the arithmetic is symv2_tile's to the bit -- the same fmaf chains, the same butterfly8, the same cross-wave sum of
+// the axpy part -- so a partial does not depend on which other vectors share the pass: NR is invisible in the results, and
+// NR = 2 reproduces symv2_lower_kernel.
+// Registers: 4 NR (row entries) + NR (column entries) + 4 NR (axpy accumulators) + 32 (the 8-column chunk); waves that meet the
+// diagonal hold a second, diagonal-free copy of the chunk, the others do not (two copies of the chunk body).  2 waves per SIMD
+// (at 4 every NR spills); the cross-wave sums go pair by pair through the one [2][256] float4 buffer, LDS = 8 KB + NR KB.
+struct SymvNArgs {
+    const float* A; long long lda; int p;
+    const float* v; long long vstride;     // right-hand vector r of this pass: v + r * vstride (allocated and zero padded to a multiple of 256)
+    float* dot; long long dot_stride;      // its planes of partials: dot + r * dot_stride is [nrb][ldo], axp + r * axp_stride is [nax_rows][ldo]
+    float* axp; long long axp_stride;
+    int nvec;                              // vectors of this pass, 1 .. NR (the kernel computes NR: slots beyond nvec repeat the last vector and store nothing)
+    long long ldo;
+    const int4* tiles;
+    const int* skip;
+};
+constexpr int kSyNR[] = {2, 4, 8, 12};    // the instantiations built (MT_RHS, options.h); every one compiles without scratch
+constexpr int kSyNRCount = (int)(sizeof(kSyNR) / sizeof(kSyNR[0]));
+
+// the 8-column chunk against the NR vectors.  DIAG: the wave's block meets the diagonal (upper entries dropped, the axpy part without the diagonal)
+template <int NR, bool DIAG>
+__device__ __forceinline__ void symvn_chunk(float4 (&av)[8], const float4 (&vI)[NR], const float (&vj)[NR], float4 (&acc)[NR],
+                                            int row, int colq, int q, int lane, float (*sdot)[kSyCBMax], int sbase) {
+    float4 ax[DIAG ? 8 : 1];
+    if (DIAG) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const int col = colq + k;
+            float4 v = av[k];
+            if (row + 0 < col) v.x = 0.f;
+            if (row + 1 < col) v.y = 0.f;
+            if (row + 2 < col) v.z = 0.f;
+            if (row + 3 < col) v.w = 0.f;
+            av[k] = v;
+            if (row + 0 == col) v.x = 0.f;
+            if (row + 1 == col) v.y = 0.f;
+            if (row + 2 == col) v.z = 0.f;
+            if (row + 3 == col) v.w = 0.f;
+            ax[DIAG ? k : 0] = v;
+        }
+    }
+#pragma unroll
+    for (int r = 0; r < NR; ++r) {
+        float d[8];
+        const float4 xi = vI[r];
+        float4 s = acc[r];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const float4 v = av[k];
+            const float4 x = DIAG ? ax[DIAG ? k : 0] : av[k];
+            d[k] = fmaf(v.x, xi.x, fmaf(v.y, xi.y, fmaf(v.z, xi.z, v.w * xi.w)));
+            const float c = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(vj[r]), (q * 8 + k) & 63));
+            s.x = fmaf(x.x, c, s.x); s.y = fmaf(x.y, c, s.y); s.z = fmaf(x.z, c, s.z); s.w = fmaf(x.w, c, s.w);
+        }
+        acc[r] = s;
+        const float dr = butterfly8(d, lane);
+        if ((lane & 7) == 0) sdot[r][sbase + (lane >> 3)] = dr;
+    }
+}
+
+template <int NR, typename Extra, bool NT = false>
+__global__ void __launch_bounds__(kSyThreads, 2)
+symvn_lower_kernel(SymvNArgs a, Extra extra) {
+    static_assert(NR >= 2 && NR % 2 == 0, "right-hand sides come in pairs (u_k, w_k)");
+    if (blockIdx.x == 0) { extra(); return; }
+    if (a.skip != nullptr && *a.skip != 0) return;
+    __shared__ float4 red[2][kSyThreads];
+    __shared__ __attribute__((aligned(16))) float sdot[NR][kSyCBMax];
+    const int4 t = a.tiles[blockIdx.x - 1];
+    const int rb = t.x, seg = t.w;
+    const int cw = t.z >> 2;
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int row = rb * kSyRB + lane * 4;
+    const int col0 = t.y + wid * cw;
+    const int p4 = (a.p + 3) & ~3;
+    const bool active = row < p4;
+    const bool has = col0 < a.p;
+    const float* base = a.A + (size_t)col0 * a.lda + row;
+    float4 acc[NR];
+#pragma unroll
+    for (int r = 0; r < NR; ++r) acc[r] = make_float4(0.f, 0.f, 0.f, 0.f);
+
+    if (has) {
+        float4 vI[NR];
+        float vj[NR];
+        const int cj = col0 + lane;
+#pragma unroll
+        for (int r = 0; r < NR; ++r) {
+            const float* vr = a.v + (size_t)min(r, a.nvec - 1) * a.vstride;
+            vI[r] = active ? *reinterpret_cast<const float4*>(vr + row) : make_float4(0.f, 0.f, 0.f, 0.f);
+            vj[r] = (lane < cw && cj < a.p) ? vr[cj] : 0.f;
+        }
+        const bool diag = col0 + (cw - 1) >= rb * kSyRB;
+        const int nq = cw >> 3;
+#pragma unroll 1
+        for (int q = 0; q < nq; ++q) {
+            float4 av[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const int col = col0 + q * 8 + k;
+                av[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if constexpr (NT) { if (active && col < a.p) av[k] = load16_nt<float4>(base + (size_t)(q * 8 + k) * a.lda); }
+                else { if (active && col < a.p) av[k] = *reinterpret_cast<const float4*>(base + (size_t)(q * 8 + k) * a.lda); }
+            }
+            if (diag) symvn_chunk<NR, true>(av, vI, vj, acc, row, col0 + q * 8, q, lane, sdot, wid * cw + q * 8);
+            else symvn_chunk<NR, false>(av, vI, vj, acc, row, col0 + q * 8, q, lane, sdot, wid * cw + q * 8);
+        }
+    } else {
+#pragma unroll
+        for (int r = 0; r < NR; ++r)
+            for (int c = lane; c < cw; c += 64) sdot[r][wid * cw + c] = 0.f;
+    }
+    // pair by pair, as symv2_tile does for its one pair: waves 0 / 1 add the 4 waves' axpy parts of vectors 2 pr / 2 pr + 1, waves 2 / 3 write their dot rows
+#pragma unroll
+    for (int pr = 0; pr < NR / 2; ++pr) {
+        if (pr > 0) __syncthreads();
+        red[0][threadIdx.x] = acc[2 * pr];
+        red[1][threadIdx.x] = acc[2 * pr + 1];
+        __syncthreads();
+        const int r = 2 * pr + (wid & 1);
+        if (r >= a.nvec) continue;
+        if (wid < 2) {
+            float4 s = red[wid][lane];
+#pragma unroll
+            for (int ww = 1; ww < 4; ++ww) {
+                const float4 o = red[wid][ww * 64 + lane];
+                s.x += o.x; s.y += o.y; s.z += o.z; s.w += o.w;
+            }
+            float* dst = a.axp + (size_t)r * a.axp_stride + (size_t)seg * a.ldo + row;
+            *reinterpret_cast<float4*>(dst) = s;
+        } else {
+            float* dst = a.dot + (size_t)r * a.dot_stride + (size_t)rb * a.ldo + t.y;
+            for (int c = lane * 4; c < t.z; c += 256) *reinterpret_cast<float4*>(dst + c) = *reinterpret_cast<const float4*>(&sdot[r][c]);
+        }
+    }
+}
+
 // Mixed-precision refinement of the tall x-update (opt-in, ADMM_HIP_REFINE=1; lasso_tall.hip): the products M x0, M x1 of the
 // float system matrix M = X'X + rho I (lower triangle read, both halves of the symmetric product per loaded element, as
 // above) with the two float vectors x0, x1, every product and every sum in DOUBLE -- the residual of a refinement step has
@@ -494,6 +634,76 @@ __device__ __forceinline__ void symv_sum_partials(const T* __restrict__ dot0, co
     }
 #pragma unroll
     for (int m = 1; m < NL; m <<= 1) { a += __shfl_xor(a, m, 64); b += __shfl_xor(b, m, 64); }
+}
+
+// Launch of one pass of symvn_lower_kernel over the tiles of `sy` with nr = one of kSyNR right-hand sides per pass.
+template <typename Extra>
+void symvn_launch(const SymvPlan& sy, int nr, const SymvNArgs& a, hipStream_t st, Extra extra, hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr) {
+    const dim3 grid(sy.ntiles + 1), block(kSyThreads);
+    const bool timed = ev_start != nullptr || ev_stop != nullptr;      // start/stop events time exactly this kernel on its stream (hipExtLaunchKernel)
+#define ADMM_SYMVN_LAUNCH(NR, NT)                                                                                                        \
+    if (timed) hipExtLaunchKernelGGL((symvn_lower_kernel<NR, Extra, NT>), grid, block, 0, st, ev_start, ev_stop, 0, a, extra);           \
+    else hipLaunchKernelGGL((symvn_lower_kernel<NR, Extra, NT>), grid, block, 0, st, a, extra)
+#define ADMM_SYMVN_CASE(NR)                                                                                                              \
+    case NR:                                                                                                                             \
+        if (sy.nt) { ADMM_SYMVN_LAUNCH(NR, true); } else { ADMM_SYMVN_LAUNCH(NR, false); }                                               \
+        break;
+    switch (nr) {
+        ADMM_SYMVN_CASE(2) ADMM_SYMVN_CASE(4) ADMM_SYMVN_CASE(8) ADMM_SYMVN_CASE(12)
+        default: throw Error(ADMM_ERR_INTERNAL, "symvn_lower_kernel is not built for that many right-hand sides per pass");
+    }
+#undef ADMM_SYMVN_CASE
+#undef ADMM_SYMVN_LAUNCH
+}
+
+// symv_sum_partials for KB consecutive pairs of planes (pair k: dot + 2 k * dot_stride and the plane behind it, the same for axp) with
+// the loads of ALL the pairs issued before any is consumed: one memory round trip per 8 NL partials of every pair instead of KB
+// dependent ones.  Per pair the additions are symv_sum_partials' in its order (8 slots per step here, 16 there: the running sums take
+// the same terms in the same order), so a[k], b[k] are its values to the bit.  Pairs >= npair are not loaded (a = b = 0).
+template <int NL, int KB>
+__device__ __forceinline__ void symv_sum_partials_n(const float* __restrict__ dot, long long dot_stride, const float* __restrict__ axp, long long axp_stride,
+                                                    int npair, long long ldo, int nrb, const SymvSched sched, int p32, int i, int sub, bool valid,
+                                                    float (&a)[KB], float (&b)[KB]) {
+    const int ic = valid ? i : 0;
+    const int rbi = ic / kSyRB;
+    const int ndot = nrb - rbi;
+    const int nax = sched.nseg(rbi, p32);
+    const int ntot = valid ? ndot + nax : 0;
+    const unsigned ld = (unsigned)ldo;
+#pragma unroll
+    for (int k = 0; k < KB; ++k) { a[k] = 0.f; b[k] = 0.f; }
+    for (int k0 = 0; k0 < ntot; k0 += 8 * NL) {
+        float va[KB][8], vb[KB][8];
+#pragma unroll
+        for (int k = 0; k < KB; ++k) {
+            const int kc = min(k, npair - 1);                                  // clamped: always a valid plane
+            const float* d0 = dot + (size_t)(2 * kc) * dot_stride; const float* d1 = d0 + dot_stride;
+            const float* x0 = axp + (size_t)(2 * kc) * axp_stride; const float* x1 = x0 + axp_stride;
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int s = k0 + j * NL + sub;
+                const bool isdot = s < ndot;
+                const int row = isdot ? rbi + s : min(s, ntot - 1) - ndot;
+                const unsigned o = (unsigned)row * ld + (unsigned)ic;
+                va[k][j] = (isdot ? d0 : x0)[o];
+                vb[k][j] = (isdot ? d1 : x1)[o];
+            }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int k = 0; k < KB; ++k) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const bool in = k0 + j * NL + sub < ntot && k < npair;
+                a[k] += in ? va[k][j] : 0.f; b[k] += in ? vb[k][j] : 0.f;
+            }
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < KB; ++k) {
+#pragma unroll
+        for (int m = 1; m < NL; m <<= 1) { a[k] += __shfl_xor(a[k], m, 64); b[k] += __shfl_xor(b[k], m, 64); }
+    }
 }
 
 }  // namespace admm

@@ -4,6 +4,7 @@
 namespace admm {
 
 void test_symv(const float* A, int p, const float* v0, const float* v1, float* y0, float* y1);
+void test_symv_multi(const float* A, int p, const float* V, int nr, int rhs_per_pass, float* Yout);
 template <typename T> void test_gram(const T* A, int rows, int cols, bool atA, T* G);
 template <typename T> void test_spd_inverse(const T* A, int n, T* Ainv, bool via64);
 template <typename T> void test_gemv_t(const T* A, int rows, int cols, const T* v, T* y);

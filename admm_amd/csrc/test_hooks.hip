@@ -42,6 +42,59 @@ void test_symv(const float* A, int p, const float* v0, const float* v1, float* y
     st.sync();
 }
 
+// The multi-vector kernel of the multi-task lasso (symvn_lower_kernel) on nr vectors V [nr][p], rhs_per_pass of them per pass over the
+// triangle, with the plan's storage: planes of right-hand sides and of partials, summed by symv_sum_partials pair by pair
+// (vectors 2k, 2k + 1 are the pair of "response" k; an odd nr gets a zero vector behind it).
+__global__ void __launch_bounds__(256)
+test_symvn_finish_kernel(const float* dot, long long dot_stride, const float* axp, long long axp_stride, long long ldo, int nrb, SymvSched sched, int p32,
+                         int p, int npair, float* y, long long ldy) {
+    const int sub = threadIdx.x & (kSySumLanes - 1);
+    const int i = blockIdx.x * (256 / kSySumLanes) + threadIdx.x / kSySumLanes;
+    for (int k = 0; k < npair; ++k) {
+        float a, b;
+        symv_sum_partials<kSySumLanes>(dot + (size_t)(2 * k) * dot_stride, dot + (size_t)(2 * k + 1) * dot_stride,
+                                       axp + (size_t)(2 * k) * axp_stride, axp + (size_t)(2 * k + 1) * axp_stride, ldo, nrb, sched, p32, i, sub, i < p, a, b);
+        if (i < p && sub == 0) { y[(size_t)(2 * k) * ldy + i] = a; y[(size_t)(2 * k + 1) * ldy + i] = b; }
+    }
+}
+
+void test_symv_multi(const float* A, int p, const float* V, int nr, int rhs_per_pass, float* Yout) {
+    bool built = false;
+    for (int k = 0; k < kSyNRCount; ++k) built = built || kSyNR[k] == rhs_per_pass;
+    ADMM_REQUIRE(built, "rhs_per_pass must be one of the built widths (2, 4, 8, 12)");
+    require_device();
+    Stream st;
+    const long long lda = round_up(p, 128), ldv = round_up(p, 256);
+    const int nv = (nr + 1) / 2 * 2;
+    DevBuf<float> dA((size_t)lda * lda), dV((size_t)nv * ldv), dY((size_t)nv * ldv);
+    dA.zero(st.s); dV.zero(st.s);
+    ADMM_HIP_CHECK(hipMemcpy2DAsync(dA.get(), lda * sizeof(float), A, (size_t)p * sizeof(float), (size_t)p * sizeof(float), p,
+                                    hipMemcpyHostToDevice, st.s));
+    ADMM_HIP_CHECK(hipMemcpy2DAsync(dV.get(), ldv * sizeof(float), V, (size_t)p * sizeof(float), (size_t)p * sizeof(float), nr,
+                                    hipMemcpyHostToDevice, st.s));
+    SymvPlan sy;
+    sy.init(p, st.s);
+    const size_t ds = (size_t)sy.nrb * sy.ldo, as = (size_t)sy.nax_rows * sy.ldo;
+    DevBuf<float> dot((size_t)nv * ds), axp((size_t)nv * as);
+    dot.zero(st.s); axp.zero(st.s);
+    for (int r0 = 0; r0 < nv; r0 += rhs_per_pass) {
+        SymvNArgs a;
+        a.A = dA.get(); a.lda = lda; a.p = p;
+        a.v = dV.get() + (size_t)r0 * ldv; a.vstride = ldv;
+        a.dot = dot.get() + (size_t)r0 * ds; a.dot_stride = (long long)ds;
+        a.axp = axp.get() + (size_t)r0 * as; a.axp_stride = (long long)as;
+        a.nvec = std::min(rhs_per_pass, nv - r0); a.ldo = sy.ldo; a.tiles = sy.tiles.get(); a.skip = nullptr;
+        symvn_launch(sy, rhs_per_pass, a, st.s, SymvNoExtra());
+    }
+    const int per = 256 / kSySumLanes;
+    hipLaunchKernelGGL(test_symvn_finish_kernel, dim3((p + per - 1) / per), dim3(256), 0, st.s, dot.get(), (long long)ds, axp.get(), (long long)as,
+                       sy.ldo, sy.nrb, sy.sched, sy.p32, p, nv / 2, dY.get(), ldv);
+    ADMM_HIP_CHECK(hipGetLastError());
+    ADMM_HIP_CHECK(hipMemcpy2DAsync(Yout, (size_t)p * sizeof(float), dY.get(), ldv * sizeof(float), (size_t)p * sizeof(float), nr,
+                                    hipMemcpyDeviceToHost, st.s));
+    st.sync();
+}
+
 // Gram matrix through the solvers' own path (gram_full: matrix-core SYRK kernels, split-K for small orders):
 // G = A'A (atA) or AA' for a host matrix A (rows x cols, column-major, leading dimension rows); G host, order k, ld k.
 template <typename T>

@@ -308,6 +308,38 @@ ADMM_HIP_API int admm_hip_grplasso_plan_create(const double* x, const double* y,
                                                int standardize, int intercept, const admm_opts* opts,
                                                admm_hip_plan** plan_out, int* nlambda_out);
 
+/* Multi-task lasso on the tall path (n > p only; not in the reference package; glmnet's family = "mgaussian", scikit-learn's
+ * MultiTaskLasso): m responses on one design, one row-wise penalty that selects a feature for all responses at once,
+ *     minimise over b0 (m), B (p x m):  1/(2n) ||Y - 1 b0' - X B||_F^2 + lambda sum_j w_j ||B_j.||_2 ,
+ * internally 1/2 ||Y_s - X_s B||_F^2 + lambda_int sum_j w_j ||B_j.||_2 with lambda_int = lambda n / scaleY as for admm_hip_lasso.
+ * It is the group lasso on X (x) I_m with p groups of m, solved with ONE rho and therefore one cached inverse: every iteration streams
+ * the inverse's triangle ceil(2m / NR) times for all responses (symvn_lower_kernel, NR right-hand sides per pass: option MT_RHS)
+ * where m independent fits stream it m times, and the z-update is a block soft-threshold across the responses of a row
+ * (tall_mt_tail_kernel).  One stopping rule over all p m coordinates: one niter per lambda (maxit + 1 on exhaustion).
+ * Y: n x m column-major doubles in the same memory as x, 1 <= m <= ADMM_HIP_MT_MAX.  x is standardised as for admm_hip_lasso; with
+ * `intercept` every response is centred by its own mean; with `standardize` ALL responses are divided by one common scale,
+ * sqrt(sum_k ||y_k - mean_k||^2 / (n m)) (flag combinations as DataStd's: standardize without intercept takes the norm about the mean
+ * without centring), which keeps their relative sizes (glmnet's default).  m = 1 with NULL weights is admm_hip_lasso bit for bit.
+ * row_weight[p] >= 0, at least one > 0; NULL = all 1 (not sqrt(m): m = 1 is then the Lasso with penalty factors).  Weight 0 leaves a
+ * row unpenalised.  Automatic grid: lambda_0 = max over rows with w_j > 0 of ||(X_s'Y_s)_j.||_2 / w_j; with unpenalised rows its first
+ * lambda is NOT guaranteed to give an empty penalised model (as for admm_hip_grplasso): pass a grid of your own there.
+ * beta_out[nlam][m][p + 1]: for lambda l and response k the intercept followed by the p coefficients, coef_k = z_k / scaleX * scaleY,
+ * b0_k = meanY_k - sum_j coef_jk meanX_j.  lambda_out[nlam], niter_out[nlam].
+ * Single device; REFINE set, an attached communicator, elastic net: refused.  No wide (n <= p), cross-validated or consensus form.
+ * The plan is an ordinary admm_hip_plan: admm_hip_lasso_plan_run / _trace_* / _state_* / _destroy work on it; a state record holds
+ * 5 p m floats laid out [5][m][p]. */
+#define ADMM_HIP_MT_MAX 16
+ADMM_HIP_API int admm_hip_mtlasso(const double* x, const double* Y, int n, int p, int m, int mem,
+                                  const double* row_weight,
+                                  const double* lambda_in, int nlambda_in, int nlambda_auto, double lmin_ratio,
+                                  int standardize, int intercept, const admm_opts* opts,
+                                  double* lambda_out, float* beta_out, int* niter_out, admm_stats* stats);
+ADMM_HIP_API int admm_hip_mtlasso_plan_create(const double* x, const double* Y, int n, int p, int m, int mem,
+                                              const double* row_weight,
+                                              const double* lambda_in, int nlambda_in, int nlambda_auto, double lmin_ratio,
+                                              int standardize, int intercept, const admm_opts* opts,
+                                              admm_hip_plan** plan_out, int* nlambda_out);
+
 /* Decision trace of a prepared Lasso-family problem (tall, wide and consensus solvers): what the reference's commented-out iteration table
  * (print_row, FADMMBase.h:135-170, ADMMBase.h:111-146) would print, recorded on the device by the iteration control itself, one record
  * per decision (the cold-start decision first, then one per ADMM iteration, over all lambdas of a run in order).
@@ -523,6 +555,9 @@ ADMM_HIP_API int admm_hip_host_lanczos(const float* A, int n, float* eig_out, in
  * the symmetric p x p float matrix A (HOST, column-major, leading dimension p) against the two right-hand sides
  * v0, v1 (HOST, length p), followed by the tail kernel's ordered partial reduction.  y0 = A v0, y1 = A v1 (HOST). */
 ADMM_HIP_API int admm_hip_test_symv(const float* A, int p, const float* v0, const float* v1, float* y0, float* y1);
+/* The multi-task lasso's multi-vector form of it: Yout[r] = A V[r] for the nr (<= 64) vectors V [nr][p], rhs_per_pass (a built width:
+ * 2, 4, 8 or 12) of them per pass over the triangle; vectors 2k and 2k + 1 share the partial sums of one "response".  Yout [nr][p]. */
+ADMM_HIP_API int admm_hip_test_symv_multi(const float* A, int p, const float* V, int nr, int rhs_per_pass, float* Yout);
 
 /* The one-time matrix-core kernels as the solvers call them (Linalg::cross_prod_lower / tcross_prod_lower,
  * BlasWrapper.h:73-154; LLT, ADMMLassoTall.h:204-205), on HOST matrices (column-major, tight leading dimensions):

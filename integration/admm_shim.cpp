@@ -124,6 +124,30 @@ BEGIN_RCPP
 END_RCPP
 }
 
+// Multi-task lasso (not in the reference; include/admm_hip.h, admm_hip_mtlasso): the arguments of admm_lasso with an n x m matrix Y
+// in the place of y, plus `row_weight`, one weight per column of x or numeric(0) for all 1.  n > p only, m <= ADMM_HIP_MT_MAX.
+// beta: a (p + 1) x (m * nlambda) dgCMatrix, column l * m + k = response k at lambda l (intercept first).
+RcppExport SEXP admm_mtlasso(SEXP x_, SEXP Y_, SEXP lambda_, SEXP nlambda_, SEXP lmin_ratio_,
+                             SEXP standardize_, SEXP intercept_, SEXP row_weight_, SEXP opts_) {
+BEGIN_RCPP
+    NumericMatrix x(x_), Y(Y_);
+    NumericVector lambda(lambda_), row_weight(row_weight_);
+    const int n = x.nrow(), p = x.ncol(), m = Y.ncol();
+    if (Y.nrow() != n) Rcpp::stop("nrow(x) should be equal to nrow(Y)");
+    if (row_weight.size() != 0 && row_weight.size() != p) Rcpp::stop("row_weight should have one entry per column of x");
+    const int nl_in = lambda.size();
+    const int nl = nl_in > 0 ? nl_in : as<int>(nlambda_);
+    admm_opts o = unpack_opts(opts_);
+    NumericVector lambda_out(nl);
+    IntegerVector niter(nl);
+    std::vector<float> beta((size_t)(p + 1) * (size_t)(m > 0 ? m : 1) * nl);
+    check(admm_hip_mtlasso(x.begin(), Y.begin(), n, p, m, ADMM_MEM_HOST, row_weight.size() ? row_weight.begin() : nullptr,
+                           nl_in > 0 ? lambda.begin() : nullptr, nl_in, as<int>(nlambda_), as<double>(lmin_ratio_),
+                           as<bool>(standardize_), as<bool>(intercept_), &o, lambda_out.begin(), beta.data(), niter.begin(), nullptr));
+    return List::create(Named("lambda") = lambda_out, Named("beta") = to_dgCMatrix(beta, p + 1, m * nl), Named("niter") = niter);
+END_RCPP
+}
+
 RcppExport SEXP admm_lad(SEXP x_, SEXP y_, SEXP intercept_, SEXP opts_) {
 BEGIN_RCPP
     NumericMatrix x(x_);
