@@ -75,7 +75,7 @@ EXPORTS = ["admm_hip_lasso", "admm_hip_enet", "admm_hip_parlasso", "admm_hip_lad
            "admm_hip_options_default", "admm_hip_options_set", "admm_hip_option_set", "admm_hip_options_reset", "admm_hip_option_get",
            "admm_hip_last_parallel_layout", "admm_hip_parallel_assign", "admm_hip_grplasso", "admm_hip_grplasso_plan_create",
            "admm_hip_quantreg", "admm_hip_quantreg_state",
-           "admm_hip_mtlasso", "admm_hip_mtlasso_plan_create", "admm_hip_test_symv_multi"]
+           "admm_hip_mtlasso", "admm_hip_mtlasso_plan_create", "admm_hip_test_symv_multi", "admm_hip_test_tall_early_exits"]
 
 GROUP_MAX = 1024          # ADMM_HIP_GROUP_MAX
 MT_MAX = 16               # ADMM_HIP_MT_MAX
@@ -236,6 +236,8 @@ def load():
     lib.admm_hip_test_symv.restype = ctypes.c_int
     lib.admm_hip_test_symv_multi.argtypes = [_c_float_p, ctypes.c_int, _c_float_p, ctypes.c_int, ctypes.c_int, _c_float_p]
     lib.admm_hip_test_symv_multi.restype = ctypes.c_int
+    lib.admm_hip_test_tall_early_exits.argtypes = [ctypes.POINTER(ctypes.c_longlong)]
+    lib.admm_hip_test_tall_early_exits.restype = ctypes.c_int
     lib.admm_hip_test_gram.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
     lib.admm_hip_test_gram.restype = ctypes.c_int
     lib.admm_hip_test_gemv_t.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]

@@ -513,6 +513,13 @@ int admm_hip_test_symv_multi(const float* A, int p, const float* V, int nr, int 
     });
 }
 
+int admm_hip_test_tall_early_exits(long long* count) {
+    return guarded([&] {
+        ADMM_REQUIRE(count != nullptr, "bad arguments");
+        *count = tall_last_early_exits();
+    });
+}
+
 int admm_hip_test_gram(const void* A, int rows, int cols, int atA, int is_double, void* G) {
     return guarded([&] {
         ADMM_REQUIRE(A && G && rows > 0 && cols > 0, "bad arguments");

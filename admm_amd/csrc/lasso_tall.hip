@@ -19,6 +19,12 @@
 //    acceleration/restart, lambda schedule) runs as ONE EXTRA WORKGROUP of the x-update launch,
 //    concurrently with the streaming workgroups.  No host round trip, no grid barrier, no atomics:
 //    two launches per ADMM iteration.
+//    The decision therefore comes too late for the launch it rides on -- and once per lambda (`mode == 0` below) and once per path
+//    (`done`) it says that this launch's products will not be read.  It then publishes a VERDICT word (symv_kernels.h: SymvVerdict):
+//    tiles that start after it leave at once, running ones when they next look (between two 8-column chunks).  Nobody waits for
+//    anybody; a tile that does not see the word streams as before.  Measured at C2, same box, five alternating runs each
+//    (profiles/r07_tall_dead_work.md): 89.1-90.7 ms per path before, 85.8-87.8 after; the 100 discarded launches of a path take
+//    19.5 us instead of 33.6, the others 33.2 (the diagonal blocks' dead loads are gone as well: symv_kernels.h).
 //    (An earlier version used x = Minv u' + tau Minv w' with u' = X'y - y + rho z: equal in exact
 //    arithmetic, but it bypasses the float rounding of the right-hand side, and with it the dead
 //    band that lets the reference's stopping rule fire when rho * ulp(z) exceeds eps_dual -- tiny
@@ -82,7 +88,16 @@ struct TallParams {
     long long refine_ld;        // the correction it sums from the partials; NULL otherwise
     float* state;               // optional [state_cap][5][p] iterates x, z, y, adj_z, adj_y of every iteration (admm_hip_lasso_plan_state_*), or NULL
     long long state_cap;
+    unsigned long long* verdict;     // the x-update's verdict words (symv_kernels.h: SymvVerdict) and, behind them, the count of tiles that left early; or NULL
+    unsigned long long run_tag;      // number of this run() of the plan, above the bits of `total` and the discard bit
 };
+
+// The verdict word of the decision that leaves `total` decisions taken: bit 0 = the products of the launch it rides on are not used.
+__host__ __device__ inline unsigned long long tall_verdict_word(unsigned long long run_tag, int total, bool discard) {
+    return run_tag | ((unsigned long long)(unsigned)total << 1) | (discard ? 1ull : 0ull);
+}
+constexpr int kVerdictShift = 33;                                              // run_tag = run number << 33
+constexpr int kVerdictWords = kSyVerdictReplicas * kSyVerdictStride;           // the early-exit counter sits behind the copies, on a line of its own
 
 constexpr int kTailThreads = 256;
 constexpr int kTailLanes = kSySumLanes;   // lanes cooperating on one element's partial sums
@@ -163,6 +178,14 @@ __device__ void tall_decide(const TallParams& q, int par) {
         }
     } else {
         out.mode = 1; out.tau = 0.0; out.restart = 0;  // cold start: adj = 0, x = Minv X'y
+    }
+    // The tiles of THIS launch compute products the tail will not read when the decision is "keep the stored x" or "finished": tell the
+    // ones that have not started yet, as early as it is known (symv_kernels.h: SymvVerdict).  Only a discard is ever published -- any
+    // other word, a missing one included, means "stream".  Write-through, no fence: one word, nothing else to be seen with it.
+    if (q.verdict != nullptr && (out.mode == 0 || out.done)) {
+        const unsigned long long word = tall_verdict_word(q.run_tag, in.total + 1, true);
+        for (int r = 0; r < kSyVerdictReplicas; ++r)
+            __hip_atomic_store(q.verdict + (size_t)r * kSyVerdictStride, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     // eps for the iteration about to run, from the CURRENT iterate (FADMMBase.h:187-188, ADMMLassoTall.h:141-149)
     out.eps_primal = fmax(sqrt(x2), sqrt(z2)) * q.eps_rel + q.sqrt_p * q.eps_abs;
@@ -682,8 +705,13 @@ __global__ void tall_init_kernel(TallParams q, double rho, double lam0) {
         c.a_next = 0.5 + 0.5 * sqrt(5.0); c.tau_next = 0.0;
         c.mode = 1; c.restart = 0; c.iter = 0; c.lam_idx = 0; c.done = 0; c.first = 1; c.total = 0; c.fin_idx = -1; c.fin_niter = 0; c.pad = 0;
         q.ctl[0] = c; q.ctl[1] = c;
+        if (q.verdict != nullptr) q.verdict[kVerdictWords] = 0;      // tiles that left early in this run (the words themselves carry the run number)
     }
 }
+
+// Tiles of the x-update that left early in the calling thread's most recent tall path (test hook admm_hip_test_tall_early_exits).
+static thread_local long long t_early_exits = 0;
+long long tall_last_early_exits() { return t_early_exits; }
 
 // ----------------------------------------------------------------------------------------------
 struct TallPlan final : LassoPlan {
@@ -710,6 +738,9 @@ struct TallPlan final : LassoPlan {
     DevBuf<int> niter;
     DevBuf<double> P, dlam;
     DevBuf<TallCtl> ctl;
+    DevBuf<unsigned long long> verdict;                 // early exit of discarded x-update launches (symv_kernels.h: SymvVerdict): the words + the counter
+    bool verdict_on = false, verdict_mid = false;
+    unsigned long long run_no = 0;                      // run() calls of this plan: part of the verdict word
     TallParams q{};
     // mixed-precision refinement of the x-update (ADMM_HIP_REFINE=1)
     bool refine = false;
@@ -971,6 +1002,15 @@ struct TallPlan final : LassoPlan {
         q.adj_z = adj_z.get(); q.adj_y = adj_y.get(); q.u = u.get(); q.w = w.get();
         q.ctl = ctl.get(); q.P = P.get(); q.beta = beta.get(); q.niter = niter.get();
         q.done_host = hflag.p;
+        // Tiles leave early only where the tail provably ignores the products of a discarded launch: the single-device, unrefined
+        // two-launch forms (tall_tail_kernel<TAIL_SYMV>, tall_group_tail_kernel<TAIL_SYMV>).  Sharded, refined and multi-task x-updates
+        // have consumers of their own between the stream and the tail.  ADMM_HIP_SYMV_VERDICT=0 turns it off, 1 keeps only the check in the tile prologue (A/B, tests).
+        verdict_on = use_sym && !shard && !refine && !mt && !opt_off(Opt::SYMV_VERDICT);
+        verdict_mid = opt_int(Opt::SYMV_VERDICT, 2) == 2;      // default: the waves also look between the chunks of their column loop
+        if (verdict_on) {
+            verdict.alloc(kVerdictWords + kSyVerdictStride); verdict.zero(st);
+            q.verdict = verdict.get();
+        }
 #ifdef ADMM_HIP_PROBE
         probe.alloc((size_t)4096 * 4 * 8); probe.zero(st);
         q.probe = probe.get();
@@ -1077,6 +1117,7 @@ struct TallPlan final : LassoPlan {
         S.factor_flops = dist_flops;
         res.lambda = lam_user;
         beta.zero(st); niter.zero(st);
+        q.run_tag = ++run_no << kVerdictShift;          // `total` restarts at 0 below: the words an earlier run left must not match this one's
         const int init_n = std::max(p, 2 * nwg * 8);
         for (int k = 0; k < std::max(mt, 1); ++k) {      // multi-task: plane by plane (every launch writes the same control block and norm partials)
             TallParams qk = q;
@@ -1120,6 +1161,9 @@ struct TallPlan final : LassoPlan {
             // sampled launches carry start/stop events that time exactly the x-update kernel on this stream
             // the decision of this iteration rides along as one extra workgroup of the x-update launch
             const TallDecideExtra dec{q, par};
+            // launch g rides the decision that leaves g + 1 taken: its tiles leave on exactly that word with the discard bit set
+            SymvVerdict vd;
+            if (verdict_on) { vd.words = verdict.get(); vd.discard = tall_verdict_word(q.run_tag, (int)(g + 1), true); vd.early = verdict.get() + kVerdictWords; vd.mid = verdict_mid; }
             if (mt) {
                 // ceil(2m / NR) passes over the triangle, NR right-hand sides each (the decision rides on the first), then the row tail
                 const int nvec = 2 * mt;
@@ -1138,7 +1182,7 @@ struct TallPlan final : LassoPlan {
                 hipLaunchKernelGGL(tall_mt_tail_kernel, dim3(nwg), dim3(kTailThreads), 0, st, q, par, mq);
             } else if (grouped) {                      // two launches, as the Lasso: the x-update with the decision, the group tail
                 if (use_sym) {
-                    sy.launch(M.get(), ldp, u.get(), w.get(), &ctl.get()[par].done, st, dec, e0, e1);
+                    sy.launch(M.get(), ldp, u.get(), w.get(), &ctl.get()[par].done, st, dec, e0, e1, vd);
                     hipLaunchKernelGGL(tall_group_tail_kernel<TAIL_SYMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, gq);
                 } else {
                     launch_gemv_t<float, 2, 4, TallDecideExtra>(pl, M.get(), ldp, p, p, u.get(), w.get(), a_part.get(), b_part.get(), ldp,
@@ -1177,7 +1221,7 @@ struct TallPlan final : LassoPlan {
                 sy.launch(M.get(), ldp, ruw.get(), ruw.get() + ldv, skip, st, SymvNoExtra());
                 hipLaunchKernelGGL(tall_tail_kernel<TAIL_SYMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, PeerExchange{});
             } else if (use_sym) {
-                sy.launch(M.get(), ldp, u.get(), w.get(), &ctl.get()[par].done, st, dec, e0, e1);
+                sy.launch(M.get(), ldp, u.get(), w.get(), &ctl.get()[par].done, st, dec, e0, e1, vd);
                 hipLaunchKernelGGL(tall_tail_kernel<TAIL_SYMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, PeerExchange{});
             } else {
                 launch_gemv_t<float, 2, 4, TallDecideExtra>(pl, M.get(), ldp, p, p, u.get(), w.get(), a_part.get(), b_part.get(), ldp,
@@ -1187,6 +1231,9 @@ struct TallPlan final : LassoPlan {
         }, LoopOpts{shard ? nullptr : hflag.p, 0, false});
         S.t_loop = lt.wall_s; S.loop_ms_events = lt.events_ms; S.xupdate_launches = lt.launched;
         const CtlPair<TallCtl> hctl = read_ctl(ctl.get());      // both slots: decisions taken
+        unsigned long long early = 0;
+        if (verdict_on) ADMM_HIP_CHECK(hipMemcpy(&early, verdict.get() + kVerdictWords, sizeof early, hipMemcpyDeviceToHost));
+        t_early_exits = (long long)early;
         WIDE_PROBE_DUMP(probe);
         if (nev > 0) {
             double tot = 0;

@@ -38,10 +38,21 @@
 //    but cross-XCD visibility needs either agent-scope fences (whole-L2 write-back per wave: 5x slower) or
 //    uncached partial arrays plus an acknowledged-store wait and an atomic round trip per tile (1.65x slower
 //    than two launches).
+// Round 7, work whose result nobody uses (profiles/r07_tall_dead_work.md; C2, same box, parent and new alternating):
+//  * diagonal blocks: a lane whose four rows all lie above a column no longer loads that float4 (`last` in symv2_tile).  PMC: 202.6 MB
+//    read per launch instead of 207.1 (the triangle is 200); 33.0 instead of 33.7 us per launch in the kernel trace;
+//  * prologue: the `done` word, the verdict word and the tile descriptor are requested together -- one round trip before the first
+//    matrix request instead of two;
+//  * launches whose products are discarded (100 of the 2264 of a C2 path) end early: SymvVerdict below.  Checked in the prologue only,
+//    the 636 tiles that are not resident at the start leave (63 600 per path) and such a launch takes 29.6 us; checked between
+//    the chunks as well it takes 19.5 us and the path 85.8-87.8 ms against 86.9-90.1 (parent: 89.1-90.7), regular launches 33.2
+//    against 33.1 us.  A first form that kept the word in vector registers through the chunk spilled (24 bytes of scratch, a reload
+//    in the loop) and was not measured: the word is compared as two scalars right behind the chunk's wait.
 #pragma once
 #include "admm_internal.h"
 #include "device_utils.h"
 #include <hip/hip_ext.h>
+#include <climits>
 
 namespace admm {
 
@@ -76,10 +87,31 @@ struct SymvArgs {
     float* axp0; float* axp1;              // [ncb][ldo]
     long long ldo;
     const int4* tiles;                     // (row block, first column, width, segment index within the strip) of every tile
-    const int* skip;
+    const int* skip;                       // sticky `done` word (a caller without one gets the plan's zero word: never null in the kernel)
+    const unsigned long long* verdict;     // kSyVerdictReplicas copies of the verdict word, one per 128-byte line (SymvVerdict below; never null in the kernel)
+    unsigned long long discard;            // the one value of that word that says "the products of this launch are not used"
+    unsigned long long* early;             // count of the tiles that left on it (added to on the exit path only)
 #ifdef ADMM_HIP_PROBE
     long long* probe; int probe_idx;       // dev build only (probe.h): entry / end stamps of the first, middle and last tile
 #endif
+};
+
+// Early exit of the tiles of a launch whose products nobody reads (tall solver, lasso_tall.hip: after a converged lambda the tail keeps
+// the stored x, and the launch that takes the last decision of a path is not consumed at all).  The decision is taken by the extra
+// workgroup of that SAME launch, so a tile can only know it if it starts late enough: the decider publishes ONE 64-bit word -- the
+// run, the number of the launch and the discard bit, so that no word of another launch or of an earlier run() can be mistaken for it
+// -- with write-through stores into kSyVerdictReplicas copies on lines of their own, and every tile reads its copy once, in its
+// prologue, with an agent-scope load (not served by this CU's L1), together with the `done` word and its tile descriptor.  The check
+// never waits: a word that is not there yet, or is another launch's, means "stream as usual".  Tiles that leave write no partials: the
+// slots keep what the previous launch left, nothing reads them (the tail of a discarded launch takes x from its stored copy and sums the
+// partials only into values it drops), and the next consumed launch rewrites every slot first.
+constexpr int kSyVerdictReplicas = 64;     // a power of two
+constexpr int kSyVerdictStride = 16;       // in words: 128 bytes
+struct SymvVerdict {
+    const unsigned long long* words = nullptr;      // null: the launch never leaves early
+    unsigned long long discard = 0;
+    unsigned long long* early = nullptr;
+    bool mid = false;                               // the waves also look between the chunks of their column loop (plain-load kernel only)
 };
 
 // Sum 8 per-lane values over the 64 lanes: afterwards every lane l holds the total of value (l >> 3).
@@ -137,7 +169,10 @@ struct SymvNoWait { __device__ __forceinline__ void operator()() const {} };
 // PRE = false (the two-launch path): no wait, right-hand entries first, every 8-column chunk loaded at the top of its loop
 // iteration -- the shape that streams best (with the PRE shape the same 128-column kernel ran at 39.3 instead of 35.1 us on
 // C2: a first chunk carried into the loop in registers and a conditional reload defeat the scheduling of the loads).
-template <bool PRE, typename Wait, typename VecLoad, bool NT = false>      // NT: matrix read with non-temporal loads (triangle larger than the Infinity Cache)
+// MID: the wave also asks for its copy of the verdict word ahead of every chunk's 8 matrix loads, reads it behind that chunk's wait and
+// leaves the column loop when it says "discard" (SymvVerdict below).  The waves of a workgroup may disagree; every one still runs the
+// epilogue and reaches its barrier, and what a tile that stopped half-way writes is as unread as what it would have written.
+template <bool PRE, typename Wait, typename VecLoad, bool NT = false, bool MID = false>      // NT: matrix read with non-temporal loads (triangle larger than the Infinity Cache)
 __device__ __forceinline__ void symv2_tile(const SymvArgs& a, const int4 t, Wait wait, VecLoad vl,
                                            float4 (*red)[kSyThreads], float (*sdot)[kSyCBMax]) {
     const int rb = t.x, seg = t.w;
@@ -168,16 +203,28 @@ __device__ __forceinline__ void symv2_tile(const SymvArgs& a, const int4 t, Wait
         const float wj = (lane < cw && cj < a.p) ? vl.load1(a.v1 + cj) : 0.f;
         const bool diag = col0 + (cw - 1) >= rb * kSyRB;         // this wave's block meets the diagonal
         const int nq = cw >> 3;
+        // Last column this lane loads: p - 1, and on a wave that meets the diagonal no column beyond its last row -- there all four
+        // entries of the float4 lie above the diagonal and are zeroed below whatever was loaded (about half of a 256 x 256 diagonal
+        // block: 4.9 MB of whole 128-byte lines per launch at p = 10^4).  av[k] stays the zero it is initialised with, so every value
+        // that enters an FMA is what it was.  One compare per column, as before (it replaces `active && col < p`).
+        const int last = active ? min(a.p - 1, diag ? row + 3 : INT_MAX) : -1;
+        const unsigned long long* vword = a.verdict + (size_t)(blockIdx.x & (kSyVerdictReplicas - 1)) * kSyVerdictStride;
 #pragma unroll 1
         for (int q = 0; q < nq; ++q) {
+            unsigned long long vq = 0;
+            if constexpr (MID) vq = __hip_atomic_load(vword, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (!PRE || q > 0) {
 #pragma unroll
                 for (int k = 0; k < 8; ++k) {
                     const int col = col0 + q * 8 + k;
                     av[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if constexpr (NT) { if (active && col < a.p) av[k] = load16_nt<float4>(base + (size_t)(q * 8 + k) * a.lda); }
-                    else { if (active && col < a.p) av[k] = *reinterpret_cast<const float4*>(base + (size_t)(q * 8 + k) * a.lda); }
+                    if constexpr (NT) { if (col <= last) av[k] = load16_nt<float4>(base + (size_t)(q * 8 + k) * a.lda); }
+                    else { if (col <= last) av[k] = *reinterpret_cast<const float4*>(base + (size_t)(q * 8 + k) * a.lda); }
                 }
+            }
+            if constexpr (MID) {      // the word was requested first, so it is there before the chunk is: no wait of its own.  Wave-uniform (one address), compared as scalars
+                const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)vq), hi = __builtin_amdgcn_readfirstlane((unsigned)(vq >> 32));
+                if ((((unsigned long long)hi << 32) | lo) == a.discard) break;
             }
             float dU[8], dW[8];
 #pragma unroll
@@ -237,17 +284,27 @@ __device__ __forceinline__ void symv2_tile(const SymvArgs& a, const int4 t, Wait
 // solver uses it for its scalar iteration control, which then costs no launch and no latency.
 struct SymvNoExtra { __device__ void operator()() const {} };
 
-template <typename Extra, bool NT = false>
+template <typename Extra, bool NT = false, bool MID = false>
 __global__ void __launch_bounds__(kSyThreads, 4)      // 4 waves/SIMD: 2 or 4 measure the same, 8 spills; non-temporal loads are 8 % slower (the 2p^2 bytes stay in the Infinity Cache)
 symv2_lower_kernel(SymvArgs a, Extra extra) {
     if (blockIdx.x == 0) { extra(); return; }
-    if (a.skip != nullptr && *a.skip != 0) return;
+    // Prologue: the `done` word, this tile's copy of the verdict word and its descriptor are requested together and waited for once --
+    // one memory round trip before the first matrix request (round 6 and before: `done`, a branch, then the descriptor: two).
+    const int4 t = a.tiles[blockIdx.x - 1];
+    const unsigned long long vw = __hip_atomic_load(a.verdict + (size_t)(blockIdx.x & (kSyVerdictReplicas - 1)) * kSyVerdictStride,
+                                                    __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int done = *a.skip;
+    if (done != 0) return;
+    if (vw == a.discard) {                 // this launch's own verdict, already published: nobody reads what this tile would write
+        if (threadIdx.x == 0) atomicAdd(a.early, 1ull);
+        return;
+    }
     __shared__ float4 red[2][kSyThreads];
     __shared__ __attribute__((aligned(16))) float sdot[2][kSyCBMax];
 #ifdef ADMM_HIP_PROBE
     const long long pt0 = wall_clock64();
 #endif
-    symv2_tile<false, SymvNoWait, SymvPlainVec, NT>(a, a.tiles[blockIdx.x - 1], SymvNoWait(), SymvPlainVec(), red, sdot);
+    symv2_tile<false, SymvNoWait, SymvPlainVec, NT, MID>(a, t, SymvNoWait(), SymvPlainVec(), red, sdot);
 #ifdef ADMM_HIP_PROBE
     if (a.probe != nullptr && threadIdx.x == 0) {
         const int nt = (int)gridDim.x - 1, t = (int)blockIdx.x - 1;
@@ -491,6 +548,7 @@ struct SymvPlan {
     std::vector<int4> htiles;      // host copy of this plan's tile list (the distributed setup derives from it which tiles of the inverse a rank reads)
     bool nt = false;
     DevBuf<float> dot0, dot1, axp0, axp1;
+    DevBuf<unsigned long long> zero;      // zeros, the size of the verdict words (the kernel indexes its copy whatever it is given): the `done` word and the verdict of launches that have none
 #ifdef ADMM_HIP_PROBE
     long long* probe = nullptr; mutable int probe_idx = 0;
 #endif
@@ -566,13 +624,20 @@ struct SymvPlan {
         dot0.alloc((size_t)nrb * ldo); dot1.alloc((size_t)nrb * ldo);
         axp0.alloc((size_t)nax_rows * ldo); axp1.alloc((size_t)nax_rows * ldo);
         dot0.zero(st); dot1.zero(st); axp0.zero(st); axp1.zero(st);
+        zero.alloc((size_t)kSyVerdictReplicas * kSyVerdictStride); zero.zero(st);
         ADMM_HIP_CHECK(hipStreamSynchronize(st));
     }
-    SymvArgs args(const float* A, long long lda, const float* v0, const float* v1, const int* skip) const {
+    SymvArgs args(const float* A, long long lda, const float* v0, const float* v1, const int* skip, const SymvVerdict& vd = SymvVerdict()) const {
         SymvArgs a;
         a.A = A; a.lda = lda; a.p = p; a.v0 = v0; a.v1 = v1;
         a.dot0 = dot0.get(); a.dot1 = dot1.get(); a.axp0 = axp0.get(); a.axp1 = axp1.get();
-        a.ldo = ldo; a.tiles = tiles.get(); a.skip = skip;
+        a.ldo = ldo; a.tiles = tiles.get();
+        // the kernel loads both words unconditionally (no branch in front of its first requests): without a `done` word or a verdict
+        // they are the plan's zero words, which no `discard` value equals (a published word always has its run number set)
+        a.skip = skip != nullptr ? skip : reinterpret_cast<const int*>(zero.get());
+        a.verdict = vd.words != nullptr ? vd.words : zero.get();
+        a.discard = vd.words != nullptr ? vd.discard : ~0ull;
+        a.early = vd.early;
 #ifdef ADMM_HIP_PROBE
         a.probe = probe; a.probe_idx = probe_idx++;
 #endif
@@ -580,12 +645,17 @@ struct SymvPlan {
     }
     template <typename Extra = SymvNoExtra>
     void launch(const float* A, long long lda, const float* v0, const float* v1, const int* skip, hipStream_t st, Extra extra = Extra(),
-                hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr) {
-        const SymvArgs a = args(A, lda, v0, v1, skip);
+                hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr, const SymvVerdict& vd = SymvVerdict()) {
+        const SymvArgs a = args(A, lda, v0, v1, skip, vd);
         // start/stop events (when given) time exactly this kernel on its stream (hipExtLaunchKernel)
         if (nt) {
             if (ev_start == nullptr && ev_stop == nullptr) hipLaunchKernelGGL((symv2_lower_kernel<Extra, true>), dim3(ntiles + 1), dim3(kSyThreads), 0, st, a, extra);
             else hipExtLaunchKernelGGL((symv2_lower_kernel<Extra, true>), dim3(ntiles + 1), dim3(kSyThreads), 0, st, ev_start, ev_stop, 0, a, extra);
+            return;
+        }
+        if (vd.words != nullptr && vd.mid) {
+            if (ev_start == nullptr && ev_stop == nullptr) hipLaunchKernelGGL((symv2_lower_kernel<Extra, false, true>), dim3(ntiles + 1), dim3(kSyThreads), 0, st, a, extra);
+            else hipExtLaunchKernelGGL((symv2_lower_kernel<Extra, false, true>), dim3(ntiles + 1), dim3(kSyThreads), 0, st, ev_start, ev_stop, 0, a, extra);
             return;
         }
         if (ev_start == nullptr && ev_stop == nullptr) hipLaunchKernelGGL((symv2_lower_kernel<Extra>), dim3(ntiles + 1), dim3(kSyThreads), 0, st, a, extra);

@@ -11,5 +11,6 @@ template <typename T> void test_gemv_t(const T* A, int rows, int cols, const T* 
 template <typename T> void test_gather(const T* A, int rows, int cols, const T* v, double* y);
 void test_cv_fold_system(const double* x, const double* y, int n, int p, const int* fold_id, int nfolds, int fold,
                          int standardize, int intercept, float* gram, float* xy, float* mean_x, float* scale_x, float* mean_scale_y);
+long long tall_last_early_exits();      // lasso_tall.hip
 
 }  // namespace admm

@@ -558,6 +558,10 @@ ADMM_HIP_API int admm_hip_test_symv(const float* A, int p, const float* v0, cons
 /* The multi-task lasso's multi-vector form of it: Yout[r] = A V[r] for the nr (<= 64) vectors V [nr][p], rhs_per_pass (a built width:
  * 2, 4, 8 or 12) of them per pass over the triangle; vectors 2k and 2k + 1 share the partial sums of one "response".  Yout [nr][p]. */
 ADMM_HIP_API int admm_hip_test_symv_multi(const float* A, int p, const float* V, int nr, int rhs_per_pass, float* Yout);
+/* Tiles of the tall x-update that left early because the launch they belonged to was known to be discarded (the first launch after a
+ * converged lambda, the launch of the last decision; ADMM_HIP_SYMV_VERDICT=0: none), counted over the most recent tall lasso /
+ * elastic-net / group-lasso path run by the CALLING THREAD.  How many leave is a matter of timing; the results do not depend on it. */
+ADMM_HIP_API int admm_hip_test_tall_early_exits(long long* count);
 
 /* The one-time matrix-core kernels as the solvers call them (Linalg::cross_prod_lower / tcross_prod_lower,
  * BlasWrapper.h:73-154; LLT, ADMMLassoTall.h:204-205), on HOST matrices (column-major, tight leading dimensions):
