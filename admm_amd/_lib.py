@@ -75,7 +75,8 @@ EXPORTS = ["admm_hip_lasso", "admm_hip_enet", "admm_hip_parlasso", "admm_hip_lad
            "admm_hip_options_default", "admm_hip_options_set", "admm_hip_option_set", "admm_hip_options_reset", "admm_hip_option_get",
            "admm_hip_last_parallel_layout", "admm_hip_parallel_assign", "admm_hip_grplasso", "admm_hip_grplasso_plan_create",
            "admm_hip_quantreg", "admm_hip_quantreg_state",
-           "admm_hip_mtlasso", "admm_hip_mtlasso_plan_create", "admm_hip_test_symv_multi", "admm_hip_test_tall_early_exits"]
+           "admm_hip_mtlasso", "admm_hip_mtlasso_plan_create", "admm_hip_test_symv_multi", "admm_hip_test_tall_early_exits",
+           "admm_hip_sgl", "admm_hip_sgl_plan_create", "admm_hip_host_sgl_lambda0"]
 
 GROUP_MAX = 1024          # ADMM_HIP_GROUP_MAX
 MT_MAX = 16               # ADMM_HIP_MT_MAX
@@ -166,6 +167,13 @@ def load():
     lib.admm_hip_grplasso.restype = ctypes.c_int
     lib.admm_hip_grplasso_plan_create.argtypes = grp_args + [ctypes.POINTER(AdmmOpts), ctypes.POINTER(ctypes.c_void_p), _c_int_p]
     lib.admm_hip_grplasso_plan_create.restype = ctypes.c_int
+    sgl_args = grp_args[:8] + [_c_double_p, ctypes.c_double] + grp_args[8:]
+    lib.admm_hip_sgl.argtypes = sgl_args + tail
+    lib.admm_hip_sgl.restype = ctypes.c_int
+    lib.admm_hip_sgl_plan_create.argtypes = sgl_args + [ctypes.POINTER(AdmmOpts), ctypes.POINTER(ctypes.c_void_p), _c_int_p]
+    lib.admm_hip_sgl_plan_create.restype = ctypes.c_int
+    lib.admm_hip_host_sgl_lambda0.argtypes = [_c_float_p, ctypes.c_int, _c_int_p, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_double, _c_float_p]
+    lib.admm_hip_host_sgl_lambda0.restype = ctypes.c_int
     mt_args = lasso_args[:4] + [ctypes.c_int, ctypes.c_int, _c_double_p] + lasso_args[5:]
     lib.admm_hip_mtlasso.argtypes = mt_args + tail
     lib.admm_hip_mtlasso.restype = ctypes.c_int

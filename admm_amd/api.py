@@ -8,6 +8,7 @@ the same names, argument meaning, defaults and error behaviour:
     admm_lad(x, y, intercept)$opts(...)$fit()                       R/20_admm_lad.R
     admm_bp(x, y)$opts(...)$fit()                                   R/10_admm_bp.R
     admm_grplasso(x, y, group)$penalty(..., group_weights)$opts(...)$fit()      (not in the reference: admm_hip_grplasso)
+    admm_sgl(x, y, group, alpha)$penalty(..., group_weights, l1_weights)$opts(...)$fit()      (not in the reference: admm_hip_sgl)
     admm_mtlasso(x, Y)$penalty(..., row_weights)$opts(...)$fit()                (not in the reference: admm_hip_mtlasso)
 
 `fit()` forwards to the C ABI of libadmm_hip.so exactly where the R `$fit()` does its
@@ -561,6 +562,9 @@ class LassoPlan:
         if isinstance(model, ADMM_MTLasso):
             check(lib.admm_hip_mtlasso_plan_create(xp, yp, model.n, model.p, model.m, xmem, model._weight_arg(), *path,
                                                    ctypes.byref(o), ctypes.byref(h), ctypes.byref(nl)))
+        elif isinstance(model, ADMM_SGL):
+            check(lib.admm_hip_sgl_plan_create(xp, yp, model.n, model.p, xmem, *model._group_args(), *path,
+                                               ctypes.byref(o), ctypes.byref(h), ctypes.byref(nl)))
         elif isinstance(model, ADMM_GrpLasso):
             check(lib.admm_hip_grplasso_plan_create(xp, yp, model.n, model.p, xmem, *model._group_args(), *path,
                                                     ctypes.byref(o), ctypes.byref(h), ctypes.byref(nl)))
@@ -785,6 +789,61 @@ class ADMM_GrpLasso(ADMM_Lasso):
 
 def admm_grplasso(x, y, group, intercept=True, standardize=True, **kw):
     return ADMM_GrpLasso(x, y, group, intercept, standardize, **kw)
+
+
+class ADMM_SGL(ADMM_GrpLasso):
+    """Sparse-group lasso on the tall path (admm_hip_sgl; n > p only, one device): the group lasso's model with the penalty
+    lambda (alpha sum_j u_j |b_j| + (1 - alpha) sum_g w_g ||b_g||_2), which selects groups and coefficients inside the groups it keeps.
+    `group` as for admm_grplasso; `l1_weights` (u, one per column, default 1) are given in the CALLER's column order and travel with the
+    columns when scattered groups are reordered.  alpha = 0 is the group lasso, alpha = 1 the Lasso with penalty factors u."""
+    _name = "ADMM Sparse-Group Lasso model"
+    _missing = "not available for the sparse-group lasso (single-device tall solver only)"
+
+    def __init__(self, x, y, group, alpha=0.95, intercept=True, standardize=True, n=None, p=None):
+        super().__init__(x, y, group, intercept, standardize, n, p)
+        a = float(alpha)
+        if not (np.isfinite(a) and 0.0 <= a <= 1.0):
+            _stop("alpha must be within [0, 1]")
+        self.alpha = a
+        self.l1_weights = None                                       # library default: 1 for every column
+
+    def penalty(self, lambda_=None, nlambda=100, lambda_min_ratio=None, group_weights=None, l1_weights=None, **kw):
+        ADMM_Lasso.penalty(self, lambda_, nlambda, lambda_min_ratio, **kw)
+        w = u = None
+        if group_weights is not None:
+            w = np.ascontiguousarray(np.asarray(group_weights, dtype=np.float64).ravel())
+            if w.size != self.ngroups:
+                _stop("group_weights should have one entry per group (in order of first appearance)")
+            if not np.all(np.isfinite(w)) or np.any(w < 0):
+                _stop("group_weights must be finite and non-negative")
+        if l1_weights is not None:
+            u = np.asarray(l1_weights, dtype=np.float64).ravel()
+            if u.size != self.p:
+                _stop("l1_weights should have one entry per column")
+            if not np.all(np.isfinite(u)) or np.any(u < 0):
+                _stop("l1_weights must be finite and non-negative")
+            u = np.ascontiguousarray(u if self._perm is None else u[self._perm])      # library column k = caller's column _perm[k]
+        wg = (1.0 - self.alpha) * (np.ones(self.ngroups) if w is None else w)
+        l1 = self.alpha * (np.ones(self.p) if u is None else u)
+        if not (np.any(l1 > 0) or np.any(wg > 0)):
+            _stop("at least one coordinate must carry a positive penalty")
+        self.group_weights, self.l1_weights = w, u
+        return self
+
+    def _group_args(self):
+        u = self.l1_weights
+        return super()._group_args() + (u.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if u is not None else None, self.alpha)
+
+    def fit(self):
+        lib, head, tail, lam_out, beta, niter, stats, keep = self._common()
+        check(lib.admm_hip_sgl(*head[:5], *self._group_args(), *head[5:], *tail))
+        fit = ADMM_Lasso_fit(lam_out, self._restore(beta), niter, stats.as_dict())
+        fit._title = "ADMM Sparse-Group Lasso fitting result"
+        return fit
+
+
+def admm_sgl(x, y, group, alpha=0.95, intercept=True, standardize=True, **kw):
+    return ADMM_SGL(x, y, group, alpha, intercept, standardize, **kw)
 
 
 class ADMM_MTLasso_fit:

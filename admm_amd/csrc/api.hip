@@ -241,6 +241,28 @@ int admm_hip_grplasso_plan_create(const double* x, const double* y, int n, int p
     });
 }
 
+// admm_hip_sgl: the group lasso's arguments plus the l1 weight of every column and the mixing parameter
+#define SGL_SPEC [&] { PathSpec s = GROUP_SPEC; s.sgl = true; s.sgl_mix = alpha; s.l1_weight = l1_weight; return s; }()
+
+int admm_hip_sgl(const double* x, const double* y, int n, int p, int mem,
+                 const int* group, const double* group_weight, int ngroups, const double* l1_weight, double alpha,
+                 const double* lambda_in, int nlambda_in, int nlambda_auto, double lmin_ratio,
+                 int standardize, int intercept, const admm_opts* opts,
+                 double* lambda_out, float* beta_out, int* niter_out, admm_stats* stats) {
+    return guarded([&] { lasso_family(x, y, n, p, mem, SGL_SPEC, 0, Shard(), PATH_OUT); });
+}
+
+int admm_hip_sgl_plan_create(const double* x, const double* y, int n, int p, int mem,
+                             const int* group, const double* group_weight, int ngroups, const double* l1_weight, double alpha,
+                             const double* lambda_in, int nlambda_in, int nlambda_auto, double lmin_ratio,
+                             int standardize, int intercept, const admm_opts* opts,
+                             admm_hip_plan** plan_out, int* nlambda_out) {
+    return guarded([&] {
+        ADMM_REQUIRE(plan_out != nullptr, "plan_out must not be NULL");
+        plan_out_set(create_plan(x, y, n, p, mem, SGL_SPEC, 0), plan_out, nlambda_out);
+    });
+}
+
 // admm_hip_mtlasso: the Lasso's path arguments plus the number of responses and the row weights
 #define MT_SPEC [&] { PathSpec s = PATH_SPEC(-1.0); s.nresp = m; s.row_weight = row_weight; s.mt_rows = p; if (m == 0) s.nresp = -1; return s; }()
 
@@ -496,6 +518,25 @@ int admm_hip_host_lanczos(const float* A, int n, float* eig_out, int* nmatop_out
             }
         };
         *eig_out = lanczos_largest_f32(op, n, nmatop_out);
+    });
+}
+
+// Host-only helper used by the CPU test-suite: lambda_0 of the sparse-group lasso's automatic grid (sgl_host.h) from a given X'y.
+int admm_hip_host_sgl_lambda0(const float* xy, int p, const int* group, const double* group_weight, int ngroups,
+                              const double* l1_weight, double alpha, float* out) {
+    return guarded([&] {
+        ADMM_REQUIRE(xy && out && p > 0, "bad arguments");
+        PathSpec s;
+        s.grouped = s.sgl = true; s.group = group; s.group_weight = group_weight; s.ngroups = ngroups; s.group_cols = p;
+        s.sgl_mix = alpha; s.l1_weight = l1_weight;
+        s.check_sgl_args(p);
+        std::vector<int> start;
+        for (int j = 0; j < p; ++j)
+            if (j == 0 || group[j] != group[j - 1]) start.push_back(j);
+        start.push_back(p);
+        std::vector<double> l1, wg;
+        sgl_prepare(alpha, l1_weight, group_weight, start, l1, wg);
+        *out = sgl_lambda0(xy, start, l1, wg);
     });
 }
 

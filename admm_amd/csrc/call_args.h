@@ -2,6 +2,7 @@
 // handed down as they are.  The solvers keep taking LassoProblem (solvers.h), which PathSpec::problem() fills.
 #pragma once
 #include "solvers.h"
+#include "sgl_host.h"
 
 namespace admm {
 
@@ -17,6 +18,11 @@ struct PathSpec {
     bool grouped = false;
     const int* group = nullptr; const double* group_weight = nullptr; int ngroups = 0;
     int group_cols = 0;                  // p, the length of `group`
+    // sparse-group lasso (admm_hip_sgl): a grouped call with the mixing parameter (its own name: `alpha` above means elastic net, which a
+    // grouped call refuses) and the l1 weight of every column (NULL: all 1)
+    bool sgl = false;
+    double sgl_mix = 0.0;
+    const double* l1_weight = nullptr;
     // multi-task lasso (admm_hip_mtlasso): the number of responses (0: an ordinary call) and the p row weights as the ABI passes them
     int nresp = 0;
     const double* row_weight = nullptr;
@@ -32,8 +38,8 @@ struct PathSpec {
         if (nlambda_in == 0) ADMM_REQUIRE(lmin_ratio > 0 && lmin_ratio < 1, "lambda_min_ratio must be within (0, 1)");
         for (int i = 0; i < nlambda_in; ++i) ADMM_REQUIRE(lambda_in[i] > 0, "lambda must be positive");
     }
-    // ... of a group-lasso call, once check_common has passed (p > 0): ids 0 .. ngroups - 1 in runs, usable weights, n > p
-    void check_groups(int n, int p) const {
+    // ... of a grouped call, once check_common has passed (p > 0): ids 0 .. ngroups - 1 in runs of at most ADMM_HIP_GROUP_MAX
+    void check_group_ids(int p) const {
         ADMM_REQUIRE(group != nullptr, "group must not be NULL");
         ADMM_REQUIRE(group[0] == 0, "group ids must start at 0");
         int run = 1;
@@ -44,6 +50,10 @@ struct PathSpec {
             ADMM_REQUIRE(run <= ADMM_HIP_GROUP_MAX, "a group has more than ADMM_HIP_GROUP_MAX (1024) columns");
         }
         ADMM_REQUIRE(ngroups == group[p - 1] + 1, "ngroups does not match the group ids");
+    }
+    // ... of a group-lasso call: the ids, usable weights, n > p
+    void check_groups(int n, int p) const {
+        check_group_ids(p);
         bool any = group_weight == nullptr;
         for (int g = 0; group_weight != nullptr && g < ngroups; ++g) {
             ADMM_REQUIRE(std::isfinite(group_weight[g]) && group_weight[g] >= 0, "group weights must be finite and non-negative");
@@ -51,6 +61,24 @@ struct PathSpec {
         }
         ADMM_REQUIRE(any, "at least one group weight must be positive");
         ADMM_REQUIRE(n > p, "the group lasso is built for n > p only");
+    }
+    // ... of a sparse-group call: the ids, the mixing parameter in [0, 1], usable weights of both kinds, and a penalty that is not
+    // identically zero (coordinate j of group g is penalised when alpha u_j > 0 or (1 - alpha) w_g > 0)
+    void check_sgl_args(int p) const {
+        check_group_ids(p);
+        ADMM_REQUIRE(std::isfinite(sgl_mix) && sgl_mix >= 0.0 && sgl_mix <= 1.0, "the mixing parameter alpha must be finite and within [0, 1]");
+        for (int g = 0; group_weight != nullptr && g < ngroups; ++g)
+            ADMM_REQUIRE(std::isfinite(group_weight[g]) && group_weight[g] >= 0, "group weights must be finite and non-negative");
+        for (int j = 0; l1_weight != nullptr && j < p; ++j)
+            ADMM_REQUIRE(std::isfinite(l1_weight[j]) && l1_weight[j] >= 0, "l1 weights must be finite and non-negative");
+        bool any = false;
+        for (int j = 0; j < p && !any; ++j)
+            any = sgl_mix * (l1_weight ? l1_weight[j] : 1.0) > 0 || (1.0 - sgl_mix) * (group_weight ? group_weight[group[j]] : 1.0) > 0;
+        ADMM_REQUIRE(any, "at least one coordinate must carry a positive penalty");
+    }
+    void check_sgl(int n, int p) const {
+        check_sgl_args(p);
+        ADMM_REQUIRE(n > p, "the sparse-group lasso is built for n > p only");
     }
     // ... of a multi-task call, once check_common has passed: 1 <= m <= ADMM_HIP_MT_MAX, usable weights, n > p
     void check_mt(int n, int p) const {
@@ -79,7 +107,11 @@ struct PathSpec {
             for (int j = 0; j < group_cols; ++j)
                 if (j == 0 || group[j] != group[j - 1]) pb.group_start.push_back(j);
             pb.group_start.push_back(group_cols);
-            for (int g = 0; g < ngroups; ++g)
+            if (sgl) {                      // (checked: check_sgl) the device's weights, not the caller's
+                pb.sgl = true;
+                sgl_prepare(sgl_mix, l1_weight, group_weight, pb.group_start, pb.l1_weight, pb.group_weight);
+            }
+            for (int g = 0; !sgl && g < ngroups; ++g)
                 pb.group_weight.push_back(group_weight ? group_weight[g] : std::sqrt((double)(pb.group_start[g + 1] - pb.group_start[g])));
         }
         if (nresp > 0) {                    // (checked: check_mt)

@@ -47,9 +47,9 @@ PlanHandle* create_plan(const double* x, const double* y, int n, int p, int mem,
     } else if (nworkers > 0) {
         ADMM_REQUIRE(nworkers <= n, "more row blocks than rows");
     }
-    if (spec.grouped) {                                     // admm_hip_grplasso: the tall solver on one device, nothing else
+    if (spec.grouped) {                                     // admm_hip_grplasso, admm_hip_sgl: the tall solver on one device, nothing else
         ADMM_REQUIRE(shard.kind == Shard::NONE && nworkers <= 0 && !spec.enet(), "the group lasso has no sharded, consensus or elastic-net form");
-        spec.check_groups(n, p);
+        if (spec.sgl) spec.check_sgl(n, p); else spec.check_groups(n, p);
         ADMM_REQUIRE(!opt_on(Opt::REFINE), "the group lasso has no refined x-update: unset REFINE");
     }
     if (spec.nresp != 0) {                                  // admm_hip_mtlasso: the tall solver on one device, nothing else (y is Y, n x m)

@@ -41,6 +41,7 @@
 #include "gemv_kernels.h"
 #include "symv_kernels.h"
 #include "solvers.h"
+#include "sgl_host.h"
 #include "comm.h"
 #include "loop_driver.h"
 #include "plan_host.h"
@@ -383,14 +384,22 @@ tall_tail_kernel(TallParams q, int par, PeerExchange ex) {
 // coordinates' v go through LDS.  Norms are sums of (double) v^2 in a fixed order: no atomics, the same bits from run to run.
 // A group of ONE column takes the Lasso's scalar soft-threshold (tall_update_elem) bit for bit, so singleton groups of weight 1
 // reproduce admm_hip_lasso exactly (the tiles are then tall_tail_kernel's workgroups, the norm partials P the same sums).
+//
+// SPARSE (admm_hip_sgl): the prox of lambda (alpha sum_j u_j |b_j| + (1 - alpha) sum_g w_g ||b_g||_2) is the element-wise soft-threshold
+// followed by the block one, so a group of several columns stores  s_j = soft(v_j, lambda l1_j / rho)  (the Lasso's double compare and
+// rounding) where the plain form stores v_j, and everything after the first half -- the norm, the shrink, the six norm partials, the
+// next right-hand sides -- is the same code on s.  The owner lane loads l1_j (sgl_host.h: alpha u_j; alpha never reaches the device)
+// beside the coordinate's other loads: its address needs neither `c` nor more of the tile entry than those do, so the kernel is still
+// one memory round trip per pass.  A one-column group keeps v and takes the scalar threshold with GroupCoord.w = l1_j + wg_g.
 struct GroupCoord { int gs, gn; double w; };      // per coordinate: first column, size and weight of its group
 struct GroupTailParams {
     const int2* tiles;                            // [TallParams.nwg]  (first coordinate, number of coordinates)
     const GroupCoord* coord;                      // [p]
+    const double* l1;                             // [p] element-wise threshold weights (SPARSE only; NULL otherwise)
 };
 constexpr int kGroupMax = ADMM_HIP_GROUP_MAX;
 
-template <int MODE>
+template <int MODE, bool SPARSE = false>
 __global__ void __launch_bounds__(kTailThreads)
 tall_group_tail_kernel(TallParams q, int par, GroupTailParams gp) {
 #pragma clang fp contract(off)
@@ -415,6 +424,8 @@ tall_group_tail_kernel(TallParams q, int par, GroupTailParams gp) {
         const bool valid = s < cnt, owner = valid && sub == 0;
         TallElem el = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
         if (owner) el = tall_load_elem(q, par, i);
+        double l1 = 0.0;
+        if (SPARSE && owner) l1 = gp.l1[i];
         float a = 0.f, b = 0.f;
         if (MODE == TAIL_SYMV) {
             symv_sum_partials<kTailLanes>(q.dot0, q.dot1, q.axp0, q.axp1, q.ldo, q.nrb, q.sched, q.p32, i, sub, valid, a, b);
@@ -442,7 +453,12 @@ tall_group_tail_kernel(TallParams q, int par, GroupTailParams gp) {
                         x = a;
                     }
                 } else { adjz = el.adjz; adjy = el.adjy; x = el.x; }
-                sx[s] = x; sadjz[s] = adjz; sadjy[s] = adjy; sv[s] = x + adjy / rho_f;
+                float vec = x + adjy / rho_f;
+                if (SPARSE && gc.gn > 1) {                              // s = soft(v, lambda l1 / rho): the Lasso's soft_threshold
+                    const double v = (double)vec, pen1 = c.lam * l1 / c.rho;
+                    vec = v > pen1 ? (float)(v - pen1) : (v < -pen1 ? (float)(v + pen1) : 0.f);
+                }
+                sx[s] = x; sadjz[s] = adjz; sadjy[s] = adjy; sv[s] = vec;
                 szc[s] = el.zc; syc[s] = el.yc; sxy[s] = el.xy;
             }
         }
@@ -450,7 +466,7 @@ tall_group_tail_kernel(TallParams q, int par, GroupTailParams gp) {
     if (c.done) return;
     __syncthreads();
 
-    // ---- squared norm of this lane's group, in double, in a fixed order
+    // ---- squared norm of this lane's group (SPARSE: of s), in double, in a fixed order
     double nrm2 = 0.0;
     if (big) {
         if (sub == 0) {
@@ -750,6 +766,7 @@ struct TallPlan final : LassoPlan {
     bool grouped = false;
     DevBuf<int2> gtiles;
     DevBuf<GroupCoord> gcoord;
+    DevBuf<double> gl1;                                 // sparse-group lasso (LassoProblem.sgl): the l1 weight of every column
     GroupTailParams gq{};
     // multi-task lasso (LassoProblem.nresp): every vector is nresp planes, the x-update passes of symvn_lower_kernel, the tail tall_mt_tail_kernel
     int mt = 0;                                         // responses (0: not a multi-task problem)
@@ -804,7 +821,8 @@ struct TallPlan final : LassoPlan {
         grouped = !pb.group_start.empty();
         ADMM_REQUIRE(!grouped || (!shard && !pb.enet && !opt_on(Opt::REFINE) && (int)pb.group_start.size() == (int)pb.group_weight.size() + 1 &&
                                   pb.group_start.back() == p), "internal: the group lasso is the plain single-device tall solver");
-        float lambda0 = grouped ? group_lambda0() : (mt ? mt_lambda0() : device_absmax<float>(XY.get(), p, st));
+        ADMM_REQUIRE(pb.sgl ? grouped && (int)pb.l1_weight.size() == p : pb.l1_weight.empty(), "internal: l1 weights belong to the sparse-group lasso");
+        float lambda0 = grouped ? (pb.sgl ? sgl_plan_lambda0() : group_lambda0()) : (mt ? mt_lambda0() : device_absmax<float>(XY.get(), p, st));
         if (pb.enet) lambda0 = (float)(lambda0 / ((double)(float)pb.alpha + 0.0001));
 
         // lambda grid (Lasso.cpp:78-89) and internal lambdas (Lasso.cpp:99), stored as float like `Scalar lambda`
@@ -1076,17 +1094,36 @@ struct TallPlan final : LassoPlan {
         return (float)best;
     }
 
+    // ... of the sparse-group lasso: the largest lambda_g over the groups, lambda_g the smallest lambda whose two-level prox empties
+    // group g started from X'y (sgl_host.h; alpha = 0: group_lambda0's value, alpha = 1 with unit weights: device_absmax's)
+    float sgl_plan_lambda0() {
+        std::vector<float> h(p);
+        read_back(h.data(), XY.get(), (size_t)p * sizeof(float), st);
+        return sgl_lambda0(h.data(), pb.group_start, pb.l1_weight, pb.group_weight);
+    }
+
     // Whole groups into tiles for tall_group_tail_kernel: consecutive groups while they total at most kTailElems coordinates; a
     // larger group alone.  Returns the number of tiles (workgroups of the tail).
+    // A sparse-group call in which NO group carries a block weight (alpha = 1, or every w_g = 0) has no block structure left: shrink is
+    // exactly 1 in every group, so each column is a one-column group of weight l1_j to the bit, and it is packed as such -- the Lasso
+    // with penalty factors on the Lasso tail's own tiles (32 consecutive coordinates, hence its norm partials and its decision trace
+    // byte for byte), without the norms and without a multi-pass workgroup for a large group.  As soon as one group has a block weight
+    // the groups are packed as admm_hip_grplasso packs them, zero-weight groups included.
     int pack_group_tiles() {
         std::vector<int2> tiles;
         std::vector<GroupCoord> coord(p);
+        const bool flat = pb.sgl && std::none_of(pb.group_weight.begin(), pb.group_weight.end(), [](double w) { return w > 0; });
+        std::vector<int> each;
+        if (flat) for (int j = 0; j <= p; ++j) each.push_back(j);
+        const std::vector<int>& start = flat ? each : pb.group_start;
         int first = 0, count = 0;
         const auto flush = [&] { if (count > 0) tiles.push_back(make_int2(first, count)); first += count; count = 0; };
-        for (size_t g = 0; g + 1 < pb.group_start.size(); ++g) {
-            const int gs = pb.group_start[g], gn = pb.group_start[g + 1] - gs;
+        for (size_t g = 0; g + 1 < start.size(); ++g) {
+            const int gs = start[g], gn = start[g + 1] - gs;
+            const double wg = flat ? 0.0 : pb.group_weight[g];
             ADMM_REQUIRE(gn >= 1 && gn <= kGroupMax && gs == first + count, "internal: bad group partition");
-            for (int j = gs; j < gs + gn; ++j) coord[j] = GroupCoord{gs, gn, pb.group_weight[g]};
+            for (int j = gs; j < gs + gn; ++j)
+                coord[j] = GroupCoord{gs, gn, pb.sgl && gn == 1 ? sgl_single_weight(pb.l1_weight[j], wg) : wg};
             if (count + gn > kTailElems) flush();
             count += gn;
             if (gn > kTailElems) flush();
@@ -1095,8 +1132,12 @@ struct TallPlan final : LassoPlan {
         gtiles.alloc(tiles.size()); gcoord.alloc(coord.size());
         ADMM_HIP_CHECK(hipMemcpyAsync(gtiles.get(), tiles.data(), tiles.size() * sizeof(int2), hipMemcpyHostToDevice, st));
         ADMM_HIP_CHECK(hipMemcpyAsync(gcoord.get(), coord.data(), coord.size() * sizeof(GroupCoord), hipMemcpyHostToDevice, st));
+        if (pb.sgl) {
+            gl1.alloc((size_t)p);
+            ADMM_HIP_CHECK(hipMemcpyAsync(gl1.get(), pb.l1_weight.data(), (size_t)p * sizeof(double), hipMemcpyHostToDevice, st));
+        }
         comm_stream_sync(st);                           // (the host vectors go out of scope)
-        gq.tiles = gtiles.get(); gq.coord = gcoord.get();
+        gq.tiles = gtiles.get(); gq.coord = gcoord.get(); gq.l1 = pb.sgl ? gl1.get() : nullptr;
         return (int)tiles.size();
     }
 
@@ -1183,11 +1224,13 @@ struct TallPlan final : LassoPlan {
             } else if (grouped) {                      // two launches, as the Lasso: the x-update with the decision, the group tail
                 if (use_sym) {
                     sy.launch(M.get(), ldp, u.get(), w.get(), &ctl.get()[par].done, st, dec, e0, e1, vd);
-                    hipLaunchKernelGGL(tall_group_tail_kernel<TAIL_SYMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, gq);
+                    if (pb.sgl) hipLaunchKernelGGL((tall_group_tail_kernel<TAIL_SYMV, true>), dim3(nwg), dim3(kTailThreads), 0, st, q, par, gq);
+                    else hipLaunchKernelGGL(tall_group_tail_kernel<TAIL_SYMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, gq);
                 } else {
                     launch_gemv_t<float, 2, 4, TallDecideExtra>(pl, M.get(), ldp, p, p, u.get(), w.get(), a_part.get(), b_part.get(), ldp,
                                                                 &ctl.get()[par].done, st, dec, e0, e1);
-                    hipLaunchKernelGGL(tall_group_tail_kernel<TAIL_GEMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, gq);
+                    if (pb.sgl) hipLaunchKernelGGL((tall_group_tail_kernel<TAIL_GEMV, true>), dim3(nwg), dim3(kTailThreads), 0, st, q, par, gq);
+                    else hipLaunchKernelGGL(tall_group_tail_kernel<TAIL_GEMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, gq);
                 }
             } else if (shard && peer_fused) {
                 // this rank's tiles -> its share of (a, b) written into every rank's exchange slot by the reduction

@@ -23,6 +23,9 @@ struct LassoProblem {
     // penalised by group_weight[g] * its Euclidean norm; empty = no groups
     std::vector<int> group_start;
     std::vector<double> group_weight;
+    // sparse-group lasso (admm_hip_sgl; sgl_host.h): group_weight holds wg_g = (1 - alpha) w_g and l1_weight [p] l1_j = alpha u_j
+    bool sgl = false;
+    std::vector<double> l1_weight;
     // multi-task lasso (admm_hip_mtlasso, tall solver only): nresp responses share the design (DeviceData.Ymt), row j of the p x nresp
     // coefficient matrix is penalised by row_weight[j] * its Euclidean norm; 0 = an ordinary single-response problem
     int nresp = 0;

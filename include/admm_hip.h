@@ -308,6 +308,38 @@ ADMM_HIP_API int admm_hip_grplasso_plan_create(const double* x, const double* y,
                                                int standardize, int intercept, const admm_opts* opts,
                                                admm_hip_plan** plan_out, int* nlambda_out);
 
+/* Sparse-group lasso on the tall path (n > p only; not in the reference package; Simon, Friedman, Hastie and Tibshirani 2013, the R
+ * packages SGL and sparsegl): groups are selected and so are coefficients inside the groups that stay,
+ *     minimise 1/2 ||y_s - X_s b||^2 + lambda_int [ alpha sum_j u_j |b_j| + (1 - alpha) sum_g w_g ||b_g||_2 ]
+ * in the solver's internal units, as admm_hip_grplasso.  The iteration is the group lasso's with the z-update  soft-threshold every
+ * coordinate by lambda alpha u_j / rho, then block soft-threshold every group by lambda (1 - alpha) w_g / rho  (the exact prox of the
+ * sum; lasso_tall.hip, tall_group_tail_kernel<., true>); the lambda path, the stopping rule, niter and the outputs are admm_hip_lasso's.
+ * group, group_weight, ngroups: as admm_hip_grplasso (group_weight NULL = sqrt(group size); a weight of 0 leaves only the l1 part).
+ * l1_weight[p] >= 0: one l1 weight per column, NULL = all 1.  0 <= alpha <= 1.  Coordinate j of group g is unpenalised when
+ * alpha u_j = 0 and (1 - alpha) w_g = 0; a call in which no coordinate carries a positive penalty is refused.
+ * alpha = 0 is admm_hip_grplasso bit for bit (grid, coefficients, niter, decision trace).  alpha = 1 is the Lasso with the penalty
+ * factors u on the tall path: with u = 1 it is admm_hip_lasso bit for bit for any grouping, and with a general u
+ * admm_hip_grplasso on one-column groups of weights u.  (A call in which no group carries a block weight -- alpha = 1, or every
+ * w_g = 0 -- has no block structure left and runs on the Lasso tail's tiling, every column a one-column group of weight alpha u_j.)
+ * Limits as admm_hip_grplasso: groups of at most ADMM_HIP_GROUP_MAX columns, single device; no row-sharded, consensus, elastic-net,
+ * refined (REFINE set: refused), cross-validated or multi-response form.
+ * Automatic grid: lambda_0 = max_g lambda_g, lambda_g the smallest lambda at which the prox empties group g started from c = X_s'y_s:
+ * the root of  sum_{j in g} max(|c_j| - lambda alpha u_j, 0)^2 = ((1 - alpha) w_g lambda)^2 , solved exactly over its breakpoints
+ * (sgl_host.h); groups that no lambda empties are left out.  With unpenalised coordinates present the first lambda of that grid is
+ * NOT guaranteed to give an empty penalised model (the unpenalised columns have not been fitted when lambda_0 is taken): pass a
+ * grid of your own there.
+ * The plan is an ordinary admm_hip_plan: admm_hip_lasso_plan_run / _trace_* / _state_* / _destroy work on it. */
+ADMM_HIP_API int admm_hip_sgl(const double* x, const double* y, int n, int p, int mem,
+                              const int* group, const double* group_weight, int ngroups, const double* l1_weight, double alpha,
+                              const double* lambda_in, int nlambda_in, int nlambda_auto, double lmin_ratio,
+                              int standardize, int intercept, const admm_opts* opts,
+                              double* lambda_out, float* beta_out, int* niter_out, admm_stats* stats);
+ADMM_HIP_API int admm_hip_sgl_plan_create(const double* x, const double* y, int n, int p, int mem,
+                                          const int* group, const double* group_weight, int ngroups, const double* l1_weight, double alpha,
+                                          const double* lambda_in, int nlambda_in, int nlambda_auto, double lmin_ratio,
+                                          int standardize, int intercept, const admm_opts* opts,
+                                          admm_hip_plan** plan_out, int* nlambda_out);
+
 /* Multi-task lasso on the tall path (n > p only; not in the reference package; glmnet's family = "mgaussian", scikit-learn's
  * MultiTaskLasso): m responses on one design, one row-wise penalty that selects a feature for all responses at once,
  *     minimise over b0 (m), B (p x m):  1/(2n) ||Y - 1 b0' - X B||_F^2 + lambda sum_j w_j ||B_j.||_2 ,
@@ -550,6 +582,11 @@ ADMM_HIP_API int admm_hip_device_synchronize(void);
 /* The host logic of the loose Lanczos call (ADMMLassoTall.h:196-201 -> SymEigsSolver.h) against a dense symmetric
  * float matrix in HOST memory (n x n, column-major).  Runs without a GPU (CPU test-suite). */
 ADMM_HIP_API int admm_hip_host_lanczos(const float* A, int n, float* eig_out, int* nmatop_out);
+
+/* lambda_0 of admm_hip_sgl's automatic grid from a given c = X_s'y_s (xy, HOST, length p), arguments as admm_hip_sgl: the host
+ * routine the plan calls (sgl_host.h).  Runs without a GPU (CPU test-suite). */
+ADMM_HIP_API int admm_hip_host_sgl_lambda0(const float* xy, int p, const int* group, const double* group_weight, int ngroups,
+                                           const double* l1_weight, double alpha, float* out);
 
 /* The tall x-update mat-vec exactly as the solver runs it for p >= 2048: symv2_lower_kernel on the lower triangle of
  * the symmetric p x p float matrix A (HOST, column-major, leading dimension p) against the two right-hand sides

@@ -124,6 +124,34 @@ BEGIN_RCPP
 END_RCPP
 }
 
+// Sparse-group lasso (not in the reference; include/admm_hip.h, admm_hip_sgl): the arguments of admm_grplasso plus `l1_weight`, one l1
+// weight per column or numeric(0) for all 1, and the mixing parameter `alpha` in [0, 1] (0 = group lasso, 1 = Lasso with penalty
+// factors l1_weight).  n > p only.
+RcppExport SEXP admm_sgl(SEXP x_, SEXP y_, SEXP lambda_, SEXP nlambda_, SEXP lmin_ratio_,
+                         SEXP standardize_, SEXP intercept_, SEXP group_, SEXP group_weight_, SEXP l1_weight_, SEXP alpha_, SEXP opts_) {
+BEGIN_RCPP
+    NumericMatrix x(x_);
+    NumericVector y(y_), lambda(lambda_), group_weight(group_weight_), l1_weight(l1_weight_);
+    IntegerVector group(group_);
+    const int n = x.nrow(), p = x.ncol();
+    if (group.size() != p) Rcpp::stop("group should have length ncol(x)");
+    const int ngroups = p > 0 ? group[p - 1] + 1 : 0;
+    if (group_weight.size() != 0 && group_weight.size() != ngroups) Rcpp::stop("group_weight should have one entry per group");
+    if (l1_weight.size() != 0 && l1_weight.size() != p) Rcpp::stop("l1_weight should have one entry per column");
+    const int nl_in = lambda.size();
+    const int nl = nl_in > 0 ? nl_in : as<int>(nlambda_);
+    admm_opts o = unpack_opts(opts_);
+    NumericVector lambda_out(nl);
+    IntegerVector niter(nl);
+    std::vector<float> beta((size_t)(p + 1) * nl);
+    check(admm_hip_sgl(x.begin(), y.begin(), n, p, ADMM_MEM_HOST, group.begin(), group_weight.size() ? group_weight.begin() : nullptr, ngroups,
+                       l1_weight.size() ? l1_weight.begin() : nullptr, as<double>(alpha_),
+                       nl_in > 0 ? lambda.begin() : nullptr, nl_in, as<int>(nlambda_), as<double>(lmin_ratio_),
+                       as<bool>(standardize_), as<bool>(intercept_), &o, lambda_out.begin(), beta.data(), niter.begin(), nullptr));
+    return List::create(Named("lambda") = lambda_out, Named("beta") = to_dgCMatrix(beta, p + 1, nl), Named("niter") = niter);
+END_RCPP
+}
+
 // Multi-task lasso (not in the reference; include/admm_hip.h, admm_hip_mtlasso): the arguments of admm_lasso with an n x m matrix Y
 // in the place of y, plus `row_weight`, one weight per column of x or numeric(0) for all 1.  n > p only, m <= ADMM_HIP_MT_MAX.
 // beta: a (p + 1) x (m * nlambda) dgCMatrix, column l * m + k = response k at lambda l (intercept first).

@@ -1,11 +1,13 @@
 #!/usr/bin/env python
-"""Dev tool (GPU box): the group lasso's ADMM rate beside the Lasso's on the same data and build (device-resident inputs).
+"""Dev tool (GPU box): the group lasso's and the sparse-group lasso's ADMM rates beside the Lasso's on the same data and build
+(device-resident inputs).
 
-    bench_grplasso.py [--n 100000] [--p 10000] [--group-size 4] [--big-group 0] [--nlambda 100] [--steps 3] [--warmup 1]
+    bench_grplasso.py [--n 100000] [--p 10000] [--group-size 4] [--big-group 0] [--alpha 0.5] [--nlambda 100] [--steps 3] [--warmup 1]
 
-Both models are prepared once (LassoPlan) and every step is one cold-started warm-chained lambda path; the rate is
+The models are prepared once (LassoPlan) and every step is one cold-started warm-chained lambda path; the rate is
 iterations / loop time as the library reports them (admm_stats.total_iter, t_loop), the median over the steps.  The x-update is the
-same kernel in both, so the gap between the two rates is the tail's (tall_group_tail_kernel against tall_tail_kernel).
+same kernel in all three, so the gaps between the rates are the tails' (tall_group_tail_kernel, plain and sparse, against
+tall_tail_kernel).  --alpha A: the mixing parameter of the sparse form (admm_sgl, l1 weights uniform in [0.5, 2]).
 --big-group G: instead of equal groups, ONE group of G columns (<= 1024) among singletons -- the cost of the multi-pass workgroup.
 Prints one JSON line."""
 import argparse
@@ -17,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 import torch  # noqa: E402  (before libadmm_hip: one HIP runtime per process)
 import numpy as np  # noqa: E402
-from admm_amd import DevicePtr, admm_grplasso, admm_lasso  # noqa: E402
+from admm_amd import DevicePtr, admm_grplasso, admm_lasso, admm_sgl  # noqa: E402
 from admm_amd.api import LassoPlan  # noqa: E402
 
 ap = argparse.ArgumentParser()
@@ -25,6 +27,7 @@ ap.add_argument("--n", type=int, default=100000)
 ap.add_argument("--p", type=int, default=10000)
 ap.add_argument("--group-size", type=int, default=4)
 ap.add_argument("--big-group", type=int, default=0)
+ap.add_argument("--alpha", type=float, default=0.5)
 ap.add_argument("--nlambda", type=int, default=100)
 ap.add_argument("--steps", type=int, default=3)
 ap.add_argument("--warmup", type=int, default=1)
@@ -48,6 +51,7 @@ if a.big_group > 0:
     group = np.concatenate([np.zeros(a.big_group, dtype=np.int64), 1 + np.arange(p - a.big_group)])
 else:
     group = np.arange(p) // a.group_size
+l1_weights = np.random.default_rng(6).uniform(0.5, 2.0, p)
 xp, yp = DevicePtr(xt.data_ptr()), DevicePtr(y.data_ptr())
 
 
@@ -68,5 +72,6 @@ def rate(model):
 out = {"n": n, "p": p, "nlambda": a.nlambda, "steps": a.steps,
        "groups": f"one group of {a.big_group} among singletons" if a.big_group > 0 else f"groups of {a.group_size}",
        "grplasso": rate(admm_grplasso(xp, yp, group, n=n, p=p).penalty(nlambda=a.nlambda)),
+       "sgl": dict(rate(admm_sgl(xp, yp, group, alpha=a.alpha, n=n, p=p).penalty(nlambda=a.nlambda, l1_weights=l1_weights)), alpha=a.alpha),
        "lasso": rate(admm_lasso(xp, yp, n=n, p=p).penalty(nlambda=a.nlambda))}
 print(json.dumps(out))
