@@ -76,7 +76,8 @@ EXPORTS = ["admm_hip_lasso", "admm_hip_enet", "admm_hip_parlasso", "admm_hip_lad
            "admm_hip_last_parallel_layout", "admm_hip_parallel_assign", "admm_hip_grplasso", "admm_hip_grplasso_plan_create",
            "admm_hip_quantreg", "admm_hip_quantreg_state",
            "admm_hip_mtlasso", "admm_hip_mtlasso_plan_create", "admm_hip_test_symv_multi", "admm_hip_test_tall_early_exits",
-           "admm_hip_sgl", "admm_hip_sgl_plan_create", "admm_hip_host_sgl_lambda0"]
+           "admm_hip_sgl", "admm_hip_sgl_plan_create", "admm_hip_host_sgl_lambda0",
+           "admm_hip_test_gemm_nt", "admm_hip_test_cholesky_linvt", "admm_hip_test_spd_inverse_shift"]
 
 GROUP_MAX = 1024          # ADMM_HIP_GROUP_MAX
 MT_MAX = 16               # ADMM_HIP_MT_MAX
@@ -252,6 +253,12 @@ def load():
     lib.admm_hip_test_gemv_t.restype = ctypes.c_int
     lib.admm_hip_test_spd_inverse.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
     lib.admm_hip_test_spd_inverse.restype = ctypes.c_int
+    lib.admm_hip_test_spd_inverse_shift.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_void_p]
+    lib.admm_hip_test_spd_inverse_shift.restype = ctypes.c_int
+    lib.admm_hip_test_cholesky_linvt.argtypes = [ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]
+    lib.admm_hip_test_cholesky_linvt.restype = ctypes.c_int
+    lib.admm_hip_test_gemm_nt.argtypes = [ctypes.c_int] * 9 + [ctypes.c_double, ctypes.c_double, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
+    lib.admm_hip_test_gemm_nt.restype = ctypes.c_int
     lib.admm_hip_test_cv_fold_system.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int,
                                                  ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
     lib.admm_hip_test_cv_fold_system.restype = ctypes.c_int

@@ -593,6 +593,40 @@ int admm_hip_test_spd_inverse(const void* A, int n, int precision, void* Ainv) {
     });
 }
 
+int admm_hip_test_spd_inverse_shift(const float* A, int n, double diag, float* Ainv) {
+    return guarded([&] {
+        ADMM_REQUIRE(A && Ainv && n > 0 && std::isfinite(diag), "bad arguments");
+        test_spd_inverse_shift(A, n, diag, Ainv);
+    });
+}
+
+int admm_hip_test_cholesky_linvt(int is_double, const void* A, int n, void* L, void* U) {
+    return guarded([&] {
+        ADMM_REQUIRE(A && L && U && n > 0, "bad arguments");
+        if (is_double) test_cholesky_linvt<double>(static_cast<const double*>(A), n, static_cast<double*>(L), static_cast<double*>(U));
+        else test_cholesky_linvt<float>(static_cast<const float*>(A), n, static_cast<float*>(L), static_cast<float*>(U));
+    });
+}
+
+int admm_hip_test_gemm_nt(int is_double, int lower, int mirror, int kstart_row, int b_lower, int in_place, int M, int N, int K,
+                          double alpha, double beta, const void* A, const void* B, void* C) {
+    return guarded([&] {
+        ADMM_REQUIRE(A && B && C, "gemm_nt hook: A, B and C must not be NULL");
+        ADMM_REQUIRE(M > 0 && N > 0 && K > 0 && M <= 16384 && N <= 16384 && K <= (1 << 20), "gemm_nt hook: M, N in 1 .. 16384 and K in 1 .. 2^20");
+        ADMM_REQUIRE(std::isfinite(alpha) && std::isfinite(beta), "gemm_nt hook: alpha and beta must be finite");
+        ADMM_REQUIRE(!lower || M == N, "gemm_nt hook: lower needs a square output (M == N)");
+        ADMM_REQUIRE(!mirror || lower, "gemm_nt hook: the mirrored store belongs to lower launches");
+        ADMM_REQUIRE(!b_lower || (is_double && !lower), "gemm_nt hook: b_lower (the K loop ended at the tile's last column) is double only and not for lower launches");
+        ADMM_REQUIRE(!in_place || (N <= 128 && K == 128 && !lower), "gemm_nt hook: in_place needs N <= 128, K == 128 and a full (not lower) launch");
+        if (is_double)
+            test_gemm_nt<double>(lower != 0, mirror != 0, kstart_row != 0, b_lower != 0, in_place != 0, M, N, K, alpha, beta, static_cast<const double*>(A),
+                                 static_cast<const double*>(B), static_cast<double*>(C));
+        else
+            test_gemm_nt<float>(lower != 0, mirror != 0, kstart_row != 0, false, in_place != 0, M, N, K, alpha, beta, static_cast<const float*>(A),
+                                static_cast<const float*>(B), static_cast<float*>(C));
+    });
+}
+
 int admm_hip_test_cv_fold_system(const double* x, const double* y, int n, int p, const int* fold_id, int nfolds, int fold,
                                  int standardize, int intercept, float* gram, float* xy, float* mean_x, float* scale_x, float* mean_scale_y) {
     return guarded([&] { test_cv_fold_system(x, y, n, p, fold_id, nfolds, fold, standardize, intercept, gram, xy, mean_x, scale_x, mean_scale_y); });

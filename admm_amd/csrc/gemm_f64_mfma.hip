@@ -319,4 +319,10 @@ void gemm_nt_f64(const double* A, long long lda, const double* B, long long ldb,
     launch_gemm_nt_f64(false, A, lda, B, ldb, C, ldc, M, N, K, 1.0, 0.0, false, false, st, b_lower);
 }
 
+// Test hook (test_hooks.hip): one launch of the NT-GEMM through the launcher above, every argument the callers in this file vary.
+void test_launch_gemm_nt_f64(bool lower, const double* A, long long lda, const double* B, long long ldb, double* C, long long ldc,
+                             int M, int N, int K, double alpha, double beta, bool mirror, bool kstart_row, bool kend_col, hipStream_t st) {
+    launch_gemm_nt_f64(lower, A, lda, B, ldb, C, ldc, M, N, K, alpha, beta, mirror, kstart_row, st, kend_col);
+}
+
 }  // namespace admm

@@ -133,6 +133,7 @@ void spd_inverse_mfma_f64(double* A, long long lda, int n, hipStream_t st);
 void spd_inverse_f64(double* A, long long lda, int n, hipStream_t st);
 // A -> Cholesky factor L in place (lower); returns U = L^-T (lda x round_up(n, 128), upper triangular, zero padded).
 DevBuf<double> cholesky_linvt_mfma_f64(double* A, long long lda, int n, hipStream_t st);
+DevBuf<float> cholesky_linvt_mfma_f32(float* A, long long lda, int n, hipStream_t st);      // (syrk_mfma.hip; the factor test hook only)
 // C (M x N) = A B' for operands with the output index contiguous (rows readable up to the next multiple of 128, K % 8 == 0).
 // b_lower: B is lower triangular (B[j, k] = 0 for k > j, zero padded) -- the K loop of a tile ends at its last column: same bits, half the flops
 void gemm_nt_f64(const double* A, long long lda, const double* B, long long ldb, double* C, long long ldc, int M, int N, int K, hipStream_t st, bool b_lower = false);

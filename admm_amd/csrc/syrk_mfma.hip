@@ -540,6 +540,16 @@ void spd_inverse_mfma_f32(float* A, long long lda, int p, hipStream_t st) {
     spd_inverse_blocked<float>(A, lda, p, st, launch_gemm_nt_f32);
 }
 
+// Test hooks (test_hooks.hip): the factor L (lower, in place) with U = L^-T returned, and one launch of the NT-GEMM, both through
+// the launcher above exactly as the inverse calls it.
+DevBuf<float> cholesky_linvt_mfma_f32(float* A, long long lda, int n, hipStream_t st) {
+    return cholesky_linvt_blocked<float>(A, lda, n, st, launch_gemm_nt_f32);
+}
+void test_launch_gemm_nt_f32(bool lower, const float* A, long long lda, const float* B, long long ldb, float* C, long long ldc,
+                             int M, int N, int K, float alpha, float beta, bool mirror, bool kstart_row, hipStream_t st) {
+    launch_gemm_nt_f32(lower, A, lda, B, ldb, C, ldc, M, N, K, alpha, beta, mirror, kstart_row, st);
+}
+
 // The same with the block columns of the factorisation dealt out to the ranks of the attached communicator (chol_inverse.h,
 // cholesky_linvt_blocked_dist) and, of the inverse U U', only the lower 128 x 128 tiles listed in `need` (bi << 16 | bj): the tiles
 // this rank's share of the sharded x-update reads.  Everything a rank computes is bit-identical to the single-process result.

@@ -7,6 +7,10 @@ void test_symv(const float* A, int p, const float* v0, const float* v1, float* y
 void test_symv_multi(const float* A, int p, const float* V, int nr, int rhs_per_pass, float* Yout);
 template <typename T> void test_gram(const T* A, int rows, int cols, bool atA, T* G);
 template <typename T> void test_spd_inverse(const T* A, int n, T* Ainv, bool via64);
+void test_spd_inverse_shift(const float* A, int n, double diag, float* Ainv);
+template <typename T> void test_cholesky_linvt(const T* A, int n, T* L, T* U);
+template <typename T> void test_gemm_nt(bool lower, bool mirror, bool kstart_row, bool b_lower, bool in_place, int M, int N, int K, double alpha, double beta,
+                                        const T* A, const T* B, T* C);
 template <typename T> void test_gemv_t(const T* A, int rows, int cols, const T* v, T* y);
 template <typename T> void test_gather(const T* A, int rows, int cols, const T* v, double* y);
 void test_cv_fold_system(const double* x, const double* y, int n, int p, const int* fold_id, int nfolds, int fold,

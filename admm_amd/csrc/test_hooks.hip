@@ -3,6 +3,8 @@
 #include "symv_kernels.h"
 #include "prep.h"
 #include "gather_kernels.h"
+#include <cstring>
+#include <limits>
 #include <vector>
 
 namespace admm {
@@ -183,5 +185,93 @@ void test_spd_inverse(const T* A, int n, T* Ainv, bool via64) {
 }
 template void test_spd_inverse<float>(const float*, int, float*, bool);
 template void test_spd_inverse<double>(const double*, int, double*, bool);
+
+// (A + diag I)^-1 of a float matrix through spd_inverse_f32_via_f64 with the caller's shift (the tall path's rho, added in float).
+void test_spd_inverse_shift(const float* A, int n, double diag, float* Ainv) {
+    require_device();
+    Stream st;
+    const long long lda = round_up(n, 128);
+    DevBuf<float> dA((size_t)lda * lda);
+    dA.zero(st.s);
+    ADMM_HIP_CHECK(hipMemcpy2DAsync(dA.get(), lda * sizeof(float), A, (size_t)n * sizeof(float), (size_t)n * sizeof(float), n, hipMemcpyHostToDevice, st.s));
+    spd_inverse_f32_via_f64(dA.get(), lda, n, diag, st.s);
+    ADMM_HIP_CHECK(hipMemcpy2DAsync(Ainv, (size_t)n * sizeof(float), dA.get(), lda * sizeof(float), (size_t)n * sizeof(float), n, hipMemcpyDeviceToHost, st.s));
+    st.sync();
+}
+
+// The blocked factorisation alone (chol_inverse.h, cholesky_linvt_blocked through the solvers' launchers): L = the overwritten A
+// (order n, ld n: the factor in the lower triangle, the strict upper triangle as the caller gave it) and U = L^-T (order n, ld n).
+template <typename T>
+void test_cholesky_linvt(const T* A, int n, T* L, T* U) {
+    require_device();
+    Stream st;
+    const long long lda = round_up(n, 128);
+    DevBuf<T> dA((size_t)lda * lda);
+    dA.zero(st.s);
+    ADMM_HIP_CHECK(hipMemcpy2DAsync(dA.get(), lda * sizeof(T), A, (size_t)n * sizeof(T), (size_t)n * sizeof(T), n, hipMemcpyHostToDevice, st.s));
+    DevBuf<T> dU;
+    if constexpr (std::is_same<T, float>::value) dU = cholesky_linvt_mfma_f32(dA.get(), lda, n, st.s);
+    else dU = cholesky_linvt_mfma_f64(dA.get(), lda, n, st.s);
+    ADMM_HIP_CHECK(hipMemcpy2DAsync(L, (size_t)n * sizeof(T), dA.get(), lda * sizeof(T), (size_t)n * sizeof(T), n, hipMemcpyDeviceToHost, st.s));
+    ADMM_HIP_CHECK(hipMemcpy2DAsync(U, (size_t)n * sizeof(T), dU.get(), lda * sizeof(T), (size_t)n * sizeof(T), n, hipMemcpyDeviceToHost, st.s));
+    st.sync();
+}
+template void test_cholesky_linvt<float>(const float*, int, float*, float*);
+template void test_cholesky_linvt<double>(const double*, int, double*, double*);
+
+// One launch of the NT-GEMM of the factorisation / inverse / Gram (syrk_mfma.hip, gemm_f64_mfma.hip): C = alpha A B' + beta C.
+// Host operands column-major with the output index contiguous and tight leading dimensions (A: M x K, B: N x K, C: M x N); on the
+// device they are stored as the callers keep them: leading dimension round_up(., 128), K padded with zero columns to the K tile.
+// in_place: the device copy of A is C as well (the factorisation's U[:, k] <- U[:, k] L_kk^-T: N <= 128, K = 128; the host C is
+// only written).  Everything of the device C outside M x N -- a NaN guard band up to the padded storage, or the rest of A when in
+// place -- must come back as it was: ADMM_ERR_INTERNAL otherwise.
+void test_launch_gemm_nt_f32(bool lower, const float* A, long long lda, const float* B, long long ldb, float* C, long long ldc,
+                             int M, int N, int K, float alpha, float beta, bool mirror, bool kstart_row, hipStream_t st);      // syrk_mfma.hip
+void test_launch_gemm_nt_f64(bool lower, const double* A, long long lda, const double* B, long long ldb, double* C, long long ldc,
+                             int M, int N, int K, double alpha, double beta, bool mirror, bool kstart_row, bool kend_col, hipStream_t st);   // gemm_f64_mfma.hip
+
+template <typename T>
+void test_gemm_nt(bool lower, bool mirror, bool kstart_row, bool b_lower, bool in_place, int M, int N, int K, double alpha, double beta,
+                  const T* A, const T* B, T* C) {
+    require_device();
+    Stream st;
+    const int Kp = round_up(K, std::is_same<T, float>::value ? 16 : 8);
+    const long long lda = round_up(M, 128), ldb = round_up(N, 128), ldc = lda;
+    const int ccols = in_place ? Kp : round_up(N, 128);
+    std::vector<T> hA((size_t)lda * Kp, T(0)), hB((size_t)ldb * Kp, T(0));
+    for (int k = 0; k < K; ++k) {
+        std::memcpy(&hA[(size_t)k * lda], A + (size_t)k * M, (size_t)M * sizeof(T));
+        std::memcpy(&hB[(size_t)k * ldb], B + (size_t)k * N, (size_t)N * sizeof(T));
+    }
+    std::vector<T> before;
+    if (in_place) before = hA;
+    else {
+        before.assign((size_t)ldc * ccols, std::numeric_limits<T>::quiet_NaN());
+        for (int j = 0; j < N; ++j) std::memcpy(&before[(size_t)j * ldc], C + (size_t)j * M, (size_t)M * sizeof(T));
+    }
+    DevBuf<T> dA(hA.size()), dB(hB.size()), dC(in_place ? 0 : before.size());
+    ADMM_HIP_CHECK(hipMemcpyAsync(dA.get(), hA.data(), hA.size() * sizeof(T), hipMemcpyHostToDevice, st.s));
+    ADMM_HIP_CHECK(hipMemcpyAsync(dB.get(), hB.data(), hB.size() * sizeof(T), hipMemcpyHostToDevice, st.s));
+    if (!in_place) ADMM_HIP_CHECK(hipMemcpyAsync(dC.get(), before.data(), before.size() * sizeof(T), hipMemcpyHostToDevice, st.s));
+    T* out = in_place ? dA.get() : dC.get();
+    if constexpr (std::is_same<T, float>::value)
+        test_launch_gemm_nt_f32(lower, dA.get(), lda, dB.get(), ldb, out, ldc, M, N, Kp, (float)alpha, (float)beta, mirror, kstart_row, st.s);
+    else
+        test_launch_gemm_nt_f64(lower, dA.get(), lda, dB.get(), ldb, out, ldc, M, N, Kp, alpha, beta, mirror, kstart_row, b_lower, st.s);
+    ADMM_HIP_CHECK(hipGetLastError());
+    std::vector<T> after(before.size());
+    ADMM_HIP_CHECK(hipMemcpyAsync(after.data(), out, after.size() * sizeof(T), hipMemcpyDeviceToHost, st.s));
+    st.sync();
+    long long touched = 0, first_row = -1, first_col = -1;
+    for (int j = 0; j < ccols; ++j)
+        for (long long i = (j < N ? M : 0); i < ldc; ++i)
+            if (std::memcmp(&after[(size_t)j * ldc + i], &before[(size_t)j * ldc + i], sizeof(T)) != 0 && touched++ == 0) { first_row = i; first_col = j; }
+    for (int j = 0; j < N; ++j) std::memcpy(C + (size_t)j * M, &after[(size_t)j * ldc], (size_t)M * sizeof(T));
+    if (touched != 0)
+        throw Error(ADMM_ERR_INTERNAL, "gemm_nt wrote outside its " + std::to_string(M) + " x " + std::to_string(N) + " output: " + std::to_string(touched) +
+                                           " entries of the padded storage changed, the first at (" + std::to_string(first_row) + ", " + std::to_string(first_col) + ")");
+}
+template void test_gemm_nt<float>(bool, bool, bool, bool, bool, int, int, int, double, double, const float*, const float*, float*);
+template void test_gemm_nt<double>(bool, bool, bool, bool, bool, int, int, int, double, double, const double*, const double*, double*);
 
 }  // namespace admm

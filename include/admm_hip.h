@@ -614,6 +614,24 @@ ADMM_HIP_API int admm_hip_test_gemv_t(const void* A, int rows, int cols, int is_
  * dimension rows), v length cols in A's type, y length rows in double (the kernel's accumulation type). */
 ADMM_HIP_API int admm_hip_test_gather(const void* A, int rows, int cols, int is_double, const void* v, double* y);
 ADMM_HIP_API int admm_hip_test_spd_inverse(const void* A, int n, int precision, void* Ainv);
+/* (A + diag I)^-1 of the float matrix A (order n) through the double route of precision 2 above with the caller's shift: the
+ * tall path's rho, added to the float diagonal as a FLOAT addition before the matrix is widened (ADMMLassoTall.h:204). */
+ADMM_HIP_API int admm_hip_test_spd_inverse_shift(const float* A, int n, double diag, float* Ainv);
+/* The blocked factorisation under those inverses alone: L (order n, tight) = A overwritten by its Cholesky factor in the lower
+ * triangle (the strict upper triangle stays the caller's), U = L^-T (upper triangular).  Float or double (is_double);
+ * ADMM_ERR_NOT_SPD names the first failing pivot (1-based). */
+ADMM_HIP_API int admm_hip_test_cholesky_linvt(int is_double, const void* A, int n, void* L, void* U);
+/* One launch of the matrix-core NT-GEMM every step of that chain runs: C = alpha A B' + beta C on 128 x 128 tiles.  HOST operands,
+ * column-major with the output index contiguous and tight leading dimensions: A is M x K, B is N x K, C is M x N (read and
+ * written); the hook stores them on the device as the callers do (leading dimension rounded up to 128, K zero padded to the K tile:
+ * 16 float, 8 double).  lower: only the tiles on or below the diagonal of a square C (M == N); mirror (with lower): the transposed
+ * tile is stored too; kstart_row: the K loop of a tile starts at its first row (upper-triangular operands: U U'); b_lower (double,
+ * not lower): the K loop ends after the tile's last column (lower-triangular B); in_place (N <= 128, K == 128, not lower): the
+ * device copy of A is the output as well, as in the factorisation's panel updates -- the host C is then only written.
+ * Inconsistent requests: ADMM_ERR_INVALID_ARG before any launch.  A launch that changes the device C outside M x N (a NaN guard
+ * band up to the padded storage; the remaining columns of A when in place): ADMM_ERR_INTERNAL, with C still copied back. */
+ADMM_HIP_API int admm_hip_test_gemm_nt(int is_double, int lower, int mirror, int kstart_row, int b_lower, int in_place, int M, int N, int K,
+                                       double alpha, double beta, const void* A, const void* B, void* C);
 /* The system admm_hip_lasso_cv hands the tall solver for fold `fold` when it forms the folds as down-dates of the full-data
  * Gram (cv.hip): x, y HOST column-major doubles, fold_id as in admm_hip_lasso_cv (NULL: i mod nfolds).  Out (HOST): gram p x p
  * float (X_T'X_T of the training rows standardised by THEIR statistics), xy p floats, mean_x / scale_x p floats, and

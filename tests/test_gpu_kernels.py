@@ -147,7 +147,7 @@ def test_spd_inverse_vs_numpy(n, precision):
     dtype = np.float64 if precision == 1 else np.float32
     A = A64.astype(dtype)
     Ainv = _inverse(A, precision)
-    assert np.abs(Ainv - Ainv.T).max() <= 1e-6 * np.abs(Ainv).max()
+    assert np.array_equal(Ainv, Ainv.T)                               # both routes store mirrored copies: symmetric by construction
     exact = np.linalg.inv(A.astype(np.float64))
     err = np.abs(Ainv - exact).max() / np.abs(exact).max()
     lapack = np.linalg.inv(A).astype(np.float64)
