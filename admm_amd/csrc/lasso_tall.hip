@@ -234,6 +234,18 @@ __device__ __forceinline__ TallElem tall_load_elem(const TallParams& q, int par,
     return e;
 }
 
+// soft_threshold of the Lasso: the compare in double, the result rounded once (ADMMLassoTall.h:55-69)
+__device__ __forceinline__ float tall_soft(float vec, double pen) {
+    const double v = (double)vec;
+    return v > pen ? (float)(v - pen) : (v < -pen ? (float)(v + pen) : 0.f);
+}
+
+// block soft-threshold of a group / row of squared norm nrm2: the factor max(0, 1 - pen / ||v||)
+__device__ __forceinline__ double tall_block_shrink(double nrm2, double pen) {
+    const double nrm = sqrt(nrm2);
+    return nrm > pen ? 1.0 - pen / nrm : 0.0;
+}
+
 template <bool WT = false>      // WT: u, w are consumed by other workgroups of the same launch -> write-through stores
 __device__ __forceinline__ void tall_update_elem(const TallParams& q, const TallCtl& c, int par, int i, const TallElem& e, float a, float b, double (&acc)[6]) {
     // The reference is built without fused multiply-adds (R's default flags on x86-64: no -march, /root/reference/src/Makevars):
@@ -258,10 +270,8 @@ __device__ __forceinline__ void tall_update_elem(const TallParams& q, const Tall
     const float vec = x + adjy / rho_f;        // next_z: main_x + adj_y / rho            ADMMLassoTall.h:83
     const double pen = c.lam / c.rho;
     float zn;
-    if (!q.enet) {                             // soft_threshold, double compare          ADMMLassoTall.h:55-69
-        const double v = (double)vec;
-        zn = v > pen ? (float)(v - pen) : (v < -pen ? (float)(v + pen) : 0.f);
-    } else {                                   // enet()                                  ADMMEnet.h:24-40
+    if (!q.enet) zn = tall_soft(vec, pen);
+    else {                                   // enet()                                  ADMMEnet.h:24-40
         const float thresh = (float)(q.alpha * pen);
         const float denom = (float)(1.0 + pen * (1.0 - q.alpha));
         zn = vec > thresh ? (vec - thresh) / denom : (vec < -thresh ? (vec + thresh) / denom : 0.f);
@@ -285,10 +295,52 @@ __device__ __forceinline__ void tall_update_elem(const TallParams& q, const Tall
     else { q.u[i] = un; q.w[i] = wn; }
 }
 
+// Block sum of the six norms into P[par ^ 1][blockIdx.x]; every thread of the workgroup calls it.  Only the owner lanes (sub == 0)
+// hold values, so wave_sum's xor-4 / 2 / 1 steps would add exact zeros: the top half of the halving butterfly (xor 32 / 16 / 8)
+// leaves the wave total of value k in lane 8 k, bit-identical to block_sum<double, 6> at 7 exchanges instead of 36.
+__device__ __forceinline__ void tall_publish_norms(const TallParams& q, int par, const double (&acc)[6], double* scratch) {
+    static_assert(kTailLanes == 8, "owner lanes are the multiples of 8");
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const double v8[8] = {acc[0], acc[1], acc[2], acc[3], acc[4], acc[5], 0.0, 0.0};
+    const double tot = halving_sum8_top(v8, lane);
+    if ((lane & 7) == 0 && lane < 48) scratch[(lane >> 3) * (kTailThreads / 64) + wid] = tot;
+    __syncthreads();
+    if (threadIdx.x < 6) {
+        double sum = 0;
+        for (int ww = 0; ww < kTailThreads / 64; ++ww) sum += scratch[threadIdx.x * (kTailThreads / 64) + ww];
+        q.P[((size_t)(par ^ 1) * q.nwg + blockIdx.x) * 8 + threadIdx.x] = sum;
+    }
+}
+
 // Element-wise part of one iteration.  `c` = the control block published by this iteration's decision.
 // MODE 0: x-update results as gemv_t partial rows; 1: as the symmetric mat-vec's partial arrays; 2: row-sharded over the
 // PEER exchange -- wait for the K flags, then sum the K ranks' shares straight out of the exchange slots.
 enum { TAIL_GEMV = 0, TAIL_SYMV = 1, TAIL_PEER = 2, TAIL_PEER1 = 3 };
+
+// The kTailLanes lanes of one element add up what each of them summed.
+__device__ __forceinline__ void tall_lane_sum(float& a, float& b) {
+#pragma unroll
+    for (int m = 1; m < kTailLanes; m <<= 1) { a += __shfl_xor(a, m, 64); b += __shfl_xor(b, m, 64); }
+}
+
+// x-update results a = Minv u, b = Minv w of element i (single device): kTailLanes lanes share one element and issue all their partial
+// loads at once, then combine with shuffles.  Nothing here depends on the control block.
+template <int MODE>
+__device__ __forceinline__ void tall_gather_ab(const TallParams& q, int i, int sub, bool valid, float& a, float& b) {
+    if (MODE == TAIL_SYMV) {
+        symv_sum_partials<kTailLanes>(q.dot0, q.dot1, q.axp0, q.axp1, q.ldo, q.nrb, q.sched, q.p32, i, sub, valid, a, b);
+        return;
+    }
+    a = 0.f; b = 0.f;
+    if (valid) {
+        for (int k = sub; k < q.nseg; k += kTailLanes) {
+            const size_t o = (size_t)k * q.part_stride + i;
+            a += q.a_part[o]; b += q.b_part[o];
+        }
+    }
+    tall_lane_sum(a, b);
+}
+
 // TAIL_PEER1: producer and consumer of the exchange in ONE launch -- every workgroup sums its elements of this rank's share,
 // writes them into every rank's slot and counts itself in (the last one raises the flags), then waits for the K flags like
 // TAIL_PEER.  A workgroup waits for flags that need ALL workgroups of this launch (on every rank) to have published, so
@@ -308,16 +360,8 @@ tall_tail_kernel(TallParams q, int par, PeerExchange ex) {
     const bool owner = valid && sub == 0;
     TallElem e = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     if (owner) e = tall_load_elem(q, par, i);
-    // ---- x-update results a = Minv u, b = Minv w: kTailLanes lanes share one element and issue all
-    // their partial loads at once, then combine with shuffles.
     float a = 0.f, b = 0.f;
-    if (MODE == TAIL_SYMV) {
-        symv_sum_partials<kTailLanes>(q.dot0, q.dot1, q.axp0, q.axp1, q.ldo, q.nrb, q.sched, q.p32, i, sub, valid, a, b);
-        if (q.refine_ab != nullptr && valid) {            // x = x1 + Minv (rhs - M x1): the partials hold the correction
-            a = q.refine_ab[i] + a;
-            b = q.refine_ab[q.refine_ld + i] + b;
-        }
-    } else if (MODE == TAIL_PEER || MODE == TAIL_PEER1) {
+    if (MODE == TAIL_PEER || MODE == TAIL_PEER1) {
         const bool live = !q.ctl[par].done;                          // finished in an earlier launch: nothing pushed, nothing to wait for (replicated flag: all ranks agree)
         if (MODE == TAIL_PEER1 && live) {
             float sa, sb;
@@ -336,17 +380,13 @@ tall_tail_kernel(TallParams q, int par, PeerExchange ex) {
                 a += v.x; b += v.y;
             }
         }
-#pragma unroll
-        for (int m = 1; m < kTailLanes; m <<= 1) { a += __shfl_xor(a, m, 64); b += __shfl_xor(b, m, 64); }
+        tall_lane_sum(a, b);
     } else {
-        if (valid) {
-            for (int k = sub; k < q.nseg; k += kTailLanes) {
-                const size_t o = (size_t)k * q.part_stride + i;
-                a += q.a_part[o]; b += q.b_part[o];
-            }
+        tall_gather_ab<MODE>(q, i, sub, valid, a, b);
+        if (MODE == TAIL_SYMV && q.refine_ab != nullptr && valid) {      // x = x1 + Minv (rhs - M x1): the partials hold the correction
+            a = q.refine_ab[i] + a;
+            b = q.refine_ab[q.refine_ld + i] + b;
         }
-#pragma unroll
-        for (int m = 1; m < kTailLanes; m <<= 1) { a += __shfl_xor(a, m, 64); b += __shfl_xor(b, m, 64); }
     }
     if (c.done && c.fin_idx < 0) return;
     WIDE_PROBE(1);
@@ -355,22 +395,7 @@ tall_tail_kernel(TallParams q, int par, PeerExchange ex) {
     if (owner) tall_update_elem(q, c, par, i, e, a, b, acc);
     if (c.done) return;
     WIDE_PROBE(2);
-    // Block sum of the six norms.  Only the owner lanes (sub == 0) hold values, so wave_sum's xor-4 / 2 / 1 steps would add
-    // exact zeros: the top half of the halving butterfly (xor 32 / 16 / 8) leaves the wave total of value k in lane 8 k,
-    // bit-identical to block_sum<double, 6> at 7 exchanges instead of 36.
-    static_assert(kTailLanes == 8, "owner lanes are the multiples of 8");
-    {
-        const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-        const double v8[8] = {acc[0], acc[1], acc[2], acc[3], acc[4], acc[5], 0.0, 0.0};
-        const double tot = halving_sum8_top(v8, lane);
-        if ((lane & 7) == 0 && lane < 48) scratch[(lane >> 3) * (kTailThreads / 64) + wid] = tot;
-        __syncthreads();
-        if (threadIdx.x < 6) {
-            double sum = 0;
-            for (int ww = 0; ww < kTailThreads / 64; ++ww) sum += scratch[threadIdx.x * (kTailThreads / 64) + ww];
-            q.P[((size_t)(par ^ 1) * q.nwg + blockIdx.x) * 8 + threadIdx.x] = sum;
-        }
-    }
+    tall_publish_norms(q, par, acc, scratch);
     WIDE_PROBE(3);
     WIDE_PROBE_FLUSH(blockIdx.x == 0 ? 0 : (blockIdx.x == gridDim.x - 1 ? 1 : -1), c.total - 1);
 }
@@ -382,13 +407,16 @@ tall_tail_kernel(TallParams q, int par, PeerExchange ex) {
 // same launch: the host packs whole groups into TILES -- a run of consecutive groups of at most kTailElems coordinates in all,
 // one workgroup, one pass; a group larger than that gets a workgroup of its own, which walks it in passes of kTailElems -- and the
 // coordinates' v go through LDS.  Norms are sums of (double) v^2 in a fixed order: no atomics, the same bits from run to run.
-// A group of ONE column takes the Lasso's scalar soft-threshold (tall_update_elem) bit for bit, so singleton groups of weight 1
-// reproduce admm_hip_lasso exactly (the tiles are then tall_tail_kernel's workgroups, the norm partials P the same sums).
+// Shared with that tail as functions: tall_gather_ab, tall_soft, tall_publish_norms (and tall_block_shrink with the multi-task tail).
+// The choice of (adj_z, adj_y, x) and the second half restate tall_update_elem and must be kept equal to it by hand: called as shared
+// functions they cost the 1024-column group and the multi-task tail 0.3 - 1.5 % of an iteration (profiles/tall_tail_shared.md).
+// A group of ONE column takes tall_soft, so singleton groups of weight 1 reproduce admm_hip_lasso exactly (the tiles are then
+// tall_tail_kernel's workgroups, the norm partials P the same sums).
 //
 // SPARSE (admm_hip_sgl): the prox of lambda (alpha sum_j u_j |b_j| + (1 - alpha) sum_g w_g ||b_g||_2) is the element-wise soft-threshold
-// followed by the block one, so a group of several columns stores  s_j = soft(v_j, lambda l1_j / rho)  (the Lasso's double compare and
-// rounding) where the plain form stores v_j, and everything after the first half -- the norm, the shrink, the six norm partials, the
-// next right-hand sides -- is the same code on s.  The owner lane loads l1_j (sgl_host.h: alpha u_j; alpha never reaches the device)
+// followed by the block one, so a group of several columns stores  s_j = tall_soft(v_j, lambda l1_j / rho)  where the plain form
+// stores v_j, and everything after the first half -- the norm, the shrink, the six norm partials, the next right-hand sides -- is the
+// same code on s.  The owner lane loads l1_j (sgl_host.h: alpha u_j; alpha never reaches the device)
 // beside the coordinate's other loads: its address needs neither `c` nor more of the tile entry than those do, so the kernel is still
 // one memory round trip per pass.  A one-column group keeps v and takes the scalar threshold with GroupCoord.w = l1_j + wg_g.
 struct GroupCoord { int gs, gn; double w; };      // per coordinate: first column, size and weight of its group
@@ -426,19 +454,8 @@ tall_group_tail_kernel(TallParams q, int par, GroupTailParams gp) {
         if (owner) el = tall_load_elem(q, par, i);
         double l1 = 0.0;
         if (SPARSE && owner) l1 = gp.l1[i];
-        float a = 0.f, b = 0.f;
-        if (MODE == TAIL_SYMV) {
-            symv_sum_partials<kTailLanes>(q.dot0, q.dot1, q.axp0, q.axp1, q.ldo, q.nrb, q.sched, q.p32, i, sub, valid, a, b);
-        } else {
-            if (valid) {
-                for (int m = sub; m < q.nseg; m += kTailLanes) {
-                    const size_t o = (size_t)m * q.part_stride + i;
-                    a += q.a_part[o]; b += q.b_part[o];
-                }
-            }
-#pragma unroll
-            for (int m = 1; m < kTailLanes; m <<= 1) { a += __shfl_xor(a, m, 64); b += __shfl_xor(b, m, 64); }
-        }
+        float a, b;
+        tall_gather_ab<MODE>(q, i, sub, valid, a, b);
         if (c.done && c.fin_idx < 0) return;
         if (owner) {
             if (c.fin_idx >= 0) q.beta[(size_t)c.fin_idx * q.p + i] = el.zc;     // get_z() snapshot (Lasso.cpp:108)
@@ -454,10 +471,7 @@ tall_group_tail_kernel(TallParams q, int par, GroupTailParams gp) {
                     }
                 } else { adjz = el.adjz; adjy = el.adjy; x = el.x; }
                 float vec = x + adjy / rho_f;
-                if (SPARSE && gc.gn > 1) {                              // s = soft(v, lambda l1 / rho): the Lasso's soft_threshold
-                    const double v = (double)vec, pen1 = c.lam * l1 / c.rho;
-                    vec = v > pen1 ? (float)(v - pen1) : (v < -pen1 ? (float)(v + pen1) : 0.f);
-                }
+                if (SPARSE && gc.gn > 1) vec = tall_soft(vec, c.lam * l1 / c.rho);      // s = soft(v, lambda l1 / rho)
                 sx[s] = x; sadjz[s] = adjz; sadjy[s] = adjy; sv[s] = vec;
                 szc[s] = el.zc; syc[s] = el.yc; sxy[s] = el.xy;
             }
@@ -482,9 +496,9 @@ tall_group_tail_kernel(TallParams q, int par, GroupTailParams gp) {
     }
     const double pen = c.lam * gc.w / c.rho;
     double shrink = 0.0;                                                // max(0, 1 - pen / ||v_g||)
-    if (gc.gn > 1) { const double nrm = sqrt(nrm2); shrink = nrm > pen ? 1.0 - pen / nrm : 0.0; }
+    if (gc.gn > 1) shrink = tall_block_shrink(nrm2, pen);
 
-    // ---- second half: next_z, residual, dual update, norms, the right-hand sides of the next x-update (as tall_update_elem)
+    // ---- second half: next_z, residual, dual update, norms, the right-hand sides of the next x-update (tall_update_elem's, restated)
     double acc[6] = {0, 0, 0, 0, 0, 0};
     const float tn = (float)c.tau_next, tn1 = (float)(1.0 + c.tau_next);
     for (int k = 0; k < npass; ++k) {
@@ -493,7 +507,7 @@ tall_group_tail_kernel(TallParams q, int par, GroupTailParams gp) {
         const float x = sx[s], adjz = sadjz[s], adjy = sadjy[s], vec = sv[s], zc = szc[s], yc = syc[s], xy = sxy[s];
         const double v = (double)vec;
         float zn;
-        if (gc.gn == 1) zn = v > pen ? (float)(v - pen) : (v < -pen ? (float)(v + pen) : 0.f);      // the Lasso's soft_threshold, double compare
+        if (gc.gn == 1) zn = tall_soft(vec, pen);
         else zn = (float)(v * shrink);
         const float r = x - zn;
         const float yn = adjy + rho_f * r;
@@ -509,20 +523,7 @@ tall_group_tail_kernel(TallParams q, int par, GroupTailParams gp) {
         q.u[i] = (float)((double)(xy - adjy_a) + c.rho * (double)adjz_a);
         q.w[i] = (float)((double)(xy - yc) + c.rho * (double)zc);
     }
-    // block sum of the six norms: tall_tail_kernel's, value for value
-    static_assert(kTailLanes == 8, "owner lanes are the multiples of 8");
-    {
-        const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-        const double v8[8] = {acc[0], acc[1], acc[2], acc[3], acc[4], acc[5], 0.0, 0.0};
-        const double tot = halving_sum8_top(v8, lane);
-        if ((lane & 7) == 0 && lane < 48) scratch[(lane >> 3) * (kTailThreads / 64) + wid] = tot;
-        __syncthreads();
-        if (threadIdx.x < 6) {
-            double sum = 0;
-            for (int ww = 0; ww < kTailThreads / 64; ++ww) sum += scratch[threadIdx.x * (kTailThreads / 64) + ww];
-            q.P[((size_t)(par ^ 1) * q.nwg + blockIdx.x) * 8 + threadIdx.x] = sum;
-        }
-    }
+    tall_publish_norms(q, par, acc, scratch);
 }
 
 // ---- multi-task lasso (admm_hip_mtlasso): m responses on ONE cached inverse, a row-wise block soft-threshold
@@ -531,8 +532,10 @@ tall_group_tail_kernel(TallParams q, int par, GroupTailParams gp) {
 // ceil(2m / NR) passes of symvn_lower_kernel (symv_kernels.h), each writing one plane of partials per right-hand side.  This tail has
 // tall_tail_kernel<TAIL_SYMV>'s geometry -- 32 coordinates per workgroup, 8 lanes per coordinate summing partials -- and loops over the
 // responses of its coordinate, kMtChunk at a time with the loads of a chunk issued together.  A row's m values belong to one owner lane:
-// the row norm is the sum of (double) v_k^2 in the order k = 0 .. m - 1 in registers -- no LDS tiles, no tile list, no atomics.  m = 1
-// takes the Lasso's scalar soft-threshold, and every sum is then tall_tail_kernel's: admm_hip_lasso bit for bit.
+// the row norm is the sum of (double) v_k^2 in the order k = 0 .. m - 1 in registers -- no LDS tiles, no tile list, no atomics.  The
+// scalar threshold, the shrink factor and the norm sum are the other tails' functions (tall_soft, tall_block_shrink, tall_publish_norms);
+// the choice of (adj_z, adj_y, x) and the second half restate tall_update_elem (see the group tail).  m = 1 takes tall_soft, and every
+// sum is then tall_tail_kernel's: admm_hip_lasso bit for bit.
 struct MtTailParams {
     int m;
     long long ldv, ldxy;                  // plane strides of the iterates and of X'Y
@@ -614,9 +617,9 @@ tall_mt_tail_kernel(TallParams q, int par, MtTailParams mp) {
 
     const double pen = c.lam * wj / c.rho;
     double shrink = 0.0;                                                // max(0, 1 - pen / ||v_j.||)
-    if (m > 1) { const double nrm = sqrt(nrm2); shrink = nrm > pen ? 1.0 - pen / nrm : 0.0; }
+    if (m > 1) shrink = tall_block_shrink(nrm2, pen);
 
-    // ---- second half: next_z, residual, dual update, norms, the right-hand sides of the next x-update (as tall_update_elem)
+    // ---- second half: next_z, residual, dual update, norms, the right-hand sides of the next x-update (tall_update_elem's, restated)
     double acc[6] = {0, 0, 0, 0, 0, 0};
     const float tn = (float)c.tau_next, tn1 = (float)(1.0 + c.tau_next);
     const size_t pm = (size_t)q.p * m;
@@ -626,7 +629,7 @@ tall_mt_tail_kernel(TallParams q, int par, MtTailParams mp) {
             const float x = sx[k], adjz = sadjz[k], adjy = sadjy[k], vec = sv[k], zc = szc[k], yc = syc[k], xy = sxy[k];
             const double v = (double)vec;
             float zn;
-            if (m == 1) zn = v > pen ? (float)(v - pen) : (v < -pen ? (float)(v + pen) : 0.f);      // the Lasso's soft_threshold, double compare
+            if (m == 1) zn = tall_soft(vec, pen);
             else zn = (float)(v * shrink);
             const float r = x - zn;
             const float yn = adjy + rho_f * r;
@@ -644,20 +647,7 @@ tall_mt_tail_kernel(TallParams q, int par, MtTailParams mp) {
             mp.uw[(size_t)(2 * k + 1) * mp.ldv + i] = (float)((double)(xy - yc) + c.rho * (double)zc);
         }
     }
-    // block sum of the six norms: tall_tail_kernel's, value for value
-    static_assert(kTailLanes == 8, "owner lanes are the multiples of 8");
-    {
-        const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-        const double v8[8] = {acc[0], acc[1], acc[2], acc[3], acc[4], acc[5], 0.0, 0.0};
-        const double tot = halving_sum8_top(v8, lane);
-        if ((lane & 7) == 0 && lane < 48) scratch[(lane >> 3) * (kTailThreads / 64) + wid] = tot;
-        __syncthreads();
-        if (threadIdx.x < 6) {
-            double sum = 0;
-            for (int ww = 0; ww < kTailThreads / 64; ++ww) sum += scratch[threadIdx.x * (kTailThreads / 64) + ww];
-            q.P[((size_t)(par ^ 1) * q.nwg + blockIdx.x) * 8 + threadIdx.x] = sum;
-        }
-    }
+    tall_publish_norms(q, par, acc, scratch);
 }
 
 // Round 4 also built the whole path as ONE persistent launch with a third of the inverse's triangle resident in registers (two
@@ -1205,6 +1195,18 @@ struct TallPlan final : LassoPlan {
             // launch g rides the decision that leaves g + 1 taken: its tiles leave on exactly that word with the discard bit set
             SymvVerdict vd;
             if (verdict_on) { vd.words = verdict.get(); vd.discard = tall_verdict_word(q.run_tag, (int)(g + 1), true); vd.early = verdict.get() + kVerdictWords; vd.mid = verdict_mid; }
+            const int* skip = &ctl.get()[par].done;
+            // single device, one stream of the inverse: the x-update with the decision riding on it, in the form p selected
+            const auto xupdate = [&] {
+                if (use_sym) sy.launch(M.get(), ldp, u.get(), w.get(), skip, st, dec, e0, e1, vd);
+                else launch_gemv_t<float, 2, 4, TallDecideExtra>(pl, M.get(), ldp, p, p, u.get(), w.get(), a_part.get(), b_part.get(), ldp, skip, st, dec, e0, e1);
+            };
+            const auto group_tail = [&] {
+                void (*tail)(TallParams, int, GroupTailParams) =
+                    use_sym ? (pb.sgl ? tall_group_tail_kernel<TAIL_SYMV, true> : tall_group_tail_kernel<TAIL_SYMV>)
+                            : (pb.sgl ? tall_group_tail_kernel<TAIL_GEMV, true> : tall_group_tail_kernel<TAIL_GEMV>);
+                hipLaunchKernelGGL(tail, dim3(nwg), dim3(kTailThreads), 0, st, q, par, gq);
+            };
             if (mt) {
                 // ceil(2m / NR) passes over the triangle, NR right-hand sides each (the decision rides on the first), then the row tail
                 const int nvec = 2 * mt;
@@ -1214,45 +1216,36 @@ struct TallPlan final : LassoPlan {
                     a.v = uw.get() + (size_t)r0 * ldv; a.vstride = ldv;
                     a.dot = mdot.get() + (size_t)r0 * mq.dot_stride; a.dot_stride = mq.dot_stride;
                     a.axp = maxp.get() + (size_t)r0 * mq.axp_stride; a.axp_stride = mq.axp_stride;
-                    a.nvec = std::min(mt_rhs, nvec - r0); a.ldo = sy.ldo; a.tiles = sy.tiles.get(); a.skip = &ctl.get()[par].done;
+                    a.nvec = std::min(mt_rhs, nvec - r0); a.ldo = sy.ldo; a.tiles = sy.tiles.get(); a.skip = skip;
                     // a sampled iteration is timed from the start of its first pass to the end of its last
                     hipEvent_t es = r0 == 0 ? e0 : nullptr, ee = r0 + mt_rhs >= nvec ? e1 : nullptr;
                     if (r0 == 0) symvn_launch(sy, mt_rhs, a, st, dec, es, ee);
                     else symvn_launch(sy, mt_rhs, a, st, SymvNoExtra(), es, ee);
                 }
                 hipLaunchKernelGGL(tall_mt_tail_kernel, dim3(nwg), dim3(kTailThreads), 0, st, q, par, mq);
-            } else if (grouped) {                      // two launches, as the Lasso: the x-update with the decision, the group tail
-                if (use_sym) {
-                    sy.launch(M.get(), ldp, u.get(), w.get(), &ctl.get()[par].done, st, dec, e0, e1, vd);
-                    if (pb.sgl) hipLaunchKernelGGL((tall_group_tail_kernel<TAIL_SYMV, true>), dim3(nwg), dim3(kTailThreads), 0, st, q, par, gq);
-                    else hipLaunchKernelGGL(tall_group_tail_kernel<TAIL_SYMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, gq);
-                } else {
-                    launch_gemv_t<float, 2, 4, TallDecideExtra>(pl, M.get(), ldp, p, p, u.get(), w.get(), a_part.get(), b_part.get(), ldp,
-                                                                &ctl.get()[par].done, st, dec, e0, e1);
-                    if (pb.sgl) hipLaunchKernelGGL((tall_group_tail_kernel<TAIL_GEMV, true>), dim3(nwg), dim3(kTailThreads), 0, st, q, par, gq);
-                    else hipLaunchKernelGGL(tall_group_tail_kernel<TAIL_GEMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, gq);
-                }
+            } else if (grouped) {                      // two launches, as the Lasso
+                xupdate();
+                group_tail();
             } else if (shard && peer_fused) {
                 // this rank's tiles -> its share of (a, b) written into every rank's exchange slot by the reduction
                 // launch itself -> the (replicated) tail waits for the K flags and sums the K slots: three launches,
                 // none of them the exchange layer's
-                sy.launch(M.get(), ldp, u.get(), w.get(), &ctl.get()[par].done, st, dec, e0, e1);
+                sy.launch(M.get(), ldp, u.get(), w.get(), skip, st, dec, e0, e1);
                 const PeerExchange ex = comm_peer_begin((size_t)2 * ldp * sizeof(float));
                 if (peer_one) {
                     hipLaunchKernelGGL(tall_tail_kernel<TAIL_PEER1>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, ex);
                 } else {
-                    hipLaunchKernelGGL(tall_shard_push_kernel, dim3(nwg), dim3(kTailThreads), 0, st, q, ex, ldp, &ctl.get()[par].done);
+                    hipLaunchKernelGGL(tall_shard_push_kernel, dim3(nwg), dim3(kTailThreads), 0, st, q, ex, ldp, skip);
                     hipLaunchKernelGGL(tall_tail_kernel<TAIL_PEER>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, ex);
                 }
             } else if (shard) {
                 // this rank's tiles -> its share of (a, b) -> ONE all-reduce of 2 ldp floats -> the (replicated) tail
-                sy.launch(M.get(), ldp, u.get(), w.get(), &ctl.get()[par].done, st, dec, e0, e1);
-                hipLaunchKernelGGL(tall_shard_reduce_kernel, dim3(nwg), dim3(kTailThreads), 0, st, q, ab.get(), ldp, &ctl.get()[par].done);
+                sy.launch(M.get(), ldp, u.get(), w.get(), skip, st, dec, e0, e1);
+                hipLaunchKernelGGL(tall_shard_reduce_kernel, dim3(nwg), dim3(kTailThreads), 0, st, q, ab.get(), ldp, skip);
                 allreduce_sum_f32(ab.get(), (size_t)2 * ldp, st);
                 hipLaunchKernelGGL(tall_tail_kernel<TAIL_GEMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, PeerExchange{});
             } else if (use_sym && refine) {
                 // x1 = Minv rhs (both candidates) -> vectors; r = rhs - M x1 in double; correction Minv r -> partials; the tail adds
-                const int* skip = &ctl.get()[par].done;
                 sy.launch(M.get(), ldp, u.get(), w.get(), skip, st, dec, e0, e1);
                 hipLaunchKernelGGL(tall_shard_reduce_kernel, dim3(nwg), dim3(kTailThreads), 0, st, q, rab.get(), ldv, skip);
                 SymvArgsD ad;
@@ -1263,13 +1256,10 @@ struct TallPlan final : LassoPlan {
                                    ruw.get(), ruw.get() + ldv, skip);
                 sy.launch(M.get(), ldp, ruw.get(), ruw.get() + ldv, skip, st, SymvNoExtra());
                 hipLaunchKernelGGL(tall_tail_kernel<TAIL_SYMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, PeerExchange{});
-            } else if (use_sym) {
-                sy.launch(M.get(), ldp, u.get(), w.get(), &ctl.get()[par].done, st, dec, e0, e1, vd);
-                hipLaunchKernelGGL(tall_tail_kernel<TAIL_SYMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, PeerExchange{});
             } else {
-                launch_gemv_t<float, 2, 4, TallDecideExtra>(pl, M.get(), ldp, p, p, u.get(), w.get(), a_part.get(), b_part.get(), ldp,
-                                                            &ctl.get()[par].done, st, dec, e0, e1);
-                hipLaunchKernelGGL(tall_tail_kernel<TAIL_GEMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, PeerExchange{});
+                xupdate();
+                if (use_sym) hipLaunchKernelGGL(tall_tail_kernel<TAIL_SYMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, PeerExchange{});
+                else hipLaunchKernelGGL(tall_tail_kernel<TAIL_GEMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, PeerExchange{});
             }
         }, LoopOpts{shard ? nullptr : hflag.p, 0, false});
         S.t_loop = lt.wall_s; S.loop_ms_events = lt.events_ms; S.xupdate_launches = lt.launched;
