@@ -77,6 +77,7 @@ EXPORTS = ["admm_hip_lasso", "admm_hip_enet", "admm_hip_parlasso", "admm_hip_lad
            "admm_hip_quantreg", "admm_hip_quantreg_state",
            "admm_hip_mtlasso", "admm_hip_mtlasso_plan_create", "admm_hip_test_symv_multi", "admm_hip_test_tall_early_exits",
            "admm_hip_sgl", "admm_hip_sgl_plan_create", "admm_hip_host_sgl_lambda0",
+           "admm_hip_boxenet", "admm_hip_boxenet_plan_create", "admm_hip_host_box_lambda0",
            "admm_hip_test_gemm_nt", "admm_hip_test_cholesky_linvt", "admm_hip_test_spd_inverse_shift"]
 
 GROUP_MAX = 1024          # ADMM_HIP_GROUP_MAX
@@ -175,6 +176,13 @@ def load():
     lib.admm_hip_sgl_plan_create.restype = ctypes.c_int
     lib.admm_hip_host_sgl_lambda0.argtypes = [_c_float_p, ctypes.c_int, _c_int_p, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_double, _c_float_p]
     lib.admm_hip_host_sgl_lambda0.restype = ctypes.c_int
+    box_args = lasso_args[:5] + [_c_double_p, _c_double_p, _c_double_p, ctypes.c_double] + lasso_args[5:]
+    lib.admm_hip_boxenet.argtypes = box_args + tail
+    lib.admm_hip_boxenet.restype = ctypes.c_int
+    lib.admm_hip_boxenet_plan_create.argtypes = box_args + [ctypes.POINTER(AdmmOpts), ctypes.POINTER(ctypes.c_void_p), _c_int_p]
+    lib.admm_hip_boxenet_plan_create.restype = ctypes.c_int
+    lib.admm_hip_host_box_lambda0.argtypes = [_c_float_p, ctypes.c_int, _c_float_p, _c_float_p, _c_double_p, ctypes.c_double, _c_float_p]
+    lib.admm_hip_host_box_lambda0.restype = ctypes.c_int
     mt_args = lasso_args[:4] + [ctypes.c_int, ctypes.c_int, _c_double_p] + lasso_args[5:]
     lib.admm_hip_mtlasso.argtypes = mt_args + tail
     lib.admm_hip_mtlasso.restype = ctypes.c_int

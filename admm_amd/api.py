@@ -10,6 +10,7 @@ the same names, argument meaning, defaults and error behaviour:
     admm_grplasso(x, y, group)$penalty(..., group_weights)$opts(...)$fit()      (not in the reference: admm_hip_grplasso)
     admm_sgl(x, y, group, alpha)$penalty(..., group_weights, l1_weights)$opts(...)$fit()      (not in the reference: admm_hip_sgl)
     admm_mtlasso(x, Y)$penalty(..., row_weights)$opts(...)$fit()                (not in the reference: admm_hip_mtlasso)
+    admm_boxenet(x, y, lower, upper)$penalty(..., alpha, penalty_factor)$opts(...)$fit()      (not in the reference: admm_hip_boxenet)
 
 `fit()` forwards to the C ABI of libadmm_hip.so exactly where the R `$fit()` does its
 `.Call("admm_*", ...)` (R/30_admm_lasso.R:136-160 etc.).  All numerics run in the HIP library;
@@ -562,6 +563,9 @@ class LassoPlan:
         if isinstance(model, ADMM_MTLasso):
             check(lib.admm_hip_mtlasso_plan_create(xp, yp, model.n, model.p, model.m, xmem, model._weight_arg(), *path,
                                                    ctypes.byref(o), ctypes.byref(h), ctypes.byref(nl)))
+        elif isinstance(model, ADMM_BoxEnet):
+            check(lib.admm_hip_boxenet_plan_create(xp, yp, model.n, model.p, xmem, *model._box_args(), *path,
+                                                   ctypes.byref(o), ctypes.byref(h), ctypes.byref(nl)))
         elif isinstance(model, ADMM_SGL):
             check(lib.admm_hip_sgl_plan_create(xp, yp, model.n, model.p, xmem, *model._group_args(), *path,
                                                ctypes.byref(o), ctypes.byref(h), ctypes.byref(nl)))
@@ -844,6 +848,79 @@ class ADMM_SGL(ADMM_GrpLasso):
 
 def admm_sgl(x, y, group, alpha=0.95, intercept=True, standardize=True, **kw):
     return ADMM_SGL(x, y, group, alpha, intercept, standardize, **kw)
+
+
+class ADMM_BoxEnet(ADMM_Lasso):
+    """Box-constrained, weighted elastic net on the tall path (admm_hip_boxenet; n > p only, one device): the Lasso (alpha=None) or the
+    elastic net (0 <= alpha <= 1) with a penalty factor per column and bounds lower_j <= beta_j <= upper_j on the ORIGINAL coefficient
+    scale -- glmnet's lower.limits / upper.limits / penalty.factor, scikit-learn's positive=True as lower=0.  `lower` <= 0 <= `upper`
+    (zero must stay feasible; lower = upper = 0 excludes a column); scalars are broadcast to all columns, None means no bound.
+    penalty_factor multiplies the whole penalty of its column; 0 leaves it unpenalised."""
+    _name = "ADMM Box-Constrained Elastic Net model"
+    _missing = "not available for the box-constrained elastic net (single-device tall solver only)"
+
+    def __init__(self, x, y, lower=None, upper=None, intercept=True, standardize=True, n=None, p=None):
+        super().__init__(x, y, intercept, standardize, n, p)
+        if self.n <= self.p:
+            _stop("nrow(x) must be greater than ncol(x): the box-constrained elastic net is built for n > p only "
+                  "(the wide solver is not built for bounds)")
+        self.lower = self._per_column(lower, "lower")
+        self.upper = self._per_column(upper, "upper")
+        if self.lower is not None and not np.all(self.lower <= 0):
+            _stop("lower bounds must be <= 0 (zero must be feasible) and not NaN")
+        if self.upper is not None and not np.all(self.upper >= 0):
+            _stop("upper bounds must be >= 0 (zero must be feasible) and not NaN")
+        self.alpha = None                                            # the Lasso prox
+        self.penalty_factor = None                                   # library default: 1 for every column
+
+    def _per_column(self, v, name):
+        if v is None:
+            return None
+        a = np.asarray(v, dtype=np.float64).ravel()
+        if a.size == 1:
+            a = np.full(self.p, float(a[0]))
+        if a.size != self.p:
+            _stop(f"{name} should be a scalar or have one entry per column")
+        return np.ascontiguousarray(a)
+
+    def penalty(self, lambda_=None, nlambda=100, lambda_min_ratio=None, alpha=None, penalty_factor=None, **kw):
+        super().penalty(lambda_, nlambda, lambda_min_ratio, **kw)
+        if alpha is not None:
+            alpha = float(alpha)
+            if not 0.0 <= alpha <= 1.0:                                  # (NaN fails both comparisons)
+                _stop("alpha must be None (the Lasso prox) or within [0, 1] (the elastic net's)")
+        u = self._per_column(penalty_factor, "penalty_factor")
+        if u is not None:
+            if not np.all(np.isfinite(u)) or np.any(u < 0):
+                _stop("penalty factors must be finite and non-negative")
+            if not np.any(u > 0):
+                _stop("at least one penalty factor must be positive")
+        self.alpha, self.penalty_factor = alpha, u
+        return self
+
+    def parallel(self, *a, **kw):
+        _stop(self._missing)
+
+    def cv(self, *a, **kw):
+        _stop(self._missing)
+
+    def fit_responses(self, *a, **kw):
+        _stop(self._missing)
+
+    def _box_args(self):
+        dp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if a is not None else None
+        return dp(self.lower), dp(self.upper), dp(self.penalty_factor), -1.0 if self.alpha is None else self.alpha
+
+    def fit(self):
+        lib, head, tail, lam_out, beta, niter, stats, keep = self._common()
+        check(lib.admm_hip_boxenet(*head[:5], *self._box_args(), *head[5:], *tail))
+        fit = ADMM_Lasso_fit(lam_out, beta, niter, stats.as_dict())
+        fit._title = "ADMM Box-Constrained Elastic Net fitting result"
+        return fit
+
+
+def admm_boxenet(x, y, lower=None, upper=None, intercept=True, standardize=True, **kw):
+    return ADMM_BoxEnet(x, y, lower, upper, intercept, standardize, **kw)
 
 
 class ADMM_MTLasso_fit:

@@ -263,6 +263,28 @@ int admm_hip_sgl_plan_create(const double* x, const double* y, int n, int p, int
     });
 }
 
+// admm_hip_boxenet: the elastic net's path arguments (alpha < 0: the Lasso prox) plus the box and the penalty factors
+#define BOX_SPEC [&] { PathSpec s = PATH_SPEC(alpha); s.box = true; s.lower = lower; s.upper = upper; s.penalty_factor = penalty_factor; s.box_cols = p; return s; }()
+
+int admm_hip_boxenet(const double* x, const double* y, int n, int p, int mem,
+                     const double* lower, const double* upper, const double* penalty_factor, double alpha,
+                     const double* lambda_in, int nlambda_in, int nlambda_auto, double lmin_ratio,
+                     int standardize, int intercept, const admm_opts* opts,
+                     double* lambda_out, float* beta_out, int* niter_out, admm_stats* stats) {
+    return guarded([&] { lasso_family(x, y, n, p, mem, BOX_SPEC, 0, Shard(), PATH_OUT); });
+}
+
+int admm_hip_boxenet_plan_create(const double* x, const double* y, int n, int p, int mem,
+                                 const double* lower, const double* upper, const double* penalty_factor, double alpha,
+                                 const double* lambda_in, int nlambda_in, int nlambda_auto, double lmin_ratio,
+                                 int standardize, int intercept, const admm_opts* opts,
+                                 admm_hip_plan** plan_out, int* nlambda_out) {
+    return guarded([&] {
+        ADMM_REQUIRE(plan_out != nullptr, "plan_out must not be NULL");
+        plan_out_set(create_plan(x, y, n, p, mem, BOX_SPEC, 0), plan_out, nlambda_out);
+    });
+}
+
 // admm_hip_mtlasso: the Lasso's path arguments plus the number of responses and the row weights
 #define MT_SPEC [&] { PathSpec s = PATH_SPEC(-1.0); s.nresp = m; s.row_weight = row_weight; s.mt_rows = p; if (m == 0) s.nresp = -1; return s; }()
 
@@ -537,6 +559,23 @@ int admm_hip_host_sgl_lambda0(const float* xy, int p, const int* group, const do
         std::vector<double> l1, wg;
         sgl_prepare(alpha, l1_weight, group_weight, start, l1, wg);
         *out = sgl_lambda0(xy, start, l1, wg);
+    });
+}
+
+// Host-only helper used by the CPU test-suite: lambda_0 of the box-constrained elastic net's automatic grid (box_host.h) from a given
+// X'y and bounds already in the solver's units.
+int admm_hip_host_box_lambda0(const float* xy, int p, const float* lower_std, const float* upper_std, const double* penalty_factor,
+                              double alpha, float* out) {
+    return guarded([&] {
+        ADMM_REQUIRE(xy && out && p > 0, "bad arguments");
+        PathSpec s;
+        s.box = true; s.penalty_factor = penalty_factor; s.alpha = alpha; s.box_cols = p;
+        s.check_box_args(p);
+        for (int j = 0; j < p; ++j)
+            ADMM_REQUIRE((!lower_std || lower_std[j] <= 0.f) && (!upper_std || upper_std[j] >= 0.f), "the box must hold zero");
+        float l0 = box_lambda0(xy, p, lower_std, upper_std, penalty_factor);
+        if (s.enet()) l0 = box_lambda0_enet(l0, alpha);
+        *out = l0;
     });
 }
 

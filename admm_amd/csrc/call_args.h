@@ -3,6 +3,7 @@
 #pragma once
 #include "solvers.h"
 #include "sgl_host.h"
+#include "box_host.h"
 
 namespace admm {
 
@@ -27,6 +28,11 @@ struct PathSpec {
     int nresp = 0;
     const double* row_weight = nullptr;
     int mt_rows = 0;                     // p, the length of `row_weight`
+    // box-constrained, weighted elastic net (admm_hip_boxenet): the bounds on the original coefficient scale and the penalty factors as
+    // the ABI passes them (each p long; NULL: no lower bounds / no upper bounds / all factors 1); `alpha` above selects the prox
+    bool box = false;
+    const double* lower = nullptr; const double* upper = nullptr; const double* penalty_factor = nullptr;
+    int box_cols = 0;                    // p, the length of the three
 
     bool enet() const { return alpha >= 0.0; }
     double alpha_eff() const { return enet() ? alpha : 1.0; }
@@ -91,6 +97,25 @@ struct PathSpec {
         ADMM_REQUIRE(any, "at least one row weight must be positive");
         ADMM_REQUIRE(n > p, "the multi-task lasso is built for n > p only");
     }
+    // ... of a box-constrained call, once check_common has passed: a box that holds zero, usable factors, an alpha that names a prox
+    // (check() lets NaN through as "the Lasso"), n > p
+    void check_box_args(int p) const {
+        for (int j = 0; lower != nullptr && j < p; ++j)
+            ADMM_REQUIRE(lower[j] <= 0, "lower bounds must be <= 0 (zero must be feasible) and not NaN");
+        for (int j = 0; upper != nullptr && j < p; ++j)
+            ADMM_REQUIRE(upper[j] >= 0, "upper bounds must be >= 0 (zero must be feasible) and not NaN");
+        bool any = penalty_factor == nullptr;
+        for (int j = 0; penalty_factor != nullptr && j < p; ++j) {
+            ADMM_REQUIRE(std::isfinite(penalty_factor[j]) && penalty_factor[j] >= 0, "penalty factors must be finite and non-negative");
+            any = any || penalty_factor[j] > 0;
+        }
+        ADMM_REQUIRE(any, "at least one penalty factor must be positive");
+        ADMM_REQUIRE(!std::isnan(alpha) && alpha <= 1.0, "alpha must be negative (the Lasso prox) or within [0, 1] (the elastic net's)");
+    }
+    void check_box(int n, int p) const {
+        check_box_args(p);
+        ADMM_REQUIRE(n > p, "the box-constrained elastic net is built for n > p only: the wide solver is not built for bounds");
+    }
     LassoProblem problem(int nworkers, bool dist) const {
         LassoProblem pb;
         pb.opts = *opts;
@@ -117,6 +142,15 @@ struct PathSpec {
         if (nresp > 0) {                    // (checked: check_mt)
             pb.nresp = nresp;
             for (int j = 0; j < mt_rows; ++j) pb.row_weight.push_back(row_weight ? row_weight[j] : 1.0);
+        }
+        if (box) {                          // (checked: check_box)
+            const double inf = std::numeric_limits<double>::infinity();
+            pb.box = true;
+            for (int j = 0; j < box_cols; ++j) {
+                pb.box_lower.push_back(lower ? lower[j] : -inf);
+                pb.box_upper.push_back(upper ? upper[j] : inf);
+                pb.penalty_factor.push_back(penalty_factor ? penalty_factor[j] : 1.0);
+            }
         }
         return pb;
     }

@@ -59,6 +59,13 @@ PlanHandle* create_plan(const double* x, const double* y, int n, int p, int mem,
         ADMM_REQUIRE(!opt_on(Opt::REFINE), "the multi-task lasso has no refined x-update: unset REFINE");
         ADMM_REQUIRE(!comm_info().active, "the multi-task lasso runs on a single device: detach the communicator (admm_hip_comm_finalize)");
     }
+    if (spec.box) {                                         // admm_hip_boxenet: the tall solver on one device, nothing else
+        spec.check_box(n, p);
+        ADMM_REQUIRE(shard.kind == Shard::NONE && nworkers <= 0 && !spec.grouped && spec.nresp == 0,
+                     "the box-constrained elastic net has no sharded, consensus, grouped or multi-response form");
+        ADMM_REQUIRE(!opt_on(Opt::REFINE), "the box-constrained elastic net has no refined x-update: unset REFINE");
+        ADMM_REQUIRE(!comm_info().active, "the box-constrained elastic net runs on a single device: detach the communicator (admm_hip_comm_finalize)");
+    }
     require_device();
     const double t0 = now_s();
     std::unique_ptr<PlanHandle> h(new PlanHandle());

@@ -42,6 +42,7 @@
 #include "symv_kernels.h"
 #include "solvers.h"
 #include "sgl_host.h"
+#include "box_host.h"
 #include "comm.h"
 #include "loop_driver.h"
 #include "plan_host.h"
@@ -526,6 +527,91 @@ tall_group_tail_kernel(TallParams q, int par, GroupTailParams gp) {
     tall_publish_norms(q, par, acc, scratch);
 }
 
+// ---- box-constrained, weighted elastic net (admm_hip_boxenet): the same iteration with a per-coordinate penalty and a clamp as next_z
+//     z_j = clamp(prox_j(v_j), lo_j, hi_j),  v = x + adj_y / rho,  pen_j = lambda u_j / rho  (this order: u_j = 1 gives lambda / rho exactly)
+//     Lasso prox (TallParams.enet == 0):  tall_soft(v_j, pen_j)
+//     elastic net:  thresh = (float)(alpha pen_j), denom = (float)(1 + pen_j (1 - alpha)), (v_j -+ thresh) / denom beyond the threshold, else 0
+// The prox of lambda u_j (alpha |z| + (1 - alpha) z^2 / 2) plus the indicator of [lo_j, hi_j], lo_j <= 0 <= hi_j, is a convex problem
+// in one variable: its minimiser is the unconstrained one moved to the nearest point of the interval, so the clamp makes the prox
+// exact and there is no inner iteration.  lo, hi are in the solver's units, rounded inwards by the host (box_host.h).
+// tall_tail_kernel's geometry: kTailElems coordinates per workgroup, kTailLanes lanes summing a coordinate's partials, no tile list, no
+// LDS beyond the norm scratch.  The owner lane loads u_j, lo_j, hi_j beside the coordinate's other loads -- their addresses need
+// nothing from the control block, so the launch is still one memory round trip.  The products of a discarded x-update are ignored
+// exactly as tall_tail_kernel ignores them (mode 0 keeps the stored x; done returns), so the tiles' early exit stays on.
+// Shared with the other tails as functions: tall_gather_ab, tall_soft, tall_extrapolate, tall_publish_norms.  The choice of
+// (adj_z, adj_y, x) and the second half restate tall_update_elem and must be kept equal to it by hand (see the group tail); with
+// u = 1 and infinite bounds every value here is tall_tail_kernel's, bit for bit.
+struct BoxTailParams {
+    const double* pf;                             // [p] penalty factors u_j
+    const float* lo; const float* hi;             // [p] bounds in the solver's units (+-infinity: none)
+};
+
+template <int MODE>
+__global__ void __launch_bounds__(kTailThreads)
+tall_box_tail_kernel(TallParams q, int par, BoxTailParams bp) {
+#pragma clang fp contract(off)
+    static_assert(MODE == TAIL_GEMV || MODE == TAIL_SYMV, "single device");
+    __shared__ double scratch[6 * (kTailThreads / 64)];
+    const TallCtl c = q.ctl[par ^ 1];
+    const int sub = threadIdx.x & (kTailLanes - 1);
+    const int i = blockIdx.x * kTailElems + threadIdx.x / kTailLanes;
+    const bool valid = i < q.p;
+    const bool owner = valid && sub == 0;
+    TallElem e = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    double pf = 0.0;
+    float lo = 0.f, hi = 0.f;
+    if (owner) { e = tall_load_elem(q, par, i); pf = bp.pf[i]; lo = bp.lo[i]; hi = bp.hi[i]; }
+    float a, b;
+    tall_gather_ab<MODE>(q, i, sub, valid, a, b);
+    if (c.done && c.fin_idx < 0) return;
+
+    double acc[6] = {0, 0, 0, 0, 0, 0};
+    if (owner) {
+        float* zo_ = par ? q.z0 : q.z1; float* yo_ = par ? q.y0 : q.y1;
+        const float zc = e.zc, yc = e.yc, zo = e.zo, yo = e.yo;
+        if (c.fin_idx >= 0) q.beta[(size_t)c.fin_idx * q.p + i] = zc;     // get_z() snapshot (Lasso.cpp:108)
+        if (!c.done) {
+            float adjz, adjy, x;
+            if (c.mode) {
+                if (c.restart) { adjz = zo; adjy = yo; x = b; }
+                else {
+                    const float t = (float)c.tau, t1 = (float)(1.0 + c.tau);
+                    adjz = tall_extrapolate(t1, t, zc, zo);
+                    adjy = tall_extrapolate(t1, t, yc, yo);
+                    x = a;
+                }
+            } else { adjz = e.adjz; adjy = e.adjy; x = e.x; }
+            const float rho_f = (float)c.rho;
+            const float vec = x + adjy / rho_f;
+            const double pen = c.lam * pf / c.rho;
+            float zn;
+            if (!q.enet) zn = tall_soft(vec, pen);
+            else {
+                const float thresh = (float)(q.alpha * pen);
+                const float denom = (float)(1.0 + pen * (1.0 - q.alpha));
+                zn = vec > thresh ? (vec - thresh) / denom : (vec < -thresh ? (vec + thresh) / denom : 0.f);
+            }
+            zn = fminf(fmaxf(zn, lo), hi);
+            const float r = x - zn;
+            const float yn = adjy + rho_f * r;
+            const float dz = zn - zc, daz = zn - adjz;
+            acc[0] = (double)r * r; acc[1] = (double)dz * dz; acc[2] = (double)daz * daz;
+            acc[3] = (double)x * x; acc[4] = (double)zn * zn; acc[5] = (double)yn * yn;
+            q.x[i] = x; zo_[i] = zn; yo_[i] = yn; q.adj_z[i] = adjz; q.adj_y[i] = adjy;
+            if (q.state != nullptr && c.total < q.state_cap) {
+                float* s = q.state + (size_t)c.total * 5 * q.p;
+                s[i] = x; s[q.p + i] = zn; s[2 * (size_t)q.p + i] = yn; s[3 * (size_t)q.p + i] = adjz; s[4 * (size_t)q.p + i] = adjy;
+            }
+            const float tn = (float)c.tau_next, tn1 = (float)(1.0 + c.tau_next);
+            const float adjz_a = tall_extrapolate(tn1, tn, zn, zc), adjy_a = tall_extrapolate(tn1, tn, yn, yc);
+            q.u[i] = (float)((double)(e.xy - adjy_a) + c.rho * (double)adjz_a);
+            q.w[i] = (float)((double)(e.xy - yc) + c.rho * (double)zc);
+        }
+    }
+    if (c.done) return;
+    tall_publish_norms(q, par, acc, scratch);
+}
+
 // ---- multi-task lasso (admm_hip_mtlasso): m responses on ONE cached inverse, a row-wise block soft-threshold
 //     Z_j. = V_j. max(0, 1 - pen_j / ||V_j.||_2),  V = X + adj_Y / rho,  pen_j = lambda w_j / rho
 // The iterates are m planes (x, z, y, adj_z, adj_y: [m][ldv]; the right-hand sides u_k, w_k planes 2k, 2k + 1 of uw), the x-update is
@@ -764,6 +850,11 @@ struct TallPlan final : LassoPlan {
     DevBuf<float> uw, mdot, maxp;                       // [2 mt][ldv] right-hand sides; [2 mt] planes of partials
     DevBuf<double> roww;
     MtTailParams mq{};
+    // box-constrained, weighted elastic net (LassoProblem.box): factors and bounds of every column, the tail tall_box_tail_kernel
+    DevBuf<double> bpf;
+    DevBuf<float> blo, bhi;                             // the bounds in the solver's units, rounded inwards (box_host.h)
+    BoxTailParams bq{};
+    BoxClamp clamp;                                     // the caller's bounds for the recovered coefficients
     PinnedFlag hflag;
 #ifdef ADMM_HIP_PROBE
     DevBuf<long long> probe;
@@ -812,7 +903,11 @@ struct TallPlan final : LassoPlan {
         ADMM_REQUIRE(!grouped || (!shard && !pb.enet && !opt_on(Opt::REFINE) && (int)pb.group_start.size() == (int)pb.group_weight.size() + 1 &&
                                   pb.group_start.back() == p), "internal: the group lasso is the plain single-device tall solver");
         ADMM_REQUIRE(pb.sgl ? grouped && (int)pb.l1_weight.size() == p : pb.l1_weight.empty(), "internal: l1 weights belong to the sparse-group lasso");
-        float lambda0 = grouped ? (pb.sgl ? sgl_plan_lambda0() : group_lambda0()) : (mt ? mt_lambda0() : device_absmax<float>(XY.get(), p, st));
+        ADMM_REQUIRE(!pb.box || (!shard && !grouped && !mt && !opt_on(Opt::REFINE) && (int)pb.box_lower.size() == p &&
+                                 (int)pb.box_upper.size() == p && (int)pb.penalty_factor.size() == p),
+                     "internal: the box-constrained elastic net is the plain single-device tall solver");
+        float lambda0 = pb.box ? box_plan_lambda0()
+                               : (grouped ? (pb.sgl ? sgl_plan_lambda0() : group_lambda0()) : (mt ? mt_lambda0() : device_absmax<float>(XY.get(), p, st)));
         if (pb.enet) lambda0 = (float)(lambda0 / ((double)(float)pb.alpha + 0.0001));
 
         // lambda grid (Lasso.cpp:78-89) and internal lambdas (Lasso.cpp:99), stored as float like `Scalar lambda`
@@ -1011,7 +1106,7 @@ struct TallPlan final : LassoPlan {
         q.ctl = ctl.get(); q.P = P.get(); q.beta = beta.get(); q.niter = niter.get();
         q.done_host = hflag.p;
         // Tiles leave early only where the tail provably ignores the products of a discarded launch: the single-device, unrefined
-        // two-launch forms (tall_tail_kernel<TAIL_SYMV>, tall_group_tail_kernel<TAIL_SYMV>).  Sharded, refined and multi-task x-updates
+        // two-launch forms (tall_tail_kernel<TAIL_SYMV>, tall_group_tail_kernel<TAIL_SYMV>, tall_box_tail_kernel<TAIL_SYMV>).  Sharded, refined and multi-task x-updates
         // have consumers of their own between the stream and the tail.  ADMM_HIP_SYMV_VERDICT=0 turns it off, 1 keeps only the check in the tile prologue (A/B, tests).
         verdict_on = use_sym && !shard && !refine && !mt && !opt_off(Opt::SYMV_VERDICT);
         verdict_mid = opt_int(Opt::SYMV_VERDICT, 2) == 2;      // default: the waves also look between the chunks of their column loop
@@ -1046,6 +1141,25 @@ struct TallPlan final : LassoPlan {
         }
         ADMM_HIP_CHECK(hipHostMalloc(reinterpret_cast<void**>(&hbeta), (size_t)nlam * p * npl * sizeof(float), hipHostMallocDefault));
         comm_stream_sync(st);
+    }
+
+    // The box-constrained elastic net's set-up: the caller's bounds into the solver's units with the standardisation this data got
+    // (scaleX is 1 where the columns were not scaled, scaleY 1 where nothing was), rounded inwards; factors and bounds to the device;
+    // lambda_0 from X'y on the host (box_host.h; no bounds, u = 1: device_absmax's value to the bit)
+    float box_plan_lambda0() {
+        std::vector<float> lo(p), hi(p), h(p);
+        for (int j = 0; j < p; ++j) {
+            lo[j] = box_round_lower(box_to_std(pb.box_lower[j], (double)d.scaleX[j], (double)d.scaleY));
+            hi[j] = box_round_upper(box_to_std(pb.box_upper[j], (double)d.scaleX[j], (double)d.scaleY));
+        }
+        clamp.set(pb.box_lower, pb.box_upper);
+        bpf.alloc((size_t)p); blo.alloc((size_t)p); bhi.alloc((size_t)p);
+        ADMM_HIP_CHECK(hipMemcpyAsync(bpf.get(), pb.penalty_factor.data(), (size_t)p * sizeof(double), hipMemcpyHostToDevice, st));
+        ADMM_HIP_CHECK(hipMemcpyAsync(blo.get(), lo.data(), (size_t)p * sizeof(float), hipMemcpyHostToDevice, st));
+        ADMM_HIP_CHECK(hipMemcpyAsync(bhi.get(), hi.data(), (size_t)p * sizeof(float), hipMemcpyHostToDevice, st));
+        read_back(h.data(), XY.get(), (size_t)p * sizeof(float), st);      // (synchronises: the host vectors may go out of scope)
+        bq.pf = bpf.get(); bq.lo = blo.get(); bq.hi = bhi.get();
+        return box_lambda0(h.data(), p, lo.data(), hi.data(), pb.penalty_factor.data());
     }
 
     // lambda_0 of the multi-task lasso: the largest ||(X'Y)_j.||_2 / w_j over the penalised rows, the norm in double from the float X'Y,
@@ -1256,6 +1370,10 @@ struct TallPlan final : LassoPlan {
                                    ruw.get(), ruw.get() + ldv, skip);
                 sy.launch(M.get(), ldp, ruw.get(), ruw.get() + ldv, skip, st, SymvNoExtra());
                 hipLaunchKernelGGL(tall_tail_kernel<TAIL_SYMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, PeerExchange{});
+            } else if (pb.box) {                       // two launches, as the Lasso
+                xupdate();
+                if (use_sym) hipLaunchKernelGGL(tall_box_tail_kernel<TAIL_SYMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, bq);
+                else hipLaunchKernelGGL(tall_box_tail_kernel<TAIL_GEMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, bq);
             } else {
                 xupdate();
                 if (use_sym) hipLaunchKernelGGL(tall_tail_kernel<TAIL_SYMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, PeerExchange{});
@@ -1291,7 +1409,7 @@ struct TallPlan final : LassoPlan {
                 for (int l = 0; l < nlam; ++l) std::memcpy(res.beta.data() + ((size_t)l * mt + k) * col, bk.data() + (size_t)l * col, col * sizeof(float));
             }
         } else {
-            S.total_iter = read_out_path<float>(d, hbeta, nlam, niter.get(), (size_t)p + 1, 0, res.niter, res.beta);
+            S.total_iter = read_out_path<float>(d, hbeta, nlam, niter.get(), (size_t)p + 1, 0, res.niter, res.beta, INT_MAX, 0, nullptr, &clamp);
         }
         decisions = hctl.c[0].done ? hctl.total() : 0;      // (the sticky no-op decisions after `done` do not write)
         res.stats = S;

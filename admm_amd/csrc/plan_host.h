@@ -4,6 +4,7 @@
 #pragma once
 #include "solvers.h"
 #include "comm.h"
+#include "box_host.h"
 #include <climits>
 
 namespace admm {
@@ -24,11 +25,13 @@ int make_path_grid(const LassoProblem& pb, double lambda0, long long n, double s
 // Lasso.cpp:108-111) from the host snapshots `snap` (nlam x d.p) -- column l of `beta` is `stride` long, row 0 the intercept, this
 // solver's columns from row 1 + col_offset.  Returns the sum of the counts, each clipped to `niter_clip`.  snap_stride: distance between the
 // snapshots of two lambdas (0: d.p; the multi-task plan keeps m of them per lambda and reads them out response by response, each with
-// its own mean `mean_y`; NULL: d.meanY).
+// its own mean `mean_y`; NULL: d.meanY).  box (admm_hip_boxenet; box_host.h): the recovered coefficients are clamped to the caller's
+// bounds, and where the clamp moved one the intercept is taken again from the clamped coefficients (recover_coef's sum, in its order);
+// a path that the clamp leaves alone -- every path without bounds -- keeps recover_coef's bits.
 template <typename T>
 long long read_out_path(const DeviceData<T>& d, const T* snap, int nlam, const int* dev_niter, size_t stride, long long col_offset,
                         std::vector<int>& niter, std::vector<T>& beta, int niter_clip = INT_MAX, size_t snap_stride = 0,
-                        const T* mean_y = nullptr) {
+                        const T* mean_y = nullptr, const BoxClamp* box = nullptr) {
     if (snap_stride == 0) snap_stride = (size_t)d.p;
     niter.assign(nlam, 0);
     ADMM_HIP_CHECK(hipMemcpy(niter.data(), dev_niter, (size_t)nlam * sizeof(int), hipMemcpyDeviceToHost));
@@ -36,7 +39,13 @@ long long read_out_path(const DeviceData<T>& d, const T* snap, int nlam, const i
     long long tot = 0;
     for (int l = 0; l < nlam; ++l) {
         T b0 = 0;
-        recover_coef<T>(d, mean_y ? *mean_y : d.meanY, snap + (size_t)l * snap_stride, &b0, beta.data() + (size_t)l * stride + 1 + col_offset);
+        T* out = beta.data() + (size_t)l * stride + 1 + col_offset;
+        recover_coef<T>(d, mean_y ? *mean_y : d.meanY, snap + (size_t)l * snap_stride, &b0, out);
+        if (box != nullptr && box->on() && box->apply(out, d.p) && (d.flag & 2)) {
+            T acc = T(0);
+            for (int j = 0; j < d.p; ++j) acc += out[j] * d.meanX[j];
+            b0 = (mean_y ? *mean_y : d.meanY) - acc;
+        }
         beta[(size_t)l * stride] = b0;
         tot += std::min(niter[l], niter_clip);
     }

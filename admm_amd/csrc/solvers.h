@@ -30,6 +30,11 @@ struct LassoProblem {
     // coefficient matrix is penalised by row_weight[j] * its Euclidean norm; 0 = an ordinary single-response problem
     int nresp = 0;
     std::vector<double> row_weight;
+    // box-constrained, weighted elastic net (admm_hip_boxenet, tall solver only; box_host.h): box_lower / box_upper [p] are the caller's
+    // bounds on the ORIGINAL coefficient scale (+-infinity where there is none), penalty_factor [p] the factors u_j; `enet` / `alpha`
+    // above select the prox as for admm_hip_lasso / admm_hip_enet
+    bool box = false;
+    std::vector<double> box_lower, box_upper, penalty_factor;
 };
 
 struct LassoResult {

@@ -340,6 +340,44 @@ ADMM_HIP_API int admm_hip_sgl_plan_create(const double* x, const double* y, int 
                                           int standardize, int intercept, const admm_opts* opts,
                                           admm_hip_plan** plan_out, int* nlambda_out);
 
+/* Box-constrained, weighted elastic net on the tall path (n > p only; not in the reference package; glmnet's lower.limits /
+ * upper.limits / penalty.factor for family = "gaussian", scikit-learn's positive = True):
+ *     minimise 1/2 ||y_s - X_s b||^2 + lambda_int sum_j u_j [ alpha |b_j| + (1 - alpha)/2 b_j^2 ]   subject to   lo_j <= b_j <= hi_j
+ * in the solver's internal units (standardised X_s, y_s; lambda_int = lambda n / scaleY), as admm_hip_lasso.  The iteration is the
+ * Lasso's with the z-update  prox of coordinate j's penalty, then clamp to [lo_j, hi_j]  -- the exact minimiser of the one-dimensional
+ * convex problem, because the box holds zero (lasso_tall.hip, tall_box_tail_kernel); the lambda path, the stopping rule, niter and the
+ * outputs are admm_hip_lasso's.
+ * alpha < 0 selects the Lasso prox (admm_hip_lasso's: compare in double), 0 <= alpha <= 1 the elastic net's (admm_hip_enet's: float
+ * threshold and denominator), the convention of admm_hip_lasso_cv; alpha > 1 or NaN is refused.
+ * penalty_factor[p] >= 0: u_j multiplies the WHOLE penalty of column j, both parts (glmnet's penalty.factor, not rescaled); NULL = all
+ * 1; 0 leaves the column unpenalised; a call without a positive factor is refused.
+ * lower[p], upper[p]: bounds on the ORIGINAL coefficient scale, NULL = none, -+infinity entries allowed.  lower_j <= 0 <= upper_j is
+ * required and NaN refused (glmnet's rule: zero stays feasible, so the cold start and the empty model at lambda_0 stay valid);
+ * lower_j = upper_j = 0 excludes column j.  The bounds go into the solver's units once, lower_j scaleX_j / scaleY in double, rounded to
+ * float towards the inside of the box.  Every returned coefficient is clamped to the caller's bounds rounded inwards to float, and the
+ * intercept is computed from the clamped coefficients: lower_j <= beta_j <= upper_j holds exactly in beta_out.
+ * Without bounds and factors the call is admm_hip_lasso (alpha < 0) or admm_hip_enet bit for bit (grid, coefficients, niter, decision
+ * trace); with factors alone and alpha < 0 it is admm_hip_sgl at alpha = 1 with l1_weight = penalty_factor.
+ * Limits: single device; no wide (n <= p), row-sharded, consensus, refined (REFINE set: refused), cross-validated or multi-response
+ * form; an attached communicator is refused; bounds that exclude zero are refused.  The group, sparse-group and multi-task penalties
+ * take no bounds (a clamp after a block shrink is not their prox).
+ * Automatic grid: with c = X_s'y_s, lambda_0 = max over u_j > 0 of g_j / u_j, g_j = max(c_j if upper_j > 0 else 0, -c_j if lower_j < 0
+ * else 0) -- the smallest lambda at which no penalised coordinate may leave zero -- in double from the float c, rounded to float; the
+ * elastic net divides by alpha + 1e-4 as admm_hip_enet.  With unpenalised columns present the first lambda of that grid is NOT
+ * guaranteed to give an empty penalised model (the unpenalised columns have not been fitted when lambda_0 is taken): pass a grid of
+ * your own there.
+ * The plan is an ordinary admm_hip_plan: admm_hip_lasso_plan_run / _trace_* / _state_* / _destroy work on it. */
+ADMM_HIP_API int admm_hip_boxenet(const double* x, const double* y, int n, int p, int mem,
+                                  const double* lower, const double* upper, const double* penalty_factor, double alpha,
+                                  const double* lambda_in, int nlambda_in, int nlambda_auto, double lmin_ratio,
+                                  int standardize, int intercept, const admm_opts* opts,
+                                  double* lambda_out, float* beta_out, int* niter_out, admm_stats* stats);
+ADMM_HIP_API int admm_hip_boxenet_plan_create(const double* x, const double* y, int n, int p, int mem,
+                                              const double* lower, const double* upper, const double* penalty_factor, double alpha,
+                                              const double* lambda_in, int nlambda_in, int nlambda_auto, double lmin_ratio,
+                                              int standardize, int intercept, const admm_opts* opts,
+                                              admm_hip_plan** plan_out, int* nlambda_out);
+
 /* Multi-task lasso on the tall path (n > p only; not in the reference package; glmnet's family = "mgaussian", scikit-learn's
  * MultiTaskLasso): m responses on one design, one row-wise penalty that selects a feature for all responses at once,
  *     minimise over b0 (m), B (p x m):  1/(2n) ||Y - 1 b0' - X B||_F^2 + lambda sum_j w_j ||B_j.||_2 ,
@@ -587,6 +625,12 @@ ADMM_HIP_API int admm_hip_host_lanczos(const float* A, int n, float* eig_out, in
  * routine the plan calls (sgl_host.h).  Runs without a GPU (CPU test-suite). */
 ADMM_HIP_API int admm_hip_host_sgl_lambda0(const float* xy, int p, const int* group, const double* group_weight, int ngroups,
                                            const double* l1_weight, double alpha, float* out);
+
+/* lambda_0 of admm_hip_boxenet's automatic grid from a given c = X_s'y_s (xy, HOST, length p) and bounds ALREADY in the solver's units
+ * (lower_std, upper_std: HOST floats, length p, NULL = none), penalty_factor and alpha as admm_hip_boxenet: the host routine the plan
+ * calls (box_host.h), with the elastic net's division for alpha >= 0.  Runs without a GPU (CPU test-suite). */
+ADMM_HIP_API int admm_hip_host_box_lambda0(const float* xy, int p, const float* lower_std, const float* upper_std,
+                                           const double* penalty_factor, double alpha, float* out);
 
 /* The tall x-update mat-vec exactly as the solver runs it for p >= 2048: symv2_lower_kernel on the lower triangle of
  * the symmetric p x p float matrix A (HOST, column-major, leading dimension p) against the two right-hand sides

@@ -152,6 +152,32 @@ BEGIN_RCPP
 END_RCPP
 }
 
+// Box-constrained, weighted elastic net (not in the reference; include/admm_hip.h, admm_hip_boxenet): the arguments of admm_enet plus
+// `lower` / `upper`, bounds on the coefficients on the original scale (one per column or numeric(0) for none; lower <= 0 <= upper,
+// -Inf / Inf allowed), and `penalty_factor`, one factor per column or numeric(0) for all 1.  alpha < 0 selects the Lasso prox.  n > p only.
+RcppExport SEXP admm_boxenet(SEXP x_, SEXP y_, SEXP lambda_, SEXP nlambda_, SEXP lmin_ratio_,
+                             SEXP standardize_, SEXP intercept_, SEXP lower_, SEXP upper_, SEXP penalty_factor_, SEXP alpha_, SEXP opts_) {
+BEGIN_RCPP
+    NumericMatrix x(x_);
+    NumericVector y(y_), lambda(lambda_), lower(lower_), upper(upper_), penalty_factor(penalty_factor_);
+    const int n = x.nrow(), p = x.ncol();
+    if (lower.size() != 0 && lower.size() != p) Rcpp::stop("lower should have one entry per column");
+    if (upper.size() != 0 && upper.size() != p) Rcpp::stop("upper should have one entry per column");
+    if (penalty_factor.size() != 0 && penalty_factor.size() != p) Rcpp::stop("penalty_factor should have one entry per column");
+    const int nl_in = lambda.size();
+    const int nl = nl_in > 0 ? nl_in : as<int>(nlambda_);
+    admm_opts o = unpack_opts(opts_);
+    NumericVector lambda_out(nl);
+    IntegerVector niter(nl);
+    std::vector<float> beta((size_t)(p + 1) * nl);
+    check(admm_hip_boxenet(x.begin(), y.begin(), n, p, ADMM_MEM_HOST, lower.size() ? lower.begin() : nullptr, upper.size() ? upper.begin() : nullptr,
+                           penalty_factor.size() ? penalty_factor.begin() : nullptr, as<double>(alpha_),
+                           nl_in > 0 ? lambda.begin() : nullptr, nl_in, as<int>(nlambda_), as<double>(lmin_ratio_),
+                           as<bool>(standardize_), as<bool>(intercept_), &o, lambda_out.begin(), beta.data(), niter.begin(), nullptr));
+    return List::create(Named("lambda") = lambda_out, Named("beta") = to_dgCMatrix(beta, p + 1, nl), Named("niter") = niter);
+END_RCPP
+}
+
 // Multi-task lasso (not in the reference; include/admm_hip.h, admm_hip_mtlasso): the arguments of admm_lasso with an n x m matrix Y
 // in the place of y, plus `row_weight`, one weight per column of x or numeric(0) for all 1.  n > p only, m <= ADMM_HIP_MT_MAX.
 // beta: a (p + 1) x (m * nlambda) dgCMatrix, column l * m + k = response k at lambda l (intercept first).
