@@ -84,6 +84,11 @@ GROUP_MAX = 1024          # ADMM_HIP_GROUP_MAX
 MT_MAX = 16               # ADMM_HIP_MT_MAX
 MT_RHS_BUILT = (2, 4, 8, 12)      # right-hand sides per pass the multi-vector kernel is built for (option MT_RHS; 0 = automatic)
 
+# the entry points of the tall-only penalties (each with its <name>_plan_create): the argument types that replace [at:5] of the Lasso's
+_GROUP_ARGS = [_c_int_p, _c_double_p, ctypes.c_int]
+TALL_ONLY = [("admm_hip_grplasso", _GROUP_ARGS, 5), ("admm_hip_sgl", _GROUP_ARGS + [_c_double_p, ctypes.c_double], 5),
+             ("admm_hip_boxenet", [_c_double_p] * 3 + [ctypes.c_double], 5), ("admm_hip_mtlasso", [ctypes.c_int, ctypes.c_int, _c_double_p], 4)]
+
 TRACE_FIELDS = 12
 TRACE_COLD, TRACE_CONVERGED, TRACE_ACCELERATE, TRACE_RESTART = -1, 0, 1, 2
 TRACE_CONTINUE = 1
@@ -164,30 +169,14 @@ def load():
     lib.admm_hip_lasso_plan_create.argtypes = lasso_args + [ctypes.c_double, ctypes.c_int, ctypes.POINTER(AdmmOpts),
                                                ctypes.POINTER(ctypes.c_void_p), _c_int_p]
     lib.admm_hip_lasso_plan_create.restype = ctypes.c_int
-    grp_args = lasso_args[:5] + [_c_int_p, _c_double_p, ctypes.c_int] + lasso_args[5:]
-    lib.admm_hip_grplasso.argtypes = grp_args + tail
-    lib.admm_hip_grplasso.restype = ctypes.c_int
-    lib.admm_hip_grplasso_plan_create.argtypes = grp_args + [ctypes.POINTER(AdmmOpts), ctypes.POINTER(ctypes.c_void_p), _c_int_p]
-    lib.admm_hip_grplasso_plan_create.restype = ctypes.c_int
-    sgl_args = grp_args[:8] + [_c_double_p, ctypes.c_double] + grp_args[8:]
-    lib.admm_hip_sgl.argtypes = sgl_args + tail
-    lib.admm_hip_sgl.restype = ctypes.c_int
-    lib.admm_hip_sgl_plan_create.argtypes = sgl_args + [ctypes.POINTER(AdmmOpts), ctypes.POINTER(ctypes.c_void_p), _c_int_p]
-    lib.admm_hip_sgl_plan_create.restype = ctypes.c_int
+    for name, extra, at in TALL_ONLY:
+        args = lasso_args[:at] + extra + lasso_args[5:]
+        for fn, rest in ((getattr(lib, name), tail), (getattr(lib, name + "_plan_create"), [tail[0], ctypes.POINTER(ctypes.c_void_p), _c_int_p])):
+            fn.argtypes, fn.restype = args + rest, ctypes.c_int
     lib.admm_hip_host_sgl_lambda0.argtypes = [_c_float_p, ctypes.c_int, _c_int_p, _c_double_p, ctypes.c_int, _c_double_p, ctypes.c_double, _c_float_p]
     lib.admm_hip_host_sgl_lambda0.restype = ctypes.c_int
-    box_args = lasso_args[:5] + [_c_double_p, _c_double_p, _c_double_p, ctypes.c_double] + lasso_args[5:]
-    lib.admm_hip_boxenet.argtypes = box_args + tail
-    lib.admm_hip_boxenet.restype = ctypes.c_int
-    lib.admm_hip_boxenet_plan_create.argtypes = box_args + [ctypes.POINTER(AdmmOpts), ctypes.POINTER(ctypes.c_void_p), _c_int_p]
-    lib.admm_hip_boxenet_plan_create.restype = ctypes.c_int
     lib.admm_hip_host_box_lambda0.argtypes = [_c_float_p, ctypes.c_int, _c_float_p, _c_float_p, _c_double_p, ctypes.c_double, _c_float_p]
     lib.admm_hip_host_box_lambda0.restype = ctypes.c_int
-    mt_args = lasso_args[:4] + [ctypes.c_int, ctypes.c_int, _c_double_p] + lasso_args[5:]
-    lib.admm_hip_mtlasso.argtypes = mt_args + tail
-    lib.admm_hip_mtlasso.restype = ctypes.c_int
-    lib.admm_hip_mtlasso_plan_create.argtypes = mt_args + [ctypes.POINTER(AdmmOpts), ctypes.POINTER(ctypes.c_void_p), _c_int_p]
-    lib.admm_hip_mtlasso_plan_create.restype = ctypes.c_int
     lib.admm_hip_lasso_plan_run.argtypes = [ctypes.c_void_p, _c_double_p, _c_float_p, _c_int_p, ctypes.POINTER(AdmmStats)]
     lib.admm_hip_lasso_plan_run.restype = ctypes.c_int
     lib.admm_hip_lasso_plan_destroy.argtypes = [ctypes.c_void_p]

@@ -192,7 +192,7 @@ class ADMM_Lasso:
         lam_in = np.ascontiguousarray(self.lambda_, dtype=np.float64)
         o = AdmmOpts(self.maxit, self.eps_abs, self.eps_rel, self.rho)
         lam_out = np.zeros(nl, dtype=np.float64)
-        beta = np.zeros((self.p + 1, nl), dtype=np.float32, order="F")
+        beta = self._beta_buffer(nl)
         niter = np.zeros(nl, dtype=np.int32)
         stats = AdmmStats()
         head = (xp, yp, self.n, self.p, xmem,
@@ -259,6 +259,19 @@ class ADMM_Lasso:
             fbeta = np.transpose(fbeta, (0, 2, 1))                               # [fold][p + 1][lambda]
         return ADMM_Lasso_cv(fit, cvm, cvse, fmse, fnit, fbeta, imin.value, i1se.value)
 
+    # -- what LassoPlan asks of a model: the entry point that creates its plan with the arguments between the path's and opts, the
+    # coefficient buffer of a path of nl lambdas and the result object
+    _plan_entry = "admm_hip_lasso_plan_create"
+
+    def _plan_args(self, head):
+        return head + (-1.0, int(self.nthread))
+
+    def _beta_buffer(self, nl):
+        return np.zeros((self.p + 1, nl), dtype=np.float32, order="F")
+
+    def _result(self, lam, beta, niter, stats):
+        return ADMM_Lasso_fit(lam, beta, niter, stats)
+
     def fit(self):
         lib, head, tail, lam_out, beta, niter, stats, keep = self._common()
         if self.nthread <= 1:
@@ -305,6 +318,9 @@ class ADMM_Enet(ADMM_Lasso):
             _stop("alpha must be within [0, 1]")                                 # R/40_admm_enet.R:38-39
         self.alpha = float(alpha)
         return self
+
+    def _plan_args(self, head):
+        return head + (float(self.alpha), int(self.nthread))
 
     def fit(self):
         lib, head, tail, lam_out, beta, niter, stats, keep = self._common()
@@ -555,44 +571,24 @@ class LassoPlan:
         yp, ymem, yk = as_input(model.y)
         lam_in = np.ascontiguousarray(model.lambda_, dtype=np.float64)
         o = AdmmOpts(model.maxit, model.eps_abs, model.eps_rel, model.rho)
-        alpha = float(model.alpha) if isinstance(model, ADMM_Enet) else -1.0
         h = ctypes.c_void_p()
         nl = ctypes.c_int()
-        path = (ctypes.c_void_p(lam_in.ctypes.data if lam_in.size else 0), int(lam_in.size),
+        head = (xp, yp, model.n, model.p, xmem, ctypes.c_void_p(lam_in.ctypes.data if lam_in.size else 0), int(lam_in.size),
                 model.nlambda, model.lambda_min_ratio, int(model.standardize), int(model.intercept))
-        if isinstance(model, ADMM_MTLasso):
-            check(lib.admm_hip_mtlasso_plan_create(xp, yp, model.n, model.p, model.m, xmem, model._weight_arg(), *path,
-                                                   ctypes.byref(o), ctypes.byref(h), ctypes.byref(nl)))
-        elif isinstance(model, ADMM_BoxEnet):
-            check(lib.admm_hip_boxenet_plan_create(xp, yp, model.n, model.p, xmem, *model._box_args(), *path,
-                                                   ctypes.byref(o), ctypes.byref(h), ctypes.byref(nl)))
-        elif isinstance(model, ADMM_SGL):
-            check(lib.admm_hip_sgl_plan_create(xp, yp, model.n, model.p, xmem, *model._group_args(), *path,
-                                               ctypes.byref(o), ctypes.byref(h), ctypes.byref(nl)))
-        elif isinstance(model, ADMM_GrpLasso):
-            check(lib.admm_hip_grplasso_plan_create(xp, yp, model.n, model.p, xmem, *model._group_args(), *path,
-                                                    ctypes.byref(o), ctypes.byref(h), ctypes.byref(nl)))
-        else:
-            check(lib.admm_hip_lasso_plan_create(xp, yp, model.n, model.p, xmem, *path, alpha,
-                                                 int(model.nthread), ctypes.byref(o), ctypes.byref(h), ctypes.byref(nl)))
+        check(getattr(lib, model._plan_entry)(*model._plan_args(head), ctypes.byref(o), ctypes.byref(h), ctypes.byref(nl)))
         self._h = h
         self.nlambda = nl.value
 
     def run(self):
         m = self.model
         lam_out = np.zeros(self.nlambda, dtype=np.float64)
-        mt = isinstance(m, ADMM_MTLasso)
-        beta = np.zeros((self.nlambda, m.m, m.p + 1), dtype=np.float32) if mt else np.zeros((m.p + 1, self.nlambda), dtype=np.float32, order="F")
+        beta = m._beta_buffer(self.nlambda)
         niter = np.zeros(self.nlambda, dtype=np.int32)
         stats = AdmmStats()
         check(self._lib.admm_hip_lasso_plan_run(self._h, lam_out.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
                                                 beta.ctypes.data_as(ctypes.POINTER(ctypes.c_float)),
                                                 niter.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), ctypes.byref(stats)))
-        if mt:
-            return ADMM_MTLasso_fit(lam_out, beta, niter, stats.as_dict())
-        if isinstance(m, ADMM_GrpLasso):
-            beta = m._restore(beta)
-        return ADMM_Lasso_fit(lam_out, beta, niter, stats.as_dict())
+        return m._result(lam_out, beta, niter, stats.as_dict())
 
     def enable_trace(self, capacity=1 << 18):
         """Record one decision record per ADMM iteration of the following run() calls (tall path only)."""
@@ -707,7 +703,62 @@ def admm_dantzig(x, y, intercept=True, standardize=True, **kw):
     return ADMM_Dantzig(x, y, intercept, standardize, **kw)
 
 
-class ADMM_GrpLasso(ADMM_Lasso):
+def _weights(a, size, size_msg, bad_msg, positive_msg=None):
+    """A weight argument of a tall-only penalty as the library takes it: `size` float64 values, finite and non-negative and, where
+    positive_msg is given, not all zero."""
+    w = np.ascontiguousarray(np.asarray(a, dtype=np.float64).ravel())
+    if w.size != size:
+        _stop(size_msg)
+    if not np.all(np.isfinite(w)) or np.any(w < 0):
+        _stop(bad_msg)
+    if positive_msg is not None and not np.any(w > 0):
+        _stop(positive_msg)
+    return w
+
+
+def _dp(a):
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if a is not None else None
+
+
+class _TallOnly(ADMM_Lasso):
+    """What the builders of the tall-only penalties share (n > p, one device): the refusals and one fit() / plan creation, driven by
+    per-class data -- _entry (the C entry point; its plan form is <_entry>_plan_create), _tall_only and _missing (the refusals' texts),
+    _title (of the fit; None: the result has its own) -- and by _extra_args(head), which replace head[_extra_at:5] of the Lasso's
+    arguments.  _beta_buffer and _result are ADMM_Lasso's hooks."""
+    _extra_at = 5
+    _title = None
+
+    def __init__(self, x, y, intercept=True, standardize=True, n=None, p=None):
+        super().__init__(x, y, intercept, standardize, n, p)
+        if self.n <= self.p:
+            _stop("nrow(x) must be greater than ncol(x): " + self._tall_only)
+
+    def parallel(self, *a, **kw):
+        _stop(self._missing)
+
+    def cv(self, *a, **kw):
+        _stop(self._missing)
+
+    def fit_responses(self, *a, **kw):
+        _stop(self._missing)
+
+    @property
+    def _plan_entry(self):
+        return self._entry + "_plan_create"
+
+    def _plan_args(self, head):                                      # (what leads the arguments of a fit too)
+        return head[:self._extra_at] + tuple(self._extra_args(head)) + head[5:]
+
+    def fit(self):
+        lib, head, tail, lam_out, beta, niter, stats, keep = self._common()
+        check(getattr(lib, self._entry)(*self._plan_args(head), *tail))
+        fit = self._result(lam_out, beta, niter, stats.as_dict())
+        if self._title is not None:
+            fit._title = self._title
+        return fit
+
+
+class ADMM_GrpLasso(_TallOnly):
     """Group lasso on the tall path (admm_hip_grplasso; n > p only, one device): `group` gives one label per column, columns with
     the same label enter or leave the model together.  Labels are arbitrary; the groups are numbered in order of first appearance
     (`group_labels`), and that is the order of `group_weights`.  The library wants the columns of a group adjacent: host input
@@ -715,11 +766,11 @@ class ADMM_GrpLasso(ADMM_Lasso):
     place, so scattered groups are refused for it."""
     _name = "ADMM Group Lasso model"
     _missing = "not available for the group lasso (single-device tall solver only)"
+    _tall_only = "the group lasso is built for n > p only"
+    _entry, _title = "admm_hip_grplasso", "ADMM Group Lasso fitting result"
 
     def __init__(self, x, y, group, intercept=True, standardize=True, n=None, p=None):
         super().__init__(x, y, intercept, standardize, n, p)
-        if self.n <= self.p:
-            _stop("nrow(x) must be greater than ncol(x): the group lasso is built for n > p only")
         g = np.asarray(group).ravel()
         if g.size != self.p:
             _stop("group should have length ncol(x)")
@@ -745,34 +796,21 @@ class ADMM_GrpLasso(ADMM_Lasso):
 
     def penalty(self, lambda_=None, nlambda=100, lambda_min_ratio=None, group_weights=None, **kw):
         super().penalty(lambda_, nlambda, lambda_min_ratio, **kw)
-        if group_weights is not None:
-            w = np.ascontiguousarray(np.asarray(group_weights, dtype=np.float64).ravel())
-            if w.size != self.ngroups:
-                _stop("group_weights should have one entry per group (in order of first appearance)")
-            if not np.all(np.isfinite(w)) or np.any(w < 0):
-                _stop("group_weights must be finite and non-negative")
-            if not np.any(w > 0):
-                _stop("at least one group weight must be positive")
-            group_weights = w
-        self.group_weights = group_weights
+        self.group_weights = None if group_weights is None else self._group_weights(group_weights, "at least one group weight must be positive")
         return self
+
+    def _group_weights(self, w, positive_msg=None):
+        return _weights(w, self.ngroups, "group_weights should have one entry per group (in order of first appearance)",
+                        "group_weights must be finite and non-negative", positive_msg)
 
     def effective_weights(self):
         return np.sqrt(self.group_sizes.astype(np.float64)) if self.group_weights is None else self.group_weights
 
-    def parallel(self, *a, **kw):
-        _stop(self._missing)
-
-    def cv(self, *a, **kw):
-        _stop(self._missing)
-
-    def fit_responses(self, *a, **kw):
-        _stop(self._missing)
-
     def _group_args(self):
-        w = self.group_weights
-        return (self.group.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
-                w.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if w is not None else None, self.ngroups)
+        return self.group.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), _dp(self.group_weights), self.ngroups
+
+    def _extra_args(self, head):
+        return self._group_args()
 
     def _restore(self, beta):
         """Coefficient rows back into the caller's column order (row 0 is the intercept)."""
@@ -783,12 +821,8 @@ class ADMM_GrpLasso(ADMM_Lasso):
         out[1 + self._perm] = beta[1:]
         return out
 
-    def fit(self):
-        lib, head, tail, lam_out, beta, niter, stats, keep = self._common()
-        check(lib.admm_hip_grplasso(*head[:5], *self._group_args(), *head[5:], *tail))
-        fit = ADMM_Lasso_fit(lam_out, self._restore(beta), niter, stats.as_dict())
-        fit._title = "ADMM Group Lasso fitting result"
-        return fit
+    def _result(self, lam, beta, niter, stats):
+        return ADMM_Lasso_fit(lam, self._restore(beta), niter, stats)
 
 
 def admm_grplasso(x, y, group, intercept=True, standardize=True, **kw):
@@ -802,6 +836,7 @@ class ADMM_SGL(ADMM_GrpLasso):
     columns when scattered groups are reordered.  alpha = 0 is the group lasso, alpha = 1 the Lasso with penalty factors u."""
     _name = "ADMM Sparse-Group Lasso model"
     _missing = "not available for the sparse-group lasso (single-device tall solver only)"
+    _entry, _title = "admm_hip_sgl", "ADMM Sparse-Group Lasso fitting result"
 
     def __init__(self, x, y, group, alpha=0.95, intercept=True, standardize=True, n=None, p=None):
         super().__init__(x, y, group, intercept, standardize, n, p)
@@ -813,19 +848,10 @@ class ADMM_SGL(ADMM_GrpLasso):
 
     def penalty(self, lambda_=None, nlambda=100, lambda_min_ratio=None, group_weights=None, l1_weights=None, **kw):
         ADMM_Lasso.penalty(self, lambda_, nlambda, lambda_min_ratio, **kw)
-        w = u = None
-        if group_weights is not None:
-            w = np.ascontiguousarray(np.asarray(group_weights, dtype=np.float64).ravel())
-            if w.size != self.ngroups:
-                _stop("group_weights should have one entry per group (in order of first appearance)")
-            if not np.all(np.isfinite(w)) or np.any(w < 0):
-                _stop("group_weights must be finite and non-negative")
+        w = None if group_weights is None else self._group_weights(group_weights)
+        u = None
         if l1_weights is not None:
-            u = np.asarray(l1_weights, dtype=np.float64).ravel()
-            if u.size != self.p:
-                _stop("l1_weights should have one entry per column")
-            if not np.all(np.isfinite(u)) or np.any(u < 0):
-                _stop("l1_weights must be finite and non-negative")
+            u = _weights(l1_weights, self.p, "l1_weights should have one entry per column", "l1_weights must be finite and non-negative")
             u = np.ascontiguousarray(u if self._perm is None else u[self._perm])      # library column k = caller's column _perm[k]
         wg = (1.0 - self.alpha) * (np.ones(self.ngroups) if w is None else w)
         l1 = self.alpha * (np.ones(self.p) if u is None else u)
@@ -835,22 +861,14 @@ class ADMM_SGL(ADMM_GrpLasso):
         return self
 
     def _group_args(self):
-        u = self.l1_weights
-        return super()._group_args() + (u.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if u is not None else None, self.alpha)
-
-    def fit(self):
-        lib, head, tail, lam_out, beta, niter, stats, keep = self._common()
-        check(lib.admm_hip_sgl(*head[:5], *self._group_args(), *head[5:], *tail))
-        fit = ADMM_Lasso_fit(lam_out, self._restore(beta), niter, stats.as_dict())
-        fit._title = "ADMM Sparse-Group Lasso fitting result"
-        return fit
+        return super()._group_args() + (_dp(self.l1_weights), self.alpha)
 
 
 def admm_sgl(x, y, group, alpha=0.95, intercept=True, standardize=True, **kw):
     return ADMM_SGL(x, y, group, alpha, intercept, standardize, **kw)
 
 
-class ADMM_BoxEnet(ADMM_Lasso):
+class ADMM_BoxEnet(_TallOnly):
     """Box-constrained, weighted elastic net on the tall path (admm_hip_boxenet; n > p only, one device): the Lasso (alpha=None) or the
     elastic net (0 <= alpha <= 1) with a penalty factor per column and bounds lower_j <= beta_j <= upper_j on the ORIGINAL coefficient
     scale -- glmnet's lower.limits / upper.limits / penalty.factor, scikit-learn's positive=True as lower=0.  `lower` <= 0 <= `upper`
@@ -858,12 +876,11 @@ class ADMM_BoxEnet(ADMM_Lasso):
     penalty_factor multiplies the whole penalty of its column; 0 leaves it unpenalised."""
     _name = "ADMM Box-Constrained Elastic Net model"
     _missing = "not available for the box-constrained elastic net (single-device tall solver only)"
+    _tall_only = "the box-constrained elastic net is built for n > p only (the wide solver is not built for bounds)"
+    _entry, _title = "admm_hip_boxenet", "ADMM Box-Constrained Elastic Net fitting result"
 
     def __init__(self, x, y, lower=None, upper=None, intercept=True, standardize=True, n=None, p=None):
         super().__init__(x, y, intercept, standardize, n, p)
-        if self.n <= self.p:
-            _stop("nrow(x) must be greater than ncol(x): the box-constrained elastic net is built for n > p only "
-                  "(the wide solver is not built for bounds)")
         self.lower = self._per_column(lower, "lower")
         self.upper = self._per_column(upper, "upper")
         if self.lower is not None and not np.all(self.lower <= 0):
@@ -890,33 +907,16 @@ class ADMM_BoxEnet(ADMM_Lasso):
             if not 0.0 <= alpha <= 1.0:                                  # (NaN fails both comparisons)
                 _stop("alpha must be None (the Lasso prox) or within [0, 1] (the elastic net's)")
         u = self._per_column(penalty_factor, "penalty_factor")
-        if u is not None:
-            if not np.all(np.isfinite(u)) or np.any(u < 0):
-                _stop("penalty factors must be finite and non-negative")
-            if not np.any(u > 0):
-                _stop("at least one penalty factor must be positive")
+        if u is not None:                                                # (_per_column fixed its length)
+            u = _weights(u, self.p, None, "penalty factors must be finite and non-negative", "at least one penalty factor must be positive")
         self.alpha, self.penalty_factor = alpha, u
         return self
 
-    def parallel(self, *a, **kw):
-        _stop(self._missing)
-
-    def cv(self, *a, **kw):
-        _stop(self._missing)
-
-    def fit_responses(self, *a, **kw):
-        _stop(self._missing)
-
     def _box_args(self):
-        dp = lambda a: a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if a is not None else None
-        return dp(self.lower), dp(self.upper), dp(self.penalty_factor), -1.0 if self.alpha is None else self.alpha
+        return _dp(self.lower), _dp(self.upper), _dp(self.penalty_factor), -1.0 if self.alpha is None else self.alpha
 
-    def fit(self):
-        lib, head, tail, lam_out, beta, niter, stats, keep = self._common()
-        check(lib.admm_hip_boxenet(*head[:5], *self._box_args(), *head[5:], *tail))
-        fit = ADMM_Lasso_fit(lam_out, beta, niter, stats.as_dict())
-        fit._title = "ADMM Box-Constrained Elastic Net fitting result"
-        return fit
+    def _extra_args(self, head):
+        return self._box_args()
 
 
 def admm_boxenet(x, y, lower=None, upper=None, intercept=True, standardize=True, **kw):
@@ -945,12 +945,14 @@ class ADMM_MTLasso_fit:
         print(repr(self))
 
 
-class ADMM_MTLasso(ADMM_Lasso):
+class ADMM_MTLasso(_TallOnly):
     """Multi-task lasso on the tall path (admm_hip_mtlasso; n > p only, one device): Y is n x m, one row-wise penalty
     lambda sum_j w_j ||B_j.||_2 selects a column of x for all responses at once.  All responses share one cached inverse, so an
     iteration streams it once for several of them (option MT_RHS).  With a DevicePtr for Y pass m."""
     _name = "ADMM multi-task Lasso model"
     _missing = "not available for the multi-task lasso (single-device tall solver only)"
+    _tall_only = "the multi-task lasso is built for n > p only"
+    _entry, _extra_at = "admm_hip_mtlasso", 4                       # m goes before mem, the weights after it
 
     def __init__(self, x, Y, intercept=True, standardize=True, n=None, p=None, m=None):
         if isinstance(Y, DevicePtr):
@@ -966,8 +968,6 @@ class ADMM_MTLasso(ADMM_Lasso):
             Y = np.asfortranarray(Y)
             m = Y.shape[1]
         super().__init__(x, Y, intercept, standardize, n, p)
-        if self.n <= self.p:
-            _stop("nrow(x) must be greater than ncol(x): the multi-task lasso is built for n > p only")
         if m < 1 or m > _lib.MT_MAX:
             _stop(f"the number of responses must be within [1, {_lib.MT_MAX}]")
         self.m = m
@@ -976,36 +976,22 @@ class ADMM_MTLasso(ADMM_Lasso):
     def penalty(self, lambda_=None, nlambda=100, lambda_min_ratio=None, row_weights=None, **kw):
         super().penalty(lambda_, nlambda, lambda_min_ratio, **kw)
         if row_weights is not None:
-            w = np.ascontiguousarray(np.asarray(row_weights, dtype=np.float64).ravel())
-            if w.size != self.p:
-                _stop("row_weights should have one entry per column of x")
-            if not np.all(np.isfinite(w)) or np.any(w < 0):
-                _stop("row_weights must be finite and non-negative")
-            if not np.any(w > 0):
-                _stop("at least one row weight must be positive")
-            row_weights = w
+            row_weights = _weights(row_weights, self.p, "row_weights should have one entry per column of x",
+                                   "row_weights must be finite and non-negative", "at least one row weight must be positive")
         self.row_weights = row_weights
         return self
 
-    def parallel(self, *a, **kw):
-        _stop(self._missing)
-
-    def cv(self, *a, **kw):
-        _stop(self._missing)
-
-    def fit_responses(self, *a, **kw):
-        _stop(self._missing)
-
     def _weight_arg(self):
-        w = self.row_weights
-        return w.ctypes.data_as(ctypes.POINTER(ctypes.c_double)) if w is not None else None
+        return _dp(self.row_weights)
 
-    def fit(self):
-        lib, head, tail, lam_out, _, niter, stats, keep = self._common()
-        beta = np.zeros((lam_out.size, self.m, self.p + 1), dtype=np.float32)
-        check(lib.admm_hip_mtlasso(*head[:4], self.m, head[4], self._weight_arg(), *head[5:], tail[0], tail[1],
-                                   beta.ctypes.data_as(ctypes.POINTER(ctypes.c_float)), tail[3], tail[4]))
-        return ADMM_MTLasso_fit(lam_out, beta, niter, stats.as_dict())
+    def _extra_args(self, head):
+        return self.m, head[4], self._weight_arg()
+
+    def _beta_buffer(self, nl):
+        return np.zeros((nl, self.m, self.p + 1), dtype=np.float32)
+
+    def _result(self, lam, beta, niter, stats):
+        return ADMM_MTLasso_fit(lam, beta, niter, stats)
 
 
 def admm_mtlasso(x, Y, intercept=True, standardize=True, **kw):

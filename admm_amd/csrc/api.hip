@@ -38,6 +38,30 @@ static void plan_out_set(PlanHandle* h, admm_hip_plan** plan_out, int* nlambda_o
     if (nlambda_out) *nlambda_out = h->nlam;
 }
 
+// The tall-only penalties: the path arguments (PATH_SPEC) plus what each adds, p being the length of its per-column arrays.
+static PathSpec group_spec(PathSpec s, int p, const int* group, const double* group_weight, int ngroups) {
+    s.penalty = Penalty::GROUP; s.cols = p; s.group = group; s.group_weight = group_weight; s.ngroups = ngroups;
+    return s;
+}
+static PathSpec sgl_spec(PathSpec s, int p, const int* group, const double* group_weight, int ngroups, const double* l1_weight, double mix) {
+    s = group_spec(s, p, group, group_weight, ngroups);
+    s.penalty = Penalty::SGL; s.l1_weight = l1_weight; s.sgl_mix = mix;
+    return s;
+}
+static PathSpec box_spec(PathSpec s, int p, const double* lower, const double* upper, const double* penalty_factor) {
+    s.penalty = Penalty::BOX; s.cols = p; s.lower = lower; s.upper = upper; s.penalty_factor = penalty_factor;
+    return s;
+}
+static PathSpec mt_spec(PathSpec s, int p, int m, const double* row_weight) {
+    s.penalty = Penalty::MULTITASK; s.cols = p; s.nresp = m; s.row_weight = row_weight;
+    return s;
+}
+// ... and how a *_plan_create entry point hands its plan out
+static void plan_create(const double* x, const double* y, int n, int p, int mem, const PathSpec& spec, admm_hip_plan** plan_out, int* nlambda_out) {
+    ADMM_REQUIRE(plan_out != nullptr, "plan_out must not be NULL");
+    plan_out_set(create_plan(x, y, n, p, mem, spec, 0), plan_out, nlambda_out);
+}
+
 extern "C" {
 
 int admm_hip_lasso(const double* x, const double* y, int n, int p, int mem,
@@ -220,14 +244,12 @@ int admm_hip_lasso_plan_create_dist_cols(const double* x_cols, const double* y, 
 }
 
 // admm_hip_grplasso: the Lasso's path arguments plus the grouping of the columns
-#define GROUP_SPEC [&] { PathSpec s = PATH_SPEC(-1.0); s.grouped = true; s.group = group; s.group_weight = group_weight; s.ngroups = ngroups; s.group_cols = p; return s; }()
-
 int admm_hip_grplasso(const double* x, const double* y, int n, int p, int mem,
                       const int* group, const double* group_weight, int ngroups,
                       const double* lambda_in, int nlambda_in, int nlambda_auto, double lmin_ratio,
                       int standardize, int intercept, const admm_opts* opts,
                       double* lambda_out, float* beta_out, int* niter_out, admm_stats* stats) {
-    return guarded([&] { lasso_family(x, y, n, p, mem, GROUP_SPEC, 0, Shard(), PATH_OUT); });
+    return guarded([&] { lasso_family(x, y, n, p, mem, group_spec(PATH_SPEC(-1.0), p, group, group_weight, ngroups), 0, Shard(), PATH_OUT); });
 }
 
 int admm_hip_grplasso_plan_create(const double* x, const double* y, int n, int p, int mem,
@@ -235,21 +257,16 @@ int admm_hip_grplasso_plan_create(const double* x, const double* y, int n, int p
                                   const double* lambda_in, int nlambda_in, int nlambda_auto, double lmin_ratio,
                                   int standardize, int intercept, const admm_opts* opts,
                                   admm_hip_plan** plan_out, int* nlambda_out) {
-    return guarded([&] {
-        ADMM_REQUIRE(plan_out != nullptr, "plan_out must not be NULL");
-        plan_out_set(create_plan(x, y, n, p, mem, GROUP_SPEC, 0), plan_out, nlambda_out);
-    });
+    return guarded([&] { plan_create(x, y, n, p, mem, group_spec(PATH_SPEC(-1.0), p, group, group_weight, ngroups), plan_out, nlambda_out); });
 }
 
 // admm_hip_sgl: the group lasso's arguments plus the l1 weight of every column and the mixing parameter
-#define SGL_SPEC [&] { PathSpec s = GROUP_SPEC; s.sgl = true; s.sgl_mix = alpha; s.l1_weight = l1_weight; return s; }()
-
 int admm_hip_sgl(const double* x, const double* y, int n, int p, int mem,
                  const int* group, const double* group_weight, int ngroups, const double* l1_weight, double alpha,
                  const double* lambda_in, int nlambda_in, int nlambda_auto, double lmin_ratio,
                  int standardize, int intercept, const admm_opts* opts,
                  double* lambda_out, float* beta_out, int* niter_out, admm_stats* stats) {
-    return guarded([&] { lasso_family(x, y, n, p, mem, SGL_SPEC, 0, Shard(), PATH_OUT); });
+    return guarded([&] { lasso_family(x, y, n, p, mem, sgl_spec(PATH_SPEC(-1.0), p, group, group_weight, ngroups, l1_weight, alpha), 0, Shard(), PATH_OUT); });
 }
 
 int admm_hip_sgl_plan_create(const double* x, const double* y, int n, int p, int mem,
@@ -257,21 +274,16 @@ int admm_hip_sgl_plan_create(const double* x, const double* y, int n, int p, int
                              const double* lambda_in, int nlambda_in, int nlambda_auto, double lmin_ratio,
                              int standardize, int intercept, const admm_opts* opts,
                              admm_hip_plan** plan_out, int* nlambda_out) {
-    return guarded([&] {
-        ADMM_REQUIRE(plan_out != nullptr, "plan_out must not be NULL");
-        plan_out_set(create_plan(x, y, n, p, mem, SGL_SPEC, 0), plan_out, nlambda_out);
-    });
+    return guarded([&] { plan_create(x, y, n, p, mem, sgl_spec(PATH_SPEC(-1.0), p, group, group_weight, ngroups, l1_weight, alpha), plan_out, nlambda_out); });
 }
 
 // admm_hip_boxenet: the elastic net's path arguments (alpha < 0: the Lasso prox) plus the box and the penalty factors
-#define BOX_SPEC [&] { PathSpec s = PATH_SPEC(alpha); s.box = true; s.lower = lower; s.upper = upper; s.penalty_factor = penalty_factor; s.box_cols = p; return s; }()
-
 int admm_hip_boxenet(const double* x, const double* y, int n, int p, int mem,
                      const double* lower, const double* upper, const double* penalty_factor, double alpha,
                      const double* lambda_in, int nlambda_in, int nlambda_auto, double lmin_ratio,
                      int standardize, int intercept, const admm_opts* opts,
                      double* lambda_out, float* beta_out, int* niter_out, admm_stats* stats) {
-    return guarded([&] { lasso_family(x, y, n, p, mem, BOX_SPEC, 0, Shard(), PATH_OUT); });
+    return guarded([&] { lasso_family(x, y, n, p, mem, box_spec(PATH_SPEC(alpha), p, lower, upper, penalty_factor), 0, Shard(), PATH_OUT); });
 }
 
 int admm_hip_boxenet_plan_create(const double* x, const double* y, int n, int p, int mem,
@@ -279,21 +291,16 @@ int admm_hip_boxenet_plan_create(const double* x, const double* y, int n, int p,
                                  const double* lambda_in, int nlambda_in, int nlambda_auto, double lmin_ratio,
                                  int standardize, int intercept, const admm_opts* opts,
                                  admm_hip_plan** plan_out, int* nlambda_out) {
-    return guarded([&] {
-        ADMM_REQUIRE(plan_out != nullptr, "plan_out must not be NULL");
-        plan_out_set(create_plan(x, y, n, p, mem, BOX_SPEC, 0), plan_out, nlambda_out);
-    });
+    return guarded([&] { plan_create(x, y, n, p, mem, box_spec(PATH_SPEC(alpha), p, lower, upper, penalty_factor), plan_out, nlambda_out); });
 }
 
 // admm_hip_mtlasso: the Lasso's path arguments plus the number of responses and the row weights
-#define MT_SPEC [&] { PathSpec s = PATH_SPEC(-1.0); s.nresp = m; s.row_weight = row_weight; s.mt_rows = p; if (m == 0) s.nresp = -1; return s; }()
-
 int admm_hip_mtlasso(const double* x, const double* Y, int n, int p, int m, int mem,
                      const double* row_weight,
                      const double* lambda_in, int nlambda_in, int nlambda_auto, double lmin_ratio,
                      int standardize, int intercept, const admm_opts* opts,
                      double* lambda_out, float* beta_out, int* niter_out, admm_stats* stats) {
-    return guarded([&] { lasso_family(x, Y, n, p, mem, MT_SPEC, 0, Shard(), PATH_OUT); });
+    return guarded([&] { lasso_family(x, Y, n, p, mem, mt_spec(PATH_SPEC(-1.0), p, m, row_weight), 0, Shard(), PATH_OUT); });
 }
 
 int admm_hip_mtlasso_plan_create(const double* x, const double* Y, int n, int p, int m, int mem,
@@ -301,10 +308,7 @@ int admm_hip_mtlasso_plan_create(const double* x, const double* Y, int n, int p,
                                  const double* lambda_in, int nlambda_in, int nlambda_auto, double lmin_ratio,
                                  int standardize, int intercept, const admm_opts* opts,
                                  admm_hip_plan** plan_out, int* nlambda_out) {
-    return guarded([&] {
-        ADMM_REQUIRE(plan_out != nullptr, "plan_out must not be NULL");
-        plan_out_set(create_plan(x, Y, n, p, mem, MT_SPEC, 0), plan_out, nlambda_out);
-    });
+    return guarded([&] { plan_create(x, Y, n, p, mem, mt_spec(PATH_SPEC(-1.0), p, m, row_weight), plan_out, nlambda_out); });
 }
 
 int admm_hip_options_default(admm_hip_options* o) {
@@ -548,14 +552,9 @@ int admm_hip_host_sgl_lambda0(const float* xy, int p, const int* group, const do
                               const double* l1_weight, double alpha, float* out) {
     return guarded([&] {
         ADMM_REQUIRE(xy && out && p > 0, "bad arguments");
-        PathSpec s;
-        s.grouped = s.sgl = true; s.group = group; s.group_weight = group_weight; s.ngroups = ngroups; s.group_cols = p;
-        s.sgl_mix = alpha; s.l1_weight = l1_weight;
+        const PathSpec s = sgl_spec(PathSpec(), p, group, group_weight, ngroups, l1_weight, alpha);
         s.check_sgl_args(p);
-        std::vector<int> start;
-        for (int j = 0; j < p; ++j)
-            if (j == 0 || group[j] != group[j - 1]) start.push_back(j);
-        start.push_back(p);
+        const std::vector<int> start = s.group_starts();
         std::vector<double> l1, wg;
         sgl_prepare(alpha, l1_weight, group_weight, start, l1, wg);
         *out = sgl_lambda0(xy, start, l1, wg);
@@ -568,8 +567,8 @@ int admm_hip_host_box_lambda0(const float* xy, int p, const float* lower_std, co
                               double alpha, float* out) {
     return guarded([&] {
         ADMM_REQUIRE(xy && out && p > 0, "bad arguments");
-        PathSpec s;
-        s.box = true; s.penalty_factor = penalty_factor; s.alpha = alpha; s.box_cols = p;
+        PathSpec s = box_spec(PathSpec(), p, nullptr, nullptr, penalty_factor);
+        s.alpha = alpha;
         s.check_box_args(p);
         for (int j = 0; j < p; ++j)
             ADMM_REQUIRE((!lower_std || lower_std[j] <= 0.f) && (!upper_std || upper_std[j] >= 0.f), "the box must hold zero");

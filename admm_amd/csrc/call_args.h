@@ -15,24 +15,21 @@ struct PathSpec {
     double alpha = -1.0;                 // as the ABI passes it: >= 0 means elastic net (and then <= 1), anything else the plain Lasso
     const admm_opts* opts = nullptr;
     bool enet_only = false;              // admm_hip_enet has no Lasso form: it refuses a negative alpha too (R/40_admm_enet.R:38-39)
-    // group lasso (admm_hip_grplasso): the group id of every column and the groups' weights as the ABI passes them
-    bool grouped = false;
+    // the tall-only penalties (solvers.h: Penalty): which one this call asks for, p (the length of the per-column arrays below), and the
+    // arguments of each as the ABI passes them
+    Penalty penalty = Penalty::PLAIN;
+    int cols = 0;
+    // GROUP, SGL: the group id of every column and the groups' weights; SGL: the mixing parameter (its own name: `alpha` above means
+    // elastic net) and the l1 weight of every column (NULL: all 1)
     const int* group = nullptr; const double* group_weight = nullptr; int ngroups = 0;
-    int group_cols = 0;                  // p, the length of `group`
-    // sparse-group lasso (admm_hip_sgl): a grouped call with the mixing parameter (its own name: `alpha` above means elastic net, which a
-    // grouped call refuses) and the l1 weight of every column (NULL: all 1)
-    bool sgl = false;
     double sgl_mix = 0.0;
     const double* l1_weight = nullptr;
-    // multi-task lasso (admm_hip_mtlasso): the number of responses (0: an ordinary call) and the p row weights as the ABI passes them
+    // MULTITASK: the number of responses and the p row weights
     int nresp = 0;
     const double* row_weight = nullptr;
-    int mt_rows = 0;                     // p, the length of `row_weight`
-    // box-constrained, weighted elastic net (admm_hip_boxenet): the bounds on the original coefficient scale and the penalty factors as
-    // the ABI passes them (each p long; NULL: no lower bounds / no upper bounds / all factors 1); `alpha` above selects the prox
-    bool box = false;
+    // BOX: the bounds on the original coefficient scale and the penalty factors (each p long; NULL: no lower bounds / no upper bounds /
+    // all factors 1); `alpha` above selects the prox
     const double* lower = nullptr; const double* upper = nullptr; const double* penalty_factor = nullptr;
-    int box_cols = 0;                    // p, the length of the three
 
     bool enet() const { return alpha >= 0.0; }
     double alpha_eff() const { return enet() ? alpha : 1.0; }
@@ -82,10 +79,6 @@ struct PathSpec {
             any = sgl_mix * (l1_weight ? l1_weight[j] : 1.0) > 0 || (1.0 - sgl_mix) * (group_weight ? group_weight[group[j]] : 1.0) > 0;
         ADMM_REQUIRE(any, "at least one coordinate must carry a positive penalty");
     }
-    void check_sgl(int n, int p) const {
-        check_sgl_args(p);
-        ADMM_REQUIRE(n > p, "the sparse-group lasso is built for n > p only");
-    }
     // ... of a multi-task call, once check_common has passed: 1 <= m <= ADMM_HIP_MT_MAX, usable weights, n > p
     void check_mt(int n, int p) const {
         ADMM_REQUIRE(nresp >= 1 && nresp <= ADMM_HIP_MT_MAX, "the number of responses must be within [1, ADMM_HIP_MT_MAX (16)]");
@@ -98,7 +91,7 @@ struct PathSpec {
         ADMM_REQUIRE(n > p, "the multi-task lasso is built for n > p only");
     }
     // ... of a box-constrained call, once check_common has passed: a box that holds zero, usable factors, an alpha that names a prox
-    // (check() lets NaN through as "the Lasso"), n > p
+    // (check() lets NaN through as "the Lasso")
     void check_box_args(int p) const {
         for (int j = 0; lower != nullptr && j < p; ++j)
             ADMM_REQUIRE(lower[j] <= 0, "lower bounds must be <= 0 (zero must be feasible) and not NaN");
@@ -112,9 +105,18 @@ struct PathSpec {
         ADMM_REQUIRE(any, "at least one penalty factor must be positive");
         ADMM_REQUIRE(!std::isnan(alpha) && alpha <= 1.0, "alpha must be negative (the Lasso prox) or within [0, 1] (the elastic net's)");
     }
-    void check_box(int n, int p) const {
-        check_box_args(p);
-        ADMM_REQUIRE(n > p, "the box-constrained elastic net is built for n > p only: the wide solver is not built for bounds");
+    // ... of the penalty this call asks for, once check_common has passed: its arguments, then n > p
+    void check_penalty(int n, int p) const {
+        switch (penalty) {
+        case Penalty::PLAIN: break;
+        case Penalty::GROUP: check_groups(n, p); break;
+        case Penalty::SGL: check_sgl_args(p); ADMM_REQUIRE(n > p, "the sparse-group lasso is built for n > p only"); break;
+        case Penalty::MULTITASK: check_mt(n, p); break;
+        case Penalty::BOX:
+            check_box_args(p);
+            ADMM_REQUIRE(n > p, "the box-constrained elastic net is built for n > p only: the wide solver is not built for bounds");
+            break;
+        }
     }
     LassoProblem problem(int nworkers, bool dist) const {
         LassoProblem pb;
@@ -128,31 +130,39 @@ struct PathSpec {
         pb.dist = dist;
         pb.batch_iters = (int)opt_int(Opt::BATCH_ITERS, 0);
         pb.profile_stride = (int)opt_int(Opt::PROFILE_STRIDE, 0);
-        if (grouped) {                      // (checked: check_groups)
-            for (int j = 0; j < group_cols; ++j)
-                if (j == 0 || group[j] != group[j - 1]) pb.group_start.push_back(j);
-            pb.group_start.push_back(group_cols);
-            if (sgl) {                      // (checked: check_sgl) the device's weights, not the caller's
-                pb.sgl = true;
-                sgl_prepare(sgl_mix, l1_weight, group_weight, pb.group_start, pb.l1_weight, pb.group_weight);
-            }
-            for (int g = 0; !sgl && g < ngroups; ++g)
+        pb.penalty = penalty;
+        const double inf = std::numeric_limits<double>::infinity();
+        switch (penalty) {                  // (checked: check_penalty)
+        case Penalty::PLAIN: break;
+        case Penalty::GROUP:
+            pb.group_start = group_starts();
+            for (int g = 0; g < ngroups; ++g)
                 pb.group_weight.push_back(group_weight ? group_weight[g] : std::sqrt((double)(pb.group_start[g + 1] - pb.group_start[g])));
-        }
-        if (nresp > 0) {                    // (checked: check_mt)
+            break;
+        case Penalty::SGL:                  // the device's weights, not the caller's
+            pb.group_start = group_starts();
+            sgl_prepare(sgl_mix, l1_weight, group_weight, pb.group_start, pb.l1_weight, pb.group_weight);
+            break;
+        case Penalty::MULTITASK:
             pb.nresp = nresp;
-            for (int j = 0; j < mt_rows; ++j) pb.row_weight.push_back(row_weight ? row_weight[j] : 1.0);
-        }
-        if (box) {                          // (checked: check_box)
-            const double inf = std::numeric_limits<double>::infinity();
-            pb.box = true;
-            for (int j = 0; j < box_cols; ++j) {
+            for (int j = 0; j < cols; ++j) pb.row_weight.push_back(row_weight ? row_weight[j] : 1.0);
+            break;
+        case Penalty::BOX:
+            for (int j = 0; j < cols; ++j) {
                 pb.box_lower.push_back(lower ? lower[j] : -inf);
                 pb.box_upper.push_back(upper ? upper[j] : inf);
                 pb.penalty_factor.push_back(penalty_factor ? penalty_factor[j] : 1.0);
             }
+            break;
         }
         return pb;
+    }
+    std::vector<int> group_starts() const {                       // group g holds columns [start[g], start[g + 1])
+        std::vector<int> start;
+        for (int j = 0; j < cols; ++j)
+            if (j == 0 || group[j] != group[j - 1]) start.push_back(j);
+        start.push_back(cols);
+        return start;
     }
     PathSpec on_grid(const std::vector<double>& lam) const {      // the same call on a grid that an earlier fit fixed
         PathSpec s = *this;

@@ -30,6 +30,21 @@ void check_common(const double* x, const double* y, int n, int p, int mem, const
     ADMM_REQUIRE(opts->eps_abs >= 0 && opts->eps_rel >= 0, "eps_abs and eps_rel should be nonnegative");
 }
 
+// What create_plan says about each tall-only penalty, by Penalty: its name, its refusal of REFINE (the sparse-group lasso answers as
+// the group lasso) and its refusal of an attached communicator (NULL: not refused -- the two grouped calls do not look)
+namespace {
+struct PenaltyText { const char* name; const char* refine; const char* comm; };
+const PenaltyText kPenaltyText[] = {
+    {"the Lasso", nullptr, nullptr},
+    {"the group lasso", "the group lasso has no refined x-update: unset REFINE", nullptr},
+    {"the sparse-group lasso", "the group lasso has no refined x-update: unset REFINE", nullptr},
+    {"the multi-task lasso", "the multi-task lasso has no refined x-update: unset REFINE",
+     "the multi-task lasso runs on a single device: detach the communicator (admm_hip_comm_finalize)"},
+    {"the box-constrained elastic net", "the box-constrained elastic net has no refined x-update: unset REFINE",
+     "the box-constrained elastic net runs on a single device: detach the communicator (admm_hip_comm_finalize)"},
+};
+}  // namespace
+
 PlanHandle* create_plan(const double* x, const double* y, int n, int p, int mem, const PathSpec& spec, int nworkers, const Shard& shard) {
     const bool rows = shard.kind == Shard::ROWS, cols = shard.kind == Shard::COLS;
     if (rows) ADMM_REQUIRE(shard.n_total >= n && n > 0, "n_total must be >= n_local > 0");
@@ -47,24 +62,13 @@ PlanHandle* create_plan(const double* x, const double* y, int n, int p, int mem,
     } else if (nworkers > 0) {
         ADMM_REQUIRE(nworkers <= n, "more row blocks than rows");
     }
-    if (spec.grouped) {                                     // admm_hip_grplasso, admm_hip_sgl: the tall solver on one device, nothing else
-        ADMM_REQUIRE(shard.kind == Shard::NONE && nworkers <= 0 && !spec.enet(), "the group lasso has no sharded, consensus or elastic-net form");
-        if (spec.sgl) spec.check_sgl(n, p); else spec.check_groups(n, p);
-        ADMM_REQUIRE(!opt_on(Opt::REFINE), "the group lasso has no refined x-update: unset REFINE");
-    }
-    if (spec.nresp != 0) {                                  // admm_hip_mtlasso: the tall solver on one device, nothing else (y is Y, n x m)
-        ADMM_REQUIRE(shard.kind == Shard::NONE && nworkers <= 0 && !spec.enet() && !spec.grouped,
-                     "the multi-task lasso has no sharded, consensus, elastic-net or grouped form");
-        spec.check_mt(n, p);
-        ADMM_REQUIRE(!opt_on(Opt::REFINE), "the multi-task lasso has no refined x-update: unset REFINE");
-        ADMM_REQUIRE(!comm_info().active, "the multi-task lasso runs on a single device: detach the communicator (admm_hip_comm_finalize)");
-    }
-    if (spec.box) {                                         // admm_hip_boxenet: the tall solver on one device, nothing else
-        spec.check_box(n, p);
-        ADMM_REQUIRE(shard.kind == Shard::NONE && nworkers <= 0 && !spec.grouped && spec.nresp == 0,
-                     "the box-constrained elastic net has no sharded, consensus, grouped or multi-response form");
-        ADMM_REQUIRE(!opt_on(Opt::REFINE), "the box-constrained elastic net has no refined x-update: unset REFINE");
-        ADMM_REQUIRE(!comm_info().active, "the box-constrained elastic net runs on a single device: detach the communicator (admm_hip_comm_finalize)");
+    if (spec.penalty != Penalty::PLAIN) {                   // the tall solver on one device, nothing else (MULTITASK: y is Y, n x m)
+        const PenaltyText& t = kPenaltyText[(int)spec.penalty];
+        ADMM_REQUIRE(shard.kind == Shard::NONE && nworkers <= 0 && (spec.penalty == Penalty::BOX || !spec.enet()),
+                     std::string("internal: ") + t.name + " has no sharded or consensus form, and only the box an elastic-net one");
+        spec.check_penalty(n, p);
+        ADMM_REQUIRE(!opt_on(Opt::REFINE), t.refine);
+        ADMM_REQUIRE(t.comm == nullptr || !comm_info().active, t.comm);
     }
     require_device();
     const double t0 = now_s();
@@ -74,10 +78,10 @@ PlanHandle* create_plan(const double* x, const double* y, int n, int p, int mem,
     DeviceData<float> d;
     const bool std_x = spec.standardize != 0, icpt = spec.intercept != 0;
     // Host input of a large tall problem: standardisation and X'X run under the PCIe transfer (bit-identical result).
-    const bool pipelined = mem == ADMM_MEM_HOST && shard.kind == Shard::NONE && nworkers <= 0 && n > p && p >= 4096 && !opt_set(Opt::GRAM) && spec.nresp == 0;
+    const bool pipelined = mem == ADMM_MEM_HOST && shard.kind == Shard::NONE && nworkers <= 0 && n > p && p >= 4096 && !opt_set(Opt::GRAM) && spec.penalty != Penalty::MULTITASK;
     if (pipelined) upload_standardize_gram_f32(d, x, y, n, p, std_x, icpt, h->st.s);
     else upload_standardize<float>(d, x, y, n, p, mem, std_x, icpt, h->st.s, shard.n_total, shard.ldx);   // COLS: column moments are local, y is replicated
-    if (spec.nresp > 0) {                                   // X went up with the first response; now all of them, standardised together
+    if (spec.penalty == Penalty::MULTITASK) {               // X went up with the first response; now all of them, standardised together
         const Resident yr(y, (size_t)n * spec.nresp, mem);
         if (mem == ADMM_MEM_HOST) comm_stream_sync(h->st.s);
         standardize_responses_f32(d, yr.p, spec.nresp, h->st.s);

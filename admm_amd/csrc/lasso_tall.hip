@@ -838,19 +838,20 @@ struct TallPlan final : LassoPlan {
     bool refine = false;
     DevBuf<float> Mg, rab, ruw;                          // the float system X'X + rho I; first solve a | b; residuals r_u | r_w
     DevBuf<double> dD0, dD1, xD0, xD1;                   // double partial arrays of M x1
-    // group lasso (LassoProblem.group_start): the tail is tall_group_tail_kernel over tiles of whole groups, nwg = their number
-    bool grouped = false;
+    // group and sparse-group lasso (Penalty::GROUP, SGL): the tail is tall_group_tail_kernel over tiles of whole groups, nwg = their number
+    bool grouped = false, sgl = false;
     DevBuf<int2> gtiles;
     DevBuf<GroupCoord> gcoord;
-    DevBuf<double> gl1;                                 // sparse-group lasso (LassoProblem.sgl): the l1 weight of every column
+    DevBuf<double> gl1;                                 // sparse-group lasso: the l1 weight of every column
     GroupTailParams gq{};
-    // multi-task lasso (LassoProblem.nresp): every vector is nresp planes, the x-update passes of symvn_lower_kernel, the tail tall_mt_tail_kernel
+    // multi-task lasso (Penalty::MULTITASK): every vector is nresp planes, the x-update passes of symvn_lower_kernel, the tail tall_mt_tail_kernel
     int mt = 0;                                         // responses (0: not a multi-task problem)
     int mt_rhs = 2;                                     // right-hand sides per pass (MT_RHS)
     DevBuf<float> uw, mdot, maxp;                       // [2 mt][ldv] right-hand sides; [2 mt] planes of partials
     DevBuf<double> roww;
     MtTailParams mq{};
-    // box-constrained, weighted elastic net (LassoProblem.box): factors and bounds of every column, the tail tall_box_tail_kernel
+    // box-constrained, weighted elastic net (Penalty::BOX): factors and bounds of every column, the tail tall_box_tail_kernel
+    bool box = false;
     DevBuf<double> bpf;
     DevBuf<float> blo, bhi;                             // the bounds in the solver's units, rounded inwards (box_host.h)
     BoxTailParams bq{};
@@ -887,10 +888,9 @@ struct TallPlan final : LassoPlan {
         if (d.xy.get()) {                                  // Gram-form data (a cross-validation fold formed as a down-date, cv.hip)
             ADMM_REQUIRE(!shard && d.gram.get() && d.ldgram == ldp, "Gram-form data needs X'X next to X'y");
             XY = std::move(d.xy);
-        } else if (pb.nresp > 0) {                         // multi-task: X'Y, one plane per response
+        } else if (pb.penalty == Penalty::MULTITASK) {     // X'Y, one plane per response
             mt = pb.nresp;
-            ADMM_REQUIRE(!shard && !pb.enet && !opt_on(Opt::REFINE) && pb.group_start.empty() && mt <= kMtMax && d.nresp == mt && d.Ymt.get() &&
-                         (int)pb.row_weight.size() == p, "internal: the multi-task lasso is the plain single-device tall solver");
+            ADMM_REQUIRE(mt >= 1 && mt <= kMtMax && d.nresp == mt && d.Ymt.get() && (int)pb.row_weight.size() == p, "internal: multi-task sizes");
             XY.alloc((size_t)mt * ldp); XY.zero(st);
             for (int k = 0; k < mt; ++k) gemv_t_simple<float>(d.X.get(), d.ldx, n, p, d.Ymt.get() + (size_t)k * d.ldx, XY.get() + (size_t)k * ldp, st);
         } else {
@@ -898,16 +898,20 @@ struct TallPlan final : LassoPlan {
             gemv_t_simple<float>(d.X.get(), d.ldx, n, p, d.Y.get(), XY.get(), st);
             if (shard) allreduce_sum_f32(XY.get(), (size_t)p, st);
         }
-        ADMM_REQUIRE(pb.nresp == mt, "internal: the multi-task lasso takes its data as columns, not in Gram form");
-        grouped = !pb.group_start.empty();
-        ADMM_REQUIRE(!grouped || (!shard && !pb.enet && !opt_on(Opt::REFINE) && (int)pb.group_start.size() == (int)pb.group_weight.size() + 1 &&
-                                  pb.group_start.back() == p), "internal: the group lasso is the plain single-device tall solver");
-        ADMM_REQUIRE(pb.sgl ? grouped && (int)pb.l1_weight.size() == p : pb.l1_weight.empty(), "internal: l1 weights belong to the sparse-group lasso");
-        ADMM_REQUIRE(!pb.box || (!shard && !grouped && !mt && !opt_on(Opt::REFINE) && (int)pb.box_lower.size() == p &&
-                                 (int)pb.box_upper.size() == p && (int)pb.penalty_factor.size() == p),
-                     "internal: the box-constrained elastic net is the plain single-device tall solver");
-        float lambda0 = pb.box ? box_plan_lambda0()
-                               : (grouped ? (pb.sgl ? sgl_plan_lambda0() : group_lambda0()) : (mt ? mt_lambda0() : device_absmax<float>(XY.get(), p, st)));
+        sgl = pb.penalty == Penalty::SGL; grouped = sgl || pb.penalty == Penalty::GROUP; box = pb.penalty == Penalty::BOX;
+        ADMM_REQUIRE(pb.penalty == Penalty::PLAIN || (!shard && !opt_on(Opt::REFINE) && (box || !pb.enet) && (mt > 0) == (pb.penalty == Penalty::MULTITASK)),
+                     "internal: a penalty other than the Lasso's is the plain single-device tall solver on column data");
+        ADMM_REQUIRE(!grouped || ((int)pb.group_start.size() == (int)pb.group_weight.size() + 1 && pb.group_start.back() == p), "internal: group sizes");
+        ADMM_REQUIRE((int)pb.l1_weight.size() == (sgl ? p : 0), "internal: l1 weights belong to the sparse-group lasso");
+        ADMM_REQUIRE(!box || ((int)pb.box_lower.size() == p && (int)pb.box_upper.size() == p && (int)pb.penalty_factor.size() == p), "internal: box sizes");
+        float lambda0 = 0.f;
+        switch (pb.penalty) {
+        case Penalty::PLAIN: lambda0 = device_absmax<float>(XY.get(), p, st); break;
+        case Penalty::GROUP: lambda0 = group_lambda0(); break;
+        case Penalty::SGL: lambda0 = sgl_plan_lambda0(); break;
+        case Penalty::MULTITASK: lambda0 = mt_lambda0(); break;
+        case Penalty::BOX: lambda0 = box_plan_lambda0(); break;
+        }
         if (pb.enet) lambda0 = (float)(lambda0 / ((double)(float)pb.alpha + 0.0001));
 
         // lambda grid (Lasso.cpp:78-89) and internal lambdas (Lasso.cpp:99), stored as float like `Scalar lambda`
@@ -1216,7 +1220,7 @@ struct TallPlan final : LassoPlan {
     int pack_group_tiles() {
         std::vector<int2> tiles;
         std::vector<GroupCoord> coord(p);
-        const bool flat = pb.sgl && std::none_of(pb.group_weight.begin(), pb.group_weight.end(), [](double w) { return w > 0; });
+        const bool flat = sgl && std::none_of(pb.group_weight.begin(), pb.group_weight.end(), [](double w) { return w > 0; });
         std::vector<int> each;
         if (flat) for (int j = 0; j <= p; ++j) each.push_back(j);
         const std::vector<int>& start = flat ? each : pb.group_start;
@@ -1227,7 +1231,7 @@ struct TallPlan final : LassoPlan {
             const double wg = flat ? 0.0 : pb.group_weight[g];
             ADMM_REQUIRE(gn >= 1 && gn <= kGroupMax && gs == first + count, "internal: bad group partition");
             for (int j = gs; j < gs + gn; ++j)
-                coord[j] = GroupCoord{gs, gn, pb.sgl && gn == 1 ? sgl_single_weight(pb.l1_weight[j], wg) : wg};
+                coord[j] = GroupCoord{gs, gn, sgl && gn == 1 ? sgl_single_weight(pb.l1_weight[j], wg) : wg};
             if (count + gn > kTailElems) flush();
             count += gn;
             if (gn > kTailElems) flush();
@@ -1236,12 +1240,12 @@ struct TallPlan final : LassoPlan {
         gtiles.alloc(tiles.size()); gcoord.alloc(coord.size());
         ADMM_HIP_CHECK(hipMemcpyAsync(gtiles.get(), tiles.data(), tiles.size() * sizeof(int2), hipMemcpyHostToDevice, st));
         ADMM_HIP_CHECK(hipMemcpyAsync(gcoord.get(), coord.data(), coord.size() * sizeof(GroupCoord), hipMemcpyHostToDevice, st));
-        if (pb.sgl) {
+        if (sgl) {
             gl1.alloc((size_t)p);
             ADMM_HIP_CHECK(hipMemcpyAsync(gl1.get(), pb.l1_weight.data(), (size_t)p * sizeof(double), hipMemcpyHostToDevice, st));
         }
         comm_stream_sync(st);                           // (the host vectors go out of scope)
-        gq.tiles = gtiles.get(); gq.coord = gcoord.get(); gq.l1 = pb.sgl ? gl1.get() : nullptr;
+        gq.tiles = gtiles.get(); gq.coord = gcoord.get(); gq.l1 = sgl ? gl1.get() : nullptr;
         return (int)tiles.size();
     }
 
@@ -1317,8 +1321,8 @@ struct TallPlan final : LassoPlan {
             };
             const auto group_tail = [&] {
                 void (*tail)(TallParams, int, GroupTailParams) =
-                    use_sym ? (pb.sgl ? tall_group_tail_kernel<TAIL_SYMV, true> : tall_group_tail_kernel<TAIL_SYMV>)
-                            : (pb.sgl ? tall_group_tail_kernel<TAIL_GEMV, true> : tall_group_tail_kernel<TAIL_GEMV>);
+                    use_sym ? (sgl ? tall_group_tail_kernel<TAIL_SYMV, true> : tall_group_tail_kernel<TAIL_SYMV>)
+                            : (sgl ? tall_group_tail_kernel<TAIL_GEMV, true> : tall_group_tail_kernel<TAIL_GEMV>);
                 hipLaunchKernelGGL(tail, dim3(nwg), dim3(kTailThreads), 0, st, q, par, gq);
             };
             if (mt) {
@@ -1370,7 +1374,7 @@ struct TallPlan final : LassoPlan {
                                    ruw.get(), ruw.get() + ldv, skip);
                 sy.launch(M.get(), ldp, ruw.get(), ruw.get() + ldv, skip, st, SymvNoExtra());
                 hipLaunchKernelGGL(tall_tail_kernel<TAIL_SYMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, PeerExchange{});
-            } else if (pb.box) {                       // two launches, as the Lasso
+            } else if (box) {                          // two launches, as the Lasso
                 xupdate();
                 if (use_sym) hipLaunchKernelGGL(tall_box_tail_kernel<TAIL_SYMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, bq);
                 else hipLaunchKernelGGL(tall_box_tail_kernel<TAIL_GEMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, bq);

@@ -6,6 +6,9 @@
 
 namespace admm {
 
+// What is penalised besides the plain l1 norm (or the elastic net's): one of the tall-only penalties, single device, no REFINE.
+enum class Penalty { PLAIN, GROUP, SGL, MULTITASK, BOX };
+
 struct LassoProblem {
     admm_opts opts{};
     std::vector<double> lambda_in;   // user grid (may be empty -> automatic)
@@ -19,21 +22,18 @@ struct LassoProblem {
     long long col_offset = 0;
     int batch_iters = 0;             // iterations enqueued per host poll (0 = default)
     int profile_stride = 0;          // > 0: time every stride-th x-update launch with HIP events
-    // group lasso (admm_hip_grplasso, tall solver only): group g holds columns [group_start[g], group_start[g + 1]) and is
-    // penalised by group_weight[g] * its Euclidean norm; empty = no groups
+    // the tall-only penalty; each kind fills its own vectors below and leaves the others empty
+    Penalty penalty = Penalty::PLAIN;
+    // GROUP (admm_hip_grplasso): group g holds columns [group_start[g], group_start[g + 1]) and is penalised by group_weight[g] * its
+    // Euclidean norm.  SGL (admm_hip_sgl; sgl_host.h): group_weight holds wg_g = (1 - alpha) w_g and l1_weight [p] l1_j = alpha u_j
     std::vector<int> group_start;
-    std::vector<double> group_weight;
-    // sparse-group lasso (admm_hip_sgl; sgl_host.h): group_weight holds wg_g = (1 - alpha) w_g and l1_weight [p] l1_j = alpha u_j
-    bool sgl = false;
-    std::vector<double> l1_weight;
-    // multi-task lasso (admm_hip_mtlasso, tall solver only): nresp responses share the design (DeviceData.Ymt), row j of the p x nresp
-    // coefficient matrix is penalised by row_weight[j] * its Euclidean norm; 0 = an ordinary single-response problem
+    std::vector<double> group_weight, l1_weight;
+    // MULTITASK (admm_hip_mtlasso): nresp responses share the design (DeviceData.Ymt), row j of the p x nresp coefficient matrix is
+    // penalised by row_weight[j] * its Euclidean norm
     int nresp = 0;
     std::vector<double> row_weight;
-    // box-constrained, weighted elastic net (admm_hip_boxenet, tall solver only; box_host.h): box_lower / box_upper [p] are the caller's
-    // bounds on the ORIGINAL coefficient scale (+-infinity where there is none), penalty_factor [p] the factors u_j; `enet` / `alpha`
-    // above select the prox as for admm_hip_lasso / admm_hip_enet
-    bool box = false;
+    // BOX (admm_hip_boxenet; box_host.h): box_lower / box_upper [p] are the caller's bounds on the ORIGINAL coefficient scale (+-infinity
+    // where there is none), penalty_factor [p] the factors u_j; `enet` / `alpha` above select the prox as for admm_hip_lasso / admm_hip_enet
     std::vector<double> box_lower, box_upper, penalty_factor;
 };
 

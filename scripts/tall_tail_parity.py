@@ -71,8 +71,11 @@ def run_case(name, model, **opts):
 
 
 def single_device():
-    from admm_amd import admm_enet, admm_grplasso, admm_lasso, admm_mtlasso, admm_sgl
+    from admm_amd import admm_boxenet, admm_enet, admm_grplasso, admm_lasso, admm_mtlasso, admm_sgl
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from box_oracle import box_pattern
     x, y = data()
+    lower, upper, factors = box_pattern(P)
     u = np.random.default_rng(31).uniform(0.5, 2.0, P)
     pen = dict(nlambda=NLAM)
     for xu in ("gemv", "sym"):
@@ -84,6 +87,8 @@ def single_device():
             run_case(f"grplasso {gname}", admm_grplasso(x, y, g).penalty(group_weights=weights(sizes), **pen), XUPDATE=xu)
             run_case(f"sgl alpha=0.5 {gname}", admm_sgl(x, y, g, alpha=0.5).penalty(l1_weights=u, **pen), XUPDATE=xu)
         run_case("sgl alpha=1", admm_sgl(x, y, labels(FOURS), alpha=1.0).penalty(l1_weights=u, **pen), XUPDATE=xu)
+        run_case("boxenet lasso prox", admm_boxenet(x, y, lower, upper).penalty(penalty_factor=factors, **pen), XUPDATE=xu)
+        run_case("boxenet alpha=0.5", admm_boxenet(x, y, lower, upper).penalty(alpha=0.5, penalty_factor=factors, **pen), XUPDATE=xu)
     run_case("lasso refined", admm_lasso(x, y).penalty(**pen), XUPDATE="sym", REFINE="1")
     for m in (1, 3, 4, 5, 16):                 # one chunk partly filled, one full, the second with one live slot, all chunks full
         xm, Y = data(m)

@@ -286,3 +286,24 @@ def test_bench_refuses_a_world_size_that_disagrees_with_gpus_without_a_gpu():
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "1"], env=env, capture_output=True, text=True, timeout=120)
     assert r.returncode != 0 and "refusing" in (r.stderr + r.stdout), (r.returncode, r.stderr[-300:])
     assert not [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+
+
+def test_argtypes_of_the_tall_only_entry_points_are_the_declared_ones():
+    """_lib.load() sets these eight by one loop (TALL_ONLY); the lists here are written out from include/admm_hip.h."""
+    from admm_amd import _lib
+    from admm_amd._lib import AdmmOpts, AdmmStats
+    lib = _lib.load()
+    V, I, D = ctypes.c_void_p, ctypes.c_int, ctypes.c_double
+    Dp, Fp, Ip = ctypes.POINTER(ctypes.c_double), ctypes.POINTER(ctypes.c_float), ctypes.POINTER(ctypes.c_int)
+    path = [V, I, I, D, I, I]
+    out = [ctypes.POINTER(AdmmOpts), Dp, Fp, Ip, ctypes.POINTER(AdmmStats)]
+    plan = [ctypes.POINTER(AdmmOpts), ctypes.POINTER(V), Ip]
+    want = {
+        "grplasso": [V, V, I, I, I, Ip, Dp, I] + path,
+        "sgl": [V, V, I, I, I, Ip, Dp, I, Dp, D] + path,
+        "boxenet": [V, V, I, I, I, Dp, Dp, Dp, D] + path,
+        "mtlasso": [V, V, I, I, I, I, Dp] + path,
+    }
+    for name, head in want.items():
+        for fn, rest in ((getattr(lib, "admm_hip_" + name), out), (getattr(lib, "admm_hip_" + name + "_plan_create"), plan)):
+            assert list(fn.argtypes) == head + rest and fn.restype is ctypes.c_int, name
