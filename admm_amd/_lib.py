@@ -78,7 +78,8 @@ EXPORTS = ["admm_hip_lasso", "admm_hip_enet", "admm_hip_parlasso", "admm_hip_lad
            "admm_hip_mtlasso", "admm_hip_mtlasso_plan_create", "admm_hip_test_symv_multi", "admm_hip_test_tall_early_exits",
            "admm_hip_sgl", "admm_hip_sgl_plan_create", "admm_hip_host_sgl_lambda0",
            "admm_hip_boxenet", "admm_hip_boxenet_plan_create", "admm_hip_host_box_lambda0",
-           "admm_hip_test_gemm_nt", "admm_hip_test_cholesky_linvt", "admm_hip_test_spd_inverse_shift"]
+           "admm_hip_test_gemm_nt", "admm_hip_test_cholesky_linvt", "admm_hip_test_spd_inverse_shift",
+           "admm_hip_test_symv_plan", "admm_hip_test_symv_ex", "admm_hip_test_symv_multi_ex", "admm_hip_test_symv_f64acc"]
 
 GROUP_MAX = 1024          # ADMM_HIP_GROUP_MAX
 MT_MAX = 16               # ADMM_HIP_MT_MAX
@@ -242,6 +243,16 @@ def load():
     lib.admm_hip_test_symv.restype = ctypes.c_int
     lib.admm_hip_test_symv_multi.argtypes = [_c_float_p, ctypes.c_int, _c_float_p, ctypes.c_int, ctypes.c_int, _c_float_p]
     lib.admm_hip_test_symv_multi.restype = ctypes.c_int
+    lib.admm_hip_test_symv_plan.argtypes = [ctypes.c_int] * 4 + [_c_int_p, ctypes.POINTER(ctypes.c_longlong), _c_int_p, ctypes.c_int]
+    lib.admm_hip_test_symv_plan.restype = ctypes.c_int
+    lib.admm_hip_test_symv_ex.argtypes = [_c_float_p, ctypes.c_int, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                          _c_float_p, _c_float_p, _c_int_p]
+    lib.admm_hip_test_symv_ex.restype = ctypes.c_int
+    lib.admm_hip_test_symv_multi_ex.argtypes = [_c_float_p, ctypes.c_int, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                _c_float_p, _c_int_p]
+    lib.admm_hip_test_symv_multi_ex.restype = ctypes.c_int
+    lib.admm_hip_test_symv_f64acc.argtypes = [_c_float_p, ctypes.c_int, _c_float_p, _c_float_p, _c_double_p, _c_double_p, _c_int_p]
+    lib.admm_hip_test_symv_f64acc.restype = ctypes.c_int
     lib.admm_hip_test_tall_early_exits.argtypes = [ctypes.POINTER(ctypes.c_longlong)]
     lib.admm_hip_test_tall_early_exits.restype = ctypes.c_int
     lib.admm_hip_test_gram.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]

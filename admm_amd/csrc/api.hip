@@ -592,6 +592,43 @@ int admm_hip_test_symv_multi(const float* A, int p, const float* V, int nr, int 
     });
 }
 
+// The four hooks of the x-update's variants refuse what they cannot run before they look for a device (tests/test_symv_plan_host.py).
+int admm_hip_test_symv_plan(int p, int cus, int part, int nparts, int* sched_out, long long* info_out, int* tiles_out, int tile_capacity) {
+    return guarded([&] {
+        ADMM_REQUIRE(sched_out && info_out && tiles_out, "symv plan hook: sched_out, info_out and tiles_out must not be NULL");
+        ADMM_REQUIRE(p >= 1 && p <= kSymvHookMaxP && cus <= 65536 && nparts >= 1 && nparts <= 64 && part >= 0 && part < nparts && tile_capacity >= 1,
+                     "symv plan hook: p in 1 .. 32768, cus <= 65536, nparts in 1 .. 64, part in 0 .. nparts - 1, tile_capacity >= 1");
+        test_symv_plan(p, cus, part, nparts, sched_out, info_out, tiles_out, tile_capacity);
+    });
+}
+
+int admm_hip_test_symv_ex(const float* A, int p, const float* v0, const float* v1, int variant, int part, int nparts, float* y0, float* y1,
+                          int* sched_out) {
+    return guarded([&] {
+        ADMM_REQUIRE(A && v0 && v1 && y0 && y1 && sched_out, "symv_ex hook: A, v0, v1, y0, y1 and sched_out must not be NULL");
+        ADMM_REQUIRE(p >= 1 && p <= kSymvHookMaxP && variant >= 0 && variant <= 2 && nparts >= 1 && nparts <= 64 && part >= 0 && part < nparts,
+                     "symv_ex hook: p in 1 .. 32768, variant in 0 .. 2, nparts in 1 .. 64, part in 0 .. nparts - 1");
+        test_symv_ex(A, p, v0, v1, variant, part, nparts, y0, y1, sched_out);
+    });
+}
+
+int admm_hip_test_symv_multi_ex(const float* A, int p, const float* V, int nr, int rhs_per_pass, int nt, int finish, float* Yout, int* sched_out) {
+    return guarded([&] {
+        ADMM_REQUIRE(A && V && Yout && sched_out, "symv_multi_ex hook: A, V, Yout and sched_out must not be NULL");
+        ADMM_REQUIRE(p >= 1 && p <= kSymvHookMaxP && nr >= 1 && nr <= 64 && test_symv_rhs_built(rhs_per_pass) && (nt == 0 || nt == 1) && (finish == 0 || finish == 1),
+                     "symv_multi_ex hook: p in 1 .. 32768, nr in 1 .. 64, rhs_per_pass one of the built widths (2, 4, 8, 12), nt and finish 0 or 1");
+        test_symv_multi_ex(A, p, V, nr, rhs_per_pass, nt, finish, Yout, sched_out);
+    });
+}
+
+int admm_hip_test_symv_f64acc(const float* A, int p, const float* v0, const float* v1, double* y0, double* y1, int* sched_out) {
+    return guarded([&] {
+        ADMM_REQUIRE(A && v0 && v1 && y0 && y1 && sched_out, "symv_f64acc hook: A, v0, v1, y0, y1 and sched_out must not be NULL");
+        ADMM_REQUIRE(p >= 1 && p <= kSymvHookMaxP, "symv_f64acc hook: p in 1 .. 32768");
+        test_symv_f64acc(A, p, v0, v1, y0, y1, sched_out);
+    });
+}
+
 int admm_hip_test_tall_early_exits(long long* count) {
     return guarded([&] {
         ADMM_REQUIRE(count != nullptr, "bad arguments");

@@ -630,8 +630,7 @@ struct MtTailParams {
     long long dot_stride, axp_stride;
     const double* row_w;                  // [p] row weights
 };
-constexpr int kMtMax = ADMM_HIP_MT_MAX;
-constexpr int kMtChunk = 4;
+constexpr int kMtMax = ADMM_HIP_MT_MAX;      // kMtChunk: symv_kernels.h
 static_assert(kMtMax % kMtChunk == 0, "whole chunks");
 
 __global__ void __launch_bounds__(kTailThreads)

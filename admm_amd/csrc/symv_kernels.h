@@ -538,10 +538,91 @@ symv2_lower_f64acc_kernel(SymvArgsD a) {
     }
 }
 
-// Number of row blocks, the segment schedule and the tile list (host).
+// Number of row blocks, the segment schedule and the tile list: everything of a plan that is decided on the host from numbers alone
+// (symv_plan_layout below; SymvPlan::init adds the device storage).  Needs no device: the test hook admm_hip_test_symv_plan returns it.
+struct SymvLayout {
+    int p = 0, nrb = 0, ncb = 0, p32 = 0;
+    int nax_rows = 0;              // rows of the axpy partial arrays = the largest number of segments of one strip
+    SymvSched sched;
+    long long ldo = 0;
+    bool nt = false;
+    std::vector<int4> tiles;
+};
+
+// cus: compute units of the device the plan is for.  part / nparts: only the tiles whose 128-column group (index in the full list)
+// % nparts == part -- the row-sharded tall x-update gives every rank an equal share of the triangle; the partial arrays keep the full
+// shape (slots of tiles owned by other ranks stay zero) so that the same consumer code sums them.  Reads the calling thread's SYMV_SCHED.
+inline SymvLayout symv_plan_layout(int p, int cus, int part, int nparts) {
+    SymvLayout L;
+    const int p32 = (p + 31) / 32 * 32;
+    const int nrb = (p + kSyRB - 1) / kSyRB;
+    L.p = p; L.p32 = p32; L.nrb = nrb;
+    L.ncb = (p + kSyCB - 1) / kSyCB;
+    L.ldo = (long long)nrb * kSyRB;
+    SymvSched sched;
+    // Segment schedule (measured on one MI355X with scripts/symv_sched_sweep.py, profiles/r03_symv_sched.md; it/s of the
+    // whole 100-lambda loop against round 2's fixed 256 x 128 tiles):
+    //   * while the triangle is small enough, the narrowest segments that still fit ONE resident round of workgroups
+    //     (4 per CU): more workgroups in flight and no second round -- p = 2048 / 3000: 32 columns, +41 % / +32 %;
+    //     p = 4096: 64 columns, +14 % (32 columns would need a second round there: -17 %);
+    //   * beyond that two classes: wide segments for the long strips, dispatched first, narrow ones (64) for the short
+    //     strips at the end of the launch, so that its end is made of small work units -- p = 6000 / 8000: 128 | 64,
+    //     +8 % / +7 %; p = 10^4: 192 | 64, +5..7 % (38.8-39.6 instead of 41.7 us per iteration); p = 16000: +8 %.
+    // ADMM_HIP_SYMV_SCHED=big,small,split_permille overrides it ("128,128,0" = round 2's tiling).
+    auto count = [&](const SymvSched& sc) { long long t = 0; for (int rb = 0; rb < nrb; ++rb) t += sc.nseg(rb, p32); return t; };
+    const long long slots = 4ll * cus * std::max(1, nparts);      // a rank of the row-sharded solver launches 1 / nparts of the tiles
+    auto uniform = [](int w) { SymvSched sc; sc.width_big = sc.width_small = w; sc.rb_split = 0; return sc; };
+    auto two = [&](int wb, int ws) { SymvSched sc; sc.width_big = wb; sc.width_small = ws; sc.rb_split = nrb / 2; return sc; };
+    if (4 * count(uniform(32)) <= 3 * slots) sched = uniform(32);
+    else if (count(uniform(64)) <= slots) sched = uniform(64);
+    else if (10 * count(two(128, 64)) <= 14 * slots) sched = two(128, 64);
+    else sched = two(192, 64);
+    if (const OptValue* v = opt(Opt::SYMV_SCHED)) {
+        sched.width_big = v->sched[0]; sched.width_small = v->sched[1]; sched.rb_split = (int)((long long)v->sched[2] * nrb / 1000);
+    }
+    std::vector<int4> h;
+    int nax_rows = 1;
+    // long row strips first so that the end of the launch is made of the short strips' (narrow) segments
+    for (int rb = nrb - 1; rb >= 0; --rb) {
+        const int w = sched.width(rb), ns = sched.nseg(rb, p32);
+        nax_rows = std::max(nax_rows, ns);
+        for (int sg = 0; sg < ns; ++sg) {
+            const int c0 = sg * w;
+            const int cols = std::min((rb + 1) * kSyRB, p32);
+            h.push_back(make_int4(rb, c0, std::min(w, cols - c0), sg));
+        }
+    }
+    if (nparts > 1) {
+        // Dealt out in groups of segments that cover whole 128-column blocks of one strip (segment widths of 32 / 64 / 128: 128
+        // columns; 192: 384), not segment by segment: the distributed factorisation (chol_inverse.h) forms, of the inverse,
+        // only the 128 x 128 tiles a rank reads here -- interleaved 32-column segments made every rank read every tile
+        // (measured: 0.78 p^3 flops per rank of 2 where 0.59 p^3 is the share).
+        auto gcd = [](int a, int b) { while (b) { const int t = a % b; a = b; b = t; } return a; };
+        std::vector<int4> mine;
+        int group = -1, last_rb = -1, last_cg = -1;
+        for (const int4& t : h) {
+            const int w = sched.width(t.x);
+            const int gw = w / gcd(w, 128) * 128;
+            const int cg = t.y / gw;
+            if (t.x != last_rb || cg != last_cg) { ++group; last_rb = t.x; last_cg = cg; }
+            if (group % nparts == part) mine.push_back(t);
+        }
+        h.swap(mine);
+    }
+    // The whole triangle is re-read every iteration.  Plain loads while most of it stays in the 256 MB Infinity Cache
+    // between two passes, non-temporal beyond.  Measured crossover (one MI355X, plain vs nt, TB/s on 2p^2 bytes):
+    // p = 10000 5.7 vs 5.3 | 11000 5.90 vs 5.24 | 12000 6.08 vs 5.41 | 13000 4.31 vs 5.50 | 16000 4.1-4.4 vs 5.3-5.4.
+    // (a rank of the row-sharded solver re-reads only its 1 / nparts share)
+    L.nt = (size_t)2 * (size_t)p * (size_t)p / (size_t)std::max(1, nparts) > (size_t)310000000;
+    L.sched = sched; L.nax_rows = nax_rows;
+    L.tiles.swap(h);
+    return L;
+}
+
+// The layout with its device storage: the tile list, the partial arrays (zeroed) and the zero words.
 struct SymvPlan {
     int p = 0, nrb = 0, ncb = 0, ntiles = 0, p32 = 0;
-    int nax_rows = 0;              // rows of the axpy partial arrays = the largest number of segments of one strip
+    int nax_rows = 0;
     SymvSched sched;
     long long ldo = 0;
     DevBuf<int4> tiles;
@@ -552,73 +633,14 @@ struct SymvPlan {
 #ifdef ADMM_HIP_PROBE
     long long* probe = nullptr; mutable int probe_idx = 0;
 #endif
-    // part / nparts: this plan launches only the tiles whose 128-column group (index in the full list) % nparts == part -- the row-sharded
-    // tall x-update gives every rank an equal share of the triangle; the partial arrays keep the full shape (slots of
-    // tiles owned by other ranks stay zero) so that the same consumer code sums them.
     void init(int p_, hipStream_t st, int part = 0, int nparts = 1) {
-        p = p_;
-        p32 = (p + 31) / 32 * 32;
-        nrb = (p + kSyRB - 1) / kSyRB;
-        ncb = (p + kSyCB - 1) / kSyCB;
-        ldo = (long long)nrb * kSyRB;
-        // Segment schedule (measured on one MI355X with scripts/symv_sched_sweep.py, profiles/r03_symv_sched.md; it/s of the
-        // whole 100-lambda loop against round 2's fixed 256 x 128 tiles):
-        //   * while the triangle is small enough, the narrowest segments that still fit ONE resident round of workgroups
-        //     (4 per CU): more workgroups in flight and no second round -- p = 2048 / 3000: 32 columns, +41 % / +32 %;
-        //     p = 4096: 64 columns, +14 % (32 columns would need a second round there: -17 %);
-        //   * beyond that two classes: wide segments for the long strips, dispatched first, narrow ones (64) for the short
-        //     strips at the end of the launch, so that its end is made of small work units -- p = 6000 / 8000: 128 | 64,
-        //     +8 % / +7 %; p = 10^4: 192 | 64, +5..7 % (38.8-39.6 instead of 41.7 us per iteration); p = 16000: +8 %.
-        // ADMM_HIP_SYMV_SCHED=big,small,split_permille overrides it ("128,128,0" = round 2's tiling).
-        auto count = [&](const SymvSched& sc) { long long t = 0; for (int rb = 0; rb < nrb; ++rb) t += sc.nseg(rb, p32); return t; };
         int cus = 256;
         { int dev = 0; hipDeviceProp_t prop; if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount; }
-        const long long slots = 4ll * cus * std::max(1, nparts);      // a rank of the row-sharded solver launches 1 / nparts of the tiles
-        auto uniform = [](int w) { SymvSched sc; sc.width_big = sc.width_small = w; sc.rb_split = 0; return sc; };
-        auto two = [&](int wb, int ws) { SymvSched sc; sc.width_big = wb; sc.width_small = ws; sc.rb_split = nrb / 2; return sc; };
-        if (4 * count(uniform(32)) <= 3 * slots) sched = uniform(32);
-        else if (count(uniform(64)) <= slots) sched = uniform(64);
-        else if (10 * count(two(128, 64)) <= 14 * slots) sched = two(128, 64);
-        else sched = two(192, 64);
-        if (const OptValue* v = opt(Opt::SYMV_SCHED)) {
-            sched.width_big = v->sched[0]; sched.width_small = v->sched[1]; sched.rb_split = (int)((long long)v->sched[2] * nrb / 1000);
-        }
-        std::vector<int4> h;
-        nax_rows = 1;
-        // long row strips first so that the end of the launch is made of the short strips' (narrow) segments
-        for (int rb = nrb - 1; rb >= 0; --rb) {
-            const int w = sched.width(rb), ns = sched.nseg(rb, p32);
-            nax_rows = std::max(nax_rows, ns);
-            for (int sg = 0; sg < ns; ++sg) {
-                const int c0 = sg * w;
-                const int cols = std::min((rb + 1) * kSyRB, p32);
-                h.push_back(make_int4(rb, c0, std::min(w, cols - c0), sg));
-            }
-        }
-        if (nparts > 1) {
-            // Dealt out in groups of segments that cover whole 128-column blocks of one strip (segment widths of 32 / 64 / 128: 128
-            // columns; 192: 384), not segment by segment: the distributed factorisation (chol_inverse.h) forms, of the inverse,
-            // only the 128 x 128 tiles a rank reads here -- interleaved 32-column segments made every rank read every tile
-            // (measured: 0.78 p^3 flops per rank of 2 where 0.59 p^3 is the share).
-            auto gcd = [](int a, int b) { while (b) { const int t = a % b; a = b; b = t; } return a; };
-            std::vector<int4> mine;
-            int group = -1, last_rb = -1, last_cg = -1;
-            for (const int4& t : h) {
-                const int w = sched.width(t.x);
-                const int gw = w / gcd(w, 128) * 128;
-                const int cg = t.y / gw;
-                if (t.x != last_rb || cg != last_cg) { ++group; last_rb = t.x; last_cg = cg; }
-                if (group % nparts == part) mine.push_back(t);
-            }
-            h.swap(mine);
-        }
+        SymvLayout L = symv_plan_layout(p_, cus, part, nparts);
+        p = L.p; nrb = L.nrb; ncb = L.ncb; p32 = L.p32; nax_rows = L.nax_rows; sched = L.sched; ldo = L.ldo; nt = L.nt;
+        htiles.swap(L.tiles);
+        const std::vector<int4>& h = htiles;
         ntiles = (int)h.size();
-        htiles = h;
-        // The whole triangle is re-read every iteration.  Plain loads while most of it stays in the 256 MB Infinity Cache
-        // between two passes, non-temporal beyond.  Measured crossover (one MI355X, plain vs nt, TB/s on 2p^2 bytes):
-        // p = 10000 5.7 vs 5.3 | 11000 5.90 vs 5.24 | 12000 6.08 vs 5.41 | 13000 4.31 vs 5.50 | 16000 4.1-4.4 vs 5.3-5.4.
-        // (a rank of the row-sharded solver re-reads only its 1 / nparts share)
-        nt = (size_t)2 * (size_t)p * (size_t)p / (size_t)std::max(1, nparts) > (size_t)310000000;
         tiles.alloc(std::max<size_t>(h.size(), 1));
         if (!h.empty()) ADMM_HIP_CHECK(hipMemcpyAsync(tiles.get(), h.data(), h.size() * sizeof(int4), hipMemcpyHostToDevice, st));
         dot0.alloc((size_t)nrb * ldo); dot1.alloc((size_t)nrb * ldo);
@@ -730,6 +752,7 @@ void symvn_launch(const SymvPlan& sy, int nr, const SymvNArgs& a, hipStream_t st
 // the loads of ALL the pairs issued before any is consumed: one memory round trip per 8 NL partials of every pair instead of KB
 // dependent ones.  Per pair the additions are symv_sum_partials' in its order (8 slots per step here, 16 there: the running sums take
 // the same terms in the same order), so a[k], b[k] are its values to the bit.  Pairs >= npair are not loaded (a = b = 0).
+constexpr int kMtChunk = 4;      // the KB of the multi-task tail (lasso_tall.hip, tall_mt_tail_kernel) and of the test hook that walks the pairs as it does
 template <int NL, int KB>
 __device__ __forceinline__ void symv_sum_partials_n(const float* __restrict__ dot, long long dot_stride, const float* __restrict__ axp, long long axp_stride,
                                                     int npair, long long ldo, int nrb, const SymvSched sched, int p32, int i, int sub, bool valid,

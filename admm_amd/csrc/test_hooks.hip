@@ -3,6 +3,7 @@
 #include "symv_kernels.h"
 #include "prep.h"
 #include "gather_kernels.h"
+#include "test_hooks.h"
 #include <cstring>
 #include <limits>
 #include <vector>
@@ -94,6 +95,171 @@ void test_symv_multi(const float* A, int p, const float* V, int nr, int rhs_per_
     ADMM_HIP_CHECK(hipGetLastError());
     ADMM_HIP_CHECK(hipMemcpy2DAsync(Yout, (size_t)p * sizeof(float), dY.get(), ldv * sizeof(float), (size_t)p * sizeof(float), nr,
                                     hipMemcpyDeviceToHost, st.s));
+    st.sync();
+}
+
+// ---- every variant of the symmetric x-update under every tile schedule (tests/test_gpu_symv_variants.py).  The three hooks below
+// use the tall plan's storage (lda = round_up(p, 128), vectors zero padded to 256), the plan's own tile list and partial arrays, and
+// report the schedule the plan used (sched_out: width_big, width_small, rb_split) so that a test can assert which class it ran.
+
+static void report_sched(const SymvSched& sc, int* sched_out) {
+    sched_out[0] = sc.width_big; sched_out[1] = sc.width_small; sched_out[2] = sc.rb_split;
+}
+
+bool test_symv_rhs_built(int rhs_per_pass) {
+    for (int k = 0; k < kSyNRCount; ++k) if (kSyNR[k] == rhs_per_pass) return true;
+    return false;
+}
+
+// The host half of SymvPlan::init alone (symv_plan_layout): no device.  info_out: nrb, p32, ldo, nax_rows, nt, number of tiles;
+// tiles_out: (row block, first column, width, segment) of every tile, in launch order.
+void test_symv_plan(int p, int cus, int part, int nparts, int* sched_out, long long* info_out, int* tiles_out, int tile_capacity) {
+    const SymvLayout L = symv_plan_layout(p, cus <= 0 ? 256 : cus, part, nparts);
+    ADMM_REQUIRE((long long)L.tiles.size() <= (long long)tile_capacity,
+                 "symv plan hook: tile_capacity is too small for the " + std::to_string(L.tiles.size()) + " tiles of this plan");
+    report_sched(L.sched, sched_out);
+    info_out[0] = L.nrb; info_out[1] = L.p32; info_out[2] = L.ldo; info_out[3] = L.nax_rows; info_out[4] = L.nt ? 1 : 0; info_out[5] = (long long)L.tiles.size();
+    for (size_t k = 0; k < L.tiles.size(); ++k) {
+        const int4 t = L.tiles[k];
+        tiles_out[4 * k + 0] = t.x; tiles_out[4 * k + 1] = t.y; tiles_out[4 * k + 2] = t.z; tiles_out[4 * k + 3] = t.w;
+    }
+}
+
+// symv2_lower_kernel, one chosen instantiation (variant 0 plain, 1 non-temporal, 2 with the mid-tile verdict check) over the tiles of
+// rank `part` of `nparts`, into the plan's zeroed partial arrays, and the usual consumer.  The verdict of variant 2 is the plan's zero
+// words with discard = ~0: no tile can leave, so the count of early exits must come back 0.
+void test_symv_ex(const float* A, int p, const float* v0, const float* v1, int variant, int part, int nparts, float* y0, float* y1, int* sched_out) {
+    require_device();
+    Stream st;
+    const long long lda = round_up(p, 128), ldv = round_up(p, 256);
+    DevBuf<float> dA((size_t)lda * lda), d0(ldv), d1(ldv), o0(ldv), o1(ldv);
+    DevBuf<unsigned long long> early(1);
+    dA.zero(st.s); d0.zero(st.s); d1.zero(st.s); early.zero(st.s);
+    ADMM_HIP_CHECK(hipMemcpy2DAsync(dA.get(), lda * sizeof(float), A, (size_t)p * sizeof(float), (size_t)p * sizeof(float), p,
+                                    hipMemcpyHostToDevice, st.s));
+    ADMM_HIP_CHECK(hipMemcpyAsync(d0.get(), v0, (size_t)p * sizeof(float), hipMemcpyHostToDevice, st.s));
+    ADMM_HIP_CHECK(hipMemcpyAsync(d1.get(), v1, (size_t)p * sizeof(float), hipMemcpyHostToDevice, st.s));
+    SymvPlan sy;
+    sy.init(p, st.s, part, nparts);
+    report_sched(sy.sched, sched_out);
+    sy.nt = variant == 1;                      // launch() takes the non-temporal instantiation on this flag alone
+    SymvVerdict vd;
+    if (variant == 2) { vd.words = sy.zero.get(); vd.discard = ~0ull; vd.early = early.get(); vd.mid = true; }
+    sy.launch(dA.get(), lda, d0.get(), d1.get(), nullptr, st.s, SymvNoExtra(), nullptr, nullptr, vd);
+    ADMM_HIP_CHECK(hipGetLastError());
+    const int per = 256 / kSySumLanes;
+    hipLaunchKernelGGL(test_symv_finish_kernel, dim3((p + per - 1) / per), dim3(256), 0, st.s, sy.dot0.get(), sy.dot1.get(),
+                       sy.axp0.get(), sy.axp1.get(), sy.ldo, sy.nrb, sy.sched, sy.p32, p, o0.get(), o1.get());
+    ADMM_HIP_CHECK(hipGetLastError());
+    unsigned long long left = 0;
+    ADMM_HIP_CHECK(hipMemcpyAsync(y0, o0.get(), (size_t)p * sizeof(float), hipMemcpyDeviceToHost, st.s));
+    ADMM_HIP_CHECK(hipMemcpyAsync(y1, o1.get(), (size_t)p * sizeof(float), hipMemcpyDeviceToHost, st.s));
+    ADMM_HIP_CHECK(hipMemcpyAsync(&left, early.get(), sizeof(left), hipMemcpyDeviceToHost, st.s));
+    st.sync();
+    if (left != 0)
+        throw Error(ADMM_ERR_INTERNAL, std::to_string(left) + " tiles left early on a verdict word that cannot equal `discard`");
+}
+
+// test_symvn_finish_kernel with the consumer the multi-task tail really uses: symv_sum_partials_n over chunks of kMtChunk pairs, walked
+// as tall_mt_tail_kernel walks them (chunk k0: planes from 2 k0, nk = min(kMtChunk, npair - k0) pairs of it valid).
+__global__ void __launch_bounds__(256)
+test_symvn_finish_chunks_kernel(const float* dot, long long dot_stride, const float* axp, long long axp_stride, long long ldo, int nrb, SymvSched sched,
+                                int p32, int p, int npair, float* y, long long ldy) {
+    const int sub = threadIdx.x & (kSySumLanes - 1);
+    const int i = blockIdx.x * (256 / kSySumLanes) + threadIdx.x / kSySumLanes;
+    for (int k0 = 0; k0 < npair; k0 += kMtChunk) {
+        const int nk = min(kMtChunk, npair - k0);
+        float a[kMtChunk], b[kMtChunk];
+        symv_sum_partials_n<kSySumLanes, kMtChunk>(dot + (size_t)(2 * k0) * dot_stride, dot_stride, axp + (size_t)(2 * k0) * axp_stride, axp_stride,
+                                                   nk, ldo, nrb, sched, p32, i, sub, i < p, a, b);
+#pragma unroll
+        for (int kk = 0; kk < kMtChunk; ++kk) {
+            if (kk < nk && i < p && sub == 0) { y[(size_t)(2 * (k0 + kk)) * ldy + i] = a[kk]; y[(size_t)(2 * (k0 + kk) + 1) * ldy + i] = b[kk]; }
+        }
+    }
+}
+
+// test_symv_multi with the instantiation (nt) and the consumer (finish 0: symv_sum_partials pair by pair, 1: symv_sum_partials_n) chosen.
+void test_symv_multi_ex(const float* A, int p, const float* V, int nr, int rhs_per_pass, int nt, int finish, float* Yout, int* sched_out) {
+    require_device();
+    Stream st;
+    const long long lda = round_up(p, 128), ldv = round_up(p, 256);
+    const int nv = (nr + 1) / 2 * 2;
+    DevBuf<float> dA((size_t)lda * lda), dV((size_t)nv * ldv), dY((size_t)nv * ldv);
+    dA.zero(st.s); dV.zero(st.s);
+    ADMM_HIP_CHECK(hipMemcpy2DAsync(dA.get(), lda * sizeof(float), A, (size_t)p * sizeof(float), (size_t)p * sizeof(float), p,
+                                    hipMemcpyHostToDevice, st.s));
+    ADMM_HIP_CHECK(hipMemcpy2DAsync(dV.get(), ldv * sizeof(float), V, (size_t)p * sizeof(float), (size_t)p * sizeof(float), nr,
+                                    hipMemcpyHostToDevice, st.s));
+    SymvPlan sy;
+    sy.init(p, st.s);
+    report_sched(sy.sched, sched_out);
+    sy.nt = nt != 0;                           // symvn_launch takes the non-temporal instantiations on this flag alone
+    const size_t ds = (size_t)sy.nrb * sy.ldo, as = (size_t)sy.nax_rows * sy.ldo;
+    DevBuf<float> dot((size_t)nv * ds), axp((size_t)nv * as);
+    dot.zero(st.s); axp.zero(st.s);
+    for (int r0 = 0; r0 < nv; r0 += rhs_per_pass) {
+        SymvNArgs a;
+        a.A = dA.get(); a.lda = lda; a.p = p;
+        a.v = dV.get() + (size_t)r0 * ldv; a.vstride = ldv;
+        a.dot = dot.get() + (size_t)r0 * ds; a.dot_stride = (long long)ds;
+        a.axp = axp.get() + (size_t)r0 * as; a.axp_stride = (long long)as;
+        a.nvec = std::min(rhs_per_pass, nv - r0); a.ldo = sy.ldo; a.tiles = sy.tiles.get(); a.skip = nullptr;
+        symvn_launch(sy, rhs_per_pass, a, st.s, SymvNoExtra());
+    }
+    ADMM_HIP_CHECK(hipGetLastError());
+    const int per = 256 / kSySumLanes;
+    if (finish == 0)
+        hipLaunchKernelGGL(test_symvn_finish_kernel, dim3((p + per - 1) / per), dim3(256), 0, st.s, dot.get(), (long long)ds, axp.get(), (long long)as,
+                           sy.ldo, sy.nrb, sy.sched, sy.p32, p, nv / 2, dY.get(), ldv);
+    else
+        hipLaunchKernelGGL(test_symvn_finish_chunks_kernel, dim3((p + per - 1) / per), dim3(256), 0, st.s, dot.get(), (long long)ds, axp.get(), (long long)as,
+                           sy.ldo, sy.nrb, sy.sched, sy.p32, p, nv / 2, dY.get(), ldv);
+    ADMM_HIP_CHECK(hipGetLastError());
+    ADMM_HIP_CHECK(hipMemcpy2DAsync(Yout, (size_t)p * sizeof(float), dY.get(), ldv * sizeof(float), (size_t)p * sizeof(float), nr,
+                                    hipMemcpyDeviceToHost, st.s));
+    st.sync();
+}
+
+// The refinement's products (lasso_tall.hip): symv2_lower_f64acc_kernel on double partial planes of the plan's shape, summed as
+// tall_refine_resid_kernel sums them.
+__global__ void __launch_bounds__(256)
+test_symv_finish_f64_kernel(const double* dot0, const double* dot1, const double* axp0, const double* axp1, long long ldo, int nrb, SymvSched sched, int p32,
+                            int p, double* y0, double* y1) {
+    const int sub = threadIdx.x & (kSySumLanes - 1);
+    const int i = blockIdx.x * (256 / kSySumLanes) + threadIdx.x / kSySumLanes;
+    double a, b;
+    symv_sum_partials<kSySumLanes, double>(dot0, dot1, axp0, axp1, ldo, nrb, sched, p32, i, sub, i < p, a, b);
+    if (i < p && sub == 0) { y0[i] = a; y1[i] = b; }
+}
+
+void test_symv_f64acc(const float* A, int p, const float* v0, const float* v1, double* y0, double* y1, int* sched_out) {
+    require_device();
+    Stream st;
+    const long long lda = round_up(p, 128), ldv = round_up(p, 256);
+    DevBuf<float> dA((size_t)lda * lda), d0(ldv), d1(ldv);
+    DevBuf<double> o0(ldv), o1(ldv);
+    dA.zero(st.s); d0.zero(st.s); d1.zero(st.s);
+    ADMM_HIP_CHECK(hipMemcpy2DAsync(dA.get(), lda * sizeof(float), A, (size_t)p * sizeof(float), (size_t)p * sizeof(float), p,
+                                    hipMemcpyHostToDevice, st.s));
+    ADMM_HIP_CHECK(hipMemcpyAsync(d0.get(), v0, (size_t)p * sizeof(float), hipMemcpyHostToDevice, st.s));
+    ADMM_HIP_CHECK(hipMemcpyAsync(d1.get(), v1, (size_t)p * sizeof(float), hipMemcpyHostToDevice, st.s));
+    SymvPlan sy;
+    sy.init(p, st.s);
+    report_sched(sy.sched, sched_out);
+    DevBuf<double> dD0((size_t)sy.nrb * sy.ldo), dD1((size_t)sy.nrb * sy.ldo), xD0((size_t)sy.nax_rows * sy.ldo), xD1((size_t)sy.nax_rows * sy.ldo);
+    dD0.zero(st.s); dD1.zero(st.s); xD0.zero(st.s); xD1.zero(st.s);
+    SymvArgsD ad;
+    ad.A = dA.get(); ad.lda = lda; ad.p = p; ad.v0 = d0.get(); ad.v1 = d1.get();
+    ad.dot0 = dD0.get(); ad.dot1 = dD1.get(); ad.axp0 = xD0.get(); ad.axp1 = xD1.get(); ad.ldo = sy.ldo; ad.tiles = sy.tiles.get(); ad.skip = nullptr;
+    hipLaunchKernelGGL(symv2_lower_f64acc_kernel, dim3(sy.ntiles), dim3(kSyThreads), 0, st.s, ad);
+    ADMM_HIP_CHECK(hipGetLastError());
+    const int per = 256 / kSySumLanes;
+    hipLaunchKernelGGL(test_symv_finish_f64_kernel, dim3((p + per - 1) / per), dim3(256), 0, st.s, dD0.get(), dD1.get(), xD0.get(), xD1.get(),
+                       sy.ldo, sy.nrb, sy.sched, sy.p32, p, o0.get(), o1.get());
+    ADMM_HIP_CHECK(hipGetLastError());
+    ADMM_HIP_CHECK(hipMemcpyAsync(y0, o0.get(), (size_t)p * sizeof(double), hipMemcpyDeviceToHost, st.s));
+    ADMM_HIP_CHECK(hipMemcpyAsync(y1, o1.get(), (size_t)p * sizeof(double), hipMemcpyDeviceToHost, st.s));
     st.sync();
 }
 

@@ -639,6 +639,27 @@ ADMM_HIP_API int admm_hip_test_symv(const float* A, int p, const float* v0, cons
 /* The multi-task lasso's multi-vector form of it: Yout[r] = A V[r] for the nr (<= 64) vectors V [nr][p], rhs_per_pass (a built width:
  * 2, 4, 8 or 12) of them per pass over the triangle; vectors 2k and 2k + 1 share the partial sums of one "response".  Yout [nr][p]. */
 ADMM_HIP_API int admm_hip_test_symv_multi(const float* A, int p, const float* V, int nr, int rhs_per_pass, float* Yout);
+/* The host half of the tall x-update's plan, without a device: the column-segment schedule and the tile list a plan for order p gets on
+ * a device with `cus` compute units (<= 0: 256) under the calling thread's SYMV_SCHED, for rank `part` of `nparts` of the row-sharded
+ * solver (1: all tiles).  sched_out[3]: width of the long strips' segments, of the short strips', first long strip.  info_out[6]: row
+ * strips, p rounded up to 32, leading dimension of the partial arrays, rows of the axpy partial arrays, 1 where the plan streams with
+ * non-temporal loads, number of tiles.  tiles_out: one int[4] record per tile in launch order (row strip, first column, width, segment
+ * of the strip); tile_capacity records fit (too few: ADMM_ERR_INVALID_ARG, the message says how many are needed). */
+ADMM_HIP_API int admm_hip_test_symv_plan(int p, int cus, int part, int nparts, int* sched_out, long long* info_out, int* tiles_out,
+                                         int tile_capacity);
+/* admm_hip_test_symv with the instantiation and the share of the tiles chosen: variant 0 plain loads, 1 non-temporal loads, 2 the form
+ * that also looks for the verdict between the chunks of a tile, given a verdict that can never say "discard" (a tile that leaves all
+ * the same: ADMM_ERR_INTERNAL); only the tiles of rank `part` of `nparts` are launched, into zeroed partial arrays, so the results of
+ * the parts add up to the product.  sched_out[3]: the schedule the plan used, as above.  p <= 32768. */
+ADMM_HIP_API int admm_hip_test_symv_ex(const float* A, int p, const float* v0, const float* v1, int variant, int part, int nparts,
+                                       float* y0, float* y1, int* sched_out);
+/* admm_hip_test_symv_multi with the non-temporal instantiations forced (nt = 1) or not (0), and the consumer chosen: finish 0 sums the
+ * partials pair by pair (as admm_hip_test_symv_multi), 1 in chunks of pairs with the routine and the walk of the multi-task tail. */
+ADMM_HIP_API int admm_hip_test_symv_multi_ex(const float* A, int p, const float* V, int nr, int rhs_per_pass, int nt, int finish,
+                                             float* Yout, int* sched_out);
+/* The double-accumulating form of the refined x-update (ADMM_HIP_REFINE): the same products of the float matrix and float vectors
+ * with every product and sum in double, on double partial arrays, summed as the refinement's residual kernel sums them.  y0, y1 double. */
+ADMM_HIP_API int admm_hip_test_symv_f64acc(const float* A, int p, const float* v0, const float* v1, double* y0, double* y1, int* sched_out);
 /* Tiles of the tall x-update that left early because the launch they belonged to was known to be discarded (the first launch after a
  * converged lambda, the launch of the last decision; ADMM_HIP_SYMV_VERDICT=0: none), counted over the most recent tall lasso /
  * elastic-net / group-lasso path run by the CALLING THREAD.  How many leave is a matter of timing; the results do not depend on it. */
