@@ -555,6 +555,77 @@ class ADMM_QuantReg(ADMM_LAD):
         return fit
 
 
+class ADMM_Huber_fit:
+    def __init__(self, delta, tau, beta, niter, stats):
+        self.delta = delta          # numeric nfit
+        self.tau = tau              # numeric nfit
+        self.beta = beta            # (p + 1) x nfit, column k = (delta[k], tau[k]), intercept first
+        self.niter = niter          # integer nfit
+        self.stats = stats
+
+    def __repr__(self):
+        return (f"ADMM Huber regression fitting result\n\n$delta\n{self.delta}\n\n$tau\n{self.tau}\n\n$beta\n"
+                f"<{self.beta.shape[0]} x {self.beta.shape[1]}> matrix\n\n$niter\n{self.niter}")
+
+    def show(self):
+        print(repr(self))
+
+
+class ADMM_Huber(ADMM_LAD):
+    """Huber / expectile regression on LAD's loop (admm_hip_huber): one fit per pair (delta[k], tau[k]), the setup paid once.  delta is in
+    the units of y (inf: expectile regression), tau = 0.5 the symmetric Huber loss.  The intercept is fitted as ADMM_QuantReg's."""
+
+    def __init__(self, x, y, delta=1.345, tau=0.5, intercept=True, n=None, p=None):
+        n_, p_ = _shape(x, n, p)
+        if n_ <= p_ + (1 if intercept else 0):
+            _stop("nrow(x) must be greater than ncol(x) + 1 (the intercept is fitted)" if intercept else "nrow(x) must be greater than ncol(x)")
+        ADMM_LAD.__init__(self, x, y, intercept, n, p)
+        dl = np.atleast_1d(np.asarray(delta, dtype=np.float64))
+        t = np.atleast_1d(np.asarray(tau, dtype=np.float64))
+        if dl.ndim != 1 or t.ndim != 1:
+            _stop("delta and tau must be scalars or 1-D arrays")
+        if dl.size != t.size and dl.size != 1 and t.size != 1:
+            _stop("delta and tau must have one common length (or length 1)")
+        nfit = max(dl.size, t.size)
+        if min(dl.size, t.size) < 1 or nfit > 4096:
+            _stop("delta and tau must hold between 1 and 4096 fits")
+        if np.any(np.isnan(dl)) or not np.all(dl > 0):
+            _stop("every delta must be positive (inf: expectile regression)")
+        if not (np.all(np.isfinite(t)) and np.all(t > 0) and np.all(t < 1)):
+            _stop("every tau must lie strictly between 0 and 1")
+        self.delta = np.array(np.broadcast_to(dl, (nfit,)))
+        self.tau = np.array(np.broadcast_to(t, (nfit,)))
+
+    def fit(self, trace=False, state=0):
+        """-> ADMM_Huber_fit.  trace / state (as ADMM_LAD.fit, admm_hip_huber_state) for a single fit only."""
+        lib = _lib.load()
+        xp, xmem, xk = as_input(self.x)
+        yp, ymem, yk = as_input(self.y)
+        if xmem != ymem:
+            _stop("x and y must live in the same memory space")
+        nfit = int(self.tau.size)
+        if (trace or state) and nfit != 1:
+            _stop("trace and state are recorded for a single fit")
+        o = AdmmOpts(self.maxit, self.eps_abs, self.eps_rel, self.rho)
+        beta = np.zeros((self.p + 1) * nfit, dtype=np.float64)
+        niter = np.zeros(nfit, dtype=np.int32)
+        stats = AdmmStats()
+        dp = ctypes.POINTER(ctypes.c_double)
+        bp, np_ = beta.ctypes.data_as(dp), niter.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+        if trace:
+            tr, ntr = _trace_buffers(self.maxit)
+            sbuf, nst = _state_buffers(state, self.n)
+            check(lib.admm_hip_huber_state(xp, yp, self.n, self.p, xmem, int(self.intercept), float(self.delta[0]), float(self.tau[0]), ctypes.byref(o),
+                                           bp, np_, ctypes.byref(stats), *_trace_args(tr, ntr), *_state_args(sbuf, nst)))
+        else:
+            check(lib.admm_hip_huber(xp, yp, self.n, self.p, xmem, int(self.intercept), self.delta.ctypes.data_as(dp), self.tau.ctypes.data_as(dp), nfit,
+                                     ctypes.byref(o), bp, np_, ctypes.byref(stats)))
+        fit = ADMM_Huber_fit(self.delta.copy(), self.tau.copy(), beta.reshape(nfit, self.p + 1).T.copy(), niter.copy(), stats.as_dict())
+        fit.trace = tr[:ntr.value].copy() if trace else None
+        fit.state = sbuf[:nst.value].copy() if (trace and state) else None
+        return fit
+
+
 class LassoPlan:
     """Prepared problem (admm_hip_lasso_plan_*): setup once, run the lambda path repeatedly.
 
@@ -661,6 +732,10 @@ def admm_lad(x, y, intercept=True, **kw):
 
 def admm_quantreg(x, y, tau=0.5, intercept=True, **kw):
     return ADMM_QuantReg(x, y, tau, intercept, **kw)
+
+
+def admm_huber(x, y, delta=1.345, tau=0.5, intercept=True, **kw):
+    return ADMM_Huber(x, y, delta, tau, intercept, **kw)
 
 
 def admm_bp(x, y, **kw):

@@ -130,6 +130,19 @@ int admm_hip_quantreg(const double* x, const double* y, int n, int p, int mem, i
     return guarded([&] { quantreg(x, y, n, p, mem, intercept, tau, ntau, opts, DenseOut{beta_out, niter_out, stats}); });
 }
 
+int admm_hip_huber(const double* x, const double* y, int n, int p, int mem, int intercept, const double* delta, const double* tau, int nfit,
+                   const admm_opts* opts, double* beta_out, int* niter_out, admm_stats* stats) {
+    return guarded([&] { huber(x, y, n, p, mem, intercept, delta, tau, nfit, opts, DenseOut{beta_out, niter_out, stats}); });
+}
+
+int admm_hip_huber_state(const double* x, const double* y, int n, int p, int mem, int intercept, double delta, double tau, const admm_opts* opts,
+                         double* beta_out, int* niter_out, admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out,
+                         double* state_out, long long state_cap, long long* nstate_out) {
+    return guarded([&] {
+        huber(x, y, n, p, mem, intercept, &delta, &tau, 1, opts, DenseOut{beta_out, niter_out, stats, {trace_out, trace_cap, ntrace_out}, {state_out, state_cap, nstate_out}});
+    });
+}
+
 int admm_hip_quantreg_state(const double* x, const double* y, int n, int p, int mem, int intercept, double tau, const admm_opts* opts,
                             double* beta_out, int* niter_out, admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out,
                             double* state_out, long long state_cap, long long* nstate_out) {

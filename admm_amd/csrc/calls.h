@@ -57,6 +57,9 @@ struct DenseOut { double* beta_out; int* niter_out; admm_stats* stats; TraceOut 
 void lad(const double* x, const double* y, int n, int p, int mem, int intercept, const admm_opts* opts, const DenseOut& out);
 // out.beta_out: (p + 1) x ntau, out.niter_out: ntau; trace / state for ntau = 1 only
 void quantreg(const double* x, const double* y, int n, int p, int mem, int intercept, const double* tau, int ntau, const admm_opts* opts, const DenseOut& out);
+// tau = NULL: 0.5 for every fit; out as quantreg's with nfit columns
+void huber(const double* x, const double* y, int n, int p, int mem, int intercept, const double* delta, const double* tau, int nfit, const admm_opts* opts,
+           const DenseOut& out);
 void bp(const double* x, const double* y, int n, int p, int mem, const admm_opts* opts, const DenseOut& out);
 // admm_hip_parbp(_traced): over in-process ranks when PAR_DEVICES lists several devices; parbp_dist: this rank's columns of p_total
 void parbp(const double* x, const double* y, int n, int p, int mem, int nthread, const admm_opts* opts, const DenseOut& out);

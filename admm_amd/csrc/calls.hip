@@ -286,13 +286,11 @@ void lad(const double* x, const double* y, int n, int p, int mem, int intercept,
               [&](const DeviceData<double>& d, DenseResult& res, hipStream_t st) { solve_lad(d, *opts, res, st); }, out);
 }
 
-// admm_hip_quantreg: LAD's checks and standardisation (always TRUE), one loop per quantile on one setup (solve_quantreg).  The
-// intercept is FITTED (a column of ones behind the standardised X), not recovered from the means as LAD's: n > p + intercept.
-void quantreg(const double* x, const double* y, int n, int p, int mem, int intercept, const double* tau, int ntau, const admm_opts* opts, const DenseOut& out) {
-    ADMM_REQUIRE(tau != nullptr, "tau must not be NULL");
-    ADMM_REQUIRE(ntau >= 1 && ntau <= 4096, "the number of quantiles must be within [1, 4096]");
-    for (int k = 0; k < ntau; ++k) ADMM_REQUIRE(std::isfinite(tau[k]) && tau[k] > 0.0 && tau[k] < 1.0, "every tau must lie strictly between 0 and 1");
-    ADMM_REQUIRE(ntau == 1 || out.trace.cap == 0, "the decision trace is recorded for a single tau");
+namespace {
+// What admm_hip_quantreg and admm_hip_huber share behind their own argument checks: the shape rule of a fitted intercept, LAD's
+// standardisation, nfit columns out.  solve: solve_quantreg / solve_huber on the standardised data.
+using GridSolve = std::function<void(DeviceData<double>&, bool, QuantResult&, hipStream_t)>;
+void run_lad_grid(const double* x, const double* y, int n, int p, int mem, int intercept, int ntau, const admm_opts* opts, const GridSolve& solve, const DenseOut& out) {
     const bool icpt = intercept != 0;
     check_dense(x, y, n, p, mem, opts, (long long)n > (long long)p + (icpt ? 1 : 0),
                 icpt ? "nrow(x) must be greater than ncol(x) + 1 (the intercept is fitted)" : "nrow(x) must be greater than ncol(x)", true, out);
@@ -304,11 +302,38 @@ void quantreg(const double* x, const double* y, int n, int p, int mem, int inter
     QuantResult res;
     begin_result(res.dense, d, out.trace);
     res.dense.state_cap = out.state.cap;
-    solve_quantreg(d, icpt, *opts, tau, ntau, res, st.s);
+    solve(d, icpt, res, st.s);
     std::memcpy(out.beta_out, res.beta.data(), res.beta.size() * sizeof(double));
     for (int k = 0; k < ntau; ++k) out.niter_out[k] = res.niter[k];
     store_state(res.dense, out.state);
     finish_result(res.dense, t0, out.trace, out.stats);
+}
+}  // namespace
+
+// admm_hip_quantreg: LAD's checks and standardisation (always TRUE), one loop per quantile on one setup (solve_quantreg).  The
+// intercept is FITTED (a column of ones behind the standardised X), not recovered from the means as LAD's: n > p + intercept.
+void quantreg(const double* x, const double* y, int n, int p, int mem, int intercept, const double* tau, int ntau, const admm_opts* opts, const DenseOut& out) {
+    ADMM_REQUIRE(tau != nullptr, "tau must not be NULL");
+    ADMM_REQUIRE(ntau >= 1 && ntau <= 4096, "the number of quantiles must be within [1, 4096]");
+    for (int k = 0; k < ntau; ++k) ADMM_REQUIRE(std::isfinite(tau[k]) && tau[k] > 0.0 && tau[k] < 1.0, "every tau must lie strictly between 0 and 1");
+    ADMM_REQUIRE(ntau == 1 || out.trace.cap == 0, "the decision trace is recorded for a single tau");
+    run_lad_grid(x, y, n, p, mem, intercept, ntau, opts,
+                 [&](DeviceData<double>& d, bool icpt, QuantResult& res, hipStream_t st) { solve_quantreg(d, icpt, *opts, tau, ntau, res, st); }, out);
+}
+
+// admm_hip_huber: the same call with the Huber form of the prox, one fit per (delta[k], tau[k]); tau = NULL: the symmetric Huber loss.
+void huber(const double* x, const double* y, int n, int p, int mem, int intercept, const double* delta, const double* tau, int nfit, const admm_opts* opts,
+           const DenseOut& out) {
+    ADMM_REQUIRE(delta != nullptr, "delta must not be NULL");
+    ADMM_REQUIRE(nfit >= 1 && nfit <= 4096, "the number of fits must be within [1, 4096]");
+    for (int k = 0; k < nfit; ++k) ADMM_REQUIRE(!std::isnan(delta[k]) && delta[k] > 0.0, "every delta must be positive (+inf: expectile regression)");
+    for (int k = 0; tau != nullptr && k < nfit; ++k)
+        ADMM_REQUIRE(std::isfinite(tau[k]) && tau[k] > 0.0 && tau[k] < 1.0, "every tau must lie strictly between 0 and 1");
+    ADMM_REQUIRE(nfit == 1 || out.trace.cap == 0, "the decision trace is recorded for a single fit");
+    std::vector<double> t(nfit, 0.5);
+    if (tau != nullptr) t.assign(tau, tau + nfit);
+    run_lad_grid(x, y, n, p, mem, intercept, nfit, opts,
+                 [&](DeviceData<double>& d, bool icpt, QuantResult& res, hipStream_t st) { solve_huber(d, icpt, *opts, delta, t.data(), nfit, res, st); }, out);
 }
 
 void bp(const double* x, const double* y, int n, int p, int mem, const admm_opts* opts, const DenseOut& out) {

@@ -66,9 +66,36 @@ struct DenseParams {
 
 constexpr int kDenseThreads = 256;
 constexpr int kQuantAutoSlots = 1;         // what QUANT_SLOTS=0 picks on the one-pass branch (decided by scripts/bench_quantreg.py)
+constexpr int kHuberAutoSlots = 4;         // the same for admm_hip_huber: as many as the layout admits (measured: scripts/bench_huber.py, profiles/huber_loss.md)
 
 __device__ __forceinline__ double soft2(double v, double hi, double lo) {
     return v > hi ? v - hi : (v < -lo ? v + lo : 0.0);
+}
+// The prox of g(z) = sum w(z_i) H_delta(z_i) / rho, w = c_hi above zero and c_lo below, H_delta the Huber function (r^2 / 2 up to
+// |r| = delta, linear beyond), with hi = c_hi / rho, lo = c_lo / rho:
+//     v >  delta (1 + hi): v - delta hi     v < -delta (1 + lo): v + delta lo     between: v / (1 + hi) for v >= 0, v / (1 + lo) below
+// (tests/huber_oracle.py restates these four lines).  Formed here on |v| with the side's constant chosen first: one division, and
+// bit for bit the same, since v beyond a knee has that knee's sign (delta > 0) and negation commutes with every rounding.
+// delta = +inf: the knee is +inf and only the central branch is taken.  Every operation is rounded on its own.  The side's constant
+// is made opaque so that the derived constants (1 + pen, delta (1 + pen), delta pen: two of each) are formed per element and not
+// held in registers across the rows loop -- there they cost the slotted kernels a slot.
+__device__ __forceinline__ double huber2(double v, double hi, double lo, double delta) {
+#pragma clang fp contract(off)
+    double pen = v >= 0.0 ? hi : lo;
+    asm volatile("" : "+v"(pen));
+    const double a = fabs(v), onep = 1.0 + pen;
+    const double z = a > delta * onep ? a - delta * pen : a / onep;
+    return copysign(z, v);
+}
+// The z-update's prox, chosen at compile time: the kernels below take PROX as a template parameter and the knee (admm_hip_huber: delta
+// in the units of the standardised response, +inf = expectile regression) as their LAST argument, behind everything the soft-threshold
+// instantiations (LAD, BP, quantile regression) read: those neither hold nor load it and keep their registers and instruction counts
+// (profiles/huber_loss.md).
+constexpr int kProxSoft = 0, kProxHuber = 1;
+template <int PROX>
+__device__ __forceinline__ double prox2(double v, double hi, double lo, double delta) {
+    if (PROX == kProxHuber) return huber2(v, hi, lo, delta);
+    return soft2(v, hi, lo);
 }
 
 // The six squared norms of the previous iteration: the tail's (rows launch's) partials summed in workgroup order.  pstage: nwg_tail * 8 doubles.
@@ -389,15 +416,15 @@ struct LadRowIn { double ajy, ajz, zc; };
 // row i with x_i = row_i . s known: z_i, y_i as the tail kernel forms them (same expressions, no contraction), thread 0 stores them and
 // adds up the six norms, every thread adds row_i z_i, row_i y_i to its columns of X'z, X'y.  LANE_NORMS (the slotted kernel, to hold
 // one accumulator per slot instead of six): thread k < 6 adds up norm k in nacc[0] -- the same squares added in the same order.
-template <int NPT, bool LANE_NORMS>
-__device__ __forceinline__ void lad_row_step(int i, int tid, double x, double dv, const LadRowIn& in, double rho, double pen_hi, double pen_lo,
+template <int NPT, bool LANE_NORMS, int PROX>
+__device__ __forceinline__ void lad_row_step(int i, int tid, double x, double dv, const LadRowIn& in, double rho, double pen_hi, double pen_lo, double delta,
                                              double* __restrict__ xo, double* __restrict__ zn_, double* __restrict__ yn_,
                                              double* state, long long state_cap, int total, int dim,
                                              double* nacc, const double2 (&rv)[NPT], double2 (&az)[NPT], double2 (&ay)[NPT]) {
     double zn, yn;
     {
 #pragma clang fp contract(off)
-        zn = soft2(x - dv + in.ajy / rho, pen_hi, pen_lo);       // dense_tail_kernel, prob 0 (ADMMLAD.h:94-107)
+        zn = prox2<PROX>(x - dv + in.ajy / rho, pen_hi, pen_lo, delta);      // dense_tail_kernel, prob 0 (ADMMLAD.h:94-107)
         const double rr = x - dv - zn;
         yn = in.ajy + rho * rr;
         if (LANE_NORMS && tid < 6) {
@@ -443,10 +470,10 @@ __device__ __forceinline__ void lad_store_partials(double* __restrict__ cpart, l
     }
 }
 
-template <int NPT>
+template <int NPT, int PROX>
 __global__ void __launch_bounds__(kLadThreads)
 lad_rows_kernel(DenseParams q, int par, const double* __restrict__ Xt, long long ld, const double* __restrict__ spart, int snseg, long long sstride,
-                double* __restrict__ cpart, int rows_per_wg) {
+                double* __restrict__ cpart, int rows_per_wg, double knee) {
     constexpr int R = NPT <= 4 ? kLadRows : 2, NWV = kLadThreads / 64;      // (beyond 4096 columns two rows at a time: the registers hold two groups of rows)
     __shared__ double wsum[2][NWV][R];
     const DenseCtl c = load_ctl_vector(q.ctl + (par ^ 1));           // written by this iteration's head
@@ -455,6 +482,7 @@ lad_rows_kernel(DenseParams q, int par, const double* __restrict__ Xt, long long
     const double* zc_ = cur ? q.z1 : q.z0;
     double* zn_ = cur ? q.z0 : q.z1; double* yn_ = cur ? q.y0 : q.y1;
     const double rho = c.rho, pen_hi = q.c_hi / rho, pen_lo = q.c_lo / rho;
+    const double delta = PROX == kProxHuber ? knee : 0.0;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int row_lo = blockIdx.x * rows_per_wg, row_hi = min(q.dim, row_lo + rows_per_wg);
     double2 sv[NPT], az[NPT], ay[NPT];
@@ -481,7 +509,7 @@ lad_rows_kernel(DenseParams q, int par, const double* __restrict__ Xt, long long
             double x = wsum[buf][0][r];
 #pragma unroll
             for (int w = 1; w < NWV; ++w) x += wsum[buf][w][r];
-            lad_row_step<NPT, false>(i, tid, x, dv[r], in[r], rho, pen_hi, pen_lo, q.x, zn_, yn_, q.state, q.state_cap, c.total, q.dim, nacc, rv[r], az, ay);
+            lad_row_step<NPT, false, PROX>(i, tid, x, dv[r], in[r], rho, pen_hi, pen_lo, delta, q.x, zn_, yn_, q.state, q.state_cap, c.total, q.dim, nacc, rv[r], az, ay);
         }
         buf ^= 1;                                                    // (the next group writes the other half of wsum: one barrier per group)
     };
@@ -503,18 +531,18 @@ lad_rows_kernel(DenseParams q, int par, const double* __restrict__ Xt, long long
 // s * slot_stride doubles (control blocks: q0.ctl + 2 s).  A slot whose control block says done (idle: its last quantile has finished
 // and none is left) does no work and stores nothing.
 template <int NPT> struct QuantRowsR { static constexpr int value = NPT <= 2 ? kLadRows : 2; };
-template <int NPT, int S>
+template <int NPT, int S, int PROX>
 __global__ void __launch_bounds__(kLadThreads)
 quant_rows_kernel(DenseParams q0, long long slot_stride, const double* __restrict__ chi, const double* __restrict__ clo, int par,
                   const double* __restrict__ Xt, long long ld, const double* __restrict__ spart0, int snseg, long long sstride,
-                  double* __restrict__ cpart0, int rows_per_wg) {
+                  double* __restrict__ cpart0, int rows_per_wg, const double* __restrict__ dlt) {
     constexpr int R = QuantRowsR<NPT>::value, NWV = kLadThreads / 64;
     constexpr int NU = R * (1 + 3 * S);                   // the vectors' entries a row group needs: d | per slot adj_y, adj_z, z
     __shared__ double wsum[2][S][NWV][R];
     __shared__ double uni[2][NU];
     bool act[S];
     int cur[S];
-    double rho[S], pen_hi[S], pen_lo[S];
+    double rho[S], pen_hi[S], pen_lo[S], delta[S];         // (wave-uniform: the control block and the grid arrays are read as such)
     bool any = false;
 #pragma unroll
     for (int s = 0; s < S; ++s) {
@@ -524,6 +552,7 @@ quant_rows_kernel(DenseParams q0, long long slot_stride, const double* __restric
         rho[s] = c.rho;
         const int k = act[s] ? c.pad : 0;                                    // the slot's place in the grid of quantiles
         pen_hi[s] = chi[k] / rho[s]; pen_lo[s] = clo[k] / rho[s];
+        delta[s] = PROX == kProxHuber ? dlt[k] : 0.0;                        // the fit's knee travels with its c_hi / c_lo: by the index the head's refill hands over
     }
     if (!any) return;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -575,7 +604,7 @@ quant_rows_kernel(DenseParams q0, long long slot_stride, const double* __restric
                 for (int w = 1; w < NWV; ++w) x += wsum[buf][s][w][r];
                 LadRowIn in;
                 in.ajy = uni[buf][(1 + 3 * s) * R + r]; in.ajz = uni[buf][(2 + 3 * s) * R + r]; in.zc = uni[buf][(3 + 3 * s) * R + r];
-                lad_row_step<NPT, true>(i, tid, x, uni[buf][r], in, rho[s], pen_hi[s], pen_lo[s], q0.x + so, zn_, yn_, nullptr, 0, 0, q0.dim, nacc[s], rv[r], az[s], ay[s]);
+                lad_row_step<NPT, true, PROX>(i, tid, x, uni[buf][r], in, rho[s], pen_hi[s], pen_lo[s], delta[s], q0.x + so, zn_, yn_, nullptr, 0, 0, q0.dim, nacc[s], rv[r], az[s], ay[s]);
             }
         }
         buf ^= 1;
@@ -605,8 +634,9 @@ bp_gather_kernel(DenseParams q, int par, GatherArgs<double> a) {
     gather_body<double>(a, (int)blockIdx.x, (int)blockIdx.y);
 }
 
+template <int PROX>
 __global__ void __launch_bounds__(kDenseThreads)
-dense_tail_kernel(DenseParams q, int par) {
+dense_tail_kernel(DenseParams q, int par, double knee) {
     __shared__ double scratch[6 * (kDenseThreads / 64)];
     const DenseCtl c = load_ctl_vector(q.ctl + (par ^ 1));           // written by this iteration's head
     if (c.done) return;
@@ -614,6 +644,7 @@ dense_tail_kernel(DenseParams q, int par) {
     const double* zc_ = cur ? q.z1 : q.z0;
     double* zn_ = cur ? q.z0 : q.z1; double* yn_ = cur ? q.y0 : q.y1;
     const double rho = c.rho, pen_hi = q.c_hi / rho, pen_lo = q.c_lo / rho;
+    const double delta = PROX == kProxHuber ? knee : 0.0;
     double acc[6] = {0, 0, 0, 0, 0, 0};
     for (int i = blockIdx.x * kDenseThreads + threadIdx.x; i < q.dim; i += gridDim.x * kDenseThreads) {
 #pragma clang fp contract(off)
@@ -624,7 +655,7 @@ dense_tail_kernel(DenseParams q, int par) {
         if (q.prob == 0) {                        // LAD: x = P_X(vec); z = prox(x - y + adj_y/rho; c_hi/rho, c_lo/rho); r = x - y - z
             x = g;
             const double d = q.data_vec[i];
-            zn = soft2(x - d + adjy / rho, pen_hi, pen_lo);
+            zn = prox2<PROX>(x - d + adjy / rho, pen_hi, pen_lo, delta);
             r = x - d - zn;
         } else {                                  // BP: x = vec + A'(AA')^-1 b - B'(B vec); z = soft(x + adj_y/rho, 1/rho); r = x - z
             x = q.vec[i] + q.data_vec[i] - g;
@@ -684,6 +715,8 @@ struct DenseLoop {
     DevBuf<int> done;
     DenseParams q{};
     int nwg_head = 0;
+    int prox = kProxSoft;                      // the tail's prox (prob 0; BP keeps the soft-threshold)
+    double delta = 0.0;                        // its knee (kProxHuber)
     DevBuf<double> trace, state;
 
     void init(int dim, int prob, const admm_opts& o, const double* data_vec, double extra_norm, hipStream_t st, long long trace_cap = 0, long long state_cap = 0,
@@ -714,7 +747,8 @@ struct DenseLoop {
         hipLaunchKernelGGL(dense_head_kernel, dim3(nwg_head), dim3(kDenseThreads), (size_t)q.nwg_tail * 8 * sizeof(double), st, q, (int)(g & 1));
     }
     void tail(long long g, hipStream_t st) {
-        hipLaunchKernelGGL(dense_tail_kernel, dim3(q.nwg_tail), dim3(kDenseThreads), 0, st, q, (int)(g & 1));
+        if (prox == kProxHuber) hipLaunchKernelGGL(dense_tail_kernel<kProxHuber>, dim3(q.nwg_tail), dim3(kDenseThreads), 0, st, q, (int)(g & 1), delta);
+        else hipLaunchKernelGGL(dense_tail_kernel<kProxSoft>, dim3(q.nwg_tail), dim3(kDenseThreads), 0, st, q, (int)(g & 1), 0.0);
     }
     DenseCtl final_ctl(hipStream_t st) {
         DenseCtl h[2];
@@ -750,6 +784,15 @@ namespace {
 // columns a thread of the rows kernels holds per row and, by that, how many slots the registers of quant_rows_kernel hold
 inline int lad_npt(long long ldxt) { return (int)((ldxt / 2 + kLadThreads - 1) / kLadThreads); }
 inline int quant_max_slots(int npt) { return npt <= 3 ? 4 : (npt == 4 ? 3 : (npt == 5 ? 2 : 1)); }      // (six double2 per row: two slots would spill)
+inline int huber_max_slots(int npt) { return npt <= 3 ? 4 : (npt <= 5 ? 2 : 1); }      // the Huber instantiations without scratch: (4, 3) spills 16 bytes and fell away
+
+// The separable loss of one fit, as the loop sees it: which prox, its weights above / below zero, and (Huber) the knee in the units
+// of the standardised response.  LAD: the default.
+struct LadProx {
+    int kind = kProxSoft;
+    double c_hi = 1.0, c_lo = 1.0, delta = 0.0;
+};
+inline int prox_max_slots(int kind, int npt) { return kind == kProxHuber ? huber_max_slots(npt) : quant_max_slots(npt); }
 
 // Everything of a LAD-type fit that does not depend on the prox constants, formed ONCE (setup), and the loop from a cold start
 // (loop: one quantile; loop_slots: a grid, several quantiles per pass over X).  admm_hip_lad is setup + one loop with c_hi = c_lo = 1.
@@ -848,12 +891,16 @@ struct LadProblem {
         ADMM_HIP_CHECK(hipStreamSynchronize(st));
     }
 
-    // One loop from a cold start with the prox constants c_hi, c_lo; coef: the p coefficients of the standardised problem.  Returns niter.
-    int loop(double c_hi, double c_lo, DenseResult& res, double* coef) {
+    // One loop from a cold start with the prox px; coef: the p coefficients of the standardised problem.  Returns niter.
+    int loop(const LadProx& px, DenseResult& res, double* coef) {
         admm_stats& S = res.stats;
         DenseLoop L;
         L.init(n, 0, opts, d.Y.get(), ynorm, st, res.trace_cap, res.state_cap, onepass ? lad_nwg : 0);
-        L.q.c_hi = c_hi; L.q.c_lo = c_lo;
+        L.q.c_hi = px.c_hi; L.q.c_lo = px.c_lo; L.delta = px.delta; L.prox = px.kind;
+        if (px.kind == kProxHuber && res.state_cap > 0) {       // iterate dump: record 0 also carries the knee as the loop holds it (delta / scaleY), first entry of its z slot
+            ADMM_HIP_CHECK(hipMemcpyAsync(L.state.get() + n, &px.delta, sizeof(double), hipMemcpyHostToDevice, st));
+            ADMM_HIP_CHECK(hipStreamSynchronize(st));
+        }
         if (hat) { L.q.gout = gH.part.get(); L.q.gout_nseg = gH.pl.nseg; L.q.gout_stride = gH.stride; }
         else if (!onepass) { L.q.gout = g3.part.get(); L.q.gout_nseg = g3.pl.nseg; L.q.gout_stride = g3.stride; }
         DevBuf<double> Xz0, Xz1, Xy0, Xy1, uvec, cpart;
@@ -865,14 +912,21 @@ struct LadProblem {
         }
         auto launch_rows = [&](long long g) {
             const int par = (int)(g & 1);
-#define ADMM_LAD_ROWS(N) hipLaunchKernelGGL((lad_rows_kernel<N>), dim3(lad_nwg), dim3(kLadThreads), 0, st, L.q, par, Xt.get(), ldxt, g2.part.get(), g2.pl.nseg, g2.stride, cpart.get(), lad_rows)
-            switch (lad_npt(ldxt)) {
-                case 1: ADMM_LAD_ROWS(1); break;
-                case 2: ADMM_LAD_ROWS(2); break;
-                case 3: ADMM_LAD_ROWS(3); break;
-                case 4: ADMM_LAD_ROWS(4); break;
-                case 5: ADMM_LAD_ROWS(5); break;
-                default: ADMM_LAD_ROWS(6); break;
+#define ADMM_LAD_ROWS(N, PX) hipLaunchKernelGGL((lad_rows_kernel<N, PX>), dim3(lad_nwg), dim3(kLadThreads), 0, st, L.q, par, Xt.get(), ldxt, g2.part.get(), g2.pl.nseg, g2.stride, cpart.get(), lad_rows, px.delta)
+            switch (lad_npt(ldxt) * 2 + (px.kind == kProxHuber ? 1 : 0)) {
+                case 2: ADMM_LAD_ROWS(1, kProxSoft); break;
+                case 3: ADMM_LAD_ROWS(1, kProxHuber); break;
+                case 4: ADMM_LAD_ROWS(2, kProxSoft); break;
+                case 5: ADMM_LAD_ROWS(2, kProxHuber); break;
+                case 6: ADMM_LAD_ROWS(3, kProxSoft); break;
+                case 7: ADMM_LAD_ROWS(3, kProxHuber); break;
+                case 8: ADMM_LAD_ROWS(4, kProxSoft); break;
+                case 9: ADMM_LAD_ROWS(4, kProxHuber); break;
+                case 10: ADMM_LAD_ROWS(5, kProxSoft); break;
+                case 11: ADMM_LAD_ROWS(5, kProxHuber); break;
+                default:
+                    if (px.kind == kProxHuber) ADMM_LAD_ROWS(6, kProxHuber); else ADMM_LAD_ROWS(6, kProxSoft);
+                    break;
             }
 #undef ADMM_LAD_ROWS
         };
@@ -906,15 +960,18 @@ struct LadProblem {
 
     // A grid of quantiles, S >= 2 of them per pass over X (one-pass branch only).  Per iteration: quant_head_kernel for all slots, ONE
     // batched launch of the slots' (X'X)^-1 u products (g2's plan: the partials of the single run), quant_rows_kernel.  The slots refill
-    // on the device; the host polls the one `done` word.  coef: [ntau][p].
-    void loop_slots(int S_, const std::vector<double>& c_hi, const std::vector<double>& c_lo, admm_stats& S, int* niter, double* coef) {
-        const int ntau = (int)c_hi.size(), nslots = S_;
+    // on the device; the host polls the one `done` word.  fits: the grid, all of one prox kind.  coef: [ntau][p].
+    void loop_slots(int S_, const std::vector<LadProx>& fits, admm_stats& S, int* niter, double* coef) {
+        const int ntau = (int)fits.size(), nslots = S_;
+        const int kind = fits[0].kind;
+        std::vector<double> c_hi(ntau), c_lo(ntau), dlt(ntau);
+        for (int k = 0; k < ntau; ++k) { c_hi[k] = fits[k].c_hi; c_lo[k] = fits[k].c_lo; dlt[k] = fits[k].delta; }
         const long long ldn = round_up(n, 32);
         const size_t gpart_sz = (size_t)g2.pl.nseg * g2.stride;
         // one slot: 8 n-vectors | X'z (2), X'y (2), u | norm partials | the rows launch's partials | the product's partial rows
         const size_t o_p = 8 * (size_t)ldn, o_P = o_p + 5 * (size_t)ldp, o_c = o_P + (size_t)lad_nwg * 8, o_g = o_c + (size_t)lad_nwg * 2 * ldp;
         const size_t stride = round_up_sz(o_g + gpart_sz, 32);
-        DevBuf<double> pool(stride * nslots), fin((size_t)ntau * ldn), chi_d(ntau), clo_d(ntau), rho_fin(ntau);
+        DevBuf<double> pool(stride * nslots), fin((size_t)ntau * ldn), chi_d(ntau), clo_d(ntau), dlt_d(ntau), rho_fin(ntau);
         DevBuf<DenseCtl> ctl(2 * (size_t)nslots);
         DevBuf<int> ints(3 + nslots + ntau);                     // done | next[2] | idle[nslots] | niter[ntau]
         DevBuf<GemvTArgs<double>> batch(nslots);
@@ -951,6 +1008,7 @@ struct LadProblem {
         ADMM_HIP_CHECK(hipMemcpyAsync(ctl.get(), hc.data(), hc.size() * sizeof(DenseCtl), hipMemcpyHostToDevice, st));
         ADMM_HIP_CHECK(hipMemcpyAsync(chi_d.get(), c_hi.data(), ntau * sizeof(double), hipMemcpyHostToDevice, st));
         ADMM_HIP_CHECK(hipMemcpyAsync(clo_d.get(), c_lo.data(), ntau * sizeof(double), hipMemcpyHostToDevice, st));
+        ADMM_HIP_CHECK(hipMemcpyAsync(dlt_d.get(), dlt.data(), ntau * sizeof(double), hipMemcpyHostToDevice, st));
         ADMM_HIP_CHECK(hipMemcpyAsync(batch.get(), hb.data(), hb.size() * sizeof(GemvTArgs<double>), hipMemcpyHostToDevice, st));
         ADMM_HIP_CHECK(hipStreamSynchronize(st));                // (the host vectors above are read by the copies)
 
@@ -958,22 +1016,33 @@ struct LadProblem {
         const double* spart0 = b + o_g;
         double* cpart0 = b + o_c;
         auto launch_rows = [&](int par) {
-#define ADMM_QUANT_ROWS(N, SS) hipLaunchKernelGGL((quant_rows_kernel<N, SS>), dim3(lad_nwg), dim3(kLadThreads), 0, st, q, (long long)stride, chi_d.get(), clo_d.get(), par, \
-                                                  Xt.get(), ldxt, spart0, g2.pl.nseg, g2.stride, cpart0, lad_rows)
-            switch (lad_npt(ldxt) * 10 + nslots) {
-                case 12: ADMM_QUANT_ROWS(1, 2); break;
-                case 13: ADMM_QUANT_ROWS(1, 3); break;
-                case 14: ADMM_QUANT_ROWS(1, 4); break;
-                case 22: ADMM_QUANT_ROWS(2, 2); break;
-                case 23: ADMM_QUANT_ROWS(2, 3); break;
-                case 24: ADMM_QUANT_ROWS(2, 4); break;
-                case 32: ADMM_QUANT_ROWS(3, 2); break;
-                case 33: ADMM_QUANT_ROWS(3, 3); break;
-                case 34: ADMM_QUANT_ROWS(3, 4); break;
-                case 42: ADMM_QUANT_ROWS(4, 2); break;
-                case 43: ADMM_QUANT_ROWS(4, 3); break;
-                case 52: ADMM_QUANT_ROWS(5, 2); break;
-                default: throw Error(ADMM_ERR_INTERNAL, "quantile slots: no rows kernel for this layout");
+#define ADMM_QUANT_ROWS(N, SS, PX) hipLaunchKernelGGL((quant_rows_kernel<N, SS, PX>), dim3(lad_nwg), dim3(kLadThreads), 0, st, q, (long long)stride, chi_d.get(), clo_d.get(), par, \
+                                                      Xt.get(), ldxt, spart0, g2.pl.nseg, g2.stride, cpart0, lad_rows, (const double*)dlt_d.get())
+            switch ((kind == kProxHuber ? 100 : 0) + lad_npt(ldxt) * 10 + nslots) {
+                case 12: ADMM_QUANT_ROWS(1, 2, kProxSoft); break;
+                case 13: ADMM_QUANT_ROWS(1, 3, kProxSoft); break;
+                case 14: ADMM_QUANT_ROWS(1, 4, kProxSoft); break;
+                case 22: ADMM_QUANT_ROWS(2, 2, kProxSoft); break;
+                case 23: ADMM_QUANT_ROWS(2, 3, kProxSoft); break;
+                case 24: ADMM_QUANT_ROWS(2, 4, kProxSoft); break;
+                case 32: ADMM_QUANT_ROWS(3, 2, kProxSoft); break;
+                case 33: ADMM_QUANT_ROWS(3, 3, kProxSoft); break;
+                case 34: ADMM_QUANT_ROWS(3, 4, kProxSoft); break;
+                case 42: ADMM_QUANT_ROWS(4, 2, kProxSoft); break;
+                case 43: ADMM_QUANT_ROWS(4, 3, kProxSoft); break;
+                case 52: ADMM_QUANT_ROWS(5, 2, kProxSoft); break;
+                case 112: ADMM_QUANT_ROWS(1, 2, kProxHuber); break;
+                case 113: ADMM_QUANT_ROWS(1, 3, kProxHuber); break;
+                case 114: ADMM_QUANT_ROWS(1, 4, kProxHuber); break;
+                case 122: ADMM_QUANT_ROWS(2, 2, kProxHuber); break;
+                case 123: ADMM_QUANT_ROWS(2, 3, kProxHuber); break;
+                case 124: ADMM_QUANT_ROWS(2, 4, kProxHuber); break;
+                case 132: ADMM_QUANT_ROWS(3, 2, kProxHuber); break;
+                case 133: ADMM_QUANT_ROWS(3, 3, kProxHuber); break;
+                case 134: ADMM_QUANT_ROWS(3, 4, kProxHuber); break;
+                case 142: ADMM_QUANT_ROWS(4, 2, kProxHuber); break;
+                case 152: ADMM_QUANT_ROWS(5, 2, kProxHuber); break;
+                default: throw Error(ADMM_ERR_INTERNAL, "slotted grid: no rows kernel for this layout");
             }
 #undef ADMM_QUANT_ROWS
         };
@@ -1005,7 +1074,7 @@ void solve_lad(const DeviceData<double>& d, const admm_opts& opts, DenseResult& 
     LadProblem P(d, opts, st);
     P.setup(res.stats);
     std::vector<double> coef(p), out(p);
-    res.niter = P.loop(1.0, 1.0, res, coef.data());
+    res.niter = P.loop(LadProx{}, res, coef.data());
     double b0 = 0;
     recover_coef<double>(d, coef.data(), &b0, out.data());      // LAD.cpp:41
     res.beta.assign(p + 1, 0.0);
@@ -1020,7 +1089,10 @@ __global__ void __launch_bounds__(256) ones_column_kernel(double* col, int n, lo
 }
 
 // d: the standardised data (DataStd flag 3 with the intercept, 1 without); with the intercept the loop fits one more column of ones.
-void solve_quantreg(DeviceData<double>& d, bool intercept, const admm_opts& opts, const double* tau, int ntau, QuantResult& res, hipStream_t st) {
+// fits: the grid in the units of the standardised response, all of one prox kind.  What admm_hip_quantreg and admm_hip_huber share:
+// the ones column, the setup, the choice of slots, the loops and the recovery.
+static void solve_lad_grid(DeviceData<double>& d, bool intercept, const admm_opts& opts, const std::vector<LadProx>& fits, QuantResult& res, hipStream_t st) {
+    const int ntau = (int)fits.size();
     const int n = d.n, p0 = d.p;
     if (intercept) {                                             // X | 1
         DevBuf<double> X1((size_t)d.ldx * (p0 + 1));
@@ -1034,24 +1106,22 @@ void solve_quantreg(DeviceData<double>& d, bool intercept, const admm_opts& opts
     DenseResult& dr = res.dense;
     LadProblem P(d, opts, st);
     P.setup(dr.stats);
-    std::vector<double> c_hi(ntau), c_lo(ntau);
-    for (int k = 0; k < ntau; ++k) { c_hi[k] = 2.0 * (1.0 - tau[k]); c_lo[k] = 2.0 * tau[k]; }
 
     // slots: the one-pass branch only; QUANT_SLOTS 0 = automatic, 1 = serial, 2 .. 8 = at most that many, clipped to what the registers
     // of the shape's layout hold and to the number of quantiles.  The get_x vectors of all quantiles (n x ntau) must fit beside the problem.
     int slots = 1;
     if (P.onepass && dr.trace_cap == 0 && ntau >= 2) {
         const long long want = opt_int(Opt::QUANT_SLOTS, 0);
-        slots = want == 0 ? kQuantAutoSlots : (int)want;
-        slots = std::min(std::min(slots, quant_max_slots(lad_npt(P.ldxt))), ntau);
+        slots = want == 0 ? (fits[0].kind == kProxHuber ? kHuberAutoSlots : kQuantAutoSlots) : (int)want;
+        slots = std::min(std::min(slots, prox_max_slots(fits[0].kind, lad_npt(P.ldxt))), ntau);
         if ((size_t)ntau * (size_t)n * sizeof(double) > (size_t(2) << 30)) slots = 1;
     }
     std::vector<double> coef((size_t)ntau * p);
     res.niter.assign(ntau, 0);
     if (slots >= 2) {
-        P.loop_slots(slots, c_hi, c_lo, dr.stats, res.niter.data(), coef.data());
+        P.loop_slots(slots, fits, dr.stats, res.niter.data(), coef.data());
     } else {
-        for (int k = 0; k < ntau; ++k) res.niter[k] = P.loop(c_hi[k], c_lo[k], dr, coef.data() + (size_t)k * p);
+        for (int k = 0; k < ntau; ++k) res.niter[k] = P.loop(fits[k], dr, coef.data() + (size_t)k * p);
     }
     dr.niter = res.niter[0];
     // beta_j = b_j scaleY / scaleX_j;  beta_0 = (meanY - sum beta_j meanX_j) + scaleY b_{p+1}
@@ -1068,6 +1138,24 @@ void solve_quantreg(DeviceData<double>& d, bool intercept, const admm_opts& opts
         for (int j = 0; j < p0; ++j) col[j + 1] = out[j];
     }
     d.p = p;
+}
+
+void solve_quantreg(DeviceData<double>& d, bool intercept, const admm_opts& opts, const double* tau, int ntau, QuantResult& res, hipStream_t st) {
+    std::vector<LadProx> fits(ntau);
+    for (int k = 0; k < ntau; ++k) { fits[k].c_hi = 2.0 * (1.0 - tau[k]); fits[k].c_lo = 2.0 * tau[k]; }
+    solve_lad_grid(d, intercept, opts, fits, res, st);
+}
+
+// Huber / expectile regression: the same grid with the Huber form of the prox.  delta is the caller's, in the units of y; the loop runs
+// on y / scaleY and H is positively homogeneous in (r, delta), so it uses delta / scaleY (+inf stays +inf).
+void solve_huber(DeviceData<double>& d, bool intercept, const admm_opts& opts, const double* delta, const double* tau, int nfit, QuantResult& res, hipStream_t st) {
+    std::vector<LadProx> fits(nfit);
+    for (int k = 0; k < nfit; ++k) {
+        fits[k].kind = kProxHuber;
+        fits[k].c_hi = 2.0 * (1.0 - tau[k]); fits[k].c_lo = 2.0 * tau[k];
+        fits[k].delta = delta[k] / d.scaleY;
+    }
+    solve_lad_grid(d, intercept, opts, fits, res, st);
 }
 
 // ---------------------------------------------------------------------------------------------- BP

@@ -64,7 +64,7 @@ constexpr double kPositive = std::numeric_limits<double>::min();  // Real(kPosit
     X(COMM_PATIENT_TIMEOUT_S, Real(kPositive, 1e300), "wait bound of setup reductions and replica joins, seconds")                     \
     X(LAD_HAT, Flag(), "LAD: 0 = the general projection also for n <= 2000")                                                            \
     X(LAD_ONEPASS, Flag(), "LAD: 0 = the reference's two products per iteration")                                                      \
-    X(QUANT_SLOTS, Int(0, 8), "admm_hip_quantreg: quantiles per pass over X on the one-pass branch: 0 = automatic, 1 = serial, else at most that many") \
+    X(QUANT_SLOTS, Int(0, 8), "admm_hip_quantreg, admm_hip_huber: fits per pass over X on the one-pass branch: 0 = automatic, 1 = serial, else at most that many") \
     X(MT_RHS, Choice("0|2|4|8|12"), "admm_hip_mtlasso: right-hand sides per pass over the cached inverse (0: automatic)")               \
     X(BP_ONEPASS, Flag(), "basis pursuit: 0 = the reference's two products per iteration")                                             \
     X(SBP_GRAM, Flag(), "admm_hip_parbp: 0 = the direct launches on every active-set iteration")                                       \

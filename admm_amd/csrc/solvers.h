@@ -136,6 +136,10 @@ struct QuantResult {
     std::vector<int> niter;
 };
 void solve_quantreg(DeviceData<double>& d, bool intercept, const admm_opts& opts, const double* tau, int ntau, QuantResult& res, hipStream_t st);
+// admm_hip_huber (fadmm_dense.hip): the same scaffolding with the Huber form of the prox, one fit per (delta[k], tau[k]); delta in the
+// units of y (the loop uses delta / scaleY), +inf = expectile regression.
+void solve_huber(DeviceData<double>& d, bool intercept, const admm_opts& opts, const double* delta, const double* tau, int nfit, QuantResult& res,
+                 hipStream_t st);
 // admm_dantzig (dantzig.hip): the Dantzig selector path in double.  res.beta: (p + 1) x nlambda column-major, row 0 = intercept.
 struct DantzigResult {
     std::vector<double> lambda, beta;

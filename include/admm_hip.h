@@ -266,6 +266,22 @@ ADMM_HIP_API int admm_hip_quantreg_state(const double* x, const double* y, int n
                             double* beta_out, int* niter_out, admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out,
                             double* state_out, long long state_cap, long long* nstate_out);
 
+/* Huber and expectile regression (no counterpart in the reference): minimise sum_i w_tau(r_i) H_delta(r_i), r_i = y_i - b0 - x_i'b, with
+ * H_delta(r) = r^2 / 2 for |r| <= delta and delta |r| - delta^2 / 2 beyond, w_tau(r) = 2 tau for r >= 0 and 2 (1 - tau) below, for
+ * every pair (delta[k], tau[k]) -- admm_hip_quantreg's loop, setup, fitted intercept (n > p + intercept) and slots (option QUANT_SLOTS)
+ * with the prox of the weighted Huber function.  tau = 0.5: the Huber loss; delta = +inf: expectile regression (asymmetric least
+ * squares); both: least squares.  delta is in the units of y (no scale is estimated), > 0, +inf allowed; tau strictly inside (0, 1),
+ * tau = NULL: 0.5 for every fit.  1 <= nfit <= 4096, any order, repeats allowed; every fit runs from a cold start.
+ * beta_out[(p + 1) * nfit]: column k = fit k, intercept first (0 when intercept = 0); niter_out[nfit]; stats->xupdate_variant as
+ * admm_hip_quantreg's (0 / 1 serial, 8 + S with S fits per pass over X).
+ * _state: one fit with the decision trace and (state_cap > 0) the iterate dump, as admm_hip_quantreg_state; record 0 of the dump
+ * (the standardised y in its x slot) also carries the knee the loop ran with, delta / scaleY, as the first entry of its z slot. */
+ADMM_HIP_API int admm_hip_huber(const double* x, const double* y, int n, int p, int mem, int intercept, const double* delta, const double* tau, int nfit,
+                   const admm_opts* opts, double* beta_out, int* niter_out, admm_stats* stats);
+ADMM_HIP_API int admm_hip_huber_state(const double* x, const double* y, int n, int p, int mem, int intercept, double delta, double tau, const admm_opts* opts,
+                         double* beta_out, int* niter_out, admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out,
+                         double* state_out, long long state_cap, long long* nstate_out);
+
 /* Prepared-problem variant of the Lasso family (the "persistent context" anticipated for a
  * re-fitting caller; the R shim does not need it).  create = everything the reference does
  * before its lambda loop (copy/convert, DataStd, X'y, Gram, Spectra, factorisation:

@@ -230,6 +230,23 @@ BEGIN_RCPP
 END_RCPP
 }
 
+// Huber / expectile regression (not in the reference): .Call("admm_huber", x, y, delta, tau, intercept, opts) with delta
+// and tau of one common length (delta in the units of y, Inf = expectile regression) -> beta: (p + 1) x length(delta), intercept first.
+RcppExport SEXP admm_huber(SEXP x_, SEXP y_, SEXP delta_, SEXP tau_, SEXP intercept_, SEXP opts_) {
+BEGIN_RCPP
+    NumericMatrix x(x_);
+    NumericVector y(y_), delta(delta_), tau(tau_);
+    admm_opts o = unpack_opts(opts_);
+    const int nfit = delta.size();
+    if (tau.size() != nfit) Rcpp::stop("delta and tau should have the same length");
+    NumericMatrix beta(x.ncol() + 1, nfit);
+    IntegerVector niter(nfit);
+    check(admm_hip_huber(x.begin(), y.begin(), x.nrow(), x.ncol(), ADMM_MEM_HOST, as<bool>(intercept_), delta.begin(), tau.begin(), nfit, &o,
+                         beta.begin(), niter.begin(), nullptr));
+    return List::create(Named("delta") = delta, Named("tau") = tau, Named("beta") = beta, Named("niter") = niter);
+END_RCPP
+}
+
 // The symbol R/50_admm_dantzig.R:38 asks for and the reference never builds (src/TODO/Dantzig.cpp:32-99): doubles throughout.
 RcppExport SEXP admm_dantzig(SEXP x_, SEXP y_, SEXP lambda_, SEXP nlambda_, SEXP lmin_ratio_, SEXP standardize_, SEXP intercept_, SEXP opts_) {
 BEGIN_RCPP
