@@ -79,7 +79,8 @@ EXPORTS = ["admm_hip_lasso", "admm_hip_enet", "admm_hip_parlasso", "admm_hip_lad
            "admm_hip_sgl", "admm_hip_sgl_plan_create", "admm_hip_host_sgl_lambda0",
            "admm_hip_boxenet", "admm_hip_boxenet_plan_create", "admm_hip_host_box_lambda0",
            "admm_hip_test_gemm_nt", "admm_hip_test_cholesky_linvt", "admm_hip_test_spd_inverse_shift",
-           "admm_hip_test_symv_plan", "admm_hip_test_symv_ex", "admm_hip_test_symv_multi_ex", "admm_hip_test_symv_f64acc"]
+           "admm_hip_test_symv_plan", "admm_hip_test_symv_ex", "admm_hip_test_symv_multi_ex", "admm_hip_test_symv_f64acc",
+           "admm_hip_test_symv_one"]
 
 GROUP_MAX = 1024          # ADMM_HIP_GROUP_MAX
 MT_MAX = 16               # ADMM_HIP_MT_MAX
@@ -255,6 +256,9 @@ def load():
     lib.admm_hip_test_symv_ex.argtypes = [_c_float_p, ctypes.c_int, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                           _c_float_p, _c_float_p, _c_int_p]
     lib.admm_hip_test_symv_ex.restype = ctypes.c_int
+    lib.admm_hip_test_symv_one.argtypes = [_c_float_p, ctypes.c_int, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint,
+                                           _c_float_p, _c_float_p, _c_float_p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong), _c_int_p]
+    lib.admm_hip_test_symv_one.restype = ctypes.c_int
     lib.admm_hip_test_symv_multi_ex.argtypes = [_c_float_p, ctypes.c_int, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                 _c_float_p, _c_int_p]
     lib.admm_hip_test_symv_multi_ex.restype = ctypes.c_int

@@ -625,6 +625,17 @@ int admm_hip_test_symv_ex(const float* A, int p, const float* v0, const float* v
     });
 }
 
+int admm_hip_test_symv_one(const float* A, int p, const float* v0, const float* v1, int gate, int nt, unsigned int fill, float* y,
+                           float* dot_out, float* axp_out, long long plane_capacity, long long* info_out, int* sched_out) {
+    return guarded([&] {
+        ADMM_REQUIRE(A && v0 && v1 && y && info_out && sched_out, "symv_one hook: A, v0, v1, y, info_out and sched_out must not be NULL");
+        ADMM_REQUIRE((dot_out == nullptr) == (axp_out == nullptr), "symv_one hook: dot_out and axp_out are given together or not at all");
+        ADMM_REQUIRE(p >= 1 && p <= kSymvHookMaxP && gate >= 0 && gate <= 3 && (nt == 0 || nt == 1) && plane_capacity >= 0,
+                     "symv_one hook: p in 1 .. 32768, gate in 0 .. 3, nt 0 or 1, plane_capacity >= 0");
+        test_symv_one(A, p, v0, v1, gate, nt, fill, y, dot_out, axp_out, plane_capacity, info_out, sched_out);
+    });
+}
+
 int admm_hip_test_symv_multi_ex(const float* A, int p, const float* V, int nr, int rhs_per_pass, int nt, int finish, float* Yout, int* sched_out) {
     return guarded([&] {
         ADMM_REQUIRE(A && V && Yout && sched_out, "symv_multi_ex hook: A, V, Yout and sched_out must not be NULL");

@@ -14,17 +14,22 @@
 //        u = fl(fl(X'y - adj_y) + rho adj_z)  with adj = (1+ratio) new - ratio old     ("accelerate")
 //        w = fl(fl(X'y - y_old) + rho z_old)                                          ("restart": adj = old)
 //    are formed by the tail of the previous iteration exactly as ADMMLassoTall.h:70-80 rounds them.
-//    The x-update kernel streams Minv ONCE against the pair (u, w), a = Minv u, b = Minv w, and the
-//    tail picks x = a or x = b.  The scalar decision itself (norm reduction, convergence,
-//    acceleration/restart, lambda schedule) runs as ONE EXTRA WORKGROUP of the x-update launch,
-//    concurrently with the streaming workgroups.  No host round trip, no grid barrier, no atomics:
-//    two launches per ADMM iteration.
-//    The decision therefore comes too late for the launch it rides on -- and once per lambda (`mode == 0` below) and once per path
-//    (`done`) it says that this launch's products will not be read.  It then publishes a VERDICT word (symv_kernels.h: SymvVerdict):
-//    tiles that start after it leave at once, running ones when they next look (between two 8-column chunks).  Nobody waits for
-//    anybody; a tile that does not see the word streams as before.  Measured at C2, same box, five alternating runs each
-//    (profiles/r07_tall_dead_work.md): 89.1-90.7 ms per path before, 85.8-87.8 after; the 100 discarded launches of a path take
-//    19.5 us instead of 33.6, the others 33.2 (the diagonal blocks' dead loads are gone as well: symv_kernels.h).
+//    Two launches per ADMM iteration, no host round trip, no grid barrier, no atomics between them: the x-update streams Minv
+//    ONCE, the tail does everything else.  The scalar decision (norm reduction, convergence, acceleration / restart, lambda
+//    schedule) turns on ctl[par] and the norm partials P[par] alone, both written by EARLIER launches, so it is taken inside the
+//    x-update launch, and (round 8, SYMV_VERDICT=3, the default) by every workgroup of it for itself:
+//      - block 0, ONE EXTRA WORKGROUP beside the streaming ones, evaluates the rule and publishes what follows from it (tall_decide:
+//        eps, a_next / tau_next, the lambda schedule, niter[], the trace, ctl[par ^ 1]) for the tail;
+//      - every tile evaluates the same rule in its prologue (TallGate -> tall_norms_sum + tall_outcome, the functions block 0 calls,
+//        on the same inputs in the same order), in the round trip of its tile descriptor, and knows before its first FMA whether it
+//        multiplies u (accelerate, cold start) or w (restart) -- symv1_lower_kernel, one plane of partials, half the partial
+//        stores, a tail with 16 loads per lane -- or that nobody will read this launch's products (once per converged lambda, and
+//        the last decision of a path): then it leaves at once.  No workgroup reads what another workgroup of its launch writes.
+//    Levels 0 - 2 of SYMV_VERDICT, and the sharded / refined paths, keep the earlier form: a = Minv u and b = Minv w from one stream
+//    against the pair (symv2_lower_kernel), the tail picks x = a or x = b, and the decision, taken BESIDE the stream by block 0 only,
+//    reaches the tiles of a discarded launch as a VERDICT word (symv_kernels.h: SymvVerdict) that late starters and running tiles
+//    (between two 8-column chunks) may or may not see in time (profiles/r07_tall_dead_work.md: 89.1-90.7 ms per C2 path before,
+//    85.8-87.8 with it).  profiles/tall_decide_first.md has the measurements of the default against that form.
 //    (An earlier version used x = Minv u' + tau Minv w' with u' = X'y - y + rho z: equal in exact
 //    arithmetic, but it bypasses the float rounding of the right-hand side, and with it the dead
 //    band that lets the reference's stopping rule fire when rho * ulp(z) exceeds eps_dual -- tiny
@@ -77,7 +82,8 @@ struct TallParams {
     long long ldo; int nrb, p32; SymvSched sched;
     float* x; float* z0; float* z1; float* y0; float* y1; float* adj_z; float* adj_y; float* u; float* w;
     TallCtl* ctl;               // [2]
-    double* P;                  // [2][nwg][8]
+    double* P;                  // [2][nwg][8] norm partials of the tails' workgroups; behind them a compact copy of columns 0 .. 2 (r^2, dz^2, daz^2),
+                                // [2][3][nwg]: the same numbers, laid out so that 256 threads read a column as consecutive doubles (TallGate)
     float* beta;                // [nlam][p] snapshots of z (standardised scale)
     int* niter;                 // [nlam]
     int* done_host;             // pinned host word set when the path has finished (loop_driver.h: PinnedFlag)
@@ -90,7 +96,8 @@ struct TallParams {
     long long refine_ld;        // the correction it sums from the partials; NULL otherwise
     float* state;               // optional [state_cap][5][p] iterates x, z, y, adj_z, adj_y of every iteration (admm_hip_lasso_plan_state_*), or NULL
     long long state_cap;
-    unsigned long long* verdict;     // the x-update's verdict words (symv_kernels.h: SymvVerdict) and, behind them, the count of tiles that left early; or NULL
+    unsigned long long* verdict;     // the x-update's verdict words (symv_kernels.h: SymvVerdict), published by the decision; NULL where no tile reads them
+    unsigned long long* early;       // counts of the tiles that left early in this run (behind the verdict words: kSyEarlySlots counters on lines of their own), or NULL
     unsigned long long run_tag;      // number of this run() of the plan, above the bits of `total` and the discard bit
 };
 
@@ -102,6 +109,10 @@ constexpr int kVerdictShift = 33;                                              /
 constexpr int kVerdictWords = kSyVerdictReplicas * kSyVerdictStride;           // the early-exit counter sits behind the copies, on a line of its own
 
 constexpr int kTailThreads = 256;
+constexpr int kGateCols = 3;              // columns of the norm partials a tile's gate needs: r^2, dz^2, daz^2 (compact copy behind P)
+// P[par] as block 0 reads it (a 64-byte row per workgroup of the tail) and the compact copy of its first kGateCols columns
+__host__ __device__ inline const double* tall_norm_rows(const double* P, int nwg, int par) { return P + (size_t)par * nwg * 8; }
+__host__ __device__ inline size_t tall_norm_compact(int nwg, int par) { return (size_t)2 * nwg * 8 + (size_t)par * kGateCols * nwg; }
 constexpr int kTailLanes = kSySumLanes;   // lanes cooperating on one element's partial sums
 constexpr int kTailElems = kTailThreads / kTailLanes;
 
@@ -120,6 +131,109 @@ __device__ __forceinline__ void tall_store_wt(double* p, double v) {
     __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), (unsigned long long)__double_as_longlong(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// ---- The decision rule, one copy (round 8).  What a decision turns on -- three comparisons on ctl[par] and the sums of the norm partials
+// P[par] -- was written by EARLIER launches, so any 256-thread workgroup of the x-update launch can evaluate it: block 0 (tall_decide
+// below, which goes on to publish ctl[par ^ 1]) and, on the decide-first path (SYMV_VERDICT=3), every tile in its prologue (TallGate),
+// which then knows before its first FMA which vector it multiplies, or that it need not run.  Same functions, same inputs, same order
+// of every addition: the outcome a tile computes equals block 0's by construction, and no workgroup of a launch reads anything another
+// workgroup of that launch writes -- no flag, no spin, no atomic wait, no fence.
+enum { TALL_COLD = 0, TALL_CONVERGED = 1, TALL_ACCELERATE = 2, TALL_RESTART = 3 };
+struct TallOutcome {
+    int code;        // TALL_*
+    int fin;         // the lambda of ctl[par] finishes at this decision (converged, or by maxit)
+    int done;        // ... and it was the last one: the path is finished
+    double rp, rd, c;
+    // what the tiles of the launch that takes this decision do: nobody reads their products after a converged lambda (the tail keeps
+    // the stored x) or at the end of the path; otherwise the tail takes x = b on a restart and x = a else (cold start included)
+    __device__ __forceinline__ bool discard() const { return code == TALL_CONVERGED || done != 0; }
+    __device__ __forceinline__ int pick() const { return code == TALL_RESTART ? 1 : 0; }
+};
+
+// Norm partials of P[par]: thread t sums rows t, t + 256, ... in that order, then block_sum.  Block 0 reads the 64-byte rows of P; the
+// tiles read the compact copy the tails write beside it (tall_publish_norms) -- the same doubles, but a column is consecutive, so a wave's
+// load touches 4 lines instead of 64: 1600 tiles asking for 157 strided lines each at the start of a launch cost the regular launches
+// 2 us (measured: 34.2 against 32.2 us), the compact copy is 59 lines.  The first two rows of a thread (all of them
+// up to p = 16384) are requested without a wait between them, so that a caller can issue other loads behind them (tall_norms_request);
+// tall_norms_sum adds them in the loop's order and continues the loop.  NK: the first NK of the 6 columns (a tile needs r^2, dz^2, daz^2;
+// the columns are summed independently, so NK = 3 returns the bits NK = 6 returns for them).
+// (rs, cs): strides of a workgroup's row and of a column in Pin -- (8, 1) for the rows of P, (1, nwg) for the compact copy.
+template <int NK> struct TallNormReq { double v[2][NK]; };
+template <int NK, bool IN_LAUNCH>
+__device__ __forceinline__ TallNormReq<NK> tall_norms_request(const double* Pin, int nwg, int rs, int cs) {
+    TallNormReq<NK> r;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const int w = threadIdx.x + j * kTailThreads;
+#pragma unroll
+        for (int k = 0; k < NK; ++k) r.v[j][k] = w < nwg ? tall_load_partial(Pin + (size_t)w * rs + (size_t)k * cs, IN_LAUNCH) : 0.0;
+    }
+    return r;
+}
+template <int NK, bool IN_LAUNCH>
+__device__ __forceinline__ void tall_norms_sum(const TallNormReq<NK>& r, const double* Pin, int nwg, int rs, int cs, double (&acc)[NK], double* scratch) {
+#pragma unroll
+    for (int k = 0; k < NK; ++k) acc[k] = 0;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        if ((int)threadIdx.x + j * kTailThreads < nwg) {
+#pragma unroll
+            for (int k = 0; k < NK; ++k) acc[k] += r.v[j][k];
+        }
+    }
+    for (int w = threadIdx.x + 2 * kTailThreads; w < nwg; w += kTailThreads) {
+#pragma unroll
+        for (int k = 0; k < NK; ++k) acc[k] += tall_load_partial(Pin + (size_t)w * rs + (size_t)k * cs, IN_LAUNCH);
+    }
+    block_sum<double, NK>(acc, scratch);
+}
+
+// The comparisons.  Contraction is off and the one fused product is written out (it is the form the compiler chose for this expression
+// before the rule was shared): the two callers must not be left to round it differently.
+__device__ __forceinline__ TallOutcome tall_outcome(const TallCtl& in, double r2, double dz2, double daz2, int maxit, int nlam) {
+#pragma clang fp contract(off)
+    TallOutcome o;
+    o.code = TALL_COLD; o.fin = 0; o.done = 0; o.rp = 0; o.rd = 0; o.c = 0;
+    if (in.first) return o;                            // cold start: adj = 0, x = Minv X'y
+    const double rp = sqrt(r2);                        // resid_primal            FADMMBase.h:208
+    const double rd = in.rho * sqrt(dz2);              // resid_dual              ADMMLassoTall.h:150-153
+    o.rp = rp; o.rd = rd;
+    if (rp < in.eps_primal && rd < in.eps_dual) {      // converged()             FADMMBase.h:213-217
+        o.code = TALL_CONVERGED; o.fin = 1;
+    } else {
+        const double c = fma(in.rho * rp, rp, in.rho * daz2);      // compute_resid_combined  ADMMLassoTall.h:154-161
+        o.c = c;
+        o.code = c < 0.999 * in.adj_c ? TALL_ACCELERATE : TALL_RESTART;      // FADMMBase.h:243-256
+        if (in.iter + 1 >= maxit) o.fin = 1;           // loop ran out: `return i + 1` with i == maxit
+    }
+    if (o.fin && in.lam_idx + 1 >= nlam) o.done = 1;
+    return o;
+}
+
+// The gate of symv1_lower_kernel (symv_kernels.h): the decision of this launch, taken by every tile for itself.
+struct TallGate {
+    const TallCtl* ctl;       // &ctl[par]
+    const double* Pin;        // the compact copy of P[par]: [kGateCols][nwg], the numbers block 0 reads from the rows of P[par]
+    int nwg, maxit, nlam;
+    struct Req { TallCtl in; TallNormReq<kGateCols> n; };
+    __device__ __forceinline__ Req request() const {
+        Req r;
+        r.in = *ctl;
+        r.n = tall_norms_request<kGateCols, false>(Pin, nwg, 1, nwg);
+        return r;
+    }
+    __device__ __forceinline__ int decide(const Req& r, double* lds) const {
+        if (r.in.done) return kSyGateLeave;            // (the kernel has returned on its `done` word already)
+        double acc[kGateCols];
+        tall_norms_sum<kGateCols, false>(r.n, Pin, nwg, 1, nwg, acc, lds);
+        const TallOutcome o = tall_outcome(r.in, acc[0], acc[1], acc[2], maxit, nlam);
+        return o.discard() ? kSyGateLeave : o.pick();
+    }
+};
+static_assert(kSyThreads == kTailThreads, "the tiles and the deciding workgroup share the decision rule: one thread <-> partial mapping");
+static_assert(kSyGateScratch >= 6 * (kTailThreads / 64), "block_sum's scratch");
+
+// Block 0's part: the outcome applied -- eps of the next iteration, a_next / tau_next, the lambda schedule, niter[], the trace record,
+// done_host and ctl[par ^ 1].
 template <bool IN_LAUNCH = false>
 __device__ void tall_decide(const TallParams& q, int par) {
     __shared__ double dscratch[6 * (kTailThreads / 64)];
@@ -132,34 +246,29 @@ __device__ void tall_decide(const TallParams& q, int par) {
         return;
     }
     WIDE_PROBE(1);
-    double acc[6] = {0, 0, 0, 0, 0, 0};
-    const double* Pin = q.P + (size_t)par * q.nwg * 8;
-    for (int w = threadIdx.x; w < q.nwg; w += kTailThreads) {
-#pragma unroll
-        for (int k = 0; k < 6; ++k) acc[k] += tall_load_partial(Pin + (size_t)w * 8 + k, IN_LAUNCH);
-    }
-    block_sum<double, 6>(acc, dscratch);
+    double acc[6];
+    const double* Pin = tall_norm_rows(q.P, q.nwg, par);
+    tall_norms_sum<6, IN_LAUNCH>(tall_norms_request<6, IN_LAUNCH>(Pin, q.nwg, 8, 1), Pin, q.nwg, 8, 1, acc, dscratch);
     if (threadIdx.x != 0) return;
     WIDE_PROBE(2);
-    const double r2 = acc[0], dz2 = acc[1], daz2 = acc[2], x2 = acc[3], z2 = acc[4], y2 = acc[5];
-    double tr_rp = 0, tr_rd = 0, tr_c = 0, tr_code = ADMM_TRACE_COLD;
+    const double x2 = acc[3], z2 = acc[4], y2 = acc[5];
+    const TallOutcome oc = tall_outcome(in, acc[0], acc[1], acc[2], q.maxit, q.nlam);
+    const double tr_rp = oc.rp, tr_rd = oc.rd, tr_c = oc.c;
+    double tr_code = ADMM_TRACE_COLD;
     TallCtl out = in;
     out.first = 0;
     out.fin_idx = -1; out.fin_niter = 0;
-    if (!in.first) {
-        const double rp = sqrt(r2);                    // resid_primal            FADMMBase.h:208
-        const double rd = in.rho * sqrt(dz2);          // resid_dual              ADMMLassoTall.h:150-153
-        tr_rp = rp; tr_rd = rd;
-        if (rp < in.eps_primal && rd < in.eps_dual) {  // converged()             FADMMBase.h:213-217
+    if (oc.code == TALL_COLD) {
+        out.mode = 1; out.tau = 0.0; out.restart = 0;  // cold start: adj = 0, x = Minv X'y
+    } else {
+        if (oc.code == TALL_CONVERGED) {
             out.fin_idx = in.lam_idx; out.fin_niter = in.iter + 1;
             out.mode = 0;
             tr_code = ADMM_TRACE_CONVERGED;
         } else {
             const double old_c = in.adj_c;
-            const double c = in.rho * rp * rp + in.rho * daz2;     // compute_resid_combined  ADMMLassoTall.h:154-161
-            tr_c = c;
-            if (c < 0.999 * old_c) {                   // FADMMBase.h:243-249
-                out.adj_a = in.a_next; out.adj_c = c; out.tau = in.tau_next; out.restart = 0;
+            if (oc.code == TALL_ACCELERATE) {          // FADMMBase.h:243-249
+                out.adj_a = in.a_next; out.adj_c = oc.c; out.tau = in.tau_next; out.restart = 0;
                 tr_code = ADMM_TRACE_ACCELERATE;
             } else {                                   // restart                 FADMMBase.h:250-256
                 out.adj_a = 1.0; out.adj_c = old_c / 0.999; out.tau = -1.0; out.restart = 1;
@@ -167,24 +276,23 @@ __device__ void tall_decide(const TallParams& q, int par) {
             }
             out.mode = 1;
             out.iter = in.iter + 1;
-            if (in.iter + 1 >= q.maxit) {              // loop ran out: `return i + 1` with i == maxit
+            if (oc.fin) {                              // loop ran out: `return i + 1` with i == maxit
                 out.fin_idx = in.lam_idx; out.fin_niter = q.maxit + 1;
             }
         }
         if (out.fin_idx >= 0) {                        // next lambda: init_warm keeps x,z,y,adj,a,c,rho (ADMMLassoTall.h:219-230)
             out.lam_idx = in.lam_idx + 1;
             out.iter = 0;
-            if (out.lam_idx >= q.nlam) out.done = 1;
+            if (oc.done) out.done = 1;
             else out.lam = q.lambdas[out.lam_idx];
             q.niter[out.fin_idx] = out.fin_niter;
         }
-    } else {
-        out.mode = 1; out.tau = 0.0; out.restart = 0;  // cold start: adj = 0, x = Minv X'y
     }
-    // The tiles of THIS launch compute products the tail will not read when the decision is "keep the stored x" or "finished": tell the
-    // ones that have not started yet, as early as it is known (symv_kernels.h: SymvVerdict).  Only a discard is ever published -- any
-    // other word, a missing one included, means "stream".  Write-through, no fence: one word, nothing else to be seen with it.
-    if (q.verdict != nullptr && (out.mode == 0 || out.done)) {
+    // Verdict-word path (SYMV_VERDICT=1|2; q.verdict is NULL on the decide-first path, whose tiles know for themselves): the tiles of THIS
+    // launch compute products the tail will not read when the decision is "keep the stored x" or "finished": tell the ones that have not
+    // started yet, as early as it is known (symv_kernels.h: SymvVerdict).  Only a discard is ever published -- any other word, a missing
+    // one included, means "stream".  Write-through, no fence: one word, nothing else to be seen with it.
+    if (q.verdict != nullptr && oc.discard()) {
         const unsigned long long word = tall_verdict_word(q.run_tag, in.total + 1, true);
         for (int r = 0; r < kSyVerdictReplicas; ++r)
             __hip_atomic_store(q.verdict + (size_t)r * kSyVerdictStride, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -310,13 +418,15 @@ __device__ __forceinline__ void tall_publish_norms(const TallParams& q, int par,
         double sum = 0;
         for (int ww = 0; ww < kTailThreads / 64; ++ww) sum += scratch[threadIdx.x * (kTailThreads / 64) + ww];
         q.P[((size_t)(par ^ 1) * q.nwg + blockIdx.x) * 8 + threadIdx.x] = sum;
+        if (threadIdx.x < kGateCols) q.P[tall_norm_compact(q.nwg, par ^ 1) + (size_t)threadIdx.x * q.nwg + blockIdx.x] = sum;
     }
 }
 
 // Element-wise part of one iteration.  `c` = the control block published by this iteration's decision.
 // MODE 0: x-update results as gemv_t partial rows; 1: as the symmetric mat-vec's partial arrays; 2: row-sharded over the
-// PEER exchange -- wait for the K flags, then sum the K ranks' shares straight out of the exchange slots.
-enum { TAIL_GEMV = 0, TAIL_SYMV = 1, TAIL_PEER = 2, TAIL_PEER1 = 3 };
+// PEER exchange -- wait for the K flags, then sum the K ranks' shares straight out of the exchange slots; 4 (TAIL_SYMV1): the
+// decide-first x-update (symv1_lower_kernel) left ONE plane of partials, those of the vector this iteration's decision picked.
+enum { TAIL_GEMV = 0, TAIL_SYMV = 1, TAIL_PEER = 2, TAIL_PEER1 = 3, TAIL_SYMV1 = 4 };
 
 // The kTailLanes lanes of one element add up what each of them summed.
 __device__ __forceinline__ void tall_lane_sum(float& a, float& b) {
@@ -330,6 +440,12 @@ template <int MODE>
 __device__ __forceinline__ void tall_gather_ab(const TallParams& q, int i, int sub, bool valid, float& a, float& b) {
     if (MODE == TAIL_SYMV) {
         symv_sum_partials<kTailLanes>(q.dot0, q.dot1, q.axp0, q.axp1, q.ldo, q.nrb, q.sched, q.p32, i, sub, valid, a, b);
+        return;
+    }
+    if (MODE == TAIL_SYMV1) {
+        // Plane 0 holds Minv u if the decision was "accelerate" and Minv w if it was "restart": the one the tail reads.  Returned as both,
+        // so that `x = restart ? b : a` (tall_update_elem and its restatements) picks it either way -- and no load depends on ctl.
+        a = b = symv_sum_partials1<kTailLanes>(q.dot0, q.axp0, q.ldo, q.nrb, q.sched, q.p32, i, sub, valid);
         return;
     }
     a = 0.f; b = 0.f;
@@ -432,7 +548,7 @@ template <int MODE, bool SPARSE = false>
 __global__ void __launch_bounds__(kTailThreads)
 tall_group_tail_kernel(TallParams q, int par, GroupTailParams gp) {
 #pragma clang fp contract(off)
-    static_assert(MODE == TAIL_GEMV || MODE == TAIL_SYMV, "single device");
+    static_assert(MODE == TAIL_GEMV || MODE == TAIL_SYMV || MODE == TAIL_SYMV1, "single device");
     __shared__ double scratch[6 * (kTailThreads / 64)];
     __shared__ double snrm[kTailElems];
     // the tile's coordinates between the two halves of the update: x, adj_z, adj_y, v and what the second half still needs of the loads
@@ -550,7 +666,7 @@ template <int MODE>
 __global__ void __launch_bounds__(kTailThreads)
 tall_box_tail_kernel(TallParams q, int par, BoxTailParams bp) {
 #pragma clang fp contract(off)
-    static_assert(MODE == TAIL_GEMV || MODE == TAIL_SYMV, "single device");
+    static_assert(MODE == TAIL_GEMV || MODE == TAIL_SYMV || MODE == TAIL_SYMV1, "single device");
     __shared__ double scratch[6 * (kTailThreads / 64)];
     const TallCtl c = q.ctl[par ^ 1];
     const int sub = threadIdx.x & (kTailLanes - 1);
@@ -788,7 +904,7 @@ __global__ void tall_init_kernel(TallParams q, double rho, double lam0) {
         q.x[i] = 0.f; q.z0[i] = 0.f; q.z1[i] = 0.f; q.y0[i] = 0.f; q.y1[i] = 0.f;
         q.adj_z[i] = 0.f; q.adj_y[i] = 0.f; q.u[i] = q.XY[i]; q.w[i] = 0.f;
     }
-    if (i < 2 * q.nwg * 8) q.P[i] = 0.0;
+    if (i < 2 * q.nwg * (8 + kGateCols)) q.P[i] = 0.0;
     if (i == 0) {
         TallCtl c;
         c.rho = rho; c.lam = lam0; c.eps_primal = 0.0; c.eps_dual = 0.0;
@@ -796,7 +912,8 @@ __global__ void tall_init_kernel(TallParams q, double rho, double lam0) {
         c.a_next = 0.5 + 0.5 * sqrt(5.0); c.tau_next = 0.0;
         c.mode = 1; c.restart = 0; c.iter = 0; c.lam_idx = 0; c.done = 0; c.first = 1; c.total = 0; c.fin_idx = -1; c.fin_niter = 0; c.pad = 0;
         q.ctl[0] = c; q.ctl[1] = c;
-        if (q.verdict != nullptr) q.verdict[kVerdictWords] = 0;      // tiles that left early in this run (the words themselves carry the run number)
+        if (q.early != nullptr)                    // tiles that left early in this run (the verdict words themselves carry the run number)
+            for (int k = 0; k < kSyEarlySlots; ++k) q.early[(size_t)k * kSyVerdictStride] = 0;
     }
 }
 
@@ -831,6 +948,7 @@ struct TallPlan final : LassoPlan {
     DevBuf<TallCtl> ctl;
     DevBuf<unsigned long long> verdict;                 // early exit of discarded x-update launches (symv_kernels.h: SymvVerdict): the words + the counter
     bool verdict_on = false, verdict_mid = false;
+    bool decide_first = false;                          // SYMV_VERDICT=3 (default): every tile takes the decision itself and multiplies one vector (symv1_lower_kernel, TAIL_SYMV1)
     unsigned long long run_no = 0;                      // run() calls of this plan: part of the verdict word
     TallParams q{};
     // mixed-precision refinement of the x-update (ADMM_HIP_REFINE=1)
@@ -1092,7 +1210,7 @@ struct TallPlan final : LassoPlan {
         x.alloc(npl * ldv); z0.alloc(npl * ldv); z1.alloc(npl * ldv); y0.alloc(npl * ldv); y1.alloc(npl * ldv);
         adj_z.alloc(npl * ldv); adj_y.alloc(npl * ldv); u.alloc(ldv); w.alloc(ldv);
         beta.alloc((size_t)nlam * p * npl); niter.alloc(nlam);
-        P.alloc((size_t)2 * nwg * 8); dlam.alloc(nlam); ctl.alloc(2);
+        P.alloc((size_t)2 * nwg * (8 + kGateCols)); dlam.alloc(nlam); ctl.alloc(2);
         u.zero(st); w.zero(st);
         ADMM_HIP_CHECK(hipMemcpyAsync(dlam.get(), lam_int.data(), nlam * sizeof(double), hipMemcpyHostToDevice, st));
 
@@ -1110,12 +1228,17 @@ struct TallPlan final : LassoPlan {
         q.done_host = hflag.p;
         // Tiles leave early only where the tail provably ignores the products of a discarded launch: the single-device, unrefined
         // two-launch forms (tall_tail_kernel<TAIL_SYMV>, tall_group_tail_kernel<TAIL_SYMV>, tall_box_tail_kernel<TAIL_SYMV>).  Sharded, refined and multi-task x-updates
-        // have consumers of their own between the stream and the tail.  ADMM_HIP_SYMV_VERDICT=0 turns it off, 1 keeps only the check in the tile prologue (A/B, tests).
-        verdict_on = use_sym && !shard && !refine && !mt && !opt_off(Opt::SYMV_VERDICT);
-        verdict_mid = opt_int(Opt::SYMV_VERDICT, 2) == 2;      // default: the waves also look between the chunks of their column loop
+        // have consumers of their own between the stream and the tail.  ADMM_HIP_SYMV_VERDICT=3 (default): the tiles take the decision themselves before they
+        // stream, and stream one vector (symv1_lower_kernel); 2 / 1: two vectors, and the tiles look for the verdict word block 0 publishes, between the
+        // chunks of their column loop as well / in their prologue only; 0: two vectors, no tile ever leaves (A/B, tests).
+        const int level = (int)opt_int(Opt::SYMV_VERDICT, 3);
+        verdict_on = use_sym && !shard && !refine && !mt && level != 0;
+        decide_first = verdict_on && level == 3;
+        verdict_mid = level == 2;
         if (verdict_on) {
-            verdict.alloc(kVerdictWords + kSyVerdictStride); verdict.zero(st);
-            q.verdict = verdict.get();
+            verdict.alloc(kVerdictWords + kSyEarlySlots * kSyVerdictStride); verdict.zero(st);
+            q.verdict = decide_first ? nullptr : verdict.get();      // decide-first: nobody reads a word, block 0 publishes none
+            q.early = verdict.get() + kVerdictWords;
         }
 #ifdef ADMM_HIP_PROBE
         probe.alloc((size_t)4096 * 4 * 8); probe.zero(st);
@@ -1266,7 +1389,7 @@ struct TallPlan final : LassoPlan {
         res.lambda = lam_user;
         beta.zero(st); niter.zero(st);
         q.run_tag = ++run_no << kVerdictShift;          // `total` restarts at 0 below: the words an earlier run left must not match this one's
-        const int init_n = std::max(p, 2 * nwg * 8);
+        const int init_n = std::max(p, 2 * nwg * (8 + kGateCols));
         for (int k = 0; k < std::max(mt, 1); ++k) {      // multi-task: plane by plane (every launch writes the same control block and norm partials)
             TallParams qk = q;
             if (mt) {
@@ -1311,16 +1434,21 @@ struct TallPlan final : LassoPlan {
             const TallDecideExtra dec{q, par};
             // launch g rides the decision that leaves g + 1 taken: its tiles leave on exactly that word with the discard bit set
             SymvVerdict vd;
-            if (verdict_on) { vd.words = verdict.get(); vd.discard = tall_verdict_word(q.run_tag, (int)(g + 1), true); vd.early = verdict.get() + kVerdictWords; vd.mid = verdict_mid; }
+            if (verdict_on && !decide_first) { vd.words = verdict.get(); vd.discard = tall_verdict_word(q.run_tag, (int)(g + 1), true); vd.early = verdict.get() + kVerdictWords; vd.mid = verdict_mid; }
             const int* skip = &ctl.get()[par].done;
             // single device, one stream of the inverse: the x-update with the decision riding on it, in the form p selected
             const auto xupdate = [&] {
-                if (use_sym) sy.launch(M.get(), ldp, u.get(), w.get(), skip, st, dec, e0, e1, vd);
+                if (decide_first) {
+                    const TallGate gate{ctl.get() + par, P.get() + tall_norm_compact(nwg, par), nwg, q.maxit, q.nlam};
+                    sy.launch_one(M.get(), ldp, u.get(), w.get(), skip, st, gate, q.early, dec, e0, e1);
+                }
+                else if (use_sym) sy.launch(M.get(), ldp, u.get(), w.get(), skip, st, dec, e0, e1, vd);
                 else launch_gemv_t<float, 2, 4, TallDecideExtra>(pl, M.get(), ldp, p, p, u.get(), w.get(), a_part.get(), b_part.get(), ldp, skip, st, dec, e0, e1);
             };
             const auto group_tail = [&] {
                 void (*tail)(TallParams, int, GroupTailParams) =
-                    use_sym ? (sgl ? tall_group_tail_kernel<TAIL_SYMV, true> : tall_group_tail_kernel<TAIL_SYMV>)
+                    decide_first ? (sgl ? tall_group_tail_kernel<TAIL_SYMV1, true> : tall_group_tail_kernel<TAIL_SYMV1>)
+                    : use_sym ? (sgl ? tall_group_tail_kernel<TAIL_SYMV, true> : tall_group_tail_kernel<TAIL_SYMV>)
                             : (sgl ? tall_group_tail_kernel<TAIL_GEMV, true> : tall_group_tail_kernel<TAIL_GEMV>);
                 hipLaunchKernelGGL(tail, dim3(nwg), dim3(kTailThreads), 0, st, q, par, gq);
             };
@@ -1375,18 +1503,24 @@ struct TallPlan final : LassoPlan {
                 hipLaunchKernelGGL(tall_tail_kernel<TAIL_SYMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, PeerExchange{});
             } else if (box) {                          // two launches, as the Lasso
                 xupdate();
-                if (use_sym) hipLaunchKernelGGL(tall_box_tail_kernel<TAIL_SYMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, bq);
+                if (decide_first) hipLaunchKernelGGL(tall_box_tail_kernel<TAIL_SYMV1>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, bq);
+                else if (use_sym) hipLaunchKernelGGL(tall_box_tail_kernel<TAIL_SYMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, bq);
                 else hipLaunchKernelGGL(tall_box_tail_kernel<TAIL_GEMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, bq);
             } else {
                 xupdate();
-                if (use_sym) hipLaunchKernelGGL(tall_tail_kernel<TAIL_SYMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, PeerExchange{});
+                if (decide_first) hipLaunchKernelGGL(tall_tail_kernel<TAIL_SYMV1>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, PeerExchange{});
+                else if (use_sym) hipLaunchKernelGGL(tall_tail_kernel<TAIL_SYMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, PeerExchange{});
                 else hipLaunchKernelGGL(tall_tail_kernel<TAIL_GEMV>, dim3(nwg), dim3(kTailThreads), 0, st, q, par, PeerExchange{});
             }
         }, LoopOpts{shard ? nullptr : hflag.p, 0, false});
         S.t_loop = lt.wall_s; S.loop_ms_events = lt.events_ms; S.xupdate_launches = lt.launched;
         const CtlPair<TallCtl> hctl = read_ctl(ctl.get());      // both slots: decisions taken
         unsigned long long early = 0;
-        if (verdict_on) ADMM_HIP_CHECK(hipMemcpy(&early, verdict.get() + kVerdictWords, sizeof early, hipMemcpyDeviceToHost));
+        if (verdict_on) {                                      // the two-vector kernel counts in slot 0, the one-vector kernel in all of them
+            std::vector<unsigned long long> slots((size_t)kSyEarlySlots * kSyVerdictStride);
+            ADMM_HIP_CHECK(hipMemcpy(slots.data(), verdict.get() + kVerdictWords, slots.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+            for (int k = 0; k < kSyEarlySlots; ++k) early += slots[(size_t)k * kSyVerdictStride];
+        }
         t_early_exits = (long long)early;
         WIDE_PROBE_DUMP(probe);
         if (nev > 0) {

@@ -34,7 +34,7 @@ constexpr double kPositive = std::numeric_limits<double>::min();  // Real(kPosit
     X(INVERSE, Choice("f32|f64"), "precision the cached inverse is built in")                                                           \
     X(XUPDATE, Choice("sym|gemv|full"), "tall x-update: symmetric lower-triangle kernel / full-matrix mat-vec (gemv and full alike)")   \
     X(SYMV_SCHED, Sched(), "tall x-update: column-segment widths of the long / short row strips and the split between them")           \
-    X(SYMV_VERDICT, Choice("0|1|2"), "tall x-update: tiles of a discarded launch leave never / when they start / also mid-tile (default)") \
+    X(SYMV_VERDICT, Choice("0|1|2|3"), "tall x-update: discarded launches stream on / leave on block 0's word at start / also mid-tile / every tile decides first, one vector (default)") \
     X(REFINE, Flag(), "tall path: refine every x-update with a double-precision residual")                                               \
     X(DIST_FACTOR, Flag(), "row-sharded tall solver: 0 = every rank factorises the whole all-reduced Gram")                            \
     X(CV_DOWNDATE, Flag(), "cross-validation folds' Grams as down-dates of the full-data Gram: 1 always, 0 never")                      \

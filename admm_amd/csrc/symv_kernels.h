@@ -48,11 +48,24 @@
 //    the chunks as well it takes 19.5 us and the path 85.8-87.8 ms against 86.9-90.1 (parent: 89.1-90.7), regular launches 33.2
 //    against 33.1 us.  A first form that kept the word in vector registers through the chunk spilled (24 bytes of scratch, a reload
 //    in the loop) and was not measured: the word is compared as two scalars right behind the chunk's wait.
+// Round 8, the decision before the stream (profiles/tall_decide_first.md): the tall solver's default x-update is symv1_lower_kernel below --
+// still two launches per iteration, but every tile takes the launch's decision itself in its prologue (a Gate functor) and multiplies ONE
+// vector, or leaves.  symv2_lower_kernel stays for the verdict-word levels, the sharded and the refined paths.
+// Measured and rejected there (C2, same box, kernel trace of parent and variants in one session):
+//  * 5 or 6 workgroups per CU for the one-vector kernel (ADMM_HIP_SYMV1_WGS): it needs 117 VGPRs at 4; bounded to 96 / 80 it spills the
+//    column chunk like the two-vector kernel did (124-128 / 188 bytes of scratch per lane, with or without the peeled first chunk):
+//    not measured, 4 kept;
+//  * the gate evaluated BEFORE the first matrix request (ADMM_HIP_SYMV1_PRE=0: no peeled chunk, a leaving tile requests nothing):
+//    regular launches 34.6 us against 32.9 with the first chunk requested ahead of the gate (two-vector kernel: 32.9) -- the block sum
+//    and its two barriers are exposed in every tile; 89.9-90.1 ms per path against 87.0-87.8;
+//  * the gate reading the 64-byte rows of the norm partials as block 0 does (313 rows, a wave's load touching 64 lines): regular launches
+//    2 us slower than the two-vector kernel's; the tails now write a compact copy (lasso_tall.hip: tall_publish_norms).
 #pragma once
 #include "admm_internal.h"
 #include "device_utils.h"
 #include <hip/hip_ext.h>
 #include <climits>
+#include <type_traits>
 
 namespace admm {
 
@@ -90,7 +103,7 @@ struct SymvArgs {
     const int* skip;                       // sticky `done` word (a caller without one gets the plan's zero word: never null in the kernel)
     const unsigned long long* verdict;     // kSyVerdictReplicas copies of the verdict word, one per 128-byte line (SymvVerdict below; never null in the kernel)
     unsigned long long discard;            // the one value of that word that says "the products of this launch are not used"
-    unsigned long long* early;             // count of the tiles that left on it (added to on the exit path only)
+    unsigned long long* early;             // count of the tiles that left on it (added to on the exit path only); symv1_lower_kernel: kSyEarlySlots counters
 #ifdef ADMM_HIP_PROBE
     long long* probe; int probe_idx;       // dev build only (probe.h): entry / end stamps of the first, middle and last tile
 #endif
@@ -309,6 +322,150 @@ symv2_lower_kernel(SymvArgs a, Extra extra) {
     if (a.probe != nullptr && threadIdx.x == 0) {
         const int nt = (int)gridDim.x - 1, t = (int)blockIdx.x - 1;
         const int which = t == 0 ? 0 : (t == nt / 2 ? 1 : (t == nt - 1 ? 2 : (t == (3 * nt) / 4 ? 3 : -1)));
+        if (which >= 0) {
+            long long* d = a.probe + ((size_t)(a.probe_idx & 4095) * 4 + 3) * 8 + which * 2;
+            d[0] = pt0; d[1] = wall_clock64();
+        }
+    }
+#endif
+}
+
+// ---- ONE right-hand side, chosen before the stream (the tall solver's default x-update: lasso_tall.hip, SYMV_VERDICT=3).
+// symv2_lower_kernel multiplies by both candidates because the decision between them is taken beside its stream.  Everything that decision
+// needs was written by EARLIER launches, so every tile can take it itself, in its prologue: a `Gate` functor answers "leave" (nobody
+// reads the products of this launch) or which of the two vectors is the one the consumer will read.
+//   gate.request()          issues the gate's loads (ordinary cached loads: per XCD one miss per line, the rest L2 hits) and returns them;
+//                           called beside the requests of the tile descriptor and the `done` word, so that all arrive in one round trip
+//   gate.decide(req, lds)   called by every thread of the workgroup; returns kSyGateLeave, 0 or 1, the same value in every thread
+// On "leave" thread 0 counts the tile in `early` and the workgroup returns without writing a partial.  Otherwise the tile is symv2_tile
+// for the picked vector alone: per right-hand side the same fmaf chains, the same butterfly8, the same cross-wave sum, the same diagonal
+// handling and `last`, so the partials written for pick = r have the bits symv2_lower_kernel writes into plane r -- but they go into
+// plane 0 (dot0, axp0) whichever vector was picked, and symv_sum_partials1 below sums that one plane.
+// PRE: the first chunk's matrix requests are issued before the gate is evaluated (its block sum and barriers then run under loads in
+// flight); that chunk is peeled off the column loop, which keeps the shape that streams best (symv2_tile, PRE = false).
+constexpr int kSyGateLeave = -1;
+// Every tile of a discarded launch counts itself.  1600 atomic adds to ONE word are served one after the other by the memory side (they
+// took 25 us of such a launch, measured; the two-vector kernel's few late leavers never showed it): the tiles spread over kSyEarlySlots
+// counters on lines of their own, which the host adds up.
+constexpr int kSyEarlySlots = kSyVerdictReplicas;          // a power of two; stride kSyVerdictStride words
+constexpr int kSyGateScratch = 6 * (kSyThreads / 64);     // doubles of LDS a gate may use in decide()
+struct SymvForcedGate {                                   // a fixed answer (test hook admm_hip_test_symv_one)
+    struct Req {};
+    int answer;
+    __device__ __forceinline__ Req request() const { return Req(); }
+    __device__ __forceinline__ int decide(const Req&, double*) const { return answer; }
+};
+#ifndef ADMM_HIP_SYMV1_WGS
+#define ADMM_HIP_SYMV1_WGS 4                              // workgroups per CU the one-vector kernel is built for (dev builds: 5, 6; "Measured and rejected" above)
+#endif
+#ifndef ADMM_HIP_SYMV1_PRE
+#define ADMM_HIP_SYMV1_PRE 8                              // columns of the first chunk requested ahead of the gate (dev builds: 0 = the gate first; "Measured and rejected" above)
+#endif
+
+template <typename Gate, typename Extra, bool NT = false, int PRE = ADMM_HIP_SYMV1_PRE>
+__global__ void __launch_bounds__(kSyThreads, ADMM_HIP_SYMV1_WGS)
+symv1_lower_kernel(SymvArgs a, Gate gate, Extra extra) {
+    if (blockIdx.x == 0) { extra(); return; }
+    __shared__ float4 red[kSyThreads];
+    __shared__ __attribute__((aligned(16))) float sdot[kSyCBMax];
+    __shared__ double gate_lds[kSyGateScratch];
+    // Prologue: the tile descriptor, the `done` word and the gate's inputs are requested together
+    const int4 t = a.tiles[blockIdx.x - 1];
+    const int done = *a.skip;
+    const typename Gate::Req greq = gate.request();
+    if (done != 0) return;                 // (arrives with the descriptor: checked before the first matrix request, not behind it)
+    const int rb = t.x, seg = t.w;
+    const int cw = t.z >> 2;               // columns per wave: a multiple of 8, at most 64
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int row = rb * kSyRB + lane * 4;
+    const int col0 = t.y + wid * cw;
+    const int p4 = (a.p + 3) & ~3;
+    const bool active = row < p4;
+    const bool has = col0 < a.p;           // every wave of a listed tile has all its columns <= the block's last row
+    const float* base = a.A + (size_t)col0 * a.lda + row;
+    const bool diag = col0 + (cw - 1) >= rb * kSyRB;         // this wave's block meets the diagonal
+    const int nq = has ? cw >> 3 : 0;
+    const int last = active ? min(a.p - 1, diag ? row + 3 : INT_MAX) : -1;      // symv2_tile's `last`
+    float4 av[8];
+    const auto request = [&](int q, auto k0, auto k1) {      // columns k0 .. k1 - 1 of chunk q
+#pragma unroll
+        for (int k = decltype(k0)::value; k < decltype(k1)::value; ++k) {
+            const int col = col0 + q * 8 + k;
+            av[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+            if constexpr (NT) { if (col <= last) av[k] = load16_nt<float4>(base + (size_t)(q * 8 + k) * a.lda); }
+            else { if (col <= last) av[k] = *reinterpret_cast<const float4*>(base + (size_t)(q * 8 + k) * a.lda); }
+        }
+    };
+    using K0 = std::integral_constant<int, 0>; using KP = std::integral_constant<int, PRE>; using K8 = std::integral_constant<int, 8>;
+    static_assert(PRE >= 0 && PRE <= 8, "columns of the first chunk requested ahead of the gate");
+    if constexpr (PRE > 0) { if (nq > 0) request(0, K0(), KP()); }
+    const int g = gate.decide(greq, gate_lds);
+    if (g == kSyGateLeave) {               // nobody reads what this launch would write: the slots keep what the last consumed launch left
+        if (threadIdx.x == 0) atomicAdd(a.early + (size_t)(blockIdx.x & (kSyEarlySlots - 1)) * kSyVerdictStride, 1ull);
+        return;
+    }
+#ifdef ADMM_HIP_PROBE
+    const long long pt0 = wall_clock64();
+#endif
+    const float* v = g != 0 ? a.v1 : a.v0;
+    float4 aU = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (has) {
+        const float4 uI = active ? *reinterpret_cast<const float4*>(v + row) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const int cj = col0 + lane;                                          // the wave's (<= 64) right-hand entries, one per lane
+        const float uj = (lane < cw && cj < a.p) ? v[cj] : 0.f;
+        const auto consume = [&](int q) {
+            float dU[8];
+#pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const int col = col0 + q * 8 + k;
+                float4 m = av[k];
+                float4 ax = m;                                    // axpy part excludes the diagonal
+                if (diag) {
+                    if (row + 0 < col) m.x = 0.f;
+                    if (row + 1 < col) m.y = 0.f;
+                    if (row + 2 < col) m.z = 0.f;
+                    if (row + 3 < col) m.w = 0.f;
+                    ax = m;
+                    if (row + 0 == col) ax.x = 0.f;
+                    if (row + 1 == col) ax.y = 0.f;
+                    if (row + 2 == col) ax.z = 0.f;
+                    if (row + 3 == col) ax.w = 0.f;
+                }
+                dU[k] = fmaf(m.x, uI.x, fmaf(m.y, uI.y, fmaf(m.z, uI.z, m.w * uI.w)));
+                const float ujc = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(uj), (q * 8 + k) & 63));
+                aU.x = fmaf(ax.x, ujc, aU.x); aU.y = fmaf(ax.y, ujc, aU.y); aU.z = fmaf(ax.z, ujc, aU.z); aU.w = fmaf(ax.w, ujc, aU.w);
+            }
+            const float du = butterfly8(dU, lane);                // every lane ends with column (lane >> 3)
+            if ((lane & 7) == 0) sdot[wid * cw + q * 8 + (lane >> 3)] = du;
+        };
+        if constexpr (PRE > 0) { request(0, KP(), K8()); consume(0); }      // the rest of the peeled chunk
+#pragma unroll 1
+        for (int q = PRE > 0 ? 1 : 0; q < nq; ++q) {
+            request(q, K0(), K8());
+            consume(q);
+        }
+    } else {
+        for (int c = lane; c < cw; c += 64) sdot[wid * cw + c] = 0.f;
+    }
+    // axpy part: wave 0 adds the 4 waves (same rows, different columns) in symv2_tile's order; dot part: wave 1 writes the one row
+    red[threadIdx.x] = aU;
+    __syncthreads();
+    if (wid == 0) {
+        float4 s = red[lane];
+#pragma unroll
+        for (int ww = 1; ww < 4; ++ww) {
+            const float4 o = red[ww * 64 + lane];
+            s.x += o.x; s.y += o.y; s.z += o.z; s.w += o.w;
+        }
+        *reinterpret_cast<float4*>(a.axp0 + (size_t)seg * a.ldo + row) = s;
+    } else if (wid == 1) {
+        float* dst = a.dot0 + (size_t)rb * a.ldo + t.y;                          // t.y + width <= (rb + 1) * 256 <= ldo
+        for (int c = lane * 4; c < t.z; c += 256) *reinterpret_cast<float4*>(dst + c) = *reinterpret_cast<const float4*>(&sdot[c]);
+    }
+#ifdef ADMM_HIP_PROBE
+    if (a.probe != nullptr && threadIdx.x == 0) {
+        const int nt = (int)gridDim.x - 1, ti = (int)blockIdx.x - 1;
+        const int which = ti == 0 ? 0 : (ti == nt / 2 ? 1 : (ti == nt - 1 ? 2 : (ti == (3 * nt) / 4 ? 3 : -1)));
         if (which >= 0) {
             long long* d = a.probe + ((size_t)(a.probe_idx & 4095) * 4 + 3) * 8 + which * 2;
             d[0] = pt0; d[1] = wall_clock64();
@@ -683,6 +840,23 @@ struct SymvPlan {
         if (ev_start == nullptr && ev_stop == nullptr) hipLaunchKernelGGL((symv2_lower_kernel<Extra>), dim3(ntiles + 1), dim3(kSyThreads), 0, st, a, extra);
         else hipExtLaunchKernelGGL((symv2_lower_kernel<Extra>), dim3(ntiles + 1), dim3(kSyThreads), 0, st, ev_start, ev_stop, 0, a, extra);
     }
+    // symv1_lower_kernel: the vector `gate` picks (v0 or v1) into plane 0, or nothing at all; `early`: kSyEarlySlots counters (stride
+    // kSyVerdictStride words) of the tiles that left, to be added up by the caller
+    template <typename Gate, typename Extra = SymvNoExtra>
+    void launch_one(const float* A, long long lda, const float* v0, const float* v1, const int* skip, hipStream_t st, Gate gate, unsigned long long* early,
+                    Extra extra = Extra(), hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr) {
+        SymvVerdict vd;
+        vd.early = early;
+        const SymvArgs a = args(A, lda, v0, v1, skip, vd);
+        const bool timed = ev_start != nullptr || ev_stop != nullptr;
+        if (nt) {
+            if (!timed) hipLaunchKernelGGL((symv1_lower_kernel<Gate, Extra, true>), dim3(ntiles + 1), dim3(kSyThreads), 0, st, a, gate, extra);
+            else hipExtLaunchKernelGGL((symv1_lower_kernel<Gate, Extra, true>), dim3(ntiles + 1), dim3(kSyThreads), 0, st, ev_start, ev_stop, 0, a, gate, extra);
+            return;
+        }
+        if (!timed) hipLaunchKernelGGL((symv1_lower_kernel<Gate, Extra>), dim3(ntiles + 1), dim3(kSyThreads), 0, st, a, gate, extra);
+        else hipExtLaunchKernelGGL((symv1_lower_kernel<Gate, Extra>), dim3(ntiles + 1), dim3(kSyThreads), 0, st, ev_start, ev_stop, 0, a, gate, extra);
+    }
 };
 
 // y_i of both right-hand sides from the partial arrays.  NL lanes (a power of two <= 64, consecutive lanes of one
@@ -726,6 +900,41 @@ __device__ __forceinline__ void symv_sum_partials(const T* __restrict__ dot0, co
     }
 #pragma unroll
     for (int m = 1; m < NL; m <<= 1) { a += __shfl_xor(a, m, 64); b += __shfl_xor(b, m, 64); }
+}
+
+// The same for plane 0 alone (symv1_lower_kernel writes no other): symv_sum_partials' slots, clamping, order and lane combine for `a`,
+// so the sum has the bits that function returns as a (or, for the same partials in plane 1, as b) -- at 16 loads per lane, not 32.
+template <int NL, typename T = float>
+__device__ __forceinline__ T symv_sum_partials1(const T* __restrict__ dot0, const T* __restrict__ axp0,
+                                                long long ldo, int nrb, const SymvSched sched, int p32, int i, int sub, bool valid) {
+    const int ic = valid ? i : 0;
+    const int rbi = ic / kSyRB;
+    const int rb0 = rbi;
+    const int ndot = nrb - rb0;
+    const int nax = sched.nseg(rbi, p32);
+    const int ntot = valid ? ndot + nax : 0;
+    const unsigned ld = (unsigned)ldo;
+    T a = T(0);
+    for (int k0 = 0; k0 < ntot; k0 += 16 * NL) {
+        T va[16];
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const int k = k0 + j * NL + sub;
+            const bool isdot = k < ndot;
+            const int row = isdot ? rb0 + k : min(k, ntot - 1) - ndot;
+            const unsigned o = (unsigned)row * ld + (unsigned)ic;
+            va[j] = (isdot ? dot0 : axp0)[o];
+        }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < 16; ++j) {
+            const bool in = k0 + j * NL + sub < ntot;
+            a += in ? va[j] : T(0);
+        }
+    }
+#pragma unroll
+    for (int m = 1; m < NL; m <<= 1) a += __shfl_xor(a, m, 64);
+    return a;
 }
 
 // Launch of one pass of symvn_lower_kernel over the tiles of `sy` with nr = one of kSyNR right-hand sides per pass.

@@ -9,6 +9,8 @@ constexpr int kSymvHookMaxP = 32768;      // largest order the hooks below accep
 bool test_symv_rhs_built(int rhs_per_pass);      // one of the widths symvn_lower_kernel is built for (kSyNR, symv_kernels.h)
 void test_symv_plan(int p, int cus, int part, int nparts, int* sched_out, long long* info_out, int* tiles_out, int tile_capacity);      // host only
 void test_symv_ex(const float* A, int p, const float* v0, const float* v1, int variant, int part, int nparts, float* y0, float* y1, int* sched_out);
+void test_symv_one(const float* A, int p, const float* v0, const float* v1, int gate, int nt, unsigned fill, float* y, float* dot_out, float* axp_out,
+                   long long plane_capacity, long long* info_out, int* sched_out);
 void test_symv_multi_ex(const float* A, int p, const float* V, int nr, int rhs_per_pass, int nt, int finish, float* Yout, int* sched_out);
 void test_symv_f64acc(const float* A, int p, const float* v0, const float* v1, double* y0, double* y1, int* sched_out);
 template <typename T> void test_gram(const T* A, int rows, int cols, bool atA, T* G);

@@ -160,6 +160,67 @@ void test_symv_ex(const float* A, int p, const float* v0, const float* v1, int v
         throw Error(ADMM_ERR_INTERNAL, std::to_string(left) + " tiles left early on a verdict word that cannot equal `discard`");
 }
 
+// symv1_lower_kernel (the decide-first x-update's one-vector kernel) with a forced gate, on the plan's storage: gate 0 / 1 multiplies v0 / v1
+// into plane 0, 2 leaves (every tile counted, nothing written); 3 runs symv2_lower_kernel on the same storage instead, the reference of the
+// bit-identity tests.  Both planes of partials are pre-filled with the 32-bit pattern `fill` and handed back as they are afterwards.
+// y[0]: plane 0 through the one-plane sum of TAIL_SYMV1 (symv_sum_partials1); gate 3: y[0], y[1] = the two-plane sum's a, b.
+__global__ void __launch_bounds__(256)
+test_symv_finish_one_kernel(const float* dot0, const float* axp0, long long ldo, int nrb, SymvSched sched, int p32, int p, float* y0) {
+    const int sub = threadIdx.x & (kSySumLanes - 1);
+    const int i = blockIdx.x * (256 / kSySumLanes) + threadIdx.x / kSySumLanes;
+    const float a = symv_sum_partials1<kSySumLanes>(dot0, axp0, ldo, nrb, sched, p32, i, sub, i < p);
+    if (i < p && sub == 0) y0[i] = a;
+}
+
+void test_symv_one(const float* A, int p, const float* v0, const float* v1, int gate, int nt, unsigned fill, float* y, float* dot_out, float* axp_out,
+                   long long plane_capacity, long long* info_out, int* sched_out) {
+    require_device();
+    Stream st;
+    const long long lda = round_up(p, 128), ldv = round_up(p, 256);
+    DevBuf<float> dA((size_t)lda * lda), d0(ldv), d1(ldv), o0(ldv), o1(ldv);
+    DevBuf<unsigned long long> early((size_t)kSyEarlySlots * kSyVerdictStride);
+    dA.zero(st.s); d0.zero(st.s); d1.zero(st.s); early.zero(st.s);
+    ADMM_HIP_CHECK(hipMemcpy2DAsync(dA.get(), lda * sizeof(float), A, (size_t)p * sizeof(float), (size_t)p * sizeof(float), p,
+                                    hipMemcpyHostToDevice, st.s));
+    ADMM_HIP_CHECK(hipMemcpyAsync(d0.get(), v0, (size_t)p * sizeof(float), hipMemcpyHostToDevice, st.s));
+    ADMM_HIP_CHECK(hipMemcpyAsync(d1.get(), v1, (size_t)p * sizeof(float), hipMemcpyHostToDevice, st.s));
+    SymvPlan sy;
+    sy.init(p, st.s);
+    report_sched(sy.sched, sched_out);
+    const size_t nd = (size_t)sy.nrb * sy.ldo, na = (size_t)sy.nax_rows * sy.ldo;
+    info_out[0] = sy.ntiles; info_out[1] = -1; info_out[2] = (long long)nd; info_out[3] = (long long)na;
+    ADMM_REQUIRE(dot_out == nullptr || (long long)std::max(nd, na) <= plane_capacity,
+                 "symv_one hook: plane_capacity is too small for the " + std::to_string(std::max(nd, na)) + " floats of a plane of partials");
+    sy.nt = nt != 0;
+    float* planes[4] = {sy.dot0.get(), sy.dot1.get(), sy.axp0.get(), sy.axp1.get()};
+    for (int k = 0; k < 4; ++k) ADMM_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(planes[k]), (int)fill, k < 2 ? nd : na, st.s));
+    const int per = 256 / kSySumLanes;
+    if (gate == 3) {
+        sy.launch(dA.get(), lda, d0.get(), d1.get(), nullptr, st.s);
+        hipLaunchKernelGGL(test_symv_finish_kernel, dim3((p + per - 1) / per), dim3(256), 0, st.s, sy.dot0.get(), sy.dot1.get(),
+                           sy.axp0.get(), sy.axp1.get(), sy.ldo, sy.nrb, sy.sched, sy.p32, p, o0.get(), o1.get());
+    } else {
+        sy.launch_one(dA.get(), lda, d0.get(), d1.get(), nullptr, st.s, SymvForcedGate{gate == 2 ? kSyGateLeave : gate}, early.get());
+        hipLaunchKernelGGL(test_symv_finish_one_kernel, dim3((p + per - 1) / per), dim3(256), 0, st.s, sy.dot0.get(), sy.axp0.get(),
+                           sy.ldo, sy.nrb, sy.sched, sy.p32, p, o0.get());
+    }
+    ADMM_HIP_CHECK(hipGetLastError());
+    std::vector<unsigned long long> slots((size_t)kSyEarlySlots * kSyVerdictStride);
+    ADMM_HIP_CHECK(hipMemcpyAsync(y, o0.get(), (size_t)p * sizeof(float), hipMemcpyDeviceToHost, st.s));
+    if (gate == 3) ADMM_HIP_CHECK(hipMemcpyAsync(y + p, o1.get(), (size_t)p * sizeof(float), hipMemcpyDeviceToHost, st.s));
+    ADMM_HIP_CHECK(hipMemcpyAsync(slots.data(), early.get(), slots.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st.s));
+    if (dot_out != nullptr) {
+        for (int k = 0; k < 2; ++k) {
+            ADMM_HIP_CHECK(hipMemcpyAsync(dot_out + (size_t)k * plane_capacity, planes[k], nd * sizeof(float), hipMemcpyDeviceToHost, st.s));
+            ADMM_HIP_CHECK(hipMemcpyAsync(axp_out + (size_t)k * plane_capacity, planes[2 + k], na * sizeof(float), hipMemcpyDeviceToHost, st.s));
+        }
+    }
+    st.sync();
+    long long left = 0;
+    for (int k = 0; k < kSyEarlySlots; ++k) left += (long long)slots[(size_t)k * kSyVerdictStride];
+    info_out[1] = left;
+}
+
 // test_symvn_finish_kernel with the consumer the multi-task tail really uses: symv_sum_partials_n over chunks of kMtChunk pairs, walked
 // as tall_mt_tail_kernel walks them (chunk k0: planes from 2 k0, nk = min(kMtChunk, npair - k0) pairs of it valid).
 __global__ void __launch_bounds__(256)

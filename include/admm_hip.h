@@ -669,6 +669,16 @@ ADMM_HIP_API int admm_hip_test_symv_plan(int p, int cus, int part, int nparts, i
  * the parts add up to the product.  sched_out[3]: the schedule the plan used, as above.  p <= 32768. */
 ADMM_HIP_API int admm_hip_test_symv_ex(const float* A, int p, const float* v0, const float* v1, int variant, int part, int nparts,
                                        float* y0, float* y1, int* sched_out);
+/* The one-vector kernel of the decide-first x-update (ADMM_HIP_SYMV_VERDICT=3) with its gate forced: gate 0 / 1 multiplies v0 / v1 into
+ * plane 0 of the partial arrays, 2 makes every tile leave (nothing written, every tile counted); 3 runs the two-vector kernel of
+ * admm_hip_test_symv_ex (variant 0, or 1 with nt = 1) on the same storage, for comparison.  All four partial arrays are pre-filled with
+ * the 32-bit pattern `fill`.  y [2][p]: y[0] = plane 0 through the one-plane sum of the solver's tails (gate 3: y[0], y[1] = the
+ * two-plane sum of both products).  dot_out, axp_out (both or neither): [2][plane_capacity] floats, planes 0 and 1 of the dot / axpy
+ * partial arrays as the launch left them (info_out[2] / info_out[3] floats each; a plane_capacity below the larger:
+ * ADMM_ERR_INVALID_ARG).  info_out[4]: tiles, tiles that left early, floats of a dot plane, of an axpy plane.  p <= 32768. */
+ADMM_HIP_API int admm_hip_test_symv_one(const float* A, int p, const float* v0, const float* v1, int gate, int nt, unsigned int fill,
+                                        float* y, float* dot_out, float* axp_out, long long plane_capacity, long long* info_out,
+                                        int* sched_out);
 /* admm_hip_test_symv_multi with the non-temporal instantiations forced (nt = 1) or not (0), and the consumer chosen: finish 0 sums the
  * partials pair by pair (as admm_hip_test_symv_multi), 1 in chunks of pairs with the routine and the walk of the multi-task tail. */
 ADMM_HIP_API int admm_hip_test_symv_multi_ex(const float* A, int p, const float* V, int nr, int rhs_per_pass, int nt, int finish,
@@ -678,7 +688,9 @@ ADMM_HIP_API int admm_hip_test_symv_multi_ex(const float* A, int p, const float*
 ADMM_HIP_API int admm_hip_test_symv_f64acc(const float* A, int p, const float* v0, const float* v1, double* y0, double* y1, int* sched_out);
 /* Tiles of the tall x-update that left early because the launch they belonged to was known to be discarded (the first launch after a
  * converged lambda, the launch of the last decision; ADMM_HIP_SYMV_VERDICT=0: none), counted over the most recent tall lasso /
- * elastic-net / group-lasso path run by the CALLING THREAD.  How many leave is a matter of timing; the results do not depend on it. */
+ * elastic-net / group-lasso path run by the CALLING THREAD.  At the default level 3 every tile takes the decision itself before it
+ * streams, so the count is exact: tiles x discarded launches.  At levels 1 and 2 how many leave is a matter of timing; the results
+ * depend on it at no level. */
 ADMM_HIP_API int admm_hip_test_tall_early_exits(long long* count);
 
 /* The one-time matrix-core kernels as the solvers call them (Linalg::cross_prod_lower / tcross_prod_lower,
