@@ -626,6 +626,63 @@ class ADMM_Huber(ADMM_LAD):
         return fit
 
 
+class ADMM_Logit_fit:
+    def __init__(self, beta, niter, stats):
+        self.beta = beta            # numeric p + 1, intercept first
+        self.niter = niter          # maxit + 1: not converged (separable labels end there)
+        self.stats = stats
+
+    def __repr__(self):
+        return f"ADMM logistic regression fitting result\n\n$beta\n{self.beta}\n\n$niter\n{self.niter}"
+
+    def show(self):
+        print(repr(self))
+
+
+class ADMM_Logit(ADMM_LAD):
+    """Logistic regression on LAD's loop (admm_hip_logit): y holds labels, every one exactly 0 or 1, both classes present.  The
+    intercept is fitted as ADMM_QuantReg's, so nrow(x) must exceed ncol(x) + intercept.  Labels behind a DevicePtr are checked by the
+    library."""
+
+    def __init__(self, x, y, intercept=True, n=None, p=None):
+        n_, p_ = _shape(x, n, p)
+        if n_ <= p_ + (1 if intercept else 0):
+            _stop("nrow(x) must be greater than ncol(x) + 1 (the intercept is fitted)" if intercept else "nrow(x) must be greater than ncol(x)")
+        if not isinstance(y, DevicePtr):
+            y = np.ascontiguousarray(np.asarray(y, dtype=np.float64).ravel())
+        ADMM_LAD.__init__(self, x, y, intercept, n, p)
+        if not isinstance(y, DevicePtr):
+            if not np.all((y == 0.0) | (y == 1.0)):
+                _stop("every label in y must be exactly 0 or 1")
+            if np.all(y == 0.0) or np.all(y == 1.0):
+                _stop("y must hold both classes")
+
+    def fit(self, trace=False, state=0):
+        """-> ADMM_Logit_fit.  trace / state as ADMM_LAD.fit (admm_hip_logit_state): record 0 of the iterate dump carries the zero response
+        in its x slot and the signs 2 y - 1 in its z slot."""
+        lib = _lib.load()
+        xp, xmem, xk = as_input(self.x)
+        yp, ymem, yk = as_input(self.y)
+        if xmem != ymem:
+            _stop("x and y must live in the same memory space")
+        o = AdmmOpts(self.maxit, self.eps_abs, self.eps_rel, self.rho)
+        beta = np.zeros(self.p + 1, dtype=np.float64)
+        niter = np.zeros(1, dtype=np.int32)
+        stats = AdmmStats()
+        bp, np_ = beta.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), niter.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+        if trace:
+            tr, ntr = _trace_buffers(self.maxit)
+            sbuf, nst = _state_buffers(state, self.n)
+            check(lib.admm_hip_logit_state(xp, yp, self.n, self.p, xmem, int(self.intercept), ctypes.byref(o), bp, np_, ctypes.byref(stats),
+                                           *_trace_args(tr, ntr), *_state_args(sbuf, nst)))
+        else:
+            check(lib.admm_hip_logit(xp, yp, self.n, self.p, xmem, int(self.intercept), ctypes.byref(o), bp, np_, ctypes.byref(stats)))
+        fit = ADMM_Logit_fit(beta, int(niter[0]), stats.as_dict())
+        fit.trace = tr[:ntr.value].copy() if trace else None
+        fit.state = sbuf[:nst.value].copy() if (trace and state) else None
+        return fit
+
+
 class LassoPlan:
     """Prepared problem (admm_hip_lasso_plan_*): setup once, run the lambda path repeatedly.
 
@@ -736,6 +793,10 @@ def admm_quantreg(x, y, tau=0.5, intercept=True, **kw):
 
 def admm_huber(x, y, delta=1.345, tau=0.5, intercept=True, **kw):
     return ADMM_Huber(x, y, delta, tau, intercept, **kw)
+
+
+def admm_logit(x, y, intercept=True, **kw):
+    return ADMM_Logit(x, y, intercept, **kw)
 
 
 def admm_bp(x, y, **kw):

@@ -143,6 +143,19 @@ int admm_hip_huber_state(const double* x, const double* y, int n, int p, int mem
     });
 }
 
+int admm_hip_logit(const double* x, const double* y, int n, int p, int mem, int intercept, const admm_opts* opts, double* beta_out, int* niter_out,
+                   admm_stats* stats) {
+    return guarded([&] { logit(x, y, n, p, mem, intercept, opts, DenseOut{beta_out, niter_out, stats}); });
+}
+
+int admm_hip_logit_state(const double* x, const double* y, int n, int p, int mem, int intercept, const admm_opts* opts, double* beta_out, int* niter_out,
+                         admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out, double* state_out, long long state_cap,
+                         long long* nstate_out) {
+    return guarded([&] {
+        logit(x, y, n, p, mem, intercept, opts, DenseOut{beta_out, niter_out, stats, {trace_out, trace_cap, ntrace_out}, {state_out, state_cap, nstate_out}});
+    });
+}
+
 int admm_hip_quantreg_state(const double* x, const double* y, int n, int p, int mem, int intercept, double tau, const admm_opts* opts,
                             double* beta_out, int* niter_out, admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out,
                             double* state_out, long long state_cap, long long* nstate_out) {
@@ -657,6 +670,14 @@ int admm_hip_test_tall_early_exits(long long* count) {
     return guarded([&] {
         ADMM_REQUIRE(count != nullptr, "bad arguments");
         *count = tall_last_early_exits();
+    });
+}
+
+int admm_hip_test_logit_prox(const double* v, long long m, double t, double* out) {
+    return guarded([&] {
+        ADMM_REQUIRE(v && out && m > 0 && t > 0.0 && std::isfinite(t), "logit prox hook: v and out must not be NULL, m > 0, t positive and finite");
+        require_device();
+        test_logit_prox(v, m, t, out);
     });
 }
 

@@ -60,6 +60,8 @@ void quantreg(const double* x, const double* y, int n, int p, int mem, int inter
 // tau = NULL: 0.5 for every fit; out as quantreg's with nfit columns
 void huber(const double* x, const double* y, int n, int p, int mem, int intercept, const double* delta, const double* tau, int nfit, const admm_opts* opts,
            const DenseOut& out);
+// y: labels, exactly 0.0 or 1.0, both present; out.beta_out: p + 1, out.niter_out: 1
+void logit(const double* x, const double* y, int n, int p, int mem, int intercept, const admm_opts* opts, const DenseOut& out);
 void bp(const double* x, const double* y, int n, int p, int mem, const admm_opts* opts, const DenseOut& out);
 // admm_hip_parbp(_traced): over in-process ranks when PAR_DEVICES lists several devices; parbp_dist: this rank's columns of p_total
 void parbp(const double* x, const double* y, int n, int p, int mem, int nthread, const admm_opts* opts, const DenseOut& out);

@@ -336,6 +336,39 @@ void huber(const double* x, const double* y, int n, int p, int mem, int intercep
                  [&](DeviceData<double>& d, bool icpt, QuantResult& res, hipStream_t st) { solve_huber(d, icpt, *opts, delta, t.data(), nfit, res, st); }, out);
 }
 
+// admm_hip_logit: logistic regression on the LAD loop (solve_logit).  The shape rule of the fitted intercept and LAD's standardisation
+// of x (always); y holds labels, exactly 0.0 or 1.0 with both classes present -- host labels are checked here, device labels by one
+// reduction kernel, without a copy to the host.  The signs come from the caller's y, not from the standardised one.
+void logit(const double* x, const double* y, int n, int p, int mem, int intercept, const admm_opts* opts, const DenseOut& out) {
+    const bool icpt = intercept != 0;
+    check_dense(x, y, n, p, mem, opts, (long long)n > (long long)p + (icpt ? 1 : 0),
+                icpt ? "nrow(x) must be greater than ncol(x) + 1 (the intercept is fitted)" : "nrow(x) must be greater than ncol(x)", true, out);
+    long long bad = 0, ones = 0;
+    if (mem == ADMM_MEM_HOST) {
+        for (int i = 0; i < n; ++i) { if (y[i] == 1.0) ++ones; else if (!(y[i] == 0.0)) ++bad; }
+    } else {
+        require_device();
+        Stream cs;
+        logit_count_labels(y, n, &bad, &ones, cs.s);
+    }
+    ADMM_REQUIRE(bad == 0, "every label in y must be exactly 0 or 1");
+    ADMM_REQUIRE(ones > 0 && ones < n, "y must hold both classes");
+    require_device();
+    const double t0 = now_s();
+    Stream st;
+    DeviceData<double> d;
+    upload_standardize<double>(d, x, y, n, p, mem, true, icpt, st.s);
+    Resident labels(y, (size_t)n, mem);
+    DenseResult res;
+    begin_result(res, d, out.trace);
+    res.state_cap = out.state.cap;
+    solve_logit(d, icpt, labels.p, *opts, res, st.s);
+    for (int i = 0; i < p + 1; ++i) out.beta_out[i] = res.beta[i];
+    out.niter_out[0] = res.niter;
+    store_state(res, out.state);
+    finish_result(res, t0, out.trace, out.stats);
+}
+
 void bp(const double* x, const double* y, int n, int p, int mem, const admm_opts* opts, const DenseOut& out) {
     run_dense(x, y, n, p, mem, opts, false, false,                                   // BP.cpp:24-27: no standardisation
               p > n, "ncol(x) must be greater than nrow(x)", true, p,                // R/10_admm_bp.R:30-31

@@ -15,6 +15,7 @@
 #include "gemv_kernels.h"
 #include "gather_kernels.h"
 #include "solvers.h"
+#include "test_hooks.h"
 #include <cstring>
 #include <cstdio>
 #include "loop_driver.h"
@@ -91,11 +92,56 @@ __device__ __forceinline__ double huber2(double v, double hi, double lo, double 
 // in the units of the standardised response, +inf = expectile regression) as their LAST argument, behind everything the soft-threshold
 // instantiations (LAD, BP, quantile regression) read: those neither hold nor load it and keep their registers and instruction counts
 // (profiles/huber_loss.md).
-constexpr int kProxSoft = 0, kProxHuber = 1;
+constexpr int kProxSoft = 0, kProxHuber = 1, kProxLogit = 2;
+// The prox of g(z) = log(1 + e^-z) / rho (admm_hip_logit: the binomial negative log-likelihood on the sign-folded matrix), t = 1 / rho:
+// the root of h(z) = z - v - t sigma(-z), sigma(-z) = 1 / (1 + e^z), by Newton's iteration.  h is increasing, 1 <= h' <= 1 + t / 4, convex
+// left of zero and concave right of it, the root lies in [v, v + t]; from the start below (v when v > 0, v + t when v + t < 0, else 0)
+// the double iteration approaches it from one side, every step clamped to the bracket.  sigma(-z) is formed from e = exp(-|z|) -- e / (1 + e)
+// for z >= 0, 1 / (1 + e) below -- so nothing overflows for any finite v.  Every operation is rounded on its own: the result is ONE
+// function of (v, t) wherever it is called (tail and rows kernels, test hook), whichever lanes run beside it.
+// Cost (profiles/logit_loss.md): two Newton steps in float (__expf) from the same start, inside the same clamp, seed the double
+// iteration -- at t <= 1, where the double iteration alone takes five steps, about three are left.  It stops on the step,
+// |z_new - z| <= 2^-50 max(1, |z|, |v|) (h is evaluated to a few ulp of max(|z|, |v|): t sigma = z - v at the root), under a cap of
+// kLogitMaxSteps.  The steps before the quadratic phase grow like ln t -- without the seed 10 at t = 1e3, 12 at 1e4, 16 at 1e6, 29 at
+// 1e12 (tests/logit_oracle.py's prox) --, which the cap leaves room for: no rho the loop's adaptation can reach is refused.  |v| or t
+// beyond 1e30 skip the float seed (it would overflow).
+constexpr int kLogitMaxSteps = 64;
+__device__ __forceinline__ double logit2(double v, double t) {
+#pragma clang fp contract(off)
+    const double hi = v + t;
+    double z = v > 0.0 ? v : (hi < 0.0 ? hi : 0.0);
+    if (fabs(v) < 1e30 && t < 1e30) {
+        const float vf = (float)v, tf = (float)t, hf = vf + tf;
+        float zf = (float)z;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const float e = __expf(-fabsf(zf));
+            const float s = (zf >= 0.f ? e : 1.f) / (1.f + e);
+            const float h = zf - vf - tf * s, d = 1.f + tf * s * (1.f - s);
+            zf = fminf(fmaxf(zf - h / d, vf), hf);
+        }
+        z = fmin(fmax((double)zf, v), hi);
+    }
+    for (int k = 0; k < kLogitMaxSteps; ++k) {
+        const double e = exp(-fabs(z));
+        const double s = (z >= 0.0 ? e : 1.0) / (1.0 + e);
+        const double h = z - v - t * s, d = 1.0 + t * s * (1.0 - s);
+        const double zn = fmin(fmax(z - h / d, v), hi);
+        const double moved = fabs(zn - z);
+        z = zn;
+        if (moved <= 0x1p-50 * fmax(1.0, fmax(fabs(z), fabs(v)))) break;
+    }
+    return z;
+}
 template <int PROX>
 __device__ __forceinline__ double prox2(double v, double hi, double lo, double delta) {
+    if (PROX == kProxLogit) return logit2(v, hi);      // hi = c_hi / rho with c_hi = 1: t
     if (PROX == kProxHuber) return huber2(v, hi, lo, delta);
     return soft2(v, hi, lo);
+}
+// lane l's double in every lane (l uniform): two scalar reads
+__device__ __forceinline__ double read_lane_f64(double v, int l) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
 }
 
 // The six squared norms of the previous iteration: the tail's (rows launch's) partials summed in workgroup order.  pstage: nwg_tail * 8 doubles.
@@ -420,11 +466,12 @@ template <int NPT, bool LANE_NORMS, int PROX>
 __device__ __forceinline__ void lad_row_step(int i, int tid, double x, double dv, const LadRowIn& in, double rho, double pen_hi, double pen_lo, double delta,
                                              double* __restrict__ xo, double* __restrict__ zn_, double* __restrict__ yn_,
                                              double* state, long long state_cap, int total, int dim,
-                                             double* nacc, const double2 (&rv)[NPT], double2 (&az)[NPT], double2 (&ay)[NPT]) {
+                                             double* nacc, const double2 (&rv)[NPT], double2 (&az)[NPT], double2 (&ay)[NPT], double zlogit = 0.0) {
     double zn, yn;
     {
 #pragma clang fp contract(off)
-        zn = prox2<PROX>(x - dv + in.ajy / rho, pen_hi, pen_lo, delta);      // dense_tail_kernel, prob 0 (ADMMLAD.h:94-107)
+        if (PROX == kProxLogit) zn = zlogit;                                 // formed once per row by lad_rows_kernel's logit group, not in every thread
+        else zn = prox2<PROX>(x - dv + in.ajy / rho, pen_hi, pen_lo, delta); // dense_tail_kernel, prob 0 (ADMMLAD.h:94-107)
         const double rr = x - dv - zn;
         yn = in.ajy + rho * rr;
         if (LANE_NORMS && tid < 6) {
@@ -490,7 +537,48 @@ lad_rows_kernel(DenseParams q, int par, const double* __restrict__ Xt, long long
     double nacc[6] = {0, 0, 0, 0, 0, 0};
     double2 ra[R][NPT], rb[R][NPT];
     int buf = 0;
+    // kProxLogit.  The Newton prox is not formed in every thread (hundreds of double instructions a row against 8 NPT multiply-adds):
+    // lane r of each wave forms row r's -- R proxes in the time of one -- and all lanes read it from there (two scalar reads, no
+    // barrier).  To leave its registers free the four vectors' entries travel through LDS as in quant_rows_kernel: thread t < 4 R
+    // requests ONE of them before the reduction.  x of a row is summed in the same order by the lane that forms the prox and by
+    // lad_row_step's callers, and the prox's argument is lad_row_step's expression.  Rows beyond the run (clamped loads: finite) are
+    // formed and dropped.
+    __shared__ double uni[2][4 * R];           // d | adj_y | adj_z | z of the R rows (unreferenced, so not allocated, in the other instantiations)
+    auto group_logit = [&](int i0, const double2 (&rv)[R][NPT]) {
+        double uval = 0.0;
+        if (tid < 4 * R) {
+            const int kind = tid / R, i = min(i0 + tid % R, q.dim - 1);
+            const double* src = kind == 0 ? q.data_vec : (kind == 1 ? q.adj_y : (kind == 2 ? q.adj_z : zc_));
+            uval = src[i];
+        }
+        const double tot = lad_rows_dot<R, NPT>(rv, sv, lane);
+        if ((lane & 7) == 0 && (lane >> 3) < R) wsum[buf][wid][lane >> 3] = tot;
+        if (tid < 4 * R) uni[buf][tid] = uval;
+        __syncthreads();
+        double zl = 0.0;
+        if (lane < R) {
+#pragma clang fp contract(off)
+            double x = wsum[buf][0][lane];
+#pragma unroll
+            for (int w = 1; w < NWV; ++w) x += wsum[buf][w][lane];
+            zl = prox2<PROX>(x - uni[buf][lane] + uni[buf][R + lane] / rho, pen_hi, pen_lo, delta);
+        }
+#pragma unroll
+        for (int r = 0; r < R; ++r) {
+            const int i = i0 + r;
+            if (i >= row_hi) break;                                  // uniform
+            double x = wsum[buf][0][r];
+#pragma unroll
+            for (int w = 1; w < NWV; ++w) x += wsum[buf][w][r];
+            LadRowIn in;
+            in.ajy = uni[buf][R + r]; in.ajz = uni[buf][2 * R + r]; in.zc = uni[buf][3 * R + r];
+            lad_row_step<NPT, false, PROX>(i, tid, x, uni[buf][r], in, rho, pen_hi, pen_lo, delta, q.x, zn_, yn_, q.state, q.state_cap, c.total, q.dim, nacc, rv[r], az, ay,
+                                           read_lane_f64(zl, r));
+        }
+        buf ^= 1;
+    };
     auto group = [&](int i0, const double2 (&rv)[R][NPT]) {
+        if (PROX == kProxLogit) { group_logit(i0, rv); return; }
         // the four vectors' entries of the R rows (the same addresses in every lane), requested before the reduction
         double dv[R];
         LadRowIn in[R];
@@ -748,6 +836,7 @@ struct DenseLoop {
     }
     void tail(long long g, hipStream_t st) {
         if (prox == kProxHuber) hipLaunchKernelGGL(dense_tail_kernel<kProxHuber>, dim3(q.nwg_tail), dim3(kDenseThreads), 0, st, q, (int)(g & 1), delta);
+        else if (prox == kProxLogit) hipLaunchKernelGGL(dense_tail_kernel<kProxLogit>, dim3(q.nwg_tail), dim3(kDenseThreads), 0, st, q, (int)(g & 1), 0.0);
         else hipLaunchKernelGGL(dense_tail_kernel<kProxSoft>, dim3(q.nwg_tail), dim3(kDenseThreads), 0, st, q, (int)(g & 1), 0.0);
     }
     DenseCtl final_ctl(hipStream_t st) {
@@ -791,6 +880,7 @@ inline int huber_max_slots(int npt) { return npt <= 3 ? 4 : (npt <= 5 ? 2 : 1); 
 struct LadProx {
     int kind = kProxSoft;
     double c_hi = 1.0, c_lo = 1.0, delta = 0.0;
+    const double* signs = nullptr;             // kProxLogit: the n label signs folded into the matrix (device), for the iterate dump
 };
 inline int prox_max_slots(int kind, int npt) { return kind == kProxHuber ? huber_max_slots(npt) : quant_max_slots(npt); }
 
@@ -901,6 +991,8 @@ struct LadProblem {
             ADMM_HIP_CHECK(hipMemcpyAsync(L.state.get() + n, &px.delta, sizeof(double), hipMemcpyHostToDevice, st));
             ADMM_HIP_CHECK(hipStreamSynchronize(st));
         }
+        if (px.kind == kProxLogit && res.state_cap > 0)         // the same for the logistic fit: the n signs the loop ran with fill record 0's z slot
+            ADMM_HIP_CHECK(hipMemcpyAsync(L.state.get() + n, px.signs, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
         if (hat) { L.q.gout = gH.part.get(); L.q.gout_nseg = gH.pl.nseg; L.q.gout_stride = gH.stride; }
         else if (!onepass) { L.q.gout = g3.part.get(); L.q.gout_nseg = g3.pl.nseg; L.q.gout_stride = g3.stride; }
         DevBuf<double> Xz0, Xz1, Xy0, Xy1, uvec, cpart;
@@ -913,20 +1005,26 @@ struct LadProblem {
         auto launch_rows = [&](long long g) {
             const int par = (int)(g & 1);
 #define ADMM_LAD_ROWS(N, PX) hipLaunchKernelGGL((lad_rows_kernel<N, PX>), dim3(lad_nwg), dim3(kLadThreads), 0, st, L.q, par, Xt.get(), ldxt, g2.part.get(), g2.pl.nseg, g2.stride, cpart.get(), lad_rows, px.delta)
-            switch (lad_npt(ldxt) * 2 + (px.kind == kProxHuber ? 1 : 0)) {
-                case 2: ADMM_LAD_ROWS(1, kProxSoft); break;
-                case 3: ADMM_LAD_ROWS(1, kProxHuber); break;
-                case 4: ADMM_LAD_ROWS(2, kProxSoft); break;
-                case 5: ADMM_LAD_ROWS(2, kProxHuber); break;
-                case 6: ADMM_LAD_ROWS(3, kProxSoft); break;
-                case 7: ADMM_LAD_ROWS(3, kProxHuber); break;
-                case 8: ADMM_LAD_ROWS(4, kProxSoft); break;
-                case 9: ADMM_LAD_ROWS(4, kProxHuber); break;
-                case 10: ADMM_LAD_ROWS(5, kProxSoft); break;
-                case 11: ADMM_LAD_ROWS(5, kProxHuber); break;
-                default:
-                    if (px.kind == kProxHuber) ADMM_LAD_ROWS(6, kProxHuber); else ADMM_LAD_ROWS(6, kProxSoft);
-                    break;
+            switch (std::min(lad_npt(ldxt), 6) * 4 + px.kind) {
+                case 4: ADMM_LAD_ROWS(1, kProxSoft); break;
+                case 5: ADMM_LAD_ROWS(1, kProxHuber); break;
+                case 6: ADMM_LAD_ROWS(1, kProxLogit); break;
+                case 8: ADMM_LAD_ROWS(2, kProxSoft); break;
+                case 9: ADMM_LAD_ROWS(2, kProxHuber); break;
+                case 10: ADMM_LAD_ROWS(2, kProxLogit); break;
+                case 12: ADMM_LAD_ROWS(3, kProxSoft); break;
+                case 13: ADMM_LAD_ROWS(3, kProxHuber); break;
+                case 14: ADMM_LAD_ROWS(3, kProxLogit); break;
+                case 16: ADMM_LAD_ROWS(4, kProxSoft); break;
+                case 17: ADMM_LAD_ROWS(4, kProxHuber); break;
+                case 18: ADMM_LAD_ROWS(4, kProxLogit); break;
+                case 20: ADMM_LAD_ROWS(5, kProxSoft); break;
+                case 21: ADMM_LAD_ROWS(5, kProxHuber); break;
+                case 22: ADMM_LAD_ROWS(5, kProxLogit); break;
+                case 24: ADMM_LAD_ROWS(6, kProxSoft); break;
+                case 25: ADMM_LAD_ROWS(6, kProxHuber); break;
+                case 26: ADMM_LAD_ROWS(6, kProxLogit); break;
+                default: throw Error(ADMM_ERR_INTERNAL, "one-pass loop: no rows kernel for this prox");
             }
 #undef ADMM_LAD_ROWS
         };
@@ -1087,6 +1185,16 @@ __global__ void __launch_bounds__(256) ones_column_kernel(double* col, int n, lo
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i < ld) col[i] = i < n ? 1.0 : 0.0;
 }
+// X | 1: the fitted intercept's column behind the standardised matrix; d.p counts it from here on
+static void append_ones_column(DeviceData<double>& d, hipStream_t st) {
+    const int p0 = d.p;
+    DevBuf<double> X1((size_t)d.ldx * (p0 + 1));
+    ADMM_HIP_CHECK(hipMemcpyAsync(X1.get(), d.X.get(), (size_t)d.ldx * p0 * sizeof(double), hipMemcpyDeviceToDevice, st));
+    hipLaunchKernelGGL(ones_column_kernel, dim3((unsigned)((d.ldx + 255) / 256)), dim3(256), 0, st, X1.get() + (size_t)d.ldx * p0, d.n, d.ldx);
+    ADMM_HIP_CHECK(hipStreamSynchronize(st));
+    d.X = std::move(X1);
+    d.p = p0 + 1;
+}
 
 // d: the standardised data (DataStd flag 3 with the intercept, 1 without); with the intercept the loop fits one more column of ones.
 // fits: the grid in the units of the standardised response, all of one prox kind.  What admm_hip_quantreg and admm_hip_huber share:
@@ -1094,14 +1202,7 @@ __global__ void __launch_bounds__(256) ones_column_kernel(double* col, int n, lo
 static void solve_lad_grid(DeviceData<double>& d, bool intercept, const admm_opts& opts, const std::vector<LadProx>& fits, QuantResult& res, hipStream_t st) {
     const int ntau = (int)fits.size();
     const int n = d.n, p0 = d.p;
-    if (intercept) {                                             // X | 1
-        DevBuf<double> X1((size_t)d.ldx * (p0 + 1));
-        ADMM_HIP_CHECK(hipMemcpyAsync(X1.get(), d.X.get(), (size_t)d.ldx * p0 * sizeof(double), hipMemcpyDeviceToDevice, st));
-        hipLaunchKernelGGL(ones_column_kernel, dim3((unsigned)((d.ldx + 255) / 256)), dim3(256), 0, st, X1.get() + (size_t)d.ldx * p0, n, d.ldx);
-        ADMM_HIP_CHECK(hipStreamSynchronize(st));
-        d.X = std::move(X1);
-        d.p = p0 + 1;
-    }
+    if (intercept) append_ones_column(d, st);
     const int p = d.p;
     DenseResult& dr = res.dense;
     LadProblem P(d, opts, st);
@@ -1156,6 +1257,83 @@ void solve_huber(DeviceData<double>& d, bool intercept, const admm_opts& opts, c
         fits[k].delta = delta[k] / d.scaleY;
     }
     solve_lad_grid(d, intercept, opts, fits, res, st);
+}
+
+// ---------------------------------------------------------------------------------------------- logistic regression
+// counts[0]: labels that are neither 0.0 nor 1.0 (NaN included); counts[1]: the ones
+__global__ void __launch_bounds__(256) logit_count_labels_kernel(const double* __restrict__ y, int n, unsigned long long* counts) {
+    unsigned bad = 0, ones = 0;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
+        const double v = y[i];
+        if (v == 1.0) ++ones;
+        else if (!(v == 0.0)) ++bad;
+    }
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) { bad += __shfl_xor(bad, m, 64); ones += __shfl_xor(ones, m, 64); }
+    if ((threadIdx.x & 63) == 0) {
+        if (bad) atomicAdd(&counts[0], (unsigned long long)bad);
+        if (ones) atomicAdd(&counts[1], (unsigned long long)ones);
+    }
+}
+void logit_count_labels(const double* y_dev, int n, long long* bad, long long* ones, hipStream_t st) {
+    DevBuf<unsigned long long> c(2);
+    c.zero(st);
+    hipLaunchKernelGGL(logit_count_labels_kernel, dim3(std::max(1, std::min(1024, (n + 255) / 256))), dim3(256), 0, st, y_dev, n, c.get());
+    unsigned long long h[2];
+    read_back(h, c.get(), sizeof(h), st);
+    *bad = (long long)h[0]; *ones = (long long)h[1];
+}
+// s_i = 2 y_i - 1, and row i of the column-major X (the ones column included) times s_i
+__global__ void __launch_bounds__(256) logit_signs_kernel(const double* __restrict__ y, int n, double* __restrict__ s) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < n) s[i] = y[i] == 1.0 ? 1.0 : -1.0;
+}
+__global__ void __launch_bounds__(256) logit_fold_kernel(double* __restrict__ X, long long ldx, int n, int p, const double* __restrict__ s) {
+    const long long r = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (r >= n) return;
+    const double sr = s[r];
+    for (int c = blockIdx.y; c < p; c += gridDim.y) X[(size_t)c * ldx + r] *= sr;
+}
+
+// Logistic regression: min sum log(1 + exp(-s_i (b0 + x_i'b))), s = 2 y - 1, as the LAD loop on X~ = diag(s) [X | 1] with a ZERO response
+// and the prox of log(1 + e^-z) (logit2).  X~'X~ = [X 1]'[X 1], so setup, branches, control and get_x are LAD's; the response is not a
+// scale: recovery with scaleY = 1, meanY = 0.  y_dev: the caller's labels (validated: 0.0 / 1.0, both present) on the device.
+void solve_logit(DeviceData<double>& d, bool intercept, const double* y_dev, const admm_opts& opts, DenseResult& res, hipStream_t st) {
+    const int n = d.n, p0 = d.p;
+    if (intercept) append_ones_column(d, st);
+    const int p = d.p;
+    DevBuf<double> sgn(n);
+    hipLaunchKernelGGL(logit_signs_kernel, dim3((n + 255) / 256), dim3(256), 0, st, y_dev, n, sgn.get());
+    hipLaunchKernelGGL(logit_fold_kernel, dim3((n + 255) / 256, std::min(p, 65535)), dim3(256), 0, st, d.X.get(), d.ldx, n, p, sgn.get());
+    d.Y.zero(st);
+    d.scaleY = 1.0; d.meanY = 0.0;
+    LadProblem P(d, opts, st);
+    P.setup(res.stats);
+    LadProx px;
+    px.kind = kProxLogit; px.signs = sgn.get();
+    std::vector<double> coef(p), out(p0);
+    res.niter = P.loop(px, res, coef.data());
+    d.p = p0;                                                    // (recover_coef: the user's columns)
+    double b0 = 0;
+    recover_coef<double>(d, coef.data(), &b0, out.data());
+    d.p = p;
+    if (intercept) b0 = b0 + coef[p0];
+    res.beta.assign(p0 + 1, 0.0);
+    res.beta[0] = b0;
+    for (int j = 0; j < p0; ++j) res.beta[j + 1] = out[j];
+}
+
+__global__ void __launch_bounds__(256) logit_prox_hook_kernel(const double* __restrict__ v, long long m, double t, double* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < m) out[i] = prox2<kProxLogit>(v[i], t, t, 0.0);
+}
+// test hook admm_hip_test_logit_prox: the device prox over an array (host in, host out)
+void test_logit_prox(const double* v, long long m, double t, double* out) {
+    Stream st;
+    DevBuf<double> dv((size_t)m), dz((size_t)m);
+    ADMM_HIP_CHECK(hipMemcpyAsync(dv.get(), v, (size_t)m * sizeof(double), hipMemcpyHostToDevice, st.s));
+    hipLaunchKernelGGL(logit_prox_hook_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st.s, dv.get(), m, t, dz.get());
+    read_back(out, dz.get(), (size_t)m * sizeof(double), st.s);
 }
 
 // ---------------------------------------------------------------------------------------------- BP

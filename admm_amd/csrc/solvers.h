@@ -140,6 +140,11 @@ void solve_quantreg(DeviceData<double>& d, bool intercept, const admm_opts& opts
 // units of y (the loop uses delta / scaleY), +inf = expectile regression.
 void solve_huber(DeviceData<double>& d, bool intercept, const admm_opts& opts, const double* delta, const double* tau, int nfit, QuantResult& res,
                  hipStream_t st);
+// admm_hip_logit (fadmm_dense.hip): logistic regression as LAD's loop on diag(2 y - 1) [X | 1] with a zero response and the Newton prox
+// of log(1 + e^-z).  d: the standardised data as for solve_quantreg (its Y is zeroed, its X sign-folded); y_dev: the caller's labels on
+// the device, exactly 0.0 / 1.0 with both classes present (logit_count_labels counts the offenders and the ones).  res.beta: p + 1.
+void solve_logit(DeviceData<double>& d, bool intercept, const double* y_dev, const admm_opts& opts, DenseResult& res, hipStream_t st);
+void logit_count_labels(const double* y_dev, int n, long long* bad, long long* ones, hipStream_t st);
 // admm_dantzig (dantzig.hip): the Dantzig selector path in double.  res.beta: (p + 1) x nlambda column-major, row 0 = intercept.
 struct DantzigResult {
     std::vector<double> lambda, beta;

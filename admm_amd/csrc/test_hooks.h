@@ -24,5 +24,6 @@ template <typename T> void test_gather(const T* A, int rows, int cols, const T* 
 void test_cv_fold_system(const double* x, const double* y, int n, int p, const int* fold_id, int nfolds, int fold,
                          int standardize, int intercept, float* gram, float* xy, float* mean_x, float* scale_x, float* mean_scale_y);
 long long tall_last_early_exits();      // lasso_tall.hip
+void test_logit_prox(const double* v, long long m, double t, double* out);      // fadmm_dense.hip: the device logit2 over a host array
 
 }  // namespace admm

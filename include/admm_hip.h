@@ -282,6 +282,27 @@ ADMM_HIP_API int admm_hip_huber_state(const double* x, const double* y, int n, i
                          double* beta_out, int* niter_out, admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out,
                          double* state_out, long long state_cap, long long* nstate_out);
 
+/* Logistic regression (no counterpart in the reference): minimise sum_i log(1 + exp(-s_i (b0 + x_i'b))), s_i = 2 y_i - 1, the binomial
+ * negative log-likelihood, unpenalised -- admm_hip_lad's loop on the sign-folded matrix diag(s) [x_std | 1] with a ZERO response and the
+ * prox of g(z) = sum log(1 + e^-z_i), which has no closed form: per row the root of z - v - sigma(-z) / rho by a clamped Newton
+ * iteration (float seed, double polish; within 1e-13 max(1, |v|, 1 / rho) of the exact root for 1e-3 <= rho <= 1e3, any finite v; a
+ * smaller rho only takes more steps, none is refused).  Setup, the three branches (hat matrix for n <= 2000, one pass over X to 6144
+ * columns, two passes beyond) and the control are admm_hip_lad's.  x is standardised as admm_hip_quantreg's, always, and the intercept
+ * is FITTED (ones column): n > p + intercept.
+ * y[n]: labels, every one exactly 0.0 or 1.0 (anything else, NaN included: ADMM_ERR_INVALID_ARG) and both classes present; labels in
+ * device memory are checked on the device.  One label vector per call: no grid, no slots (the folded matrix depends on the labels),
+ * no class or observation weights, no penalty on b, no multi-GPU form.
+ * beta_out[p + 1]: intercept first (0 when intercept = 0); niter_out[1] as admm_hip_lad's: a fit that has not converged within
+ * opts->maxit returns ADMM_OK with maxit + 1 and finite coefficients -- perfectly separable labels end there, the maximum-likelihood
+ * estimate does not exist.  stats->xupdate_variant: 0 (hat matrix, two passes) or 1 (one pass).
+ * _state: the decision trace and (state_cap > 0) the iterate dump, layouts as admm_hip_lad_state (dim = n); record 0 of the dump
+ * carries the zero response in its x slot and the n signs s_i the loop ran with in its z slot. */
+ADMM_HIP_API int admm_hip_logit(const double* x, const double* y, int n, int p, int mem, int intercept, const admm_opts* opts,
+                   double* beta_out, int* niter_out, admm_stats* stats);
+ADMM_HIP_API int admm_hip_logit_state(const double* x, const double* y, int n, int p, int mem, int intercept, const admm_opts* opts,
+                         double* beta_out, int* niter_out, admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out,
+                         double* state_out, long long state_cap, long long* nstate_out);
+
 /* Prepared-problem variant of the Lasso family (the "persistent context" anticipated for a
  * re-fitting caller; the R shim does not need it).  create = everything the reference does
  * before its lambda loop (copy/convert, DataStd, X'y, Gram, Spectra, factorisation:
@@ -692,6 +713,9 @@ ADMM_HIP_API int admm_hip_test_symv_f64acc(const float* A, int p, const float* v
  * streams, so the count is exact: tiles x discarded launches.  At levels 1 and 2 how many leave is a matter of timing; the results
  * depend on it at no level. */
 ADMM_HIP_API int admm_hip_test_tall_early_exits(long long* count);
+/* The device prox of admm_hip_logit alone: out[k] = the root z of z - v[k] - t / (1 + e^z), t = 1 / rho > 0, over HOST arrays of
+ * length m, by the device function the tail and rows kernels call. */
+ADMM_HIP_API int admm_hip_test_logit_prox(const double* v, long long m, double t, double* out);
 
 /* The one-time matrix-core kernels as the solvers call them (Linalg::cross_prod_lower / tcross_prod_lower,
  * BlasWrapper.h:73-154; LLT, ADMMLassoTall.h:204-205), on HOST matrices (column-major, tight leading dimensions):

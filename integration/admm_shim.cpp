@@ -247,6 +247,20 @@ BEGIN_RCPP
 END_RCPP
 }
 
+// Logistic regression (not in the reference): .Call("admm_logit", x, y, intercept, opts) with y holding labels 0 / 1
+// -> beta: p + 1, intercept first; niter = maxit + 1 when the fit has not converged (separable labels).
+RcppExport SEXP admm_logit(SEXP x_, SEXP y_, SEXP intercept_, SEXP opts_) {
+BEGIN_RCPP
+    NumericMatrix x(x_);
+    NumericVector y(y_);
+    admm_opts o = unpack_opts(opts_);
+    NumericVector beta(x.ncol() + 1);
+    int niter = 0;
+    check(admm_hip_logit(x.begin(), y.begin(), x.nrow(), x.ncol(), ADMM_MEM_HOST, as<bool>(intercept_), &o, beta.begin(), &niter, nullptr));
+    return List::create(Named("beta") = beta, Named("niter") = niter);
+END_RCPP
+}
+
 // The symbol R/50_admm_dantzig.R:38 asks for and the reference never builds (src/TODO/Dantzig.cpp:32-99): doubles throughout.
 RcppExport SEXP admm_dantzig(SEXP x_, SEXP y_, SEXP lambda_, SEXP nlambda_, SEXP lmin_ratio_, SEXP standardize_, SEXP intercept_, SEXP opts_) {
 BEGIN_RCPP
