@@ -683,6 +683,94 @@ class ADMM_Logit(ADMM_LAD):
         return fit
 
 
+class ADMM_LogitMulti_fit:
+    def __init__(self, beta, niter, stats):
+        self.beta = beta            # (p + 1) x k, column c = label column c, intercept first
+        self.niter = niter          # integer k; maxit + 1: that column has not converged
+        self.stats = stats
+
+    def __repr__(self):
+        return f"ADMM logistic regression fitting result\n\n$beta\n<{self.beta.shape[0]} x {self.beta.shape[1]}> matrix\n\n$niter\n{self.niter}"
+
+    def show(self):
+        print(repr(self))
+
+
+class ADMM_LogitMulti(ADMM_LAD):
+    """Logistic regression for the k columns of a label matrix on ONE setup (admm_hip_logit_multi): column c of the fit is
+    admm_logit(x, Y[:, c]), number for number.  Y is n x k (a vector is one column), every label exactly 0 or 1 and both classes present
+    in every column; behind a DevicePtr it is column-major, k is required and the library checks the labels."""
+
+    def __init__(self, x, Y, intercept=True, n=None, p=None, k=None):
+        n_, p_ = _shape(x, n, p)
+        if n_ <= p_ + (1 if intercept else 0):
+            _stop("nrow(x) must be greater than ncol(x) + 1 (the intercept is fitted)" if intercept else "nrow(x) must be greater than ncol(x)")
+        if isinstance(Y, DevicePtr):
+            if k is None:
+                _stop("k is required with a DevicePtr")
+            k_ = int(k)
+        else:
+            Y = np.asarray(Y, dtype=np.float64)
+            if Y.ndim == 1:
+                Y = Y[:, None]
+            if Y.ndim != 2:
+                _stop("Y must be a matrix")
+            Y = np.asfortranarray(Y)
+            k_ = Y.shape[1]
+        if k_ < 1:
+            _stop("y must have at least one column")
+        ADMM_LAD.__init__(self, x, Y, intercept, n, p)
+        self.k = k_
+        if not isinstance(Y, DevicePtr):
+            for c in range(k_):
+                col = Y[:, c]
+                if not np.all((col == 0.0) | (col == 1.0)):
+                    _stop(f"column {c} of y: every label must be exactly 0 or 1")
+                if np.all(col == 0.0) or np.all(col == 1.0):
+                    _stop(f"column {c} of y must hold both classes")
+
+    def fit(self):
+        """-> ADMM_LogitMulti_fit (there is no trace / state form)."""
+        lib = _lib.load()
+        xp, xmem, xk = as_input(self.x)
+        yp, ymem, yk = as_input(self.y)
+        if xmem != ymem:
+            _stop("x and y must live in the same memory space")
+        o = AdmmOpts(self.maxit, self.eps_abs, self.eps_rel, self.rho)
+        beta = np.zeros((self.p + 1) * self.k, dtype=np.float64)
+        niter = np.zeros(self.k, dtype=np.int32)
+        stats = AdmmStats()
+        check(lib.admm_hip_logit_multi(xp, yp, self.n, self.p, self.k, xmem, int(self.intercept), ctypes.byref(o),
+                                       beta.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), niter.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
+                                       ctypes.byref(stats)))
+        return ADMM_LogitMulti_fit(beta.reshape((self.p + 1, self.k), order="F"), niter, stats.as_dict())
+
+
+class ADMM_LogitOvR(ADMM_LogitMulti):
+    """One-vs-rest on ADMM_LogitMulti: `labels` is an integer vector with at least two distinct values; `classes` holds them sorted and
+    column c of the fit separates classes[c] from the rest.  No softmax, no calibration: k independent binary fits."""
+
+    def __init__(self, x, labels, intercept=True, n=None, p=None):
+        lab = np.asarray(labels)
+        if lab.ndim != 1:
+            _stop("labels must be a vector")
+        if not (np.issubdtype(lab.dtype, np.integer) or np.issubdtype(lab.dtype, np.bool_)):
+            if not (np.issubdtype(lab.dtype, np.floating) and np.all(np.isfinite(lab)) and np.all(lab == np.round(lab))):
+                _stop("labels must be integers")
+            lab = lab.astype(np.int64)
+        classes = np.unique(lab)
+        if classes.size < 2:
+            _stop("labels must hold at least two classes")
+        ADMM_LogitMulti.__init__(self, x, (lab[:, None] == classes[None, :]).astype(np.float64), intercept, n, p)
+        self.classes = classes
+
+    def fit(self):
+        """-> ADMM_LogitMulti_fit with `classes`."""
+        fit = ADMM_LogitMulti.fit(self)
+        fit.classes = self.classes
+        return fit
+
+
 class LassoPlan:
     """Prepared problem (admm_hip_lasso_plan_*): setup once, run the lambda path repeatedly.
 
@@ -797,6 +885,14 @@ def admm_huber(x, y, delta=1.345, tau=0.5, intercept=True, **kw):
 
 def admm_logit(x, y, intercept=True, **kw):
     return ADMM_Logit(x, y, intercept, **kw)
+
+
+def admm_logit_multi(x, Y, intercept=True, **kw):
+    return ADMM_LogitMulti(x, Y, intercept, **kw)
+
+
+def admm_logit_ovr(x, labels, intercept=True, **kw):
+    return ADMM_LogitOvR(x, labels, intercept, **kw)
 
 
 def admm_bp(x, y, **kw):

@@ -148,6 +148,11 @@ int admm_hip_logit(const double* x, const double* y, int n, int p, int mem, int 
     return guarded([&] { logit(x, y, n, p, mem, intercept, opts, DenseOut{beta_out, niter_out, stats}); });
 }
 
+int admm_hip_logit_multi(const double* x, const double* y, int n, int p, int k, int mem, int intercept, const admm_opts* opts, double* beta_out,
+                         int* niter_out, admm_stats* stats) {
+    return guarded([&] { logit_multi(x, y, n, p, k, mem, intercept, opts, DenseOut{beta_out, niter_out, stats}); });
+}
+
 int admm_hip_logit_state(const double* x, const double* y, int n, int p, int mem, int intercept, const admm_opts* opts, double* beta_out, int* niter_out,
                          admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out, double* state_out, long long state_cap,
                          long long* nstate_out) {

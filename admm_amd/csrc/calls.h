@@ -62,6 +62,8 @@ void huber(const double* x, const double* y, int n, int p, int mem, int intercep
            const DenseOut& out);
 // y: labels, exactly 0.0 or 1.0, both present; out.beta_out: p + 1, out.niter_out: 1
 void logit(const double* x, const double* y, int n, int p, int mem, int intercept, const admm_opts* opts, const DenseOut& out);
+// y: n x k labels, column-major, every column as logit's; out.beta_out: (p + 1) x k, out.niter_out: k; no trace / state
+void logit_multi(const double* x, const double* y, int n, int p, int k, int mem, int intercept, const admm_opts* opts, const DenseOut& out);
 void bp(const double* x, const double* y, int n, int p, int mem, const admm_opts* opts, const DenseOut& out);
 // admm_hip_parbp(_traced): over in-process ranks when PAR_DEVICES lists several devices; parbp_dist: this rank's columns of p_total
 void parbp(const double* x, const double* y, int n, int p, int mem, int nthread, const admm_opts* opts, const DenseOut& out);

@@ -369,6 +369,40 @@ void logit(const double* x, const double* y, int n, int p, int mem, int intercep
     finish_result(res, t0, out.trace, out.stats);
 }
 
+// admm_hip_logit_multi: k label columns on one setup (solve_logit_multi).  logit's checks, every column validated as its vector; a
+// refusal names the first offending column.  No trace / state form.
+void logit_multi(const double* x, const double* y, int n, int p, int k, int mem, int intercept, const admm_opts* opts, const DenseOut& out) {
+    const bool icpt = intercept != 0;
+    ADMM_REQUIRE(k >= 1, "y must have at least one column");
+    check_dense(x, y, n, p, mem, opts, (long long)n > (long long)p + (icpt ? 1 : 0),
+                icpt ? "nrow(x) must be greater than ncol(x) + 1 (the intercept is fitted)" : "nrow(x) must be greater than ncol(x)", true, out);
+    for (int c = 0; c < k; ++c) {
+        const double* yc = y + (size_t)c * n;
+        long long bad = 0, ones = 0;
+        if (mem == ADMM_MEM_HOST) {
+            for (int i = 0; i < n; ++i) { if (yc[i] == 1.0) ++ones; else if (!(yc[i] == 0.0)) ++bad; }
+        } else {
+            require_device();
+            Stream cs;
+            logit_count_labels(yc, n, &bad, &ones, cs.s);
+        }
+        ADMM_REQUIRE(bad == 0, "column " + std::to_string(c) + " of y: every label must be exactly 0 or 1");
+        ADMM_REQUIRE(ones > 0 && ones < n, "column " + std::to_string(c) + " of y must hold both classes");
+    }
+    require_device();
+    const double t0 = now_s();
+    Stream st;
+    DeviceData<double> d;
+    upload_standardize<double>(d, x, y, n, p, mem, true, icpt, st.s);      // (the response it standardises, column 0, is zeroed by the solver)
+    Resident labels(y, (size_t)n * k, mem);
+    QuantResult res;
+    begin_result(res.dense, d, out.trace);
+    solve_logit_multi(d, icpt, labels.p, k, *opts, res, st.s);
+    std::memcpy(out.beta_out, res.beta.data(), res.beta.size() * sizeof(double));
+    for (int c = 0; c < k; ++c) out.niter_out[c] = res.niter[c];
+    finish_result(res.dense, t0, out.trace, out.stats);
+}
+
 void bp(const double* x, const double* y, int n, int p, int mem, const admm_opts* opts, const DenseOut& out) {
     run_dense(x, y, n, p, mem, opts, false, false,                                   // BP.cpp:24-27: no standardisation
               p > n, "ncol(x) must be greater than nrow(x)", true, p,                // R/10_admm_bp.R:30-31

@@ -46,7 +46,10 @@ struct DenseParams {
     // -e / rho as well and the true B y_new = B adj_y + e + rho (w0 - e / rho - B z_new) equals the held one.  What is left per iteration
     // is (I - B B') B vec, i.e. the rounding of the factorisation, and the rounding of the elementwise updates.
     int bpn;
-    const double* w0;
+    // (w0 is BP's; sgn is the signed logit prox's, kProxLogitS: the signs of the label column the loop fits, or, in the slotted loop, the
+    // sign matrix.  A LAD-type loop has bpn = 0 and never reads w0, so the two share one word and the argument block of every kernel keeps
+    // its size and offsets.)
+    union { const double* w0; const double* sgn; };
     double *Bz0, *Bz1, *By0, *By1, *Badjy, *w;
     const double* gpart; int gngroups; long long gpstride;
     // LAD, one-pass form (round 6; lp = 0: the two-pass form).  The projection needs X'vec with vec = d - adj_y / rho + adj_z, and adj_z /
@@ -67,6 +70,7 @@ struct DenseParams {
 
 constexpr int kDenseThreads = 256;
 constexpr int kQuantAutoSlots = 1;         // what QUANT_SLOTS=0 picks on the one-pass branch (decided by scripts/bench_quantreg.py)
+constexpr int kLogitAutoSlots = 4;         // the same for admm_hip_logit_multi: as many as the layout admits (measured: scripts/bench_logit_multi.py, profiles/logit_multi.md)
 constexpr int kHuberAutoSlots = 4;         // the same for admm_hip_huber: as many as the layout admits (measured: scripts/bench_huber.py, profiles/huber_loss.md)
 
 __device__ __forceinline__ double soft2(double v, double hi, double lo) {
@@ -92,7 +96,11 @@ __device__ __forceinline__ double huber2(double v, double hi, double lo, double 
 // in the units of the standardised response, +inf = expectile regression) as their LAST argument, behind everything the soft-threshold
 // instantiations (LAD, BP, quantile regression) read: those neither hold nor load it and keep their registers and instruction counts
 // (profiles/huber_loss.md).
-constexpr int kProxSoft = 0, kProxHuber = 1, kProxLogit = 2;
+constexpr int kProxSoft = 0, kProxHuber = 1, kProxLogit = 2, kProxLogitS = 3;
+// kProxLogitS (admm_hip_logit_multi): the same loss on the UNFOLDED matrix [X | 1], the label's sign taken inside the prox --
+// prox of log(1 + e^(-s z)) / rho at v is s logit2(s v, t).  Multiplying by +-1 is exact and rounding is symmetric in sign, so every n-vector
+// of this loop is s times the folded loop's and every p-vector, norm and decision equal to it: the matrix no longer depends on the labels.
+constexpr bool prox_is_logit(int prox) { return prox == kProxLogit || prox == kProxLogitS; }
 // The prox of g(z) = log(1 + e^-z) / rho (admm_hip_logit: the binomial negative log-likelihood on the sign-folded matrix), t = 1 / rho:
 // the root of h(z) = z - v - t sigma(-z), sigma(-z) = 1 / (1 + e^z), by Newton's iteration.  h is increasing, 1 <= h' <= 1 + t / 4, convex
 // left of zero and concave right of it, the root lies in [v, v + t]; from the start below (v when v > 0, v + t when v + t < 0, else 0)
@@ -470,7 +478,7 @@ __device__ __forceinline__ void lad_row_step(int i, int tid, double x, double dv
     double zn, yn;
     {
 #pragma clang fp contract(off)
-        if (PROX == kProxLogit) zn = zlogit;                                 // formed once per row by lad_rows_kernel's logit group, not in every thread
+        if (prox_is_logit(PROX)) zn = zlogit;                                // formed once per row by the rows kernels' logit lanes, not in every thread
         else zn = prox2<PROX>(x - dv + in.ajy / rho, pen_hi, pen_lo, delta); // dense_tail_kernel, prob 0 (ADMMLAD.h:94-107)
         const double rr = x - dv - zn;
         yn = in.ajy + rho * rr;
@@ -543,12 +551,14 @@ lad_rows_kernel(DenseParams q, int par, const double* __restrict__ Xt, long long
     // requests ONE of them before the reduction.  x of a row is summed in the same order by the lane that forms the prox and by
     // lad_row_step's callers, and the prox's argument is lad_row_step's expression.  Rows beyond the run (clamped loads: finite) are
     // formed and dropped.
-    __shared__ double uni[2][4 * R];           // d | adj_y | adj_z | z of the R rows (unreferenced, so not allocated, in the other instantiations)
+    // kProxLogitS: the response is identically zero there (x - 0 = x exactly, for every x), so the rows' label signs travel in its place.
+    constexpr bool SIGNED = PROX == kProxLogitS;
+    __shared__ double uni[2][4 * R];           // d (kProxLogitS: the sign) | adj_y | adj_z | z of the R rows (unreferenced, so not allocated, in the other instantiations)
     auto group_logit = [&](int i0, const double2 (&rv)[R][NPT]) {
         double uval = 0.0;
         if (tid < 4 * R) {
             const int kind = tid / R, i = min(i0 + tid % R, q.dim - 1);
-            const double* src = kind == 0 ? q.data_vec : (kind == 1 ? q.adj_y : (kind == 2 ? q.adj_z : zc_));
+            const double* src = kind == 0 ? (SIGNED ? q.sgn : q.data_vec) : (kind == 1 ? q.adj_y : (kind == 2 ? q.adj_z : zc_));
             uval = src[i];
         }
         const double tot = lad_rows_dot<R, NPT>(rv, sv, lane);
@@ -561,7 +571,12 @@ lad_rows_kernel(DenseParams q, int par, const double* __restrict__ Xt, long long
             double x = wsum[buf][0][lane];
 #pragma unroll
             for (int w = 1; w < NWV; ++w) x += wsum[buf][w][lane];
-            zl = prox2<PROX>(x - uni[buf][lane] + uni[buf][R + lane] / rho, pen_hi, pen_lo, delta);
+            if (SIGNED) {
+                // s logit2(s v, t); the sign is read from LDS again behind the iteration, not held in registers across it
+                const double zs = logit2(uni[buf][lane] * (x + uni[buf][R + lane] / rho), pen_hi);
+                asm volatile("" ::: "memory");
+                zl = uni[buf][lane] * zs;
+            } else zl = prox2<PROX>(x - uni[buf][lane] + uni[buf][R + lane] / rho, pen_hi, pen_lo, delta);
         }
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -572,13 +587,13 @@ lad_rows_kernel(DenseParams q, int par, const double* __restrict__ Xt, long long
             for (int w = 1; w < NWV; ++w) x += wsum[buf][w][r];
             LadRowIn in;
             in.ajy = uni[buf][R + r]; in.ajz = uni[buf][2 * R + r]; in.zc = uni[buf][3 * R + r];
-            lad_row_step<NPT, false, PROX>(i, tid, x, uni[buf][r], in, rho, pen_hi, pen_lo, delta, q.x, zn_, yn_, q.state, q.state_cap, c.total, q.dim, nacc, rv[r], az, ay,
-                                           read_lane_f64(zl, r));
+            lad_row_step<NPT, false, PROX>(i, tid, x, SIGNED ? 0.0 : uni[buf][r], in, rho, pen_hi, pen_lo, delta, q.x, zn_, yn_, q.state, q.state_cap, c.total, q.dim, nacc,
+                                           rv[r], az, ay, read_lane_f64(zl, r));
         }
         buf ^= 1;
     };
     auto group = [&](int i0, const double2 (&rv)[R][NPT]) {
-        if (PROX == kProxLogit) { group_logit(i0, rv); return; }
+        if (prox_is_logit(PROX)) { group_logit(i0, rv); return; }
         // the four vectors' entries of the R rows (the same addresses in every lane), requested before the reduction
         double dv[R];
         LadRowIn in[R];
@@ -625,11 +640,19 @@ quant_rows_kernel(DenseParams q0, long long slot_stride, const double* __restric
                   const double* __restrict__ Xt, long long ld, const double* __restrict__ spart0, int snseg, long long sstride,
                   double* __restrict__ cpart0, int rows_per_wg, const double* __restrict__ dlt) {
     constexpr int R = QuantRowsR<NPT>::value, NWV = kLadThreads / 64;
-    constexpr int NU = R * (1 + 3 * S);                   // the vectors' entries a row group needs: d | per slot adj_y, adj_z, z
+    // kProxLogitS (admm_hip_logit_multi: the slots are label columns): c_hi = c_lo = 1 and no knee, so chi / clo / dlt are not read; slot
+    // s takes its rows' signs from column c.pad of the sign matrix q0.sgn (n x ncol, leading dimension n rounded up to 32) -- one more
+    // per-slot entry of uni -- and the Newton prox is formed by lane s R + r of each wave for slot s, row r (see the group below).  The
+    // shared response entry goes: the response is identically zero there and x - 0 = x exactly.
+    constexpr bool LOGIT = PROX == kProxLogitS;
+    constexpr int NV = LOGIT ? 4 : 3, NB = LOGIT ? 0 : 1;
+    constexpr int NU = R * (NB + NV * S);                 // the vectors' entries a row group needs: d | per slot adj_y, adj_z, z   (LOGIT: no d; per slot also the sign)
+    static_assert(!LOGIT || S * R <= 64, "one lane per slot and row");
     __shared__ double wsum[2][S][NWV][R];
     __shared__ double uni[2][NU];
     bool act[S];
     int cur[S];
+    int col[S];                                            // (LOGIT) the slot's label column
     double rho[S], pen_hi[S], pen_lo[S], delta[S];         // (wave-uniform: the control block and the grid arrays are read as such)
     bool any = false;
 #pragma unroll
@@ -639,12 +662,23 @@ quant_rows_kernel(DenseParams q0, long long slot_stride, const double* __restric
         cur[s] = (c.total - 1) & 1;
         rho[s] = c.rho;
         const int k = act[s] ? c.pad : 0;                                    // the slot's place in the grid of quantiles
-        pen_hi[s] = chi[k] / rho[s]; pen_lo[s] = clo[k] / rho[s];
+        if constexpr (LOGIT) { col[s] = k; pen_hi[s] = 0.0; pen_lo[s] = 0.0; }
+        else { pen_hi[s] = chi[k] / rho[s]; pen_lo[s] = clo[k] / rho[s]; }
         delta[s] = PROX == kProxHuber ? dlt[k] : 0.0;                        // the fit's knee travels with its c_hi / c_lo: by the index the head's refill hands over
     }
     if (!any) return;
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int row_lo = blockIdx.x * rows_per_wg, row_hi = min(q0.dim, row_lo + rows_per_wg);
+    // LOGIT: a prox lane needs the rho of ITS slot: through LDS (written here, read behind a group's barrier) and a mask of the live slots
+    __shared__ double srho[S];
+    unsigned live_slots = 0;
+    if constexpr (LOGIT) {
+#pragma unroll
+        for (int s = 0; s < S; ++s) {
+            if (tid == s) srho[s] = rho[s];
+            live_slots |= act[s] ? 1u << s : 0u;
+        }
+    }
     double2 sv[S][NPT], az[S][NPT], ay[S][NPT];
     double nacc[S][1];
 #pragma unroll
@@ -661,12 +695,13 @@ quant_rows_kernel(DenseParams q0, long long slot_stride, const double* __restric
         if (tid < NU) {
             const int kind = tid / R, i = min(i0 + tid % R, q0.dim - 1);
             const double* src = q0.data_vec;
-            bool live = kind == 0;
+            bool live = !LOGIT && kind == 0;
 #pragma unroll
             for (int s = 0; s < S; ++s) {
-                if (kind == 1 + 3 * s) { src = q0.adj_y + (size_t)s * slot_stride; live = act[s]; }
-                if (kind == 2 + 3 * s) { src = q0.adj_z + (size_t)s * slot_stride; live = act[s]; }
-                if (kind == 3 + 3 * s) { src = (cur[s] ? q0.z1 : q0.z0) + (size_t)s * slot_stride; live = act[s]; }
+                if (kind == NB + NV * s) { src = q0.adj_y + (size_t)s * slot_stride; live = act[s]; }
+                if (kind == NB + 1 + NV * s) { src = q0.adj_z + (size_t)s * slot_stride; live = act[s]; }
+                if (kind == NB + 2 + NV * s) { src = (cur[s] ? q0.z1 : q0.z0) + (size_t)s * slot_stride; live = act[s]; }
+                if constexpr (LOGIT) if (kind == NB + 3 + NV * s) { src = q0.sgn + (size_t)col[s] * (((size_t)q0.dim + 31) & ~(size_t)31); live = act[s]; }
             }
             if (live) uval = src[i];
         }
@@ -678,6 +713,27 @@ quant_rows_kernel(DenseParams q0, long long slot_stride, const double* __restric
         }
         if (tid < NU) uni[buf][tid] = uval;
         __syncthreads();
+        // LOGIT: lane s R + r of each wave forms the prox of slot s, row r -- the S R proxes of the group in the time of one -- and
+        // every lane reads it from there, as lad_rows_kernel's logit group does for one slot.  The lane takes its slot's rho and its
+        // entries of wsum / uni by address (a chain of selects over the per-slot registers became a table in LDS); x is summed in the order of the row loop
+        // below.  An idle slot's lanes form nothing.
+        double zl = 0.0;
+        if constexpr (LOGIT) {
+            const int ls = lane / R, lr = lane % R;
+            if (lane < S * R && (live_slots >> ls & 1u)) {
+#pragma clang fp contract(off)
+                const double rho_l = srho[ls];
+                double x = wsum[buf][ls][0][lr];
+#pragma unroll
+                for (int w = 1; w < NWV; ++w) x += wsum[buf][ls][w][lr];
+                const double v = x + uni[buf][(NB + NV * ls) * R + lr] / rho_l;
+                // s logit2(s v, t), t = c_hi / rho with c_hi = 1 as the single fit forms it; the sign is read again behind the iteration,
+                // as in lad_rows_kernel
+                const double zs = logit2(uni[buf][(NB + 3 + NV * ls) * R + lr] * v, 1.0 / rho_l);
+                asm volatile("" ::: "memory");
+                zl = uni[buf][(NB + 3 + NV * ls) * R + lr] * zs;
+            }
+        }
 #pragma unroll
         for (int s = 0; s < S; ++s) {
             if (!act[s]) continue;
@@ -691,8 +747,10 @@ quant_rows_kernel(DenseParams q0, long long slot_stride, const double* __restric
 #pragma unroll
                 for (int w = 1; w < NWV; ++w) x += wsum[buf][s][w][r];
                 LadRowIn in;
-                in.ajy = uni[buf][(1 + 3 * s) * R + r]; in.ajz = uni[buf][(2 + 3 * s) * R + r]; in.zc = uni[buf][(3 + 3 * s) * R + r];
-                lad_row_step<NPT, true, PROX>(i, tid, x, uni[buf][r], in, rho[s], pen_hi[s], pen_lo[s], delta[s], q0.x + so, zn_, yn_, nullptr, 0, 0, q0.dim, nacc[s], rv[r], az[s], ay[s]);
+                in.ajy = uni[buf][(NB + NV * s) * R + r]; in.ajz = uni[buf][(NB + 1 + NV * s) * R + r]; in.zc = uni[buf][(NB + 2 + NV * s) * R + r];
+                double zrow = 0.0;
+                if constexpr (LOGIT) zrow = read_lane_f64(zl, s * R + r);
+                lad_row_step<NPT, true, PROX>(i, tid, x, LOGIT ? 0.0 : uni[buf][r], in, rho[s], pen_hi[s], pen_lo[s], delta[s], q0.x + so, zn_, yn_, nullptr, 0, 0, q0.dim, nacc[s], rv[r], az[s], ay[s], zrow);
             }
         }
         buf ^= 1;
@@ -743,7 +801,8 @@ dense_tail_kernel(DenseParams q, int par, double knee) {
         if (q.prob == 0) {                        // LAD: x = P_X(vec); z = prox(x - y + adj_y/rho; c_hi/rho, c_lo/rho); r = x - y - z
             x = g;
             const double d = q.data_vec[i];
-            zn = prox2<PROX>(x - d + adjy / rho, pen_hi, pen_lo, delta);
+            if (PROX == kProxLogitS) { const double sg = q.sgn[i]; zn = sg * logit2(sg * (x - d + adjy / rho), pen_hi); }
+            else zn = prox2<PROX>(x - d + adjy / rho, pen_hi, pen_lo, delta);
             r = x - d - zn;
         } else {                                  // BP: x = vec + A'(AA')^-1 b - B'(B vec); z = soft(x + adj_y/rho, 1/rho); r = x - z
             x = q.vec[i] + q.data_vec[i] - g;
@@ -837,6 +896,7 @@ struct DenseLoop {
     void tail(long long g, hipStream_t st) {
         if (prox == kProxHuber) hipLaunchKernelGGL(dense_tail_kernel<kProxHuber>, dim3(q.nwg_tail), dim3(kDenseThreads), 0, st, q, (int)(g & 1), delta);
         else if (prox == kProxLogit) hipLaunchKernelGGL(dense_tail_kernel<kProxLogit>, dim3(q.nwg_tail), dim3(kDenseThreads), 0, st, q, (int)(g & 1), 0.0);
+        else if (prox == kProxLogitS) hipLaunchKernelGGL(dense_tail_kernel<kProxLogitS>, dim3(q.nwg_tail), dim3(kDenseThreads), 0, st, q, (int)(g & 1), 0.0);
         else hipLaunchKernelGGL(dense_tail_kernel<kProxSoft>, dim3(q.nwg_tail), dim3(kDenseThreads), 0, st, q, (int)(g & 1), 0.0);
     }
     DenseCtl final_ctl(hipStream_t st) {
@@ -875,14 +935,19 @@ inline int lad_npt(long long ldxt) { return (int)((ldxt / 2 + kLadThreads - 1) /
 inline int quant_max_slots(int npt) { return npt <= 3 ? 4 : (npt == 4 ? 3 : (npt == 5 ? 2 : 1)); }      // (six double2 per row: two slots would spill)
 inline int huber_max_slots(int npt) { return npt <= 3 ? 4 : (npt <= 5 ? 2 : 1); }      // the Huber instantiations without scratch: (4, 3) spills 16 bytes and fell away
 
+inline int logit_max_slots(int npt) { return npt <= 3 ? 4 : (npt == 4 ? 2 : 1); }      // the kProxLogitS instantiations without scratch: (4, 3) spills 64 bytes, (5, 2) 24 (profiles/logit_multi.md)
+
 // The separable loss of one fit, as the loop sees it: which prox, its weights above / below zero, and (Huber) the knee in the units
 // of the standardised response.  LAD: the default.
 struct LadProx {
     int kind = kProxSoft;
     double c_hi = 1.0, c_lo = 1.0, delta = 0.0;
     const double* signs = nullptr;             // kProxLogit: the n label signs folded into the matrix (device), for the iterate dump
+                                               // kProxLogitS: the signs the prox reads -- fit k's is column k of ONE matrix, leading dimension round_up(n, 32)
 };
-inline int prox_max_slots(int kind, int npt) { return kind == kProxHuber ? huber_max_slots(npt) : quant_max_slots(npt); }
+inline int prox_max_slots(int kind, int npt) {
+    return kind == kProxHuber ? huber_max_slots(npt) : (kind == kProxLogitS ? logit_max_slots(npt) : quant_max_slots(npt));
+}
 
 // Everything of a LAD-type fit that does not depend on the prox constants, formed ONCE (setup), and the loop from a cold start
 // (loop: one quantile; loop_slots: a grid, several quantiles per pass over X).  admm_hip_lad is setup + one loop with c_hi = c_lo = 1.
@@ -987,6 +1052,7 @@ struct LadProblem {
         DenseLoop L;
         L.init(n, 0, opts, d.Y.get(), ynorm, st, res.trace_cap, res.state_cap, onepass ? lad_nwg : 0);
         L.q.c_hi = px.c_hi; L.q.c_lo = px.c_lo; L.delta = px.delta; L.prox = px.kind;
+        if (px.kind == kProxLogitS) L.q.sgn = px.signs;
         if (px.kind == kProxHuber && res.state_cap > 0) {       // iterate dump: record 0 also carries the knee as the loop holds it (delta / scaleY), first entry of its z slot
             ADMM_HIP_CHECK(hipMemcpyAsync(L.state.get() + n, &px.delta, sizeof(double), hipMemcpyHostToDevice, st));
             ADMM_HIP_CHECK(hipStreamSynchronize(st));
@@ -1009,21 +1075,27 @@ struct LadProblem {
                 case 4: ADMM_LAD_ROWS(1, kProxSoft); break;
                 case 5: ADMM_LAD_ROWS(1, kProxHuber); break;
                 case 6: ADMM_LAD_ROWS(1, kProxLogit); break;
+                case 7: ADMM_LAD_ROWS(1, kProxLogitS); break;
                 case 8: ADMM_LAD_ROWS(2, kProxSoft); break;
                 case 9: ADMM_LAD_ROWS(2, kProxHuber); break;
                 case 10: ADMM_LAD_ROWS(2, kProxLogit); break;
+                case 11: ADMM_LAD_ROWS(2, kProxLogitS); break;
                 case 12: ADMM_LAD_ROWS(3, kProxSoft); break;
                 case 13: ADMM_LAD_ROWS(3, kProxHuber); break;
                 case 14: ADMM_LAD_ROWS(3, kProxLogit); break;
+                case 15: ADMM_LAD_ROWS(3, kProxLogitS); break;
                 case 16: ADMM_LAD_ROWS(4, kProxSoft); break;
                 case 17: ADMM_LAD_ROWS(4, kProxHuber); break;
                 case 18: ADMM_LAD_ROWS(4, kProxLogit); break;
+                case 19: ADMM_LAD_ROWS(4, kProxLogitS); break;
                 case 20: ADMM_LAD_ROWS(5, kProxSoft); break;
                 case 21: ADMM_LAD_ROWS(5, kProxHuber); break;
                 case 22: ADMM_LAD_ROWS(5, kProxLogit); break;
+                case 23: ADMM_LAD_ROWS(5, kProxLogitS); break;
                 case 24: ADMM_LAD_ROWS(6, kProxSoft); break;
                 case 25: ADMM_LAD_ROWS(6, kProxHuber); break;
                 case 26: ADMM_LAD_ROWS(6, kProxLogit); break;
+                case 27: ADMM_LAD_ROWS(6, kProxLogitS); break;
                 default: throw Error(ADMM_ERR_INTERNAL, "one-pass loop: no rows kernel for this prox");
             }
 #undef ADMM_LAD_ROWS
@@ -1093,6 +1165,7 @@ struct LadProblem {
         q.lp = p; q.Xd = Xd.get(); q.Xz0 = b + o_p; q.Xz1 = b + o_p + ldp; q.Xy0 = b + o_p + 2 * ldp; q.Xy1 = b + o_p + 3 * ldp; q.u = b + o_p + 4 * ldp;
         q.cpart = b + o_c; q.cnwg = lad_nwg; q.cstride = ldp;
         q.c_hi = 1.0; q.c_lo = 1.0;                              // (unused: the slots' constants are chi / clo of their quantile)
+        if (kind == kProxLogitS) q.sgn = fits[0].signs;          // the sign matrix: a slot reads the column of the fit it holds
         QuantGrid G{};
         G.nslots = nslots; G.ntau = ntau; G.slot_stride = (long long)stride; G.rho0 = opts.rho;
         G.next = ints.get() + 1; G.idle = ints.get() + 3; G.niter = ints.get() + 3 + nslots; G.rho_fin = rho_fin.get();
@@ -1116,7 +1189,7 @@ struct LadProblem {
         auto launch_rows = [&](int par) {
 #define ADMM_QUANT_ROWS(N, SS, PX) hipLaunchKernelGGL((quant_rows_kernel<N, SS, PX>), dim3(lad_nwg), dim3(kLadThreads), 0, st, q, (long long)stride, chi_d.get(), clo_d.get(), par, \
                                                       Xt.get(), ldxt, spart0, g2.pl.nseg, g2.stride, cpart0, lad_rows, (const double*)dlt_d.get())
-            switch ((kind == kProxHuber ? 100 : 0) + lad_npt(ldxt) * 10 + nslots) {
+            switch ((kind == kProxHuber ? 100 : (kind == kProxLogitS ? 200 : 0)) + lad_npt(ldxt) * 10 + nslots) {
                 case 12: ADMM_QUANT_ROWS(1, 2, kProxSoft); break;
                 case 13: ADMM_QUANT_ROWS(1, 3, kProxSoft); break;
                 case 14: ADMM_QUANT_ROWS(1, 4, kProxSoft); break;
@@ -1140,6 +1213,16 @@ struct LadProblem {
                 case 134: ADMM_QUANT_ROWS(3, 4, kProxHuber); break;
                 case 142: ADMM_QUANT_ROWS(4, 2, kProxHuber); break;
                 case 152: ADMM_QUANT_ROWS(5, 2, kProxHuber); break;
+                case 212: ADMM_QUANT_ROWS(1, 2, kProxLogitS); break;
+                case 213: ADMM_QUANT_ROWS(1, 3, kProxLogitS); break;
+                case 214: ADMM_QUANT_ROWS(1, 4, kProxLogitS); break;
+                case 222: ADMM_QUANT_ROWS(2, 2, kProxLogitS); break;
+                case 223: ADMM_QUANT_ROWS(2, 3, kProxLogitS); break;
+                case 224: ADMM_QUANT_ROWS(2, 4, kProxLogitS); break;
+                case 232: ADMM_QUANT_ROWS(3, 2, kProxLogitS); break;
+                case 233: ADMM_QUANT_ROWS(3, 3, kProxLogitS); break;
+                case 234: ADMM_QUANT_ROWS(3, 4, kProxLogitS); break;
+                case 242: ADMM_QUANT_ROWS(4, 2, kProxLogitS); break;
                 default: throw Error(ADMM_ERR_INTERNAL, "slotted grid: no rows kernel for this layout");
             }
 #undef ADMM_QUANT_ROWS
@@ -1213,7 +1296,8 @@ static void solve_lad_grid(DeviceData<double>& d, bool intercept, const admm_opt
     int slots = 1;
     if (P.onepass && dr.trace_cap == 0 && ntau >= 2) {
         const long long want = opt_int(Opt::QUANT_SLOTS, 0);
-        slots = want == 0 ? (fits[0].kind == kProxHuber ? kHuberAutoSlots : kQuantAutoSlots) : (int)want;
+        const int kind = fits[0].kind;
+        slots = want == 0 ? (kind == kProxHuber ? kHuberAutoSlots : (kind == kProxLogitS ? kLogitAutoSlots : kQuantAutoSlots)) : (int)want;
         slots = std::min(std::min(slots, prox_max_slots(fits[0].kind, lad_npt(P.ldxt))), ntau);
         if ((size_t)ntau * (size_t)n * sizeof(double) > (size_t(2) << 30)) slots = 1;
     }
@@ -1321,6 +1405,30 @@ void solve_logit(DeviceData<double>& d, bool intercept, const double* y_dev, con
     res.beta.assign(p0 + 1, 0.0);
     res.beta[0] = b0;
     for (int j = 0; j < p0; ++j) res.beta[j + 1] = out[j];
+}
+
+// column c of the n x ncol labels (leading dimension n) as signs, leading dimension lds; the padding rows zero
+__global__ void __launch_bounds__(256) logit_sign_matrix_kernel(const double* __restrict__ y, int n, int ncol, long long lds, double* __restrict__ s) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= lds) return;
+    for (int c = blockIdx.y; c < ncol; c += gridDim.y) s[(size_t)c * lds + i] = i < n ? (y[(size_t)c * n + i] == 1.0 ? 1.0 : -1.0) : 0.0;
+}
+
+// Logistic regression for ncol label columns on ONE setup (admm_hip_logit_multi).  Nothing is folded: the loop runs on [X_std | 1] with a
+// zero response and the prox takes row i's sign s_i = 2 y_i - 1 itself (kProxLogitS), so the matrix, its Gram, the inverse, the transpose
+// and the hat matrix are shared by all columns, and on the one-pass branch several columns advance on one pass over X: solve_lad_grid
+// with the signs as the grid.  Column k equals solve_logit on that column -- every n-vector is s times the folded loop's, everything else
+// identical, rounding being symmetric in sign.  y_dev: n x ncol validated labels on the device, leading dimension n.
+void solve_logit_multi(DeviceData<double>& d, bool intercept, const double* y_dev, int ncol, const admm_opts& opts, QuantResult& res, hipStream_t st) {
+    const int n = d.n;
+    const long long lds = round_up(n, 32);
+    DevBuf<double> sgn((size_t)lds * ncol);
+    hipLaunchKernelGGL(logit_sign_matrix_kernel, dim3((unsigned)((lds + 255) / 256), std::min(ncol, 65535)), dim3(256), 0, st, y_dev, n, ncol, lds, sgn.get());
+    d.Y.zero(st);
+    d.scaleY = 1.0; d.meanY = 0.0;
+    std::vector<LadProx> fits(ncol);
+    for (int k = 0; k < ncol; ++k) { fits[k].kind = kProxLogitS; fits[k].signs = sgn.get() + (size_t)k * lds; }
+    solve_lad_grid(d, intercept, opts, fits, res, st);
 }
 
 __global__ void __launch_bounds__(256) logit_prox_hook_kernel(const double* __restrict__ v, long long m, double t, double* __restrict__ out) {

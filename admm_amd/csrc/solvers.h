@@ -145,6 +145,11 @@ void solve_huber(DeviceData<double>& d, bool intercept, const admm_opts& opts, c
 // the device, exactly 0.0 / 1.0 with both classes present (logit_count_labels counts the offenders and the ones).  res.beta: p + 1.
 void solve_logit(DeviceData<double>& d, bool intercept, const double* y_dev, const admm_opts& opts, DenseResult& res, hipStream_t st);
 void logit_count_labels(const double* y_dev, int n, long long* bad, long long* ones, hipStream_t st);
+// admm_hip_logit_multi (fadmm_dense.hip): ncol label columns on ONE setup.  The matrix stays unfolded ([X | 1], zero response) and the
+// prox takes the row's sign itself, so the setup is shared and, on the one-pass branch, several columns advance per pass over X
+// (QUANT_SLOTS, as solve_huber).  y_dev: n x ncol labels on the device (leading dimension n), every column validated as solve_logit's.
+// res.beta: (p + 1) x ncol, res.niter: ncol; column k equals solve_logit on column k.
+void solve_logit_multi(DeviceData<double>& d, bool intercept, const double* y_dev, int ncol, const admm_opts& opts, QuantResult& res, hipStream_t st);
 // admm_dantzig (dantzig.hip): the Dantzig selector path in double.  res.beta: (p + 1) x nlambda column-major, row 0 = intercept.
 struct DantzigResult {
     std::vector<double> lambda, beta;

@@ -303,6 +303,23 @@ ADMM_HIP_API int admm_hip_logit_state(const double* x, const double* y, int n, i
                          double* beta_out, int* niter_out, admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out,
                          double* state_out, long long state_cap, long long* nstate_out);
 
+/* Logistic regression for k label columns of one design matrix (one-vs-rest multiclass, multi-label): column c of the result is
+ * admm_hip_logit(x, column c of y), number for number (niter and every coefficient equal; only the sign of an exact zero may differ),
+ * but the upload, the standardisation, the Gram matrix, its inverse, the transpose and the hat matrix are formed ONCE.  Nothing is
+ * folded into the matrix here: the loop runs on [x_std | 1] with a zero response and the prox takes the row's sign itself,
+ * s logit2(s v, 1 / rho) -- multiplication by +-1 is exact and rounding is symmetric in sign.  On the one-pass branch (n > 2000, up to
+ * 5120 columns with the intercept) several columns advance on one pass over the rows of x ("slots", as admm_hip_huber's): option
+ * QUANT_SLOTS, 0 = automatic (as many as the layout admits: measured), 1 = serial, 2 ... 8 = at most that many,
+ * clipped to what the shape's register layout holds (4 to 3072 columns, 2 to 4096, 1 beyond) and to k, and only while the n x k vectors stay under 2 GB.
+ * y[n * k]: column-major labels in the memory space `mem` names; every column as admm_hip_logit's y.  A refusal names the first
+ * offending column, 0-based ("column 3 of y: every label must be exactly 0 or 1", "column 3 of y must hold both classes"); k < 1:
+ * "y must have at least one column".  A refusal touches no output.
+ * beta_out[(p + 1) * k]: column-major, intercept first in each column; niter_out[k].  stats->xupdate_variant: 8 + slots on the slotted
+ * route, else 1 (one pass) or 0 (hat matrix, two passes).  There is no trace / state form.  Not offered: a softmax / multinomial
+ * likelihood, class or observation weights, any penalty on b, warm starts between columns, a multi-GPU form. */
+ADMM_HIP_API int admm_hip_logit_multi(const double* x, const double* y, int n, int p, int k, int mem, int intercept, const admm_opts* opts,
+                         double* beta_out, int* niter_out, admm_stats* stats);
+
 /* Prepared-problem variant of the Lasso family (the "persistent context" anticipated for a
  * re-fitting caller; the R shim does not need it).  create = everything the reference does
  * before its lambda loop (copy/convert, DataStd, X'y, Gram, Spectra, factorisation:

@@ -261,6 +261,21 @@ BEGIN_RCPP
 END_RCPP
 }
 
+// Logistic regression for the columns of a label matrix on one setup (not in the reference):
+// .Call("admm_logit_multi", x, Y, intercept, opts) with Y n x k holding labels 0 / 1 -> beta: (p + 1) x k, intercept first; niter: k.
+RcppExport SEXP admm_logit_multi(SEXP x_, SEXP y_, SEXP intercept_, SEXP opts_) {
+BEGIN_RCPP
+    NumericMatrix x(x_);
+    NumericMatrix y(y_);
+    if (y.nrow() != x.nrow()) Rcpp::stop("nrow(x) should be equal to nrow(Y)");
+    admm_opts o = unpack_opts(opts_);
+    NumericMatrix beta(x.ncol() + 1, y.ncol());
+    IntegerVector niter(y.ncol());
+    check(admm_hip_logit_multi(x.begin(), y.begin(), x.nrow(), x.ncol(), y.ncol(), ADMM_MEM_HOST, as<bool>(intercept_), &o, beta.begin(), niter.begin(), nullptr));
+    return List::create(Named("beta") = beta, Named("niter") = niter);
+END_RCPP
+}
+
 // The symbol R/50_admm_dantzig.R:38 asks for and the reference never builds (src/TODO/Dantzig.cpp:32-99): doubles throughout.
 RcppExport SEXP admm_dantzig(SEXP x_, SEXP y_, SEXP lambda_, SEXP nlambda_, SEXP lmin_ratio_, SEXP standardize_, SEXP intercept_, SEXP opts_) {
 BEGIN_RCPP
