@@ -81,7 +81,8 @@ EXPORTS = ["admm_hip_lasso", "admm_hip_enet", "admm_hip_parlasso", "admm_hip_lad
            "admm_hip_boxenet", "admm_hip_boxenet_plan_create", "admm_hip_host_box_lambda0",
            "admm_hip_test_gemm_nt", "admm_hip_test_cholesky_linvt", "admm_hip_test_spd_inverse_shift",
            "admm_hip_test_symv_plan", "admm_hip_test_symv_ex", "admm_hip_test_symv_multi_ex", "admm_hip_test_symv_f64acc",
-           "admm_hip_test_symv_one"]
+           "admm_hip_test_symv_one", "admm_hip_test_symv_pack_host", "admm_hip_test_symv_packed", "admm_hip_test_symv_packed_time",
+           "admm_hip_test_tall_pack_info"]
 
 GROUP_MAX = 1024          # ADMM_HIP_GROUP_MAX
 MT_MAX = 16               # ADMM_HIP_MT_MAX
@@ -270,6 +271,17 @@ def load():
     lib.admm_hip_test_symv_one.argtypes = [_c_float_p, ctypes.c_int, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint,
                                            _c_float_p, _c_float_p, _c_float_p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong), _c_int_p]
     lib.admm_hip_test_symv_one.restype = ctypes.c_int
+    _c_uint_p = ctypes.POINTER(ctypes.c_uint)
+    lib.admm_hip_test_symv_pack_host.argtypes = [_c_uint_p, ctypes.c_int, _c_int_p, _c_uint_p, _c_uint_p, ctypes.c_int,
+                                                 ctypes.POINTER(ctypes.c_longlong), _c_uint_p]
+    lib.admm_hip_test_symv_pack_host.restype = ctypes.c_int
+    lib.admm_hip_test_symv_packed.argtypes = [_c_float_p, ctypes.c_int, _c_float_p, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_uint, ctypes.c_int,
+                                              _c_float_p, _c_float_p, _c_float_p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong), _c_int_p]
+    lib.admm_hip_test_symv_packed.restype = ctypes.c_int
+    lib.admm_hip_test_symv_packed_time.argtypes = [_c_float_p, ctypes.c_int, _c_float_p, ctypes.c_int, _c_float_p, ctypes.POINTER(ctypes.c_longlong)]
+    lib.admm_hip_test_symv_packed_time.restype = ctypes.c_int
+    lib.admm_hip_test_tall_pack_info.argtypes = [ctypes.POINTER(ctypes.c_longlong)]
+    lib.admm_hip_test_tall_pack_info.restype = ctypes.c_int
     lib.admm_hip_test_symv_multi_ex.argtypes = [_c_float_p, ctypes.c_int, _c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                 _c_float_p, _c_int_p]
     lib.admm_hip_test_symv_multi_ex.restype = ctypes.c_int

@@ -654,6 +654,35 @@ int admm_hip_test_symv_one(const float* A, int p, const float* v0, const float* 
     });
 }
 
+int admm_hip_test_symv_pack_host(const unsigned int* bits, int nchunks, int* base_io, unsigned int* stream_out, unsigned int* esc_out, int esc_cap,
+                                 long long* nesc_out, unsigned int* decoded_out) {
+    return guarded([&] {
+        ADMM_REQUIRE(bits && base_io && stream_out && nesc_out && decoded_out && (esc_out || esc_cap == 0),
+                     "symv_pack_host hook: bits, base_io, stream_out, nesc_out and decoded_out must not be NULL, esc_out only with esc_cap 0");
+        ADMM_REQUIRE(nchunks >= 1 && nchunks <= 4096 && *base_io <= 127 && esc_cap >= 0, "symv_pack_host hook: nchunks in 1 .. 4096, base <= 127, esc_cap >= 0");
+        test_symv_pack_host(bits, nchunks, base_io, stream_out, esc_out, esc_cap, nesc_out, decoded_out);
+    });
+}
+
+int admm_hip_test_symv_packed(const float* A, int p, const float* v0, const float* v1, int gate, int nt, unsigned int fill, int esc_cap, float* y,
+                              float* dot_out, float* axp_out, long long plane_capacity, long long* info_out, int* sched_out) {
+    return guarded([&] {
+        ADMM_REQUIRE(A && v0 && v1 && y && info_out && sched_out, "symv_packed hook: A, v0, v1, y, info_out and sched_out must not be NULL");
+        ADMM_REQUIRE((dot_out == nullptr) == (axp_out == nullptr), "symv_packed hook: dot_out and axp_out are given together or not at all");
+        ADMM_REQUIRE(p >= 1 && p <= kSymvHookMaxP && gate >= 0 && gate <= 2 && (nt == 0 || nt == 1) && esc_cap >= 0 && esc_cap <= 4096 && plane_capacity >= 0,
+                     "symv_packed hook: p in 1 .. 32768, gate in 0 .. 2, nt 0 or 1, esc_cap in 0 .. 4096, plane_capacity >= 0");
+        test_symv_packed(A, p, v0, v1, gate, nt, fill, esc_cap, y, dot_out, axp_out, plane_capacity, info_out, sched_out);
+    });
+}
+
+int admm_hip_test_symv_packed_time(const float* A, int p, const float* v0, int reps, float* us_out, long long* info_out) {
+    return guarded([&] {
+        ADMM_REQUIRE(A && v0 && us_out && info_out, "symv_packed_time hook: A, v0, us_out and info_out must not be NULL");
+        ADMM_REQUIRE(p >= 1 && p <= kSymvHookMaxP && reps >= 2 && reps <= 1000 && reps % 2 == 0, "symv_packed_time hook: p in 1 .. 32768, reps even, 2 .. 1000");
+        test_symv_packed_time(A, p, v0, reps, us_out, info_out);
+    });
+}
+
 int admm_hip_test_symv_multi_ex(const float* A, int p, const float* V, int nr, int rhs_per_pass, int nt, int finish, float* Yout, int* sched_out) {
     return guarded([&] {
         ADMM_REQUIRE(A && V && Yout && sched_out, "symv_multi_ex hook: A, V, Yout and sched_out must not be NULL");
@@ -675,6 +704,13 @@ int admm_hip_test_tall_early_exits(long long* count) {
     return guarded([&] {
         ADMM_REQUIRE(count != nullptr, "bad arguments");
         *count = tall_last_early_exits();
+    });
+}
+
+int admm_hip_test_tall_pack_info(long long* info_out) {
+    return guarded([&] {
+        ADMM_REQUIRE(info_out != nullptr, "bad arguments");
+        tall_last_pack_info(info_out);
     });
 }
 

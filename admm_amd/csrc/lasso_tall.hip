@@ -920,6 +920,10 @@ __global__ void tall_init_kernel(TallParams q, double rho, double lam0) {
 // Tiles of the x-update that left early in the calling thread's most recent tall path (test hook admm_hip_test_tall_early_exits).
 static thread_local long long t_early_exits = 0;
 long long tall_last_early_exits() { return t_early_exits; }
+// The calling thread's most recent tall plan: 1 if its x-update streams the 29-bit copy, escapes met while packing, tiles whose escape list
+// overflowed, bytes of the copy (all 0 where no copy was attempted).
+static thread_local long long t_pack_info[4] = {0, 0, 0, 0};
+void tall_last_pack_info(long long* out) { for (int k = 0; k < 4; ++k) out[k] = t_pack_info[k]; }
 
 // ----------------------------------------------------------------------------------------------
 struct TallPlan final : LassoPlan {
@@ -949,6 +953,8 @@ struct TallPlan final : LassoPlan {
     DevBuf<unsigned long long> verdict;                 // early exit of discarded x-update launches (symv_kernels.h: SymvVerdict): the words + the counter
     bool verdict_on = false, verdict_mid = false;
     bool decide_first = false;                          // SYMV_VERDICT=3 (default): every tile takes the decision itself and multiplies one vector (symv1_lower_kernel, TAIL_SYMV1)
+    SymvPacked pk;                                      // SYMV_PACK=1 (default): the exact 29-bit copy of the tiles the decide-first x-update streams (symv_pack.h)
+    bool packed = false;                                // ... is in use (false: the fp32 stream -- option off, no memory for the copy, or a tile's escape list overflowed)
     unsigned long long run_no = 0;                      // run() calls of this plan: part of the verdict word
     TallParams q{};
     // mixed-precision refinement of the x-update (ADMM_HIP_REFINE=1)
@@ -1240,6 +1246,24 @@ struct TallPlan final : LassoPlan {
             q.verdict = decide_first ? nullptr : verdict.get();      // decide-first: nobody reads a word, block 0 publishes none
             q.early = verdict.get() + kVerdictWords;
         }
+        // The decide-first x-update streams an exact 29-bit copy of the inverse's tiles (symv1_packed_kernel: 29/32 of the bytes, the same 32 bits
+        // after the decode, so nothing downstream changes).  Packed once here: the inverse and the tile list are fixed for the life of the
+        // plan.  The fp32 stream stays when the option is off, the copy does not fit the device, or a tile has more entries outside its
+        // exponent window than its list holds.
+        packed = false;
+        t_pack_info[0] = t_pack_info[1] = t_pack_info[2] = t_pack_info[3] = 0;
+        if (decide_first && opt_int(Opt::SYMV_PACK, 1) != 0) {
+            size_t free_b = 0, total_b = 0;
+            ADMM_HIP_CHECK(hipMemGetInfo(&free_b, &total_b));
+            free_b += pool_cached_bytes();
+            if (opt_set(Opt::TEST_FREE_BYTES)) free_b = (size_t)opt_int(Opt::TEST_FREE_BYTES, 0);
+            if ((double)SymvPacked::bytes_for(sy) <= 0.97 * (double)free_b) {
+                packed = pk.build(sy, M.get(), ldp, st, (int)opt_int(Opt::SYMV_PACK_ESC, kSpEscCap));
+                t_pack_info[1] = (long long)pk.escapes; t_pack_info[2] = (long long)pk.overflowed; t_pack_info[3] = (long long)pk.bytes();
+                if (!packed) pk.release();
+            }
+            t_pack_info[0] = packed ? 1 : 0;
+        }
 #ifdef ADMM_HIP_PROBE
         probe.alloc((size_t)4096 * 4 * 8); probe.zero(st);
         q.probe = probe.get();
@@ -1440,7 +1464,8 @@ struct TallPlan final : LassoPlan {
             const auto xupdate = [&] {
                 if (decide_first) {
                     const TallGate gate{ctl.get() + par, P.get() + tall_norm_compact(nwg, par), nwg, q.maxit, q.nlam};
-                    sy.launch_one(M.get(), ldp, u.get(), w.get(), skip, st, gate, q.early, dec, e0, e1);
+                    if (packed) symv_launch_one_packed(sy, pk, u.get(), w.get(), skip, st, gate, q.early, dec, e0, e1);
+                    else sy.launch_one(M.get(), ldp, u.get(), w.get(), skip, st, gate, q.early, dec, e0, e1);
                 }
                 else if (use_sym) sy.launch(M.get(), ldp, u.get(), w.get(), skip, st, dec, e0, e1, vd);
                 else launch_gemv_t<float, 2, 4, TallDecideExtra>(pl, M.get(), ldp, p, p, u.get(), w.get(), a_part.get(), b_part.get(), ldp, skip, st, dec, e0, e1);

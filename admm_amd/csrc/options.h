@@ -35,6 +35,8 @@ constexpr double kPositive = std::numeric_limits<double>::min();  // Real(kPosit
     X(XUPDATE, Choice("sym|gemv|full"), "tall x-update: symmetric lower-triangle kernel / full-matrix mat-vec (gemv and full alike)")   \
     X(SYMV_SCHED, Sched(), "tall x-update: column-segment widths of the long / short row strips and the split between them")           \
     X(SYMV_VERDICT, Choice("0|1|2|3"), "tall x-update: discarded launches stream on / leave on block 0's word at start / also mid-tile / every tile decides first, one vector (default)") \
+    X(SYMV_PACK, Choice("0|1"), "tall x-update, decide-first form: stream the fp32 inverse / its exact 29-bit copy (default)")          \
+    X(SYMV_PACK_ESC, Int(0, 4096), "tall x-update: entries a tile of the 29-bit copy may hold outside its exponent window (default 32; one tile beyond it: the fp32 stream)") \
     X(REFINE, Flag(), "tall path: refine every x-update with a double-precision residual")                                               \
     X(DIST_FACTOR, Flag(), "row-sharded tall solver: 0 = every rank factorises the whole all-reduced Gram")                            \
     X(CV_DOWNDATE, Flag(), "cross-validation folds' Grams as down-dates of the full-data Gram: 1 always, 0 never")                      \

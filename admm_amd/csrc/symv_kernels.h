@@ -60,9 +60,20 @@
 //    and its two barriers are exposed in every tile; 89.9-90.1 ms per path against 87.0-87.8;
 //  * the gate reading the 64-byte rows of the norm partials as block 0 does (313 rows, a wave's load touching 64 lines): regular launches
 //    2 us slower than the two-vector kernel's; the tails now write a compact copy (lasso_tall.hip: tall_publish_norms).
+// Round 9, fewer bytes (profiles/tall_packed_stream.md): symv1_packed_kernel streams an exact 29-bit copy of the tiles (symv_pack.h) and decodes
+// it to the fp32 matrix's bits in front of symv1_tile's one copy of the arithmetic; the tall solver's default where it runs symv1_lower_kernel.
+// The bare tile loops, p = 10^4, replayed back to back (C2's box type, event-timed, medians of 20 launches, two sessions of each):
+//   fp32 31.0 - 32.6 us | packed 29.6 - 29.9 us | the 29 dwords consumed undecoded (the floor of this stream) 29.0 - 29.4 us.
+// Measured and rejected there:
+//  * the decode entry by entry (extract d, subtract, compare and select for the zero code, shift and or: 646 vector and 294 scalar
+//    instructions in the column loop against the fp32 kernel's 298 and 134): 31.7 - 31.9 us, no faster than the fp32 stream -- the loop
+//    then IS bound by its instructions.  The format's code bits are therefore laid out so that the four top bytes of a column are formed
+//    byte-wise in one register and every entry is one or two v_perm_b32 (about 420 vector instructions on the path without escapes, 99 VGPRs): within 0.6 us of the floor;
+//  * the floor itself is 2 us under the fp32 stream, not the 2.9 us the byte ratio promises: a chunk is still eight requests per lane.
 #pragma once
 #include "admm_internal.h"
 #include "device_utils.h"
+#include "symv_pack.h"
 #include <hip/hip_ext.h>
 #include <climits>
 #include <type_traits>
@@ -362,17 +373,118 @@ struct SymvForcedGate {                                   // a fixed answer (tes
 #define ADMM_HIP_SYMV1_PRE 8                              // columns of the first chunk requested ahead of the gate (dev builds: 0 = the gate first; "Measured and rejected" above)
 #endif
 
-template <typename Gate, typename Extra, bool NT = false, int PRE = ADMM_HIP_SYMV1_PRE>
-__global__ void __launch_bounds__(kSyThreads, ADMM_HIP_SYMV1_WGS)
-symv1_lower_kernel(SymvArgs a, Gate gate, Extra extra) {
-    if (blockIdx.x == 0) { extra(); return; }
-    __shared__ float4 red[kSyThreads];
-    __shared__ __attribute__((aligned(16))) float sdot[kSyCBMax];
-    __shared__ double gate_lds[kSyGateScratch];
-    // Prologue: the tile descriptor, the `done` word and the gate's inputs are requested together
+// Where a tile's 8-column chunk comes from.  symv1_tile below asks a source for (part of) chunk q -- request<K0, K1>(q) issues the loads of
+// its columns K0 .. K1 - 1 -- and takes the chunk over as eight float4 (get); everything from there on is one copy of code.
+struct SymvTileGeom { int row, col0, last, lane, wid, nqw; };      // nqw: chunks per wave
+
+// The fp32 matrix itself: one float4 per column, columns beyond `last` not loaded (zero).
+struct SymvDenseSrc {
+    struct Desc {};
+    __device__ __forceinline__ Desc describe(int) const { return Desc(); }
+    template <bool NT>
+    struct Chunk {
+        const float* base; long long lda; int col0, last;
+        float4 av[8];
+        __device__ __forceinline__ Chunk(const SymvDenseSrc&, const Desc&, const SymvArgs& a, const SymvTileGeom& g)
+            : base(a.A + (size_t)g.col0 * a.lda + g.row), lda(a.lda), col0(g.col0), last(g.last) {}
+        template <int K0, int K1>
+        __device__ __forceinline__ void request(int q) {
+#pragma unroll
+            for (int k = K0; k < K1; ++k) {
+                const int col = col0 + q * 8 + k;
+                av[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if constexpr (NT) { if (col <= last) av[k] = load16_nt<float4>(base + (size_t)(q * 8 + k) * lda); }
+                else { if (col <= last) av[k] = *reinterpret_cast<const float4*>(base + (size_t)(q * 8 + k) * lda); }
+            }
+        }
+        __device__ __forceinline__ void get(int, float4 (&out)[8]) const {
+#pragma unroll
+            for (int k = 0; k < 8; ++k) out[k] = av[k];
+        }
+    };
+};
+
+// The exact 29-bit copy of the tiles (symv_pack.h; written by symv_pack_kernel below): eight requests per chunk as well, seven of 16 bytes
+// and one of 4, all of them issued with the chunk's first column.  A lane whose chunk lies wholly above the diagonal, beyond column p - 1
+// or beyond the last row requests nothing and gets zeros (d = 14 everywhere), as the fp32 source's `last` does column by column.
+struct SymvPackedSrc {
+    const unsigned* stream;      // chunk c of the plan at stream + c * kSpChunkDwords
+    const int4* ptile;           // per tile: first chunk, base, escapes listed, escapes met
+    const uint2* esc;            // per tile esc_cap entries: (chunk of the tile << 11 | lane << 5 | entry, the float's bits)
+    int esc_cap;
+    using Desc = int4;
+    __device__ __forceinline__ Desc describe(int tile) const { return ptile[tile]; }
+    template <bool NT>
+    struct Chunk {
+        const unsigned* mine;    // this lane's first piece of its wave's first chunk
+        const uint2* esc; int nesc, ebase, col0, last, lane, chunk0;
+        uint4 pc[kSpPieces]; unsigned signs;
+        __device__ __forceinline__ Chunk(const SymvPackedSrc& s, const Desc& d, const SymvArgs&, const SymvTileGeom& g)
+            : mine(s.stream + ((size_t)d.x + (size_t)(g.wid * g.nqw)) * kSpChunkDwords + g.lane * 4), esc(s.esc + (size_t)(blockIdx.x - 1) * s.esc_cap),
+              nesc(d.z), ebase(d.y), col0(g.col0), last(g.last), lane(g.lane), chunk0(g.wid * g.nqw) {}
+        template <int K0, int K1>
+        __device__ __forceinline__ void request(int q) {
+            if constexpr (K0 == 0 && K1 > 0) {
+                const unsigned* c = mine + (size_t)q * kSpChunkDwords;
+                pc[0] = make_uint4(0xEEEEEEEEu, 0xEEEEEEEEu, 0xEEEEEEEEu, 0xEEEEEEEEu);      // d = 14: every entry a zero
+#pragma unroll
+                for (int i = 1; i < kSpPieces; ++i) pc[i] = make_uint4(0u, 0u, 0u, 0u);
+                signs = 0u;
+                if (col0 + q * 8 <= last) {
+                    if constexpr (NT) {
+#pragma unroll
+                        for (int i = 0; i < kSpPieces; ++i) pc[i] = load16_nt<uint4>(c + i * 256);
+                        signs = __builtin_nontemporal_load(c + 4 * kSpPieces * 64 - 3 * lane);
+                    } else {
+#pragma unroll
+                        for (int i = 0; i < kSpPieces; ++i) pc[i] = *reinterpret_cast<const uint4*>(c + i * 256);
+                        signs = c[4 * kSpPieces * 64 - 3 * lane];
+                    }
+                }
+            }
+        }
+        __device__ __forceinline__ void get(int q, float4 (&out)[8]) const {
+            unsigned rec[kSpRecDwords], bits[kSpEntries];
+#pragma unroll
+            for (int i = 0; i < kSpPieces; ++i) { rec[4 * i] = pc[i].x; rec[4 * i + 1] = pc[i].y; rec[4 * i + 2] = pc[i].z; rec[4 * i + 3] = pc[i].w; }
+            rec[4 * kSpPieces] = signs;
+#if ADMM_HIP_SYMV_PACK_DEC == 2      // dev build, timing only: the 29 dwords as they come (meaningless products) -- what the stream costs without any decode
+#pragma unroll
+            for (int e = 0; e < kSpEntries; ++e) bits[e] = rec[e < kSpRecDwords ? e : e - 4] ^ (unsigned)ebase;
+#else
+            sp_record_decode(rec, ebase, bits);
+#endif
+#pragma unroll
+            for (int k = 0; k < 8; ++k)
+                out[k] = make_float4(__uint_as_float(bits[4 * k]), __uint_as_float(bits[4 * k + 1]), __uint_as_float(bits[4 * k + 2]), __uint_as_float(bits[4 * k + 3]));
+            if (nesc > 0) {            // wave-uniform, a handful of tiles per launch: the listed floats replace the +0.0 of their places
+                const unsigned me = ((unsigned)(chunk0 + q) << 6) | (unsigned)lane;
+                for (int i = 0; i < nesc; ++i) {
+                    const uint2 en = esc[i];
+                    const bool hit = (en.x >> 5) == me;
+                    const unsigned e = en.x & 31u;
+                    const float val = __uint_as_float(en.y);
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) {
+                        if (hit && e == 4u * k + 0u) out[k].x = val;
+                        if (hit && e == 4u * k + 1u) out[k].y = val;
+                        if (hit && e == 4u * k + 2u) out[k].z = val;
+                        if (hit && e == 4u * k + 3u) out[k].w = val;
+                    }
+                }
+            }
+        }
+    };
+};
+
+// One tile of the one-vector product, behind the `extra` workgroup's exit: prologue, gate, peeled first chunk, column loop, epilogue.
+template <typename Src, typename Gate, bool NT, int PRE>
+__device__ __forceinline__ void symv1_tile(const SymvArgs& a, const Src& src, const Gate& gate, float4* red, float* sdot, double* gate_lds) {
+    // Prologue: the tile descriptor(s), the `done` word and the gate's inputs are requested together
     const int4 t = a.tiles[blockIdx.x - 1];
     const int done = *a.skip;
     const typename Gate::Req greq = gate.request();
+    const typename Src::Desc sd = src.describe(blockIdx.x - 1);
     if (done != 0) return;                 // (arrives with the descriptor: checked before the first matrix request, not behind it)
     const int rb = t.x, seg = t.w;
     const int cw = t.z >> 2;               // columns per wave: a multiple of 8, at most 64
@@ -382,23 +494,13 @@ symv1_lower_kernel(SymvArgs a, Gate gate, Extra extra) {
     const int p4 = (a.p + 3) & ~3;
     const bool active = row < p4;
     const bool has = col0 < a.p;           // every wave of a listed tile has all its columns <= the block's last row
-    const float* base = a.A + (size_t)col0 * a.lda + row;
     const bool diag = col0 + (cw - 1) >= rb * kSyRB;         // this wave's block meets the diagonal
     const int nq = has ? cw >> 3 : 0;
     const int last = active ? min(a.p - 1, diag ? row + 3 : INT_MAX) : -1;      // symv2_tile's `last`
-    float4 av[8];
-    const auto request = [&](int q, auto k0, auto k1) {      // columns k0 .. k1 - 1 of chunk q
-#pragma unroll
-        for (int k = decltype(k0)::value; k < decltype(k1)::value; ++k) {
-            const int col = col0 + q * 8 + k;
-            av[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if constexpr (NT) { if (col <= last) av[k] = load16_nt<float4>(base + (size_t)(q * 8 + k) * a.lda); }
-            else { if (col <= last) av[k] = *reinterpret_cast<const float4*>(base + (size_t)(q * 8 + k) * a.lda); }
-        }
-    };
-    using K0 = std::integral_constant<int, 0>; using KP = std::integral_constant<int, PRE>; using K8 = std::integral_constant<int, 8>;
+    const SymvTileGeom geom = {row, col0, last, lane, wid, cw >> 3};
+    typename Src::template Chunk<NT> ch(src, sd, a, geom);
     static_assert(PRE >= 0 && PRE <= 8, "columns of the first chunk requested ahead of the gate");
-    if constexpr (PRE > 0) { if (nq > 0) request(0, K0(), KP()); }
+    if constexpr (PRE > 0) { if (nq > 0) ch.template request<0, PRE>(0); }
     const int g = gate.decide(greq, gate_lds);
     if (g == kSyGateLeave) {               // nobody reads what this launch would write: the slots keep what the last consumed launch left
         if (threadIdx.x == 0) atomicAdd(a.early + (size_t)(blockIdx.x & (kSyEarlySlots - 1)) * kSyVerdictStride, 1ull);
@@ -414,6 +516,8 @@ symv1_lower_kernel(SymvArgs a, Gate gate, Extra extra) {
         const int cj = col0 + lane;                                          // the wave's (<= 64) right-hand entries, one per lane
         const float uj = (lane < cw && cj < a.p) ? v[cj] : 0.f;
         const auto consume = [&](int q) {
+            float4 av[8];
+            ch.get(q, av);
             float dU[8];
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
@@ -438,10 +542,10 @@ symv1_lower_kernel(SymvArgs a, Gate gate, Extra extra) {
             const float du = butterfly8(dU, lane);                // every lane ends with column (lane >> 3)
             if ((lane & 7) == 0) sdot[wid * cw + q * 8 + (lane >> 3)] = du;
         };
-        if constexpr (PRE > 0) { request(0, KP(), K8()); consume(0); }      // the rest of the peeled chunk
+        if constexpr (PRE > 0) { ch.template request<PRE, 8>(0); consume(0); }      // the rest of the peeled chunk
 #pragma unroll 1
         for (int q = PRE > 0 ? 1 : 0; q < nq; ++q) {
-            request(q, K0(), K8());
+            ch.template request<0, 8>(q);
             consume(q);
         }
     } else {
@@ -472,6 +576,110 @@ symv1_lower_kernel(SymvArgs a, Gate gate, Extra extra) {
         }
     }
 #endif
+}
+
+template <typename Gate, typename Extra, bool NT = false, int PRE = ADMM_HIP_SYMV1_PRE>
+__global__ void __launch_bounds__(kSyThreads, ADMM_HIP_SYMV1_WGS)
+symv1_lower_kernel(SymvArgs a, Gate gate, Extra extra) {
+    if (blockIdx.x == 0) { extra(); return; }
+    __shared__ float4 red[kSyThreads];
+    __shared__ __attribute__((aligned(16))) float sdot[kSyCBMax];
+    __shared__ double gate_lds[kSyGateScratch];
+    symv1_tile<SymvDenseSrc, Gate, NT, PRE>(a, SymvDenseSrc(), gate, red, sdot, gate_lds);
+}
+
+// The same kernel on the 29-bit copy of the tiles: 181.25 instead of 200 bytes per 50 entries, decoded to the bits of the fp32 matrix.
+template <typename Gate, typename Extra, bool NT = false, int PRE = ADMM_HIP_SYMV1_PRE>
+__global__ void __launch_bounds__(kSyThreads, ADMM_HIP_SYMV1_WGS)
+symv1_packed_kernel(SymvArgs a, SymvPackedSrc src, Gate gate, Extra extra) {
+    if (blockIdx.x == 0) { extra(); return; }
+    __shared__ float4 red[kSyThreads];
+    __shared__ __attribute__((aligned(16))) float sdot[kSyCBMax];
+    __shared__ double gate_lds[kSyGateScratch];
+    symv1_tile<SymvPackedSrc, Gate, NT, PRE>(a, src, gate, red, sdot, gate_lds);
+}
+
+// Packs the tiles of a plan: one workgroup per tile, thread = (wave, lane) of the streaming kernel.  First the tile's base (the largest
+// upper-seven-bit exponent among the entries the fp32 kernel uses that are finite and not zero), then record by record.  Entries the fp32
+// kernel never uses -- above the diagonal, rows >= p rounded up to 4, columns >= p -- are +0.0 and are not read from the matrix.
+struct SymvPackArgs {
+    const float* A; long long lda; int p;
+    const int4* tiles;
+    int4* ptile;                       // x (first chunk) is given; y, z, w are written: base, escapes listed, escapes met
+    unsigned* stream;
+    uint2* esc; int esc_cap;
+    unsigned long long* totals;        // [0] escapes met, [1] tiles whose list overflowed
+};
+static __global__ void __launch_bounds__(kSyThreads)
+symv_pack_kernel(SymvPackArgs a) {
+    __shared__ int s_base;
+    __shared__ unsigned s_cnt;
+    const int4 t = a.tiles[blockIdx.x];
+    const int rb = t.x, cw = t.z >> 2, nqw = cw >> 3;
+    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int row = rb * kSyRB + lane * 4;
+    const int col0 = t.y + wid * cw;
+    const int p4 = (a.p + 3) & ~3;
+    const bool active = row < p4;
+    if (threadIdx.x == 0) { s_base = 0; s_cnt = 0u; }
+    __syncthreads();
+    const float* base = a.A + (size_t)col0 * a.lda + row;
+    const auto column = [&](int j, unsigned (&b)[4]) {      // the four entries of this lane in column col0 + j, unused ones as +0.0
+        const int col = col0 + j;
+        b[0] = b[1] = b[2] = b[3] = 0u;
+        if (active && col < a.p && row + 3 >= col) {
+            const float4 m = *reinterpret_cast<const float4*>(base + (size_t)j * a.lda);
+            if (row + 0 >= col) b[0] = __float_as_uint(m.x);
+            if (row + 1 >= col) b[1] = __float_as_uint(m.y);
+            if (row + 2 >= col) b[2] = __float_as_uint(m.z);
+            b[3] = __float_as_uint(m.w);
+        }
+    };
+    int mx = 0;
+    for (int j = 0; j < cw; ++j) {
+        unsigned b[4];
+        column(j, b);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) if (sp_counts(b[c])) mx = max(mx, sp_exp7(b[c]));
+    }
+    atomicMax(&s_base, mx);
+    __syncthreads();
+    const int ebase = s_base;
+    const size_t first = (size_t)a.ptile[blockIdx.x].x;
+    for (int q = 0; q < nqw; ++q) {
+        unsigned bits[kSpEntries], rec[kSpRecDwords];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            unsigned b[4];
+            column(q * 8 + k, b);
+            bits[4 * k] = b[0]; bits[4 * k + 1] = b[1]; bits[4 * k + 2] = b[2]; bits[4 * k + 3] = b[3];
+        }
+        const unsigned em = sp_record_encode(bits, ebase, rec);
+        unsigned* c = a.stream + (first + (size_t)(wid * nqw + q)) * kSpChunkDwords;
+#pragma unroll
+        for (int i = 0; i < kSpPieces; ++i)
+            *reinterpret_cast<uint4*>(c + (i * 64 + lane) * 4) = make_uint4(rec[4 * i], rec[4 * i + 1], rec[4 * i + 2], rec[4 * i + 3]);
+        c[4 * kSpPieces * 64 + lane] = rec[4 * kSpPieces];
+        if (em != 0u) {
+#pragma unroll
+            for (int e = 0; e < kSpEntries; ++e) {
+                if ((em >> e) & 1u) {
+                    const unsigned slot = atomicAdd(&s_cnt, 1u);
+                    if (slot < (unsigned)a.esc_cap)
+                        a.esc[(size_t)blockIdx.x * a.esc_cap + slot] = make_uint2(((unsigned)(wid * nqw + q) << 11) | ((unsigned)lane << 5) | (unsigned)e, bits[e]);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        const unsigned n = s_cnt;
+        int4 d = a.ptile[blockIdx.x];
+        d.y = ebase; d.z = (int)min(n, (unsigned)a.esc_cap); d.w = (int)n;
+        a.ptile[blockIdx.x] = d;
+        if (n != 0u) atomicAdd(a.totals, (unsigned long long)n);
+        if (n > (unsigned)a.esc_cap) atomicAdd(a.totals + 1, 1ull);
+    }
 }
 
 // ---- NR right-hand sides on ONE load of every matrix element (multi-task lasso: lasso_tall.hip, tall_mt_tail_kernel).
@@ -858,6 +1066,70 @@ struct SymvPlan {
         else hipExtLaunchKernelGGL((symv1_lower_kernel<Gate, Extra>), dim3(ntiles + 1), dim3(kSyThreads), 0, st, ev_start, ev_stop, 0, a, gate, extra);
     }
 };
+
+// The 29-bit copy of a plan's tiles (symv_pack.h) with its per-tile descriptors and escape lists.  build() packs once per inverse and
+// tile list; a list that overflows its capacity leaves `ready` false and the caller on the fp32 stream.
+struct SymvPacked {
+    DevBuf<unsigned> stream;
+    DevBuf<int4> ptile;
+    DevBuf<uint2> esc;
+    DevBuf<unsigned long long> totals;
+    int esc_cap = kSpEscCap;
+    size_t chunks = 0;
+    unsigned long long escapes = 0, overflowed = 0;      // escapes met over all tiles; tiles whose list overflowed
+    bool ready = false, nt = false;
+    size_t bytes() const { return chunks * (size_t)kSpChunkBytes; }
+    static size_t bytes_for(const SymvPlan& sy) {      // of the copy of that plan's tiles, before anything is allocated
+        size_t c = 0;
+        for (const int4& t : sy.htiles) c += (size_t)(t.z >> 3);
+        return c * (size_t)kSpChunkBytes;
+    }
+    void release() { stream.release(); ptile.release(); esc.release(); totals.release(); chunks = 0; ready = false; }
+    bool build(const SymvPlan& sy, const float* A, long long lda, hipStream_t st, int cap = kSpEscCap) {
+        ready = false;
+        esc_cap = cap;
+        std::vector<int4> h((size_t)std::max(sy.ntiles, 1), make_int4(0, 0, 0, 0));
+        chunks = 0;
+        for (int k = 0; k < sy.ntiles; ++k) { h[k].x = (int)chunks; chunks += (size_t)(sy.htiles[k].z >> 3); }
+        if (sy.ntiles == 0) return false;
+        stream.alloc(chunks * (size_t)kSpChunkDwords);
+        ptile.alloc(h.size());
+        esc.alloc(std::max<size_t>((size_t)sy.ntiles * (size_t)cap, 1));
+        totals.alloc(2); totals.zero(st);
+        ADMM_HIP_CHECK(hipMemcpyAsync(ptile.get(), h.data(), h.size() * sizeof(int4), hipMemcpyHostToDevice, st));
+        SymvPackArgs a;
+        a.A = A; a.lda = lda; a.p = sy.p; a.tiles = sy.tiles.get(); a.ptile = ptile.get(); a.stream = stream.get();
+        a.esc = esc.get(); a.esc_cap = cap; a.totals = totals.get();
+        hipLaunchKernelGGL(symv_pack_kernel, dim3(sy.ntiles), dim3(kSyThreads), 0, st, a);
+        ADMM_HIP_CHECK(hipGetLastError());
+        unsigned long long tt[2] = {0, 0};
+        ADMM_HIP_CHECK(hipMemcpyAsync(tt, totals.get(), sizeof(tt), hipMemcpyDeviceToHost, st));
+        ADMM_HIP_CHECK(hipStreamSynchronize(st));      // (also keeps `h` alive until it is copied)
+        escapes = tt[0]; overflowed = tt[1];
+        nt = bytes() > (size_t)310000000;              // the fp32 stream's crossover (symv_plan_layout) on the bytes streamed here
+        ready = overflowed == 0;
+        return ready;
+    }
+    SymvPackedSrc src() const { return SymvPackedSrc{stream.get(), ptile.get(), esc.get(), esc_cap}; }
+};
+
+// SymvPlan::launch_one on the packed copy: same gate, same partials into plane 0.
+template <typename Gate, typename Extra = SymvNoExtra>
+void symv_launch_one_packed(const SymvPlan& sy, const SymvPacked& pk, const float* v0, const float* v1, const int* skip, hipStream_t st, Gate gate,
+                            unsigned long long* early, Extra extra = Extra(), hipEvent_t ev_start = nullptr, hipEvent_t ev_stop = nullptr) {
+    SymvVerdict vd;
+    vd.early = early;
+    const SymvArgs a = sy.args(nullptr, 0, v0, v1, skip, vd);
+    const SymvPackedSrc src = pk.src();
+    const bool timed = ev_start != nullptr || ev_stop != nullptr;
+    if (pk.nt) {
+        if (!timed) hipLaunchKernelGGL((symv1_packed_kernel<Gate, Extra, true>), dim3(sy.ntiles + 1), dim3(kSyThreads), 0, st, a, src, gate, extra);
+        else hipExtLaunchKernelGGL((symv1_packed_kernel<Gate, Extra, true>), dim3(sy.ntiles + 1), dim3(kSyThreads), 0, st, ev_start, ev_stop, 0, a, src, gate, extra);
+        return;
+    }
+    if (!timed) hipLaunchKernelGGL((symv1_packed_kernel<Gate, Extra>), dim3(sy.ntiles + 1), dim3(kSyThreads), 0, st, a, src, gate, extra);
+    else hipExtLaunchKernelGGL((symv1_packed_kernel<Gate, Extra>), dim3(sy.ntiles + 1), dim3(kSyThreads), 0, st, ev_start, ev_stop, 0, a, src, gate, extra);
+}
 
 // y_i of both right-hand sides from the partial arrays.  NL lanes (a power of two <= 64, consecutive lanes of one
 // wave, `sub` = this lane's index among them) share element i: each issues up to 16 partial loads per array at once

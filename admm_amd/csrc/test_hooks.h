@@ -11,6 +11,11 @@ void test_symv_plan(int p, int cus, int part, int nparts, int* sched_out, long l
 void test_symv_ex(const float* A, int p, const float* v0, const float* v1, int variant, int part, int nparts, float* y0, float* y1, int* sched_out);
 void test_symv_one(const float* A, int p, const float* v0, const float* v1, int gate, int nt, unsigned fill, float* y, float* dot_out, float* axp_out,
                    long long plane_capacity, long long* info_out, int* sched_out);
+void test_symv_pack_host(const unsigned* bits, int nchunks, int* base_io, unsigned* stream_out, unsigned* esc_out, int esc_cap, long long* nesc_out,
+                         unsigned* decoded_out);      // host only
+void test_symv_packed(const float* A, int p, const float* v0, const float* v1, int gate, int nt, unsigned fill, int esc_cap, float* y, float* dot_out,
+                      float* axp_out, long long plane_capacity, long long* info_out, int* sched_out);
+void test_symv_packed_time(const float* A, int p, const float* v0, int reps, float* us_out, long long* info_out);
 void test_symv_multi_ex(const float* A, int p, const float* V, int nr, int rhs_per_pass, int nt, int finish, float* Yout, int* sched_out);
 void test_symv_f64acc(const float* A, int p, const float* v0, const float* v1, double* y0, double* y1, int* sched_out);
 template <typename T> void test_gram(const T* A, int rows, int cols, bool atA, T* G);
@@ -24,6 +29,7 @@ template <typename T> void test_gather(const T* A, int rows, int cols, const T* 
 void test_cv_fold_system(const double* x, const double* y, int n, int p, const int* fold_id, int nfolds, int fold,
                          int standardize, int intercept, float* gram, float* xy, float* mean_x, float* scale_x, float* mean_scale_y);
 long long tall_last_early_exits();      // lasso_tall.hip
+void tall_last_pack_info(long long* out);      // lasso_tall.hip
 void test_logit_prox(const double* v, long long m, double t, double* out);      // fadmm_dense.hip: the device logit2 over a host array
 
 }  // namespace admm

@@ -221,6 +221,145 @@ void test_symv_one(const float* A, int p, const float* v0, const float* v1, int 
     info_out[1] = left;
 }
 
+// The 29-bit record format (symv_pack.h) on the host alone: bits [nchunks][64][32] (lane-major records of 32 entries) are encoded against
+// *base_io (negative: the largest upper-seven-bit exponent among the finite non-zero entries, handed back) into stream_out
+// [nchunks][1856] dwords in the memory layout of a wave's chunk; escapes go to esc_out as (chunk << 11 | lane << 5 | entry, bits) while
+// they fit esc_cap and are all counted in *nesc_out; decoded_out [nchunks][64][32]: the stream decoded again (escapes as +0.0).
+void test_symv_pack_host(const unsigned* bits, int nchunks, int* base_io, unsigned* stream_out, unsigned* esc_out, int esc_cap, long long* nesc_out,
+                         unsigned* decoded_out) {
+    const size_t n = (size_t)nchunks * 64 * kSpEntries;
+    int base = *base_io;
+    if (base < 0) {
+        base = 0;
+        for (size_t k = 0; k < n; ++k) if (sp_counts(bits[k])) base = std::max(base, sp_exp7(bits[k]));
+        *base_io = base;
+    }
+    long long met = 0;
+    for (int c = 0; c < nchunks; ++c) {
+        for (int lane = 0; lane < 64; ++lane) {
+            unsigned in[kSpEntries], rec[kSpRecDwords], out[kSpEntries];
+            const size_t at = ((size_t)c * 64 + lane) * kSpEntries;
+            for (int e = 0; e < kSpEntries; ++e) in[e] = bits[at + e];
+            const unsigned em = sp_record_encode(in, base, rec);
+            for (int j = 0; j < kSpRecDwords; ++j) stream_out[(size_t)c * kSpChunkDwords + sp_dword_pos(lane, j)] = rec[j];
+            for (int e = 0; e < kSpEntries; ++e) {
+                if (((em >> e) & 1u) == 0u) continue;
+                if (met < esc_cap) { esc_out[2 * met] = ((unsigned)c << 11) | ((unsigned)lane << 5) | (unsigned)e; esc_out[2 * met + 1] = in[e]; }
+                ++met;
+            }
+            unsigned back[kSpRecDwords];
+            for (int j = 0; j < kSpRecDwords; ++j) back[j] = stream_out[(size_t)c * kSpChunkDwords + sp_dword_pos(lane, j)];
+            sp_record_decode(back, base, out);
+            for (int k = 0; k < 8; ++k) {              // the byte-wise decode against the format as it is stated, entry by entry
+                unsigned plain[4];
+                sp_column_decode_plain(back[k >> 1], back[4 + 3 * k], back[5 + 3 * k], back[6 + 3 * k], back[28], k, base, plain);
+                for (int cc = 0; cc < 4; ++cc)
+                    if (plain[cc] != out[4 * k + cc]) throw Error(ADMM_ERR_INTERNAL, "symv_pack_host hook: the two decodes of a record disagree");
+            }
+            for (int e = 0; e < kSpEntries; ++e) decoded_out[at + e] = out[e];
+        }
+    }
+    *nesc_out = met;
+}
+
+// test_symv_one's storage and read-out for symv1_packed_kernel: the plan's tiles are packed (escape lists of esc_cap entries) and the forced gate
+// runs on the packed copy.  info_out[8]: tiles, tiles that left, floats of a dot / axpy plane, escapes met, tiles whose list overflowed,
+// bytes of the packed stream, 1 if the packed kernel ran (an overflow leaves the planes as filled and this 0).
+void test_symv_packed(const float* A, int p, const float* v0, const float* v1, int gate, int nt, unsigned fill, int esc_cap, float* y, float* dot_out,
+                      float* axp_out, long long plane_capacity, long long* info_out, int* sched_out) {
+    require_device();
+    Stream st;
+    const long long lda = round_up(p, 128), ldv = round_up(p, 256);
+    DevBuf<float> dA((size_t)lda * lda), d0(ldv), d1(ldv), o0(ldv);
+    DevBuf<unsigned long long> early((size_t)kSyEarlySlots * kSyVerdictStride);
+    dA.zero(st.s); d0.zero(st.s); d1.zero(st.s); o0.zero(st.s); early.zero(st.s);
+    ADMM_HIP_CHECK(hipMemcpy2DAsync(dA.get(), lda * sizeof(float), A, (size_t)p * sizeof(float), (size_t)p * sizeof(float), p,
+                                    hipMemcpyHostToDevice, st.s));
+    ADMM_HIP_CHECK(hipMemcpyAsync(d0.get(), v0, (size_t)p * sizeof(float), hipMemcpyHostToDevice, st.s));
+    ADMM_HIP_CHECK(hipMemcpyAsync(d1.get(), v1, (size_t)p * sizeof(float), hipMemcpyHostToDevice, st.s));
+    SymvPlan sy;
+    sy.init(p, st.s);
+    report_sched(sy.sched, sched_out);
+    const size_t nd = (size_t)sy.nrb * sy.ldo, na = (size_t)sy.nax_rows * sy.ldo;
+    info_out[0] = sy.ntiles; info_out[1] = -1; info_out[2] = (long long)nd; info_out[3] = (long long)na;
+    ADMM_REQUIRE(dot_out == nullptr || (long long)std::max(nd, na) <= plane_capacity,
+                 "symv_packed hook: plane_capacity is too small for the " + std::to_string(std::max(nd, na)) + " floats of a plane of partials");
+    float* planes[4] = {sy.dot0.get(), sy.dot1.get(), sy.axp0.get(), sy.axp1.get()};
+    for (int k = 0; k < 4; ++k) ADMM_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(planes[k]), (int)fill, k < 2 ? nd : na, st.s));
+    SymvPacked pk;
+    const bool ok = pk.build(sy, dA.get(), lda, st.s, esc_cap);
+    info_out[4] = (long long)pk.escapes; info_out[5] = (long long)pk.overflowed; info_out[6] = (long long)pk.bytes(); info_out[7] = ok ? 1 : 0;
+    pk.nt = nt != 0;
+    const int per = 256 / kSySumLanes;
+    if (ok) {
+        symv_launch_one_packed(sy, pk, d0.get(), d1.get(), nullptr, st.s, SymvForcedGate{gate == 2 ? kSyGateLeave : gate}, early.get());
+        hipLaunchKernelGGL(test_symv_finish_one_kernel, dim3((p + per - 1) / per), dim3(256), 0, st.s, sy.dot0.get(), sy.axp0.get(),
+                           sy.ldo, sy.nrb, sy.sched, sy.p32, p, o0.get());
+    }
+    ADMM_HIP_CHECK(hipGetLastError());
+    std::vector<unsigned long long> slots((size_t)kSyEarlySlots * kSyVerdictStride);
+    ADMM_HIP_CHECK(hipMemcpyAsync(y, o0.get(), (size_t)p * sizeof(float), hipMemcpyDeviceToHost, st.s));
+    ADMM_HIP_CHECK(hipMemcpyAsync(slots.data(), early.get(), slots.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost, st.s));
+    if (dot_out != nullptr) {
+        for (int k = 0; k < 2; ++k) {
+            ADMM_HIP_CHECK(hipMemcpyAsync(dot_out + (size_t)k * plane_capacity, planes[k], nd * sizeof(float), hipMemcpyDeviceToHost, st.s));
+            ADMM_HIP_CHECK(hipMemcpyAsync(axp_out + (size_t)k * plane_capacity, planes[2 + k], na * sizeof(float), hipMemcpyDeviceToHost, st.s));
+        }
+    }
+    st.sync();
+    long long left = 0;
+    for (int k = 0; k < kSyEarlySlots; ++k) left += (long long)slots[(size_t)k * kSyVerdictStride];
+    info_out[1] = left;
+}
+
+// The bare tile loops against each other, event-timed launch by launch (scripts/symv_packed_gate.py): us_out [4][reps] = fp32 / packed after
+// a pass over a buffer larger than the Infinity Cache ("cold"), fp32 / packed replayed back to back (two launches of warm-up per block, two
+// alternating blocks of reps / 2 each).  info_out[4]: tiles, escapes met, tiles overflowed, bytes of the packed stream.
+void test_symv_packed_time(const float* A, int p, const float* v0, int reps, float* us_out, long long* info_out) {
+    require_device();
+    Stream st;
+    const long long lda = round_up(p, 128), ldv = round_up(p, 256);
+    DevBuf<float> dA((size_t)lda * lda), d0(ldv);
+    DevBuf<unsigned long long> early((size_t)kSyEarlySlots * kSyVerdictStride);
+    DevBuf<unsigned> flush((size_t)192 << 20);      // 768 MB
+    dA.zero(st.s); d0.zero(st.s); early.zero(st.s);
+    ADMM_HIP_CHECK(hipMemcpy2DAsync(dA.get(), lda * sizeof(float), A, (size_t)p * sizeof(float), (size_t)p * sizeof(float), p,
+                                    hipMemcpyHostToDevice, st.s));
+    ADMM_HIP_CHECK(hipMemcpyAsync(d0.get(), v0, (size_t)p * sizeof(float), hipMemcpyHostToDevice, st.s));
+    SymvPlan sy;
+    sy.init(p, st.s);
+    SymvPacked pk;
+    const bool ok = pk.build(sy, dA.get(), lda, st.s);
+    info_out[0] = sy.ntiles; info_out[1] = (long long)pk.escapes; info_out[2] = (long long)pk.overflowed; info_out[3] = (long long)pk.bytes();
+    ADMM_REQUIRE(ok, "symv_packed_time hook: a tile's escape list overflowed");
+    hipEvent_t e0, e1;
+    ADMM_HIP_CHECK(hipEventCreate(&e0)); ADMM_HIP_CHECK(hipEventCreate(&e1));
+    const SymvForcedGate gate{0};
+    const auto one = [&](int kind, bool timed) {
+        float ms = 0.f;
+        if (kind == 0) sy.launch_one(dA.get(), lda, d0.get(), d0.get(), nullptr, st.s, gate, early.get(), SymvNoExtra(), timed ? e0 : nullptr, timed ? e1 : nullptr);
+        else symv_launch_one_packed(sy, pk, d0.get(), d0.get(), nullptr, st.s, gate, early.get(), SymvNoExtra(), timed ? e0 : nullptr, timed ? e1 : nullptr);
+        ADMM_HIP_CHECK(hipGetLastError());
+        if (timed) { ADMM_HIP_CHECK(hipEventSynchronize(e1)); ADMM_HIP_CHECK(hipEventElapsedTime(&ms, e0, e1)); }
+        return ms * 1000.f;
+    };
+    for (int r = 0; r < reps; ++r) {
+        for (int kind = 0; kind < 2; ++kind) {
+            ADMM_HIP_CHECK(hipMemsetAsync(flush.get(), r + kind, flush.n * sizeof(unsigned), st.s));
+            us_out[(size_t)kind * reps + r] = one(kind, true);
+        }
+    }
+    const int half = reps / 2;
+    for (int blk = 0; blk < 2; ++blk) {
+        for (int kind = 0; kind < 2; ++kind) {
+            one(kind, false); one(kind, false);
+            for (int r = 0; r < half; ++r) us_out[(size_t)(2 + kind) * reps + blk * half + r] = one(kind, true);
+        }
+    }
+    st.sync();
+    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+}
+
 // test_symvn_finish_kernel with the consumer the multi-task tail really uses: symv_sum_partials_n over chunks of kMtChunk pairs, walked
 // as tall_mt_tail_kernel walks them (chunk k0: planes from 2 k0, nk = min(kMtChunk, npair - k0) pairs of it valid).
 __global__ void __launch_bounds__(256)

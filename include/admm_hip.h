@@ -717,6 +717,26 @@ ADMM_HIP_API int admm_hip_test_symv_ex(const float* A, int p, const float* v0, c
 ADMM_HIP_API int admm_hip_test_symv_one(const float* A, int p, const float* v0, const float* v1, int gate, int nt, unsigned int fill,
                                         float* y, float* dot_out, float* axp_out, long long plane_capacity, long long* info_out,
                                         int* sched_out);
+/* The exact 29-bit record format of the packed x-update stream, on the host alone.  bits [nchunks][64][32]: per lane of a wave the 32
+ * entries (4 k + c: column k of an 8-column chunk, component c of the lane's float4) of a record, as 32-bit patterns.  They are encoded
+ * against *base_io (negative: the largest upper-seven-bit exponent among the finite non-zero entries, which is handed back) into
+ * stream_out [nchunks][1856] dwords, the memory image of the wave's chunks.  Entries that do not fit go to esc_out as pairs
+ * (chunk << 11 | lane << 5 | entry, bits) while they fit esc_cap and are all counted in *nesc_out.  decoded_out [nchunks][64][32]: the
+ * image decoded again, escapes as +0.0. */
+ADMM_HIP_API int admm_hip_test_symv_pack_host(const unsigned int* bits, int nchunks, int* base_io, unsigned int* stream_out,
+                                              unsigned int* esc_out, int esc_cap, long long* nesc_out, unsigned int* decoded_out);
+/* admm_hip_test_symv_one (gates 0, 1, 2) on the 29-bit copy of the plan's tiles: the tiles are packed with escape lists of esc_cap entries
+ * per tile and the one-vector kernel streams the copy.  info_out[8]: tiles, tiles that left early, floats of a dot plane, of an axpy
+ * plane, escapes met, tiles whose escape list overflowed, bytes of the packed stream, 1 if the packed kernel ran (after an overflow it
+ * does not: the planes keep `fill` and this is 0). */
+ADMM_HIP_API int admm_hip_test_symv_packed(const float* A, int p, const float* v0, const float* v1, int gate, int nt, unsigned int fill,
+                                           int esc_cap, float* y, float* dot_out, float* axp_out, long long plane_capacity,
+                                           long long* info_out, int* sched_out);
+/* The bare one-vector tile loops on the fp32 matrix and on its 29-bit copy, event-timed launch by launch.  us_out [4][reps] microseconds:
+ * fp32 and packed, each launch behind a pass over a buffer larger than the Infinity Cache; fp32 and packed replayed back to back (two
+ * alternating blocks of reps / 2 launches, two untimed launches in front of each).  info_out[4]: tiles, escapes met, tiles overflowed,
+ * bytes of the packed stream. */
+ADMM_HIP_API int admm_hip_test_symv_packed_time(const float* A, int p, const float* v0, int reps, float* us_out, long long* info_out);
 /* admm_hip_test_symv_multi with the non-temporal instantiations forced (nt = 1) or not (0), and the consumer chosen: finish 0 sums the
  * partials pair by pair (as admm_hip_test_symv_multi), 1 in chunks of pairs with the routine and the walk of the multi-task tail. */
 ADMM_HIP_API int admm_hip_test_symv_multi_ex(const float* A, int p, const float* V, int nr, int rhs_per_pass, int nt, int finish,
@@ -730,6 +750,11 @@ ADMM_HIP_API int admm_hip_test_symv_f64acc(const float* A, int p, const float* v
  * streams, so the count is exact: tiles x discarded launches.  At levels 1 and 2 how many leave is a matter of timing; the results
  * depend on it at no level. */
 ADMM_HIP_API int admm_hip_test_tall_early_exits(long long* count);
+/* The stream of the x-update of the most recent tall plan (lasso, elastic net, group, sparse-group, box) created by the CALLING THREAD.
+ * info_out[4]: 1 if it streams the exact 29-bit copy of the inverse's tiles (ADMM_HIP_SYMV_PACK, the default) and 0 if the fp32 matrix;
+ * entries met outside their tile's exponent window while packing; tiles whose list of such entries overflowed (any: the fp32 stream);
+ * bytes of the copy.  All 0 where no copy was attempted. */
+ADMM_HIP_API int admm_hip_test_tall_pack_info(long long* info_out);
 /* The device prox of admm_hip_logit alone: out[k] = the root z of z - v[k] - t / (1 + e^z), t = 1 / rho > 0, over HOST arrays of
  * length m, by the device function the tail and rows kernels call. */
 ADMM_HIP_API int admm_hip_test_logit_prox(const double* v, long long m, double t, double* out);
