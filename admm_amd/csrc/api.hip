@@ -738,6 +738,59 @@ int admm_hip_test_gemv_t(const void* A, int rows, int cols, int is_double, const
     });
 }
 
+// The three hooks below refuse what they cannot run before they look for a device (tests/test_cabi_refusals.py).
+int admm_hip_test_gemv_t_ex(int is_double, int form, int nrhs, int nt, int max_seg_rows, int lda_extra, unsigned long long fill, int count,
+                            const int* m, const int* k, const void* const* A, const void* const* v, const int* from, const int* skip,
+                            void* const* part_out, long long part_capacity, void* const* y_out, long long* info_out) {
+    return guarded([&] {
+        ADMM_REQUIRE(m && k && A && v && part_out && info_out, "gemv_t_ex hook: m, k, A, v, part_out and info_out must not be NULL");
+        ADMM_REQUIRE((is_double == 0 || is_double == 1) && form >= 0 && form <= 3 && (nrhs == 1 || nrhs == 2) && nt >= -1 && nt <= 1 &&
+                         max_seg_rows >= 0 && lda_extra >= 0 && lda_extra <= 4096 && lda_extra % 32 == 0 && part_capacity >= 1,
+                     "gemv_t_ex hook: is_double 0 or 1, form in 0 .. 3, nrhs 1 or 2, nt in -1 .. 1, max_seg_rows >= 0, lda_extra a multiple of 32 "
+                     "in 0 .. 4096, part_capacity >= 1");
+        ADMM_REQUIRE(nrhs == 1 || form == 0, "gemv_t_ex hook: two right-hand sides are built for form 0 only");
+        ADMM_REQUIRE(form == 3 ? (count >= 1 && count <= kGemvHookMaxCount) : count == (form == 2 ? 2 : 1),
+                     "gemv_t_ex hook: forms 0 and 1 take one product, form 2 two, form 3 one to eight");
+        ADMM_REQUIRE(from == nullptr || form == 3, "gemv_t_ex hook: from belongs to form 3 (form 2 chains its two products itself)");
+        for (int i = 0; i < count; ++i) {
+            ADMM_REQUIRE(m[i] >= 1 && k[i] >= 1 && m[i] <= (1 << 20) && k[i] <= (1 << 20) &&
+                             ((long long)m[i] + 31 + lda_extra) * (long long)k[i] <= (1ll << 28) && part_capacity <= (1ll << 28),
+                         "gemv_t_ex hook: m and k in 1 .. 2^20, at most 2^28 elements of storage per matrix and per partial buffer");
+            ADMM_REQUIRE(A[i] && part_out[i], "gemv_t_ex hook: every A[i] and part_out[i] must not be NULL");
+            ADMM_REQUIRE(skip == nullptr || skip[i] == 0 || skip[i] == 1, "gemv_t_ex hook: skip values are 0 or 1");
+            const int f = from ? from[i] : -1;
+            ADMM_REQUIRE(f == -1 || (f >= 0 && f < count && f != i && from[f] == -1 && k[f] == m[i]),
+                         "gemv_t_ex hook: from[i] is -1 or a product that is not chained itself and has k[from[i]] == m[i]");
+            ADMM_REQUIRE(v[i] || f >= 0 || (form == 2 && i == 1), "gemv_t_ex hook: every product that is not chained needs its v[i]");
+        }
+        ADMM_REQUIRE(form != 2 || m[1] == k[0], "gemv_t_ex hook: a chain needs m[1] == k[0]");
+        ADMM_REQUIRE((form != 1 && form != 2) || (y_out && y_out[count - 1]), "gemv_t_ex hook: forms 1 and 2 need y_out of the last product");
+        const GemvExRequest q{form, nrhs, nt, max_seg_rows, lda_extra, count, fill, m, k, A, v, from, skip, part_out, part_capacity, y_out, info_out};
+        if (is_double) test_gemv_t_ex<double>(q);
+        else test_gemv_t_ex<float>(q);
+    });
+}
+
+int admm_hip_test_wide_op(const float* X, int n, int p, const float* v, float* w) {
+    return guarded([&] {
+        ADMM_REQUIRE(X && v && w, "wide_op hook: X, v and w must not be NULL");
+        ADMM_REQUIRE(n >= 1 && p >= 1 && n <= (1 << 20) && p <= (1 << 20) && ((long long)n + 31) * (long long)p <= (1ll << 28),
+                     "wide_op hook: n and p in 1 .. 2^20, at most 2^28 elements of storage");
+        test_wide_op(X, n, p, v, w);
+    });
+}
+
+int admm_hip_test_block_sprad(const double* A, int n, int p, int nblocks, double* out, int* nsteps_out) {
+    return guarded([&] {
+        ADMM_REQUIRE(A && out && nsteps_out, "block_sprad hook: A, out and nsteps_out must not be NULL");
+        ADMM_REQUIRE(n >= 1 && n <= 16384 && p >= 1 && p <= (1 << 20) && ((long long)n + 31) * (long long)p <= (1ll << 27),
+                     "block_sprad hook: n in 1 .. 16384, p in 1 .. 2^20, at most 2^27 elements of storage");
+        ADMM_REQUIRE(nblocks >= 1 && nblocks <= 64 && nblocks <= p, "block_sprad hook: nblocks in 1 .. min(64, p)");
+        ADMM_REQUIRE(block_sprad_bytes(n, nblocks) <= 3.0e9, "block_sprad hook: the blocks must fit one batch of Lanczos runs (3 GB of Gram matrices and bases)");
+        test_block_sprad(A, n, p, nblocks, out, nsteps_out);
+    });
+}
+
 int admm_hip_test_gather(const void* A, int rows, int cols, int is_double, const void* v, double* y) {
     return guarded([&] {
         ADMM_REQUIRE(A && v && y && rows > 0 && cols > 0, "bad arguments");

@@ -38,6 +38,7 @@
 #include "comm.h"
 #include "device_utils.h"
 #include "gather_kernels.h"
+#include "test_hooks.h"
 
 #include <cmath>
 #include <exception>
@@ -1452,6 +1453,31 @@ static void sbp_sprad_batch(const double* A, long long lda, int n, const std::ve
     ADMM_HIP_CHECK(hipGetLastError());
 }
 
+// device bytes of one batch of `nblocks` runs: Gram matrices, Lanczos bases and the small vectors
+double block_sprad_bytes(int n, int nblocks) {
+    return (double)round_up(n, 32) * ((double)round_up(n, 32) + (double)std::min(n, 600) + 8.0) * 8.0 * (double)nblocks;
+}
+
+// admm_hip_test_block_sprad: sbp_sprad_batch over the partition of solve_parbp (N - 1 blocks of p div N columns, the last takes the
+// remainder) of a host matrix, stored as DeviceData stores it (leading dimension round_up(n, 32), zero padded), all blocks in one batch.
+void require_device();
+void test_block_sprad(const double* A, int n, int p, int nblocks, double* out, int* nsteps_out) {
+    require_device();
+    Stream st;
+    const long long lda = round_up(n, 32);
+    DevBuf<double> dA((size_t)lda * p);
+    dA.zero(st.s);
+    ADMM_HIP_CHECK(hipMemcpy2DAsync(dA.get(), lda * sizeof(double), A, (size_t)n * sizeof(double), (size_t)n * sizeof(double), p, hipMemcpyHostToDevice, st.s));
+    const int chunk = p / nblocks;
+    std::vector<int> c0(nblocks + 1);
+    for (int b = 0; b < nblocks; ++b) c0[b] = b * chunk;
+    c0[nblocks] = p;
+    std::vector<double> sprad(nblocks, 0.0);
+    std::vector<int> ns(nblocks, 0);
+    sbp_sprad_batch(dA.get(), lda, n, c0, 0, nblocks, st.s, sprad.data(), ns.data());
+    for (int b = 0; b < nblocks; ++b) { out[b] = sprad[b]; nsteps_out[b] = ns[b]; }
+}
+
 // d: this rank's columns (n x pl).  nblocks: N (global); blk_first / nloc: the global blocks this rank holds; p_total.
 void solve_parbp(const DeviceData<double>& d, const admm_opts& opts, int nblocks, long long p_total, long long col_offset,
                  DenseResult& res, hipStream_t st) {
@@ -1488,7 +1514,7 @@ void solve_parbp(const DeviceData<double>& d, const admm_opts& opts, int nblocks
     int lsteps = 0;
     {
         // as many blocks in lockstep as ~3 GB of Gram matrices and Lanczos bases allow
-        const double per = (double)round_up(n, 32) * ((double)round_up(n, 32) + (double)std::min(n, 600) + 8.0) * 8.0;
+        const double per = block_sprad_bytes(n, 1);
         const int Bmax = std::max(1, std::min(NL, (int)(3.0e9 / per)));
         for (int b = 0; b < NL; b += Bmax) {
             const int B = std::min(Bmax, NL - b);

@@ -25,6 +25,17 @@ template <typename T> void test_cholesky_linvt(const T* A, int n, T* L, T* U);
 template <typename T> void test_gemm_nt(bool lower, bool mirror, bool kstart_row, bool b_lower, bool in_place, int M, int N, int K, double alpha, double beta,
                                         const T* A, const T* B, T* C);
 template <typename T> void test_gemv_t(const T* A, int rows, int cols, const T* v, T* y);
+constexpr int kGemvHookMaxCount = 8;      // products of one admm_hip_test_gemv_t_ex call
+struct GemvExRequest {                    // admm_hip_test_gemv_t_ex's arguments, checked by api.hip as far as that goes without a device
+    int form, nrhs, nt, max_seg_rows, lda_extra, count;
+    unsigned long long fill;
+    const int* m; const int* k; const void* const* A; const void* const* v; const int* from; const int* skip;
+    void* const* part_out; long long part_capacity; void* const* y_out; long long* info_out;
+};
+template <typename T> void test_gemv_t_ex(const GemvExRequest& q);
+void test_wide_op(const float* X, int n, int p, const float* v, float* w);
+void test_block_sprad(const double* A, int n, int p, int nblocks, double* out, int* nsteps_out);      // sharing_bp.hip
+double block_sprad_bytes(int n, int nblocks);      // sharing_bp.hip: device bytes of one batch of nblocks Lanczos runs (host only)
 template <typename T> void test_gather(const T* A, int rows, int cols, const T* v, double* y);
 void test_cv_fold_system(const double* x, const double* y, int n, int p, const int* fold_id, int nfolds, int fold,
                          int standardize, int intercept, float* gram, float* xy, float* mean_x, float* scale_x, float* mean_scale_y);

@@ -3,6 +3,7 @@
 #include "symv_kernels.h"
 #include "prep.h"
 #include "gather_kernels.h"
+#include "gemv_kernels.h"
 #include "test_hooks.h"
 #include <cstring>
 #include <limits>
@@ -499,6 +500,141 @@ void test_gemv_t(const T* A, int rows, int cols, const T* v, T* y) {
 }
 template void test_gemv_t<float>(const float*, int, int, const float*, float*);
 template void test_gemv_t<double>(const double*, int, int, const double*, double*);
+
+// ---- every launch form of gemv_t (tests/test_gpu_gemv_family.py): launch_gemv_t with one or two right-hand sides, GemvT::run, the chain
+// GemvT::run_partials -> GemvT::run_from, and gemv_t_batch_kernel over argument blocks of different shapes (with a second batched launch
+// for the blocks whose right-hand side is the partial rows of a block of the first).  Storage as the callers hold it, but hostile where
+// they promise nothing: rows [m, round_up(m, 32)) of a matrix are zero (the callers' contract), every row beyond them and the tail of
+// every right-hand vector is NaN, and every partial / output buffer starts as the caller's bit pattern.
+template <typename T>
+void test_gemv_t_ex(const GemvExRequest& q) {
+    require_device();
+    Stream st;
+    struct Prod {
+        GemvT<T> g;
+        DevBuf<T> dA, dv, dy;
+        long long lda = 0;
+        int from = -1, route = 0, vparts = 1, width = 0, nt = 0;
+    } P[kGemvHookMaxCount];
+    DevBuf<int> dskip(q.count);
+    std::vector<int> hskip(q.count, 0);
+    std::vector<std::vector<T>> keep;                                 // host staging, alive until the stream has been synchronised
+    struct SyncOnExit { hipStream_t s; ~SyncOnExit() { (void)hipStreamSynchronize(s); } } sync_first{st.s};      // (on a refusal too)
+    const auto upload = [&](T* dst, std::vector<T>&& h) {
+        keep.push_back(std::move(h));
+        ADMM_HIP_CHECK(hipMemcpyAsync(dst, keep.back().data(), keep.back().size() * sizeof(T), hipMemcpyHostToDevice, st.s));
+    };
+    T pattern;
+    std::memcpy(&pattern, &q.fill, sizeof(T));                         // (float: the low 32 bits)
+    const auto fill = [&](DevBuf<T>& b) { upload(b.get(), std::vector<T>(b.n, pattern)); };
+    const T nan = std::numeric_limits<T>::quiet_NaN();
+    const size_t cap = (size_t)q.part_capacity;
+
+    for (int i = 0; i < q.count; ++i) {
+        Prod& p = P[i];
+        const int m = q.m[i], k = q.k[i];
+        p.from = q.form == 2 ? (i == 1 ? 0 : -1) : (q.from ? q.from[i] : -1);
+        p.lda = round_up(m, 32) + q.lda_extra;
+        std::vector<T> hA((size_t)p.lda * k, nan);
+        const T* A = static_cast<const T*>(q.A[i]);
+        for (int j = 0; j < k; ++j) {
+            std::memcpy(&hA[(size_t)j * p.lda], A + (size_t)j * m, (size_t)m * sizeof(T));
+            for (long long r = m; r < round_up(m, 32); ++r) hA[(size_t)j * p.lda + r] = T(0);
+        }
+        p.dA.alloc(hA.size());
+        upload(p.dA.get(), std::move(hA));
+        if (p.from < 0) {
+            std::vector<T> hv((size_t)q.nrhs * p.lda, nan);
+            for (int r = 0; r < q.nrhs; ++r) std::memcpy(&hv[(size_t)r * p.lda], static_cast<const T*>(q.v[i]) + (size_t)r * m, (size_t)m * sizeof(T));
+            p.dv.alloc(hv.size());
+            upload(p.dv.get(), std::move(hv));
+        }
+        p.g.init(p.dA.get(), p.lda, m, k);                             // (the plan of the solvers' struct, big64 included)
+        if (q.form == 0 || q.max_seg_rows > 0) p.g.pl = plan_gemv_t<T>(m, k, q.nrhs, 4, q.max_seg_rows);
+        if (q.nt >= 0) p.g.set_nt(q.nt != 0);
+        ADMM_REQUIRE((size_t)p.g.pl.nseg * (size_t)p.g.stride <= cap,
+                     "gemv_t_ex hook: part_capacity is too small for the " + std::to_string((size_t)p.g.pl.nseg * (size_t)p.g.stride) + " elements of product " +
+                         std::to_string(i) + "'s partial rows");
+        p.g.part = DevBuf<T>((size_t)q.nrhs * cap);
+        p.dy.alloc((size_t)p.g.stride);
+        fill(p.g.part); fill(p.dy);
+    }
+    if (q.skip) hskip.assign(q.skip, q.skip + q.count);
+    ADMM_HIP_CHECK(hipMemcpyAsync(dskip.get(), hskip.data(), hskip.size() * sizeof(int), hipMemcpyHostToDevice, st.s));
+    for (int i = 0; i < q.count; ++i) {
+        Prod& p = P[i];
+        p.nt = p.g.pl.nt ? 1 : 0; p.width = p.g.pl.grid;
+        if (p.from >= 0) p.vparts = P[p.from].g.pl.nseg;
+        p.route = p.vparts > 1 ? 1 : 0;
+    }
+
+    if (q.form == 0) {
+        Prod& p = P[0];
+        T* part = p.g.part.get();
+        if (q.nrhs == 1)
+            launch_gemv_t<T, 1, 4>(p.g.pl, p.dA.get(), p.lda, p.g.m, p.g.k, p.dv.get(), nullptr, part, nullptr, p.g.stride, dskip.get(), st.s);
+        else
+            launch_gemv_t<T, 2, 4>(p.g.pl, p.dA.get(), p.lda, p.g.m, p.g.k, p.dv.get(), p.dv.get() + p.lda, part, part + cap, p.g.stride, dskip.get(), st.s);
+    } else if (q.form == 1) {
+        P[0].g.run(P[0].dv.get(), P[0].dy.get(), dskip.get(), st.s);
+    } else if (q.form == 2) {
+        Prod& a = P[0];
+        Prod& b = P[1];
+        if (b.g.pl.nseg > 1 && a.g.pl.nseg > GemvT<T>::kChainRows) {   // the reduce route: its buffer is the struct's, allocated here so that it starts as the pattern
+            b.g.red.alloc((size_t)round_up(b.g.m, 32));
+            fill(b.g.red);
+            b.route = 2;
+        }
+        a.g.run_partials(a.dv.get(), dskip.get(), st.s);
+        b.g.run_from(a.g, b.dy.get(), dskip.get() + 1, st.s);
+    } else {
+        for (int stage = 0; stage < 2; ++stage) {
+            std::vector<GemvTArgs<T>> ha;
+            int width = 0, nt = 0;
+            size_t lds = 0;
+            for (int i = 0; i < q.count; ++i) {
+                Prod& p = P[i];
+                if ((p.from >= 0) != (stage == 1)) continue;
+                ha.push_back(stage == 0 ? p.g.args_partials(p.dv.get(), dskip.get() + i) : p.g.args_partials_from(P[p.from].g, dskip.get() + i));
+                width = std::max(width, p.g.pl.grid); lds = std::max(lds, p.g.pl.lds_bytes); nt |= p.g.pl.nt ? 1 : 0;
+            }
+            if (ha.empty()) continue;
+            for (int i = 0; i < q.count; ++i) if ((P[i].from >= 0) == (stage == 1)) { P[i].width = width; P[i].nt = nt; }
+            DevBuf<GemvTArgs<T>> dargs(ha.size());
+            ADMM_HIP_CHECK(hipMemcpyAsync(dargs.get(), ha.data(), ha.size() * sizeof(GemvTArgs<T>), hipMemcpyHostToDevice, st.s));
+            launch_gemv_t_batch<T>(dargs.get(), (int)ha.size(), width, lds, nt != 0, st.s);
+            st.sync();                                                 // the argument blocks go out of scope
+        }
+    }
+    ADMM_HIP_CHECK(hipGetLastError());
+    for (int i = 0; i < q.count; ++i) {
+        Prod& p = P[i];
+        ADMM_HIP_CHECK(hipMemcpyAsync(q.part_out[i], p.g.part.get(), (size_t)q.nrhs * cap * sizeof(T), hipMemcpyDeviceToHost, st.s));
+        if ((q.form == 1 || q.form == 2) && i == q.count - 1)
+            ADMM_HIP_CHECK(hipMemcpyAsync(q.y_out[i], p.dy.get(), (size_t)p.g.stride * sizeof(T), hipMemcpyDeviceToHost, st.s));
+        long long* info = q.info_out + 8 * i;
+        info[0] = p.g.pl.nseg; info[1] = p.g.pl.seg_len; info[2] = p.g.pl.groups_per_wg; info[3] = p.g.pl.grid; info[4] = p.nt;
+        info[5] = p.route; info[6] = p.vparts; info[7] = p.width;
+    }
+    st.sync();
+}
+template void test_gemv_t_ex<float>(const GemvExRequest&);
+template void test_gemv_t_ex<double>(const GemvExRequest&);
+
+// w = X (X'v) through the wide solver's Gram-free operator (prep.hip: gemv_t_simple, gemv_n_partial_kernel, the ordered sum of its partial
+// rows) on the storage DeviceData gives it: leading dimension round_up(n, 32), the padding rows zero.
+void test_wide_op(const float* X, int n, int p, const float* v, float* w) {
+    require_device();
+    Stream st;
+    const long long ldx = round_up(n, 32);
+    DevBuf<float> dX((size_t)ldx * p);
+    dX.zero(st.s);
+    ADMM_HIP_CHECK(hipMemcpy2DAsync(dX.get(), ldx * sizeof(float), X, (size_t)n * sizeof(float), (size_t)n * sizeof(float), p, hipMemcpyHostToDevice, st.s));
+    GramFreeWideOp op(dX.get(), ldx, n, p, st.s);
+    op(v, w);
+    st.sync();
+    ADMM_HIP_CHECK(hipGetLastError());
+}
 
 // y = A v over the non-zeros of v through the gather mat-vec of the one-pass forms (gather_kernels.h): A host, rows x cols
 // column-major (ld rows), v length cols, y length rows in DOUBLE (the kernel accumulates in double whatever T is); the column

@@ -768,6 +768,36 @@ ADMM_HIP_API int admm_hip_test_gram(const void* A, int rows, int cols, int atA, 
 /* y = A' v with the streaming mat-vec every other product of the solvers uses (X'y, the wide regular step, the consensus /
  * LAD / BP products, the tall x-update below p = 2048): A HOST rows x cols column-major (leading dimension rows). */
 ADMM_HIP_API int admm_hip_test_gemv_t(const void* A, int rows, int cols, int is_double, const void* v, void* y);
+/* Every launch form of that mat-vec (gemv_kernels.h) on `count` products y_i = A_i' v_i: A[i] HOST m[i] x k[i] column-major (leading
+ * dimension m[i]), float or double (is_double), v[i] HOST [nrhs][m[i]].  On the device a matrix is stored as the callers hold it: leading
+ * dimension round_up(m, 32) + lda_extra (a multiple of 32), rows [m, round_up(m, 32)) zero, every row beyond and the tail of v NaN.
+ * form 0: launch_gemv_t, partial rows only (count 1; nrhs 1 or 2, the two-vector instantiation of the tall fallback's body).
+ * form 1: GemvT::run (count 1): the one-segment shortcut straight into y, or partial rows and the reduce launch.
+ * form 2: a chain (count 2, m[1] == k[0]): GemvT::run_partials on product 0, GemvT::run_from on product 1, whose right-hand side is the
+ *         un-reduced partial rows of product 0 -- staged in the kernel, or behind a reduce launch beyond 12 rows, as the struct decides.
+ * form 3: gemv_t_batch_kernel, one launch of `count` (<= 8) argument blocks as wide as the widest; from (NULL: none) names for product i
+ *         the product (from[i] >= 0, itself not chained, k[from[i]] == m[i]) whose partial rows are its right-hand side: those products
+ *         go into a second batched launch behind the first.  v[i] is not read for a chained product.
+ * nt: 0 plain loads, 1 non-temporal loads, -1 the plan's own choice.  max_seg_rows: 0 the default plan, otherwise the cap on the rows of
+ * a segment handed to plan_gemv_t (2048 is what GemvT::init takes for fp64 operands beyond the cache).  skip (NULL: zeros): the value
+ * of product i's device skip flag.  Every partial and output buffer is pre-filled with the pattern `fill` (float: its low 32 bits).
+ * part_out[i]: [nrhs][part_capacity] elements, the partial rows [nseg][round_up(k, 32)] as the launch left them and `fill` behind (a
+ * part_capacity below nseg rows: ADMM_ERR_INVALID_ARG).  y_out (forms 1 and 2, the last product): round_up(k, 32) elements.
+ * info_out [count][8]: nseg, seg_len, groups_per_wg, grid, 1 if non-temporal loads ran, the route of the right-hand side (0 a plain
+ * vector, 1 partial rows summed in the kernel, 2 summed by a reduce launch into a single row), the partial rows it arrived in, and the
+ * width of the launch (form 3: of the batched launch).  Inconsistent requests: ADMM_ERR_INVALID_ARG before any launch. */
+ADMM_HIP_API int admm_hip_test_gemv_t_ex(int is_double, int form, int nrhs, int nt, int max_seg_rows, int lda_extra, unsigned long long fill,
+                                         int count, const int* m, const int* k, const void* const* A, const void* const* v, const int* from,
+                                         const int* skip, void* const* part_out, long long part_capacity, void* const* y_out,
+                                         long long* info_out);
+/* w = X (X' v), the Gram-free operator under the wide solver's spectral-radius estimate (GramFreeWideOp: the streaming mat-vec above,
+ * then gemv_n_partial_kernel and its ordered sum): X HOST n x p float column-major (leading dimension n), v and w HOST length n. */
+ADMM_HIP_API int admm_hip_test_wide_op(const float* X, int n, int p, const float* v, float* w);
+/* The spectral radii admm_hip_parbp takes for its column blocks: out[b] = its estimate of lambda_max(A_b'A_b) for the nblocks blocks of
+ * the solver's own partition of the p columns (nblocks - 1 blocks of p div nblocks columns, the last takes the rest) of the HOST double
+ * matrix A (n x p column-major, leading dimension n), all blocks in ONE batch of Lanczos runs in lockstep; nsteps_out[b]: the steps
+ * block b was judged on.  ADMM_ERR_EIGS as the solver raises it. */
+ADMM_HIP_API int admm_hip_test_block_sprad(const double* A, int n, int p, int nblocks, double* out, int* nsteps_out);
 /* y = A v over the NON-ZERO entries of v with the gather mat-vec of the one-pass consensus workers and of basis pursuit (the product
  * that replaces the reference's first streaming pass, PADMMLasso.h:25 / ADMMBP.h:65): A HOST rows x cols column-major (leading
  * dimension rows), v length cols in A's type, y length rows in double (the kernel's accumulation type). */

@@ -724,3 +724,108 @@ def test_well_formed_calls_pass_every_check_and_then_find_no_device():
     for entry in SIGNATURES:
         if entry not in DIST:
             assert _call(lib, entry, {})[0] == NO_DEVICE, (entry, lib.admm_hip_last_error())
+
+
+# ---- the hooks of the shared mat-vec family (tests/test_gpu_gemv_family.py, tests/test_gpu_block_sprad.py): argument checks only
+_GEMV_EX = "is_double form nrhs nt max_seg_rows lda_extra fill count m k A v from skip part_out part_capacity y_out info_out"
+_GEMV_SHAPE = "gemv_t_ex hook: m and k in 1 .. 2^20, at most 2^28 elements of storage per matrix and per partial buffer"
+_GEMV_SCALARS = ("gemv_t_ex hook: is_double 0 or 1, form in 0 .. 3, nrhs 1 or 2, nt in -1 .. 1, max_seg_rows >= 0, lda_extra a multiple of 32 in 0 .. 4096, "
+                 "part_capacity >= 1")
+_GEMV_COUNT = "gemv_t_ex hook: forms 0 and 1 take one product, form 2 two, form 3 one to eight"
+_GEMV_FROM = "gemv_t_ex hook: from[i] is -1 or a product that is not chained itself and has k[from[i]] == m[i]"
+# (overrides of a well-formed form-3 call of three 4 x 4 products, the message of the refusal)
+GEMV_EX_TABLE = [
+    (dict(m=None), "gemv_t_ex hook: m, k, A, v, part_out and info_out must not be NULL"),
+    (dict(A=None), "gemv_t_ex hook: m, k, A, v, part_out and info_out must not be NULL"),
+    (dict(info_out=None), "gemv_t_ex hook: m, k, A, v, part_out and info_out must not be NULL"),
+    (dict(is_double=2), _GEMV_SCALARS), (dict(form=4), _GEMV_SCALARS), (dict(form=-1), _GEMV_SCALARS), (dict(nrhs=3), _GEMV_SCALARS),
+    (dict(nt=2), _GEMV_SCALARS), (dict(nt=-2), _GEMV_SCALARS), (dict(max_seg_rows=-1), _GEMV_SCALARS), (dict(lda_extra=16), _GEMV_SCALARS),
+    (dict(lda_extra=8192), _GEMV_SCALARS), (dict(part_capacity=0), _GEMV_SCALARS),
+    (dict(nrhs=2), "gemv_t_ex hook: two right-hand sides are built for form 0 only"),
+    (dict(form=0), _GEMV_COUNT), (dict(form=1), _GEMV_COUNT), (dict(form=2), _GEMV_COUNT), (dict(count=0), _GEMV_COUNT), (dict(count=9), _GEMV_COUNT),
+    (dict(form=2, count=2, **{"from": (-1, 0, -1)}), "gemv_t_ex hook: from belongs to form 3 (form 2 chains its two products itself)"),
+    (dict(m=(4, 0, 4)), _GEMV_SHAPE), (dict(k=(4, 4, (1 << 20) + 1)), _GEMV_SHAPE), (dict(m=(1 << 20, 4, 4), k=(1 << 20, 4, 4)), _GEMV_SHAPE),
+    (dict(A_null=1), "gemv_t_ex hook: every A[i] and part_out[i] must not be NULL"),
+    (dict(part_null=2), "gemv_t_ex hook: every A[i] and part_out[i] must not be NULL"),
+    (dict(skip=(0, 2, 0)), "gemv_t_ex hook: skip values are 0 or 1"),
+    (dict(**{"from": (-1, 3, -1)}), _GEMV_FROM), (dict(**{"from": (-1, 1, -1)}), _GEMV_FROM), (dict(**{"from": (1, 0, -1)}), _GEMV_FROM),
+    (dict(k=(5, 4, 4), **{"from": (-1, 0, -1)}), _GEMV_FROM),
+    (dict(v_null=0), "gemv_t_ex hook: every product that is not chained needs its v[i]"),
+    (dict(form=2, count=2, m=(4, 5, 4)), "gemv_t_ex hook: a chain needs m[1] == k[0]"),
+    (dict(form=1, count=1, y_out=None), "gemv_t_ex hook: forms 1 and 2 need y_out of the last product"),
+    (dict(form=2, count=2, y_null=1), "gemv_t_ex hook: forms 1 and 2 need y_out of the last product"),
+]
+GEMV_EX_GOOD = [dict(), dict(**{"from": (-1, 0, -1)}, v_null=1), dict(form=0, count=1, nrhs=2), dict(form=1, count=1), dict(form=2, count=2, v_null=1),
+                dict(is_double=1, nt=1, max_seg_rows=128, lda_extra=64, skip=(1, 0, 1))]
+
+
+def _gemv_ex(lib, over):
+    n = 3
+    keep = [np.zeros(64) for _ in range(4 * n)]
+    v = dict(is_double=0, form=3, nrhs=1, nt=-1, max_seg_rows=0, lda_extra=0, fill=0x7FC00000, count=n, m=(4,) * n, k=(4,) * n, skip=None, part_capacity=64,
+             info_out=(ctypes.c_longlong * (8 * n))(), **{"from": None})
+    arrays = {name: [keep[n * j + i].ctypes.data for i in range(n)] for j, name in enumerate(("A", "v", "part_out", "y_out"))}
+    over = dict(over)
+    for name, key in (("A", "A_null"), ("v", "v_null"), ("part_out", "part_null"), ("y_out", "y_null")):
+        if key in over:
+            arrays[name][over.pop(key)] = None
+    v.update({name: (ctypes.c_void_p * n)(*ptrs) for name, ptrs in arrays.items()})
+    v.update(over)
+    for name in ("m", "k", "from", "skip"):
+        if v[name] is not None:
+            v[name] = (ctypes.c_int * n)(*v[name])
+    rc = lib.admm_hip_test_gemv_t_ex(*[v[name] for name in _GEMV_EX.split()])
+    return rc, lib.admm_hip_last_error().decode()
+
+
+def test_the_gemv_family_hook_refuses_bad_requests_before_it_looks_for_a_device():
+    from admm_amd import _lib
+    lib = _lib.load()
+    for over, message in GEMV_EX_TABLE:
+        assert _gemv_ex(lib, over) == (INVALID_ARG, message), over
+
+
+_WIDE_SHAPE = "wide_op hook: n and p in 1 .. 2^20, at most 2^28 elements of storage"
+_SPRAD_SHAPE = "block_sprad hook: n in 1 .. 16384, p in 1 .. 2^20, at most 2^27 elements of storage"
+# (hook, overrides of a well-formed call on 4 x 6 data, message)
+SMALL_HOOK_TABLE = [
+    ("wide_op", dict(X=None), "wide_op hook: X, v and w must not be NULL"), ("wide_op", dict(v=None), "wide_op hook: X, v and w must not be NULL"),
+    ("wide_op", dict(w=None), "wide_op hook: X, v and w must not be NULL"), ("wide_op", dict(n=0), _WIDE_SHAPE), ("wide_op", dict(p=-1), _WIDE_SHAPE),
+    ("wide_op", dict(n=(1 << 20) + 1), _WIDE_SHAPE), ("wide_op", dict(n=1 << 20, p=1 << 20), _WIDE_SHAPE),
+    ("block_sprad", dict(A=None), "block_sprad hook: A, out and nsteps_out must not be NULL"),
+    ("block_sprad", dict(out=None), "block_sprad hook: A, out and nsteps_out must not be NULL"),
+    ("block_sprad", dict(nsteps_out=None), "block_sprad hook: A, out and nsteps_out must not be NULL"),
+    ("block_sprad", dict(n=0), _SPRAD_SHAPE), ("block_sprad", dict(n=16385), _SPRAD_SHAPE), ("block_sprad", dict(p=0), _SPRAD_SHAPE),
+    ("block_sprad", dict(n=16384, p=1 << 14), _SPRAD_SHAPE),
+    ("block_sprad", dict(nblocks=0), "block_sprad hook: nblocks in 1 .. min(64, p)"), ("block_sprad", dict(nblocks=7), "block_sprad hook: nblocks in 1 .. min(64, p)"),
+    ("block_sprad", dict(p=100, nblocks=65), "block_sprad hook: nblocks in 1 .. min(64, p)"),
+    ("block_sprad", dict(n=8000, p=8000, nblocks=6), "block_sprad hook: the blocks must fit one batch of Lanczos runs (3 GB of Gram matrices and bases)"),
+]
+
+
+def _small_hook(lib, hook, over):
+    keep = dict(X=np.zeros(24, np.float32), v=np.zeros(4, np.float32), w=np.zeros(4, np.float32), A=np.zeros(24), out=np.zeros(6),
+                nsteps_out=np.zeros(6, np.int32))
+    types = dict(X=ctypes.c_float, v=ctypes.c_float, w=ctypes.c_float, A=ctypes.c_double, out=ctypes.c_double, nsteps_out=ctypes.c_int)
+    v = dict({name: _pointer(a, types[name]) for name, a in keep.items()}, n=4, p=6, nblocks=2)
+    v.update(over)
+    names = "X n p v w" if hook == "wide_op" else "A n p nblocks out nsteps_out"
+    rc = getattr(lib, "admm_hip_test_" + hook)(*[v[name] for name in names.split()])
+    return rc, lib.admm_hip_last_error().decode()
+
+
+def test_the_wide_op_and_block_sprad_hooks_refuse_bad_requests_before_they_look_for_a_device():
+    from admm_amd import _lib
+    lib = _lib.load()
+    for hook, over, message in SMALL_HOOK_TABLE:
+        assert _small_hook(lib, hook, over) == (INVALID_ARG, message), (hook, over)
+
+
+@pytest.mark.skipif(os.path.exists("/dev/kfd"), reason="only meaningful on a machine without a GPU")
+def test_well_formed_hook_requests_pass_every_check_and_then_find_no_device():
+    from admm_amd import _lib
+    lib = _lib.load()
+    for over in GEMV_EX_GOOD:
+        assert _gemv_ex(lib, over)[0] == NO_DEVICE, (over, lib.admm_hip_last_error())
+    for hook in ("wide_op", "block_sprad"):
+        assert _small_hook(lib, hook, {})[0] == NO_DEVICE, (hook, lib.admm_hip_last_error())
