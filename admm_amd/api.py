@@ -771,6 +771,127 @@ class ADMM_LogitOvR(ADMM_LogitMulti):
         return fit
 
 
+class ADMM_LogitRidge_fit:
+    def __init__(self, lam, beta, niter, stats):
+        self.lam = lam              # numeric nlambda, in the order given
+        self.beta = beta            # (p + 1) x k x nlambda, intercept first          (fit(trace=True): p + 1)
+        self.niter = niter          # integer k x nlambda; maxit + 1: not converged   (fit(trace=True): a scalar)
+        self.stats = stats
+
+    def __repr__(self):
+        shape = " x ".join(str(s) for s in np.shape(self.beta))
+        return f"ADMM ridge logistic regression fitting result\n\n$lambda\n{self.lam}\n\n$beta\n<{shape}> array\n\n$niter\n{self.niter}"
+
+    def show(self):
+        print(repr(self))
+
+
+class ADMM_LogitRidge(ADMM_LAD):
+    """Ridge logistic regression (admm_hip_logit_ridge): per label column c and lambda l
+        minimise  sum_i log(1 + exp(-s_i (b0 + x~_i'b))) + lam[l] / 2 sum_j b_j^2,   s = 2 Y[:, c] - 1,
+    on the library's standardised columns x~ (scikit-learn's C is 1 / lam on standardised x), the intercept not penalised, the
+    coefficients returned on the caller's scale.  Y as ADMM_LogitMulti's; lam: a positive scalar or vector, used in the order given,
+    every fit from a cold start.  There is no condition on nrow(x) against ncol(x), and separable labels have an estimate."""
+
+    def __init__(self, x, Y, lam, intercept=True, n=None, p=None, k=None):
+        n_, p_ = _shape(x, n, p)
+        if n_ < 2:
+            _stop("nrow(x) must be at least 2")
+        if isinstance(Y, DevicePtr):
+            if k is None:
+                _stop("k is required with a DevicePtr")
+            k_ = int(k)
+        else:
+            Y = np.asarray(Y, dtype=np.float64)
+            if Y.ndim == 1:
+                Y = Y[:, None]
+            if Y.ndim != 2:
+                _stop("Y must be a matrix")
+            Y = np.asfortranarray(Y)
+            k_ = Y.shape[1]
+            if Y.shape[0] != n_:
+                _stop("nrow(x) should be equal to nrow(Y)")
+        if k_ < 1:
+            _stop("y must have at least one column")
+        lm = np.atleast_1d(np.asarray(lam, dtype=np.float64))
+        if lm.ndim != 1 or lm.size < 1:
+            _stop("lam must hold at least one value")
+        if not (np.all(np.isfinite(lm)) and np.all(lm > 0)):
+            _stop("every lambda must be finite and positive (lambda = 0 is admm_logit_multi)")
+        if not isinstance(Y, DevicePtr):
+            for c in range(k_):
+                col = Y[:, c]
+                if not np.all((col == 0.0) | (col == 1.0)):
+                    _stop(f"column {c} of y: every label must be exactly 0 or 1")
+                if np.all(col == 0.0) or np.all(col == 1.0):
+                    _stop(f"column {c} of y must hold both classes")
+        self.x, self.y, self.n, self.p, self.k = x, Y, int(n_), int(p_), k_
+        self.lam = np.ascontiguousarray(lm)
+        self.maxit = 10000
+        self.eps_abs = 1e-4
+        self.eps_rel = 1e-4
+        self.rho = 1.0
+        self.intercept = bool(intercept)
+
+    def fit(self, trace=False, state=0):
+        """-> ADMM_LogitRidge_fit.  trace / state (admm_hip_logit_ridge_state) for one column and one lambda only: beta is then the
+        vector p + 1 and niter a scalar, and the iterate dump has dimension n + p (the ridge rows behind the data rows); its record 0
+        carries the zero response in its x slot and [2 y - 1, 0 ... 0] in its z slot."""
+        lib = _lib.load()
+        xp, xmem, xk = as_input(self.x)
+        yp, ymem, yk = as_input(self.y)
+        if xmem != ymem:
+            _stop("x and y must live in the same memory space")
+        nlam = int(self.lam.size)
+        if (trace or state) and (self.k != 1 or nlam != 1):
+            _stop("trace and state are recorded for a single label column and a single lambda")
+        o = AdmmOpts(self.maxit, self.eps_abs, self.eps_rel, self.rho)
+        beta = np.zeros((self.p + 1) * self.k * nlam, dtype=np.float64)
+        niter = np.zeros(self.k * nlam, dtype=np.int32)
+        stats = AdmmStats()
+        dp = ctypes.POINTER(ctypes.c_double)
+        bp, np_ = beta.ctypes.data_as(dp), niter.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+        if trace:
+            tr, ntr = _trace_buffers(self.maxit)
+            sbuf, nst = _state_buffers(state, self.n + self.p)
+            check(lib.admm_hip_logit_ridge_state(xp, yp, self.n, self.p, xmem, int(self.intercept), float(self.lam[0]), ctypes.byref(o), bp, np_,
+                                                 ctypes.byref(stats), *_trace_args(tr, ntr), *_state_args(sbuf, nst)))
+            fit = ADMM_LogitRidge_fit(self.lam.copy(), beta, int(niter[0]), stats.as_dict())
+            fit.trace = tr[:ntr.value].copy()
+            fit.state = sbuf[:nst.value].copy() if state else None
+            return fit
+        check(lib.admm_hip_logit_ridge(xp, yp, self.n, self.p, self.k, xmem, int(self.intercept), self.lam.ctypes.data_as(dp), nlam, ctypes.byref(o), bp, np_,
+                                       ctypes.byref(stats)))
+        fit = ADMM_LogitRidge_fit(self.lam.copy(), beta.reshape((self.p + 1, self.k, nlam), order="F"), niter.reshape((self.k, nlam), order="F"),
+                                  stats.as_dict())
+        fit.trace = fit.state = None
+        return fit
+
+
+class ADMM_LogitRidgeOvR(ADMM_LogitRidge):
+    """One-vs-rest on ADMM_LogitRidge: the indicator matrix of ADMM_LogitOvR, `classes` sorted, column c separates classes[c] from the rest."""
+
+    def __init__(self, x, labels, lam, intercept=True, n=None, p=None):
+        lab = np.asarray(labels)
+        if lab.ndim != 1:
+            _stop("labels must be a vector")
+        if not (np.issubdtype(lab.dtype, np.integer) or np.issubdtype(lab.dtype, np.bool_)):
+            if not (np.issubdtype(lab.dtype, np.floating) and np.all(np.isfinite(lab)) and np.all(lab == np.round(lab))):
+                _stop("labels must be integers")
+            lab = lab.astype(np.int64)
+        classes = np.unique(lab)
+        if classes.size < 2:
+            _stop("labels must hold at least two classes")
+        ADMM_LogitRidge.__init__(self, x, (lab[:, None] == classes[None, :]).astype(np.float64), lam, intercept, n, p)
+        self.classes = classes
+
+    def fit(self, trace=False, state=0):
+        """-> ADMM_LogitRidge_fit with `classes`."""
+        fit = ADMM_LogitRidge.fit(self, trace, state)
+        fit.classes = self.classes
+        return fit
+
+
 class LassoPlan:
     """Prepared problem (admm_hip_lasso_plan_*): setup once, run the lambda path repeatedly.
 
@@ -893,6 +1014,14 @@ def admm_logit_multi(x, Y, intercept=True, **kw):
 
 def admm_logit_ovr(x, labels, intercept=True, **kw):
     return ADMM_LogitOvR(x, labels, intercept, **kw)
+
+
+def admm_logit_ridge(x, Y, lam, intercept=True, **kw):
+    return ADMM_LogitRidge(x, Y, lam, intercept, **kw)
+
+
+def admm_logit_ridge_ovr(x, labels, lam, intercept=True, **kw):
+    return ADMM_LogitRidgeOvR(x, labels, lam, intercept, **kw)
 
 
 def admm_bp(x, y, **kw):

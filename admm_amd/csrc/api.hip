@@ -153,6 +153,20 @@ int admm_hip_logit_multi(const double* x, const double* y, int n, int p, int k, 
     return guarded([&] { logit_multi(x, y, n, p, k, mem, intercept, opts, DenseOut{beta_out, niter_out, stats}); });
 }
 
+int admm_hip_logit_ridge(const double* x, const double* y, int n, int p, int k, int mem, int intercept, const double* lambda, int nlambda, const admm_opts* opts,
+                         double* beta_out, int* niter_out, admm_stats* stats) {
+    return guarded([&] { logit_ridge(x, y, n, p, k, mem, intercept, lambda, nlambda, opts, DenseOut{beta_out, niter_out, stats}); });
+}
+
+int admm_hip_logit_ridge_state(const double* x, const double* y, int n, int p, int mem, int intercept, double lambda, const admm_opts* opts, double* beta_out,
+                               int* niter_out, admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out, double* state_out,
+                               long long state_cap, long long* nstate_out) {
+    return guarded([&] {
+        logit_ridge(x, y, n, p, 1, mem, intercept, &lambda, 1, opts,
+                    DenseOut{beta_out, niter_out, stats, {trace_out, trace_cap, ntrace_out}, {state_out, state_cap, nstate_out}});
+    });
+}
+
 int admm_hip_logit_state(const double* x, const double* y, int n, int p, int mem, int intercept, const admm_opts* opts, double* beta_out, int* niter_out,
                          admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out, double* state_out, long long state_cap,
                          long long* nstate_out) {

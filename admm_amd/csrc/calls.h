@@ -64,6 +64,10 @@ void huber(const double* x, const double* y, int n, int p, int mem, int intercep
 void logit(const double* x, const double* y, int n, int p, int mem, int intercept, const admm_opts* opts, const DenseOut& out);
 // y: n x k labels, column-major, every column as logit's; out.beta_out: (p + 1) x k, out.niter_out: k; no trace / state
 void logit_multi(const double* x, const double* y, int n, int p, int k, int mem, int intercept, const admm_opts* opts, const DenseOut& out);
+// the same with a ridge penalty: nlambda values, used in the order given; out.beta_out: (p + 1) x k x nlambda, out.niter_out: k x nlambda;
+// trace / state for k = 1 and nlambda = 1 only
+void logit_ridge(const double* x, const double* y, int n, int p, int k, int mem, int intercept, const double* lambda, int nlambda, const admm_opts* opts,
+                 const DenseOut& out);
 void bp(const double* x, const double* y, int n, int p, int mem, const admm_opts* opts, const DenseOut& out);
 // admm_hip_parbp(_traced): over in-process ranks when PAR_DEVICES lists several devices; parbp_dist: this rank's columns of p_total
 void parbp(const double* x, const double* y, int n, int p, int mem, int nthread, const admm_opts* opts, const DenseOut& out);

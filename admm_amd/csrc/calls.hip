@@ -403,6 +403,47 @@ void logit_multi(const double* x, const double* y, int n, int p, int k, int mem,
     finish_result(res.dense, t0, out.trace, out.stats);
 }
 
+// admm_hip_logit_ridge: logit_multi with the ridge penalty lambda / 2 sum b_j^2 (solve_logit_ridge), one fit per (column, lambda).  The
+// penalty makes the augmented matrix of full column rank for any n: no n > p condition, separable labels have an estimate.
+void logit_ridge(const double* x, const double* y, int n, int p, int k, int mem, int intercept, const double* lambda, int nlambda, const admm_opts* opts,
+                 const DenseOut& out) {
+    const bool icpt = intercept != 0;
+    ADMM_REQUIRE(k >= 1, "y must have at least one column");
+    ADMM_REQUIRE(lambda != nullptr, "lambda must not be NULL");
+    ADMM_REQUIRE(nlambda >= 1, "lambda must have at least one value");
+    for (int l = 0; l < nlambda; ++l)
+        ADMM_REQUIRE(std::isfinite(lambda[l]) && lambda[l] > 0.0, "every lambda must be finite and positive (lambda = 0 is admm_hip_logit_multi)");
+    ADMM_REQUIRE((k == 1 && nlambda == 1) || out.trace.cap == 0, "the decision trace is recorded for a single column and a single lambda");
+    check_dense(x, y, n, p, mem, opts, n >= 2, "nrow(x) must be at least 2", true, out);
+    for (int c = 0; c < k; ++c) {
+        const double* yc = y + (size_t)c * n;
+        long long bad = 0, ones = 0;
+        if (mem == ADMM_MEM_HOST) {
+            for (int i = 0; i < n; ++i) { if (yc[i] == 1.0) ++ones; else if (!(yc[i] == 0.0)) ++bad; }
+        } else {
+            require_device();
+            Stream cs;
+            logit_count_labels(yc, n, &bad, &ones, cs.s);
+        }
+        ADMM_REQUIRE(bad == 0, "column " + std::to_string(c) + " of y: every label must be exactly 0 or 1");
+        ADMM_REQUIRE(ones > 0 && ones < n, "column " + std::to_string(c) + " of y must hold both classes");
+    }
+    require_device();
+    const double t0 = now_s();
+    Stream st;
+    DeviceData<double> d;
+    upload_standardize<double>(d, x, y, n, p, mem, true, icpt, st.s);      // (the response it standardises, column 0, is replaced by zeros)
+    Resident labels(y, (size_t)n * k, mem);
+    QuantResult res;
+    begin_result(res.dense, d, out.trace);
+    res.dense.state_cap = out.state.cap;
+    solve_logit_ridge(d, icpt, labels.p, k, lambda, nlambda, *opts, res, st.s);
+    std::memcpy(out.beta_out, res.beta.data(), res.beta.size() * sizeof(double));
+    for (size_t c = 0; c < res.niter.size(); ++c) out.niter_out[c] = res.niter[c];
+    store_state(res.dense, out.state);
+    finish_result(res.dense, t0, out.trace, out.stats);
+}
+
 void bp(const double* x, const double* y, int n, int p, int mem, const admm_opts* opts, const DenseOut& out) {
     run_dense(x, y, n, p, mem, opts, false, false,                                   // BP.cpp:24-27: no standardisation
               p > n, "ncol(x) must be greater than nrow(x)", true, p,                // R/10_admm_bp.R:30-31

@@ -71,6 +71,7 @@ struct DenseParams {
 constexpr int kDenseThreads = 256;
 constexpr int kQuantAutoSlots = 1;         // what QUANT_SLOTS=0 picks on the one-pass branch (decided by scripts/bench_quantreg.py)
 constexpr int kLogitAutoSlots = 4;         // the same for admm_hip_logit_multi: as many as the layout admits (measured: scripts/bench_logit_multi.py, profiles/logit_multi.md)
+constexpr int kLogitRidgeAutoSlots = kLogitAutoSlots;      // the same for admm_hip_logit_ridge: ahead of serial at every layout with slots (measured: scripts/bench_logit_ridge.py, profiles/logit_ridge.md)
 constexpr int kHuberAutoSlots = 4;         // the same for admm_hip_huber: as many as the layout admits (measured: scripts/bench_huber.py, profiles/huber_loss.md)
 
 __device__ __forceinline__ double soft2(double v, double hi, double lo) {
@@ -96,11 +97,16 @@ __device__ __forceinline__ double huber2(double v, double hi, double lo, double 
 // in the units of the standardised response, +inf = expectile regression) as their LAST argument, behind everything the soft-threshold
 // instantiations (LAD, BP, quantile regression) read: those neither hold nor load it and keep their registers and instruction counts
 // (profiles/huber_loss.md).
-constexpr int kProxSoft = 0, kProxHuber = 1, kProxLogit = 2, kProxLogitS = 3;
+constexpr int kProxSoft = 0, kProxHuber = 1, kProxLogit = 2, kProxLogitS = 3, kProxLogitR = 4;
 // kProxLogitS (admm_hip_logit_multi): the same loss on the UNFOLDED matrix [X | 1], the label's sign taken inside the prox --
 // prox of log(1 + e^(-s z)) / rho at v is s logit2(s v, t).  Multiplying by +-1 is exact and rounding is symmetric in sign, so every n-vector
 // of this loop is s times the folded loop's and every p-vector, norm and decision equal to it: the matrix no longer depends on the labels.
-constexpr bool prox_is_logit(int prox) { return prox == kProxLogit || prox == kProxLogitS; }
+// kProxLogitR (admm_hip_logit_ridge): kProxLogitS on the matrix with the ridge rows sqrt(lambda) e_j' appended.  Their entries of the sign
+// vector are 0.0 (the padding logit_sign_matrix_kernel writes anyway), and sign 0 means a square-loss row: the prox of z^2 / (2 rho) at v,
+// z = v (rho / (1 + rho)) -- in this association, rounded operation by operation (tests/logit_ridge_oracle.py replays it).  The rows with
+// sign +-1 run the S form's expressions.
+constexpr bool prox_is_logit(int prox) { return prox == kProxLogit || prox == kProxLogitS || prox == kProxLogitR; }
+constexpr bool prox_is_signed(int prox) { return prox == kProxLogitS || prox == kProxLogitR; }
 // The prox of g(z) = log(1 + e^-z) / rho (admm_hip_logit: the binomial negative log-likelihood on the sign-folded matrix), t = 1 / rho:
 // the root of h(z) = z - v - t sigma(-z), sigma(-z) = 1 / (1 + e^z), by Newton's iteration.  h is increasing, 1 <= h' <= 1 + t / 4, convex
 // left of zero and concave right of it, the root lies in [v, v + t]; from the start below (v when v > 0, v + t when v + t < 0, else 0)
@@ -552,7 +558,8 @@ lad_rows_kernel(DenseParams q, int par, const double* __restrict__ Xt, long long
     // lad_row_step's callers, and the prox's argument is lad_row_step's expression.  Rows beyond the run (clamped loads: finite) are
     // formed and dropped.
     // kProxLogitS: the response is identically zero there (x - 0 = x exactly, for every x), so the rows' label signs travel in its place.
-    constexpr bool SIGNED = PROX == kProxLogitS;
+    // kProxLogitR: the same, and a row whose sign is 0.0 (a ridge row: the last rows of the matrix) takes the square loss's prox instead.
+    constexpr bool SIGNED = prox_is_signed(PROX);
     __shared__ double uni[2][4 * R];           // d (kProxLogitS: the sign) | adj_y | adj_z | z of the R rows (unreferenced, so not allocated, in the other instantiations)
     auto group_logit = [&](int i0, const double2 (&rv)[R][NPT]) {
         double uval = 0.0;
@@ -571,7 +578,9 @@ lad_rows_kernel(DenseParams q, int par, const double* __restrict__ Xt, long long
             double x = wsum[buf][0][lane];
 #pragma unroll
             for (int w = 1; w < NWV; ++w) x += wsum[buf][w][lane];
-            if (SIGNED) {
+            if (PROX == kProxLogitR && uni[buf][lane] == 0.0) {
+                zl = (x + uni[buf][R + lane] / rho) * (rho / (1.0 + rho));
+            } else if (SIGNED) {
                 // s logit2(s v, t); the sign is read from LDS again behind the iteration, not held in registers across it
                 const double zs = logit2(uni[buf][lane] * (x + uni[buf][R + lane] / rho), pen_hi);
                 asm volatile("" ::: "memory");
@@ -644,7 +653,8 @@ quant_rows_kernel(DenseParams q0, long long slot_stride, const double* __restric
     // s takes its rows' signs from column c.pad of the sign matrix q0.sgn (n x ncol, leading dimension n rounded up to 32) -- one more
     // per-slot entry of uni -- and the Newton prox is formed by lane s R + r of each wave for slot s, row r (see the group below).  The
     // shared response entry goes: the response is identically zero there and x - 0 = x exactly.
-    constexpr bool LOGIT = PROX == kProxLogitS;
+    // kProxLogitR (admm_hip_logit_ridge): the same; a prox lane whose row has sign 0.0 forms v (rho / (1 + rho)) with its slot's rho.
+    constexpr bool LOGIT = prox_is_signed(PROX);
     constexpr int NV = LOGIT ? 4 : 3, NB = LOGIT ? 0 : 1;
     constexpr int NU = R * (NB + NV * S);                 // the vectors' entries a row group needs: d | per slot adj_y, adj_z, z   (LOGIT: no d; per slot also the sign)
     static_assert(!LOGIT || S * R <= 64, "one lane per slot and row");
@@ -729,9 +739,13 @@ quant_rows_kernel(DenseParams q0, long long slot_stride, const double* __restric
                 const double v = x + uni[buf][(NB + NV * ls) * R + lr] / rho_l;
                 // s logit2(s v, t), t = c_hi / rho with c_hi = 1 as the single fit forms it; the sign is read again behind the iteration,
                 // as in lad_rows_kernel
-                const double zs = logit2(uni[buf][(NB + 3 + NV * ls) * R + lr] * v, 1.0 / rho_l);
-                asm volatile("" ::: "memory");
-                zl = uni[buf][(NB + 3 + NV * ls) * R + lr] * zs;
+                if (PROX == kProxLogitR && uni[buf][(NB + 3 + NV * ls) * R + lr] == 0.0) {
+                    zl = v * (rho_l / (1.0 + rho_l));
+                } else {
+                    const double zs = logit2(uni[buf][(NB + 3 + NV * ls) * R + lr] * v, 1.0 / rho_l);
+                    asm volatile("" ::: "memory");
+                    zl = uni[buf][(NB + 3 + NV * ls) * R + lr] * zs;
+                }
             }
         }
 #pragma unroll
@@ -801,7 +815,10 @@ dense_tail_kernel(DenseParams q, int par, double knee) {
         if (q.prob == 0) {                        // LAD: x = P_X(vec); z = prox(x - y + adj_y/rho; c_hi/rho, c_lo/rho); r = x - y - z
             x = g;
             const double d = q.data_vec[i];
-            if (PROX == kProxLogitS) { const double sg = q.sgn[i]; zn = sg * logit2(sg * (x - d + adjy / rho), pen_hi); }
+            if (PROX == kProxLogitR) {
+                const double sg = q.sgn[i], v = x - d + adjy / rho;
+                zn = sg == 0.0 ? v * (rho / (1.0 + rho)) : sg * logit2(sg * v, pen_hi);
+            } else if (PROX == kProxLogitS) { const double sg = q.sgn[i]; zn = sg * logit2(sg * (x - d + adjy / rho), pen_hi); }
             else zn = prox2<PROX>(x - d + adjy / rho, pen_hi, pen_lo, delta);
             r = x - d - zn;
         } else {                                  // BP: x = vec + A'(AA')^-1 b - B'(B vec); z = soft(x + adj_y/rho, 1/rho); r = x - z
@@ -897,6 +914,7 @@ struct DenseLoop {
         if (prox == kProxHuber) hipLaunchKernelGGL(dense_tail_kernel<kProxHuber>, dim3(q.nwg_tail), dim3(kDenseThreads), 0, st, q, (int)(g & 1), delta);
         else if (prox == kProxLogit) hipLaunchKernelGGL(dense_tail_kernel<kProxLogit>, dim3(q.nwg_tail), dim3(kDenseThreads), 0, st, q, (int)(g & 1), 0.0);
         else if (prox == kProxLogitS) hipLaunchKernelGGL(dense_tail_kernel<kProxLogitS>, dim3(q.nwg_tail), dim3(kDenseThreads), 0, st, q, (int)(g & 1), 0.0);
+        else if (prox == kProxLogitR) hipLaunchKernelGGL(dense_tail_kernel<kProxLogitR>, dim3(q.nwg_tail), dim3(kDenseThreads), 0, st, q, (int)(g & 1), 0.0);
         else hipLaunchKernelGGL(dense_tail_kernel<kProxSoft>, dim3(q.nwg_tail), dim3(kDenseThreads), 0, st, q, (int)(g & 1), 0.0);
     }
     DenseCtl final_ctl(hipStream_t st) {
@@ -936,6 +954,7 @@ inline int quant_max_slots(int npt) { return npt <= 3 ? 4 : (npt == 4 ? 3 : (npt
 inline int huber_max_slots(int npt) { return npt <= 3 ? 4 : (npt <= 5 ? 2 : 1); }      // the Huber instantiations without scratch: (4, 3) spills 16 bytes and fell away
 
 inline int logit_max_slots(int npt) { return npt <= 3 ? 4 : (npt == 4 ? 2 : 1); }      // the kProxLogitS instantiations without scratch: (4, 3) spills 64 bytes, (5, 2) 24 (profiles/logit_multi.md)
+inline int logit_ridge_max_slots(int npt) { return npt <= 3 ? 4 : (npt == 4 ? 2 : 1); }      // the kProxLogitR instantiations without scratch: the S form's table (profiles/logit_ridge.md)
 
 // The separable loss of one fit, as the loop sees it: which prox, its weights above / below zero, and (Huber) the knee in the units
 // of the standardised response.  LAD: the default.
@@ -944,9 +963,27 @@ struct LadProx {
     double c_hi = 1.0, c_lo = 1.0, delta = 0.0;
     const double* signs = nullptr;             // kProxLogit: the n label signs folded into the matrix (device), for the iterate dump
                                                // kProxLogitS: the signs the prox reads -- fit k's is column k of ONE matrix, leading dimension round_up(n, 32)
+                                               // kProxLogitR: the same over the augmented rows, 0.0 on the ridge rows
 };
 inline int prox_max_slots(int kind, int npt) {
-    return kind == kProxHuber ? huber_max_slots(npt) : (kind == kProxLogitS ? logit_max_slots(npt) : quant_max_slots(npt));
+    return kind == kProxHuber ? huber_max_slots(npt) : (kind == kProxLogitS ? logit_max_slots(npt) : (kind == kProxLogitR ? logit_ridge_max_slots(npt) : quant_max_slots(npt)));
+}
+
+// M = G0 + lambda D, D = 1 on the first p0 diagonal entries (the user's columns; the intercept's entry is not shifted): one pass, both
+// ld x ld, padding included
+__global__ void __launch_bounds__(256) ridge_gram_kernel(const double* __restrict__ G0, double* __restrict__ M, long long ld, int p0, double lambda) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= ld * ld) return;
+    const long long r = i % ld, c = i / ld;
+    const double g = G0[i];
+    M[i] = r == c && r < p0 ? g + lambda : g;
+}
+// the p0 non-zeros of the ridge rows sqrt(lambda) e_j' (rows n0 + j, j < p0) in the column-major X and in its stored transpose
+__global__ void __launch_bounds__(256) ridge_rows_kernel(double* __restrict__ X, long long ldx, double* __restrict__ Xt, long long ldxt, int n0, int p0, double root) {
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= p0) return;
+    X[(size_t)j * ldx + n0 + j] = root;
+    Xt[((size_t)n0 + j) * ldxt + j] = root;
 }
 
 // Everything of a LAD-type fit that does not depend on the prox constants, formed ONCE (setup), and the loop from a cold start
@@ -962,33 +999,76 @@ struct LadProblem {
     double ynorm = 0;
     DevBuf<double> M, Xt, H, Xd, tvec, svec;
     GemvT<double> g1, g2, g3, gH;                // t = X' vec ; s = (X'X)^-1 t ; xs = X s ;  or xs = H vec
+    int n0 = 0, ridge_p0 = 0;                    // ridge rows (setup_ridge): the data rows and the ridge rows behind them, n = n0 + ridge_p0
+    DevBuf<double> G0;                           // ... and the Gram matrix of the data rows
 
     LadProblem(const DeviceData<double>& d_, const admm_opts& o, hipStream_t st_) : d(d_), opts(o), st(st_), n(d_.n), p(d_.p) {}
 
-    void setup(admm_stats& S) {
+    // setup = the Gram matrix | its inverse | the stored transpose | everything behind them (finish_setup).  A lambda grid of ridge rows
+    // (setup_ridge / setup_lambda below) pays the first and the third once and the other two per lambda.
+    // the Gram matrix of the first `rows` rows of X into G (ldp x ldp)
+    void form_gram(DevBuf<double>& G, int rows, admm_stats& S) {
         ldp = round_up(p, 128);                // whole 128-blocks for the matrix-core inverse
-        // X'X, its inverse (LLT of X'X in the reference, ADMMLAD.h:186-189), X' stored for the X*s product
-        double t0 = now_s();
-        M.alloc((size_t)ldp * ldp); M.zero(st);
-        gram_full<double>(d.X.get(), d.ldx, n, p, true, M.get(), ldp, st);
+        const double t0 = now_s();
+        G.alloc((size_t)ldp * ldp); G.zero(st);
+        gram_full<double>(d.X.get(), d.ldx, rows, p, true, G.get(), ldp, st);
         ADMM_HIP_CHECK(hipStreamSynchronize(st));
         S.t_gram = now_s() - t0;
-        t0 = now_s();
-        // n <= 2000: the hat-matrix branch below also needs the Cholesky factor of the same Gram matrix: keep a copy
+    }
+    // M -> its inverse; n <= 2000: the hat-matrix branch also needs the Cholesky factor of the same Gram matrix: G2 keeps a copy
+    void invert_gram(DevBuf<double>& G2) {
         hat = n <= 2000;
         if (opt_off(Opt::LAD_HAT)) hat = false;
-        DevBuf<double> G2;
         if (hat) {
             G2.alloc((size_t)ldp * ldp);
             ADMM_HIP_CHECK(hipMemcpyAsync(G2.get(), M.get(), (size_t)ldp * ldp * sizeof(double), hipMemcpyDeviceToDevice, st));
         }
         spd_inverse_f64(M.get(), ldp, p, st);
+    }
+    void form_transpose() {
         ldxt = round_up(p, 32);
         Xt.alloc((size_t)ldxt * n); Xt.zero(st);
         transpose<double>(d.X.get(), d.ldx, n, p, Xt.get(), ldxt, st);
+    }
+
+    void setup(admm_stats& S) {
+        // X'X, its inverse (LLT of X'X in the reference, ADMMLAD.h:186-189), X' stored for the X*s product
+        form_gram(M, n, S);
+        const double t0 = now_s();
+        DevBuf<double> G2;
+        invert_gram(G2);
+        form_transpose();
         ADMM_HIP_CHECK(hipStreamSynchronize(st));
         S.t_factor = now_s() - t0;
+        finish_setup(S, G2);
+    }
 
+    // Ridge rows (solve_logit_ridge): d.X holds n0 data rows and, behind them, p0 rows that are zero until setup_lambda writes
+    // sqrt(lambda) e_j' into them.  Once per call: G0 = the Gram matrix of the DATA rows, and the transpose.
+    void setup_ridge(int n0_, int p0_, admm_stats& S) {
+        n0 = n0_; ridge_p0 = p0_;
+        form_gram(G0, n0, S);
+        const double t0 = now_s();
+        M.alloc((size_t)ldp * ldp);
+        form_transpose();
+        ADMM_HIP_CHECK(hipStreamSynchronize(st));
+        S.t_factor = now_s() - t0;
+    }
+    // Per lambda: M = G0 + lambda D (the Gram matrix of the augmented rows, D = 1 on the p0 user columns), the p0 entries of the ridge
+    // rows in X and in its transpose, and what setup does behind the Gram matrix.
+    void setup_lambda(double lambda, admm_stats& S) {
+        const double t0 = now_s();
+        hipLaunchKernelGGL(ridge_gram_kernel, dim3((unsigned)(((size_t)ldp * ldp + 255) / 256)), dim3(256), 0, st, G0.get(), M.get(), ldp, ridge_p0, lambda);
+        hipLaunchKernelGGL(ridge_rows_kernel, dim3((ridge_p0 + 255) / 256), dim3(256), 0, st, d.X.get(), d.ldx, Xt.get(), ldxt, n0, ridge_p0, std::sqrt(lambda));
+        DevBuf<double> G2;
+        invert_gram(G2);
+        ADMM_HIP_CHECK(hipStreamSynchronize(st));
+        S.t_factor += now_s() - t0;
+        finish_setup(S, G2);
+    }
+
+    void finish_setup(admm_stats& S, DevBuf<double>& G2) {
+        double t0;
         DevBuf<double> ynorm_d(1);
         hipLaunchKernelGGL(norm2_kernel, dim3(1), dim3(1024), 0, st, d.Y.get(), n, ynorm_d.get());
         ADMM_HIP_CHECK(hipMemcpyAsync(&ynorm, ynorm_d.get(), sizeof(double), hipMemcpyDeviceToHost, st));
@@ -1052,12 +1132,12 @@ struct LadProblem {
         DenseLoop L;
         L.init(n, 0, opts, d.Y.get(), ynorm, st, res.trace_cap, res.state_cap, onepass ? lad_nwg : 0);
         L.q.c_hi = px.c_hi; L.q.c_lo = px.c_lo; L.delta = px.delta; L.prox = px.kind;
-        if (px.kind == kProxLogitS) L.q.sgn = px.signs;
+        if (prox_is_signed(px.kind)) L.q.sgn = px.signs;
         if (px.kind == kProxHuber && res.state_cap > 0) {       // iterate dump: record 0 also carries the knee as the loop holds it (delta / scaleY), first entry of its z slot
             ADMM_HIP_CHECK(hipMemcpyAsync(L.state.get() + n, &px.delta, sizeof(double), hipMemcpyHostToDevice, st));
             ADMM_HIP_CHECK(hipStreamSynchronize(st));
         }
-        if (px.kind == kProxLogit && res.state_cap > 0)         // the same for the logistic fit: the n signs the loop ran with fill record 0's z slot
+        if ((px.kind == kProxLogit || px.kind == kProxLogitR) && res.state_cap > 0)      // the same for the logistic fit: the n signs the loop ran with fill record 0's z slot (ridge rows: 0.0)
             ADMM_HIP_CHECK(hipMemcpyAsync(L.state.get() + n, px.signs, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
         if (hat) { L.q.gout = gH.part.get(); L.q.gout_nseg = gH.pl.nseg; L.q.gout_stride = gH.stride; }
         else if (!onepass) { L.q.gout = g3.part.get(); L.q.gout_nseg = g3.pl.nseg; L.q.gout_stride = g3.stride; }
@@ -1071,31 +1151,37 @@ struct LadProblem {
         auto launch_rows = [&](long long g) {
             const int par = (int)(g & 1);
 #define ADMM_LAD_ROWS(N, PX) hipLaunchKernelGGL((lad_rows_kernel<N, PX>), dim3(lad_nwg), dim3(kLadThreads), 0, st, L.q, par, Xt.get(), ldxt, g2.part.get(), g2.pl.nseg, g2.stride, cpart.get(), lad_rows, px.delta)
-            switch (std::min(lad_npt(ldxt), 6) * 4 + px.kind) {
-                case 4: ADMM_LAD_ROWS(1, kProxSoft); break;
-                case 5: ADMM_LAD_ROWS(1, kProxHuber); break;
-                case 6: ADMM_LAD_ROWS(1, kProxLogit); break;
-                case 7: ADMM_LAD_ROWS(1, kProxLogitS); break;
-                case 8: ADMM_LAD_ROWS(2, kProxSoft); break;
-                case 9: ADMM_LAD_ROWS(2, kProxHuber); break;
-                case 10: ADMM_LAD_ROWS(2, kProxLogit); break;
-                case 11: ADMM_LAD_ROWS(2, kProxLogitS); break;
-                case 12: ADMM_LAD_ROWS(3, kProxSoft); break;
-                case 13: ADMM_LAD_ROWS(3, kProxHuber); break;
-                case 14: ADMM_LAD_ROWS(3, kProxLogit); break;
-                case 15: ADMM_LAD_ROWS(3, kProxLogitS); break;
-                case 16: ADMM_LAD_ROWS(4, kProxSoft); break;
-                case 17: ADMM_LAD_ROWS(4, kProxHuber); break;
-                case 18: ADMM_LAD_ROWS(4, kProxLogit); break;
-                case 19: ADMM_LAD_ROWS(4, kProxLogitS); break;
-                case 20: ADMM_LAD_ROWS(5, kProxSoft); break;
-                case 21: ADMM_LAD_ROWS(5, kProxHuber); break;
-                case 22: ADMM_LAD_ROWS(5, kProxLogit); break;
-                case 23: ADMM_LAD_ROWS(5, kProxLogitS); break;
-                case 24: ADMM_LAD_ROWS(6, kProxSoft); break;
-                case 25: ADMM_LAD_ROWS(6, kProxHuber); break;
-                case 26: ADMM_LAD_ROWS(6, kProxLogit); break;
-                case 27: ADMM_LAD_ROWS(6, kProxLogitS); break;
+            switch (std::min(lad_npt(ldxt), 6) * 8 + px.kind) {
+                case 8: ADMM_LAD_ROWS(1, kProxSoft); break;
+                case 9: ADMM_LAD_ROWS(1, kProxHuber); break;
+                case 10: ADMM_LAD_ROWS(1, kProxLogit); break;
+                case 11: ADMM_LAD_ROWS(1, kProxLogitS); break;
+                case 12: ADMM_LAD_ROWS(1, kProxLogitR); break;
+                case 16: ADMM_LAD_ROWS(2, kProxSoft); break;
+                case 17: ADMM_LAD_ROWS(2, kProxHuber); break;
+                case 18: ADMM_LAD_ROWS(2, kProxLogit); break;
+                case 19: ADMM_LAD_ROWS(2, kProxLogitS); break;
+                case 20: ADMM_LAD_ROWS(2, kProxLogitR); break;
+                case 24: ADMM_LAD_ROWS(3, kProxSoft); break;
+                case 25: ADMM_LAD_ROWS(3, kProxHuber); break;
+                case 26: ADMM_LAD_ROWS(3, kProxLogit); break;
+                case 27: ADMM_LAD_ROWS(3, kProxLogitS); break;
+                case 28: ADMM_LAD_ROWS(3, kProxLogitR); break;
+                case 32: ADMM_LAD_ROWS(4, kProxSoft); break;
+                case 33: ADMM_LAD_ROWS(4, kProxHuber); break;
+                case 34: ADMM_LAD_ROWS(4, kProxLogit); break;
+                case 35: ADMM_LAD_ROWS(4, kProxLogitS); break;
+                case 36: ADMM_LAD_ROWS(4, kProxLogitR); break;
+                case 40: ADMM_LAD_ROWS(5, kProxSoft); break;
+                case 41: ADMM_LAD_ROWS(5, kProxHuber); break;
+                case 42: ADMM_LAD_ROWS(5, kProxLogit); break;
+                case 43: ADMM_LAD_ROWS(5, kProxLogitS); break;
+                case 44: ADMM_LAD_ROWS(5, kProxLogitR); break;
+                case 48: ADMM_LAD_ROWS(6, kProxSoft); break;
+                case 49: ADMM_LAD_ROWS(6, kProxHuber); break;
+                case 50: ADMM_LAD_ROWS(6, kProxLogit); break;
+                case 51: ADMM_LAD_ROWS(6, kProxLogitS); break;
+                case 52: ADMM_LAD_ROWS(6, kProxLogitR); break;
                 default: throw Error(ADMM_ERR_INTERNAL, "one-pass loop: no rows kernel for this prox");
             }
 #undef ADMM_LAD_ROWS
@@ -1165,7 +1251,7 @@ struct LadProblem {
         q.lp = p; q.Xd = Xd.get(); q.Xz0 = b + o_p; q.Xz1 = b + o_p + ldp; q.Xy0 = b + o_p + 2 * ldp; q.Xy1 = b + o_p + 3 * ldp; q.u = b + o_p + 4 * ldp;
         q.cpart = b + o_c; q.cnwg = lad_nwg; q.cstride = ldp;
         q.c_hi = 1.0; q.c_lo = 1.0;                              // (unused: the slots' constants are chi / clo of their quantile)
-        if (kind == kProxLogitS) q.sgn = fits[0].signs;          // the sign matrix: a slot reads the column of the fit it holds
+        if (prox_is_signed(kind)) q.sgn = fits[0].signs;         // the sign matrix: a slot reads the column of the fit it holds
         QuantGrid G{};
         G.nslots = nslots; G.ntau = ntau; G.slot_stride = (long long)stride; G.rho0 = opts.rho;
         G.next = ints.get() + 1; G.idle = ints.get() + 3; G.niter = ints.get() + 3 + nslots; G.rho_fin = rho_fin.get();
@@ -1189,7 +1275,7 @@ struct LadProblem {
         auto launch_rows = [&](int par) {
 #define ADMM_QUANT_ROWS(N, SS, PX) hipLaunchKernelGGL((quant_rows_kernel<N, SS, PX>), dim3(lad_nwg), dim3(kLadThreads), 0, st, q, (long long)stride, chi_d.get(), clo_d.get(), par, \
                                                       Xt.get(), ldxt, spart0, g2.pl.nseg, g2.stride, cpart0, lad_rows, (const double*)dlt_d.get())
-            switch ((kind == kProxHuber ? 100 : (kind == kProxLogitS ? 200 : 0)) + lad_npt(ldxt) * 10 + nslots) {
+            switch ((kind == kProxHuber ? 100 : (kind == kProxLogitS ? 200 : (kind == kProxLogitR ? 300 : 0))) + lad_npt(ldxt) * 10 + nslots) {
                 case 12: ADMM_QUANT_ROWS(1, 2, kProxSoft); break;
                 case 13: ADMM_QUANT_ROWS(1, 3, kProxSoft); break;
                 case 14: ADMM_QUANT_ROWS(1, 4, kProxSoft); break;
@@ -1223,6 +1309,16 @@ struct LadProblem {
                 case 233: ADMM_QUANT_ROWS(3, 3, kProxLogitS); break;
                 case 234: ADMM_QUANT_ROWS(3, 4, kProxLogitS); break;
                 case 242: ADMM_QUANT_ROWS(4, 2, kProxLogitS); break;
+                case 312: ADMM_QUANT_ROWS(1, 2, kProxLogitR); break;
+                case 313: ADMM_QUANT_ROWS(1, 3, kProxLogitR); break;
+                case 314: ADMM_QUANT_ROWS(1, 4, kProxLogitR); break;
+                case 322: ADMM_QUANT_ROWS(2, 2, kProxLogitR); break;
+                case 323: ADMM_QUANT_ROWS(2, 3, kProxLogitR); break;
+                case 324: ADMM_QUANT_ROWS(2, 4, kProxLogitR); break;
+                case 332: ADMM_QUANT_ROWS(3, 2, kProxLogitR); break;
+                case 333: ADMM_QUANT_ROWS(3, 3, kProxLogitR); break;
+                case 334: ADMM_QUANT_ROWS(3, 4, kProxLogitR); break;
+                case 342: ADMM_QUANT_ROWS(4, 2, kProxLogitR); break;
                 default: throw Error(ADMM_ERR_INTERNAL, "slotted grid: no rows kernel for this layout");
             }
 #undef ADMM_QUANT_ROWS
@@ -1279,17 +1375,40 @@ static void append_ones_column(DeviceData<double>& d, hipStream_t st) {
     d.p = p0 + 1;
 }
 
+// p0 more rows behind the n of X (all columns, the ones column included) and of the response, zero: the ridge rows sqrt(lambda) e_j', whose
+// p0 non-zeros LadProblem::setup_lambda writes per lambda.  d.n counts them from here on; the leading dimension grows with it.
+static void append_ridge_rows(DeviceData<double>& d, int p0, hipStream_t st) {
+    const int n0 = d.n;
+    const long long ld1 = round_up((long long)n0 + p0, 32);
+    DevBuf<double> X1((size_t)ld1 * d.p), Y1((size_t)ld1);
+    X1.zero(st); Y1.zero(st);
+    for (int c0 = 0; c0 < d.p; c0 += 65535) {                    // (the grid's y extent)
+        const int nc = std::min(65535, d.p - c0);
+        hipLaunchKernelGGL(copy_cols_f64_kernel, dim3((n0 + 255) / 256, nc), dim3(256), 0, st, d.X.get() + (size_t)c0 * d.ldx, d.ldx, n0, X1.get() + (size_t)c0 * ld1, ld1);
+    }
+    ADMM_HIP_CHECK(hipStreamSynchronize(st));
+    d.X = std::move(X1);
+    d.Y = std::move(Y1);
+    d.ldx = ld1;
+    d.n = n0 + p0;
+}
+
 // d: the standardised data (DataStd flag 3 with the intercept, 1 without); with the intercept the loop fits one more column of ones.
 // fits: the grid in the units of the standardised response, all of one prox kind.  What admm_hip_quantreg and admm_hip_huber share:
 // the ones column, the setup, the choice of slots, the loops and the recovery.
+static void run_lad_fits(LadProblem& P, DeviceData<double>& d, int p0, bool intercept, const std::vector<LadProx>& fits, QuantResult& res);
 static void solve_lad_grid(DeviceData<double>& d, bool intercept, const admm_opts& opts, const std::vector<LadProx>& fits, QuantResult& res, hipStream_t st) {
-    const int ntau = (int)fits.size();
-    const int n = d.n, p0 = d.p;
+    const int p0 = d.p;
     if (intercept) append_ones_column(d, st);
-    const int p = d.p;
-    DenseResult& dr = res.dense;
     LadProblem P(d, opts, st);
-    P.setup(dr.stats);
+    P.setup(res.dense.stats);
+    run_lad_fits(P, d, p0, intercept, fits, res);
+}
+// the fits of a grid on a problem that is set up (d.p: the loop's columns, p0 of them the user's): the choice of slots, the loops, the recovery
+static void run_lad_fits(LadProblem& P, DeviceData<double>& d, int p0, bool intercept, const std::vector<LadProx>& fits, QuantResult& res) {
+    const int ntau = (int)fits.size();
+    const int n = d.n, p = d.p;
+    DenseResult& dr = res.dense;
 
     // slots: the one-pass branch only; QUANT_SLOTS 0 = automatic, 1 = serial, 2 .. 8 = at most that many, clipped to what the registers
     // of the shape's layout hold and to the number of quantiles.  The get_x vectors of all quantiles (n x ntau) must fit beside the problem.
@@ -1297,7 +1416,7 @@ static void solve_lad_grid(DeviceData<double>& d, bool intercept, const admm_opt
     if (P.onepass && dr.trace_cap == 0 && ntau >= 2) {
         const long long want = opt_int(Opt::QUANT_SLOTS, 0);
         const int kind = fits[0].kind;
-        slots = want == 0 ? (kind == kProxHuber ? kHuberAutoSlots : (kind == kProxLogitS ? kLogitAutoSlots : kQuantAutoSlots)) : (int)want;
+        slots = want == 0 ? (kind == kProxHuber ? kHuberAutoSlots : (kind == kProxLogitS ? kLogitAutoSlots : (kind == kProxLogitR ? kLogitRidgeAutoSlots : kQuantAutoSlots))) : (int)want;
         slots = std::min(std::min(slots, prox_max_slots(fits[0].kind, lad_npt(P.ldxt))), ntau);
         if ((size_t)ntau * (size_t)n * sizeof(double) > (size_t(2) << 30)) slots = 1;
     }
@@ -1429,6 +1548,44 @@ void solve_logit_multi(DeviceData<double>& d, bool intercept, const double* y_de
     std::vector<LadProx> fits(ncol);
     for (int k = 0; k < ncol; ++k) { fits[k].kind = kProxLogitS; fits[k].signs = sgn.get() + (size_t)k * lds; }
     solve_lad_grid(d, intercept, opts, fits, res, st);
+}
+
+// Ridge logistic regression (admm_hip_logit_ridge): sum log(1 + exp(-s_i (b0 + x_i'b))) + lambda / 2 sum b_j^2 per label column and
+// lambda, b on the standardised scale, the intercept not penalised.  The penalty is not written on b -- the x-update's matrix would be
+// X'X + (lambda / rho) D and change with rho -- but as p0 more ROWS sqrt(lambda) e_j' with a zero response and the loss z^2 / 2: the Gram
+// matrix of the augmented rows is X'X + lambda D whatever rho does, and the loop is solve_logit_multi's with one more case in the prox
+// (kProxLogitR: sign 0 = a square-loss row).  Once per call: the upload's standardisation, the ones column, the ridge rows, the Gram
+// matrix of the data rows, the transpose, the sign matrix.  Per lambda, in the order given, every fit from a cold start: M = G0 + lambda
+// D, the ridge rows' entries, the inverse (and the hat matrix), then the ncol columns as solve_lad_grid runs a grid.
+// res.beta: (p + 1) x ncol x nlambda, res.niter: ncol x nlambda.
+void solve_logit_ridge(DeviceData<double>& d, bool intercept, const double* y_dev, int ncol, const double* lambda, int nlambda, const admm_opts& opts, QuantResult& res,
+                       hipStream_t st) {
+    const int n0 = d.n, p0 = d.p;
+    if (intercept) append_ones_column(d, st);
+    append_ridge_rows(d, p0, st);
+    const long long lds = round_up(d.n, 32);
+    DevBuf<double> sgn((size_t)lds * ncol);
+    hipLaunchKernelGGL(logit_sign_matrix_kernel, dim3((unsigned)((lds + 255) / 256), std::min(ncol, 65535)), dim3(256), 0, st, y_dev, n0, ncol, lds, sgn.get());
+    d.scaleY = 1.0; d.meanY = 0.0;
+    std::vector<LadProx> fits(ncol);
+    for (int k = 0; k < ncol; ++k) { fits[k].kind = kProxLogitR; fits[k].signs = sgn.get() + (size_t)k * lds; }
+    LadProblem P(d, opts, st);
+    P.setup_ridge(n0, p0, res.dense.stats);
+    res.beta.clear(); res.niter.clear();
+    for (int l = 0; l < nlambda; ++l) {
+        P.setup_lambda(lambda[l], res.dense.stats);
+        QuantResult one;
+        one.dense.trace_cap = res.dense.trace_cap; one.dense.state_cap = res.dense.state_cap;
+        one.dense.stats = res.dense.stats;
+        run_lad_fits(P, d, p0, intercept, fits, one);
+        res.beta.insert(res.beta.end(), one.beta.begin(), one.beta.end());
+        res.niter.insert(res.niter.end(), one.niter.begin(), one.niter.end());
+        res.dense.stats = one.dense.stats;
+        if (l == nlambda - 1) {
+            res.dense.niter = one.dense.niter;
+            res.dense.trace = std::move(one.dense.trace); res.dense.state = std::move(one.dense.state); res.dense.state_dim = one.dense.state_dim;
+        }
+    }
 }
 
 __global__ void __launch_bounds__(256) logit_prox_hook_kernel(const double* __restrict__ v, long long m, double t, double* __restrict__ out) {

@@ -150,6 +150,13 @@ void logit_count_labels(const double* y_dev, int n, long long* bad, long long* o
 // (QUANT_SLOTS, as solve_huber).  y_dev: n x ncol labels on the device (leading dimension n), every column validated as solve_logit's.
 // res.beta: (p + 1) x ncol, res.niter: ncol; column k equals solve_logit on column k.
 void solve_logit_multi(DeviceData<double>& d, bool intercept, const double* y_dev, int ncol, const admm_opts& opts, QuantResult& res, hipStream_t st);
+// admm_hip_logit_ridge (fadmm_dense.hip): the same with the ridge penalty lambda / 2 sum b_j^2 on the standardised coefficients (never the
+// intercept), as p more rows sqrt(lambda) e_j' with a zero response and a square loss (kProxLogitR), so the cached inverse does not
+// depend on rho.  One upload, standardisation, data-row Gram matrix and transpose per call; per lambda (in the order given, every fit
+// cold) the inverse and the ncol columns.  No n > p condition.  res.beta: (p + 1) x ncol x nlambda, res.niter: ncol x nlambda; dense: the
+// stats, and for one column and one lambda the trace / iterate dump of the augmented loop (n + p rows).
+void solve_logit_ridge(DeviceData<double>& d, bool intercept, const double* y_dev, int ncol, const double* lambda, int nlambda, const admm_opts& opts, QuantResult& res,
+                       hipStream_t st);
 // admm_dantzig (dantzig.hip): the Dantzig selector path in double.  res.beta: (p + 1) x nlambda column-major, row 0 = intercept.
 struct DantzigResult {
     std::vector<double> lambda, beta;

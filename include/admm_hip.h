@@ -320,6 +320,33 @@ ADMM_HIP_API int admm_hip_logit_state(const double* x, const double* y, int n, i
 ADMM_HIP_API int admm_hip_logit_multi(const double* x, const double* y, int n, int p, int k, int mem, int intercept, const admm_opts* opts,
                          double* beta_out, int* niter_out, admm_stats* stats);
 
+/* Ridge (L2-penalised) logistic regression for k label columns and a grid of nlambda penalties.  Per label column c and lambda_l:
+ *     minimise  sum_i log(1 + exp(-s_i (b0 + x~_i'b))) + (lambda_l / 2) sum_j b_j^2,   s = 2 y - 1,
+ * x~ the library's standardised columns (always standardised, as admm_hip_logit), b on the standardised scale, the intercept never
+ * penalised; scikit-learn's C is 1 / lambda on standardised x.  Unlike the unpenalised calls it has a unique answer on perfectly
+ * separable labels and there is NO n > p condition (n >= 2).  The penalty is not written on b: it becomes p more rows sqrt(lambda) e_j'
+ * with a zero response and the loss z^2 / 2, so the Gram matrix of the augmented matrix is X'X + lambda D whatever rho does, and the
+ * loop is admm_hip_logit_multi's (hat matrix for n + p <= 2000, else one pass / two passes, QUANT_SLOTS as there) with one more case
+ * in the prox: a row of sign 0 takes z = v (rho / (1 + rho)).  The upload, the standardisation, the Gram matrix of the data rows and the
+ * transpose are formed once per call; the inverse (and the hat matrix) once per lambda.  lambda is used in the order given and EVERY
+ * fit starts cold.  The ridge rows are stored and streamed dense: p / (n + p) more bytes per iteration than admm_hip_logit_multi.
+ * y[n * k]: column-major labels as admm_hip_logit_multi's, with its refusals; further "lambda must not be NULL", "lambda must have at
+ * least one value", "every lambda must be finite and positive (lambda = 0 is admm_hip_logit_multi)", "nrow(x) must be at least 2".
+ * A refusal touches no output.
+ * beta_out[(p + 1) * k * nlambda]: entry ((l * k + c) * (p + 1) + j), intercept first, on the caller's scale; niter_out[k * nlambda]:
+ * entry l * k + c, maxit + 1 = not converged.  stats->xupdate_variant: 8 + slots on the slotted route, else 1 (one pass) or 0.
+ * QUANT_SLOTS = 0 (automatic) takes as many slots as the layout admits (4 to 3072 columns counting the intercept, 2 to 4096, 1 beyond),
+ * clipped to k: measured + 31 ... + 60 % over the serial route (profiles/logit_ridge.md).
+ * Not offered: an l1 / elastic-net penalty, observation or class weights, softmax, warm starts along the grid, a multi-GPU form. */
+ADMM_HIP_API int admm_hip_logit_ridge(const double* x, const double* y, int n, int p, int k, int mem, int intercept, const double* lambda, int nlambda,
+                         const admm_opts* opts, double* beta_out, int* niter_out, admm_stats* stats);
+/* One label vector and one lambda, with the decision trace and the iterate dump of the AUGMENTED loop: records x | z | y | adj_z | adj_y
+ * of n + p entries each (state_out: state_cap * 5 * (n + p) doubles); record 0 carries the zero response in its x slot and, in its z
+ * slot, the n + p "signs" the loop ran with: 2 y - 1, then p zeros (the ridge rows). */
+ADMM_HIP_API int admm_hip_logit_ridge_state(const double* x, const double* y, int n, int p, int mem, int intercept, double lambda, const admm_opts* opts,
+                         double* beta_out, int* niter_out, admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out,
+                         double* state_out, long long state_cap, long long* nstate_out);
+
 /* Prepared-problem variant of the Lasso family (the "persistent context" anticipated for a
  * re-fitting caller; the R shim does not need it).  create = everything the reference does
  * before its lambda loop (copy/convert, DataStd, X'y, Gram, Spectra, factorisation:

@@ -276,6 +276,26 @@ BEGIN_RCPP
 END_RCPP
 }
 
+// Ridge logistic regression for the columns of a label matrix and a grid of lambda (not in the reference):
+// .Call("admm_logit_ridge", x, Y, lambda, intercept, opts) -> beta: (p + 1) x (k nlambda), column l k + c = (lambda l, label column c),
+// intercept first -- dim(res$beta) <- c(p + 1, k, nlambda) gives the array; niter: k nlambda, entry l k + c.  lambda is on the
+// standardised scale and used in the order given.
+RcppExport SEXP admm_logit_ridge(SEXP x_, SEXP y_, SEXP lambda_, SEXP intercept_, SEXP opts_) {
+BEGIN_RCPP
+    NumericMatrix x(x_);
+    NumericMatrix y(y_);
+    NumericVector lambda(lambda_);
+    if (y.nrow() != x.nrow()) Rcpp::stop("nrow(x) should be equal to nrow(Y)");
+    admm_opts o = unpack_opts(opts_);
+    const int nlambda = lambda.size();
+    NumericMatrix beta(x.ncol() + 1, y.ncol() * nlambda);
+    IntegerVector niter(y.ncol() * nlambda);
+    check(admm_hip_logit_ridge(x.begin(), y.begin(), x.nrow(), x.ncol(), y.ncol(), ADMM_MEM_HOST, as<bool>(intercept_), lambda.begin(), nlambda, &o,
+                               beta.begin(), niter.begin(), nullptr));
+    return List::create(Named("beta") = beta, Named("niter") = niter, Named("lambda") = lambda);
+END_RCPP
+}
+
 // The symbol R/50_admm_dantzig.R:38 asks for and the reference never builds (src/TODO/Dantzig.cpp:32-99): doubles throughout.
 RcppExport SEXP admm_dantzig(SEXP x_, SEXP y_, SEXP lambda_, SEXP nlambda_, SEXP lmin_ratio_, SEXP standardize_, SEXP intercept_, SEXP opts_) {
 BEGIN_RCPP
