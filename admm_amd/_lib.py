@@ -82,7 +82,8 @@ EXPORTS = ["admm_hip_lasso", "admm_hip_enet", "admm_hip_parlasso", "admm_hip_lad
            "admm_hip_test_gemm_nt", "admm_hip_test_cholesky_linvt", "admm_hip_test_spd_inverse_shift",
            "admm_hip_test_symv_plan", "admm_hip_test_symv_ex", "admm_hip_test_symv_multi_ex", "admm_hip_test_symv_f64acc",
            "admm_hip_test_symv_one", "admm_hip_test_symv_pack_host", "admm_hip_test_symv_packed", "admm_hip_test_symv_packed_time",
-           "admm_hip_test_tall_pack_info", "admm_hip_test_gemv_t_ex", "admm_hip_test_wide_op", "admm_hip_test_block_sprad"]
+           "admm_hip_test_tall_pack_info", "admm_hip_test_gemv_t_ex", "admm_hip_test_wide_op", "admm_hip_test_block_sprad",
+           "admm_hip_test_wide_screen_prep", "admm_hip_test_sbp_screen_prep"]
 
 GROUP_MAX = 1024          # ADMM_HIP_GROUP_MAX
 MT_MAX = 16               # ADMM_HIP_MT_MAX
@@ -308,6 +309,12 @@ def load():
     lib.admm_hip_test_wide_op.restype = ctypes.c_int
     lib.admm_hip_test_block_sprad.argtypes = [_c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_double_p, _c_int_p]
     lib.admm_hip_test_block_sprad.restype = ctypes.c_int
+    lib.admm_hip_test_wide_screen_prep.argtypes = [_c_float_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint, ctypes.c_void_p,
+                                                   ctypes.c_longlong, _c_float_p, _c_float_p, _c_double_p, _c_ll_p]
+    lib.admm_hip_test_wide_screen_prep.restype = ctypes.c_int
+    lib.admm_hip_test_sbp_screen_prep.argtypes = [_c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_uint, ctypes.c_void_p, ctypes.c_longlong,
+                                                  _c_float_p, _c_ll_p]
+    lib.admm_hip_test_sbp_screen_prep.restype = ctypes.c_int
     lib.admm_hip_test_spd_inverse.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
     lib.admm_hip_test_spd_inverse.restype = ctypes.c_int
     lib.admm_hip_test_spd_inverse_shift.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_double, ctypes.c_void_p]

@@ -805,6 +805,31 @@ int admm_hip_test_block_sprad(const double* A, int n, int p, int nblocks, double
     });
 }
 
+int admm_hip_test_wide_screen_prep(const float* X, int n, int p, int fmt, int nw, unsigned pad_fill, void* copy_out, long long copy_capacity,
+                                   float* s_out, float* scale_out, double* rate_out, long long* info_out) {
+    return guarded([&] {
+        ADMM_REQUIRE(X && copy_out && s_out && rate_out && info_out, "wide_screen_prep hook: X, copy_out, s_out, rate_out and info_out must not be NULL");
+        ADMM_REQUIRE(fmt == 8 || fmt == 16, "wide_screen_prep hook: fmt is 8 or 16");
+        ADMM_REQUIRE(fmt == 16 || scale_out, "wide_screen_prep hook: the 8-bit code needs scale_out");
+        ADMM_REQUIRE(n >= 1 && p >= 1 && nw >= 1 && n <= (1 << 20) && p <= (1 << 20) && nw <= (1 << 20) && ((long long)n + 15) * (long long)p <= (1ll << 28),
+                     "wide_screen_prep hook: n, p and nw in 1 .. 2^20, at most 2^28 elements of storage");
+        ADMM_REQUIRE(copy_capacity >= (long long)p * wide_screen_layout(n, p, fmt, nw).ldh, "wide_screen_prep hook: copy_capacity below p * ldh elements");
+        test_wide_screen_prep(X, n, p, fmt, nw, pad_fill, copy_out, s_out, scale_out, rate_out, info_out);
+    });
+}
+
+int admm_hip_test_sbp_screen_prep(const double* A, int n, int pl, int lda_extra, unsigned pad_fill, unsigned short* copy_out, long long copy_capacity,
+                                  float* s_out, long long* info_out) {
+    return guarded([&] {
+        ADMM_REQUIRE(A && copy_out && s_out && info_out, "sbp_screen_prep hook: A, copy_out, s_out and info_out must not be NULL");
+        ADMM_REQUIRE(n >= 1 && pl >= 1 && n <= (1 << 20) && pl <= (1 << 20) && lda_extra >= 0 && lda_extra <= 4096 &&
+                         ((long long)n + 31 + lda_extra) * (long long)pl <= (1ll << 27),
+                     "sbp_screen_prep hook: n and pl in 1 .. 2^20, lda_extra in 0 .. 4096, at most 2^27 elements of storage");
+        ADMM_REQUIRE(copy_capacity >= (long long)pl * sbp_screen_ldh(n), "sbp_screen_prep hook: copy_capacity below pl * ldh elements");
+        test_sbp_screen_prep(A, n, pl, lda_extra, pad_fill, copy_out, s_out, info_out);
+    });
+}
+
 int admm_hip_test_gather(const void* A, int rows, int cols, int is_double, const void* v, double* y) {
     return guarded([&] {
         ADMM_REQUIRE(A && v && y && rows > 0 && cols > 0, "bad arguments");

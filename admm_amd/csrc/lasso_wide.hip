@@ -34,6 +34,7 @@
 #include "comm.h"
 #include "probe.h"
 #include "peer_device.h"
+#include "test_hooks.h"
 
 namespace admm {
 
@@ -457,7 +458,7 @@ wide_x_kernel(WideParams q, int par) {
     // ---- safe screening of a regular step (fused mode).  A regular step applies the prox to EVERY column, and for all but a per cent
     // of them the outcome is "stays zero": x_j = 0 and |fl(X_j't)| / gamma below the threshold.  Which ones cannot be known without a
     // product with every column -- but a product with a ROUNDED column is enough to prove it: with Xh = fp16(X),
-    //     |fl32(X_j't)| <= |fl32(Xh_j't)| + s_j ||t||_2 ,     s_j = ||X_j - Xh_j||_2 + gamma_n (||X_j||_2 + ||Xh_j||_2)
+    //     |fl32(X_j't)| <= |fl32(Xh_j't)| + s_j ||t||_2 ,     s_j = ||X_j - Xh_j||_2 + 2 gamma_n max(||X_j||_2, ||Xh_j||_2)
     // (Cauchy-Schwarz on the rounding of the column, the standard bound gamma_n = n u / (1 - n u) on an n-term float inner product in
     // ANY order for each of the two computed sums; s_j is formed once at setup in double and rounded UP, wide_screen_prep_kernel).  A
     // column with x_j = 0 whose bound stays below gamma * threshold * (1 - 2^-21) is left alone -- the exact step would have stored the
@@ -1755,6 +1756,8 @@ wide_screen_prep_kernel(const float* __restrict__ X, long long ldx, int n, int p
 
 // The same for a linear 8-bit code: q_ij = round(X_ij / scale_j) in [-127, 127], scale_j = max_i |X_ij| / 127; the copy stands for
 // scale_j q_j in the bound (||X_j - scale_j q_j||_2 measured here, in double).  The screen's product is fl32(q_j't) times scale_j in double.
+// A column with an entry that is not finite OR beyond 3e38 (max / 127 and the products with the codes stay well inside float) gets scale 0,
+// all codes 0 and s_j = +Inf.
 __global__ void __launch_bounds__(256)
 wide_screen_prep8_kernel(const float* __restrict__ X, long long ldx, int n, int p, signed char* __restrict__ Xq, long long ldq,
                          float* __restrict__ s, float* __restrict__ scale, int NW, int S, double loosen) {
@@ -1828,6 +1831,17 @@ wide_screen_rate8_kernel(const float* __restrict__ X, long long ldx, int n, int 
     if (lane == 0) sh[wid] = rj;
     __syncthreads();
     if (threadIdx.x == 0) part[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+}
+
+constexpr double kWideScreenLoosen = 1.0;      // factor on every bound (the setup kernels' argument `loosen`): the plan's and the test hook's
+
+// Where the screen's setup kernels put their results: the leading dimension of the copy (whole 16-byte pieces: 8 fp16 values or 16
+// codes) and the stride S of the [NW][S] bound / scale arrays (wave w's k-th column, j = k NW + w, at [w S + k]; whole 256-byte lines).
+WideScreenLayout wide_screen_layout(int n, int p, int fmt, int NW) {
+    WideScreenLayout L;
+    L.ldh = round_up(n, fmt == 8 ? 16 : 8);
+    L.S = (int)round_up((p + NW - 1) / NW, 64);
+    return L;
 }
 
 struct WidePlan final : LassoPlan {
@@ -2029,11 +2043,11 @@ struct WidePlan final : LassoPlan {
             for (double v : hp) sum += v;
             fmt = sum / (double)p <= 0.6 ? 8 : 16;
         }
-        const int epl = fmt == 8 ? 16 : 8;
-        const long long ldh = round_up(n, epl);
-        if (ldh > d.ldx) return;
         const int NW = nwg_x * (kWideThreads / 64);
-        const int S = (int)round_up((p + NW - 1) / NW, 64);
+        const WideScreenLayout lay = wide_screen_layout(n, p, fmt, NW);
+        const long long ldh = lay.ldh;
+        const int S = lay.S;
+        if (ldh > d.ldx) return;
         try {
             Xh.alloc((size_t)p * (size_t)ldh * (size_t)(fmt / 8));
             scr_s.alloc((size_t)NW * (size_t)S);
@@ -2043,7 +2057,7 @@ struct WidePlan final : LassoPlan {
             return;
         }
         scr_s.zero(st);
-        const double loosen = 1.0;                                    // factor on every bound (the kernels' argument)
+        const double loosen = kWideScreenLoosen;
         if (fmt == 8) {
             scr_scale.zero(st);
             hipLaunchKernelGGL(wide_screen_prep8_kernel, dim3((unsigned)((p + 3) / 4)), dim3(256), 0, st, d.X.get(), d.ldx, n, p,
@@ -2239,6 +2253,39 @@ struct WidePlan final : LassoPlan {
 
 std::unique_ptr<LassoPlan> make_wide_plan(DeviceData<float>&& d, const LassoProblem& pb, hipStream_t st) {
     return std::unique_ptr<LassoPlan>(new WidePlan(std::move(d), pb, st));
+}
+
+// admm_hip_test_wide_screen_prep: the screen's setup kernels on a host matrix, stored as the plan stores it (leading dimension
+// round_up(n, 16)) with the padding rows [n, ldx) of every column set to the caller's 32-bit pattern; the copy is pre-filled with 0xff
+// bytes (the plan does not clear it: the kernel must write every row), the bound / scale arrays with zeros as setup_screen does.
+void test_wide_screen_prep(const float* X, int n, int p, int fmt, int nw, unsigned pad_fill, void* copy_out, float* s_out, float* scale_out,
+                           double* rate_out, long long* info_out) {
+    require_device();
+    Stream st;
+    const long long ldx = round_up(n, 16);
+    const WideScreenLayout lay = wide_screen_layout(n, p, fmt, nw);
+    const size_t ncopy = (size_t)p * (size_t)lay.ldh * (size_t)(fmt / 8), nslot = (size_t)nw * (size_t)lay.S;
+    const int nb = (p + 3) / 4;
+    DevBuf<float> dX((size_t)ldx * p), ds(nslot), dscale(nslot);
+    DevBuf<unsigned char> dcopy(ncopy);
+    DevBuf<double> part(nb);
+    ADMM_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(dX.get()), (int)pad_fill, (size_t)ldx * p, st.s));
+    ADMM_HIP_CHECK(hipMemcpy2DAsync(dX.get(), ldx * sizeof(float), X, (size_t)n * sizeof(float), (size_t)n * sizeof(float), p, hipMemcpyHostToDevice, st.s));
+    ADMM_HIP_CHECK(hipMemsetAsync(dcopy.get(), 0xff, ncopy, st.s));
+    ds.zero(st.s); dscale.zero(st.s);
+    hipLaunchKernelGGL(wide_screen_rate8_kernel, dim3((unsigned)nb), dim3(256), 0, st.s, dX.get(), ldx, n, p, part.get());
+    if (fmt == 8)
+        hipLaunchKernelGGL(wide_screen_prep8_kernel, dim3((unsigned)nb), dim3(256), 0, st.s, dX.get(), ldx, n, p,
+                           reinterpret_cast<signed char*>(dcopy.get()), lay.ldh, ds.get(), dscale.get(), nw, lay.S, kWideScreenLoosen);
+    else
+        hipLaunchKernelGGL(wide_screen_prep_kernel, dim3((unsigned)nb), dim3(256), 0, st.s, dX.get(), ldx, n, p,
+                           reinterpret_cast<unsigned short*>(dcopy.get()), lay.ldh, ds.get(), nw, lay.S, kWideScreenLoosen);
+    ADMM_HIP_CHECK(hipGetLastError());
+    read_back(copy_out, dcopy.get(), ncopy, st.s);
+    read_back(s_out, ds.get(), nslot * sizeof(float), st.s);
+    if (scale_out != nullptr) read_back(scale_out, dscale.get(), nslot * sizeof(float), st.s);
+    read_back(rate_out, part.get(), (size_t)nb * sizeof(double), st.s);
+    info_out[0] = lay.ldh; info_out[1] = lay.S; info_out[2] = nw; info_out[3] = ldx;
 }
 
 }  // namespace admm

@@ -342,7 +342,7 @@ sbp_xreg_screen_kernel(SbpParams q, int par) {
     if (q.scr_stat != nullptr && lane == 0) { atomicAdd(q.scr_stat, seen); atomicAdd(q.scr_stat + 1, exact); }
 }
 
-// Setup of the screen: column j of A rounded to fp16 (a wave per column; a rounding that is not finite is stored as zero and counts
+// Setup of the screen: column j of A rounded to float and then to fp16 (a wave per column; a rounding that is not finite is stored as zero and counts
 // as rounding error in full) and its bound s_j, sums in double, rounded up to float; a column holding a NaN / Inf gets +Inf.
 __global__ void __launch_bounds__(256)
 sbp_screen_prep_kernel(const double* __restrict__ A, long long lda, int n, int pl, unsigned short* __restrict__ Ah, long long ldh, float* __restrict__ s) {
@@ -358,7 +358,9 @@ sbp_screen_prep_kernel(const double* __restrict__ A, long long lda, int n, int p
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             const double x = r + e < n ? col[r + e] : 0.0;
-            _Float16 hh = (_Float16)(float)x;
+            float xf = (float)x;
+            asm volatile("" : "+v"(xf));      // two roundings, as written: the compiler otherwise merges them into one double -> half conversion
+            _Float16 hh = (_Float16)xf;
             double back = (double)(float)hh;
             if (!(fabs(back) <= 65504.0)) { hh = (_Float16)0.f; back = 0.0; }
             hv[e] = hh;
@@ -1453,6 +1455,9 @@ static void sbp_sprad_batch(const double* A, long long lda, int n, const std::ve
     ADMM_HIP_CHECK(hipGetLastError());
 }
 
+// leading dimension of the screen's fp16 copy (sbp_screen_prep_kernel, sbp_xreg_screen_kernel): whole 16-byte pieces
+long long sbp_screen_ldh(int n) { return round_up(n, 8); }
+
 // device bytes of one batch of `nblocks` runs: Gram matrices, Lanczos bases and the small vectors
 double block_sprad_bytes(int n, int nblocks) {
     return (double)round_up(n, 32) * ((double)round_up(n, 32) + (double)std::min(n, 600) + 8.0) * 8.0 * (double)nblocks;
@@ -1476,6 +1481,27 @@ void test_block_sprad(const double* A, int n, int p, int nblocks, double* out, i
     std::vector<int> ns(nblocks, 0);
     sbp_sprad_batch(dA.get(), lda, n, c0, 0, nblocks, st.s, sprad.data(), ns.data());
     for (int b = 0; b < nblocks; ++b) { out[b] = sprad[b]; nsteps_out[b] = ns[b]; }
+}
+
+// admm_hip_test_sbp_screen_prep: sbp_screen_prep_kernel on a host matrix stored with leading dimension round_up(n, 32) + lda_extra,
+// every row beyond n set to the caller's pattern (both halves of a double); the copy is pre-filled with 0xff bytes (solve_parbp does
+// not clear it: the kernel must write every row of [0, ldh)).
+void test_sbp_screen_prep(const double* A, int n, int pl, int lda_extra, unsigned pad_fill, unsigned short* copy_out, float* s_out, long long* info_out) {
+    require_device();
+    Stream st;
+    const long long lda = round_up(n, 32) + lda_extra, ldh = sbp_screen_ldh(n);
+    DevBuf<double> dA((size_t)lda * pl);
+    DevBuf<unsigned short> dcopy((size_t)pl * (size_t)ldh);
+    DevBuf<float> ds(pl);
+    ADMM_HIP_CHECK(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(dA.get()), (int)pad_fill, (size_t)lda * pl * 2, st.s));
+    ADMM_HIP_CHECK(hipMemcpy2DAsync(dA.get(), lda * sizeof(double), A, (size_t)n * sizeof(double), (size_t)n * sizeof(double), pl, hipMemcpyHostToDevice, st.s));
+    ADMM_HIP_CHECK(hipMemsetAsync(dcopy.get(), 0xff, (size_t)pl * (size_t)ldh * sizeof(unsigned short), st.s));
+    ds.zero(st.s);
+    hipLaunchKernelGGL(sbp_screen_prep_kernel, dim3((unsigned)((pl + 3) / 4)), dim3(256), 0, st.s, dA.get(), lda, n, pl, dcopy.get(), ldh, ds.get());
+    ADMM_HIP_CHECK(hipGetLastError());
+    read_back(copy_out, dcopy.get(), (size_t)pl * (size_t)ldh * sizeof(unsigned short), st.s);
+    read_back(s_out, ds.get(), (size_t)pl * sizeof(float), st.s);
+    info_out[0] = ldh; info_out[1] = lda;
 }
 
 // d: this rank's columns (n x pl).  nblocks: N (global); blk_first / nloc: the global blocks this rank holds; p_total.
@@ -1676,7 +1702,7 @@ void solve_parbp(const DeviceData<double>& d, const admm_opts& opts, int nblocks
     DevBuf<float> scr_s;
     DevBuf<unsigned long long> scr_stat;
     if (screen) {
-        const long long ldh = round_up(n, 8);
+        const long long ldh = sbp_screen_ldh(n);
         try {
             Ah.alloc((size_t)pl * (size_t)ldh); scr_s.alloc(pl);
         } catch (const Error&) {

@@ -36,6 +36,13 @@ template <typename T> void test_gemv_t_ex(const GemvExRequest& q);
 void test_wide_op(const float* X, int n, int p, const float* v, float* w);
 void test_block_sprad(const double* A, int n, int p, int nblocks, double* out, int* nsteps_out);      // sharing_bp.hip
 double block_sprad_bytes(int n, int nblocks);      // sharing_bp.hip: device bytes of one batch of nblocks Lanczos runs (host only)
+struct WideScreenLayout { long long ldh; int S; };      // lasso_wide.hip: leading dimension of the screen's copy, stride of its [NW][S] bound / scale arrays
+WideScreenLayout wide_screen_layout(int n, int p, int fmt, int NW);      // (host only) what WidePlan::setup_screen and the hook below both use
+void test_wide_screen_prep(const float* X, int n, int p, int fmt, int nw, unsigned pad_fill, void* copy_out, float* s_out, float* scale_out,
+                           double* rate_out, long long* info_out);      // lasso_wide.hip
+long long sbp_screen_ldh(int n);      // sharing_bp.hip (host only)
+void test_sbp_screen_prep(const double* A, int n, int pl, int lda_extra, unsigned pad_fill, unsigned short* copy_out, float* s_out,
+                          long long* info_out);      // sharing_bp.hip
 template <typename T> void test_gather(const T* A, int rows, int cols, const T* v, double* y);
 void test_cv_fold_system(const double* x, const double* y, int n, int p, const int* fold_id, int nfolds, int fold,
                          int standardize, int intercept, float* gram, float* xy, float* mean_x, float* scale_x, float* mean_scale_y);

@@ -825,6 +825,21 @@ ADMM_HIP_API int admm_hip_test_wide_op(const float* X, int n, int p, const float
  * matrix A (n x p column-major, leading dimension n), all blocks in ONE batch of Lanczos runs in lockstep; nsteps_out[b]: the steps
  * block b was judged on.  ADMM_ERR_EIGS as the solver raises it. */
 ADMM_HIP_API int admm_hip_test_block_sprad(const double* A, int n, int p, int nblocks, double* out, int* nsteps_out);
+/* The setup of the wide solver's safe screen (wide_screen_prep_kernel for fmt 16, wide_screen_prep8_kernel for fmt 8, and
+ * wide_screen_rate8_kernel, which picks the format) on the HOST float matrix X (n x p column-major, leading dimension n), stored on the
+ * device as the plan stores it: leading dimension ldx = round_up(n, 16), rows [n, ldx) of every column set to the 32-bit pattern
+ * pad_fill.  nw stands for the plan's number of waves NW.  copy_out: the raw copy, p * ldh elements of 2 bytes (fmt 16, ldh =
+ * round_up(n, 8)) or 1 byte (fmt 8, ldh = round_up(n, 16)), pre-filled with 0xff bytes; copy_capacity: its size in elements.  s_out,
+ * scale_out (fmt 8 only; may be NULL for fmt 16): the raw [nw * S] arrays, S = round_up(ceil(p / nw), 64), cleared before the launch as
+ * the plan clears them; column j is at [(j % nw) * S + j / nw].  rate_out: the ceil(p / 4) partial sums of wide_screen_rate8_kernel.
+ * info_out [4]: ldh, S, nw, ldx. */
+ADMM_HIP_API int admm_hip_test_wide_screen_prep(const float* X, int n, int p, int fmt, int nw, unsigned pad_fill, void* copy_out,
+                                                long long copy_capacity, float* s_out, float* scale_out, double* rate_out, long long* info_out);
+/* The same for the sharing basis pursuit's screen (sbp_screen_prep_kernel): HOST double A (n x pl column-major, leading dimension n) stored
+ * with leading dimension round_up(n, 32) + lda_extra, every row beyond n set to pad_fill in both halves of the double.  copy_out: pl * ldh
+ * fp16 values, ldh = round_up(n, 8), pre-filled with 0xff bytes; s_out [pl]; info_out [2]: ldh, lda. */
+ADMM_HIP_API int admm_hip_test_sbp_screen_prep(const double* A, int n, int pl, int lda_extra, unsigned pad_fill, unsigned short* copy_out,
+                                               long long copy_capacity, float* s_out, long long* info_out);
 /* y = A v over the NON-ZERO entries of v with the gather mat-vec of the one-pass consensus workers and of basis pursuit (the product
  * that replaces the reference's first streaming pass, PADMMLasso.h:25 / ADMMBP.h:65): A HOST rows x cols column-major (leading
  * dimension rows), v length cols in A's type, y length rows in double (the kernel's accumulation type). */

@@ -821,6 +821,64 @@ def test_the_wide_op_and_block_sprad_hooks_refuse_bad_requests_before_they_look_
         assert _small_hook(lib, hook, over) == (INVALID_ARG, message), (hook, over)
 
 
+# ---- the hooks of the safe screens' setup kernels (tests/test_gpu_screen_prep.py): argument checks only
+_WSCR_NULL = "wide_screen_prep hook: X, copy_out, s_out, rate_out and info_out must not be NULL"
+_WSCR_SHAPE = "wide_screen_prep hook: n, p and nw in 1 .. 2^20, at most 2^28 elements of storage"
+_WSCR_CAP = "wide_screen_prep hook: copy_capacity below p * ldh elements"
+_SSCR_NULL = "sbp_screen_prep hook: A, copy_out, s_out and info_out must not be NULL"
+_SSCR_SHAPE = "sbp_screen_prep hook: n and pl in 1 .. 2^20, lda_extra in 0 .. 4096, at most 2^27 elements of storage"
+# (hook, overrides of a well-formed call on 4 x 6 data -- fmt 16, nw 4, capacity 48 = 6 columns of ldh 8 --, message)
+SCREEN_HOOK_TABLE = [
+    ("wide_screen_prep", dict(X=None), _WSCR_NULL), ("wide_screen_prep", dict(copy_out=None), _WSCR_NULL), ("wide_screen_prep", dict(s_out=None), _WSCR_NULL),
+    ("wide_screen_prep", dict(rate_out=None), _WSCR_NULL), ("wide_screen_prep", dict(info_out=None), _WSCR_NULL),
+    ("wide_screen_prep", dict(fmt=0), "wide_screen_prep hook: fmt is 8 or 16"), ("wide_screen_prep", dict(fmt=32), "wide_screen_prep hook: fmt is 8 or 16"),
+    ("wide_screen_prep", dict(fmt=8, copy_capacity=96, scale_out=None), "wide_screen_prep hook: the 8-bit code needs scale_out"),
+    ("wide_screen_prep", dict(n=0), _WSCR_SHAPE), ("wide_screen_prep", dict(n=(1 << 20) + 1), _WSCR_SHAPE), ("wide_screen_prep", dict(p=0), _WSCR_SHAPE),
+    ("wide_screen_prep", dict(p=(1 << 20) + 1), _WSCR_SHAPE), ("wide_screen_prep", dict(nw=0), _WSCR_SHAPE), ("wide_screen_prep", dict(nw=-4), _WSCR_SHAPE),
+    ("wide_screen_prep", dict(nw=(1 << 20) + 1), _WSCR_SHAPE), ("wide_screen_prep", dict(n=1 << 20, p=1 << 20), _WSCR_SHAPE),
+    ("wide_screen_prep", dict(copy_capacity=47), _WSCR_CAP), ("wide_screen_prep", dict(copy_capacity=0), _WSCR_CAP),
+    ("wide_screen_prep", dict(fmt=8, copy_capacity=95), _WSCR_CAP), ("wide_screen_prep", dict(n=9, copy_capacity=95), _WSCR_CAP),
+    ("sbp_screen_prep", dict(A=None), _SSCR_NULL), ("sbp_screen_prep", dict(copy_out=None), _SSCR_NULL), ("sbp_screen_prep", dict(s_out=None), _SSCR_NULL),
+    ("sbp_screen_prep", dict(info_out=None), _SSCR_NULL),
+    ("sbp_screen_prep", dict(n=0), _SSCR_SHAPE), ("sbp_screen_prep", dict(n=(1 << 20) + 1), _SSCR_SHAPE), ("sbp_screen_prep", dict(p=0), _SSCR_SHAPE),
+    ("sbp_screen_prep", dict(p=(1 << 20) + 1), _SSCR_SHAPE), ("sbp_screen_prep", dict(lda_extra=-8), _SSCR_SHAPE), ("sbp_screen_prep", dict(lda_extra=4104), _SSCR_SHAPE),
+    ("sbp_screen_prep", dict(n=1 << 14, p=1 << 14), _SSCR_SHAPE),
+    ("sbp_screen_prep", dict(copy_capacity=47), "sbp_screen_prep hook: copy_capacity below pl * ldh elements"),
+    ("sbp_screen_prep", dict(n=9, copy_capacity=95), "sbp_screen_prep hook: copy_capacity below pl * ldh elements"),
+]
+SCREEN_HOOK_GOOD = [("wide_screen_prep", dict()), ("wide_screen_prep", dict(fmt=8, copy_capacity=96)), ("wide_screen_prep", dict(scale_out=None)),
+                    ("wide_screen_prep", dict(nw=96)), ("sbp_screen_prep", dict()), ("sbp_screen_prep", dict(lda_extra=8))]
+
+
+def _screen_hook(lib, hook, over):
+    keep = dict(X=np.zeros(1 << 10, np.float32), A=np.zeros(1 << 10), copy_out=np.zeros(1 << 10, np.uint16), s_out=np.zeros(1 << 14, np.float32),
+                scale_out=np.zeros(1 << 14, np.float32), rate_out=np.zeros(64), info_out=np.zeros(4, np.int64))
+    types = dict(X=ctypes.c_float, A=ctypes.c_double, copy_out=ctypes.c_ushort, s_out=ctypes.c_float, scale_out=ctypes.c_float, rate_out=ctypes.c_double,
+                 info_out=ctypes.c_longlong)
+    v = dict({name: _pointer(a, types[name]) for name, a in keep.items()}, n=4, p=6, fmt=16, nw=4, lda_extra=0, pad_fill=0x7FC00000, copy_capacity=48)
+    v["copy_out"] = ctypes.cast(v["copy_out"], ctypes.c_void_p)
+    v.update(over)
+    names = ("X n p fmt nw pad_fill copy_out copy_capacity s_out scale_out rate_out info_out" if hook == "wide_screen_prep"
+             else "A n p lda_extra pad_fill copy_out copy_capacity s_out info_out")
+    rc = getattr(lib, "admm_hip_test_" + hook)(*[v[name] for name in names.split()])
+    return rc, lib.admm_hip_last_error().decode()
+
+
+def test_the_screen_setup_hooks_refuse_bad_requests_before_they_look_for_a_device():
+    from admm_amd import _lib
+    lib = _lib.load()
+    for hook, over, message in SCREEN_HOOK_TABLE:
+        assert _screen_hook(lib, hook, over) == (INVALID_ARG, message), (hook, over)
+
+
+@pytest.mark.skipif(os.path.exists("/dev/kfd"), reason="only meaningful on a machine without a GPU")
+def test_well_formed_screen_hook_requests_pass_every_check_and_then_find_no_device():
+    from admm_amd import _lib
+    lib = _lib.load()
+    for hook, over in SCREEN_HOOK_GOOD:
+        assert _screen_hook(lib, hook, over)[0] == NO_DEVICE, (hook, over, lib.admm_hip_last_error())
+
+
 @pytest.mark.skipif(os.path.exists("/dev/kfd"), reason="only meaningful on a machine without a GPU")
 def test_well_formed_hook_requests_pass_every_check_and_then_find_no_device():
     from admm_amd import _lib
