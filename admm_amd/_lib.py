@@ -75,7 +75,8 @@ EXPORTS = ["admm_hip_lasso", "admm_hip_enet", "admm_hip_parlasso", "admm_hip_lad
            "admm_hip_options_default", "admm_hip_options_set", "admm_hip_option_set", "admm_hip_options_reset", "admm_hip_option_get",
            "admm_hip_last_parallel_layout", "admm_hip_parallel_assign", "admm_hip_grplasso", "admm_hip_grplasso_plan_create",
            "admm_hip_quantreg", "admm_hip_quantreg_state", "admm_hip_huber", "admm_hip_huber_state",
-           "admm_hip_logit", "admm_hip_logit_state", "admm_hip_logit_multi", "admm_hip_logit_ridge", "admm_hip_logit_ridge_state", "admm_hip_test_logit_prox",
+           "admm_hip_logit", "admm_hip_logit_state", "admm_hip_logit_multi", "admm_hip_logit_ridge", "admm_hip_logit_ridge_state",
+           "admm_hip_logit_enet", "admm_hip_logit_enet_lambda_max", "admm_hip_logit_enet_state", "admm_hip_test_logit_prox",
            "admm_hip_mtlasso", "admm_hip_mtlasso_plan_create", "admm_hip_test_symv_multi", "admm_hip_test_tall_early_exits",
            "admm_hip_sgl", "admm_hip_sgl_plan_create", "admm_hip_host_sgl_lambda0",
            "admm_hip_boxenet", "admm_hip_boxenet_plan_create", "admm_hip_host_box_lambda0",
@@ -172,6 +173,15 @@ def load():
                                                 _c_double_p, _c_int_p, ctypes.POINTER(AdmmStats)]
                                                + [_c_double_p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)] * 2)
     lib.admm_hip_logit_ridge_state.restype = ctypes.c_int
+    lib.admm_hip_logit_enet.argtypes = [_DP, _DP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_double_p, _c_double_p, ctypes.c_int,
+                                        ctypes.POINTER(AdmmOpts), _c_double_p, _c_int_p, ctypes.POINTER(AdmmStats)]
+    lib.admm_hip_logit_enet.restype = ctypes.c_int
+    lib.admm_hip_logit_enet_lambda_max.argtypes = [_DP, _DP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_double_p]
+    lib.admm_hip_logit_enet_lambda_max.restype = ctypes.c_int
+    lib.admm_hip_logit_enet_state.argtypes = ([_DP, _DP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.POINTER(AdmmOpts),
+                                               _c_double_p, _c_int_p, ctypes.POINTER(AdmmStats)]
+                                              + [_c_double_p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)] * 2)
+    lib.admm_hip_logit_enet_state.restype = ctypes.c_int
     lib.admm_hip_test_logit_prox.argtypes = [_c_double_p, ctypes.c_longlong, ctypes.c_double, _c_double_p]
     lib.admm_hip_test_logit_prox.restype = ctypes.c_int
     lib.admm_hip_bp_state.argtypes = lib.admm_hip_bp_traced.argtypes + [_c_double_p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]

@@ -892,6 +892,173 @@ class ADMM_LogitRidgeOvR(ADMM_LogitRidge):
         return fit
 
 
+class ADMM_LogitEnet_fit:
+    def __init__(self, lam, alpha, beta, niter, stats):
+        self.lam = lam              # numeric ncell, in the order given
+        self.alpha = alpha          # numeric ncell: cell l is the pair (lam[l], alpha[l])
+        self.beta = beta            # (p + 1) x k x ncell, intercept first            (fit(trace=True): p + 1)
+        self.niter = niter          # integer k x ncell; maxit + 1: not converged     (fit(trace=True): a scalar)
+        self.stats = stats
+
+    def __repr__(self):
+        shape = " x ".join(str(s) for s in np.shape(self.beta))
+        return (f"ADMM elastic-net logistic regression fitting result\n\n$lambda\n{self.lam}\n\n$alpha\n{self.alpha}\n\n$beta\n<{shape}> array\n\n"
+                f"$niter\n{self.niter}")
+
+    def show(self):
+        print(repr(self))
+
+
+class ADMM_LogitEnet(ADMM_LAD):
+    """Elastic-net logistic regression (admm_hip_logit_enet): per label column c and cell l = (lam[l], alpha[l])
+        minimise  sum_i log(1 + exp(-s_i (b0 + x~_i'b))) + lam[l] (alpha[l] sum_j |b_j| + (1 - alpha[l]) / 2 sum_j b_j^2),   s = 2 Y[:, c] - 1,
+    on the library's standardised columns x~ (glmnet's lambda times n), the intercept not penalised, the coefficients returned on the
+    caller's scale with exact zeros.  Y as ADMM_LogitMulti's.  lam: None, a positive scalar or a vector; alpha: a scalar in [0, 1] (every
+    cell's) or a vector as long as lam (cells are PAIRS).  lam = None: nlambda values log-spaced from max_c lambda_1(c) / alpha down to
+    lambda_min_ratio times that (admm_lasso's defaults: 100 values, ratio 1e-4, or 1e-2 when nrow(x) < ncol(x)); it needs a scalar
+    alpha > 0 and asks the device for lambda_1 (admm_hip_logit_enet_lambda_max) when fit() or lambda_one() is called.  Every fit starts
+    cold, all of them on one inverse; there is no condition on nrow(x) against ncol(x)."""
+
+    def __init__(self, x, Y, lam=None, alpha=1.0, intercept=True, nlambda=100, lambda_min_ratio=None, n=None, p=None, k=None):
+        n_, p_ = _shape(x, n, p)
+        if n_ < 2:
+            _stop("nrow(x) must be at least 2")
+        if isinstance(Y, DevicePtr):
+            if k is None:
+                _stop("k is required with a DevicePtr")
+            k_ = int(k)
+        else:
+            Y = np.asarray(Y, dtype=np.float64)
+            if Y.ndim == 1:
+                Y = Y[:, None]
+            if Y.ndim != 2:
+                _stop("Y must be a matrix")
+            Y = np.asfortranarray(Y)
+            k_ = Y.shape[1]
+            if Y.shape[0] != n_:
+                _stop("nrow(x) should be equal to nrow(Y)")
+        if k_ < 1:
+            _stop("y must have at least one column")
+        al = np.asarray(alpha, dtype=np.float64)
+        if al.ndim > 1 or al.size < 1:
+            _stop("alpha must be a scalar or a vector")
+        if not np.all((al >= 0.0) & (al <= 1.0)):
+            _stop("every alpha must lie in [0, 1]")
+        if lam is None:
+            if al.ndim != 0 or not float(al) > 0.0:
+                _stop("the automatic lambda grid needs one alpha > 0 (alpha = 0 has no lambda_max: pass lam)")
+            if int(nlambda) <= 0:
+                _stop("nlambda must be a positive integer")
+            lmr = (0.01 if n_ < p_ else 0.0001) if lambda_min_ratio is None else float(lambda_min_ratio)
+            if lmr <= 0 or lmr >= 1:
+                _stop("lambda_min_ratio must be within (0, 1)")
+            self.lam, self.alpha = None, np.full(int(nlambda), float(al))
+            self.nlambda, self.lambda_min_ratio = int(nlambda), lmr
+        else:
+            lm = np.atleast_1d(np.asarray(lam, dtype=np.float64))
+            if lm.ndim != 1 or lm.size < 1:
+                _stop("lam must hold at least one value")
+            if not (np.all(np.isfinite(lm)) and np.all(lm > 0)):
+                _stop("every lambda must be finite and positive")
+            if al.ndim == 1 and al.size != lm.size:
+                _stop("alpha must be a scalar or as long as lam (cells are pairs)")
+            self.lam = np.ascontiguousarray(lm)
+            self.alpha = np.ascontiguousarray(np.broadcast_to(al, lm.shape), dtype=np.float64)
+            self.nlambda, self.lambda_min_ratio = int(lm.size), None
+        if not isinstance(Y, DevicePtr):
+            for c in range(k_):
+                col = Y[:, c]
+                if not np.all((col == 0.0) | (col == 1.0)):
+                    _stop(f"column {c} of y: every label must be exactly 0 or 1")
+                if np.all(col == 0.0) or np.all(col == 1.0):
+                    _stop(f"column {c} of y must hold both classes")
+        self.x, self.y, self.n, self.p, self.k = x, Y, int(n_), int(p_), k_
+        self.maxit = 10000
+        self.eps_abs = 1e-4
+        self.eps_rel = 1e-4
+        self.rho = 1.0
+        self.intercept = bool(intercept)
+
+    def _inputs(self):
+        xp, xmem, xk = as_input(self.x)
+        yp, ymem, yk = as_input(self.y)
+        if xmem != ymem:
+            _stop("x and y must live in the same memory space")
+        return xp, yp, xmem, (xk, yk)              # (the last: what keeps converted buffers alive during the call)
+
+    def lambda_one(self):
+        """-> (k,) lambda_1 per label column: max_j |x~_j'(y_c - mean(y_c))| (intercept) or |x~_j'(y_c - 1/2)| (none), on the device.
+        For alpha > 0 the coefficients of column c are all zero from lambda_1[c] / alpha on."""
+        lib = _lib.load()
+        xp, yp, xmem, keep = self._inputs()
+        out = np.zeros(self.k, dtype=np.float64)
+        check(lib.admm_hip_logit_enet_lambda_max(xp, yp, self.n, self.p, self.k, xmem, int(self.intercept), out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+        return out
+
+    def _cells(self):
+        if self.lam is not None:
+            return self.lam, self.alpha
+        top = float(self.lambda_one().max()) / float(self.alpha[0])
+        lam = np.exp(np.linspace(np.log(top), np.log(top * self.lambda_min_ratio), self.nlambda))
+        return np.ascontiguousarray(lam), self.alpha
+
+    def fit(self, trace=False, state=0):
+        """-> ADMM_LogitEnet_fit.  trace / state (admm_hip_logit_enet_state) for one column and one cell only: beta is then the vector
+        p + 1 and niter a scalar, and the iterate dump has dimension n + p (the penalty rows behind the data rows); its record 0
+        carries the zero response in its x slot and [2 y - 1, 0 ... 0] in its z slot."""
+        lib = _lib.load()
+        xp, yp, xmem, keep = self._inputs()
+        if (trace or state) and (self.k != 1 or self.nlambda != 1):
+            _stop("trace and state are recorded for a single label column and a single cell")
+        lam, alpha = self._cells()
+        ncell = int(lam.size)
+        o = AdmmOpts(self.maxit, self.eps_abs, self.eps_rel, self.rho)
+        beta = np.zeros((self.p + 1) * self.k * ncell, dtype=np.float64)
+        niter = np.zeros(self.k * ncell, dtype=np.int32)
+        stats = AdmmStats()
+        dp = ctypes.POINTER(ctypes.c_double)
+        bp, np_ = beta.ctypes.data_as(dp), niter.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+        if trace:
+            tr, ntr = _trace_buffers(self.maxit)
+            sbuf, nst = _state_buffers(state, self.n + self.p)
+            check(lib.admm_hip_logit_enet_state(xp, yp, self.n, self.p, xmem, int(self.intercept), float(lam[0]), float(alpha[0]), ctypes.byref(o), bp, np_,
+                                                ctypes.byref(stats), *_trace_args(tr, ntr), *_state_args(sbuf, nst)))
+            fit = ADMM_LogitEnet_fit(lam.copy(), alpha.copy(), beta, int(niter[0]), stats.as_dict())
+            fit.trace = tr[:ntr.value].copy()
+            fit.state = sbuf[:nst.value].copy() if state else None
+            return fit
+        check(lib.admm_hip_logit_enet(xp, yp, self.n, self.p, self.k, xmem, int(self.intercept), lam.ctypes.data_as(dp), alpha.ctypes.data_as(dp), ncell,
+                                      ctypes.byref(o), bp, np_, ctypes.byref(stats)))
+        fit = ADMM_LogitEnet_fit(lam.copy(), alpha.copy(), beta.reshape((self.p + 1, self.k, ncell), order="F"), niter.reshape((self.k, ncell), order="F"),
+                                 stats.as_dict())
+        fit.trace = fit.state = None
+        return fit
+
+
+class ADMM_LogitEnetOvR(ADMM_LogitEnet):
+    """One-vs-rest on ADMM_LogitEnet: the indicator matrix of ADMM_LogitOvR, `classes` sorted, column c separates classes[c] from the rest."""
+
+    def __init__(self, x, labels, lam=None, alpha=1.0, intercept=True, nlambda=100, lambda_min_ratio=None, n=None, p=None):
+        lab = np.asarray(labels)
+        if lab.ndim != 1:
+            _stop("labels must be a vector")
+        if not (np.issubdtype(lab.dtype, np.integer) or np.issubdtype(lab.dtype, np.bool_)):
+            if not (np.issubdtype(lab.dtype, np.floating) and np.all(np.isfinite(lab)) and np.all(lab == np.round(lab))):
+                _stop("labels must be integers")
+            lab = lab.astype(np.int64)
+        classes = np.unique(lab)
+        if classes.size < 2:
+            _stop("labels must hold at least two classes")
+        ADMM_LogitEnet.__init__(self, x, (lab[:, None] == classes[None, :]).astype(np.float64), lam, alpha, intercept, nlambda, lambda_min_ratio, n, p)
+        self.classes = classes
+
+    def fit(self, trace=False, state=0):
+        """-> ADMM_LogitEnet_fit with `classes`."""
+        fit = ADMM_LogitEnet.fit(self, trace, state)
+        fit.classes = self.classes
+        return fit
+
+
 class LassoPlan:
     """Prepared problem (admm_hip_lasso_plan_*): setup once, run the lambda path repeatedly.
 
@@ -1022,6 +1189,14 @@ def admm_logit_ridge(x, Y, lam, intercept=True, **kw):
 
 def admm_logit_ridge_ovr(x, labels, lam, intercept=True, **kw):
     return ADMM_LogitRidgeOvR(x, labels, lam, intercept, **kw)
+
+
+def admm_logit_enet(x, Y, lam=None, alpha=1.0, intercept=True, nlambda=100, lambda_min_ratio=None, **kw):
+    return ADMM_LogitEnet(x, Y, lam, alpha, intercept, nlambda, lambda_min_ratio, **kw)
+
+
+def admm_logit_enet_ovr(x, labels, lam=None, alpha=1.0, intercept=True, nlambda=100, lambda_min_ratio=None, **kw):
+    return ADMM_LogitEnetOvR(x, labels, lam, alpha, intercept, nlambda, lambda_min_ratio, **kw)
 
 
 def admm_bp(x, y, **kw):

@@ -167,6 +167,24 @@ int admm_hip_logit_ridge_state(const double* x, const double* y, int n, int p, i
     });
 }
 
+int admm_hip_logit_enet(const double* x, const double* y, int n, int p, int k, int mem, int intercept, const double* lambda, const double* alpha, int ncell,
+                        const admm_opts* opts, double* beta_out, int* niter_out, admm_stats* stats) {
+    return guarded([&] { logit_enet(x, y, n, p, k, mem, intercept, lambda, alpha, ncell, opts, DenseOut{beta_out, niter_out, stats}); });
+}
+
+int admm_hip_logit_enet_lambda_max(const double* x, const double* y, int n, int p, int k, int mem, int intercept, double* out) {
+    return guarded([&] { logit_enet_lambda_max(x, y, n, p, k, mem, intercept, out); });
+}
+
+int admm_hip_logit_enet_state(const double* x, const double* y, int n, int p, int mem, int intercept, double lambda, double alpha, const admm_opts* opts,
+                              double* beta_out, int* niter_out, admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out,
+                              double* state_out, long long state_cap, long long* nstate_out) {
+    return guarded([&] {
+        logit_enet(x, y, n, p, 1, mem, intercept, &lambda, &alpha, 1, opts,
+                   DenseOut{beta_out, niter_out, stats, {trace_out, trace_cap, ntrace_out}, {state_out, state_cap, nstate_out}});
+    });
+}
+
 int admm_hip_logit_state(const double* x, const double* y, int n, int p, int mem, int intercept, const admm_opts* opts, double* beta_out, int* niter_out,
                          admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out, double* state_out, long long state_cap,
                          long long* nstate_out) {

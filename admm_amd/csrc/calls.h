@@ -68,6 +68,12 @@ void logit_multi(const double* x, const double* y, int n, int p, int k, int mem,
 // trace / state for k = 1 and nlambda = 1 only
 void logit_ridge(const double* x, const double* y, int n, int p, int k, int mem, int intercept, const double* lambda, int nlambda, const admm_opts* opts,
                  const DenseOut& out);
+// the same with the elastic-net penalty: ncell (lambda, alpha) pairs, used in the order given, all on one inverse; out.beta_out:
+// (p + 1) x k x ncell, out.niter_out: k x ncell; trace / state for k = 1 and ncell = 1 only
+void logit_enet(const double* x, const double* y, int n, int p, int k, int mem, int intercept, const double* lambda, const double* alpha, int ncell,
+                const admm_opts* opts, const DenseOut& out);
+// out[k]: per label column max_j |x~_j'(y_c - mean)| on the standardised columns (lambda_max of a cell is this over its alpha)
+void logit_enet_lambda_max(const double* x, const double* y, int n, int p, int k, int mem, int intercept, double* out);
 void bp(const double* x, const double* y, int n, int p, int mem, const admm_opts* opts, const DenseOut& out);
 // admm_hip_parbp(_traced): over in-process ranks when PAR_DEVICES lists several devices; parbp_dist: this rank's columns of p_total
 void parbp(const double* x, const double* y, int n, int p, int mem, int nthread, const admm_opts* opts, const DenseOut& out);

@@ -444,6 +444,76 @@ void logit_ridge(const double* x, const double* y, int n, int p, int k, int mem,
     finish_result(res.dense, t0, out.trace, out.stats);
 }
 
+// the label validation of logit_multi / logit_ridge (first offending column, 0-based); ones: per column the count of labels 1.0, or NULL
+static void check_label_columns(const double* y, int n, int k, int mem, std::vector<long long>* ones_out) {
+    for (int c = 0; c < k; ++c) {
+        const double* yc = y + (size_t)c * n;
+        long long bad = 0, ones = 0;
+        if (mem == ADMM_MEM_HOST) {
+            for (int i = 0; i < n; ++i) { if (yc[i] == 1.0) ++ones; else if (!(yc[i] == 0.0)) ++bad; }
+        } else {
+            require_device();
+            Stream cs;
+            logit_count_labels(yc, n, &bad, &ones, cs.s);
+        }
+        ADMM_REQUIRE(bad == 0, "column " + std::to_string(c) + " of y: every label must be exactly 0 or 1");
+        ADMM_REQUIRE(ones > 0 && ones < n, "column " + std::to_string(c) + " of y must hold both classes");
+        if (ones_out) (*ones_out)[c] = ones;
+    }
+}
+
+// admm_hip_logit_enet: logit_ridge's call with (lambda, alpha) cells in place of the lambda grid (solve_logit_enet): one fit per
+// (column, cell), all of them on ONE inverse.
+void logit_enet(const double* x, const double* y, int n, int p, int k, int mem, int intercept, const double* lambda, const double* alpha, int ncell,
+                const admm_opts* opts, const DenseOut& out) {
+    const bool icpt = intercept != 0;
+    ADMM_REQUIRE(k >= 1, "y must have at least one column");
+    ADMM_REQUIRE(lambda != nullptr && alpha != nullptr, "lambda and alpha must not be NULL");
+    ADMM_REQUIRE(ncell >= 1, "lambda must have at least one value");
+    for (int l = 0; l < ncell; ++l) ADMM_REQUIRE(std::isfinite(lambda[l]) && lambda[l] > 0.0, "every lambda must be finite and positive");
+    for (int l = 0; l < ncell; ++l) ADMM_REQUIRE(alpha[l] >= 0.0 && alpha[l] <= 1.0, "every alpha must lie in [0, 1]");
+    ADMM_REQUIRE((k == 1 && ncell == 1) || out.trace.cap == 0, "the decision trace is recorded for a single column and a single cell");
+    check_dense(x, y, n, p, mem, opts, n >= 2, "nrow(x) must be at least 2", true, out);
+    check_label_columns(y, n, k, mem, nullptr);
+    require_device();
+    const double t0 = now_s();
+    Stream st;
+    DeviceData<double> d;
+    upload_standardize<double>(d, x, y, n, p, mem, true, icpt, st.s);      // (the response it standardises, column 0, is replaced by zeros)
+    Resident labels(y, (size_t)n * k, mem);
+    QuantResult res;
+    begin_result(res.dense, d, out.trace);
+    res.dense.state_cap = out.state.cap;
+    solve_logit_enet(d, icpt, labels.p, k, lambda, alpha, ncell, *opts, res, st.s);
+    std::memcpy(out.beta_out, res.beta.data(), res.beta.size() * sizeof(double));
+    for (size_t c = 0; c < res.niter.size(); ++c) out.niter_out[c] = res.niter[c];
+    store_state(res.dense, out.state);
+    finish_result(res.dense, t0, out.trace, out.stats);
+}
+
+// admm_hip_logit_enet_lambda_max: lambda_1 per label column on the standardised columns, max_j |x~_j'(y_c - mean)|, mean = the column's
+// share of ones with the intercept and 1/2 without (the gradient of the likelihood at b = 0 with the fitted, or the absent, intercept)
+void logit_enet_lambda_max(const double* x, const double* y, int n, int p, int k, int mem, int intercept, double* out) {
+    const bool icpt = intercept != 0;
+    ADMM_REQUIRE(k >= 1, "y must have at least one column");
+    ADMM_REQUIRE(x != nullptr && y != nullptr, "x and y must not be NULL");
+    ADMM_REQUIRE(n > 0 && p > 0, "n and p must be positive");
+    ADMM_REQUIRE(mem == ADMM_MEM_HOST || mem == ADMM_MEM_DEVICE, "mem must be ADMM_MEM_HOST or ADMM_MEM_DEVICE");
+    ADMM_REQUIRE(out != nullptr, "output pointers must not be NULL");
+    ADMM_REQUIRE(n >= 2, "nrow(x) must be at least 2");
+    std::vector<long long> ones(k);
+    check_label_columns(y, n, k, mem, &ones);
+    require_device();
+    Stream st;
+    DeviceData<double> d;
+    upload_standardize<double>(d, x, y, n, p, mem, true, icpt, st.s);
+    Resident labels(y, (size_t)n * k, mem);
+    std::vector<double> mean(k), lam1(k);
+    for (int c = 0; c < k; ++c) mean[c] = icpt ? (double)ones[c] / (double)n : 0.5;
+    logit_enet_lambda_one(d, labels.p, k, mean.data(), lam1.data(), st.s);
+    for (int c = 0; c < k; ++c) out[c] = lam1[c];
+}
+
 void bp(const double* x, const double* y, int n, int p, int mem, const admm_opts* opts, const DenseOut& out) {
     run_dense(x, y, n, p, mem, opts, false, false,                                   // BP.cpp:24-27: no standardisation
               p > n, "ncol(x) must be greater than nrow(x)", true, p,                // R/10_admm_bp.R:30-31

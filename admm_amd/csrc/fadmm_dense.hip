@@ -18,6 +18,7 @@
 #include "test_hooks.h"
 #include <cstring>
 #include <cstdio>
+#include <type_traits>
 #include "loop_driver.h"
 
 namespace admm {
@@ -59,6 +60,7 @@ struct DenseParams {
     // row_i y_i to its partials of X'z, X'y.  One pass over X per iteration instead of two (X'vec, then X s); the p-vectors are direct
     // products of the current iterates, not recurrences: nothing accumulates.
     int lp;
+    int sgn_cols;                             // kProxLogitE, slotted loop: the label columns of the sign matrix -- fit k reads column k mod sgn_cols (in the padding behind lp: the argument block keeps its size and offsets)
     const double* Xd;                         // X'd [lp]
     double *Xz0, *Xz1, *Xy0, *Xy1;            // X'z, X'y in the slots of z0 / z1, y0 / y1
     double* u;                                // X'vec of this iteration
@@ -72,6 +74,7 @@ constexpr int kDenseThreads = 256;
 constexpr int kQuantAutoSlots = 1;         // what QUANT_SLOTS=0 picks on the one-pass branch (decided by scripts/bench_quantreg.py)
 constexpr int kLogitAutoSlots = 4;         // the same for admm_hip_logit_multi: as many as the layout admits (measured: scripts/bench_logit_multi.py, profiles/logit_multi.md)
 constexpr int kLogitRidgeAutoSlots = kLogitAutoSlots;      // the same for admm_hip_logit_ridge: ahead of serial at every layout with slots (measured: scripts/bench_logit_ridge.py, profiles/logit_ridge.md)
+constexpr int kLogitEnetAutoSlots = kLogitAutoSlots;      // the same for admm_hip_logit_enet: ahead of serial at every layout with slots (measured: scripts/bench_logit_enet.py, profiles/logit_enet.md)
 constexpr int kHuberAutoSlots = 4;         // the same for admm_hip_huber: as many as the layout admits (measured: scripts/bench_huber.py, profiles/huber_loss.md)
 
 __device__ __forceinline__ double soft2(double v, double hi, double lo) {
@@ -97,7 +100,7 @@ __device__ __forceinline__ double huber2(double v, double hi, double lo, double 
 // in the units of the standardised response, +inf = expectile regression) as their LAST argument, behind everything the soft-threshold
 // instantiations (LAD, BP, quantile regression) read: those neither hold nor load it and keep their registers and instruction counts
 // (profiles/huber_loss.md).
-constexpr int kProxSoft = 0, kProxHuber = 1, kProxLogit = 2, kProxLogitS = 3, kProxLogitR = 4;
+constexpr int kProxSoft = 0, kProxHuber = 1, kProxLogit = 2, kProxLogitS = 3, kProxLogitR = 4, kProxLogitE = 5;
 // kProxLogitS (admm_hip_logit_multi): the same loss on the UNFOLDED matrix [X | 1], the label's sign taken inside the prox --
 // prox of log(1 + e^(-s z)) / rho at v is s logit2(s v, t).  Multiplying by +-1 is exact and rounding is symmetric in sign, so every n-vector
 // of this loop is s times the folded loop's and every p-vector, norm and decision equal to it: the matrix no longer depends on the labels.
@@ -105,8 +108,19 @@ constexpr int kProxSoft = 0, kProxHuber = 1, kProxLogit = 2, kProxLogitS = 3, kP
 // vector are 0.0 (the padding logit_sign_matrix_kernel writes anyway), and sign 0 means a square-loss row: the prox of z^2 / (2 rho) at v,
 // z = v (rho / (1 + rho)) -- in this association, rounded operation by operation (tests/logit_ridge_oracle.py replays it).  The rows with
 // sign +-1 run the S form's expressions.
-constexpr bool prox_is_logit(int prox) { return prox == kProxLogit || prox == kProxLogitS || prox == kProxLogitR; }
-constexpr bool prox_is_signed(int prox) { return prox == kProxLogitS || prox == kProxLogitR; }
+// kProxLogitE (admm_hip_logit_enet): kProxLogitS on the matrix with the penalty rows c e_j' appended (c^2 = the number of data rows, for
+// every lambda and alpha: the penalty's constants sit in the prox, not in the row).  A row of sign 0.0 takes the elastic net's prox with
+// the fit's constants c_hi = lambda alpha / c, c_lo = lambda (1 - alpha) / c^2: enet2 below.  The rows with sign +-1 run the S form's
+// expressions (t = 1 / rho whatever c_hi is).
+constexpr bool prox_is_logit(int prox) { return prox == kProxLogit || prox == kProxLogitS || prox == kProxLogitR || prox == kProxLogitE; }
+constexpr bool prox_is_signed(int prox) { return prox == kProxLogitS || prox == kProxLogitR || prox == kProxLogitE; }
+// The prox of (c_hi |z| + c_lo z^2 / 2) / rho at v: t = c_hi / rho, d = 1 + c_lo / rho, z = soft(v, t) / d -- in this association, every
+// operation rounded on its own (tests/logit_enet_oracle.py replays it)
+__device__ __forceinline__ double enet2(double v, double c_hi, double c_lo, double rho) {
+#pragma clang fp contract(off)
+    const double t = c_hi / rho, d = 1.0 + c_lo / rho;
+    return soft2(v, t, t) / d;
+}
 // The prox of g(z) = log(1 + e^-z) / rho (admm_hip_logit: the binomial negative log-likelihood on the sign-folded matrix), t = 1 / rho:
 // the root of h(z) = z - v - t sigma(-z), sigma(-z) = 1 / (1 + e^z), by Newton's iteration.  h is increasing, 1 <= h' <= 1 + t / 4, convex
 // left of zero and concave right of it, the root lies in [v, v + t]; from the start below (v when v > 0, v + t when v + t < 0, else 0)
@@ -339,6 +353,13 @@ struct QuantGrid {
     int* niter; double* rho_fin;              // [ntau] per quantile: iterations (LAD's convention) and final rho
     double* fin; long long fin_ld;            // [ntau][fin_ld] y - adj_y / rho + adj_z of the finished loop: what get_x needs
 };
+// kProxLogitE: the grid with one more per-fit buffer beside `fin` -- the entries [zrow0, zrow0 + zrows) (the penalty rows) of the LAST z
+// of every finished fit, the prox output of its final iteration, which the elastic net returns in place of get_x's dense read-out.
+// Every other kind launches the head with the plain QuantGrid and carries neither the words nor the code.
+struct QuantGridZ : QuantGrid {
+    double* zpen;                             // [ntau][zrows]
+    int zrow0, zrows;
+};
 // slot s: every buffer of slot 0 shifted by s * stride doubles, its pair of control blocks behind slot 0's
 __device__ __forceinline__ DenseParams quant_slot_params(DenseParams q, int s, long long stride) {
     const size_t o = (size_t)s * (size_t)stride;
@@ -358,8 +379,9 @@ __device__ __forceinline__ DenseCtl dense_cold_ctl(double rho, int pad) {
 // which quantile each of them takes next: the unclaimed ones are handed out in slot order.  A finishing slot records its quantile's
 // niter, rho and get_x vector and starts the next quantile cold IN THIS LAUNCH (control block pad = the quantile's index): zero
 // iterates, first = 1, rho = opts.rho.  With no quantile left it goes idle; when all are idle the sticky `done` word is set.
+template <class GRID>
 __global__ void __launch_bounds__(kDenseThreads)
-quant_head_kernel(DenseParams q0, QuantGrid G, int par) {
+quant_head_kernel(DenseParams q0, GRID G, int par) {
     __shared__ double sums[8];
     extern __shared__ __attribute__((aligned(16))) double pstage[];
     const int me = blockIdx.y;
@@ -402,6 +424,14 @@ quant_head_kernel(DenseParams q0, QuantGrid G, int par) {
     const int k = in.pad;
     if (lead) { G.niter[k] = out.niter; G.rho_fin[k] = out.rho; }
     double* fin = G.fin + (size_t)k * G.fin_ld;
+    if constexpr (std::is_same<GRID, QuantGridZ>::value) {
+        // the latest z is the rows launch's of the finished iteration, in the slot the head calls `cur` (in.total is not advanced by a
+        // finishing decision, converged or out of iterations): taken BEFORE the loop below zeroes it for the refill
+        const double* zl = (in.total & 1) ? q.z1 : q.z0;
+        double* zp = G.zpen + (size_t)k * G.zrows;
+        for (int i = blockIdx.x * kDenseThreads + threadIdx.x; i < q.dim; i += gridDim.x * kDenseThreads)      // (the zeroing loop's mapping: a thread zeroes what it has read)
+            if (i >= G.zrow0 && i - G.zrow0 < G.zrows) zp[i - G.zrow0] = zl[i];
+    }
     for (int i = blockIdx.x * kDenseThreads + threadIdx.x; i < q.dim; i += gridDim.x * kDenseThreads) {      // (the mapping of dense_head_vectors: a thread reads what it wrote)
         fin[i] = q.data_vec[i] - q.adj_y[i] / out.rho + q.adj_z[i];                                          // lad_final_vec_kernel
         q.x[i] = 0; q.z0[i] = 0; q.z1[i] = 0; q.y0[i] = 0; q.y1[i] = 0;
@@ -559,6 +589,7 @@ lad_rows_kernel(DenseParams q, int par, const double* __restrict__ Xt, long long
     // formed and dropped.
     // kProxLogitS: the response is identically zero there (x - 0 = x exactly, for every x), so the rows' label signs travel in its place.
     // kProxLogitR: the same, and a row whose sign is 0.0 (a ridge row: the last rows of the matrix) takes the square loss's prox instead.
+    // kProxLogitE: the same with the elastic net's prox on those rows (q.c_hi, q.c_lo: the fit's constants; t of the +-1 rows stays 1 / rho).
     constexpr bool SIGNED = prox_is_signed(PROX);
     __shared__ double uni[2][4 * R];           // d (kProxLogitS: the sign) | adj_y | adj_z | z of the R rows (unreferenced, so not allocated, in the other instantiations)
     auto group_logit = [&](int i0, const double2 (&rv)[R][NPT]) {
@@ -580,9 +611,11 @@ lad_rows_kernel(DenseParams q, int par, const double* __restrict__ Xt, long long
             for (int w = 1; w < NWV; ++w) x += wsum[buf][w][lane];
             if (PROX == kProxLogitR && uni[buf][lane] == 0.0) {
                 zl = (x + uni[buf][R + lane] / rho) * (rho / (1.0 + rho));
+            } else if (PROX == kProxLogitE && uni[buf][lane] == 0.0) {
+                zl = enet2(x + uni[buf][R + lane] / rho, q.c_hi, q.c_lo, rho);
             } else if (SIGNED) {
                 // s logit2(s v, t); the sign is read from LDS again behind the iteration, not held in registers across it
-                const double zs = logit2(uni[buf][lane] * (x + uni[buf][R + lane] / rho), pen_hi);
+                const double zs = logit2(uni[buf][lane] * (x + uni[buf][R + lane] / rho), PROX == kProxLogitE ? 1.0 / rho : pen_hi);
                 asm volatile("" ::: "memory");
                 zl = uni[buf][lane] * zs;
             } else zl = prox2<PROX>(x - uni[buf][lane] + uni[buf][R + lane] / rho, pen_hi, pen_lo, delta);
@@ -654,12 +687,16 @@ quant_rows_kernel(DenseParams q0, long long slot_stride, const double* __restric
     // per-slot entry of uni -- and the Newton prox is formed by lane s R + r of each wave for slot s, row r (see the group below).  The
     // shared response entry goes: the response is identically zero there and x - 0 = x exactly.
     // kProxLogitR (admm_hip_logit_ridge): the same; a prox lane whose row has sign 0.0 forms v (rho / (1 + rho)) with its slot's rho.
+    // kProxLogitE (admm_hip_logit_enet: the slots are cells of a (column, lambda, alpha) grid, cell-major): chi / clo ARE read, by the fit
+    // index c.pad, and the slot's label column is c.pad mod q0.sgn_cols; a prox lane whose row has sign 0.0 forms enet2 with its slot's
+    // constants and rho.
     constexpr bool LOGIT = prox_is_signed(PROX);
     constexpr int NV = LOGIT ? 4 : 3, NB = LOGIT ? 0 : 1;
     constexpr int NU = R * (NB + NV * S);                 // the vectors' entries a row group needs: d | per slot adj_y, adj_z, z   (LOGIT: no d; per slot also the sign)
     static_assert(!LOGIT || S * R <= 64, "one lane per slot and row");
     __shared__ double wsum[2][S][NWV][R];
     __shared__ double uni[2][NU];
+    __shared__ double spen[2][S];                          // kProxLogitE: c_hi | c_lo of the fit the slot holds, for the prox lanes (written below, read behind a group's barrier; unreferenced, so not allocated, in the other instantiations)
     bool act[S];
     int cur[S];
     int col[S];                                            // (LOGIT) the slot's label column
@@ -672,7 +709,11 @@ quant_rows_kernel(DenseParams q0, long long slot_stride, const double* __restric
         cur[s] = (c.total - 1) & 1;
         rho[s] = c.rho;
         const int k = act[s] ? c.pad : 0;                                    // the slot's place in the grid of quantiles
-        if constexpr (LOGIT) { col[s] = k; pen_hi[s] = 0.0; pen_lo[s] = 0.0; }
+        if constexpr (PROX == kProxLogitE) {
+            col[s] = k % q0.sgn_cols; pen_hi[s] = 0.0; pen_lo[s] = 0.0;
+            if ((int)threadIdx.x == s) { spen[0][s] = chi[k]; spen[1][s] = clo[k]; }      // the fit's constants as they are (enet2 divides by its slot's rho), to LDS at once: no slot holds them in registers
+        }
+        else if constexpr (LOGIT) { col[s] = k; pen_hi[s] = 0.0; pen_lo[s] = 0.0; }
         else { pen_hi[s] = chi[k] / rho[s]; pen_lo[s] = clo[k] / rho[s]; }
         delta[s] = PROX == kProxHuber ? dlt[k] : 0.0;                        // the fit's knee travels with its c_hi / c_lo: by the index the head's refill hands over
     }
@@ -741,6 +782,8 @@ quant_rows_kernel(DenseParams q0, long long slot_stride, const double* __restric
                 // as in lad_rows_kernel
                 if (PROX == kProxLogitR && uni[buf][(NB + 3 + NV * ls) * R + lr] == 0.0) {
                     zl = v * (rho_l / (1.0 + rho_l));
+                } else if (PROX == kProxLogitE && uni[buf][(NB + 3 + NV * ls) * R + lr] == 0.0) {
+                    zl = enet2(v, spen[0][ls], spen[1][ls], rho_l);
                 } else {
                     const double zs = logit2(uni[buf][(NB + 3 + NV * ls) * R + lr] * v, 1.0 / rho_l);
                     asm volatile("" ::: "memory");
@@ -818,6 +861,9 @@ dense_tail_kernel(DenseParams q, int par, double knee) {
             if (PROX == kProxLogitR) {
                 const double sg = q.sgn[i], v = x - d + adjy / rho;
                 zn = sg == 0.0 ? v * (rho / (1.0 + rho)) : sg * logit2(sg * v, pen_hi);
+            } else if (PROX == kProxLogitE) {
+                const double sg = q.sgn[i], v = x - d + adjy / rho;
+                zn = sg == 0.0 ? enet2(v, q.c_hi, q.c_lo, rho) : sg * logit2(sg * v, 1.0 / rho);
             } else if (PROX == kProxLogitS) { const double sg = q.sgn[i]; zn = sg * logit2(sg * (x - d + adjy / rho), pen_hi); }
             else zn = prox2<PROX>(x - d + adjy / rho, pen_hi, pen_lo, delta);
             r = x - d - zn;
@@ -915,6 +961,7 @@ struct DenseLoop {
         else if (prox == kProxLogit) hipLaunchKernelGGL(dense_tail_kernel<kProxLogit>, dim3(q.nwg_tail), dim3(kDenseThreads), 0, st, q, (int)(g & 1), 0.0);
         else if (prox == kProxLogitS) hipLaunchKernelGGL(dense_tail_kernel<kProxLogitS>, dim3(q.nwg_tail), dim3(kDenseThreads), 0, st, q, (int)(g & 1), 0.0);
         else if (prox == kProxLogitR) hipLaunchKernelGGL(dense_tail_kernel<kProxLogitR>, dim3(q.nwg_tail), dim3(kDenseThreads), 0, st, q, (int)(g & 1), 0.0);
+        else if (prox == kProxLogitE) hipLaunchKernelGGL(dense_tail_kernel<kProxLogitE>, dim3(q.nwg_tail), dim3(kDenseThreads), 0, st, q, (int)(g & 1), 0.0);
         else hipLaunchKernelGGL(dense_tail_kernel<kProxSoft>, dim3(q.nwg_tail), dim3(kDenseThreads), 0, st, q, (int)(g & 1), 0.0);
     }
     DenseCtl final_ctl(hipStream_t st) {
@@ -955,6 +1002,7 @@ inline int huber_max_slots(int npt) { return npt <= 3 ? 4 : (npt <= 5 ? 2 : 1); 
 
 inline int logit_max_slots(int npt) { return npt <= 3 ? 4 : (npt == 4 ? 2 : 1); }      // the kProxLogitS instantiations without scratch: (4, 3) spills 64 bytes, (5, 2) 24 (profiles/logit_multi.md)
 inline int logit_ridge_max_slots(int npt) { return npt <= 3 ? 4 : (npt == 4 ? 2 : 1); }      // the kProxLogitR instantiations without scratch: the S form's table (profiles/logit_ridge.md)
+inline int logit_enet_max_slots(int npt) { return npt <= 2 ? 4 : (npt == 3 ? 3 : (npt == 4 ? 2 : 1)); }      // the kProxLogitE instantiations without scratch: the R form's table less (3, 4), which spills 16 bytes (profiles/logit_enet.md)
 
 // The separable loss of one fit, as the loop sees it: which prox, its weights above / below zero, and (Huber) the knee in the units
 // of the standardised response.  LAD: the default.
@@ -964,9 +1012,11 @@ struct LadProx {
     const double* signs = nullptr;             // kProxLogit: the n label signs folded into the matrix (device), for the iterate dump
                                                // kProxLogitS: the signs the prox reads -- fit k's is column k of ONE matrix, leading dimension round_up(n, 32)
                                                // kProxLogitR: the same over the augmented rows, 0.0 on the ridge rows
+                                               // kProxLogitE: the same; fit k's column is k mod ncols of the matrix at fits[0].signs, and c_hi / c_lo are the penalty rows' constants
+    int ncols = 0;                             // kProxLogitE: the label columns of the sign matrix
 };
 inline int prox_max_slots(int kind, int npt) {
-    return kind == kProxHuber ? huber_max_slots(npt) : (kind == kProxLogitS ? logit_max_slots(npt) : (kind == kProxLogitR ? logit_ridge_max_slots(npt) : quant_max_slots(npt)));
+    return kind == kProxHuber ? huber_max_slots(npt) : (kind == kProxLogitS ? logit_max_slots(npt) : (kind == kProxLogitR ? logit_ridge_max_slots(npt) : (kind == kProxLogitE ? logit_enet_max_slots(npt) : quant_max_slots(npt))));
 }
 
 // M = G0 + lambda D, D = 1 on the first p0 diagonal entries (the user's columns; the intercept's entry is not shifted): one pass, both
@@ -1127,7 +1177,8 @@ struct LadProblem {
     }
 
     // One loop from a cold start with the prox px; coef: the p coefficients of the standardised problem.  Returns niter.
-    int loop(const LadProx& px, DenseResult& res, double* coef) {
+    // zpen (kProxLogitE): the ridge_p0 penalty-row entries of the last z, the prox output of the final iteration.
+    int loop(const LadProx& px, DenseResult& res, double* coef, double* zpen = nullptr) {
         admm_stats& S = res.stats;
         DenseLoop L;
         L.init(n, 0, opts, d.Y.get(), ynorm, st, res.trace_cap, res.state_cap, onepass ? lad_nwg : 0);
@@ -1137,7 +1188,7 @@ struct LadProblem {
             ADMM_HIP_CHECK(hipMemcpyAsync(L.state.get() + n, &px.delta, sizeof(double), hipMemcpyHostToDevice, st));
             ADMM_HIP_CHECK(hipStreamSynchronize(st));
         }
-        if ((px.kind == kProxLogit || px.kind == kProxLogitR) && res.state_cap > 0)      // the same for the logistic fit: the n signs the loop ran with fill record 0's z slot (ridge rows: 0.0)
+        if ((px.kind == kProxLogit || px.kind == kProxLogitR || px.kind == kProxLogitE) && res.state_cap > 0)      // the same for the logistic fit: the n signs the loop ran with fill record 0's z slot (ridge rows: 0.0)
             ADMM_HIP_CHECK(hipMemcpyAsync(L.state.get() + n, px.signs, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
         if (hat) { L.q.gout = gH.part.get(); L.q.gout_nseg = gH.pl.nseg; L.q.gout_stride = gH.stride; }
         else if (!onepass) { L.q.gout = g3.part.get(); L.q.gout_nseg = g3.pl.nseg; L.q.gout_stride = g3.stride; }
@@ -1157,31 +1208,37 @@ struct LadProblem {
                 case 10: ADMM_LAD_ROWS(1, kProxLogit); break;
                 case 11: ADMM_LAD_ROWS(1, kProxLogitS); break;
                 case 12: ADMM_LAD_ROWS(1, kProxLogitR); break;
+                case 13: ADMM_LAD_ROWS(1, kProxLogitE); break;
                 case 16: ADMM_LAD_ROWS(2, kProxSoft); break;
                 case 17: ADMM_LAD_ROWS(2, kProxHuber); break;
                 case 18: ADMM_LAD_ROWS(2, kProxLogit); break;
                 case 19: ADMM_LAD_ROWS(2, kProxLogitS); break;
                 case 20: ADMM_LAD_ROWS(2, kProxLogitR); break;
+                case 21: ADMM_LAD_ROWS(2, kProxLogitE); break;
                 case 24: ADMM_LAD_ROWS(3, kProxSoft); break;
                 case 25: ADMM_LAD_ROWS(3, kProxHuber); break;
                 case 26: ADMM_LAD_ROWS(3, kProxLogit); break;
                 case 27: ADMM_LAD_ROWS(3, kProxLogitS); break;
                 case 28: ADMM_LAD_ROWS(3, kProxLogitR); break;
+                case 29: ADMM_LAD_ROWS(3, kProxLogitE); break;
                 case 32: ADMM_LAD_ROWS(4, kProxSoft); break;
                 case 33: ADMM_LAD_ROWS(4, kProxHuber); break;
                 case 34: ADMM_LAD_ROWS(4, kProxLogit); break;
                 case 35: ADMM_LAD_ROWS(4, kProxLogitS); break;
                 case 36: ADMM_LAD_ROWS(4, kProxLogitR); break;
+                case 37: ADMM_LAD_ROWS(4, kProxLogitE); break;
                 case 40: ADMM_LAD_ROWS(5, kProxSoft); break;
                 case 41: ADMM_LAD_ROWS(5, kProxHuber); break;
                 case 42: ADMM_LAD_ROWS(5, kProxLogit); break;
                 case 43: ADMM_LAD_ROWS(5, kProxLogitS); break;
                 case 44: ADMM_LAD_ROWS(5, kProxLogitR); break;
+                case 45: ADMM_LAD_ROWS(5, kProxLogitE); break;
                 case 48: ADMM_LAD_ROWS(6, kProxSoft); break;
                 case 49: ADMM_LAD_ROWS(6, kProxHuber); break;
                 case 50: ADMM_LAD_ROWS(6, kProxLogit); break;
                 case 51: ADMM_LAD_ROWS(6, kProxLogitS); break;
                 case 52: ADMM_LAD_ROWS(6, kProxLogitR); break;
+                case 53: ADMM_LAD_ROWS(6, kProxLogitE); break;
                 default: throw Error(ADMM_ERR_INTERNAL, "one-pass loop: no rows kernel for this prox");
             }
 #undef ADMM_LAD_ROWS
@@ -1211,13 +1268,15 @@ struct LadProblem {
         dense_collect_trace(L, fc, res, st);
         hipLaunchKernelGGL(lad_final_vec_kernel, dim3((n + 255) / 256), dim3(256), 0, st, d.Y.get(), L.adj_y.get(), L.adj_z.get(), fc.rho, n, L.vec.get());
         coef_of(L.vec.get(), coef);
+        if (zpen != nullptr)     // get_z() of the finished loop (solve_bp reads it the same way), the penalty rows' part
+            read_back(zpen, ((fc.total & 1) ? L.z1.get() : L.z0.get()) + n0, (size_t)ridge_p0 * sizeof(double), st);
         return fc.niter;
     }
 
     // A grid of quantiles, S >= 2 of them per pass over X (one-pass branch only).  Per iteration: quant_head_kernel for all slots, ONE
     // batched launch of the slots' (X'X)^-1 u products (g2's plan: the partials of the single run), quant_rows_kernel.  The slots refill
     // on the device; the host polls the one `done` word.  fits: the grid, all of one prox kind.  coef: [ntau][p].
-    void loop_slots(int S_, const std::vector<LadProx>& fits, admm_stats& S, int* niter, double* coef) {
+    void loop_slots(int S_, const std::vector<LadProx>& fits, admm_stats& S, int* niter, double* coef, double* zpen = nullptr) {
         const int ntau = (int)fits.size(), nslots = S_;
         const int kind = fits[0].kind;
         std::vector<double> c_hi(ntau), c_lo(ntau), dlt(ntau);
@@ -1252,7 +1311,13 @@ struct LadProblem {
         q.cpart = b + o_c; q.cnwg = lad_nwg; q.cstride = ldp;
         q.c_hi = 1.0; q.c_lo = 1.0;                              // (unused: the slots' constants are chi / clo of their quantile)
         if (prox_is_signed(kind)) q.sgn = fits[0].signs;         // the sign matrix: a slot reads the column of the fit it holds
-        QuantGrid G{};
+        q.sgn_cols = kind == kProxLogitE ? fits[0].ncols : 0;
+        DevBuf<double> zpen_d;
+        QuantGridZ G{};
+        if (kind == kProxLogitE) {
+            zpen_d.alloc((size_t)ntau * ridge_p0); zpen_d.zero(st);
+            G.zpen = zpen_d.get(); G.zrow0 = n0; G.zrows = ridge_p0;
+        }
         G.nslots = nslots; G.ntau = ntau; G.slot_stride = (long long)stride; G.rho0 = opts.rho;
         G.next = ints.get() + 1; G.idle = ints.get() + 3; G.niter = ints.get() + 3 + nslots; G.rho_fin = rho_fin.get();
         G.fin = fin.get(); G.fin_ld = ldn;
@@ -1275,7 +1340,7 @@ struct LadProblem {
         auto launch_rows = [&](int par) {
 #define ADMM_QUANT_ROWS(N, SS, PX) hipLaunchKernelGGL((quant_rows_kernel<N, SS, PX>), dim3(lad_nwg), dim3(kLadThreads), 0, st, q, (long long)stride, chi_d.get(), clo_d.get(), par, \
                                                       Xt.get(), ldxt, spart0, g2.pl.nseg, g2.stride, cpart0, lad_rows, (const double*)dlt_d.get())
-            switch ((kind == kProxHuber ? 100 : (kind == kProxLogitS ? 200 : (kind == kProxLogitR ? 300 : 0))) + lad_npt(ldxt) * 10 + nslots) {
+            switch ((kind == kProxHuber ? 100 : (kind == kProxLogitS ? 200 : (kind == kProxLogitR ? 300 : (kind == kProxLogitE ? 400 : 0)))) + lad_npt(ldxt) * 10 + nslots) {
                 case 12: ADMM_QUANT_ROWS(1, 2, kProxSoft); break;
                 case 13: ADMM_QUANT_ROWS(1, 3, kProxSoft); break;
                 case 14: ADMM_QUANT_ROWS(1, 4, kProxSoft); break;
@@ -1319,6 +1384,15 @@ struct LadProblem {
                 case 333: ADMM_QUANT_ROWS(3, 3, kProxLogitR); break;
                 case 334: ADMM_QUANT_ROWS(3, 4, kProxLogitR); break;
                 case 342: ADMM_QUANT_ROWS(4, 2, kProxLogitR); break;
+                case 412: ADMM_QUANT_ROWS(1, 2, kProxLogitE); break;
+                case 413: ADMM_QUANT_ROWS(1, 3, kProxLogitE); break;
+                case 414: ADMM_QUANT_ROWS(1, 4, kProxLogitE); break;
+                case 422: ADMM_QUANT_ROWS(2, 2, kProxLogitE); break;
+                case 423: ADMM_QUANT_ROWS(2, 3, kProxLogitE); break;
+                case 424: ADMM_QUANT_ROWS(2, 4, kProxLogitE); break;
+                case 432: ADMM_QUANT_ROWS(3, 2, kProxLogitE); break;
+                case 433: ADMM_QUANT_ROWS(3, 3, kProxLogitE); break;
+                case 442: ADMM_QUANT_ROWS(4, 2, kProxLogitE); break;
                 default: throw Error(ADMM_ERR_INTERNAL, "slotted grid: no rows kernel for this layout");
             }
 #undef ADMM_QUANT_ROWS
@@ -1326,7 +1400,8 @@ struct LadProblem {
         const long long bound = (long long)ntau * ((long long)opts.maxit + 2);      // (all quantiles through one slot)
         LoopTimes lt = run_until_done(st, (const int*)ints.get(), batch_iters((int)opt_int(Opt::BATCH_ITERS, 0), 8), bound, [&](long long g) {
             const int par = (int)(g & 1);
-            hipLaunchKernelGGL(quant_head_kernel, dim3(nwg_head, nslots), dim3(kDenseThreads), (size_t)lad_nwg * 8 * sizeof(double), st, q, G, par);
+            if (kind == kProxLogitE) hipLaunchKernelGGL(quant_head_kernel<QuantGridZ>, dim3(nwg_head, nslots), dim3(kDenseThreads), (size_t)lad_nwg * 8 * sizeof(double), st, q, G, par);
+            else hipLaunchKernelGGL(quant_head_kernel<QuantGrid>, dim3(nwg_head, nslots), dim3(kDenseThreads), (size_t)lad_nwg * 8 * sizeof(double), st, q, (QuantGrid)G, par);
             launch_gemv_t_batch<double>(batch.get(), nslots, g2.pl.grid, g2.pl.lds_bytes, g2.pl.nt, st);
             launch_rows(par);
         });
@@ -1339,6 +1414,7 @@ struct LadProblem {
             S.total_iter += niter[k];
             coef_of(fin.get() + (size_t)k * ldn, coef + (size_t)k * p);
         }
+        if (zpen != nullptr) read_back(zpen, zpen_d.get(), (size_t)ntau * ridge_p0 * sizeof(double), st);
         S.rho = hr[ntau - 1];
         S.xupdate_variant = 8 + nslots;
     }
@@ -1416,16 +1492,25 @@ static void run_lad_fits(LadProblem& P, DeviceData<double>& d, int p0, bool inte
     if (P.onepass && dr.trace_cap == 0 && ntau >= 2) {
         const long long want = opt_int(Opt::QUANT_SLOTS, 0);
         const int kind = fits[0].kind;
-        slots = want == 0 ? (kind == kProxHuber ? kHuberAutoSlots : (kind == kProxLogitS ? kLogitAutoSlots : (kind == kProxLogitR ? kLogitRidgeAutoSlots : kQuantAutoSlots))) : (int)want;
+        slots = want == 0 ? (kind == kProxHuber ? kHuberAutoSlots : (kind == kProxLogitS ? kLogitAutoSlots : (kind == kProxLogitR ? kLogitRidgeAutoSlots : (kind == kProxLogitE ? kLogitEnetAutoSlots : kQuantAutoSlots)))) : (int)want;
         slots = std::min(std::min(slots, prox_max_slots(fits[0].kind, lad_npt(P.ldxt))), ntau);
         if ((size_t)ntau * (size_t)n * sizeof(double) > (size_t(2) << 30)) slots = 1;
     }
     std::vector<double> coef((size_t)ntau * p);
     res.niter.assign(ntau, 0);
+    // kProxLogitE: the penalised coefficients are read from the penalty rows of the last z (exact zeros), b_j = z_{n0 + j} / c with c the
+    // rows' scale sqrt(n0); get_x keeps only the intercept's entry
+    const bool enet = fits[0].kind == kProxLogitE;
+    std::vector<double> zpen(enet ? (size_t)ntau * p0 : 0);
     if (slots >= 2) {
-        P.loop_slots(slots, fits, dr.stats, res.niter.data(), coef.data());
+        P.loop_slots(slots, fits, dr.stats, res.niter.data(), coef.data(), enet ? zpen.data() : nullptr);
     } else {
-        for (int k = 0; k < ntau; ++k) res.niter[k] = P.loop(fits[k], dr, coef.data() + (size_t)k * p);
+        for (int k = 0; k < ntau; ++k) res.niter[k] = P.loop(fits[k], dr, coef.data() + (size_t)k * p, enet ? zpen.data() + (size_t)k * p0 : nullptr);
+    }
+    if (enet) {
+        const double c = std::sqrt((double)P.n0);
+        for (int k = 0; k < ntau; ++k)
+            for (int j = 0; j < p0; ++j) coef[(size_t)k * p + j] = zpen[(size_t)k * p0 + j] / c;
     }
     dr.niter = res.niter[0];
     // beta_j = b_j scaleY / scaleX_j;  beta_0 = (meanY - sum beta_j meanX_j) + scaleY b_{p+1}
@@ -1586,6 +1671,89 @@ void solve_logit_ridge(DeviceData<double>& d, bool intercept, const double* y_de
             res.dense.trace = std::move(one.dense.trace); res.dense.state = std::move(one.dense.state); res.dense.state_dim = one.dense.state_dim;
         }
     }
+}
+
+// Elastic-net logistic regression (admm_hip_logit_enet): per label column and cell (lambda, alpha)
+//     sum log(1 + exp(-s_i (b0 + x_i'b))) + lambda (alpha sum |b_j| + (1 - alpha) / 2 sum b_j^2),
+// b on the standardised scale, the intercept not penalised.  solve_logit_ridge's restatement with the penalty's constants moved from
+// the rows into the prox: the p0 penalty rows are c e_j' for EVERY cell, z_{n0 + j} = c b_j, and their loss is
+// (lambda alpha / c) |z| + (lambda (1 - alpha) / c^2) z^2 / 2 (kProxLogitE: c_hi, c_lo).  The Gram matrix of the augmented rows is
+// X'X + c^2 D whatever lambda, alpha and rho are: ONE Gram matrix, ONE inverse (and hat matrix), ONE transpose per call, and every cell
+// of the ncol x ncell grid is one more fit of run_lad_fits -- cell-major, fit cell * ncol + column --, so the slots refill across the
+// whole grid.  c^2 = n0, the squared norm of a standardised column: with unit rows the loop needs hundreds to thousands of iterations,
+// with c = sqrt(n0) 18 - 66 (tests/test_logit_enet_host.py).  Returned: the penalty rows of the last z over c (exact zeros), the
+// intercept from get_x (run_lad_fits).  res.beta: (p + 1) x ncol x ncell, res.niter: ncol x ncell.
+void solve_logit_enet(DeviceData<double>& d, bool intercept, const double* y_dev, int ncol, const double* lambda, const double* alpha, int ncell, const admm_opts& opts,
+                      QuantResult& res, hipStream_t st) {
+    const int n0 = d.n, p0 = d.p;
+    if (intercept) append_ones_column(d, st);
+    append_ridge_rows(d, p0, st);
+    const long long lds = round_up(d.n, 32);
+    DevBuf<double> sgn((size_t)lds * ncol);
+    hipLaunchKernelGGL(logit_sign_matrix_kernel, dim3((unsigned)((lds + 255) / 256), std::min(ncol, 65535)), dim3(256), 0, st, y_dev, n0, ncol, lds, sgn.get());
+    d.scaleY = 1.0; d.meanY = 0.0;
+    const double c2 = (double)n0, c = std::sqrt(c2);
+    std::vector<LadProx> fits((size_t)ncol * ncell);
+    for (int l = 0; l < ncell; ++l)
+        for (int k = 0; k < ncol; ++k) {
+            LadProx& f = fits[(size_t)l * ncol + k];
+            f.kind = kProxLogitE; f.ncols = ncol;
+            f.signs = sgn.get() + (size_t)k * lds;
+            f.c_hi = lambda[l] * alpha[l] / c;
+            f.c_lo = lambda[l] * (1.0 - alpha[l]) / c2;
+        }
+    LadProblem P(d, opts, st);
+    P.setup_ridge(n0, p0, res.dense.stats);
+    P.setup_lambda(c2, res.dense.stats);
+    run_lad_fits(P, d, p0, intercept, fits, res);
+}
+
+// lambda_1 of admm_hip_logit_enet_lambda_max: per label column max_j |x~_j'r|, r = y - mean(y) (mean[c] = 0.5 without the intercept)
+__global__ void __launch_bounds__(256) enet_resid_kernel(const double* __restrict__ y, int n, int ncol, long long ldr, const double* __restrict__ mean, double* __restrict__ r) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= ldr) return;
+    for (int c = blockIdx.y; c < ncol; c += gridDim.y) r[(size_t)c * ldr + i] = i < n ? y[(size_t)c * n + i] - mean[c] : 0.0;
+}
+// block c: the nseg partial rows of product c summed in order, then the largest magnitude over the p outputs
+__global__ void __launch_bounds__(256) enet_lambda_one_kernel(const double* __restrict__ part, long long pstride, int nseg, long long ostride, int p, double* __restrict__ out) {
+    __shared__ double m[256];
+    const double* pc = part + (size_t)blockIdx.x * pstride;
+    double best = 0.0;
+    for (int j = threadIdx.x; j < p; j += 256) {
+        double s = 0.0;
+        for (int g = 0; g < nseg; ++g) s += pc[(size_t)g * ostride + j];
+        best = fmax(best, fabs(s));
+    }
+    m[threadIdx.x] = best;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) m[threadIdx.x] = fmax(m[threadIdx.x], m[threadIdx.x + h]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[blockIdx.x] = m[0];
+}
+// d: the standardised data BEFORE the ones column; mean: ncol host values; out: ncol host values.  One batched gemv_t launch for the
+// ncol right-hand sides (at most 65535 per launch).
+void logit_enet_lambda_one(const DeviceData<double>& d, const double* y_dev, int ncol, const double* mean, double* out, hipStream_t st) {
+    const int n = d.n, p = d.p;
+    const long long ldr = round_up(n, 32);
+    GemvT<double> g;
+    g.init(d.X.get(), d.ldx, n, p);
+    const size_t pstride = (size_t)g.pl.nseg * g.stride;
+    DevBuf<double> r((size_t)ldr * ncol), part(pstride * ncol), mean_d(ncol), out_d(ncol);
+    ADMM_HIP_CHECK(hipMemcpyAsync(mean_d.get(), mean, (size_t)ncol * sizeof(double), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(enet_resid_kernel, dim3((unsigned)((ldr + 255) / 256), std::min(ncol, 65535)), dim3(256), 0, st, y_dev, n, ncol, ldr, mean_d.get(), r.get());
+    std::vector<GemvTArgs<double>> hb(ncol);
+    for (int c = 0; c < ncol; ++c) {
+        hb[c] = g.args_partials(r.get() + (size_t)c * ldr, nullptr);
+        hb[c].out[0] = part.get() + (size_t)c * pstride;
+    }
+    DevBuf<GemvTArgs<double>> batch(ncol);
+    ADMM_HIP_CHECK(hipMemcpyAsync(batch.get(), hb.data(), hb.size() * sizeof(GemvTArgs<double>), hipMemcpyHostToDevice, st));
+    for (int c0 = 0; c0 < ncol; c0 += 65535)
+        launch_gemv_t_batch<double>(batch.get() + c0, std::min(65535, ncol - c0), g.pl.grid, g.pl.lds_bytes, g.pl.nt, st);
+    hipLaunchKernelGGL(enet_lambda_one_kernel, dim3(ncol), dim3(256), 0, st, part.get(), (long long)pstride, g.pl.nseg, g.stride, p, out_d.get());
+    read_back(out, out_d.get(), (size_t)ncol * sizeof(double), st);
 }
 
 __global__ void __launch_bounds__(256) logit_prox_hook_kernel(const double* __restrict__ v, long long m, double t, double* __restrict__ out) {

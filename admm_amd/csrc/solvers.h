@@ -157,6 +157,15 @@ void solve_logit_multi(DeviceData<double>& d, bool intercept, const double* y_de
 // stats, and for one column and one lambda the trace / iterate dump of the augmented loop (n + p rows).
 void solve_logit_ridge(DeviceData<double>& d, bool intercept, const double* y_dev, int ncol, const double* lambda, int nlambda, const admm_opts& opts, QuantResult& res,
                        hipStream_t st);
+// admm_hip_logit_enet (fadmm_dense.hip): the same with the elastic-net penalty lambda (alpha sum |b_j| + (1 - alpha) / 2 sum b_j^2), as p
+// more rows sqrt(n) e_j' whose loss carries the cell's constants (kProxLogitE): ONE Gram matrix, inverse and transpose per call, and the
+// ncol x ncell fits (cell-major) as one grid of run_lad_fits.  The penalised coefficients are read from the penalty rows of the last z
+// (exact zeros), the intercept from get_x.  res.beta: (p + 1) x ncol x ncell, res.niter: ncol x ncell; dense: as solve_logit_ridge.
+void solve_logit_enet(DeviceData<double>& d, bool intercept, const double* y_dev, int ncol, const double* lambda, const double* alpha, int ncell, const admm_opts& opts,
+                      QuantResult& res, hipStream_t st);
+// out[c] = max_j |x_j'(y_c - mean[c])| over the columns of d (standardised, before any ones column); y_dev: n x ncol on the device,
+// mean / out: ncol host values
+void logit_enet_lambda_one(const DeviceData<double>& d, const double* y_dev, int ncol, const double* mean, double* out, hipStream_t st);
 // admm_dantzig (dantzig.hip): the Dantzig selector path in double.  res.beta: (p + 1) x nlambda column-major, row 0 = intercept.
 struct DantzigResult {
     std::vector<double> lambda, beta;

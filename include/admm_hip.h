@@ -337,7 +337,8 @@ ADMM_HIP_API int admm_hip_logit_multi(const double* x, const double* y, int n, i
  * entry l * k + c, maxit + 1 = not converged.  stats->xupdate_variant: 8 + slots on the slotted route, else 1 (one pass) or 0.
  * QUANT_SLOTS = 0 (automatic) takes as many slots as the layout admits (4 to 3072 columns counting the intercept, 2 to 4096, 1 beyond),
  * clipped to k: measured + 31 ... + 60 % over the serial route (profiles/logit_ridge.md).
- * Not offered: an l1 / elastic-net penalty, observation or class weights, softmax, warm starts along the grid, a multi-GPU form. */
+ * An l1 / elastic-net penalty is admm_hip_logit_enet's, below.  Not offered: observation or class weights, softmax, warm starts along
+ * the grid, a multi-GPU form. */
 ADMM_HIP_API int admm_hip_logit_ridge(const double* x, const double* y, int n, int p, int k, int mem, int intercept, const double* lambda, int nlambda,
                          const admm_opts* opts, double* beta_out, int* niter_out, admm_stats* stats);
 /* One label vector and one lambda, with the decision trace and the iterate dump of the AUGMENTED loop: records x | z | y | adj_z | adj_y
@@ -346,6 +347,41 @@ ADMM_HIP_API int admm_hip_logit_ridge(const double* x, const double* y, int n, i
 ADMM_HIP_API int admm_hip_logit_ridge_state(const double* x, const double* y, int n, int p, int mem, int intercept, double lambda, const admm_opts* opts,
                          double* beta_out, int* niter_out, admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out,
                          double* state_out, long long state_cap, long long* nstate_out);
+
+/* Elastic-net (l1 / l1 + l2) logistic regression for k label columns and ncell (lambda, alpha) PAIRS, as admm_hip_huber's (delta, tau)
+ * are pairs.  Per label column c and cell l:
+ *     minimise  sum_i log(1 + exp(-s_i (b0 + x~_i'b))) + lambda_l (alpha_l sum_j |b_j| + (1 - alpha_l) / 2 sum_j b_j^2),   s = 2 y - 1,
+ * x~ the library's standardised columns, b on the standardised scale, the intercept never penalised: glmnet family = "binomial" with
+ * its lambda times n, scikit-learn penalty = "l1" / "elasticnet".  alpha = 1 is the lasso, alpha = 0 admm_hip_logit_ridge's problem.
+ * n >= 2; there is no n > p condition.  The penalty is admm_hip_logit_ridge's p more rows with the penalty's constants moved from the
+ * row into the prox: the rows are sqrt(n) e_j' for EVERY cell (sqrt(n): a standardised column's norm; unit rows cost 10 - 100 times
+ * the iterations) and a row of sign 0 takes z = soft(v, t) / d, t = (lambda alpha / sqrt(n)) / rho, d = 1 + (lambda (1 - alpha) / n) / rho.
+ * So the Gram matrix is X'X + n D for every lambda, alpha and rho: ONE Gram matrix, ONE inverse (and hat matrix, n + p <= 2000) and ONE
+ * transpose per call, and all k * ncell fits run as one grid of the loop -- on the one-pass branch the QUANT_SLOTS slots refill across
+ * the whole grid.  Every fit starts cold, cells in the order given.  Returned: b_j = z_{n + j} / sqrt(n) from the penalty rows of the
+ * LAST z (the prox output of the final iteration: coefficients the penalty removes are exactly 0.0), the intercept from the loop's
+ * coefficient read-out, recovered to the caller's scale as admm_hip_logit_multi does.
+ * y[n * k]: as admm_hip_logit_ridge's, with its refusals; further "lambda and alpha must not be NULL", "lambda must have at least one
+ * value" (ncell < 1), "every lambda must be finite and positive", "every alpha must lie in [0, 1]", "nrow(x) must be at least 2".
+ * A refusal touches no output.
+ * beta_out[(p + 1) * k * ncell]: entry ((l * k + c) * (p + 1) + j), intercept first; niter_out[k * ncell]: entry l * k + c, maxit + 1 =
+ * not converged (the last z is returned all the same).  stats->xupdate_variant: 8 + slots on the slotted route, else 1 (one pass) or 0.
+ * QUANT_SLOTS = 0 (automatic) takes as many slots as the layout admits (4 to 2048 columns counting the intercept, 3 to 3072, 2 to 4096,
+ * 1 beyond), clipped to k * ncell: measured + 33 ... + 57 % over the serial route (profiles/logit_enet.md); 2 ... 8 take up to that many.
+ * lambda = lambda_max exactly (admm_hip_logit_enet_lambda_max over alpha) is degenerate for the loop: ask for the empty model above it.
+ * Not offered: penalty factors, observation or class weights, softmax, warm starts along the grid, strong-rule screening, a multi-GPU form. */
+ADMM_HIP_API int admm_hip_logit_enet(const double* x, const double* y, int n, int p, int k, int mem, int intercept, const double* lambda, const double* alpha,
+                         int ncell, const admm_opts* opts, double* beta_out, int* niter_out, admm_stats* stats);
+/* out[k]: per label column lambda_1 = max_j |x~_j'(y_c - mean(y_c))| with the intercept, max_j |x~_j'(y_c - 1/2)| without it -- one
+ * product with k right-hand sides on the standardised matrix.  For a cell with alpha > 0 the optimum has b = 0 from lambda_1 / alpha on.
+ * The label validation is admm_hip_logit_enet's. */
+ADMM_HIP_API int admm_hip_logit_enet_lambda_max(const double* x, const double* y, int n, int p, int k, int mem, int intercept, double* out);
+/* One label vector and one cell, with the decision trace and the iterate dump of the augmented loop, in the shape of
+ * admm_hip_logit_ridge_state: records of n + p entries, record 0 with the zero response in its x slot and 2 y - 1, then p zeros, in
+ * its z slot. */
+ADMM_HIP_API int admm_hip_logit_enet_state(const double* x, const double* y, int n, int p, int mem, int intercept, double lambda, double alpha,
+                         const admm_opts* opts, double* beta_out, int* niter_out, admm_stats* stats, double* trace_out, long long trace_cap,
+                         long long* ntrace_out, double* state_out, long long state_cap, long long* nstate_out);
 
 /* Prepared-problem variant of the Lasso family (the "persistent context" anticipated for a
  * re-fitting caller; the R shim does not need it).  create = everything the reference does
