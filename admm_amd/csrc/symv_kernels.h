@@ -70,6 +70,18 @@
 //    then IS bound by its instructions.  The format's code bits are therefore laid out so that the four top bytes of a column are formed
 //    byte-wise in one register and every entry is one or two v_perm_b32 (about 420 vector instructions on the path without escapes, 99 VGPRs): within 0.6 us of the floor;
 //  * the floor itself is 2 us under the fp32 stream, not the 2.9 us the byte ratio promises: a chunk is still eight requests per lane.
+// Round 10, a second chunk in flight per wave (profiles/tall_two_chunks.md): the packed kernel's column loop requests chunk q + 1 into a second
+// record buffer before it decodes chunk q (SymvPackedSrc: ping / pong; symv1_tile: the loop unrolled by two).  What made it fit and overlap:
+//  * the requests are buffer loads whose dead lanes (above the diagonal, beyond p - 1 or the last row, no chunk left) carry an offset out of
+//    the descriptor's range -- straight-line code.  With the loads under the per-lane branch they had, the compiler's wait counts cover the
+//    path that skipped them, and the decode of chunk q waited for chunk q + 1 as well (s_waitcnt vmcnt(0) behind the request ahead);
+//  * the wave's number is a scalar (readfirstlane): first column, chunk count and the descriptor are scalars, 128 VGPRs and 8 - 12 bytes of
+//    scratch became 124 and none (4 waves per SIMD).  One chunk deep the same source needs 92 VGPRs (99 before) and runs 5 workgroups per CU.
+// Bare tile loops, p = 10^4, replayed back to back, three builds in one process, medians of 3 x 20 launches, two sessions: parent 31.10 /
+// 30.84 us | two chunks at 4 workgroups per CU (kept) 30.68 / 30.40 | one chunk deep at 5 (ADMM_HIP_SYMV1_DEPTH=1) 30.96 / 30.14; the fp32
+// loop, the same code in all three builds, 30.6 - 31.7.  C2 path: 81.9 - 82.4 ms per step against 82.8 - 83.0 (five alternating pairs).
+// Measured and not kept: the one-deep loop at 5 workgroups per CU (above: the same gain on average, less steady; not run through the
+// path); not built: requesting only the first pieces of chunk q + 1 ahead (two whole chunks fit).
 #pragma once
 #include "admm_internal.h"
 #include "device_utils.h"
@@ -167,37 +179,20 @@ __device__ __forceinline__ T butterfly8(const T (&v)[8], int lane) {
     return r;
 }
 
-// How a tile reads the right-hand vectors.  Plain: ordinary loads (the vectors were written by an earlier launch).
-// Bypass: agent-scope relaxed atomic loads that skip this XCD's L2 -- for vectors written with write-through stores by
-// OTHER workgroups of the SAME launch (the single-launch tall iteration, lasso_tall.hip).
+// How a tile reads the right-hand vectors: ordinary loads (the vectors were written by an earlier launch).
 struct SymvPlainVec {
     __device__ __forceinline__ float4 load4(const float* p) const { return *reinterpret_cast<const float4*>(p); }
     __device__ __forceinline__ float load1(const float* p) const { return *p; }
 };
-struct SymvBypassVec {
-    __device__ __forceinline__ float4 load4(const float* p) const {
-        const unsigned long long lo = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned long long hi = __hip_atomic_load(reinterpret_cast<const unsigned long long*>(p) + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return make_float4(__uint_as_float((unsigned)lo), __uint_as_float((unsigned)(lo >> 32)), __uint_as_float((unsigned)hi), __uint_as_float((unsigned)(hi >> 32)));
-    }
-    __device__ __forceinline__ float load1(const float* p) const {
-        return __uint_as_float(__hip_atomic_load(reinterpret_cast<const unsigned int*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-    }
-};
-struct SymvNoWait { __device__ __forceinline__ void operator()() const {} };
 
-// One tile (kSyRB rows x kSyCB columns, 4 waves) of the symmetric product.  The first 8 matrix columns of every wave are
-// requested BEFORE `wait()` -- they do not depend on the right-hand vectors -- so that a caller whose vectors are still
-// being produced (wait() = poll a flag + barrier) already has its share of the stream in flight.  wait() is called by
-// every thread of the workgroup exactly once.
-// PRE = false (the two-launch path): no wait, right-hand entries first, every 8-column chunk loaded at the top of its loop
-// iteration -- the shape that streams best (with the PRE shape the same 128-column kernel ran at 39.3 instead of 35.1 us on
-// C2: a first chunk carried into the loop in registers and a conditional reload defeat the scheduling of the loads).
+// One tile (kSyRB rows x kSyCB columns, 4 waves) of the symmetric product: right-hand entries first, every 8-column chunk loaded at
+// the top of its loop iteration -- the shape that streams best (a first chunk requested ahead and carried into the loop in registers ran
+// the same 128-column kernel at 39.3 instead of 35.1 us on C2: the carried chunk and a conditional reload defeat the scheduling of the loads).
 // MID: the wave also asks for its copy of the verdict word ahead of every chunk's 8 matrix loads, reads it behind that chunk's wait and
 // leaves the column loop when it says "discard" (SymvVerdict below).  The waves of a workgroup may disagree; every one still runs the
 // epilogue and reaches its barrier, and what a tile that stopped half-way writes is as unread as what it would have written.
-template <bool PRE, typename Wait, typename VecLoad, bool NT = false, bool MID = false>      // NT: matrix read with non-temporal loads (triangle larger than the Infinity Cache)
-__device__ __forceinline__ void symv2_tile(const SymvArgs& a, const int4 t, Wait wait, VecLoad vl,
+template <typename VecLoad, bool NT = false, bool MID = false>      // NT: matrix read with non-temporal loads (triangle larger than the Infinity Cache)
+__device__ __forceinline__ void symv2_tile(const SymvArgs& a, const int4 t, VecLoad vl,
                                            float4 (*red)[kSyThreads], float (*sdot)[kSyCBMax]) {
     const int rb = t.x, seg = t.w;
     const int cw = t.z >> 2;               // columns per wave: a multiple of 8, at most 64
@@ -209,14 +204,6 @@ __device__ __forceinline__ void symv2_tile(const SymvArgs& a, const int4 t, Wait
     const bool has = col0 < a.p;           // every wave of a listed tile has all its columns <= the block's last row
     const float* base = a.A + (size_t)col0 * a.lda + row;
     float4 av[8];
-    if (PRE) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-            av[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (has && active && col0 + k < a.p) av[k] = *reinterpret_cast<const float4*>(base + (size_t)k * a.lda);
-        }
-        wait();
-    }
     float4 aU = make_float4(0.f, 0.f, 0.f, 0.f), aW = aU;
 
     if (has) {
@@ -237,14 +224,12 @@ __device__ __forceinline__ void symv2_tile(const SymvArgs& a, const int4 t, Wait
         for (int q = 0; q < nq; ++q) {
             unsigned long long vq = 0;
             if constexpr (MID) vq = __hip_atomic_load(vword, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (!PRE || q > 0) {
 #pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    const int col = col0 + q * 8 + k;
-                    av[k] = make_float4(0.f, 0.f, 0.f, 0.f);
-                    if constexpr (NT) { if (col <= last) av[k] = load16_nt<float4>(base + (size_t)(q * 8 + k) * a.lda); }
-                    else { if (col <= last) av[k] = *reinterpret_cast<const float4*>(base + (size_t)(q * 8 + k) * a.lda); }
-                }
+            for (int k = 0; k < 8; ++k) {
+                const int col = col0 + q * 8 + k;
+                av[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+                if constexpr (NT) { if (col <= last) av[k] = load16_nt<float4>(base + (size_t)(q * 8 + k) * a.lda); }
+                else { if (col <= last) av[k] = *reinterpret_cast<const float4*>(base + (size_t)(q * 8 + k) * a.lda); }
             }
             if constexpr (MID) {      // the word was requested first, so it is there before the chunk is: no wait of its own.  Wave-uniform (one address), compared as scalars
                 const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)vq), hi = __builtin_amdgcn_readfirstlane((unsigned)(vq >> 32));
@@ -328,7 +313,7 @@ symv2_lower_kernel(SymvArgs a, Extra extra) {
 #ifdef ADMM_HIP_PROBE
     const long long pt0 = wall_clock64();
 #endif
-    symv2_tile<false, SymvNoWait, SymvPlainVec, NT, MID>(a, t, SymvNoWait(), SymvPlainVec(), red, sdot);
+    symv2_tile<SymvPlainVec, NT, MID>(a, t, SymvPlainVec(), red, sdot);
 #ifdef ADMM_HIP_PROBE
     if (a.probe != nullptr && threadIdx.x == 0) {
         const int nt = (int)gridDim.x - 1, t = (int)blockIdx.x - 1;
@@ -353,7 +338,7 @@ symv2_lower_kernel(SymvArgs a, Extra extra) {
 // handling and `last`, so the partials written for pick = r have the bits symv2_lower_kernel writes into plane r -- but they go into
 // plane 0 (dot0, axp0) whichever vector was picked, and symv_sum_partials1 below sums that one plane.
 // PRE: the first chunk's matrix requests are issued before the gate is evaluated (its block sum and barriers then run under loads in
-// flight); that chunk is peeled off the column loop, which keeps the shape that streams best (symv2_tile, PRE = false).
+// flight); that chunk is peeled off the column loop, which keeps the shape that streams best (symv2_tile).
 constexpr int kSyGateLeave = -1;
 // Every tile of a discarded launch counts itself.  1600 atomic adds to ONE word are served one after the other by the memory side (they
 // took 25 us of such a launch, measured; the two-vector kernel's few late leavers never showed it): the tiles spread over kSyEarlySlots
@@ -369,6 +354,9 @@ struct SymvForcedGate {                                   // a fixed answer (tes
 #ifndef ADMM_HIP_SYMV1_WGS
 #define ADMM_HIP_SYMV1_WGS 4                              // workgroups per CU the one-vector kernel is built for (dev builds: 5, 6; "Measured and rejected" above)
 #endif
+#ifndef ADMM_HIP_SYMV1_DEPTH
+#define ADMM_HIP_SYMV1_DEPTH 2                            // chunks a wave of the packed kernel keeps in flight (dev builds: 1 = request, wait, decode; profiles/tall_two_chunks.md)
+#endif
 #ifndef ADMM_HIP_SYMV1_PRE
 #define ADMM_HIP_SYMV1_PRE 8                              // columns of the first chunk requested ahead of the gate (dev builds: 0 = the gate first; "Measured and rejected" above)
 #endif
@@ -379,6 +367,8 @@ struct SymvTileGeom { int row, col0, last, lane, wid, nqw; };      // nqw: chunk
 
 // The fp32 matrix itself: one float4 per column, columns beyond `last` not loaded (zero).
 struct SymvDenseSrc {
+    static constexpr int kDepth = 1;      // chunks a wave keeps in flight (117 VGPRs at one: no room for a second)
+    static __device__ __forceinline__ int wave_id() { return threadIdx.x >> 6; }
     struct Desc {};
     __device__ __forceinline__ Desc describe(int) const { return Desc(); }
     template <bool NT>
@@ -397,6 +387,7 @@ struct SymvDenseSrc {
                 else { if (col <= last) av[k] = *reinterpret_cast<const float4*>(base + (size_t)(q * 8 + k) * lda); }
             }
         }
+        template <int B = 0>
         __device__ __forceinline__ void get(int, float4 (&out)[8]) const {
 #pragma unroll
             for (int k = 0; k < 8; ++k) out[k] = av[k];
@@ -407,6 +398,10 @@ struct SymvDenseSrc {
 // The exact 29-bit copy of the tiles (symv_pack.h; written by symv_pack_kernel below): eight requests per chunk as well, seven of 16 bytes
 // and one of 4, all of them issued with the chunk's first column.  A lane whose chunk lies wholly above the diagonal, beyond column p - 1
 // or beyond the last row requests nothing and gets zeros (d = 14 everywhere), as the fp32 source's `last` does column by column.
+// The requests are buffer loads through a descriptor of the wave's own chunks, and such a lane's offset lies beyond the descriptor's
+// range: the range check drops its part of the request and hands back zeros, so the eight loads of a chunk stand in straight-line code.
+// (Under a per-lane branch the compiler's wait counts have to cover the path that skipped the loads as well, and the decode of one
+// chunk then waits for the chunk requested behind it.)  get() puts the sixteen d = 14 in.
 struct SymvPackedSrc {
     const unsigned* stream;      // chunk c of the plan at stream + c * kSpChunkDwords
     const int4* ptile;           // per tile: first chunk, base, escapes listed, escapes met
@@ -414,40 +409,52 @@ struct SymvPackedSrc {
     int esc_cap;
     using Desc = int4;
     __device__ __forceinline__ Desc describe(int tile) const { return ptile[tile]; }
+    static constexpr int kDepth = ADMM_HIP_SYMV1_DEPTH;       // chunks a wave keeps in flight: 2 x 29 of the 128 VGPRs of 4 waves per SIMD
+    // the wave's number as a scalar: its first column, its chunk count and its place in the tile's row of dot partials then are scalars too
+    static __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
+    static constexpr unsigned kNoRequest = 0x7FFF0000u;       // a byte offset beyond any wave's chunks (8 x 7424 bytes), immediates added
+    struct Rec { uint4 pc[kSpPieces]; unsigned signs; };      // one lane's record of a chunk as it is loaded
     template <bool NT>
     struct Chunk {
-        const unsigned* mine;    // this lane's first piece of its wave's first chunk
+        __amdgpu_buffer_rsrc_t chunks;      // the wave's chunks (wave-uniform: built from scalars)
+        unsigned off16, off4;               // this lane's byte offsets into the 16-byte pieces and into the sign words of a chunk
         const uint2* esc; int nesc, ebase, col0, last, lane, chunk0;
-        uint4 pc[kSpPieces]; unsigned signs;
+        Rec ping, pong;                     // two named buffers: while one is decoded the other's loads are in flight (symv1_tile's column loop)
         __device__ __forceinline__ Chunk(const SymvPackedSrc& s, const Desc& d, const SymvArgs&, const SymvTileGeom& g)
-            : mine(s.stream + ((size_t)d.x + (size_t)(g.wid * g.nqw)) * kSpChunkDwords + g.lane * 4), esc(s.esc + (size_t)(blockIdx.x - 1) * s.esc_cap),
-              nesc(d.z), ebase(d.y), col0(g.col0), last(g.last), lane(g.lane), chunk0(g.wid * g.nqw) {}
-        template <int K0, int K1>
-        __device__ __forceinline__ void request(int q) {
+            : off16(g.lane * 16u), off4((4u * kSpPieces * 64u + g.lane) * 4u), esc(s.esc + (size_t)(blockIdx.x - 1) * s.esc_cap),
+              nesc(d.z), ebase(d.y), col0(g.col0), last(g.last), lane(g.lane), chunk0(g.wid * g.nqw) {
+            const int w = g.wid, first = __builtin_amdgcn_readfirstlane(d.x), nqw = __builtin_amdgcn_readfirstlane(g.nqw);
+            const unsigned* base = s.stream + ((size_t)first + (size_t)(w * nqw)) * kSpChunkDwords;
+            chunks = __builtin_amdgcn_make_buffer_rsrc(const_cast<unsigned*>(base), 0, nqw * kSpChunkBytes, 0x00020000);
+        }
+        template <int B> __device__ __forceinline__ Rec& rec() { if constexpr (B == 0) return ping; else return pong; }
+        template <int B> __device__ __forceinline__ const Rec& rec() const { if constexpr (B == 0) return ping; else return pong; }
+        __device__ __forceinline__ bool requested(int q) const { return col0 + q * 8 <= last; }
+        template <int K0, int K1, int B = 0>
+        __device__ __forceinline__ void request(int q, bool exists = true) {      // exists: q < the wave's chunks (ahead of the last one there is none)
             if constexpr (K0 == 0 && K1 > 0) {
-                const unsigned* c = mine + (size_t)q * kSpChunkDwords;
-                pc[0] = make_uint4(0xEEEEEEEEu, 0xEEEEEEEEu, 0xEEEEEEEEu, 0xEEEEEEEEu);      // d = 14: every entry a zero
+                typedef unsigned int u4_t __attribute__((ext_vector_type(4)));
+                constexpr int aux = NT ? 2 : 0;               // the non-temporal hint of load16_nt
+                Rec& r = rec<B>();
+                const bool on = exists && requested(q);
+                const unsigned at = (unsigned)q * (unsigned)kSpChunkBytes;
+                const unsigned o16 = on ? at + off16 : kNoRequest, o4 = on ? at + off4 : kNoRequest;
 #pragma unroll
-                for (int i = 1; i < kSpPieces; ++i) pc[i] = make_uint4(0u, 0u, 0u, 0u);
-                signs = 0u;
-                if (col0 + q * 8 <= last) {
-                    if constexpr (NT) {
-#pragma unroll
-                        for (int i = 0; i < kSpPieces; ++i) pc[i] = load16_nt<uint4>(c + i * 256);
-                        signs = __builtin_nontemporal_load(c + 4 * kSpPieces * 64 - 3 * lane);
-                    } else {
-#pragma unroll
-                        for (int i = 0; i < kSpPieces; ++i) pc[i] = *reinterpret_cast<const uint4*>(c + i * 256);
-                        signs = c[4 * kSpPieces * 64 - 3 * lane];
-                    }
+                for (int i = 0; i < kSpPieces; ++i) {
+                    const u4_t v = __builtin_amdgcn_raw_buffer_load_b128(chunks, o16 + 1024u * i, 0, aux);
+                    r.pc[i] = make_uint4(v.x, v.y, v.z, v.w);
                 }
+                r.signs = __builtin_amdgcn_raw_buffer_load_b32(chunks, o4, 0, aux);
             }
         }
+        template <int B = 0>
         __device__ __forceinline__ void get(int q, float4 (&out)[8]) const {
+            const Rec& r = rec<B>();
             unsigned rec[kSpRecDwords], bits[kSpEntries];
 #pragma unroll
-            for (int i = 0; i < kSpPieces; ++i) { rec[4 * i] = pc[i].x; rec[4 * i + 1] = pc[i].y; rec[4 * i + 2] = pc[i].z; rec[4 * i + 3] = pc[i].w; }
-            rec[4 * kSpPieces] = signs;
+            for (int i = 0; i < kSpPieces; ++i) { rec[4 * i] = r.pc[i].x; rec[4 * i + 1] = r.pc[i].y; rec[4 * i + 2] = r.pc[i].z; rec[4 * i + 3] = r.pc[i].w; }
+            rec[4 * kSpPieces] = r.signs;
+            if (!requested(q)) { rec[0] = 0xEEEEEEEEu; rec[1] = 0xEEEEEEEEu; rec[2] = 0xEEEEEEEEu; rec[3] = 0xEEEEEEEEu; }      // d = 14: every entry a zero
 #if ADMM_HIP_SYMV_PACK_DEC == 2      // dev build, timing only: the 29 dwords as they come (meaningless products) -- what the stream costs without any decode
 #pragma unroll
             for (int e = 0; e < kSpEntries; ++e) bits[e] = rec[e < kSpRecDwords ? e : e - 4] ^ (unsigned)ebase;
@@ -488,7 +495,7 @@ __device__ __forceinline__ void symv1_tile(const SymvArgs& a, const Src& src, co
     if (done != 0) return;                 // (arrives with the descriptor: checked before the first matrix request, not behind it)
     const int rb = t.x, seg = t.w;
     const int cw = t.z >> 2;               // columns per wave: a multiple of 8, at most 64
-    const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+    const int lane = threadIdx.x & 63, wid = Src::wave_id();
     const int row = rb * kSyRB + lane * 4;
     const int col0 = t.y + wid * cw;
     const int p4 = (a.p + 3) & ~3;
@@ -515,9 +522,9 @@ __device__ __forceinline__ void symv1_tile(const SymvArgs& a, const Src& src, co
         const float4 uI = active ? *reinterpret_cast<const float4*>(v + row) : make_float4(0.f, 0.f, 0.f, 0.f);
         const int cj = col0 + lane;                                          // the wave's (<= 64) right-hand entries, one per lane
         const float uj = (lane < cw && cj < a.p) ? v[cj] : 0.f;
-        const auto consume = [&](int q) {
+        const auto consume = [&](int q, auto buf) {
             float4 av[8];
-            ch.get(q, av);
+            ch.template get<decltype(buf)::value>(q, av);
             float dU[8];
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
@@ -542,11 +549,32 @@ __device__ __forceinline__ void symv1_tile(const SymvArgs& a, const Src& src, co
             const float du = butterfly8(dU, lane);                // every lane ends with column (lane >> 3)
             if ((lane & 7) == 0) sdot[wid * cw + q * 8 + (lane >> 3)] = du;
         };
-        if constexpr (PRE > 0) { ch.template request<PRE, 8>(0); consume(0); }      // the rest of the peeled chunk
+        constexpr std::integral_constant<int, 0> ping;
+        constexpr std::integral_constant<int, 1> pong;
+        if constexpr (Src::kDepth == 2) {
+            // Two chunks in flight per wave: chunk q + 1 is requested into the other buffer before chunk q is decoded, so a wave is never
+            // without an outstanding request while it has columns left.  Unrolled by two by hand over the two named buffers -- no register
+            // moves between them; the request ahead of a wave's last chunk asks for nothing.
+            if constexpr (PRE > 0) ch.template request<PRE, 8, 0>(0); else ch.template request<0, 8, 0>(0);
 #pragma unroll 1
-        for (int q = PRE > 0 ? 1 : 0; q < nq; ++q) {
-            ch.template request<0, 8>(q);
-            consume(q);
+            for (int q = 0; q < nq; q += 2) {             // chunk q is in ping
+                __builtin_amdgcn_sched_barrier(0);
+                ch.template request<0, 8, 1>(q + 1, q + 1 < nq);
+                __builtin_amdgcn_sched_barrier(0);
+                consume(q, ping);
+                if (q + 1 >= nq) break;
+                __builtin_amdgcn_sched_barrier(0);
+                ch.template request<0, 8, 0>(q + 2, q + 2 < nq);
+                __builtin_amdgcn_sched_barrier(0);
+                consume(q + 1, pong);
+            }
+        } else {
+            if constexpr (PRE > 0) { ch.template request<PRE, 8>(0); consume(0, ping); }      // the rest of the peeled chunk
+#pragma unroll 1
+            for (int q = PRE > 0 ? 1 : 0; q < nq; ++q) {
+                ch.template request<0, 8>(q);
+                consume(q, ping);
+            }
         }
     } else {
         for (int c = lane; c < cw; c += 64) sdot[wid * cw + c] = 0.f;
