@@ -77,6 +77,7 @@ EXPORTS = ["admm_hip_lasso", "admm_hip_enet", "admm_hip_parlasso", "admm_hip_lad
            "admm_hip_quantreg", "admm_hip_quantreg_state", "admm_hip_huber", "admm_hip_huber_state",
            "admm_hip_logit", "admm_hip_logit_state", "admm_hip_logit_multi", "admm_hip_logit_ridge", "admm_hip_logit_ridge_state",
            "admm_hip_logit_enet", "admm_hip_logit_enet_lambda_max", "admm_hip_logit_enet_state", "admm_hip_test_logit_prox",
+           "admm_hip_poisson", "admm_hip_poisson_lambda_max", "admm_hip_poisson_state", "admm_hip_test_poisson_prox",
            "admm_hip_mtlasso", "admm_hip_mtlasso_plan_create", "admm_hip_test_symv_multi", "admm_hip_test_tall_early_exits",
            "admm_hip_sgl", "admm_hip_sgl_plan_create", "admm_hip_host_sgl_lambda0",
            "admm_hip_boxenet", "admm_hip_boxenet_plan_create", "admm_hip_host_box_lambda0",
@@ -184,6 +185,14 @@ def load():
     lib.admm_hip_logit_enet_state.restype = ctypes.c_int
     lib.admm_hip_test_logit_prox.argtypes = [_c_double_p, ctypes.c_longlong, ctypes.c_double, _c_double_p]
     lib.admm_hip_test_logit_prox.restype = ctypes.c_int
+    lib.admm_hip_poisson.argtypes = list(lib.admm_hip_logit_enet.argtypes)
+    lib.admm_hip_poisson.restype = ctypes.c_int
+    lib.admm_hip_poisson_lambda_max.argtypes = list(lib.admm_hip_logit_enet_lambda_max.argtypes)
+    lib.admm_hip_poisson_lambda_max.restype = ctypes.c_int
+    lib.admm_hip_poisson_state.argtypes = list(lib.admm_hip_logit_enet_state.argtypes)
+    lib.admm_hip_poisson_state.restype = ctypes.c_int
+    lib.admm_hip_test_poisson_prox.argtypes = [_c_double_p, _c_double_p, ctypes.c_longlong, ctypes.c_double, _c_double_p]
+    lib.admm_hip_test_poisson_prox.restype = ctypes.c_int
     lib.admm_hip_bp_state.argtypes = lib.admm_hip_bp_traced.argtypes + [_c_double_p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]
     lib.admm_hip_bp_state.restype = ctypes.c_int
     lib.admm_hip_dantzig.argtypes = [_DP, _DP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _DP, ctypes.c_int, ctypes.c_int, ctypes.c_double,

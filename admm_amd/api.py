@@ -1059,6 +1059,135 @@ class ADMM_LogitEnetOvR(ADMM_LogitEnet):
         return fit
 
 
+class ADMM_Poisson_fit:
+    def __init__(self, lam, alpha, beta, niter, stats):
+        self.lam = lam              # numeric ncell, in the order given
+        self.alpha = alpha          # numeric ncell: cell l is the pair (lam[l], alpha[l])
+        self.beta = beta            # (p + 1) x k x ncell, intercept first            (fit(trace=True): p + 1)
+        self.niter = niter          # integer k x ncell; maxit + 1: not converged     (fit(trace=True): a scalar)
+        self.stats = stats
+
+    def __repr__(self):
+        shape = " x ".join(str(s) for s in np.shape(self.beta))
+        return (f"ADMM Poisson regression fitting result\n\n$lambda\n{self.lam}\n\n$alpha\n{self.alpha}\n\n$beta\n<{shape}> array\n\n"
+                f"$niter\n{self.niter}")
+
+    def show(self):
+        print(repr(self))
+
+
+class ADMM_Poisson(ADMM_LogitEnet):
+    """Poisson regression with the elastic-net penalty (admm_hip_poisson): per count column c and cell l = (lam[l], alpha[l])
+        minimise  sum_i [exp(eta_i) - Y[i, c] eta_i] + lam[l] (alpha[l] sum_j |b_j| + (1 - alpha[l]) / 2 sum_j b_j^2),   eta_i = b0 + x~_i'b,
+    on the library's standardised columns x~ (glmnet family = "poisson" with its lambda times n), the intercept not penalised, the
+    coefficients returned on the caller's scale with exact zeros.  Y: n counts or an n x k matrix of them, finite and >= 0 (non-integers
+    are accepted), every column with a positive sum.  lam: None, a scalar >= 0 or a vector (0: the plain Poisson GLM, which needs
+    nrow(x) > ncol(x) + intercept); alpha: a scalar in [0, 1] (every cell's) or a vector as long as lam (cells are PAIRS).  lam = None:
+    nlambda values log-spaced from max_c lambda_1(c) / alpha down to lambda_min_ratio times that, as ADMM_LogitEnet builds them.  Every
+    fit starts cold, all of them on one inverse."""
+
+    def __init__(self, x, Y, lam=None, alpha=1.0, intercept=True, nlambda=100, lambda_min_ratio=None, n=None, p=None, k=None):
+        n_, p_ = _shape(x, n, p)
+        if n_ < 2:
+            _stop("nrow(x) must be at least 2")
+        if isinstance(Y, DevicePtr):
+            if k is None:
+                _stop("k is required with a DevicePtr")
+            k_ = int(k)
+        else:
+            Y = np.asarray(Y, dtype=np.float64)
+            if Y.ndim == 1:
+                Y = Y[:, None]
+            if Y.ndim != 2:
+                _stop("Y must be a matrix")
+            Y = np.asfortranarray(Y)
+            k_ = Y.shape[1]
+            if Y.shape[0] != n_:
+                _stop("nrow(x) should be equal to nrow(Y)")
+        if k_ < 1:
+            _stop("y must have at least one column")
+        al = np.asarray(alpha, dtype=np.float64)
+        if al.ndim > 1 or al.size < 1:
+            _stop("alpha must be a scalar or a vector")
+        if not np.all((al >= 0.0) & (al <= 1.0)):
+            _stop("every alpha must lie in [0, 1]")
+        if lam is None:
+            if al.ndim != 0 or not float(al) > 0.0:
+                _stop("the automatic lambda grid needs one alpha > 0 (alpha = 0 has no lambda_max: pass lam)")
+            if int(nlambda) <= 0:
+                _stop("nlambda must be a positive integer")
+            lmr = (0.01 if n_ < p_ else 0.0001) if lambda_min_ratio is None else float(lambda_min_ratio)
+            if lmr <= 0 or lmr >= 1:
+                _stop("lambda_min_ratio must be within (0, 1)")
+            self.lam, self.alpha = None, np.full(int(nlambda), float(al))
+            self.nlambda, self.lambda_min_ratio = int(nlambda), lmr
+        else:
+            lm = np.atleast_1d(np.asarray(lam, dtype=np.float64))
+            if lm.ndim != 1 or lm.size < 1:
+                _stop("lam must hold at least one value")
+            if not (np.all(np.isfinite(lm)) and np.all(lm >= 0)):
+                _stop("every lambda must be finite and non-negative")
+            if np.any(lm == 0) and not n_ > p_ + int(bool(intercept)):
+                _stop("lambda = 0 needs nrow(x) > ncol(x) + intercept")
+            if al.ndim == 1 and al.size != lm.size:
+                _stop("alpha must be a scalar or as long as lam (cells are pairs)")
+            self.lam = np.ascontiguousarray(lm)
+            self.alpha = np.ascontiguousarray(np.broadcast_to(al, lm.shape), dtype=np.float64)
+            self.nlambda, self.lambda_min_ratio = int(lm.size), None
+        if not isinstance(Y, DevicePtr):
+            if not (np.all(np.isfinite(Y)) and np.all(Y >= 0.0)):
+                _stop("every y must be finite and non-negative")
+            if not np.all(Y.sum(axis=0) > 0.0):
+                _stop("every column of y must have a positive sum")
+        self.x, self.y, self.n, self.p, self.k = x, Y, int(n_), int(p_), k_
+        self.maxit = 10000
+        self.eps_abs = 1e-4
+        self.eps_rel = 1e-4
+        self.rho = 1.0
+        self.intercept = bool(intercept)
+
+    def lambda_one(self):
+        """-> (k,) lambda_1 per count column: max_j |x~_j'(y_c - mean(y_c))| (intercept) or |x~_j'(y_c - 1)| (none), on the device.
+        For alpha > 0 the coefficients of column c are all zero from lambda_1[c] / alpha on."""
+        lib = _lib.load()
+        xp, yp, xmem, keep = self._inputs()
+        out = np.zeros(self.k, dtype=np.float64)
+        check(lib.admm_hip_poisson_lambda_max(xp, yp, self.n, self.p, self.k, xmem, int(self.intercept), out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+        return out
+
+    def fit(self, trace=False, state=0):
+        """-> ADMM_Poisson_fit.  trace / state (admm_hip_poisson_state) for one column and one cell only: beta is then the vector p + 1
+        and niter a scalar, and the iterate dump has dimension n + p (the penalty rows behind the data rows); its record 0 carries the
+        zero response in its x slot and [y, -1 ... -1] in its z slot."""
+        lib = _lib.load()
+        xp, yp, xmem, keep = self._inputs()
+        if (trace or state) and (self.k != 1 or self.nlambda != 1):
+            _stop("trace and state are recorded for a single count column and a single cell")
+        lam, alpha = self._cells()
+        ncell = int(lam.size)
+        o = AdmmOpts(self.maxit, self.eps_abs, self.eps_rel, self.rho)
+        beta = np.zeros((self.p + 1) * self.k * ncell, dtype=np.float64)
+        niter = np.zeros(self.k * ncell, dtype=np.int32)
+        stats = AdmmStats()
+        dp = ctypes.POINTER(ctypes.c_double)
+        bp, np_ = beta.ctypes.data_as(dp), niter.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
+        if trace:
+            tr, ntr = _trace_buffers(self.maxit)
+            sbuf, nst = _state_buffers(state, self.n + self.p)
+            check(lib.admm_hip_poisson_state(xp, yp, self.n, self.p, xmem, int(self.intercept), float(lam[0]), float(alpha[0]), ctypes.byref(o), bp, np_,
+                                             ctypes.byref(stats), *_trace_args(tr, ntr), *_state_args(sbuf, nst)))
+            fit = ADMM_Poisson_fit(lam.copy(), alpha.copy(), beta, int(niter[0]), stats.as_dict())
+            fit.trace = tr[:ntr.value].copy()
+            fit.state = sbuf[:nst.value].copy() if state else None
+            return fit
+        check(lib.admm_hip_poisson(xp, yp, self.n, self.p, self.k, xmem, int(self.intercept), lam.ctypes.data_as(dp), alpha.ctypes.data_as(dp), ncell,
+                                   ctypes.byref(o), bp, np_, ctypes.byref(stats)))
+        fit = ADMM_Poisson_fit(lam.copy(), alpha.copy(), beta.reshape((self.p + 1, self.k, ncell), order="F"), niter.reshape((self.k, ncell), order="F"),
+                               stats.as_dict())
+        fit.trace = fit.state = None
+        return fit
+
+
 class LassoPlan:
     """Prepared problem (admm_hip_lasso_plan_*): setup once, run the lambda path repeatedly.
 
@@ -1197,6 +1326,10 @@ def admm_logit_enet(x, Y, lam=None, alpha=1.0, intercept=True, nlambda=100, lamb
 
 def admm_logit_enet_ovr(x, labels, lam=None, alpha=1.0, intercept=True, nlambda=100, lambda_min_ratio=None, **kw):
     return ADMM_LogitEnetOvR(x, labels, lam, alpha, intercept, nlambda, lambda_min_ratio, **kw)
+
+
+def admm_poisson(x, Y, lam=None, alpha=1.0, intercept=True, nlambda=100, lambda_min_ratio=None, **kw):
+    return ADMM_Poisson(x, Y, lam, alpha, intercept, nlambda, lambda_min_ratio, **kw)
 
 
 def admm_bp(x, y, **kw):

@@ -185,6 +185,24 @@ int admm_hip_logit_enet_state(const double* x, const double* y, int n, int p, in
     });
 }
 
+int admm_hip_poisson(const double* x, const double* y, int n, int p, int k, int mem, int intercept, const double* lambda, const double* alpha, int ncell,
+                     const admm_opts* opts, double* beta_out, int* niter_out, admm_stats* stats) {
+    return guarded([&] { poisson(x, y, n, p, k, mem, intercept, lambda, alpha, ncell, opts, DenseOut{beta_out, niter_out, stats}); });
+}
+
+int admm_hip_poisson_lambda_max(const double* x, const double* y, int n, int p, int k, int mem, int intercept, double* out) {
+    return guarded([&] { poisson_lambda_max(x, y, n, p, k, mem, intercept, out); });
+}
+
+int admm_hip_poisson_state(const double* x, const double* y, int n, int p, int mem, int intercept, double lambda, double alpha, const admm_opts* opts,
+                           double* beta_out, int* niter_out, admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out,
+                           double* state_out, long long state_cap, long long* nstate_out) {
+    return guarded([&] {
+        poisson(x, y, n, p, 1, mem, intercept, &lambda, &alpha, 1, opts,
+                DenseOut{beta_out, niter_out, stats, {trace_out, trace_cap, ntrace_out}, {state_out, state_cap, nstate_out}});
+    });
+}
+
 int admm_hip_logit_state(const double* x, const double* y, int n, int p, int mem, int intercept, const admm_opts* opts, double* beta_out, int* niter_out,
                          admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out, double* state_out, long long state_cap,
                          long long* nstate_out) {
@@ -751,6 +769,15 @@ int admm_hip_test_logit_prox(const double* v, long long m, double t, double* out
         ADMM_REQUIRE(v && out && m > 0 && t > 0.0 && std::isfinite(t), "logit prox hook: v and out must not be NULL, m > 0, t positive and finite");
         require_device();
         test_logit_prox(v, m, t, out);
+    });
+}
+
+int admm_hip_test_poisson_prox(const double* v, const double* y, long long m, double t, double* out) {
+    return guarded([&] {
+        ADMM_REQUIRE(v && y && out && m > 0 && t > 0.0 && std::isfinite(t), "poisson prox hook: v, y and out must not be NULL, m > 0, t positive and finite");
+        for (long long i = 0; i < m; ++i) ADMM_REQUIRE(std::isfinite(v[i]) && std::isfinite(y[i]) && y[i] >= 0.0, "poisson prox hook: v finite, y finite and non-negative");
+        require_device();
+        test_poisson_prox(v, y, m, t, out);
     });
 }
 

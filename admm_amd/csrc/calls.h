@@ -74,6 +74,12 @@ void logit_enet(const double* x, const double* y, int n, int p, int k, int mem, 
                 const admm_opts* opts, const DenseOut& out);
 // out[k]: per label column max_j |x~_j'(y_c - mean)| on the standardised columns (lambda_max of a cell is this over its alpha)
 void logit_enet_lambda_max(const double* x, const double* y, int n, int p, int k, int mem, int intercept, double* out);
+// admm_hip_poisson: the same call shape with count columns (finite, >= 0, a positive sum each) and the Poisson likelihood; lambda >= 0
+// (0: the plain GLM, n > p + intercept); trace / state for k = 1 and ncell = 1 only
+void poisson(const double* x, const double* y, int n, int p, int k, int mem, int intercept, const double* lambda, const double* alpha, int ncell,
+             const admm_opts* opts, const DenseOut& out);
+// out[k]: per count column max_j |x~_j'(y_c - mean(y_c))| with the intercept, max_j |x~_j'(y_c - 1)| without it
+void poisson_lambda_max(const double* x, const double* y, int n, int p, int k, int mem, int intercept, double* out);
 void bp(const double* x, const double* y, int n, int p, int mem, const admm_opts* opts, const DenseOut& out);
 // admm_hip_parbp(_traced): over in-process ranks when PAR_DEVICES lists several devices; parbp_dist: this rank's columns of p_total
 void parbp(const double* x, const double* y, int n, int p, int mem, int nthread, const admm_opts* opts, const DenseOut& out);

@@ -514,6 +514,86 @@ void logit_enet_lambda_max(const double* x, const double* y, int n, int p, int k
     for (int c = 0; c < k; ++c) out[c] = lam1[c];
 }
 
+// the count validation of admm_hip_poisson: every entry finite and >= 0 (non-integers pass: quasi-likelihood use), every column with a
+// positive sum.  Host counts are checked here, device counts by one reduction kernel per call, without a copy to the host.
+static void check_count_columns(const double* y, int n, int k, int mem) {
+    long long bad = 0;
+    std::vector<double> sums(k, 0.0);
+    if (mem == ADMM_MEM_HOST) {
+        for (int c = 0; c < k; ++c) {
+            const double* yc = y + (size_t)c * n;
+            for (int i = 0; i < n; ++i) { if (!(yc[i] >= 0.0) || std::isinf(yc[i])) ++bad; else sums[c] += yc[i]; }
+        }
+    } else {
+        require_device();
+        Stream cs;
+        pois_column_stats(y, n, k, &bad, sums.data(), cs.s);
+    }
+    ADMM_REQUIRE(bad == 0, "every y must be finite and non-negative");
+    for (int c = 0; c < k; ++c) ADMM_REQUIRE(sums[c] > 0.0, "every column of y must have a positive sum");
+}
+
+// admm_hip_poisson: logit_enet's call with count columns and the Poisson likelihood (solve_poisson): one fit per (column, cell), all of
+// them on ONE inverse.  lambda = 0 is accepted -- the plain Poisson GLM -- and then needs a design of full column rank by shape.
+void poisson(const double* x, const double* y, int n, int p, int k, int mem, int intercept, const double* lambda, const double* alpha, int ncell,
+             const admm_opts* opts, const DenseOut& out) {
+    const bool icpt = intercept != 0;
+    ADMM_REQUIRE(k >= 1, "y must have at least one column");
+    ADMM_REQUIRE(lambda != nullptr && alpha != nullptr, "lambda and alpha must not be NULL");
+    ADMM_REQUIRE(ncell >= 1, "lambda must have at least one value");
+    bool unpenalised = false;
+    for (int l = 0; l < ncell; ++l) {
+        ADMM_REQUIRE(std::isfinite(lambda[l]) && lambda[l] >= 0.0, "every lambda must be finite and non-negative");
+        unpenalised = unpenalised || lambda[l] == 0.0;
+    }
+    for (int l = 0; l < ncell; ++l) ADMM_REQUIRE(alpha[l] >= 0.0 && alpha[l] <= 1.0, "every alpha must lie in [0, 1]");
+    ADMM_REQUIRE((k == 1 && ncell == 1) || out.trace.cap == 0, "the decision trace is recorded for a single column and a single cell");
+    check_dense(x, y, n, p, mem, opts, n >= 2, "nrow(x) must be at least 2", true, out);
+    ADMM_REQUIRE(!unpenalised || (long long)n > (long long)p + (icpt ? 1 : 0), "lambda = 0 needs nrow(x) > ncol(x) + intercept");
+    check_count_columns(y, n, k, mem);
+    require_device();
+    const double t0 = now_s();
+    Stream st;
+    DeviceData<double> d;
+    upload_standardize<double>(d, x, y, n, p, mem, true, icpt, st.s);      // (the response it standardises, column 0, is replaced by zeros)
+    Resident counts(y, (size_t)n * k, mem);
+    QuantResult res;
+    begin_result(res.dense, d, out.trace);
+    res.dense.state_cap = out.state.cap;
+    solve_poisson(d, icpt, counts.p, k, lambda, alpha, ncell, *opts, res, st.s);
+    std::memcpy(out.beta_out, res.beta.data(), res.beta.size() * sizeof(double));
+    for (size_t c = 0; c < res.niter.size(); ++c) out.niter_out[c] = res.niter[c];
+    store_state(res.dense, out.state);
+    finish_result(res.dense, t0, out.trace, out.stats);
+}
+
+// admm_hip_poisson_lambda_max: lambda_1 per count column on the standardised columns, max_j |x~_j'(y_c - mu)|: mu = mean(y_c) with the
+// intercept (the fitted intercept at b = 0 is log mean(y_c)), mu = 1 without it (eta = 0).  The column means are formed on the device
+// from the resident counts, for host and device input alike.
+void poisson_lambda_max(const double* x, const double* y, int n, int p, int k, int mem, int intercept, double* out) {
+    const bool icpt = intercept != 0;
+    ADMM_REQUIRE(k >= 1, "y must have at least one column");
+    ADMM_REQUIRE(x != nullptr && y != nullptr, "x and y must not be NULL");
+    ADMM_REQUIRE(n > 0 && p > 0, "n and p must be positive");
+    ADMM_REQUIRE(mem == ADMM_MEM_HOST || mem == ADMM_MEM_DEVICE, "mem must be ADMM_MEM_HOST or ADMM_MEM_DEVICE");
+    ADMM_REQUIRE(out != nullptr, "output pointers must not be NULL");
+    ADMM_REQUIRE(n >= 2, "nrow(x) must be at least 2");
+    check_count_columns(y, n, k, mem);
+    require_device();
+    Stream st;
+    DeviceData<double> d;
+    upload_standardize<double>(d, x, y, n, p, mem, true, icpt, st.s);
+    Resident counts(y, (size_t)n * k, mem);
+    std::vector<double> mean(k, 1.0), lam1(k);
+    if (icpt) {
+        long long bad = 0;
+        pois_column_stats(counts.p, n, k, &bad, mean.data(), st.s);
+        for (int c = 0; c < k; ++c) mean[c] /= (double)n;
+    }
+    logit_enet_lambda_one(d, counts.p, k, mean.data(), lam1.data(), st.s);
+    for (int c = 0; c < k; ++c) out[c] = lam1[c];
+}
+
 void bp(const double* x, const double* y, int n, int p, int mem, const admm_opts* opts, const DenseOut& out) {
     run_dense(x, y, n, p, mem, opts, false, false,                                   // BP.cpp:24-27: no standardisation
               p > n, "ncol(x) must be greater than nrow(x)", true, p,                // R/10_admm_bp.R:30-31

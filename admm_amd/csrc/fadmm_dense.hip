@@ -75,6 +75,7 @@ constexpr int kQuantAutoSlots = 1;         // what QUANT_SLOTS=0 picks on the on
 constexpr int kLogitAutoSlots = 4;         // the same for admm_hip_logit_multi: as many as the layout admits (measured: scripts/bench_logit_multi.py, profiles/logit_multi.md)
 constexpr int kLogitRidgeAutoSlots = kLogitAutoSlots;      // the same for admm_hip_logit_ridge: ahead of serial at every layout with slots (measured: scripts/bench_logit_ridge.py, profiles/logit_ridge.md)
 constexpr int kLogitEnetAutoSlots = kLogitAutoSlots;      // the same for admm_hip_logit_enet: ahead of serial at every layout with slots (measured: scripts/bench_logit_enet.py, profiles/logit_enet.md)
+constexpr int kPoissonAutoSlots = kLogitAutoSlots;      // the same for admm_hip_poisson: ahead of serial at every layout with slots (measured: scripts/bench_poisson.py, profiles/poisson.md)
 constexpr int kHuberAutoSlots = 4;         // the same for admm_hip_huber: as many as the layout admits (measured: scripts/bench_huber.py, profiles/huber_loss.md)
 
 __device__ __forceinline__ double soft2(double v, double hi, double lo) {
@@ -100,7 +101,7 @@ __device__ __forceinline__ double huber2(double v, double hi, double lo, double 
 // in the units of the standardised response, +inf = expectile regression) as their LAST argument, behind everything the soft-threshold
 // instantiations (LAD, BP, quantile regression) read: those neither hold nor load it and keep their registers and instruction counts
 // (profiles/huber_loss.md).
-constexpr int kProxSoft = 0, kProxHuber = 1, kProxLogit = 2, kProxLogitS = 3, kProxLogitR = 4, kProxLogitE = 5;
+constexpr int kProxSoft = 0, kProxHuber = 1, kProxLogit = 2, kProxLogitS = 3, kProxLogitR = 4, kProxLogitE = 5, kProxPoisE = 6;
 // kProxLogitS (admm_hip_logit_multi): the same loss on the UNFOLDED matrix [X | 1], the label's sign taken inside the prox --
 // prox of log(1 + e^(-s z)) / rho at v is s logit2(s v, t).  Multiplying by +-1 is exact and rounding is symmetric in sign, so every n-vector
 // of this loop is s times the folded loop's and every p-vector, norm and decision equal to it: the matrix no longer depends on the labels.
@@ -112,8 +113,14 @@ constexpr int kProxSoft = 0, kProxHuber = 1, kProxLogit = 2, kProxLogitS = 3, kP
 // every lambda and alpha: the penalty's constants sit in the prox, not in the row).  A row of sign 0.0 takes the elastic net's prox with
 // the fit's constants c_hi = lambda alpha / c, c_lo = lambda (1 - alpha) / c^2: enet2 below.  The rows with sign +-1 run the S form's
 // expressions (t = 1 / rho whatever c_hi is).
-constexpr bool prox_is_logit(int prox) { return prox == kProxLogit || prox == kProxLogitS || prox == kProxLogitR || prox == kProxLogitE; }
-constexpr bool prox_is_signed(int prox) { return prox == kProxLogitS || prox == kProxLogitR || prox == kProxLogitE; }
+// kProxPoisE (admm_hip_poisson): kProxLogitE's matrix and penalty rows with the Poisson loss e^z - y z on the data rows.  The "sign" matrix
+// carries the row's COUNT y_i >= 0 instead of +-1 and the marker -1.0 on every penalty row and padding entry (counts are refused below
+// zero): an entry >= 0 takes pois2(v, y, 1 / rho) below -- no sign round trip --, a marker row enet2 as the E form calls it.
+// prox_is_logit: the prox is iterative and is formed once per row by the rows kernels' prox lanes; prox_is_signed: the per-row entry
+// of DenseParams::sgn travels in the response's place; prox_is_enet: penalty rows whose constants are the fit's c_hi / c_lo.
+constexpr bool prox_is_logit(int prox) { return prox == kProxLogit || prox == kProxLogitS || prox == kProxLogitR || prox == kProxLogitE || prox == kProxPoisE; }
+constexpr bool prox_is_signed(int prox) { return prox == kProxLogitS || prox == kProxLogitR || prox == kProxLogitE || prox == kProxPoisE; }
+constexpr bool prox_is_enet(int prox) { return prox == kProxLogitE || prox == kProxPoisE; }
 // The prox of (c_hi |z| + c_lo z^2 / 2) / rho at v: t = c_hi / rho, d = 1 + c_lo / rho, z = soft(v, t) / d -- in this association, every
 // operation rounded on its own (tests/logit_enet_oracle.py replays it)
 __device__ __forceinline__ double enet2(double v, double c_hi, double c_lo, double rho) {
@@ -158,6 +165,39 @@ __device__ __forceinline__ double logit2(double v, double t) {
         const double moved = fabs(zn - z);
         z = zn;
         if (moved <= 0x1p-50 * fmax(1.0, fmax(fabs(z), fabs(v)))) break;
+    }
+    return z;
+}
+// The prox of g(z) = (e^z - y z) / rho (admm_hip_poisson: the Poisson negative log-likelihood of the count y >= 0 at the linear predictor
+// z), t = 1 / rho: the root of h(z) = z + t e^z - w, w = v + t y, by Newton's iteration.  h is increasing and convex, h' = 1 + t e^z >= 1,
+// and the root lies at or below w; from a point right of the root Newton descends monotonically, so the start decides what exp sees.
+// w >= t (h(0) <= 0: the root is >= 0): the root is also <= ln(w / t), start min(w, L) with L an upper estimate of ln(w / t); below
+// that (root < 0; ln(w / t) is NOT a bound there -- started from it the iteration begins left of the root) min(w, 0).
+// L: the FLOAT logarithm of the quotient (one hardware instruction; the double logarithm cost every rows kernel about 22 VGPRs, two
+// of them scratch, profiles/poisson.md) plus 2^-18 (1 + ln), above its error; a quotient beyond 2^100 (or overflowed: t tiny) takes
+// (ilogb(w) - ilogb(t) + 1) ln 2, which lies above ln(w / t) by less than 2 ln 2.  With these starts t e^z <= 4 max(w, t) at every
+// evaluation: nothing overflows for any finite v, any y >= 0 and any t > 0.  Every step is clamped to <= w.  A start that rounding
+// puts left of the root all the same takes one step to its right and descends from there (the clamp is w, not the start).  It
+// stops on the step, |z_new - z| <= 2^-50 max(1, |z|, |w|), under a cap of kPoisMaxSteps.  Steps (tests/poisson_oracle.py's prox):
+// 6 - 8 at t <= 1, 11 at 1e3, 17 at 1e6, 30 at 1e12 -- about one per unit of ln t before the quadratic phase.  Every operation is
+// rounded on its own: ONE function of (v, y, t) wherever it is called (tail and rows kernels, test hook).
+constexpr int kPoisMaxSteps = 64;
+__device__ __forceinline__ double pois2(double v, double y, double t) {
+#pragma clang fp contract(off)
+    const double w = v + t * y;
+    double z = fmin(w, 0.0);
+    if (w >= t) {
+        const double q = w / t;                                  // >= 1; +inf where the quotient overflows
+        const double lf = (double)__logf((float)q);
+        z = fmin(w, q < 0x1p100 ? lf + 0x1p-18 * (1.0 + lf) : (double)(ilogb(w) - ilogb(t) + 1) * 0.6931471805599453);
+    }
+    for (int k = 0; k < kPoisMaxSteps; ++k) {
+        const double e = t * exp(z);
+        const double h = z + e - w, d = 1.0 + e;
+        const double zn = fmin(z - h / d, w);
+        const double moved = fabs(zn - z);
+        z = zn;
+        if (moved <= 0x1p-50 * fmax(1.0, fmax(fabs(z), fabs(w)))) break;
     }
     return z;
 }
@@ -590,6 +630,7 @@ lad_rows_kernel(DenseParams q, int par, const double* __restrict__ Xt, long long
     // kProxLogitS: the response is identically zero there (x - 0 = x exactly, for every x), so the rows' label signs travel in its place.
     // kProxLogitR: the same, and a row whose sign is 0.0 (a ridge row: the last rows of the matrix) takes the square loss's prox instead.
     // kProxLogitE: the same with the elastic net's prox on those rows (q.c_hi, q.c_lo: the fit's constants; t of the +-1 rows stays 1 / rho).
+    // kProxPoisE: the rows' counts travel there; a count >= 0 takes the Poisson prox, the marker -1.0 (a penalty row) the elastic net's.
     constexpr bool SIGNED = prox_is_signed(PROX);
     __shared__ double uni[2][4 * R];           // d (kProxLogitS: the sign) | adj_y | adj_z | z of the R rows (unreferenced, so not allocated, in the other instantiations)
     auto group_logit = [&](int i0, const double2 (&rv)[R][NPT]) {
@@ -609,7 +650,11 @@ lad_rows_kernel(DenseParams q, int par, const double* __restrict__ Xt, long long
             double x = wsum[buf][0][lane];
 #pragma unroll
             for (int w = 1; w < NWV; ++w) x += wsum[buf][w][lane];
-            if (PROX == kProxLogitR && uni[buf][lane] == 0.0) {
+            if constexpr (PROX == kProxPoisE) {
+                // the row's count (>= 0: a data row) or the marker -1.0 (a penalty row)
+                const double v = x + uni[buf][R + lane] / rho;
+                zl = uni[buf][lane] < 0.0 ? enet2(v, q.c_hi, q.c_lo, rho) : pois2(v, uni[buf][lane], 1.0 / rho);
+            } else if (PROX == kProxLogitR && uni[buf][lane] == 0.0) {
                 zl = (x + uni[buf][R + lane] / rho) * (rho / (1.0 + rho));
             } else if (PROX == kProxLogitE && uni[buf][lane] == 0.0) {
                 zl = enet2(x + uni[buf][R + lane] / rho, q.c_hi, q.c_lo, rho);
@@ -690,6 +735,8 @@ quant_rows_kernel(DenseParams q0, long long slot_stride, const double* __restric
     // kProxLogitE (admm_hip_logit_enet: the slots are cells of a (column, lambda, alpha) grid, cell-major): chi / clo ARE read, by the fit
     // index c.pad, and the slot's label column is c.pad mod q0.sgn_cols; a prox lane whose row has sign 0.0 forms enet2 with its slot's
     // constants and rho.
+    // kProxPoisE (admm_hip_poisson): kProxLogitE's indexing with the count matrix in the sign matrix's place; a prox lane whose row
+    // carries a count >= 0 forms pois2 with its slot's rho, one whose row carries the marker -1.0 enet2.
     constexpr bool LOGIT = prox_is_signed(PROX);
     constexpr int NV = LOGIT ? 4 : 3, NB = LOGIT ? 0 : 1;
     constexpr int NU = R * (NB + NV * S);                 // the vectors' entries a row group needs: d | per slot adj_y, adj_z, z   (LOGIT: no d; per slot also the sign)
@@ -709,7 +756,7 @@ quant_rows_kernel(DenseParams q0, long long slot_stride, const double* __restric
         cur[s] = (c.total - 1) & 1;
         rho[s] = c.rho;
         const int k = act[s] ? c.pad : 0;                                    // the slot's place in the grid of quantiles
-        if constexpr (PROX == kProxLogitE) {
+        if constexpr (prox_is_enet(PROX)) {
             col[s] = k % q0.sgn_cols; pen_hi[s] = 0.0; pen_lo[s] = 0.0;
             if ((int)threadIdx.x == s) { spen[0][s] = chi[k]; spen[1][s] = clo[k]; }      // the fit's constants as they are (enet2 divides by its slot's rho), to LDS at once: no slot holds them in registers
         }
@@ -780,7 +827,10 @@ quant_rows_kernel(DenseParams q0, long long slot_stride, const double* __restric
                 const double v = x + uni[buf][(NB + NV * ls) * R + lr] / rho_l;
                 // s logit2(s v, t), t = c_hi / rho with c_hi = 1 as the single fit forms it; the sign is read again behind the iteration,
                 // as in lad_rows_kernel
-                if (PROX == kProxLogitR && uni[buf][(NB + 3 + NV * ls) * R + lr] == 0.0) {
+                if constexpr (PROX == kProxPoisE) {
+                    const double cnt = uni[buf][(NB + 3 + NV * ls) * R + lr];
+                    zl = cnt < 0.0 ? enet2(v, spen[0][ls], spen[1][ls], rho_l) : pois2(v, cnt, 1.0 / rho_l);
+                } else if (PROX == kProxLogitR && uni[buf][(NB + 3 + NV * ls) * R + lr] == 0.0) {
                     zl = v * (rho_l / (1.0 + rho_l));
                 } else if (PROX == kProxLogitE && uni[buf][(NB + 3 + NV * ls) * R + lr] == 0.0) {
                     zl = enet2(v, spen[0][ls], spen[1][ls], rho_l);
@@ -858,7 +908,10 @@ dense_tail_kernel(DenseParams q, int par, double knee) {
         if (q.prob == 0) {                        // LAD: x = P_X(vec); z = prox(x - y + adj_y/rho; c_hi/rho, c_lo/rho); r = x - y - z
             x = g;
             const double d = q.data_vec[i];
-            if (PROX == kProxLogitR) {
+            if (PROX == kProxPoisE) {
+                const double cnt = q.sgn[i], v = x - d + adjy / rho;
+                zn = cnt < 0.0 ? enet2(v, q.c_hi, q.c_lo, rho) : pois2(v, cnt, 1.0 / rho);
+            } else if (PROX == kProxLogitR) {
                 const double sg = q.sgn[i], v = x - d + adjy / rho;
                 zn = sg == 0.0 ? v * (rho / (1.0 + rho)) : sg * logit2(sg * v, pen_hi);
             } else if (PROX == kProxLogitE) {
@@ -962,6 +1015,7 @@ struct DenseLoop {
         else if (prox == kProxLogitS) hipLaunchKernelGGL(dense_tail_kernel<kProxLogitS>, dim3(q.nwg_tail), dim3(kDenseThreads), 0, st, q, (int)(g & 1), 0.0);
         else if (prox == kProxLogitR) hipLaunchKernelGGL(dense_tail_kernel<kProxLogitR>, dim3(q.nwg_tail), dim3(kDenseThreads), 0, st, q, (int)(g & 1), 0.0);
         else if (prox == kProxLogitE) hipLaunchKernelGGL(dense_tail_kernel<kProxLogitE>, dim3(q.nwg_tail), dim3(kDenseThreads), 0, st, q, (int)(g & 1), 0.0);
+        else if (prox == kProxPoisE) hipLaunchKernelGGL(dense_tail_kernel<kProxPoisE>, dim3(q.nwg_tail), dim3(kDenseThreads), 0, st, q, (int)(g & 1), 0.0);
         else hipLaunchKernelGGL(dense_tail_kernel<kProxSoft>, dim3(q.nwg_tail), dim3(kDenseThreads), 0, st, q, (int)(g & 1), 0.0);
     }
     DenseCtl final_ctl(hipStream_t st) {
@@ -1002,6 +1056,7 @@ inline int huber_max_slots(int npt) { return npt <= 3 ? 4 : (npt <= 5 ? 2 : 1); 
 
 inline int logit_max_slots(int npt) { return npt <= 3 ? 4 : (npt == 4 ? 2 : 1); }      // the kProxLogitS instantiations without scratch: (4, 3) spills 64 bytes, (5, 2) 24 (profiles/logit_multi.md)
 inline int logit_ridge_max_slots(int npt) { return npt <= 3 ? 4 : (npt == 4 ? 2 : 1); }      // the kProxLogitR instantiations without scratch: the S form's table (profiles/logit_ridge.md)
+inline int pois_max_slots(int npt) { return npt <= 2 ? 4 : (npt == 3 ? 3 : (npt == 4 ? 2 : 1)); }      // the kProxPoisE instantiations without scratch (profiles/poisson.md)
 inline int logit_enet_max_slots(int npt) { return npt <= 2 ? 4 : (npt == 3 ? 3 : (npt == 4 ? 2 : 1)); }      // the kProxLogitE instantiations without scratch: the R form's table less (3, 4), which spills 16 bytes (profiles/logit_enet.md)
 
 // The separable loss of one fit, as the loop sees it: which prox, its weights above / below zero, and (Huber) the knee in the units
@@ -1013,10 +1068,11 @@ struct LadProx {
                                                // kProxLogitS: the signs the prox reads -- fit k's is column k of ONE matrix, leading dimension round_up(n, 32)
                                                // kProxLogitR: the same over the augmented rows, 0.0 on the ridge rows
                                                // kProxLogitE: the same; fit k's column is k mod ncols of the matrix at fits[0].signs, and c_hi / c_lo are the penalty rows' constants
-    int ncols = 0;                             // kProxLogitE: the label columns of the sign matrix
+                                               // kProxPoisE: the E form's layout with the counts in the signs' place, -1.0 on the penalty rows and the padding
+    int ncols = 0;                             // kProxLogitE, kProxPoisE: the label (count) columns of the sign matrix
 };
 inline int prox_max_slots(int kind, int npt) {
-    return kind == kProxHuber ? huber_max_slots(npt) : (kind == kProxLogitS ? logit_max_slots(npt) : (kind == kProxLogitR ? logit_ridge_max_slots(npt) : (kind == kProxLogitE ? logit_enet_max_slots(npt) : quant_max_slots(npt))));
+    return kind == kProxHuber ? huber_max_slots(npt) : (kind == kProxLogitS ? logit_max_slots(npt) : (kind == kProxLogitR ? logit_ridge_max_slots(npt) : (kind == kProxLogitE ? logit_enet_max_slots(npt) : (kind == kProxPoisE ? pois_max_slots(npt) : quant_max_slots(npt)))));
 }
 
 // M = G0 + lambda D, D = 1 on the first p0 diagonal entries (the user's columns; the intercept's entry is not shifted): one pass, both
@@ -1188,7 +1244,7 @@ struct LadProblem {
             ADMM_HIP_CHECK(hipMemcpyAsync(L.state.get() + n, &px.delta, sizeof(double), hipMemcpyHostToDevice, st));
             ADMM_HIP_CHECK(hipStreamSynchronize(st));
         }
-        if ((px.kind == kProxLogit || px.kind == kProxLogitR || px.kind == kProxLogitE) && res.state_cap > 0)      // the same for the logistic fit: the n signs the loop ran with fill record 0's z slot (ridge rows: 0.0)
+        if ((px.kind == kProxLogit || px.kind == kProxLogitR || prox_is_enet(px.kind)) && res.state_cap > 0)      // the same for the logistic fit: the n signs the loop ran with fill record 0's z slot (ridge rows: 0.0; kProxPoisE: the counts, penalty rows -1.0)
             ADMM_HIP_CHECK(hipMemcpyAsync(L.state.get() + n, px.signs, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
         if (hat) { L.q.gout = gH.part.get(); L.q.gout_nseg = gH.pl.nseg; L.q.gout_stride = gH.stride; }
         else if (!onepass) { L.q.gout = g3.part.get(); L.q.gout_nseg = g3.pl.nseg; L.q.gout_stride = g3.stride; }
@@ -1209,36 +1265,42 @@ struct LadProblem {
                 case 11: ADMM_LAD_ROWS(1, kProxLogitS); break;
                 case 12: ADMM_LAD_ROWS(1, kProxLogitR); break;
                 case 13: ADMM_LAD_ROWS(1, kProxLogitE); break;
+                case 14: ADMM_LAD_ROWS(1, kProxPoisE); break;
                 case 16: ADMM_LAD_ROWS(2, kProxSoft); break;
                 case 17: ADMM_LAD_ROWS(2, kProxHuber); break;
                 case 18: ADMM_LAD_ROWS(2, kProxLogit); break;
                 case 19: ADMM_LAD_ROWS(2, kProxLogitS); break;
                 case 20: ADMM_LAD_ROWS(2, kProxLogitR); break;
                 case 21: ADMM_LAD_ROWS(2, kProxLogitE); break;
+                case 22: ADMM_LAD_ROWS(2, kProxPoisE); break;
                 case 24: ADMM_LAD_ROWS(3, kProxSoft); break;
                 case 25: ADMM_LAD_ROWS(3, kProxHuber); break;
                 case 26: ADMM_LAD_ROWS(3, kProxLogit); break;
                 case 27: ADMM_LAD_ROWS(3, kProxLogitS); break;
                 case 28: ADMM_LAD_ROWS(3, kProxLogitR); break;
                 case 29: ADMM_LAD_ROWS(3, kProxLogitE); break;
+                case 30: ADMM_LAD_ROWS(3, kProxPoisE); break;
                 case 32: ADMM_LAD_ROWS(4, kProxSoft); break;
                 case 33: ADMM_LAD_ROWS(4, kProxHuber); break;
                 case 34: ADMM_LAD_ROWS(4, kProxLogit); break;
                 case 35: ADMM_LAD_ROWS(4, kProxLogitS); break;
                 case 36: ADMM_LAD_ROWS(4, kProxLogitR); break;
                 case 37: ADMM_LAD_ROWS(4, kProxLogitE); break;
+                case 38: ADMM_LAD_ROWS(4, kProxPoisE); break;
                 case 40: ADMM_LAD_ROWS(5, kProxSoft); break;
                 case 41: ADMM_LAD_ROWS(5, kProxHuber); break;
                 case 42: ADMM_LAD_ROWS(5, kProxLogit); break;
                 case 43: ADMM_LAD_ROWS(5, kProxLogitS); break;
                 case 44: ADMM_LAD_ROWS(5, kProxLogitR); break;
                 case 45: ADMM_LAD_ROWS(5, kProxLogitE); break;
+                case 46: ADMM_LAD_ROWS(5, kProxPoisE); break;
                 case 48: ADMM_LAD_ROWS(6, kProxSoft); break;
                 case 49: ADMM_LAD_ROWS(6, kProxHuber); break;
                 case 50: ADMM_LAD_ROWS(6, kProxLogit); break;
                 case 51: ADMM_LAD_ROWS(6, kProxLogitS); break;
                 case 52: ADMM_LAD_ROWS(6, kProxLogitR); break;
                 case 53: ADMM_LAD_ROWS(6, kProxLogitE); break;
+                case 54: ADMM_LAD_ROWS(6, kProxPoisE); break;
                 default: throw Error(ADMM_ERR_INTERNAL, "one-pass loop: no rows kernel for this prox");
             }
 #undef ADMM_LAD_ROWS
@@ -1311,10 +1373,10 @@ struct LadProblem {
         q.cpart = b + o_c; q.cnwg = lad_nwg; q.cstride = ldp;
         q.c_hi = 1.0; q.c_lo = 1.0;                              // (unused: the slots' constants are chi / clo of their quantile)
         if (prox_is_signed(kind)) q.sgn = fits[0].signs;         // the sign matrix: a slot reads the column of the fit it holds
-        q.sgn_cols = kind == kProxLogitE ? fits[0].ncols : 0;
+        q.sgn_cols = prox_is_enet(kind) ? fits[0].ncols : 0;
         DevBuf<double> zpen_d;
         QuantGridZ G{};
-        if (kind == kProxLogitE) {
+        if (prox_is_enet(kind)) {
             zpen_d.alloc((size_t)ntau * ridge_p0); zpen_d.zero(st);
             G.zpen = zpen_d.get(); G.zrow0 = n0; G.zrows = ridge_p0;
         }
@@ -1340,7 +1402,7 @@ struct LadProblem {
         auto launch_rows = [&](int par) {
 #define ADMM_QUANT_ROWS(N, SS, PX) hipLaunchKernelGGL((quant_rows_kernel<N, SS, PX>), dim3(lad_nwg), dim3(kLadThreads), 0, st, q, (long long)stride, chi_d.get(), clo_d.get(), par, \
                                                       Xt.get(), ldxt, spart0, g2.pl.nseg, g2.stride, cpart0, lad_rows, (const double*)dlt_d.get())
-            switch ((kind == kProxHuber ? 100 : (kind == kProxLogitS ? 200 : (kind == kProxLogitR ? 300 : (kind == kProxLogitE ? 400 : 0)))) + lad_npt(ldxt) * 10 + nslots) {
+            switch ((kind == kProxHuber ? 100 : (kind == kProxLogitS ? 200 : (kind == kProxLogitR ? 300 : (kind == kProxLogitE ? 400 : (kind == kProxPoisE ? 500 : 0))))) + lad_npt(ldxt) * 10 + nslots) {
                 case 12: ADMM_QUANT_ROWS(1, 2, kProxSoft); break;
                 case 13: ADMM_QUANT_ROWS(1, 3, kProxSoft); break;
                 case 14: ADMM_QUANT_ROWS(1, 4, kProxSoft); break;
@@ -1393,6 +1455,15 @@ struct LadProblem {
                 case 432: ADMM_QUANT_ROWS(3, 2, kProxLogitE); break;
                 case 433: ADMM_QUANT_ROWS(3, 3, kProxLogitE); break;
                 case 442: ADMM_QUANT_ROWS(4, 2, kProxLogitE); break;
+                case 512: ADMM_QUANT_ROWS(1, 2, kProxPoisE); break;
+                case 513: ADMM_QUANT_ROWS(1, 3, kProxPoisE); break;
+                case 514: ADMM_QUANT_ROWS(1, 4, kProxPoisE); break;
+                case 522: ADMM_QUANT_ROWS(2, 2, kProxPoisE); break;
+                case 523: ADMM_QUANT_ROWS(2, 3, kProxPoisE); break;
+                case 524: ADMM_QUANT_ROWS(2, 4, kProxPoisE); break;
+                case 532: ADMM_QUANT_ROWS(3, 2, kProxPoisE); break;
+                case 533: ADMM_QUANT_ROWS(3, 3, kProxPoisE); break;
+                case 542: ADMM_QUANT_ROWS(4, 2, kProxPoisE); break;
                 default: throw Error(ADMM_ERR_INTERNAL, "slotted grid: no rows kernel for this layout");
             }
 #undef ADMM_QUANT_ROWS
@@ -1400,7 +1471,7 @@ struct LadProblem {
         const long long bound = (long long)ntau * ((long long)opts.maxit + 2);      // (all quantiles through one slot)
         LoopTimes lt = run_until_done(st, (const int*)ints.get(), batch_iters((int)opt_int(Opt::BATCH_ITERS, 0), 8), bound, [&](long long g) {
             const int par = (int)(g & 1);
-            if (kind == kProxLogitE) hipLaunchKernelGGL(quant_head_kernel<QuantGridZ>, dim3(nwg_head, nslots), dim3(kDenseThreads), (size_t)lad_nwg * 8 * sizeof(double), st, q, G, par);
+            if (prox_is_enet(kind)) hipLaunchKernelGGL(quant_head_kernel<QuantGridZ>, dim3(nwg_head, nslots), dim3(kDenseThreads), (size_t)lad_nwg * 8 * sizeof(double), st, q, G, par);
             else hipLaunchKernelGGL(quant_head_kernel<QuantGrid>, dim3(nwg_head, nslots), dim3(kDenseThreads), (size_t)lad_nwg * 8 * sizeof(double), st, q, (QuantGrid)G, par);
             launch_gemv_t_batch<double>(batch.get(), nslots, g2.pl.grid, g2.pl.lds_bytes, g2.pl.nt, st);
             launch_rows(par);
@@ -1492,15 +1563,15 @@ static void run_lad_fits(LadProblem& P, DeviceData<double>& d, int p0, bool inte
     if (P.onepass && dr.trace_cap == 0 && ntau >= 2) {
         const long long want = opt_int(Opt::QUANT_SLOTS, 0);
         const int kind = fits[0].kind;
-        slots = want == 0 ? (kind == kProxHuber ? kHuberAutoSlots : (kind == kProxLogitS ? kLogitAutoSlots : (kind == kProxLogitR ? kLogitRidgeAutoSlots : (kind == kProxLogitE ? kLogitEnetAutoSlots : kQuantAutoSlots)))) : (int)want;
+        slots = want == 0 ? (kind == kProxHuber ? kHuberAutoSlots : (kind == kProxLogitS ? kLogitAutoSlots : (kind == kProxLogitR ? kLogitRidgeAutoSlots : (kind == kProxLogitE ? kLogitEnetAutoSlots : (kind == kProxPoisE ? kPoissonAutoSlots : kQuantAutoSlots))))) : (int)want;
         slots = std::min(std::min(slots, prox_max_slots(fits[0].kind, lad_npt(P.ldxt))), ntau);
         if ((size_t)ntau * (size_t)n * sizeof(double) > (size_t(2) << 30)) slots = 1;
     }
     std::vector<double> coef((size_t)ntau * p);
     res.niter.assign(ntau, 0);
-    // kProxLogitE: the penalised coefficients are read from the penalty rows of the last z (exact zeros), b_j = z_{n0 + j} / c with c the
+    // kProxLogitE / kProxPoisE: the penalised coefficients are read from the penalty rows of the last z (exact zeros), b_j = z_{n0 + j} / c with c the
     // rows' scale sqrt(n0); get_x keeps only the intercept's entry
-    const bool enet = fits[0].kind == kProxLogitE;
+    const bool enet = prox_is_enet(fits[0].kind);
     std::vector<double> zpen(enet ? (size_t)ntau * p0 : 0);
     if (slots >= 2) {
         P.loop_slots(slots, fits, dr.stats, res.niter.data(), coef.data(), enet ? zpen.data() : nullptr);
@@ -1754,6 +1825,87 @@ void logit_enet_lambda_one(const DeviceData<double>& d, const double* y_dev, int
         launch_gemv_t_batch<double>(batch.get() + c0, std::min(65535, ncol - c0), g.pl.grid, g.pl.lds_bytes, g.pl.nt, st);
     hipLaunchKernelGGL(enet_lambda_one_kernel, dim3(ncol), dim3(256), 0, st, part.get(), (long long)pstride, g.pl.nseg, g.stride, p, out_d.get());
     read_back(out, out_d.get(), (size_t)ncol * sizeof(double), st);
+}
+
+// ---------------------------------------------------------------------------------------------- Poisson regression
+// block c: column c of the n x ncol counts -- stats[2 c] = the entries that are not finite or lie below zero, stats[2 c + 1] = the
+// column's sum (the waves' sums added in wave order: the same on every run)
+__global__ void __launch_bounds__(256) pois_column_stats_kernel(const double* __restrict__ y, int n, double* __restrict__ stats) {
+    __shared__ double scratch[2 * 4];
+    const double* yc = y + (size_t)blockIdx.x * n;
+    double acc[2] = {0.0, 0.0};
+    for (int i = threadIdx.x; i < n; i += 256) {
+        const double v = yc[i];
+        if (!(v >= 0.0) || isinf(v)) acc[0] += 1.0;
+        else acc[1] += v;
+    }
+    block_sum<double, 2>(acc, scratch);
+    if (threadIdx.x == 0) { stats[2 * blockIdx.x] = acc[0]; stats[2 * blockIdx.x + 1] = acc[1]; }
+}
+// bad: the entries of ALL columns that are not finite or negative; sums: ncol host values (of the valid entries)
+void pois_column_stats(const double* y_dev, int n, int ncol, long long* bad, double* sums, hipStream_t st) {
+    DevBuf<double> s_d((size_t)2 * ncol);
+    std::vector<double> h((size_t)2 * ncol);
+    for (int c0 = 0; c0 < ncol; c0 += 65535) {
+        const int nc = std::min(65535, ncol - c0);
+        hipLaunchKernelGGL(pois_column_stats_kernel, dim3(nc), dim3(256), 0, st, y_dev + (size_t)c0 * n, n, s_d.get() + (size_t)2 * c0);
+    }
+    read_back(h.data(), s_d.get(), h.size() * sizeof(double), st);
+    *bad = 0;
+    for (int c = 0; c < ncol; ++c) { *bad += (long long)h[2 * c]; sums[c] = h[2 * c + 1]; }
+}
+// column c of the n x ncol counts (leading dimension n) with leading dimension lds; the rows behind the n data rows -- the penalty rows
+// and the padding -- carry the marker -1.0 (kProxPoisE)
+__global__ void __launch_bounds__(256) pois_count_matrix_kernel(const double* __restrict__ y, int n, int ncol, long long lds, double* __restrict__ s) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= lds) return;
+    for (int c = blockIdx.y; c < ncol; c += gridDim.y) s[(size_t)c * lds + i] = i < n ? y[(size_t)c * n + i] : -1.0;
+}
+
+// Poisson regression with the elastic-net penalty (admm_hip_poisson): per count column and cell (lambda, alpha)
+//     sum [exp(eta_i) - y_i eta_i] + lambda (alpha sum |b_j| + (1 - alpha) / 2 sum b_j^2),   eta_i = b0 + x_i'b,
+// b on the standardised scale, the intercept not penalised.  solve_logit_enet with another loss on the data rows: the same penalty rows
+// c e_j', c^2 = n0, for every cell, the same constants c_hi = lambda alpha / c, c_lo = lambda (1 - alpha) / c^2 in the prox, ONE Gram
+// matrix X'X + n0 D, inverse and transpose per call, the ncol x ncell fits cell-major as one grid of run_lad_fits, the penalised
+// coefficients from the penalty rows of the last z.  The count matrix stands where the sign matrix stood (kProxPoisE).  lambda = 0: both
+// constants are 0 and a penalty row's prox is the identity -- the plain Poisson GLM on the same inverse.
+void solve_poisson(DeviceData<double>& d, bool intercept, const double* y_dev, int ncol, const double* lambda, const double* alpha, int ncell, const admm_opts& opts,
+                   QuantResult& res, hipStream_t st) {
+    const int n0 = d.n, p0 = d.p;
+    if (intercept) append_ones_column(d, st);
+    append_ridge_rows(d, p0, st);
+    const long long lds = round_up(d.n, 32);
+    DevBuf<double> cnt((size_t)lds * ncol);
+    hipLaunchKernelGGL(pois_count_matrix_kernel, dim3((unsigned)((lds + 255) / 256), std::min(ncol, 65535)), dim3(256), 0, st, y_dev, n0, ncol, lds, cnt.get());
+    d.scaleY = 1.0; d.meanY = 0.0;
+    const double c2 = (double)n0, c = std::sqrt(c2);
+    std::vector<LadProx> fits((size_t)ncol * ncell);
+    for (int l = 0; l < ncell; ++l)
+        for (int k = 0; k < ncol; ++k) {
+            LadProx& f = fits[(size_t)l * ncol + k];
+            f.kind = kProxPoisE; f.ncols = ncol;
+            f.signs = cnt.get() + (size_t)k * lds;
+            f.c_hi = lambda[l] * alpha[l] / c;
+            f.c_lo = lambda[l] * (1.0 - alpha[l]) / c2;
+        }
+    LadProblem P(d, opts, st);
+    P.setup_ridge(n0, p0, res.dense.stats);
+    P.setup_lambda(c2, res.dense.stats);
+    run_lad_fits(P, d, p0, intercept, fits, res);
+}
+
+__global__ void __launch_bounds__(256) pois_prox_hook_kernel(const double* __restrict__ v, const double* __restrict__ y, long long m, double t, double* __restrict__ out) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i < m) out[i] = pois2(v[i], y[i], t);
+}
+// test hook admm_hip_test_poisson_prox: the device prox over arrays (host in, host out)
+void test_poisson_prox(const double* v, const double* y, long long m, double t, double* out) {
+    Stream st;
+    DevBuf<double> dv((size_t)m), dy((size_t)m), dz((size_t)m);
+    ADMM_HIP_CHECK(hipMemcpyAsync(dv.get(), v, (size_t)m * sizeof(double), hipMemcpyHostToDevice, st.s));
+    ADMM_HIP_CHECK(hipMemcpyAsync(dy.get(), y, (size_t)m * sizeof(double), hipMemcpyHostToDevice, st.s));
+    hipLaunchKernelGGL(pois_prox_hook_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st.s, dv.get(), dy.get(), m, t, dz.get());
+    read_back(out, dz.get(), (size_t)m * sizeof(double), st.s);
 }
 
 __global__ void __launch_bounds__(256) logit_prox_hook_kernel(const double* __restrict__ v, long long m, double t, double* __restrict__ out) {

@@ -166,6 +166,14 @@ void solve_logit_enet(DeviceData<double>& d, bool intercept, const double* y_dev
 // out[c] = max_j |x_j'(y_c - mean[c])| over the columns of d (standardised, before any ones column); y_dev: n x ncol on the device,
 // mean / out: ncol host values
 void logit_enet_lambda_one(const DeviceData<double>& d, const double* y_dev, int ncol, const double* mean, double* out, hipStream_t st);
+// admm_hip_poisson (fadmm_dense.hip): solve_logit_enet with the Poisson loss exp(eta) - y eta on the data rows (kProxPoisE): the count
+// matrix stands where the sign matrix stood, -1.0 marking the penalty rows.  y_dev: n x ncol validated counts (finite, >= 0) on the
+// device, leading dimension n.  lambda >= 0 (0: the plain GLM, the caller checks n > p + intercept).  res as solve_logit_enet's.
+void solve_poisson(DeviceData<double>& d, bool intercept, const double* y_dev, int ncol, const double* lambda, const double* alpha, int ncell, const admm_opts& opts,
+                   QuantResult& res, hipStream_t st);
+// one reduction per column of the n x ncol counts on the device: *bad = the entries that are not finite or lie below zero (all columns),
+// sums[c] = column c's sum (ncol host values; the same bits on every run)
+void pois_column_stats(const double* y_dev, int n, int ncol, long long* bad, double* sums, hipStream_t st);
 // admm_dantzig (dantzig.hip): the Dantzig selector path in double.  res.beta: (p + 1) x nlambda column-major, row 0 = intercept.
 struct DantzigResult {
     std::vector<double> lambda, beta;

@@ -49,5 +49,6 @@ void test_cv_fold_system(const double* x, const double* y, int n, int p, const i
 long long tall_last_early_exits();      // lasso_tall.hip
 void tall_last_pack_info(long long* out);      // lasso_tall.hip
 void test_logit_prox(const double* v, long long m, double t, double* out);      // fadmm_dense.hip: the device logit2 over a host array
+void test_poisson_prox(const double* v, const double* y, long long m, double t, double* out);      // fadmm_dense.hip: the device pois2 over host arrays
 
 }  // namespace admm

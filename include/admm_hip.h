@@ -383,6 +383,42 @@ ADMM_HIP_API int admm_hip_logit_enet_state(const double* x, const double* y, int
                          const admm_opts* opts, double* beta_out, int* niter_out, admm_stats* stats, double* trace_out, long long trace_cap,
                          long long* ntrace_out, double* state_out, long long state_cap, long long* nstate_out);
 
+/* Poisson regression (count data) with the elastic-net penalty, for k count columns and ncell (lambda, alpha) PAIRS.  Per count column
+ * c and cell l:
+ *     minimise  sum_i [exp(eta_i) - y_ic eta_i] + lambda_l (alpha_l sum_j |b_j| + (1 - alpha_l) / 2 sum_j b_j^2),   eta_i = b0 + x~_i'b,
+ * x~ the library's standardised columns, b on the standardised scale, the intercept never penalised: glmnet family = "poisson" with its
+ * lambda times n.  lambda = 0 is the plain Poisson GLM (log link).  It is admm_hip_logit_enet's restatement with another loss on the
+ * data rows: p more rows sqrt(n) e_j' for EVERY cell, whose prox is z = soft(v, t) / d, t = (lambda alpha / sqrt(n)) / rho,
+ * d = 1 + (lambda (1 - alpha) / n) / rho, and on a data row the root of z + e^z / rho = v + y / rho (Newton from the right of the root,
+ * within 1e-13 max(1, |v|, y / rho, 1 / rho) of it; nothing overflows for any finite v).  So the Gram matrix is X'X + n D for every
+ * lambda, alpha and rho: ONE Gram matrix, ONE inverse (and hat matrix, n + p <= 2000) and ONE transpose per call, all k * ncell fits one
+ * grid of the loop, every fit from a cold start, cells in the order given.  Returned: b_j = z_{n + j} / sqrt(n) from the penalty rows of
+ * the LAST z (coefficients the penalty removes are exactly 0.0), the intercept from the loop's coefficient read-out, on the caller's
+ * scale, intercept first.
+ * y[n * k]: column-major counts, finite and >= 0; non-integers are accepted (quasi-likelihood use).  Refusals, each touching no output:
+ * the argument checks of admm_hip_logit_enet and "every y must be finite and non-negative", "every column of y must have a positive
+ * sum", "every lambda must be finite and non-negative", "every alpha must lie in [0, 1]", "lambda = 0 needs nrow(x) > ncol(x) +
+ * intercept", "nrow(x) must be at least 2".
+ * beta_out[(p + 1) * k * ncell]: entry ((l * k + c) * (p + 1) + j); niter_out[k * ncell]: entry l * k + c, maxit + 1 = not converged
+ * (the last z is returned all the same).  stats->xupdate_variant: 8 + slots on the slotted route, else 1 (one pass) or 0.
+ * QUANT_SLOTS = 2 ... 8 take up to that many slots on the one-pass branch (4 to 2048 columns counting the intercept, 3 to 3072, 2 to
+ * 4096, 1 beyond), clipped to k * ncell; 0 (automatic) takes as many as the layout admits: measured + 33 ... + 62 % over the serial
+ * route (profiles/poisson.md).
+ * Not offered: an exposure offset, observation weights, penalty factors, negative-binomial or other dispersion models, warm starts
+ * along the grid, strong-rule screening, a multi-GPU form. */
+ADMM_HIP_API int admm_hip_poisson(const double* x, const double* y, int n, int p, int k, int mem, int intercept, const double* lambda, const double* alpha,
+                         int ncell, const admm_opts* opts, double* beta_out, int* niter_out, admm_stats* stats);
+/* out[k]: per count column lambda_1 = max_j |x~_j'(y_c - mean(y_c))| with the intercept, max_j |x~_j'(y_c - 1)| without it (mu = 1 at
+ * eta = 0) -- one product with k right-hand sides on the standardised matrix.  For a cell with alpha > 0 the optimum has b = 0 from
+ * lambda_1 / alpha on.  The count validation is admm_hip_poisson's. */
+ADMM_HIP_API int admm_hip_poisson_lambda_max(const double* x, const double* y, int n, int p, int k, int mem, int intercept, double* out);
+/* One count vector and one cell, with the decision trace and the iterate dump of the augmented loop: records x | z | y | adj_z | adj_y of
+ * n + p entries each; record 0 carries the zero response in its x slot and the counts followed by p entries of -1.0 (the penalty rows'
+ * marker) in its z slot. */
+ADMM_HIP_API int admm_hip_poisson_state(const double* x, const double* y, int n, int p, int mem, int intercept, double lambda, double alpha,
+                         const admm_opts* opts, double* beta_out, int* niter_out, admm_stats* stats, double* trace_out, long long trace_cap,
+                         long long* ntrace_out, double* state_out, long long state_cap, long long* nstate_out);
+
 /* Prepared-problem variant of the Lasso family (the "persistent context" anticipated for a
  * re-fitting caller; the R shim does not need it).  create = everything the reference does
  * before its lambda loop (copy/convert, DataStd, X'y, Gram, Spectra, factorisation:
@@ -821,6 +857,9 @@ ADMM_HIP_API int admm_hip_test_tall_pack_info(long long* info_out);
 /* The device prox of admm_hip_logit alone: out[k] = the root z of z - v[k] - t / (1 + e^z), t = 1 / rho > 0, over HOST arrays of
  * length m, by the device function the tail and rows kernels call. */
 ADMM_HIP_API int admm_hip_test_logit_prox(const double* v, long long m, double t, double* out);
+/* The device prox of admm_hip_poisson's data rows alone: out[k] = the root z of z + t e^z - (v[k] + t y[k]), t = 1 / rho > 0, over HOST
+ * arrays of length m (v finite, y finite and >= 0), by the device function the tail and rows kernels call. */
+ADMM_HIP_API int admm_hip_test_poisson_prox(const double* v, const double* y, long long m, double t, double* out);
 
 /* The one-time matrix-core kernels as the solvers call them (Linalg::cross_prod_lower / tcross_prod_lower,
  * BlasWrapper.h:73-154; LLT, ADMMLassoTall.h:204-205), on HOST matrices (column-major, tight leading dimensions):

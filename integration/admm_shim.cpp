@@ -351,6 +351,61 @@ BEGIN_RCPP
 END_RCPP
 }
 
+// Poisson regression with the elastic-net penalty for the columns of a count matrix and (lambda, alpha) PAIRS (not in the reference;
+// INTEGRATION.md): .Call("admm_poisson", x, Y, lambda, alpha, intercept, opts) -> beta: (p + 1) x (k ncell), column l k + c = (cell l,
+// count column c), intercept first, exact zeros where the penalty removes a coefficient; niter: k ncell.  alpha: as long as lambda, or
+// one value for every lambda.  lambda is on the standardised scale (glmnet's lambda times nrow(x)); 0 is the plain GLM.
+RcppExport SEXP admm_poisson(SEXP x_, SEXP y_, SEXP lambda_, SEXP alpha_, SEXP intercept_, SEXP opts_) {
+BEGIN_RCPP
+    NumericMatrix x(x_);
+    NumericMatrix y(y_);
+    NumericVector lambda(lambda_);
+    NumericVector alpha_in(alpha_);
+    if (y.nrow() != x.nrow()) Rcpp::stop("nrow(x) should be equal to nrow(Y)");
+    const int ncell = lambda.size();
+    if (alpha_in.size() != ncell && alpha_in.size() != 1) Rcpp::stop("alpha must have one value or as many as lambda");
+    NumericVector alpha(ncell);
+    for (int l = 0; l < ncell; ++l) alpha[l] = alpha_in[alpha_in.size() == 1 ? 0 : l];
+    admm_opts o = unpack_opts(opts_);
+    NumericMatrix beta(x.ncol() + 1, y.ncol() * ncell);
+    IntegerVector niter(y.ncol() * ncell);
+    check(admm_hip_poisson(x.begin(), y.begin(), x.nrow(), x.ncol(), y.ncol(), ADMM_MEM_HOST, as<bool>(intercept_), lambda.begin(), alpha.begin(), ncell, &o,
+                           beta.begin(), niter.begin(), nullptr));
+    return List::create(Named("beta") = beta, Named("niter") = niter, Named("lambda") = lambda, Named("alpha") = alpha);
+END_RCPP
+}
+
+// lambda_1 per count column: .Call("admm_poisson_lambda_max", x, Y, intercept) -> numeric k; a cell's lambda_max is this over its alpha
+RcppExport SEXP admm_poisson_lambda_max(SEXP x_, SEXP y_, SEXP intercept_) {
+BEGIN_RCPP
+    NumericMatrix x(x_);
+    NumericMatrix y(y_);
+    if (y.nrow() != x.nrow()) Rcpp::stop("nrow(x) should be equal to nrow(Y)");
+    NumericVector out(y.ncol());
+    check(admm_hip_poisson_lambda_max(x.begin(), y.begin(), x.nrow(), x.ncol(), y.ncol(), ADMM_MEM_HOST, as<bool>(intercept_), out.begin()));
+    return out;
+END_RCPP
+}
+
+// One count vector and one cell with the decision trace (ADMM_TRACE_FIELDS doubles per record, at most maxit + 2 records):
+// .Call("admm_poisson_state", x, y, lambda, alpha, intercept, opts) -> beta (p + 1), niter, trace (ADMM_TRACE_FIELDS x records)
+RcppExport SEXP admm_poisson_state(SEXP x_, SEXP y_, SEXP lambda_, SEXP alpha_, SEXP intercept_, SEXP opts_) {
+BEGIN_RCPP
+    NumericMatrix x(x_);
+    NumericVector y(y_);
+    if (y.size() != x.nrow()) Rcpp::stop("nrow(x) should be equal to length(y)");
+    admm_opts o = unpack_opts(opts_);
+    NumericVector beta(x.ncol() + 1);
+    int niter = 0;
+    const long long cap = (long long)o.maxit + 2;
+    NumericMatrix trace(ADMM_TRACE_FIELDS, (int)cap);
+    long long ntrace = 0;
+    check(admm_hip_poisson_state(x.begin(), y.begin(), x.nrow(), x.ncol(), ADMM_MEM_HOST, as<bool>(intercept_), as<double>(lambda_), as<double>(alpha_), &o,
+                                 beta.begin(), &niter, nullptr, trace.begin(), cap, &ntrace, nullptr, 0, nullptr));
+    return List::create(Named("beta") = beta, Named("niter") = niter, Named("trace") = trace, Named("ntrace") = (double)ntrace);
+END_RCPP
+}
+
 // The symbol R/50_admm_dantzig.R:38 asks for and the reference never builds (src/TODO/Dantzig.cpp:32-99): doubles throughout.
 RcppExport SEXP admm_dantzig(SEXP x_, SEXP y_, SEXP lambda_, SEXP nlambda_, SEXP lmin_ratio_, SEXP standardize_, SEXP intercept_, SEXP opts_) {
 BEGIN_RCPP
