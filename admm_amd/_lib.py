@@ -85,7 +85,7 @@ EXPORTS = ["admm_hip_lasso", "admm_hip_enet", "admm_hip_parlasso", "admm_hip_lad
            "admm_hip_test_symv_plan", "admm_hip_test_symv_ex", "admm_hip_test_symv_multi_ex", "admm_hip_test_symv_f64acc",
            "admm_hip_test_symv_one", "admm_hip_test_symv_pack_host", "admm_hip_test_symv_packed", "admm_hip_test_symv_packed_time",
            "admm_hip_test_tall_pack_info", "admm_hip_test_gemv_t_ex", "admm_hip_test_wide_op", "admm_hip_test_block_sprad",
-           "admm_hip_test_wide_screen_prep", "admm_hip_test_sbp_screen_prep"]
+           "admm_hip_test_wide_screen_prep", "admm_hip_test_sbp_screen_prep", "admm_hip_test_tall_gate", "admm_hip_test_tall_norms"]
 
 GROUP_MAX = 1024          # ADMM_HIP_GROUP_MAX
 MT_MAX = 16               # ADMM_HIP_MT_MAX
@@ -316,6 +316,10 @@ def load():
     lib.admm_hip_test_symv_f64acc.restype = ctypes.c_int
     lib.admm_hip_test_tall_early_exits.argtypes = [ctypes.POINTER(ctypes.c_longlong)]
     lib.admm_hip_test_tall_early_exits.restype = ctypes.c_int
+    lib.admm_hip_test_tall_gate.argtypes = [_c_double_p, _c_int_p, _c_double_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_double_p, _c_int_p]
+    lib.admm_hip_test_tall_gate.restype = ctypes.c_int
+    lib.admm_hip_test_tall_norms.argtypes = [_c_double_p, ctypes.c_int, _c_double_p]
+    lib.admm_hip_test_tall_norms.restype = ctypes.c_int
     lib.admm_hip_test_gram.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
     lib.admm_hip_test_gram.restype = ctypes.c_int
     lib.admm_hip_test_gemv_t.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_void_p]

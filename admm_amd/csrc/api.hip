@@ -764,6 +764,24 @@ int admm_hip_test_tall_pack_info(long long* info_out) {
     });
 }
 
+int admm_hip_test_tall_gate(const double* ctl_d, const int* ctl_i, const double* compact, int nwg, int maxit, int nlam, double* sums_out, int* answer_out) {
+    return guarded([&] {
+        ADMM_REQUIRE(ctl_d && ctl_i && compact && sums_out && answer_out, "tall_gate hook: no argument may be NULL");
+        ADMM_REQUIRE(nwg >= 1 && nwg <= kTallGateHookMaxNwg && maxit >= 1 && nlam >= 1, "tall_gate hook: nwg in 1 .. 65536, maxit and nlam >= 1");
+        require_device();
+        test_tall_gate(ctl_d, ctl_i, compact, nwg, maxit, nlam, sums_out, answer_out);
+    });
+}
+
+int admm_hip_test_tall_norms(const double* rows, int nwg, double* sums_out) {
+    return guarded([&] {
+        ADMM_REQUIRE(rows && sums_out, "tall_norms hook: rows and sums_out must not be NULL");
+        ADMM_REQUIRE(nwg >= 1 && nwg <= kTallGateHookMaxNwg, "tall_norms hook: nwg in 1 .. 65536");
+        require_device();
+        test_tall_norms(rows, nwg, sums_out);
+    });
+}
+
 int admm_hip_test_logit_prox(const double* v, long long m, double t, double* out) {
     return guarded([&] {
         ADMM_REQUIRE(v && out && m > 0 && t > 0.0 && std::isfinite(t), "logit prox hook: v and out must not be NULL, m > 0, t positive and finite");

@@ -157,15 +157,20 @@ struct TallOutcome {
 // tall_norms_sum adds them in the loop's order and continues the loop.  NK: the first NK of the 6 columns (a tile needs r^2, dz^2, daz^2;
 // the columns are summed independently, so NK = 3 returns the bits NK = 6 returns for them).
 // (rs, cs): strides of a workgroup's row and of a column in Pin -- (8, 1) for the rows of P, (1, nwg) for the compact copy.
+// Round 11: the requests are branch-free -- a thread without a row asks for the last row instead (nwg >= 1: always a valid address) and
+// tall_norms_sum adds +0.0 in its place -- and nothing in tall_norms_request USES what it loads.  (Guarded by `w < nwg` on both sides,
+// the load and its add were merged into one predicated block per column, the add -- and a wait for the load -- directly behind each
+// request: three serialised round trips at the head of every tile.)  The bits are the guarded form's: a skipped add left acc = +0.0
+// (first row) or 0.0 + v, which is never -0.0 (second row), and x + (+0.0) is x for either.
 template <int NK> struct TallNormReq { double v[2][NK]; };
 template <int NK, bool IN_LAUNCH>
 __device__ __forceinline__ TallNormReq<NK> tall_norms_request(const double* Pin, int nwg, int rs, int cs) {
     TallNormReq<NK> r;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-        const int w = threadIdx.x + j * kTailThreads;
+        const int w = min((int)threadIdx.x + j * kTailThreads, nwg - 1);
 #pragma unroll
-        for (int k = 0; k < NK; ++k) r.v[j][k] = w < nwg ? tall_load_partial(Pin + (size_t)w * rs + (size_t)k * cs, IN_LAUNCH) : 0.0;
+        for (int k = 0; k < NK; ++k) r.v[j][k] = tall_load_partial(Pin + (size_t)w * rs + (size_t)k * cs, IN_LAUNCH);
     }
     return r;
 }
@@ -175,10 +180,9 @@ __device__ __forceinline__ void tall_norms_sum(const TallNormReq<NK>& r, const d
     for (int k = 0; k < NK; ++k) acc[k] = 0;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
-        if ((int)threadIdx.x + j * kTailThreads < nwg) {
+        const bool live = (int)threadIdx.x + j * kTailThreads < nwg;
 #pragma unroll
-            for (int k = 0; k < NK; ++k) acc[k] += r.v[j][k];
-        }
+        for (int k = 0; k < NK; ++k) acc[k] += live ? r.v[j][k] : 0.0;
     }
     for (int w = threadIdx.x + 2 * kTailThreads; w < nwg; w += kTailThreads) {
 #pragma unroll
@@ -215,16 +219,20 @@ struct TallGate {
     const double* Pin;        // the compact copy of P[par]: [kGateCols][nwg], the numbers block 0 reads from the rows of P[par]
     int nwg, maxit, nlam;
     struct Req { TallCtl in; TallNormReq<kGateCols> n; };
+    __device__ __forceinline__ void pin() const { asm volatile("" :: "s"(ctl), "s"(Pin), "s"(nwg), "s"(maxit), "s"(nlam)); }
     __device__ __forceinline__ Req request() const {
         Req r;
         r.in = *ctl;
         r.n = tall_norms_request<kGateCols, false>(Pin, nwg, 1, nwg);
         return r;
     }
+    __device__ __forceinline__ void sums(const Req& r, double* lds, double (&acc)[kGateCols]) const {
+        tall_norms_sum<kGateCols, false>(r.n, Pin, nwg, 1, nwg, acc, lds);
+    }
     __device__ __forceinline__ int decide(const Req& r, double* lds) const {
         if (r.in.done) return kSyGateLeave;            // (the kernel has returned on its `done` word already)
         double acc[kGateCols];
-        tall_norms_sum<kGateCols, false>(r.n, Pin, nwg, 1, nwg, acc, lds);
+        sums(r, lds, acc);
         const TallOutcome o = tall_outcome(r.in, acc[0], acc[1], acc[2], maxit, nlam);
         return o.discard() ? kSyGateLeave : o.pick();
     }
@@ -436,8 +444,11 @@ __device__ __forceinline__ void tall_lane_sum(float& a, float& b) {
 
 // x-update results a = Minv u, b = Minv w of element i (single device): kTailLanes lanes share one element and issue all their partial
 // loads at once, then combine with shuffles.  Nothing here depends on the control block.
-template <int MODE>
-__device__ __forceinline__ void tall_gather_ab(const TallParams& q, int i, int sub, bool valid, float& a, float& b) {
+// `behind`: the caller's own loads of the coordinate (only lanes with valid == true may have any).  TAIL_SYMV1 issues them behind its
+// sixteen partial requests and ahead of their first use (symv_kernels.h: symv_sum_partials1), the other forms ahead of the partials as before.
+template <int MODE, typename Behind = SymvNothingBehind>
+__device__ __forceinline__ void tall_gather_ab(const TallParams& q, int i, int sub, bool valid, float& a, float& b, Behind behind = Behind()) {
+    if (MODE != TAIL_SYMV1) behind();
     if (MODE == TAIL_SYMV) {
         symv_sum_partials<kTailLanes>(q.dot0, q.dot1, q.axp0, q.axp1, q.ldo, q.nrb, q.sched, q.p32, i, sub, valid, a, b);
         return;
@@ -445,7 +456,7 @@ __device__ __forceinline__ void tall_gather_ab(const TallParams& q, int i, int s
     if (MODE == TAIL_SYMV1) {
         // Plane 0 holds Minv u if the decision was "accelerate" and Minv w if it was "restart": the one the tail reads.  Returned as both,
         // so that `x = restart ? b : a` (tall_update_elem and its restatements) picks it either way -- and no load depends on ctl.
-        a = b = symv_sum_partials1<kTailLanes>(q.dot0, q.axp0, q.ldo, q.nrb, q.sched, q.p32, i, sub, valid);
+        a = b = symv_sum_partials1<kTailLanes>(q.dot0, q.axp0, q.ldo, q.nrb, q.sched, q.p32, i, sub, valid, behind);
         return;
     }
     a = 0.f; b = 0.f;
@@ -470,15 +481,17 @@ tall_tail_kernel(TallParams q, int par, PeerExchange ex) {
     WIDE_PROBE(0);
     const TallCtl c = q.ctl[par ^ 1];
     // Every load below is independent of `c` (the ping-pong parity equals the launch parity because
-    // the decision advances `total` once per launch), so the whole kernel is one memory round trip.
+    // the decision advances `total` once per launch), so the whole kernel is one memory round trip -- for TAIL_SYMV1 also as compiled:
+    // the sixteen partial requests go first and the owner lane's eight loads behind them, ahead of any wait (tall_gather_ab's `behind`).
     const int sub = threadIdx.x & (kTailLanes - 1);
     const int i = blockIdx.x * kTailElems + threadIdx.x / kTailLanes;
     const bool valid = i < q.p;
     const bool owner = valid && sub == 0;
     TallElem e = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    if (owner) e = tall_load_elem(q, par, i);
+    const auto load_elem = [&]() { if (owner) e = tall_load_elem(q, par, i); };      // the owner lane's eight loads; tall_gather_ab places them
     float a = 0.f, b = 0.f;
     if (MODE == TAIL_PEER || MODE == TAIL_PEER1) {
+        load_elem();
         const bool live = !q.ctl[par].done;                          // finished in an earlier launch: nothing pushed, nothing to wait for (replicated flag: all ranks agree)
         if (MODE == TAIL_PEER1 && live) {
             float sa, sb;
@@ -499,7 +512,7 @@ tall_tail_kernel(TallParams q, int par, PeerExchange ex) {
         }
         tall_lane_sum(a, b);
     } else {
-        tall_gather_ab<MODE>(q, i, sub, valid, a, b);
+        tall_gather_ab<MODE>(q, i, sub, valid, a, b, load_elem);
         if (MODE == TAIL_SYMV && q.refine_ab != nullptr && valid) {      // x = x1 + Minv (rhs - M x1): the partials hold the correction
             a = q.refine_ab[i] + a;
             b = q.refine_ab[q.refine_ld + i] + b;
@@ -924,6 +937,55 @@ long long tall_last_early_exits() { return t_early_exits; }
 // overflowed, bytes of the copy (all 0 where no copy was attempted).
 static thread_local long long t_pack_info[4] = {0, 0, 0, 0};
 void tall_last_pack_info(long long* out) { for (int k = 0; k < 4; ++k) out[k] = t_pack_info[k]; }
+
+// Test hooks admm_hip_test_tall_gate / admm_hip_test_tall_norms: the decision as ONE tile takes it (TallGate's request, sums and decide on
+// the compact copy of the norm partials) and the six sums as block 0 forms them from the rows of P, each by one workgroup of the kernels'
+// size on caller-supplied inputs.  The two must agree to the bit in the first three sums: a tile that decided otherwise than block 0
+// would multiply the wrong vector.
+__global__ void __launch_bounds__(kSyThreads) tall_gate_hook_kernel(TallGate gate, double* sums_out, int* answer_out) {
+    __shared__ double lds[kSyGateScratch];
+    const TallGate::Req r = gate.request();
+    double acc[kGateCols];
+    gate.sums(r, lds, acc);
+    const int g = gate.decide(r, lds);
+    if (threadIdx.x == 0) {
+        for (int k = 0; k < kGateCols; ++k) sums_out[k] = acc[k];
+        *answer_out = g;
+    }
+}
+__global__ void __launch_bounds__(kTailThreads) tall_norms_hook_kernel(const double* rows, int nwg, double* sums_out) {
+    __shared__ double lds[6 * (kTailThreads / 64)];
+    double acc[6];
+    tall_norms_sum<6, false>(tall_norms_request<6, false>(rows, nwg, 8, 1), rows, nwg, 8, 1, acc, lds);
+    if (threadIdx.x == 0) { for (int k = 0; k < 6; ++k) sums_out[k] = acc[k]; }
+}
+void test_tall_gate(const double* ctl_d, const int* ctl_i, const double* compact, int nwg, int maxit, int nlam, double* sums_out, int* answer_out) {
+    Stream st;
+    TallCtl c;
+    c.rho = ctl_d[0]; c.lam = ctl_d[1]; c.eps_primal = ctl_d[2]; c.eps_dual = ctl_d[3]; c.adj_a = ctl_d[4]; c.adj_c = ctl_d[5]; c.tau = ctl_d[6];
+    c.a_next = ctl_d[7]; c.tau_next = ctl_d[8];
+    c.mode = ctl_i[0]; c.restart = ctl_i[1]; c.iter = ctl_i[2]; c.lam_idx = ctl_i[3]; c.done = ctl_i[4]; c.first = ctl_i[5]; c.total = ctl_i[6];
+    c.fin_idx = ctl_i[7]; c.fin_niter = ctl_i[8]; c.pad = 0;
+    DevBuf<TallCtl> dc(1);
+    DevBuf<double> dP((size_t)kGateCols * nwg), ds(kGateCols);
+    DevBuf<int> da(1);
+    ADMM_HIP_CHECK(hipMemcpyAsync(dc.get(), &c, sizeof(TallCtl), hipMemcpyHostToDevice, st.s));
+    ADMM_HIP_CHECK(hipMemcpyAsync(dP.get(), compact, (size_t)kGateCols * nwg * sizeof(double), hipMemcpyHostToDevice, st.s));
+    ADMM_HIP_CHECK(hipStreamSynchronize(st.s));       // (c is on this frame)
+    const TallGate gate = {dc.get(), dP.get(), nwg, maxit, nlam};
+    hipLaunchKernelGGL(tall_gate_hook_kernel, dim3(1), dim3(kSyThreads), 0, st.s, gate, ds.get(), da.get());
+    ADMM_HIP_CHECK(hipGetLastError());
+    read_back(sums_out, ds.get(), kGateCols * sizeof(double), st.s);
+    read_back(answer_out, da.get(), sizeof(int), st.s);
+}
+void test_tall_norms(const double* rows, int nwg, double* sums_out) {
+    Stream st;
+    DevBuf<double> dP((size_t)8 * nwg), ds(6);
+    ADMM_HIP_CHECK(hipMemcpyAsync(dP.get(), rows, (size_t)8 * nwg * sizeof(double), hipMemcpyHostToDevice, st.s));
+    hipLaunchKernelGGL(tall_norms_hook_kernel, dim3(1), dim3(kTailThreads), 0, st.s, dP.get(), nwg, ds.get());
+    ADMM_HIP_CHECK(hipGetLastError());
+    read_back(sums_out, ds.get(), 6 * sizeof(double), st.s);
+}
 
 // ----------------------------------------------------------------------------------------------
 struct TallPlan final : LassoPlan {

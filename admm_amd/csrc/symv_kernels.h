@@ -82,6 +82,19 @@
 // loop, the same code in all three builds, 30.6 - 31.7.  C2 path: 81.9 - 82.4 ms per step against 82.8 - 83.0 (five alternating pairs).
 // Measured and not kept: the one-deep loop at 5 workgroups per CU (above: the same gain on average, less steady; not run through the
 // path); not built: requesting only the first pieces of chunk q + 1 ahead (two whole chunks fit).
+// Round 11, every prologue request before the first wait (profiles/tall_prologue.md; the measurements are there).  Read from the compiled
+// code, not from the source: symv1_tile's "one batch" had become three serialised vector round trips (a norm-partial load, its wait and
+// its add per column: the guards `w < nwg` on the load and on the add had been merged into one predicated block) and three to four
+// scalar ones (kernel arguments fetched as first used; the descriptor, the packed descriptor and the gate's control block sunk below the
+// `done` branch) in front of the first matrix byte, and the one-plane tail was two round trips (element loads, a wait, then the partials:
+// the address of the first partial read a register pair whose upper half was a pending load's destination).  Now, in the four default
+// instantiations: kernel arguments, one lgkmcnt(0); the batch -- six branch-free norm-partial loads (lasso_tall.hip), the tile descriptor,
+// `done`, the control block, the packed descriptor -- one lgkmcnt(0); chunk 0; the gate's first use of a norm partial at vmcnt(13), i.e.
+// behind nothing but its own loads.  What holds the order: a scheduling barrier above the batch, a compiler-level memory fence and pins
+// of the kernel arguments below it (a pin ABOVE the batch turned the control words' scalar loads into vector loads), the packed source's
+// chunk-0 request without its branch, and the tail's partial requests ahead of its element loads (symv_sum_partials1: `behind`).
+// tests/test_tall_prologue_asm.py reads the order from the assembly.  Same addends, same order, same block_sum: no result moves.
+// Not built: the row and column entries of both candidate vectors requested with chunk 0 (5 + 5 more live VGPRs at 124 of 128).
 #pragma once
 #include "admm_internal.h"
 #include "device_utils.h"
@@ -348,6 +361,7 @@ constexpr int kSyGateScratch = 6 * (kSyThreads / 64);     // doubles of LDS a ga
 struct SymvForcedGate {                                   // a fixed answer (test hook admm_hip_test_symv_one)
     struct Req {};
     int answer;
+    __device__ __forceinline__ void pin() const {}        // (a gate's kernel arguments, held in front of the prologue's batch: symv1_tile)
     __device__ __forceinline__ Req request() const { return Req(); }
     __device__ __forceinline__ int decide(const Req&, double*) const { return answer; }
 };
@@ -368,9 +382,11 @@ struct SymvTileGeom { int row, col0, last, lane, wid, nqw; };      // nqw: chunk
 // The fp32 matrix itself: one float4 per column, columns beyond `last` not loaded (zero).
 struct SymvDenseSrc {
     static constexpr int kDepth = 1;      // chunks a wave keeps in flight (117 VGPRs at one: no room for a second)
+    static constexpr bool kStraightLine = false;      // every column's load stands under a per-lane branch
     static __device__ __forceinline__ int wave_id() { return threadIdx.x >> 6; }
     struct Desc {};
     __device__ __forceinline__ Desc describe(int) const { return Desc(); }
+    __device__ __forceinline__ void pin() const {}      // kernel arguments of its own to hold in the prologue's batch: none
     template <bool NT>
     struct Chunk {
         const float* base; long long lda; int col0, last;
@@ -409,7 +425,9 @@ struct SymvPackedSrc {
     int esc_cap;
     using Desc = int4;
     __device__ __forceinline__ Desc describe(int tile) const { return ptile[tile]; }
+    __device__ __forceinline__ void pin() const { asm volatile("" :: "s"(stream), "s"(ptile), "s"(esc), "s"(esc_cap)); }
     static constexpr int kDepth = ADMM_HIP_SYMV1_DEPTH;       // chunks a wave keeps in flight: 2 x 29 of the 128 VGPRs of 4 waves per SIMD
+    static constexpr bool kStraightLine = true;               // request(q, exists): dead lanes and missing chunks by offset, no branch
     // the wave's number as a scalar: its first column, its chunk count and its place in the tile's row of dot partials then are scalars too
     static __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
     static constexpr unsigned kNoRequest = 0x7FFF0000u;       // a byte offset beyond any wave's chunks (8 x 7424 bytes), immediates added
@@ -487,12 +505,26 @@ struct SymvPackedSrc {
 // One tile of the one-vector product, behind the `extra` workgroup's exit: prologue, gate, peeled first chunk, column loop, epilogue.
 template <typename Src, typename Gate, bool NT, int PRE>
 __device__ __forceinline__ void symv1_tile(const SymvArgs& a, const Src& src, const Gate& gate, float4* red, float* sdot, double* gate_lds) {
-    // Prologue: the tile descriptor(s), the `done` word and the gate's inputs are requested together
+    // Prologue: the tile descriptor(s), the `done` word and the gate's inputs are requested together -- everything that needs only
+    // blockIdx, threadIdx and kernel arguments leaves in ONE batch, behind the wait for the kernel arguments and ahead of any other wait.
+    // Round 11: held there by a compiler-level memory fence in front of the `done` branch (no instruction; without it the descriptor
+    // loads and the gate's control block were sunk below the branch, one scalar round trip each) and by gates that do not use what they
+    // request before decide() (tests/test_tall_prologue_asm.py reads the compiled order).  The kernel arguments come in one fetch in
+    // front of the batch: every one the tile uses is pinned in this block, and the scheduling barrier keeps their fetches, which stand at
+    // its head, above the batch (fetched as they were first used, the pointers the batch starts from and the rest came in two or three
+    // scalar round trips).  The pins stand BEHIND the batch's loads: an asm statement in front of them makes the compiler read the
+    // control words through the vector path.
+    __builtin_amdgcn_sched_barrier(0);
     const int4 t = a.tiles[blockIdx.x - 1];
     const int done = *a.skip;
     const typename Gate::Req greq = gate.request();
     const typename Src::Desc sd = src.describe(blockIdx.x - 1);
-    if (done != 0) return;                 // (arrives with the descriptor: checked before the first matrix request, not behind it)
+    asm volatile("" ::: "memory");
+    asm volatile("" :: "s"(a.A), "s"(a.lda), "s"(a.p), "s"(a.v0), "s"(a.v1), "s"(a.dot0), "s"(a.axp0), "s"(a.ldo), "s"(a.early));
+    src.pin();
+    gate.pin();
+    __builtin_amdgcn_sched_barrier(0);
+    if (done != 0) return;                // (arrives with the descriptor: checked before the first matrix request, not behind it)
     const int rb = t.x, seg = t.w;
     const int cw = t.z >> 2;               // columns per wave: a multiple of 8, at most 64
     const int lane = threadIdx.x & 63, wid = Src::wave_id();
@@ -507,7 +539,13 @@ __device__ __forceinline__ void symv1_tile(const SymvArgs& a, const Src& src, co
     const SymvTileGeom geom = {row, col0, last, lane, wid, cw >> 3};
     typename Src::template Chunk<NT> ch(src, sd, a, geom);
     static_assert(PRE >= 0 && PRE <= 8, "columns of the first chunk requested ahead of the gate");
-    if constexpr (PRE > 0) { if (nq > 0) ch.template request<0, PRE>(0); }
+    if constexpr (PRE > 0) {
+        // a source whose requests are straight-line code asks without a branch (a wave without columns asks for nothing): behind a
+        // branch, the gate's wait for its own loads has to cover the path that skipped the chunk's, and takes part of the chunk in
+        if constexpr (Src::kStraightLine) ch.template request<0, PRE>(0, nq > 0);
+        else if (nq > 0) ch.template request<0, PRE>(0);
+    }
+    __builtin_amdgcn_sched_barrier(0);     // the gate's first use of its requests stays behind the chunk's
     const int g = gate.decide(greq, gate_lds);
     if (g == kSyGateLeave) {               // nobody reads what this launch would write: the slots keep what the last consumed launch left
         if (threadIdx.x == 0) atomicAdd(a.early + (size_t)(blockIdx.x & (kSyEarlySlots - 1)) * kSyVerdictStride, 1ull);
@@ -1204,9 +1242,16 @@ __device__ __forceinline__ void symv_sum_partials(const T* __restrict__ dot0, co
 
 // The same for plane 0 alone (symv1_lower_kernel writes no other): symv_sum_partials' slots, clamping, order and lane combine for `a`,
 // so the sum has the bits that function returns as a (or, for the same partials in plane 1, as b) -- at 16 loads per lane, not 32.
-template <int NL, typename T = float>
+// Round 11: `behind` is called once, behind the first 16 requests and ahead of their first use, by every lane with valid == true (the
+// only lanes that request anything): the caller's own loads go there -- the tall tail's element loads -- so that they and the partials
+// are ONE round trip.  The partials go first because their addresses take the longer arithmetic: formed while the caller's loads are
+// pending, a 64-bit multiply-add read a register pair whose upper half was a pending load's destination, and the wait for that load
+// stood in front of all sixteen requests.
+struct SymvNothingBehind { __device__ __forceinline__ void operator()() const {} };
+template <int NL, typename T = float, typename Behind = SymvNothingBehind>
 __device__ __forceinline__ T symv_sum_partials1(const T* __restrict__ dot0, const T* __restrict__ axp0,
-                                                long long ldo, int nrb, const SymvSched sched, int p32, int i, int sub, bool valid) {
+                                                long long ldo, int nrb, const SymvSched sched, int p32, int i, int sub, bool valid,
+                                                Behind behind = Behind()) {
     const int ic = valid ? i : 0;
     const int rbi = ic / kSyRB;
     const int rb0 = rbi;
@@ -1215,8 +1260,7 @@ __device__ __forceinline__ T symv_sum_partials1(const T* __restrict__ dot0, cons
     const int ntot = valid ? ndot + nax : 0;
     const unsigned ld = (unsigned)ldo;
     T a = T(0);
-    for (int k0 = 0; k0 < ntot; k0 += 16 * NL) {
-        T va[16];
+    const auto request = [&](int k0, T (&va)[16]) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             const int k = k0 + j * NL + sub;
@@ -1225,12 +1269,28 @@ __device__ __forceinline__ T symv_sum_partials1(const T* __restrict__ dot0, cons
             const unsigned o = (unsigned)row * ld + (unsigned)ic;
             va[j] = (isdot ? dot0 : axp0)[o];
         }
-        __builtin_amdgcn_sched_barrier(0);
+    };
+    const auto add = [&](int k0, const T (&va)[16]) {
 #pragma unroll
         for (int j = 0; j < 16; ++j) {
             const bool in = k0 + j * NL + sub < ntot;
             a += in ? va[j] : T(0);
         }
+    };
+    constexpr bool peel = !std::is_same<Behind, SymvNothingBehind>::value;      // (a caller without loads of its own keeps the plain loop: the tails of the other penalties compile as before)
+    if (peel && ntot > 0) {                  // the first pass, peeled for `behind`; the loop goes on where it ends
+        T va[16];
+        request(0, va);
+        __builtin_amdgcn_sched_barrier(0);
+        behind();
+        __builtin_amdgcn_sched_barrier(0);
+        add(0, va);
+    }
+    for (int k0 = peel ? 16 * NL : 0; k0 < ntot; k0 += 16 * NL) {
+        T va[16];
+        request(k0, va);
+        __builtin_amdgcn_sched_barrier(0);
+        add(k0, va);
     }
 #pragma unroll
     for (int m = 1; m < NL; m <<= 1) a += __shfl_xor(a, m, 64);

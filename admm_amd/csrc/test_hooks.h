@@ -48,6 +48,10 @@ void test_cv_fold_system(const double* x, const double* y, int n, int p, const i
                          int standardize, int intercept, float* gram, float* xy, float* mean_x, float* scale_x, float* mean_scale_y);
 long long tall_last_early_exits();      // lasso_tall.hip
 void tall_last_pack_info(long long* out);      // lasso_tall.hip
+constexpr int kTallGateHookMaxNwg = 1 << 16;
+void test_tall_gate(const double* ctl_d, const int* ctl_i, const double* compact, int nwg, int maxit, int nlam, double* sums_out,
+                    int* answer_out);      // lasso_tall.hip (TallGate lives there): a tile's decision on caller-supplied inputs
+void test_tall_norms(const double* rows, int nwg, double* sums_out);      // lasso_tall.hip: block 0's six sums from the rows of P
 void test_logit_prox(const double* v, long long m, double t, double* out);      // fadmm_dense.hip: the device logit2 over a host array
 void test_poisson_prox(const double* v, const double* y, long long m, double t, double* out);      // fadmm_dense.hip: the device pois2 over host arrays
 

@@ -854,6 +854,14 @@ ADMM_HIP_API int admm_hip_test_tall_early_exits(long long* count);
  * entries met outside their tile's exponent window while packing; tiles whose list of such entries overflowed (any: the fp32 stream);
  * bytes of the copy.  All 0 where no copy was attempted. */
 ADMM_HIP_API int admm_hip_test_tall_pack_info(long long* info_out);
+/* The decision of the decide-first x-update as ONE tile takes it in its prologue, on caller-supplied HOST inputs: the control block
+ * (ctl_d[9]: rho, lam, eps_primal, eps_dual, adj_a, adj_c, tau, a_next, tau_next; ctl_i[9]: mode, restart, iter, lam_idx, done, first,
+ * total, fin_idx, fin_niter) and the compact copy [3][nwg] of the norm partials r^2, dz^2, daz^2 of nwg tail workgroups.
+ * sums_out[3]: the three sums the tile formed; *answer_out: -1 leave (the launch's products are not used), 0 multiply u, 1 multiply w. */
+ADMM_HIP_API int admm_hip_test_tall_gate(const double* ctl_d, const int* ctl_i, const double* compact, int nwg, int maxit, int nlam,
+                                         double* sums_out, int* answer_out);
+/* The six norm sums as the x-update's deciding workgroup forms them from the rows [nwg][8] of the norm partials (HOST); sums_out[6]. */
+ADMM_HIP_API int admm_hip_test_tall_norms(const double* rows, int nwg, double* sums_out);
 /* The device prox of admm_hip_logit alone: out[k] = the root z of z - v[k] - t / (1 + e^z), t = 1 / rho > 0, over HOST arrays of
  * length m, by the device function the tail and rows kernels call. */
 ADMM_HIP_API int admm_hip_test_logit_prox(const double* v, long long m, double t, double* out);
