@@ -287,24 +287,46 @@ void lad(const double* x, const double* y, int n, int p, int mem, int intercept,
 }
 
 namespace {
-// What admm_hip_quantreg and admm_hip_huber share behind their own argument checks: the shape rule of a fitted intercept, LAD's
-// standardisation, nfit columns out.  solve: solve_quantreg / solve_huber on the standardised data.
-using GridSolve = std::function<void(DeviceData<double>&, bool, QuantResult&, hipStream_t)>;
-void run_lad_grid(const double* x, const double* y, int n, int p, int mem, int intercept, int ntau, const admm_opts* opts, const GridSolve& solve, const DenseOut& out) {
-    const bool icpt = intercept != 0;
+// the checks of a call whose intercept is FITTED (a column of ones behind the standardised X): n > p + intercept
+void check_fitted(const double* x, const double* y, int n, int p, int mem, bool icpt, const admm_opts* opts, const DenseOut& out) {
     check_dense(x, y, n, p, mem, opts, (long long)n > (long long)p + (icpt ? 1 : 0),
                 icpt ? "nrow(x) must be greater than ncol(x) + 1 (the intercept is fitted)" : "nrow(x) must be greater than ncol(x)", true, out);
+}
+// the label validation of a k-column call (first offending column, 0-based); ones: per column the count of labels 1.0, or NULL.
+// Host labels are checked here, device labels by one reduction kernel per column, without a copy to the host.
+void check_label_columns(const double* y, int n, int k, int mem, std::vector<long long>* ones_out) {
+    for (int c = 0; c < k; ++c) {
+        const double* yc = y + (size_t)c * n;
+        long long bad = 0, ones = 0;
+        if (mem == ADMM_MEM_HOST) {
+            for (int i = 0; i < n; ++i) { if (yc[i] == 1.0) ++ones; else if (!(yc[i] == 0.0)) ++bad; }
+        } else {
+            require_device();
+            Stream cs;
+            logit_count_labels(yc, n, &bad, &ones, cs.s);
+        }
+        ADMM_REQUIRE(bad == 0, "column " + std::to_string(c) + " of y: every label must be exactly 0 or 1");
+        ADMM_REQUIRE(ones > 0 && ones < n, "column " + std::to_string(c) + " of y must hold both classes");
+        if (ones_out) (*ones_out)[c] = ones;
+    }
+}
+// What the grid calls on the LAD loop share behind their own argument checks: LAD's standardisation (always), the caller's ycols
+// columns of y resident on the device for the solver (labels, counts; 0: it needs the standardised response only -- with columns the
+// response the upload standardises, column 0, is replaced by zeros there), every fit's coefficients and iterations out.
+using GridSolve = std::function<void(DeviceData<double>&, const double*, QuantResult&, hipStream_t)>;
+void run_lad_grid(const double* x, const double* y, int n, int p, int ycols, int mem, bool icpt, const admm_opts* opts, const GridSolve& solve, const DenseOut& out) {
     require_device();
     const double t0 = now_s();
     Stream st;
     DeviceData<double> d;
     upload_standardize<double>(d, x, y, n, p, mem, true, icpt, st.s);
+    const Resident cols(y, (size_t)n * ycols, mem);
     QuantResult res;
     begin_result(res.dense, d, out.trace);
     res.dense.state_cap = out.state.cap;
-    solve(d, icpt, res, st.s);
+    solve(d, cols.p, res, st.s);
     std::memcpy(out.beta_out, res.beta.data(), res.beta.size() * sizeof(double));
-    for (int k = 0; k < ntau; ++k) out.niter_out[k] = res.niter[k];
+    for (size_t k = 0; k < res.niter.size(); ++k) out.niter_out[k] = res.niter[k];
     store_state(res.dense, out.state);
     finish_result(res.dense, t0, out.trace, out.stats);
 }
@@ -317,8 +339,9 @@ void quantreg(const double* x, const double* y, int n, int p, int mem, int inter
     ADMM_REQUIRE(ntau >= 1 && ntau <= 4096, "the number of quantiles must be within [1, 4096]");
     for (int k = 0; k < ntau; ++k) ADMM_REQUIRE(std::isfinite(tau[k]) && tau[k] > 0.0 && tau[k] < 1.0, "every tau must lie strictly between 0 and 1");
     ADMM_REQUIRE(ntau == 1 || out.trace.cap == 0, "the decision trace is recorded for a single tau");
-    run_lad_grid(x, y, n, p, mem, intercept, ntau, opts,
-                 [&](DeviceData<double>& d, bool icpt, QuantResult& res, hipStream_t st) { solve_quantreg(d, icpt, *opts, tau, ntau, res, st); }, out);
+    const bool icpt = intercept != 0;
+    check_fitted(x, y, n, p, mem, icpt, opts, out);
+    run_lad_grid(x, y, n, p, 0, mem, icpt, opts, [&](DeviceData<double>& d, const double*, QuantResult& res, hipStream_t st) { solve_quantreg(d, icpt, *opts, tau, ntau, res, st); }, out);
 }
 
 // admm_hip_huber: the same call with the Huber form of the prox, one fit per (delta[k], tau[k]); tau = NULL: the symmetric Huber loss.
@@ -332,8 +355,9 @@ void huber(const double* x, const double* y, int n, int p, int mem, int intercep
     ADMM_REQUIRE(nfit == 1 || out.trace.cap == 0, "the decision trace is recorded for a single fit");
     std::vector<double> t(nfit, 0.5);
     if (tau != nullptr) t.assign(tau, tau + nfit);
-    run_lad_grid(x, y, n, p, mem, intercept, nfit, opts,
-                 [&](DeviceData<double>& d, bool icpt, QuantResult& res, hipStream_t st) { solve_huber(d, icpt, *opts, delta, t.data(), nfit, res, st); }, out);
+    const bool icpt = intercept != 0;
+    check_fitted(x, y, n, p, mem, icpt, opts, out);
+    run_lad_grid(x, y, n, p, 0, mem, icpt, opts, [&](DeviceData<double>& d, const double*, QuantResult& res, hipStream_t st) { solve_huber(d, icpt, *opts, delta, t.data(), nfit, res, st); }, out);
 }
 
 // admm_hip_logit: logistic regression on the LAD loop (solve_logit).  The shape rule of the fitted intercept and LAD's standardisation
@@ -341,8 +365,7 @@ void huber(const double* x, const double* y, int n, int p, int mem, int intercep
 // reduction kernel, without a copy to the host.  The signs come from the caller's y, not from the standardised one.
 void logit(const double* x, const double* y, int n, int p, int mem, int intercept, const admm_opts* opts, const DenseOut& out) {
     const bool icpt = intercept != 0;
-    check_dense(x, y, n, p, mem, opts, (long long)n > (long long)p + (icpt ? 1 : 0),
-                icpt ? "nrow(x) must be greater than ncol(x) + 1 (the intercept is fitted)" : "nrow(x) must be greater than ncol(x)", true, out);
+    check_fitted(x, y, n, p, mem, icpt, opts, out);
     long long bad = 0, ones = 0;
     if (mem == ADMM_MEM_HOST) {
         for (int i = 0; i < n; ++i) { if (y[i] == 1.0) ++ones; else if (!(y[i] == 0.0)) ++bad; }
@@ -374,33 +397,9 @@ void logit(const double* x, const double* y, int n, int p, int mem, int intercep
 void logit_multi(const double* x, const double* y, int n, int p, int k, int mem, int intercept, const admm_opts* opts, const DenseOut& out) {
     const bool icpt = intercept != 0;
     ADMM_REQUIRE(k >= 1, "y must have at least one column");
-    check_dense(x, y, n, p, mem, opts, (long long)n > (long long)p + (icpt ? 1 : 0),
-                icpt ? "nrow(x) must be greater than ncol(x) + 1 (the intercept is fitted)" : "nrow(x) must be greater than ncol(x)", true, out);
-    for (int c = 0; c < k; ++c) {
-        const double* yc = y + (size_t)c * n;
-        long long bad = 0, ones = 0;
-        if (mem == ADMM_MEM_HOST) {
-            for (int i = 0; i < n; ++i) { if (yc[i] == 1.0) ++ones; else if (!(yc[i] == 0.0)) ++bad; }
-        } else {
-            require_device();
-            Stream cs;
-            logit_count_labels(yc, n, &bad, &ones, cs.s);
-        }
-        ADMM_REQUIRE(bad == 0, "column " + std::to_string(c) + " of y: every label must be exactly 0 or 1");
-        ADMM_REQUIRE(ones > 0 && ones < n, "column " + std::to_string(c) + " of y must hold both classes");
-    }
-    require_device();
-    const double t0 = now_s();
-    Stream st;
-    DeviceData<double> d;
-    upload_standardize<double>(d, x, y, n, p, mem, true, icpt, st.s);      // (the response it standardises, column 0, is zeroed by the solver)
-    Resident labels(y, (size_t)n * k, mem);
-    QuantResult res;
-    begin_result(res.dense, d, out.trace);
-    solve_logit_multi(d, icpt, labels.p, k, *opts, res, st.s);
-    std::memcpy(out.beta_out, res.beta.data(), res.beta.size() * sizeof(double));
-    for (int c = 0; c < k; ++c) out.niter_out[c] = res.niter[c];
-    finish_result(res.dense, t0, out.trace, out.stats);
+    check_fitted(x, y, n, p, mem, icpt, opts, out);
+    check_label_columns(y, n, k, mem, nullptr);
+    run_lad_grid(x, y, n, p, k, mem, icpt, opts, [&](DeviceData<double>& d, const double* labels, QuantResult& res, hipStream_t st) { solve_logit_multi(d, icpt, labels, k, *opts, res, st); }, out);
 }
 
 // admm_hip_logit_ridge: logit_multi with the ridge penalty lambda / 2 sum b_j^2 (solve_logit_ridge), one fit per (column, lambda).  The
@@ -415,51 +414,9 @@ void logit_ridge(const double* x, const double* y, int n, int p, int k, int mem,
         ADMM_REQUIRE(std::isfinite(lambda[l]) && lambda[l] > 0.0, "every lambda must be finite and positive (lambda = 0 is admm_hip_logit_multi)");
     ADMM_REQUIRE((k == 1 && nlambda == 1) || out.trace.cap == 0, "the decision trace is recorded for a single column and a single lambda");
     check_dense(x, y, n, p, mem, opts, n >= 2, "nrow(x) must be at least 2", true, out);
-    for (int c = 0; c < k; ++c) {
-        const double* yc = y + (size_t)c * n;
-        long long bad = 0, ones = 0;
-        if (mem == ADMM_MEM_HOST) {
-            for (int i = 0; i < n; ++i) { if (yc[i] == 1.0) ++ones; else if (!(yc[i] == 0.0)) ++bad; }
-        } else {
-            require_device();
-            Stream cs;
-            logit_count_labels(yc, n, &bad, &ones, cs.s);
-        }
-        ADMM_REQUIRE(bad == 0, "column " + std::to_string(c) + " of y: every label must be exactly 0 or 1");
-        ADMM_REQUIRE(ones > 0 && ones < n, "column " + std::to_string(c) + " of y must hold both classes");
-    }
-    require_device();
-    const double t0 = now_s();
-    Stream st;
-    DeviceData<double> d;
-    upload_standardize<double>(d, x, y, n, p, mem, true, icpt, st.s);      // (the response it standardises, column 0, is replaced by zeros)
-    Resident labels(y, (size_t)n * k, mem);
-    QuantResult res;
-    begin_result(res.dense, d, out.trace);
-    res.dense.state_cap = out.state.cap;
-    solve_logit_ridge(d, icpt, labels.p, k, lambda, nlambda, *opts, res, st.s);
-    std::memcpy(out.beta_out, res.beta.data(), res.beta.size() * sizeof(double));
-    for (size_t c = 0; c < res.niter.size(); ++c) out.niter_out[c] = res.niter[c];
-    store_state(res.dense, out.state);
-    finish_result(res.dense, t0, out.trace, out.stats);
-}
-
-// the label validation of logit_multi / logit_ridge (first offending column, 0-based); ones: per column the count of labels 1.0, or NULL
-static void check_label_columns(const double* y, int n, int k, int mem, std::vector<long long>* ones_out) {
-    for (int c = 0; c < k; ++c) {
-        const double* yc = y + (size_t)c * n;
-        long long bad = 0, ones = 0;
-        if (mem == ADMM_MEM_HOST) {
-            for (int i = 0; i < n; ++i) { if (yc[i] == 1.0) ++ones; else if (!(yc[i] == 0.0)) ++bad; }
-        } else {
-            require_device();
-            Stream cs;
-            logit_count_labels(yc, n, &bad, &ones, cs.s);
-        }
-        ADMM_REQUIRE(bad == 0, "column " + std::to_string(c) + " of y: every label must be exactly 0 or 1");
-        ADMM_REQUIRE(ones > 0 && ones < n, "column " + std::to_string(c) + " of y must hold both classes");
-        if (ones_out) (*ones_out)[c] = ones;
-    }
+    check_label_columns(y, n, k, mem, nullptr);
+    run_lad_grid(x, y, n, p, k, mem, icpt, opts,
+                 [&](DeviceData<double>& d, const double* labels, QuantResult& res, hipStream_t st) { solve_logit_ridge(d, icpt, labels, k, lambda, nlambda, *opts, res, st); }, out);
 }
 
 // admm_hip_logit_enet: logit_ridge's call with (lambda, alpha) cells in place of the lambda grid (solve_logit_enet): one fit per
@@ -475,20 +432,8 @@ void logit_enet(const double* x, const double* y, int n, int p, int k, int mem, 
     ADMM_REQUIRE((k == 1 && ncell == 1) || out.trace.cap == 0, "the decision trace is recorded for a single column and a single cell");
     check_dense(x, y, n, p, mem, opts, n >= 2, "nrow(x) must be at least 2", true, out);
     check_label_columns(y, n, k, mem, nullptr);
-    require_device();
-    const double t0 = now_s();
-    Stream st;
-    DeviceData<double> d;
-    upload_standardize<double>(d, x, y, n, p, mem, true, icpt, st.s);      // (the response it standardises, column 0, is replaced by zeros)
-    Resident labels(y, (size_t)n * k, mem);
-    QuantResult res;
-    begin_result(res.dense, d, out.trace);
-    res.dense.state_cap = out.state.cap;
-    solve_logit_enet(d, icpt, labels.p, k, lambda, alpha, ncell, *opts, res, st.s);
-    std::memcpy(out.beta_out, res.beta.data(), res.beta.size() * sizeof(double));
-    for (size_t c = 0; c < res.niter.size(); ++c) out.niter_out[c] = res.niter[c];
-    store_state(res.dense, out.state);
-    finish_result(res.dense, t0, out.trace, out.stats);
+    run_lad_grid(x, y, n, p, k, mem, icpt, opts,
+                 [&](DeviceData<double>& d, const double* labels, QuantResult& res, hipStream_t st) { solve_logit_enet(d, icpt, labels, k, lambda, alpha, ncell, *opts, res, st); }, out);
 }
 
 // admm_hip_logit_enet_lambda_max: lambda_1 per label column on the standardised columns, max_j |x~_j'(y_c - mean)|, mean = the column's
@@ -551,20 +496,8 @@ void poisson(const double* x, const double* y, int n, int p, int k, int mem, int
     check_dense(x, y, n, p, mem, opts, n >= 2, "nrow(x) must be at least 2", true, out);
     ADMM_REQUIRE(!unpenalised || (long long)n > (long long)p + (icpt ? 1 : 0), "lambda = 0 needs nrow(x) > ncol(x) + intercept");
     check_count_columns(y, n, k, mem);
-    require_device();
-    const double t0 = now_s();
-    Stream st;
-    DeviceData<double> d;
-    upload_standardize<double>(d, x, y, n, p, mem, true, icpt, st.s);      // (the response it standardises, column 0, is replaced by zeros)
-    Resident counts(y, (size_t)n * k, mem);
-    QuantResult res;
-    begin_result(res.dense, d, out.trace);
-    res.dense.state_cap = out.state.cap;
-    solve_poisson(d, icpt, counts.p, k, lambda, alpha, ncell, *opts, res, st.s);
-    std::memcpy(out.beta_out, res.beta.data(), res.beta.size() * sizeof(double));
-    for (size_t c = 0; c < res.niter.size(); ++c) out.niter_out[c] = res.niter[c];
-    store_state(res.dense, out.state);
-    finish_result(res.dense, t0, out.trace, out.stats);
+    run_lad_grid(x, y, n, p, k, mem, icpt, opts,
+                 [&](DeviceData<double>& d, const double* counts, QuantResult& res, hipStream_t st) { solve_poisson(d, icpt, counts, k, lambda, alpha, ncell, *opts, res, st); }, out);
 }
 
 // admm_hip_poisson_lambda_max: lambda_1 per count column on the standardised columns, max_j |x~_j'(y_c - mu)|: mu = mean(y_c) with the

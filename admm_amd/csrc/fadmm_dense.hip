@@ -71,12 +71,6 @@ struct DenseParams {
 };
 
 constexpr int kDenseThreads = 256;
-constexpr int kQuantAutoSlots = 1;         // what QUANT_SLOTS=0 picks on the one-pass branch (decided by scripts/bench_quantreg.py)
-constexpr int kLogitAutoSlots = 4;         // the same for admm_hip_logit_multi: as many as the layout admits (measured: scripts/bench_logit_multi.py, profiles/logit_multi.md)
-constexpr int kLogitRidgeAutoSlots = kLogitAutoSlots;      // the same for admm_hip_logit_ridge: ahead of serial at every layout with slots (measured: scripts/bench_logit_ridge.py, profiles/logit_ridge.md)
-constexpr int kLogitEnetAutoSlots = kLogitAutoSlots;      // the same for admm_hip_logit_enet: ahead of serial at every layout with slots (measured: scripts/bench_logit_enet.py, profiles/logit_enet.md)
-constexpr int kPoissonAutoSlots = kLogitAutoSlots;      // the same for admm_hip_poisson: ahead of serial at every layout with slots (measured: scripts/bench_poisson.py, profiles/poisson.md)
-constexpr int kHuberAutoSlots = 4;         // the same for admm_hip_huber: as many as the layout admits (measured: scripts/bench_huber.py, profiles/huber_loss.md)
 
 __device__ __forceinline__ double soft2(double v, double hi, double lo) {
     return v > hi ? v - hi : (v < -lo ? v + lo : 0.0);
@@ -116,11 +110,40 @@ constexpr int kProxSoft = 0, kProxHuber = 1, kProxLogit = 2, kProxLogitS = 3, kP
 // kProxPoisE (admm_hip_poisson): kProxLogitE's matrix and penalty rows with the Poisson loss e^z - y z on the data rows.  The "sign" matrix
 // carries the row's COUNT y_i >= 0 instead of +-1 and the marker -1.0 on every penalty row and padding entry (counts are refused below
 // zero): an entry >= 0 takes pois2(v, y, 1 / rho) below -- no sign round trip --, a marker row enet2 as the E form calls it.
-// prox_is_logit: the prox is iterative and is formed once per row by the rows kernels' prox lanes; prox_is_signed: the per-row entry
-// of DenseParams::sgn travels in the response's place; prox_is_enet: penalty rows whose constants are the fit's c_hi / c_lo.
-constexpr bool prox_is_logit(int prox) { return prox == kProxLogit || prox == kProxLogitS || prox == kProxLogitR || prox == kProxLogitE || prox == kProxPoisE; }
-constexpr bool prox_is_signed(int prox) { return prox == kProxLogitS || prox == kProxLogitR || prox == kProxLogitE || prox == kProxPoisE; }
-constexpr bool prox_is_enet(int prox) { return prox == kProxLogitE || prox == kProxPoisE; }
+// What the kernels and the host need to know of a kind, stated once and indexed by it.  iterative: the prox is a Newton iteration and
+// is formed once per row by the rows kernels' prox lanes; tagged: the per-row entry of DenseParams::sgn (sign or count) travels in the
+// response's place and row_prox_tagged below holds the case analysis; enet: penalty rows whose constants are the fit's c_hi / c_lo.
+// auto_slots: what QUANT_SLOTS=0 picks on the one-pass branch.  max_slots[NPT - 1], NPT = 1 .. 6 the columns a thread of the rows
+// kernels holds per row (lad_npt): how many slots the registers of quant_rows_kernel hold -- the instantiations without scratch
+// (tests/test_lad_kernels_asm.py pins that they have none); 1 = no slotted form.  The dispatch below instantiates
+// quant_rows_kernel<NPT, S, kind> for S = 2 .. max_slots[NPT - 1] and nothing else.
+struct ProxKind {
+    bool iterative, tagged, enet;
+    int auto_slots;
+    int max_slots[6];
+};
+constexpr int kProxKindCount = 7, kLadMaxNpt = 6;
+constexpr ProxKind kProxKinds[kProxKindCount] = {
+    // kProxSoft (admm_hip_quantreg).  auto 1: DESIGN §8, decided by scripts/bench_quantreg.py.  NPT 6 is six double2 per row: two slots would spill
+    {false, false, false, 1, {4, 4, 4, 3, 2, 1}},
+    // kProxHuber (admm_hip_huber).  auto: as many as the layout admits (measured: scripts/bench_huber.py, profiles/huber_loss.md).
+    // (4, 3) spills 16 bytes and fell away
+    {false, false, false, 4, {4, 4, 4, 2, 2, 1}},
+    // kProxLogit (admm_hip_logit): the matrix carries the labels, one fit per call -- no slotted form
+    {true, false, false, 1, {1, 1, 1, 1, 1, 1}},
+    // kProxLogitS (admm_hip_logit_multi).  auto: as many as the layout admits (measured: scripts/bench_logit_multi.py,
+    // profiles/logit_multi.md).  (4, 3) spills 64 bytes, (5, 2) 24 (profiles/logit_multi.md)
+    {true, true, false, 4, {4, 4, 4, 2, 1, 1}},
+    // kProxLogitR (admm_hip_logit_ridge).  auto: ahead of serial at every layout with slots (measured: scripts/bench_logit_ridge.py,
+    // profiles/logit_ridge.md).  The S form's table (profiles/logit_ridge.md)
+    {true, true, false, 4, {4, 4, 4, 2, 1, 1}},
+    // kProxLogitE (admm_hip_logit_enet).  auto: ahead of serial at every layout with slots (measured: scripts/bench_logit_enet.py,
+    // profiles/logit_enet.md).  The R form's table less (3, 4), which spills 16 bytes (profiles/logit_enet.md)
+    {true, true, true, 4, {4, 4, 3, 2, 1, 1}},
+    // kProxPoisE (admm_hip_poisson).  auto: ahead of serial at every layout with slots (measured: scripts/bench_poisson.py,
+    // profiles/poisson.md).  The kProxPoisE instantiations without scratch (profiles/poisson.md)
+    {true, true, true, 4, {4, 4, 3, 2, 1, 1}},
+};
 // The prox of (c_hi |z| + c_lo z^2 / 2) / rho at v: t = c_hi / rho, d = 1 + c_lo / rho, z = soft(v, t) / d -- in this association, every
 // operation rounded on its own (tests/logit_enet_oracle.py replays it)
 __device__ __forceinline__ double enet2(double v, double c_hi, double c_lo, double rho) {
@@ -206,6 +229,25 @@ __device__ __forceinline__ double prox2(double v, double hi, double lo, double d
     if (PROX == kProxLogit) return logit2(v, hi);      // hi = c_hi / rho with c_hi = 1: t
     if (PROX == kProxHuber) return huber2(v, hi, lo, delta);
     return soft2(v, hi, lo);
+}
+// The row prox of the tagged kinds, the one statement of it (tail kernel, both rows kernels).  tag() returns the row's entry of the sign
+// or count column; c_hi / c_lo are the fit's penalty constants (read by the enet kinds only).  t = 1 / rho for every kind: the S and R
+// fits carry c_hi = 1.0 (LadProx's default), so the c_hi / rho the serial kernels once formed for them is the same double.  The rows
+// kernels pass a callable that reads LDS on every call: the tag is read again behind the Newton iteration (the barrier below keeps the
+// two reads apart), not held in registers across it.
+template <int PROX, class TAG>
+__device__ __forceinline__ double row_prox_tagged(double v, TAG tag, double c_hi, double c_lo, double rho) {
+#pragma clang fp contract(off)
+    if constexpr (PROX == kProxPoisE) {
+        const double cnt = tag();                                    // >= 0: a data row's count; the marker -1.0: a penalty row
+        return cnt < 0.0 ? enet2(v, c_hi, c_lo, rho) : pois2(v, cnt, 1.0 / rho);
+    } else {
+        if (PROX == kProxLogitR && tag() == 0.0) return v * (rho / (1.0 + rho));
+        if (PROX == kProxLogitE && tag() == 0.0) return enet2(v, c_hi, c_lo, rho);
+        const double zs = logit2(tag() * v, 1.0 / rho);              // s logit2(s v, t)
+        asm volatile("" ::: "memory");
+        return tag() * zs;
+    }
 }
 // lane l's double in every lane (l uniform): two scalar reads
 __device__ __forceinline__ double read_lane_f64(double v, int l) {
@@ -408,7 +450,8 @@ __device__ __forceinline__ DenseParams quant_slot_params(DenseParams q, int s, l
     q.ctl += 2 * s;
     return q;
 }
-__device__ __forceinline__ DenseCtl dense_cold_ctl(double rho, int pad) {
+// the control block of a cold start (pad: the slotted loop's index of the fit)
+__host__ __device__ __forceinline__ DenseCtl dense_cold_ctl(double rho, int pad) {
     DenseCtl c;
     c.rho = rho; c.eps_primal = 0; c.eps_dual = 0; c.adj_a = 1.0; c.adj_c = 9999.0; c.tau = 0.0;
     c.restart = 0; c.iter = 0; c.done = 0; c.first = 1; c.total = 0; c.niter = 0; c.conv = 0; c.pad = pad;
@@ -554,7 +597,7 @@ __device__ __forceinline__ void lad_row_step(int i, int tid, double x, double dv
     double zn, yn;
     {
 #pragma clang fp contract(off)
-        if (prox_is_logit(PROX)) zn = zlogit;                                // formed once per row by the rows kernels' logit lanes, not in every thread
+        if (kProxKinds[PROX].iterative) zn = zlogit;                         // formed once per row by the rows kernels' logit lanes, not in every thread
         else zn = prox2<PROX>(x - dv + in.ajy / rho, pen_hi, pen_lo, delta); // dense_tail_kernel, prob 0 (ADMMLAD.h:94-107)
         const double rr = x - dv - zn;
         yn = in.ajy + rho * rr;
@@ -631,7 +674,7 @@ lad_rows_kernel(DenseParams q, int par, const double* __restrict__ Xt, long long
     // kProxLogitR: the same, and a row whose sign is 0.0 (a ridge row: the last rows of the matrix) takes the square loss's prox instead.
     // kProxLogitE: the same with the elastic net's prox on those rows (q.c_hi, q.c_lo: the fit's constants; t of the +-1 rows stays 1 / rho).
     // kProxPoisE: the rows' counts travel there; a count >= 0 takes the Poisson prox, the marker -1.0 (a penalty row) the elastic net's.
-    constexpr bool SIGNED = prox_is_signed(PROX);
+    constexpr bool SIGNED = kProxKinds[PROX].tagged;
     __shared__ double uni[2][4 * R];           // d (kProxLogitS: the sign) | adj_y | adj_z | z of the R rows (unreferenced, so not allocated, in the other instantiations)
     auto group_logit = [&](int i0, const double2 (&rv)[R][NPT]) {
         double uval = 0.0;
@@ -650,20 +693,8 @@ lad_rows_kernel(DenseParams q, int par, const double* __restrict__ Xt, long long
             double x = wsum[buf][0][lane];
 #pragma unroll
             for (int w = 1; w < NWV; ++w) x += wsum[buf][w][lane];
-            if constexpr (PROX == kProxPoisE) {
-                // the row's count (>= 0: a data row) or the marker -1.0 (a penalty row)
-                const double v = x + uni[buf][R + lane] / rho;
-                zl = uni[buf][lane] < 0.0 ? enet2(v, q.c_hi, q.c_lo, rho) : pois2(v, uni[buf][lane], 1.0 / rho);
-            } else if (PROX == kProxLogitR && uni[buf][lane] == 0.0) {
-                zl = (x + uni[buf][R + lane] / rho) * (rho / (1.0 + rho));
-            } else if (PROX == kProxLogitE && uni[buf][lane] == 0.0) {
-                zl = enet2(x + uni[buf][R + lane] / rho, q.c_hi, q.c_lo, rho);
-            } else if (SIGNED) {
-                // s logit2(s v, t); the sign is read from LDS again behind the iteration, not held in registers across it
-                const double zs = logit2(uni[buf][lane] * (x + uni[buf][R + lane] / rho), PROX == kProxLogitE ? 1.0 / rho : pen_hi);
-                asm volatile("" ::: "memory");
-                zl = uni[buf][lane] * zs;
-            } else zl = prox2<PROX>(x - uni[buf][lane] + uni[buf][R + lane] / rho, pen_hi, pen_lo, delta);
+            if constexpr (SIGNED) zl = row_prox_tagged<PROX>(x + uni[buf][R + lane] / rho, [&] { return uni[buf][lane]; }, q.c_hi, q.c_lo, rho);
+            else zl = prox2<PROX>(x - uni[buf][lane] + uni[buf][R + lane] / rho, pen_hi, pen_lo, delta);
         }
 #pragma unroll
         for (int r = 0; r < R; ++r) {
@@ -680,7 +711,7 @@ lad_rows_kernel(DenseParams q, int par, const double* __restrict__ Xt, long long
         buf ^= 1;
     };
     auto group = [&](int i0, const double2 (&rv)[R][NPT]) {
-        if (prox_is_logit(PROX)) { group_logit(i0, rv); return; }
+        if (kProxKinds[PROX].iterative) { group_logit(i0, rv); return; }
         // the four vectors' entries of the R rows (the same addresses in every lane), requested before the reduction
         double dv[R];
         LadRowIn in[R];
@@ -737,7 +768,7 @@ quant_rows_kernel(DenseParams q0, long long slot_stride, const double* __restric
     // constants and rho.
     // kProxPoisE (admm_hip_poisson): kProxLogitE's indexing with the count matrix in the sign matrix's place; a prox lane whose row
     // carries a count >= 0 forms pois2 with its slot's rho, one whose row carries the marker -1.0 enet2.
-    constexpr bool LOGIT = prox_is_signed(PROX);
+    constexpr bool LOGIT = kProxKinds[PROX].tagged, ENET = kProxKinds[PROX].enet;
     constexpr int NV = LOGIT ? 4 : 3, NB = LOGIT ? 0 : 1;
     constexpr int NU = R * (NB + NV * S);                 // the vectors' entries a row group needs: d | per slot adj_y, adj_z, z   (LOGIT: no d; per slot also the sign)
     static_assert(!LOGIT || S * R <= 64, "one lane per slot and row");
@@ -756,7 +787,7 @@ quant_rows_kernel(DenseParams q0, long long slot_stride, const double* __restric
         cur[s] = (c.total - 1) & 1;
         rho[s] = c.rho;
         const int k = act[s] ? c.pad : 0;                                    // the slot's place in the grid of quantiles
-        if constexpr (prox_is_enet(PROX)) {
+        if constexpr (ENET) {
             col[s] = k % q0.sgn_cols; pen_hi[s] = 0.0; pen_lo[s] = 0.0;
             if ((int)threadIdx.x == s) { spen[0][s] = chi[k]; spen[1][s] = clo[k]; }      // the fit's constants as they are (enet2 divides by its slot's rho), to LDS at once: no slot holds them in registers
         }
@@ -825,20 +856,10 @@ quant_rows_kernel(DenseParams q0, long long slot_stride, const double* __restric
 #pragma unroll
                 for (int w = 1; w < NWV; ++w) x += wsum[buf][ls][w][lr];
                 const double v = x + uni[buf][(NB + NV * ls) * R + lr] / rho_l;
-                // s logit2(s v, t), t = c_hi / rho with c_hi = 1 as the single fit forms it; the sign is read again behind the iteration,
-                // as in lad_rows_kernel
-                if constexpr (PROX == kProxPoisE) {
-                    const double cnt = uni[buf][(NB + 3 + NV * ls) * R + lr];
-                    zl = cnt < 0.0 ? enet2(v, spen[0][ls], spen[1][ls], rho_l) : pois2(v, cnt, 1.0 / rho_l);
-                } else if (PROX == kProxLogitR && uni[buf][(NB + 3 + NV * ls) * R + lr] == 0.0) {
-                    zl = v * (rho_l / (1.0 + rho_l));
-                } else if (PROX == kProxLogitE && uni[buf][(NB + 3 + NV * ls) * R + lr] == 0.0) {
-                    zl = enet2(v, spen[0][ls], spen[1][ls], rho_l);
-                } else {
-                    const double zs = logit2(uni[buf][(NB + 3 + NV * ls) * R + lr] * v, 1.0 / rho_l);
-                    asm volatile("" ::: "memory");
-                    zl = uni[buf][(NB + 3 + NV * ls) * R + lr] * zs;
-                }
+                // the single fit's expressions with the slot's tag, constants and rho, as in lad_rows_kernel
+                const auto tag = [&] { return uni[buf][(NB + 3 + NV * ls) * R + lr]; };
+                if constexpr (ENET) zl = row_prox_tagged<PROX>(v, tag, spen[0][ls], spen[1][ls], rho_l);
+                else zl = row_prox_tagged<PROX>(v, tag, 0.0, 0.0, rho_l);
             }
         }
 #pragma unroll
@@ -908,17 +929,10 @@ dense_tail_kernel(DenseParams q, int par, double knee) {
         if (q.prob == 0) {                        // LAD: x = P_X(vec); z = prox(x - y + adj_y/rho; c_hi/rho, c_lo/rho); r = x - y - z
             x = g;
             const double d = q.data_vec[i];
-            if (PROX == kProxPoisE) {
-                const double cnt = q.sgn[i], v = x - d + adjy / rho;
-                zn = cnt < 0.0 ? enet2(v, q.c_hi, q.c_lo, rho) : pois2(v, cnt, 1.0 / rho);
-            } else if (PROX == kProxLogitR) {
-                const double sg = q.sgn[i], v = x - d + adjy / rho;
-                zn = sg == 0.0 ? v * (rho / (1.0 + rho)) : sg * logit2(sg * v, pen_hi);
-            } else if (PROX == kProxLogitE) {
-                const double sg = q.sgn[i], v = x - d + adjy / rho;
-                zn = sg == 0.0 ? enet2(v, q.c_hi, q.c_lo, rho) : sg * logit2(sg * v, 1.0 / rho);
-            } else if (PROX == kProxLogitS) { const double sg = q.sgn[i]; zn = sg * logit2(sg * (x - d + adjy / rho), pen_hi); }
-            else zn = prox2<PROX>(x - d + adjy / rho, pen_hi, pen_lo, delta);
+            if constexpr (kProxKinds[PROX].tagged) {
+                const double tg = q.sgn[i];
+                zn = row_prox_tagged<PROX>(x - d + adjy / rho, [tg] { return tg; }, q.c_hi, q.c_lo, rho);
+            } else zn = prox2<PROX>(x - d + adjy / rho, pen_hi, pen_lo, delta);
             r = x - d - zn;
         } else {                                  // BP: x = vec + A'(AA')^-1 b - B'(B vec); z = soft(x + adj_y/rho, 1/rho); r = x - z
             x = q.vec[i] + q.data_vec[i] - g;
@@ -947,9 +961,7 @@ __global__ void dense_init_kernel(DenseParams q, double rho) {
     if (i < q.dim) { q.x[i] = 0; q.z0[i] = 0; q.z1[i] = 0; q.y0[i] = 0; q.y1[i] = 0; q.adj_z[i] = 0; q.adj_y[i] = 0; q.vec[i] = 0; }
     if (i < q.nwg_tail * 8) q.P[i] = 0.0;
     if (i == 0) {
-        DenseCtl c;
-        c.rho = rho; c.eps_primal = 0; c.eps_dual = 0; c.adj_a = 1.0; c.adj_c = 9999.0; c.tau = 0.0;
-        c.restart = 0; c.iter = 0; c.done = 0; c.first = 1; c.total = 0; c.niter = 0; c.conv = 0; c.pad = 0;
+        const DenseCtl c = dense_cold_ctl(rho, 0);
         q.ctl[0] = c; q.ctl[1] = c;
         *q.done = 0;
     }
@@ -971,6 +983,19 @@ norm2_kernel(const double* v, int n, double* out) {
 }
 
 namespace {
+
+// Kernel selection: f(std::integral_constant<int, V>) for the V of the compile-time range LO .. HI that equals the runtime v; false
+// if there is none (an empty range included).  Nested over kind, NPT and S with the bounds read from kProxKinds, this instantiates
+// exactly the kernels the table admits.
+template <int LO, int HI, class F>
+bool with_constant(int v, const F& f) {
+    if constexpr (LO > HI) return false;
+    else {
+        if (v != LO) return with_constant<LO + 1, HI>(v, f);
+        f(std::integral_constant<int, LO>{});
+        return true;
+    }
+}
 
 struct DenseLoop {
     DevBuf<double> x, z0, z1, y0, y1, adj_z, adj_y, vec, P;
@@ -1010,13 +1035,10 @@ struct DenseLoop {
         hipLaunchKernelGGL(dense_head_kernel, dim3(nwg_head), dim3(kDenseThreads), (size_t)q.nwg_tail * 8 * sizeof(double), st, q, (int)(g & 1));
     }
     void tail(long long g, hipStream_t st) {
-        if (prox == kProxHuber) hipLaunchKernelGGL(dense_tail_kernel<kProxHuber>, dim3(q.nwg_tail), dim3(kDenseThreads), 0, st, q, (int)(g & 1), delta);
-        else if (prox == kProxLogit) hipLaunchKernelGGL(dense_tail_kernel<kProxLogit>, dim3(q.nwg_tail), dim3(kDenseThreads), 0, st, q, (int)(g & 1), 0.0);
-        else if (prox == kProxLogitS) hipLaunchKernelGGL(dense_tail_kernel<kProxLogitS>, dim3(q.nwg_tail), dim3(kDenseThreads), 0, st, q, (int)(g & 1), 0.0);
-        else if (prox == kProxLogitR) hipLaunchKernelGGL(dense_tail_kernel<kProxLogitR>, dim3(q.nwg_tail), dim3(kDenseThreads), 0, st, q, (int)(g & 1), 0.0);
-        else if (prox == kProxLogitE) hipLaunchKernelGGL(dense_tail_kernel<kProxLogitE>, dim3(q.nwg_tail), dim3(kDenseThreads), 0, st, q, (int)(g & 1), 0.0);
-        else if (prox == kProxPoisE) hipLaunchKernelGGL(dense_tail_kernel<kProxPoisE>, dim3(q.nwg_tail), dim3(kDenseThreads), 0, st, q, (int)(g & 1), 0.0);
-        else hipLaunchKernelGGL(dense_tail_kernel<kProxSoft>, dim3(q.nwg_tail), dim3(kDenseThreads), 0, st, q, (int)(g & 1), 0.0);
+        const bool found = with_constant<0, kProxKindCount - 1>(prox, [&](auto kind) {      // (the knee is read by the Huber instantiation alone)
+            hipLaunchKernelGGL(dense_tail_kernel<decltype(kind)::value>, dim3(q.nwg_tail), dim3(kDenseThreads), 0, st, q, (int)(g & 1), delta);
+        });
+        if (!found) throw Error(ADMM_ERR_INTERNAL, "dense loop: no tail kernel for this prox");
     }
     DenseCtl final_ctl(hipStream_t st) {
         DenseCtl h[2];
@@ -1049,15 +1071,8 @@ static void dense_collect_trace(DenseLoop& L, const DenseCtl& fc, DenseResult& r
 
 namespace {
 
-// columns a thread of the rows kernels holds per row and, by that, how many slots the registers of quant_rows_kernel hold
+// columns a thread of the rows kernels holds per row (kProxKinds' max_slots is indexed by it)
 inline int lad_npt(long long ldxt) { return (int)((ldxt / 2 + kLadThreads - 1) / kLadThreads); }
-inline int quant_max_slots(int npt) { return npt <= 3 ? 4 : (npt == 4 ? 3 : (npt == 5 ? 2 : 1)); }      // (six double2 per row: two slots would spill)
-inline int huber_max_slots(int npt) { return npt <= 3 ? 4 : (npt <= 5 ? 2 : 1); }      // the Huber instantiations without scratch: (4, 3) spills 16 bytes and fell away
-
-inline int logit_max_slots(int npt) { return npt <= 3 ? 4 : (npt == 4 ? 2 : 1); }      // the kProxLogitS instantiations without scratch: (4, 3) spills 64 bytes, (5, 2) 24 (profiles/logit_multi.md)
-inline int logit_ridge_max_slots(int npt) { return npt <= 3 ? 4 : (npt == 4 ? 2 : 1); }      // the kProxLogitR instantiations without scratch: the S form's table (profiles/logit_ridge.md)
-inline int pois_max_slots(int npt) { return npt <= 2 ? 4 : (npt == 3 ? 3 : (npt == 4 ? 2 : 1)); }      // the kProxPoisE instantiations without scratch (profiles/poisson.md)
-inline int logit_enet_max_slots(int npt) { return npt <= 2 ? 4 : (npt == 3 ? 3 : (npt == 4 ? 2 : 1)); }      // the kProxLogitE instantiations without scratch: the R form's table less (3, 4), which spills 16 bytes (profiles/logit_enet.md)
 
 // The separable loss of one fit, as the loop sees it: which prox, its weights above / below zero, and (Huber) the knee in the units
 // of the standardised response.  LAD: the default.
@@ -1071,9 +1086,6 @@ struct LadProx {
                                                // kProxPoisE: the E form's layout with the counts in the signs' place, -1.0 on the penalty rows and the padding
     int ncols = 0;                             // kProxLogitE, kProxPoisE: the label (count) columns of the sign matrix
 };
-inline int prox_max_slots(int kind, int npt) {
-    return kind == kProxHuber ? huber_max_slots(npt) : (kind == kProxLogitS ? logit_max_slots(npt) : (kind == kProxLogitR ? logit_ridge_max_slots(npt) : (kind == kProxLogitE ? logit_enet_max_slots(npt) : (kind == kProxPoisE ? pois_max_slots(npt) : quant_max_slots(npt)))));
-}
 
 // M = G0 + lambda D, D = 1 on the first p0 diagonal entries (the user's columns; the intercept's entry is not shifted): one pass, both
 // ld x ld, padding included
@@ -1181,7 +1193,7 @@ struct LadProblem {
         ADMM_HIP_CHECK(hipStreamSynchronize(st));
 
         // general branch, one-pass form (DenseParams::lp): X streamed once per iteration by rows.  LAD_ONEPASS=0: the reference's two products.
-        constexpr int kLadMaxCols = 2 * kLadThreads * 6;             // 6144 columns: six double2 per thread and row (more would spill)
+        constexpr int kLadMaxCols = 2 * kLadThreads * kLadMaxNpt;            // 6144 columns: six double2 per thread and row (more would spill)
         onepass = !hat && p <= kLadMaxCols;
         if (opt_off(Opt::LAD_ONEPASS)) onepass = false;
         lad_nwg = std::max(1, std::min(device_info().num_cu, (n + 2 * kLadRows - 1) / (2 * kLadRows)));
@@ -1239,12 +1251,12 @@ struct LadProblem {
         DenseLoop L;
         L.init(n, 0, opts, d.Y.get(), ynorm, st, res.trace_cap, res.state_cap, onepass ? lad_nwg : 0);
         L.q.c_hi = px.c_hi; L.q.c_lo = px.c_lo; L.delta = px.delta; L.prox = px.kind;
-        if (prox_is_signed(px.kind)) L.q.sgn = px.signs;
+        if (kProxKinds[px.kind].tagged) L.q.sgn = px.signs;
         if (px.kind == kProxHuber && res.state_cap > 0) {       // iterate dump: record 0 also carries the knee as the loop holds it (delta / scaleY), first entry of its z slot
             ADMM_HIP_CHECK(hipMemcpyAsync(L.state.get() + n, &px.delta, sizeof(double), hipMemcpyHostToDevice, st));
             ADMM_HIP_CHECK(hipStreamSynchronize(st));
         }
-        if ((px.kind == kProxLogit || px.kind == kProxLogitR || prox_is_enet(px.kind)) && res.state_cap > 0)      // the same for the logistic fit: the n signs the loop ran with fill record 0's z slot (ridge rows: 0.0; kProxPoisE: the counts, penalty rows -1.0)
+        if ((px.kind == kProxLogit || px.kind == kProxLogitR || kProxKinds[px.kind].enet) && res.state_cap > 0)      // the same for the logistic fit: the n signs the loop ran with fill record 0's z slot (ridge rows: 0.0; kProxPoisE: the counts, penalty rows -1.0)
             ADMM_HIP_CHECK(hipMemcpyAsync(L.state.get() + n, px.signs, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, st));
         if (hat) { L.q.gout = gH.part.get(); L.q.gout_nseg = gH.pl.nseg; L.q.gout_stride = gH.stride; }
         else if (!onepass) { L.q.gout = g3.part.get(); L.q.gout_nseg = g3.pl.nseg; L.q.gout_stride = g3.stride; }
@@ -1257,53 +1269,14 @@ struct LadProblem {
         }
         auto launch_rows = [&](long long g) {
             const int par = (int)(g & 1);
-#define ADMM_LAD_ROWS(N, PX) hipLaunchKernelGGL((lad_rows_kernel<N, PX>), dim3(lad_nwg), dim3(kLadThreads), 0, st, L.q, par, Xt.get(), ldxt, g2.part.get(), g2.pl.nseg, g2.stride, cpart.get(), lad_rows, px.delta)
-            switch (std::min(lad_npt(ldxt), 6) * 8 + px.kind) {
-                case 8: ADMM_LAD_ROWS(1, kProxSoft); break;
-                case 9: ADMM_LAD_ROWS(1, kProxHuber); break;
-                case 10: ADMM_LAD_ROWS(1, kProxLogit); break;
-                case 11: ADMM_LAD_ROWS(1, kProxLogitS); break;
-                case 12: ADMM_LAD_ROWS(1, kProxLogitR); break;
-                case 13: ADMM_LAD_ROWS(1, kProxLogitE); break;
-                case 14: ADMM_LAD_ROWS(1, kProxPoisE); break;
-                case 16: ADMM_LAD_ROWS(2, kProxSoft); break;
-                case 17: ADMM_LAD_ROWS(2, kProxHuber); break;
-                case 18: ADMM_LAD_ROWS(2, kProxLogit); break;
-                case 19: ADMM_LAD_ROWS(2, kProxLogitS); break;
-                case 20: ADMM_LAD_ROWS(2, kProxLogitR); break;
-                case 21: ADMM_LAD_ROWS(2, kProxLogitE); break;
-                case 22: ADMM_LAD_ROWS(2, kProxPoisE); break;
-                case 24: ADMM_LAD_ROWS(3, kProxSoft); break;
-                case 25: ADMM_LAD_ROWS(3, kProxHuber); break;
-                case 26: ADMM_LAD_ROWS(3, kProxLogit); break;
-                case 27: ADMM_LAD_ROWS(3, kProxLogitS); break;
-                case 28: ADMM_LAD_ROWS(3, kProxLogitR); break;
-                case 29: ADMM_LAD_ROWS(3, kProxLogitE); break;
-                case 30: ADMM_LAD_ROWS(3, kProxPoisE); break;
-                case 32: ADMM_LAD_ROWS(4, kProxSoft); break;
-                case 33: ADMM_LAD_ROWS(4, kProxHuber); break;
-                case 34: ADMM_LAD_ROWS(4, kProxLogit); break;
-                case 35: ADMM_LAD_ROWS(4, kProxLogitS); break;
-                case 36: ADMM_LAD_ROWS(4, kProxLogitR); break;
-                case 37: ADMM_LAD_ROWS(4, kProxLogitE); break;
-                case 38: ADMM_LAD_ROWS(4, kProxPoisE); break;
-                case 40: ADMM_LAD_ROWS(5, kProxSoft); break;
-                case 41: ADMM_LAD_ROWS(5, kProxHuber); break;
-                case 42: ADMM_LAD_ROWS(5, kProxLogit); break;
-                case 43: ADMM_LAD_ROWS(5, kProxLogitS); break;
-                case 44: ADMM_LAD_ROWS(5, kProxLogitR); break;
-                case 45: ADMM_LAD_ROWS(5, kProxLogitE); break;
-                case 46: ADMM_LAD_ROWS(5, kProxPoisE); break;
-                case 48: ADMM_LAD_ROWS(6, kProxSoft); break;
-                case 49: ADMM_LAD_ROWS(6, kProxHuber); break;
-                case 50: ADMM_LAD_ROWS(6, kProxLogit); break;
-                case 51: ADMM_LAD_ROWS(6, kProxLogitS); break;
-                case 52: ADMM_LAD_ROWS(6, kProxLogitR); break;
-                case 53: ADMM_LAD_ROWS(6, kProxLogitE); break;
-                case 54: ADMM_LAD_ROWS(6, kProxPoisE); break;
-                default: throw Error(ADMM_ERR_INTERNAL, "one-pass loop: no rows kernel for this prox");
-            }
-#undef ADMM_LAD_ROWS
+            bool found = false;
+            with_constant<0, kProxKindCount - 1>(px.kind, [&](auto kind) {
+                found = with_constant<1, kLadMaxNpt>(std::min(lad_npt(ldxt), kLadMaxNpt), [&](auto npt) {
+                    hipLaunchKernelGGL((lad_rows_kernel<decltype(npt)::value, decltype(kind)::value>), dim3(lad_nwg), dim3(kLadThreads), 0, st, L.q, par, Xt.get(), ldxt,
+                                       g2.part.get(), g2.pl.nseg, g2.stride, cpart.get(), lad_rows, px.delta);
+                });
+            });
+            if (!found) throw Error(ADMM_ERR_INTERNAL, "one-pass loop: no rows kernel for this prox");
         };
 
         const int* skip = L.done.get();
@@ -1356,12 +1329,7 @@ struct LadProblem {
         std::vector<int> hi(3 + nslots + ntau, 0);
         hi[1] = hi[2] = nslots;                                  // slots 0 .. S-1 start with the first S quantiles
         std::vector<DenseCtl> hc(2 * (size_t)nslots);
-        for (int s = 0; s < nslots; ++s) {
-            DenseCtl c;
-            c.rho = opts.rho; c.eps_primal = 0; c.eps_dual = 0; c.adj_a = 1.0; c.adj_c = 9999.0; c.tau = 0.0;
-            c.restart = 0; c.iter = 0; c.done = 0; c.first = 1; c.total = 0; c.niter = 0; c.conv = 0; c.pad = s;
-            hc[2 * s] = hc[2 * s + 1] = c;
-        }
+        for (int s = 0; s < nslots; ++s) hc[2 * s] = hc[2 * s + 1] = dense_cold_ctl(opts.rho, s);
         DenseParams q{};
         double* b = pool.get();
         q.dim = n; q.prob = 0; q.maxit = opts.maxit; q.nwg_tail = lad_nwg;
@@ -1372,11 +1340,11 @@ struct LadProblem {
         q.lp = p; q.Xd = Xd.get(); q.Xz0 = b + o_p; q.Xz1 = b + o_p + ldp; q.Xy0 = b + o_p + 2 * ldp; q.Xy1 = b + o_p + 3 * ldp; q.u = b + o_p + 4 * ldp;
         q.cpart = b + o_c; q.cnwg = lad_nwg; q.cstride = ldp;
         q.c_hi = 1.0; q.c_lo = 1.0;                              // (unused: the slots' constants are chi / clo of their quantile)
-        if (prox_is_signed(kind)) q.sgn = fits[0].signs;         // the sign matrix: a slot reads the column of the fit it holds
-        q.sgn_cols = prox_is_enet(kind) ? fits[0].ncols : 0;
+        if (kProxKinds[kind].tagged) q.sgn = fits[0].signs;         // the sign matrix: a slot reads the column of the fit it holds
+        q.sgn_cols = kProxKinds[kind].enet ? fits[0].ncols : 0;
         DevBuf<double> zpen_d;
         QuantGridZ G{};
-        if (prox_is_enet(kind)) {
+        if (kProxKinds[kind].enet) {
             zpen_d.alloc((size_t)ntau * ridge_p0); zpen_d.zero(st);
             G.zpen = zpen_d.get(); G.zrow0 = n0; G.zrows = ridge_p0;
         }
@@ -1400,78 +1368,22 @@ struct LadProblem {
         const double* spart0 = b + o_g;
         double* cpart0 = b + o_c;
         auto launch_rows = [&](int par) {
-#define ADMM_QUANT_ROWS(N, SS, PX) hipLaunchKernelGGL((quant_rows_kernel<N, SS, PX>), dim3(lad_nwg), dim3(kLadThreads), 0, st, q, (long long)stride, chi_d.get(), clo_d.get(), par, \
-                                                      Xt.get(), ldxt, spart0, g2.pl.nseg, g2.stride, cpart0, lad_rows, (const double*)dlt_d.get())
-            switch ((kind == kProxHuber ? 100 : (kind == kProxLogitS ? 200 : (kind == kProxLogitR ? 300 : (kind == kProxLogitE ? 400 : (kind == kProxPoisE ? 500 : 0))))) + lad_npt(ldxt) * 10 + nslots) {
-                case 12: ADMM_QUANT_ROWS(1, 2, kProxSoft); break;
-                case 13: ADMM_QUANT_ROWS(1, 3, kProxSoft); break;
-                case 14: ADMM_QUANT_ROWS(1, 4, kProxSoft); break;
-                case 22: ADMM_QUANT_ROWS(2, 2, kProxSoft); break;
-                case 23: ADMM_QUANT_ROWS(2, 3, kProxSoft); break;
-                case 24: ADMM_QUANT_ROWS(2, 4, kProxSoft); break;
-                case 32: ADMM_QUANT_ROWS(3, 2, kProxSoft); break;
-                case 33: ADMM_QUANT_ROWS(3, 3, kProxSoft); break;
-                case 34: ADMM_QUANT_ROWS(3, 4, kProxSoft); break;
-                case 42: ADMM_QUANT_ROWS(4, 2, kProxSoft); break;
-                case 43: ADMM_QUANT_ROWS(4, 3, kProxSoft); break;
-                case 52: ADMM_QUANT_ROWS(5, 2, kProxSoft); break;
-                case 112: ADMM_QUANT_ROWS(1, 2, kProxHuber); break;
-                case 113: ADMM_QUANT_ROWS(1, 3, kProxHuber); break;
-                case 114: ADMM_QUANT_ROWS(1, 4, kProxHuber); break;
-                case 122: ADMM_QUANT_ROWS(2, 2, kProxHuber); break;
-                case 123: ADMM_QUANT_ROWS(2, 3, kProxHuber); break;
-                case 124: ADMM_QUANT_ROWS(2, 4, kProxHuber); break;
-                case 132: ADMM_QUANT_ROWS(3, 2, kProxHuber); break;
-                case 133: ADMM_QUANT_ROWS(3, 3, kProxHuber); break;
-                case 134: ADMM_QUANT_ROWS(3, 4, kProxHuber); break;
-                case 142: ADMM_QUANT_ROWS(4, 2, kProxHuber); break;
-                case 152: ADMM_QUANT_ROWS(5, 2, kProxHuber); break;
-                case 212: ADMM_QUANT_ROWS(1, 2, kProxLogitS); break;
-                case 213: ADMM_QUANT_ROWS(1, 3, kProxLogitS); break;
-                case 214: ADMM_QUANT_ROWS(1, 4, kProxLogitS); break;
-                case 222: ADMM_QUANT_ROWS(2, 2, kProxLogitS); break;
-                case 223: ADMM_QUANT_ROWS(2, 3, kProxLogitS); break;
-                case 224: ADMM_QUANT_ROWS(2, 4, kProxLogitS); break;
-                case 232: ADMM_QUANT_ROWS(3, 2, kProxLogitS); break;
-                case 233: ADMM_QUANT_ROWS(3, 3, kProxLogitS); break;
-                case 234: ADMM_QUANT_ROWS(3, 4, kProxLogitS); break;
-                case 242: ADMM_QUANT_ROWS(4, 2, kProxLogitS); break;
-                case 312: ADMM_QUANT_ROWS(1, 2, kProxLogitR); break;
-                case 313: ADMM_QUANT_ROWS(1, 3, kProxLogitR); break;
-                case 314: ADMM_QUANT_ROWS(1, 4, kProxLogitR); break;
-                case 322: ADMM_QUANT_ROWS(2, 2, kProxLogitR); break;
-                case 323: ADMM_QUANT_ROWS(2, 3, kProxLogitR); break;
-                case 324: ADMM_QUANT_ROWS(2, 4, kProxLogitR); break;
-                case 332: ADMM_QUANT_ROWS(3, 2, kProxLogitR); break;
-                case 333: ADMM_QUANT_ROWS(3, 3, kProxLogitR); break;
-                case 334: ADMM_QUANT_ROWS(3, 4, kProxLogitR); break;
-                case 342: ADMM_QUANT_ROWS(4, 2, kProxLogitR); break;
-                case 412: ADMM_QUANT_ROWS(1, 2, kProxLogitE); break;
-                case 413: ADMM_QUANT_ROWS(1, 3, kProxLogitE); break;
-                case 414: ADMM_QUANT_ROWS(1, 4, kProxLogitE); break;
-                case 422: ADMM_QUANT_ROWS(2, 2, kProxLogitE); break;
-                case 423: ADMM_QUANT_ROWS(2, 3, kProxLogitE); break;
-                case 424: ADMM_QUANT_ROWS(2, 4, kProxLogitE); break;
-                case 432: ADMM_QUANT_ROWS(3, 2, kProxLogitE); break;
-                case 433: ADMM_QUANT_ROWS(3, 3, kProxLogitE); break;
-                case 442: ADMM_QUANT_ROWS(4, 2, kProxLogitE); break;
-                case 512: ADMM_QUANT_ROWS(1, 2, kProxPoisE); break;
-                case 513: ADMM_QUANT_ROWS(1, 3, kProxPoisE); break;
-                case 514: ADMM_QUANT_ROWS(1, 4, kProxPoisE); break;
-                case 522: ADMM_QUANT_ROWS(2, 2, kProxPoisE); break;
-                case 523: ADMM_QUANT_ROWS(2, 3, kProxPoisE); break;
-                case 524: ADMM_QUANT_ROWS(2, 4, kProxPoisE); break;
-                case 532: ADMM_QUANT_ROWS(3, 2, kProxPoisE); break;
-                case 533: ADMM_QUANT_ROWS(3, 3, kProxPoisE); break;
-                case 542: ADMM_QUANT_ROWS(4, 2, kProxPoisE); break;
-                default: throw Error(ADMM_ERR_INTERNAL, "slotted grid: no rows kernel for this layout");
-            }
-#undef ADMM_QUANT_ROWS
+            bool found = false;
+            with_constant<0, kProxKindCount - 1>(kind, [&](auto kc) {
+                with_constant<1, kLadMaxNpt>(lad_npt(ldxt), [&](auto npt) {
+                    constexpr int K = decltype(kc)::value, N = decltype(npt)::value;
+                    found = with_constant<2, kProxKinds[K].max_slots[N - 1]>(nslots, [&](auto ns) {
+                        hipLaunchKernelGGL((quant_rows_kernel<N, decltype(ns)::value, K>), dim3(lad_nwg), dim3(kLadThreads), 0, st, q, (long long)stride, chi_d.get(), clo_d.get(), par,
+                                           Xt.get(), ldxt, spart0, g2.pl.nseg, g2.stride, cpart0, lad_rows, (const double*)dlt_d.get());
+                    });
+                });
+            });
+            if (!found) throw Error(ADMM_ERR_INTERNAL, "slotted grid: no rows kernel for this layout");
         };
         const long long bound = (long long)ntau * ((long long)opts.maxit + 2);      // (all quantiles through one slot)
         LoopTimes lt = run_until_done(st, (const int*)ints.get(), batch_iters((int)opt_int(Opt::BATCH_ITERS, 0), 8), bound, [&](long long g) {
             const int par = (int)(g & 1);
-            if (prox_is_enet(kind)) hipLaunchKernelGGL(quant_head_kernel<QuantGridZ>, dim3(nwg_head, nslots), dim3(kDenseThreads), (size_t)lad_nwg * 8 * sizeof(double), st, q, G, par);
+            if (kProxKinds[kind].enet) hipLaunchKernelGGL(quant_head_kernel<QuantGridZ>, dim3(nwg_head, nslots), dim3(kDenseThreads), (size_t)lad_nwg * 8 * sizeof(double), st, q, G, par);
             else hipLaunchKernelGGL(quant_head_kernel<QuantGrid>, dim3(nwg_head, nslots), dim3(kDenseThreads), (size_t)lad_nwg * 8 * sizeof(double), st, q, (QuantGrid)G, par);
             launch_gemv_t_batch<double>(batch.get(), nslots, g2.pl.grid, g2.pl.lds_bytes, g2.pl.nt, st);
             launch_rows(par);
@@ -1562,16 +1474,15 @@ static void run_lad_fits(LadProblem& P, DeviceData<double>& d, int p0, bool inte
     int slots = 1;
     if (P.onepass && dr.trace_cap == 0 && ntau >= 2) {
         const long long want = opt_int(Opt::QUANT_SLOTS, 0);
-        const int kind = fits[0].kind;
-        slots = want == 0 ? (kind == kProxHuber ? kHuberAutoSlots : (kind == kProxLogitS ? kLogitAutoSlots : (kind == kProxLogitR ? kLogitRidgeAutoSlots : (kind == kProxLogitE ? kLogitEnetAutoSlots : (kind == kProxPoisE ? kPoissonAutoSlots : kQuantAutoSlots))))) : (int)want;
-        slots = std::min(std::min(slots, prox_max_slots(fits[0].kind, lad_npt(P.ldxt))), ntau);
+        const ProxKind& K = kProxKinds[fits[0].kind];
+        slots = std::min(std::min(want == 0 ? K.auto_slots : (int)want, K.max_slots[lad_npt(P.ldxt) - 1]), ntau);
         if ((size_t)ntau * (size_t)n * sizeof(double) > (size_t(2) << 30)) slots = 1;
     }
     std::vector<double> coef((size_t)ntau * p);
     res.niter.assign(ntau, 0);
     // kProxLogitE / kProxPoisE: the penalised coefficients are read from the penalty rows of the last z (exact zeros), b_j = z_{n0 + j} / c with c the
     // rows' scale sqrt(n0); get_x keeps only the intercept's entry
-    const bool enet = prox_is_enet(fits[0].kind);
+    const bool enet = kProxKinds[fits[0].kind].enet;
     std::vector<double> zpen(enet ? (size_t)ntau * p0 : 0);
     if (slots >= 2) {
         P.loop_slots(slots, fits, dr.stats, res.niter.data(), coef.data(), enet ? zpen.data() : nullptr);
@@ -1706,6 +1617,21 @@ void solve_logit_multi(DeviceData<double>& d, bool intercept, const double* y_de
     solve_lad_grid(d, intercept, opts, fits, res, st);
 }
 
+// What the fits with penalty rows share ahead of their setup: the ones column, the p0 zero rows behind the data, the tag matrix (signs or
+// counts: `tags` writes column c of the n0 x ncol labels with leading dimension round_up(d.n, 32) and its own filler behind them), and
+// a response that is no scale.  Returns the tag matrix.
+using TagMatrixKernel = void (*)(const double*, int, int, long long, double*);
+static DevBuf<double> augment_tagged(DeviceData<double>& d, bool intercept, const double* y_dev, int ncol, TagMatrixKernel tags, hipStream_t st) {
+    const int n0 = d.n, p0 = d.p;
+    if (intercept) append_ones_column(d, st);
+    append_ridge_rows(d, p0, st);
+    const long long lds = round_up(d.n, 32);
+    DevBuf<double> tag((size_t)lds * ncol);
+    hipLaunchKernelGGL(tags, dim3((unsigned)((lds + 255) / 256), std::min(ncol, 65535)), dim3(256), 0, st, y_dev, n0, ncol, lds, tag.get());
+    d.scaleY = 1.0; d.meanY = 0.0;
+    return tag;
+}
+
 // Ridge logistic regression (admm_hip_logit_ridge): sum log(1 + exp(-s_i (b0 + x_i'b))) + lambda / 2 sum b_j^2 per label column and
 // lambda, b on the standardised scale, the intercept not penalised.  The penalty is not written on b -- the x-update's matrix would be
 // X'X + (lambda / rho) D and change with rho -- but as p0 more ROWS sqrt(lambda) e_j' with a zero response and the loss z^2 / 2: the Gram
@@ -1717,12 +1643,8 @@ void solve_logit_multi(DeviceData<double>& d, bool intercept, const double* y_de
 void solve_logit_ridge(DeviceData<double>& d, bool intercept, const double* y_dev, int ncol, const double* lambda, int nlambda, const admm_opts& opts, QuantResult& res,
                        hipStream_t st) {
     const int n0 = d.n, p0 = d.p;
-    if (intercept) append_ones_column(d, st);
-    append_ridge_rows(d, p0, st);
+    const DevBuf<double> sgn = augment_tagged(d, intercept, y_dev, ncol, logit_sign_matrix_kernel, st);
     const long long lds = round_up(d.n, 32);
-    DevBuf<double> sgn((size_t)lds * ncol);
-    hipLaunchKernelGGL(logit_sign_matrix_kernel, dim3((unsigned)((lds + 255) / 256), std::min(ncol, 65535)), dim3(256), 0, st, y_dev, n0, ncol, lds, sgn.get());
-    d.scaleY = 1.0; d.meanY = 0.0;
     std::vector<LadProx> fits(ncol);
     for (int k = 0; k < ncol; ++k) { fits[k].kind = kProxLogitR; fits[k].signs = sgn.get() + (size_t)k * lds; }
     LadProblem P(d, opts, st);
@@ -1754,22 +1676,19 @@ void solve_logit_ridge(DeviceData<double>& d, bool intercept, const double* y_de
 // whole grid.  c^2 = n0, the squared norm of a standardised column: with unit rows the loop needs hundreds to thousands of iterations,
 // with c = sqrt(n0) 18 - 66 (tests/test_logit_enet_host.py).  Returned: the penalty rows of the last z over c (exact zeros), the
 // intercept from get_x (run_lad_fits).  res.beta: (p + 1) x ncol x ncell, res.niter: ncol x ncell.
-void solve_logit_enet(DeviceData<double>& d, bool intercept, const double* y_dev, int ncol, const double* lambda, const double* alpha, int ncell, const admm_opts& opts,
-                      QuantResult& res, hipStream_t st) {
+// (solve_poisson is the same function with another kind and another tag matrix: solve_enet_rows.)
+static void solve_enet_rows(int kind, TagMatrixKernel tags, DeviceData<double>& d, bool intercept, const double* y_dev, int ncol, const double* lambda, const double* alpha,
+                            int ncell, const admm_opts& opts, QuantResult& res, hipStream_t st) {
     const int n0 = d.n, p0 = d.p;
-    if (intercept) append_ones_column(d, st);
-    append_ridge_rows(d, p0, st);
+    const DevBuf<double> tag = augment_tagged(d, intercept, y_dev, ncol, tags, st);
     const long long lds = round_up(d.n, 32);
-    DevBuf<double> sgn((size_t)lds * ncol);
-    hipLaunchKernelGGL(logit_sign_matrix_kernel, dim3((unsigned)((lds + 255) / 256), std::min(ncol, 65535)), dim3(256), 0, st, y_dev, n0, ncol, lds, sgn.get());
-    d.scaleY = 1.0; d.meanY = 0.0;
     const double c2 = (double)n0, c = std::sqrt(c2);
     std::vector<LadProx> fits((size_t)ncol * ncell);
     for (int l = 0; l < ncell; ++l)
         for (int k = 0; k < ncol; ++k) {
             LadProx& f = fits[(size_t)l * ncol + k];
-            f.kind = kProxLogitE; f.ncols = ncol;
-            f.signs = sgn.get() + (size_t)k * lds;
+            f.kind = kind; f.ncols = ncol;
+            f.signs = tag.get() + (size_t)k * lds;
             f.c_hi = lambda[l] * alpha[l] / c;
             f.c_lo = lambda[l] * (1.0 - alpha[l]) / c2;
         }
@@ -1777,6 +1696,10 @@ void solve_logit_enet(DeviceData<double>& d, bool intercept, const double* y_dev
     P.setup_ridge(n0, p0, res.dense.stats);
     P.setup_lambda(c2, res.dense.stats);
     run_lad_fits(P, d, p0, intercept, fits, res);
+}
+void solve_logit_enet(DeviceData<double>& d, bool intercept, const double* y_dev, int ncol, const double* lambda, const double* alpha, int ncell, const admm_opts& opts,
+                      QuantResult& res, hipStream_t st) {
+    solve_enet_rows(kProxLogitE, logit_sign_matrix_kernel, d, intercept, y_dev, ncol, lambda, alpha, ncell, opts, res, st);
 }
 
 // lambda_1 of admm_hip_logit_enet_lambda_max: per label column max_j |x~_j'r|, r = y - mean(y) (mean[c] = 0.5 without the intercept)
@@ -1871,27 +1794,7 @@ __global__ void __launch_bounds__(256) pois_count_matrix_kernel(const double* __
 // constants are 0 and a penalty row's prox is the identity -- the plain Poisson GLM on the same inverse.
 void solve_poisson(DeviceData<double>& d, bool intercept, const double* y_dev, int ncol, const double* lambda, const double* alpha, int ncell, const admm_opts& opts,
                    QuantResult& res, hipStream_t st) {
-    const int n0 = d.n, p0 = d.p;
-    if (intercept) append_ones_column(d, st);
-    append_ridge_rows(d, p0, st);
-    const long long lds = round_up(d.n, 32);
-    DevBuf<double> cnt((size_t)lds * ncol);
-    hipLaunchKernelGGL(pois_count_matrix_kernel, dim3((unsigned)((lds + 255) / 256), std::min(ncol, 65535)), dim3(256), 0, st, y_dev, n0, ncol, lds, cnt.get());
-    d.scaleY = 1.0; d.meanY = 0.0;
-    const double c2 = (double)n0, c = std::sqrt(c2);
-    std::vector<LadProx> fits((size_t)ncol * ncell);
-    for (int l = 0; l < ncell; ++l)
-        for (int k = 0; k < ncol; ++k) {
-            LadProx& f = fits[(size_t)l * ncol + k];
-            f.kind = kProxPoisE; f.ncols = ncol;
-            f.signs = cnt.get() + (size_t)k * lds;
-            f.c_hi = lambda[l] * alpha[l] / c;
-            f.c_lo = lambda[l] * (1.0 - alpha[l]) / c2;
-        }
-    LadProblem P(d, opts, st);
-    P.setup_ridge(n0, p0, res.dense.stats);
-    P.setup_lambda(c2, res.dense.stats);
-    run_lad_fits(P, d, p0, intercept, fits, res);
+    solve_enet_rows(kProxPoisE, pois_count_matrix_kernel, d, intercept, y_dev, ncol, lambda, alpha, ncell, opts, res, st);
 }
 
 __global__ void __launch_bounds__(256) pois_prox_hook_kernel(const double* __restrict__ v, const double* __restrict__ y, long long m, double t, double* __restrict__ out) {

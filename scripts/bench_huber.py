@@ -85,7 +85,7 @@ def grid(slots, maxit, eps):
 
 
 npt = ((p + 31) // 32 * 32 // 2 + 511) // 512
-max_slots = 4 if npt <= 3 else (2 if npt <= 5 else 1)      # huber_max_slots (fadmm_dense.hip)
+max_slots = 4 if npt <= 3 else (2 if npt <= 5 else 1)      # kProxKinds[kProxHuber].max_slots (fadmm_dense.hip)
 routes = [1] + list(range(2, min(max_slots, len(GRID)) + 1))
 
 rates = lad_rates(args.repeats)

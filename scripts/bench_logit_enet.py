@@ -39,7 +39,7 @@ import torch  # noqa: E402  (before libadmm_hip)
 from admm_amd import DevicePtr, admm_logit_enet, admm_logit_ridge, options  # noqa: E402
 
 dev = torch.device("cuda", 0)
-ENET_MAX_SLOTS = {1: 4, 2: 4, 3: 3, 4: 2, 5: 1, 6: 1}      # fadmm_dense.hip, logit_enet_max_slots
+ENET_MAX_SLOTS = {1: 4, 2: 4, 3: 3, 4: 2, 5: 1, 6: 1}      # fadmm_dense.hip, kProxKinds[kProxLogitE].max_slots
 FRACTIONS = (0.5, 0.3, 0.2, 0.1, 0.05)
 RIDGE_GRID = (100.0, 10.0, 1.0, 0.1, 0.01)
 

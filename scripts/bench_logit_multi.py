@@ -45,7 +45,7 @@ from admm_amd import DevicePtr, admm_huber, admm_logit, options  # noqa: E402
 
 assert os.path.dirname(os.path.dirname(os.path.abspath(admm_amd.__file__))) == TREE, admm_amd.__file__
 dev = torch.device("cuda", 0)
-LOGIT_MAX_SLOTS = {1: 4, 2: 4, 3: 4, 4: 2, 5: 1, 6: 1}      # fadmm_dense.hip, logit_max_slots
+LOGIT_MAX_SLOTS = {1: 4, 2: 4, 3: 4, 4: 2, 5: 1, 6: 1}      # fadmm_dense.hip, kProxKinds[kProxLogitS].max_slots
 
 
 def make(p):

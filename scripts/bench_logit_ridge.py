@@ -36,7 +36,7 @@ import torch  # noqa: E402  (before libadmm_hip)
 from admm_amd import DevicePtr, admm_logit_multi, admm_logit_ridge, options  # noqa: E402
 
 dev = torch.device("cuda", 0)
-RIDGE_MAX_SLOTS = {1: 4, 2: 4, 3: 4, 4: 2, 5: 1, 6: 1}      # fadmm_dense.hip, logit_ridge_max_slots
+RIDGE_MAX_SLOTS = {1: 4, 2: 4, 3: 4, 4: 2, 5: 1, 6: 1}      # fadmm_dense.hip, kProxKinds[kProxLogitR].max_slots
 GRID = (100.0, 10.0, 1.0, 0.1, 0.01)
 
 

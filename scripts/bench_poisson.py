@@ -42,7 +42,7 @@ import torch  # noqa: E402  (before libadmm_hip)
 from admm_amd import DevicePtr, admm_poisson, options  # noqa: E402
 
 dev = torch.device("cuda", 0)
-POIS_MAX_SLOTS = {1: 4, 2: 4, 3: 3, 4: 2, 5: 1, 6: 1}      # fadmm_dense.hip, pois_max_slots
+POIS_MAX_SLOTS = {1: 4, 2: 4, 3: 3, 4: 2, 5: 1, 6: 1}      # fadmm_dense.hip, kProxKinds[kProxPoisE].max_slots
 FRACTIONS = (0.5, 0.3, 0.2, 0.1, 0.05)
 
 

@@ -25,7 +25,7 @@ _cache = {}
 
 
 def huber_max_slots(cols):
-    """The Huber instantiations of quant_rows_kernel that compile without scratch (fadmm_dense.hip, huber_max_slots): by the double2
+    """The Huber instantiations of quant_rows_kernel that compile without scratch (fadmm_dense.hip, kProxKinds[kProxHuber].max_slots): by the double2
     a thread holds per row, 4 slots up to 3, 2 up to 5 (3 at 4 spilled and fell away), none beside the first at 6."""
     npt = ((cols + 31) // 32 * 32 // 2 + 511) // 512
     return 4 if npt <= 3 else (2 if npt <= 5 else 1)

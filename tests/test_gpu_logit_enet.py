@@ -33,8 +33,8 @@ pytestmark = pytest.mark.gpu
 
 INVALID_ARG = 1
 F = 0.3                                                     # the one cell: lambda = F lambda_1, alpha = 1
-MAX_SLOTS = {1: 4, 2: 4, 3: 3, 4: 2, 5: 1, 6: 1}            # logit_enet_max_slots: by the double2 a thread holds per row (profiles/logit_enet.md)
-AUTO_SLOTS = 4                                              # kLogitEnetAutoSlots: as many as the layout admits
+MAX_SLOTS = {1: 4, 2: 4, 3: 3, 4: 2, 5: 1, 6: 1}            # kProxKinds[kProxLogitE].max_slots: by the double2 a thread holds per row (profiles/logit_enet.md)
+AUTO_SLOTS = 4                                              # kProxKinds[kProxLogitE].auto_slots: as many as the layout admits
 LAMBDA_ONE_RTOL = 1e-12
 
 _cache = {}
@@ -136,7 +136,7 @@ def test_slots_are_byte_identical_to_the_serial_route(slots):
 
 
 def test_the_automatic_slot_choice():
-    """QUANT_SLOTS unset: kLogitEnetAutoSlots (profiles/logit_enet.md), clipped to the layout's table and to the number of fits."""
+    """QUANT_SLOTS unset: kProxLogitE's auto_slots (profiles/logit_enet.md), clipped to the layout's table and to the number of fits."""
     n, p, seed, _ = BRANCHES["onepass"]
     x, Y = problem(n, p, seed)
     lam, alpha = _grid(x, Y)
@@ -158,7 +158,7 @@ def _layout_cases():
 
 @pytest.mark.parametrize("n,p,maxit,want", list(_layout_cases()))
 def test_slots_on_every_register_layout(n, p, maxit, want):
-    """Five label columns at one cell.  Asking for more than logit_enet_max_slots admits is clipped to it (4 at three double2 per thread
+    """Five label columns at one cell.  Asking for more than the kind's max_slots row admits is clipped to it (4 at three double2 per thread
     and row runs 3); five and six double2 leave the form no second slot: serial."""
     x, Y = _layout_problem(n, p)
     lam = F * float(le.lambda_one(x, Y, True).max())

@@ -25,7 +25,7 @@ from test_logit_multi_host import problem
 pytestmark = pytest.mark.gpu
 
 INVALID_ARG = 1
-MAX_SLOTS = {1: 4, 2: 4, 3: 4, 4: 2, 5: 1, 6: 1}         # logit_max_slots: by the double2 a thread holds per row
+MAX_SLOTS = {1: 4, 2: 4, 3: 4, 4: 2, 5: 1, 6: 1}         # kProxKinds[kProxLogitS].max_slots: by the double2 a thread holds per row
 
 _cache = {}
 

@@ -126,7 +126,7 @@ def test_automatic_takes_as_many_slots_as_the_layout_admits():
 
 def _layout_cases():
     for n, p, maxit in LAYOUTS:
-        top = MAX_SLOTS[_npt(p)]                                  # logit_ridge_max_slots is the S form's table
+        top = MAX_SLOTS[_npt(p)]                                  # kProxLogitR's max_slots row is the S form's
         for want in sorted({max(top, 2), 2}, reverse=True):
             yield pytest.param(n, p, maxit, want, id=f"{n}x{p}-slots{want}")
 

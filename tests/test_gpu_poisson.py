@@ -31,8 +31,8 @@ pytestmark = pytest.mark.gpu
 
 INVALID_ARG = 1
 F = 0.3                                                     # the one cell: lambda = F lambda_1, alpha = 1
-MAX_SLOTS = {1: 4, 2: 4, 3: 3, 4: 2, 5: 1, 6: 1}            # pois_max_slots: by the double2 a thread holds per row (profiles/poisson.md)
-AUTO_SLOTS = 4                                              # kPoissonAutoSlots: as many as the layout admits (profiles/poisson.md)
+MAX_SLOTS = {1: 4, 2: 4, 3: 3, 4: 2, 5: 1, 6: 1}            # kProxKinds[kProxPoisE].max_slots: by the double2 a thread holds per row (profiles/poisson.md)
+AUTO_SLOTS = 4                                              # kProxKinds[kProxPoisE].auto_slots: as many as the layout admits (profiles/poisson.md)
 LAMBDA_ONE_RTOL = 1e-12
 
 _cache = {}
@@ -173,7 +173,7 @@ def test_slots_are_byte_identical_to_the_serial_route(slots):
 
 
 def test_the_automatic_slot_choice():
-    """QUANT_SLOTS unset: kPoissonAutoSlots (profiles/poisson.md), clipped to the layout's table and to the number of fits."""
+    """QUANT_SLOTS unset: kProxPoisE's auto_slots (profiles/poisson.md), clipped to the layout's table and to the number of fits."""
     n, p, seed, _ = BRANCHES["onepass"]
     x, Y = problem(n, p, seed)
     lam, alpha = _grid(x, Y)
@@ -196,7 +196,7 @@ def _layout_cases():
 
 @pytest.mark.parametrize("n,p,maxit,want", list(_layout_cases()))
 def test_slots_on_every_register_layout(n, p, maxit, want):
-    """Five count columns at one cell.  Asking for more than pois_max_slots admits is clipped to it (4 at three double2 per thread and
+    """Five count columns at one cell.  Asking for more than the kind's max_slots row admits is clipped to it (4 at three double2 per thread and
     row runs 3); five and six double2 leave the form no second slot: serial."""
     x, Y = _layout_problem(n, p)
     lam = F * float(po.lambda_one(x, Y, True).max())
