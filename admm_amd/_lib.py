@@ -96,6 +96,24 @@ _GROUP_ARGS = [_c_int_p, _c_double_p, ctypes.c_int]
 TALL_ONLY = [("admm_hip_grplasso", _GROUP_ARGS, 5), ("admm_hip_sgl", _GROUP_ARGS + [_c_double_p, ctypes.c_double], 5),
              ("admm_hip_boxenet", [_c_double_p] * 3 + [ctypes.c_double], 5), ("admm_hip_mtlasso", [ctypes.c_int, ctypes.c_int, _c_double_p], 4)]
 
+# the dense entry points (basis pursuit, LAD and the losses on LAD's loop; admm_amd/api.py reaches all of them through _dense_call):
+#   admm_hip_<loss>(x, y, n, p[, k], mem, after_mem..., grid arrays...[, their length], opts, beta, niter, stats)
+#   <loss>_traced: never k or a grid, and one record block (buffer, capacity, count out); <loss>_state: never k, ONE value per grid
+#   array and two record blocks (trace, state); <loss>_lambda_max(x, y, n, p, k, mem, after_mem..., out)
+_RECORDS = [_c_double_p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]
+_INT = [ctypes.c_int]          # after mem: the intercept flag (admm_hip_parbp: nthread)
+#         loss           k      after mem  grid arrays         length  _traced  _state  _lambda_max
+DENSE = [("bp",          False, [],        [],                 False,  True,    True,   False),
+         ("parbp",       False, _INT,      [],                 False,  True,    False,  False),
+         ("lad",         False, _INT,      [],                 False,  True,    True,   False),
+         ("quantreg",    False, _INT,      [_c_double_p],      True,   False,   True,   False),
+         ("huber",       False, _INT,      [_c_double_p] * 2,  True,   False,   True,   False),
+         ("logit",       False, _INT,      [],                 False,  False,   True,   False),
+         ("logit_multi", True,  _INT,      [],                 False,  False,   False,  False),
+         ("logit_ridge", True,  _INT,      [_c_double_p],      True,   False,   True,   False),
+         ("logit_enet",  True,  _INT,      [_c_double_p] * 2,  True,   False,   True,   True),
+         ("poisson",     True,  _INT,      [_c_double_p] * 2,  True,   False,   True,   True)]
+
 TRACE_FIELDS = 12
 TRACE_COLD, TRACE_CONVERGED, TRACE_ACCELERATE, TRACE_RESTART = -1, 0, 1, 2
 TRACE_CONTINUE = 1
@@ -135,76 +153,29 @@ def load():
                                           _DP, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_int, ctypes.c_int, ctypes.c_double,
                                           ctypes.POINTER(AdmmOpts), _c_double_p, _c_float_p, _c_int_p, ctypes.POINTER(AdmmStats)])
     lib.admm_hip_lasso_multi.restype = ctypes.c_int
-    lib.admm_hip_lad.argtypes = [_DP, _DP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                 ctypes.POINTER(AdmmOpts), _c_double_p, _c_int_p, ctypes.POINTER(AdmmStats)]
-    lib.admm_hip_bp.argtypes = [_DP, _DP, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                ctypes.POINTER(AdmmOpts), _c_double_p, _c_int_p, ctypes.POINTER(AdmmStats)]
-    lib.admm_hip_lad_traced.argtypes = lib.admm_hip_lad.argtypes + [_c_double_p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]
-    lib.admm_hip_lad_traced.restype = ctypes.c_int
-    lib.admm_hip_bp_traced.argtypes = lib.admm_hip_bp.argtypes + [_c_double_p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]
-    lib.admm_hip_bp_traced.restype = ctypes.c_int
-    lib.admm_hip_lad_state.argtypes = lib.admm_hip_lad_traced.argtypes + [_c_double_p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]
-    lib.admm_hip_lad_state.restype = ctypes.c_int
-    lib.admm_hip_quantreg.argtypes = [_DP, _DP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_double_p, ctypes.c_int,
-                                      ctypes.POINTER(AdmmOpts), _c_double_p, _c_int_p, ctypes.POINTER(AdmmStats)]
-    lib.admm_hip_quantreg.restype = ctypes.c_int
-    lib.admm_hip_quantreg_state.argtypes = ([_DP, _DP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double,
-                                             ctypes.POINTER(AdmmOpts), _c_double_p, _c_int_p, ctypes.POINTER(AdmmStats)]
-                                            + [_c_double_p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)] * 2)
-    lib.admm_hip_quantreg_state.restype = ctypes.c_int
-    lib.admm_hip_huber.argtypes = [_DP, _DP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_double_p, _c_double_p, ctypes.c_int,
-                                   ctypes.POINTER(AdmmOpts), _c_double_p, _c_int_p, ctypes.POINTER(AdmmStats)]
-    lib.admm_hip_huber.restype = ctypes.c_int
-    lib.admm_hip_huber_state.argtypes = ([_DP, _DP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double,
-                                          ctypes.POINTER(AdmmOpts), _c_double_p, _c_int_p, ctypes.POINTER(AdmmStats)]
-                                         + [_c_double_p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)] * 2)
-    lib.admm_hip_huber_state.restype = ctypes.c_int
-    lib.admm_hip_logit.argtypes = [_DP, _DP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(AdmmOpts), _c_double_p, _c_int_p,
-                                   ctypes.POINTER(AdmmStats)]
-    lib.admm_hip_logit.restype = ctypes.c_int
-    lib.admm_hip_logit_state.argtypes = lib.admm_hip_logit.argtypes + [_c_double_p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)] * 2
-    lib.admm_hip_logit_state.restype = ctypes.c_int
-    lib.admm_hip_logit_multi.argtypes = [_DP, _DP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.POINTER(AdmmOpts), _c_double_p,
-                                         _c_int_p, ctypes.POINTER(AdmmStats)]
-    lib.admm_hip_logit_multi.restype = ctypes.c_int
-    lib.admm_hip_logit_ridge.argtypes = [_DP, _DP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_double_p, ctypes.c_int,
-                                         ctypes.POINTER(AdmmOpts), _c_double_p, _c_int_p, ctypes.POINTER(AdmmStats)]
-    lib.admm_hip_logit_ridge.restype = ctypes.c_int
-    lib.admm_hip_logit_ridge_state.argtypes = ([_DP, _DP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.POINTER(AdmmOpts),
-                                                _c_double_p, _c_int_p, ctypes.POINTER(AdmmStats)]
-                                               + [_c_double_p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)] * 2)
-    lib.admm_hip_logit_ridge_state.restype = ctypes.c_int
-    lib.admm_hip_logit_enet.argtypes = [_DP, _DP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_double_p, _c_double_p, ctypes.c_int,
-                                        ctypes.POINTER(AdmmOpts), _c_double_p, _c_int_p, ctypes.POINTER(AdmmStats)]
-    lib.admm_hip_logit_enet.restype = ctypes.c_int
-    lib.admm_hip_logit_enet_lambda_max.argtypes = [_DP, _DP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _c_double_p]
-    lib.admm_hip_logit_enet_lambda_max.restype = ctypes.c_int
-    lib.admm_hip_logit_enet_state.argtypes = ([_DP, _DP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.POINTER(AdmmOpts),
-                                               _c_double_p, _c_int_p, ctypes.POINTER(AdmmStats)]
-                                              + [_c_double_p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)] * 2)
-    lib.admm_hip_logit_enet_state.restype = ctypes.c_int
+    dense_out = [ctypes.POINTER(AdmmOpts), _c_double_p, _c_int_p, ctypes.POINTER(AdmmStats)]
+    for loss, has_k, after_mem, grid, count, traced, state, lambda_max in DENSE:
+        head = [_DP, _DP, ctypes.c_int, ctypes.c_int, ctypes.c_int] + after_mem               # x, y, n, p, mem, ...
+        head_k = head[:4] + [ctypes.c_int] + head[4:] if has_k else head
+        forms = [("", head_k + grid + [ctypes.c_int] * count + dense_out)]
+        if traced:
+            forms.append(("_traced", head + dense_out + _RECORDS))
+        if state:
+            forms.append(("_state", head + [g._type_ for g in grid] + dense_out + _RECORDS * 2))
+        if lambda_max:
+            forms.append(("_lambda_max", head_k + [_c_double_p]))
+        for suffix, args in forms:
+            fn = getattr(lib, "admm_hip_" + loss + suffix)
+            fn.argtypes, fn.restype = args, ctypes.c_int
     lib.admm_hip_test_logit_prox.argtypes = [_c_double_p, ctypes.c_longlong, ctypes.c_double, _c_double_p]
     lib.admm_hip_test_logit_prox.restype = ctypes.c_int
-    lib.admm_hip_poisson.argtypes = list(lib.admm_hip_logit_enet.argtypes)
-    lib.admm_hip_poisson.restype = ctypes.c_int
-    lib.admm_hip_poisson_lambda_max.argtypes = list(lib.admm_hip_logit_enet_lambda_max.argtypes)
-    lib.admm_hip_poisson_lambda_max.restype = ctypes.c_int
-    lib.admm_hip_poisson_state.argtypes = list(lib.admm_hip_logit_enet_state.argtypes)
-    lib.admm_hip_poisson_state.restype = ctypes.c_int
     lib.admm_hip_test_poisson_prox.argtypes = [_c_double_p, _c_double_p, ctypes.c_longlong, ctypes.c_double, _c_double_p]
     lib.admm_hip_test_poisson_prox.restype = ctypes.c_int
-    lib.admm_hip_bp_state.argtypes = lib.admm_hip_bp_traced.argtypes + [_c_double_p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]
-    lib.admm_hip_bp_state.restype = ctypes.c_int
     lib.admm_hip_dantzig.argtypes = [_DP, _DP, ctypes.c_int, ctypes.c_int, ctypes.c_int, _DP, ctypes.c_int, ctypes.c_int, ctypes.c_double,
                                      ctypes.c_int, ctypes.c_int, ctypes.POINTER(AdmmOpts), _c_double_p, _c_double_p, _c_int_p, ctypes.POINTER(AdmmStats)]
     lib.admm_hip_dantzig.restype = ctypes.c_int
     lib.admm_hip_dantzig_traced.argtypes = lib.admm_hip_dantzig.argtypes + [_c_double_p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]
     lib.admm_hip_dantzig_traced.restype = ctypes.c_int
-    lib.admm_hip_parbp.argtypes = [_DP, _DP, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
-                                   ctypes.POINTER(AdmmOpts), _c_double_p, _c_int_p, ctypes.POINTER(AdmmStats)]
-    lib.admm_hip_parbp.restype = ctypes.c_int
-    lib.admm_hip_parbp_traced.argtypes = lib.admm_hip_parbp.argtypes + [_c_double_p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]
-    lib.admm_hip_parbp_traced.restype = ctypes.c_int
     lib.admm_hip_parbp_dist.argtypes = [_DP, _DP, ctypes.c_int, ctypes.c_int, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_int, ctypes.c_int,
                                         ctypes.POINTER(AdmmOpts), _c_double_p, _c_int_p, ctypes.POINTER(AdmmStats)]
     lib.admm_hip_parbp_dist.restype = ctypes.c_int

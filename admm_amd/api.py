@@ -362,17 +362,136 @@ def _state_args(sbuf, nst):
     return sbuf.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), sbuf.cap, ctypes.byref(nst)
 
 
-class ADMM_BP_fit:
+# ---- the dense builders: basis pursuit, LAD and the losses on LAD's loop.  What they share is written once, here: the call into the
+# library (_dense_call), the argument rules of the builders and the base of the result classes.
+
+def _dense_call(model, entry, lead, grid, nfit, dim, trace=False, state=0, k=None, width=None, records_only=False):
+    """The one path from a dense builder's fit() into the library.  `entry` is admm_hip_<loss>; `lead` its arguments between mem and
+    the grid (the intercept flag; nthread for admm_hip_parbp); `grid` the loss's parameter arrays, one fit per entry (k fits where the
+    symbol takes `k`); `nfit` the number of fits; `dim` the length of one iterate (None: the symbol has a _traced form only).
+    Without trace this calls `entry`(x, y, n, p[, k], mem, lead..., grid arrays..., their length, opts, beta, niter, stats); with
+    trace -- and always with records_only: ADMM_BP and ADMM_LAD use no other form -- `entry`_state, which takes the FIRST value of every
+    grid array, never k or a length, and then the trace block and the state block (`state` records; ignored without trace).
+    -> (beta: flat float64, nfit times `width` (default p + 1); niter: int32 nfit; stats: dict; trace records or None; state records or None)."""
+    lib = _lib.load()
+    xp, xmem, xk = as_input(model.x)
+    yp, ymem, yk = as_input(model.y)
+    if xmem != ymem:
+        _stop("x and y must live in the same memory space")
+    o = AdmmOpts(model.maxit, model.eps_abs, model.eps_rel, model.rho)
+    beta = np.zeros((model.p + 1 if width is None else width) * nfit, dtype=np.float64)
+    niter = np.zeros(nfit, dtype=np.int32)
+    stats = AdmmStats()
+    dp = ctypes.POINTER(ctypes.c_double)
+    out = (ctypes.byref(o), beta.ctypes.data_as(dp), niter.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), ctypes.byref(stats))
+    sbuf = None
+    if trace or records_only:
+        tr, ntr = _trace_buffers(model.maxit if trace else 0)
+        records = _trace_args(tr, ntr)
+        if dim is not None:
+            sbuf, nst = _state_buffers(state if trace else 0, dim)
+            records += _state_args(sbuf, nst)
+        check(getattr(lib, entry + ("_traced" if dim is None else "_state"))(xp, yp, model.n, model.p, xmem, *lead, *(float(g[0]) for g in grid), *out, *records))
+    else:
+        check(getattr(lib, entry)(xp, yp, model.n, model.p, *(() if k is None else (k,)), xmem, *lead, *(g.ctypes.data_as(dp) for g in grid),
+                                  *((int(grid[0].size),) if grid else ()), *out))
+    # every buffer whose address went into the call -- x and y as converted (xk, yk), the grid arrays, beta, niter and the record buffers -- is
+    # a local of this frame and so alive until the call has returned: fit() passes its arrays in, never bare pointers
+    return (beta, niter, stats.as_dict(), tr[:ntr.value].copy() if trace else None,
+            sbuf[:nst.value].copy() if (trace and state and sbuf is not None) else None)
+
+
+def _with_records(fit, trace, state):
+    fit.trace, fit.state = trace, state
+    return fit
+
+
+def _fitted_intercept_shape(x, n, p, intercept):
+    """The losses that fit the intercept as a column of ones: nrow(x) must exceed ncol(x) + intercept."""
+    n_, p_ = _shape(x, n, p)
+    if n_ <= p_ + (1 if intercept else 0):
+        _stop("nrow(x) must be greater than ncol(x) + 1 (the intercept is fitted)" if intercept else "nrow(x) must be greater than ncol(x)")
+
+
+def _label_matrix(Y, k, nrow=None):
+    """-> (Y, k): Y as an n x k column-major matrix (a vector is one column), or the DevicePtr it was, which needs k.  nrow: the row
+    count to insist on here (the builders that go through ADMM_LAD.__init__ leave that to its length(y) check)."""
+    if isinstance(Y, DevicePtr):
+        if k is None:
+            _stop("k is required with a DevicePtr")
+        k = int(k)
+    else:
+        Y = np.asarray(Y, dtype=np.float64)
+        if Y.ndim == 1:
+            Y = Y[:, None]
+        if Y.ndim != 2:
+            _stop("Y must be a matrix")
+        Y = np.asfortranarray(Y)
+        k = Y.shape[1]
+        if nrow is not None and Y.shape[0] != nrow:
+            _stop("nrow(x) should be equal to nrow(Y)")
+    if k < 1:
+        _stop("y must have at least one column")
+    return Y, k
+
+
+def _binary_columns(Y):
+    """Every column of a host label matrix holds exactly 0 and 1, and both (labels behind a DevicePtr are checked by the library)."""
+    if isinstance(Y, DevicePtr):
+        return
+    for c in range(Y.shape[1]):
+        col = Y[:, c]
+        if not np.all((col == 0.0) | (col == 1.0)):
+            _stop(f"column {c} of y: every label must be exactly 0 or 1")
+        if np.all(col == 0.0) or np.all(col == 1.0):
+            _stop(f"column {c} of y must hold both classes")
+
+
+def _ovr_indicator(labels):
+    """An integer label vector -> (n x classes indicator matrix, the sorted classes): the one-vs-rest builders' Y."""
+    lab = np.asarray(labels)
+    if lab.ndim != 1:
+        _stop("labels must be a vector")
+    if not (np.issubdtype(lab.dtype, np.integer) or np.issubdtype(lab.dtype, np.bool_)):
+        if not (np.issubdtype(lab.dtype, np.floating) and np.all(np.isfinite(lab)) and np.all(lab == np.round(lab))):
+            _stop("labels must be integers")
+        lab = lab.astype(np.int64)
+    classes = np.unique(lab)
+    if classes.size < 2:
+        _stop("labels must hold at least two classes")
+    return (lab[:, None] == classes[None, :]).astype(np.float64), classes
+
+
+def _lad_defaults(model, intercept):
+    model.maxit = 10000
+    model.eps_abs = 1e-4
+    model.eps_rel = 1e-4
+    model.rho = 1.0
+    model.intercept = bool(intercept)
+
+
+class _DenseFit:
+    """What the dense builders' results share: the fields beta, niter and stats, show(), and a repr made of `_title`, the grid fields
+    `_grid` (label, attribute), beta -- the values, or its shape and `_beta_noun` -- and niter."""
+    _title = _beta_noun = None
+    _grid = ()
+
     def __init__(self, beta, niter, stats):
         self.beta = beta
         self.niter = niter
         self.stats = stats
 
-    def __repr__(self):                                                      # ADMM_BP_fit$show (R/10_admm_bp.R:125-133)
-        return f"ADMM Basis Pursuit fitting result\n\n$beta\n<{self.beta.shape[0]} x 1> sparse matrix\n\n$niter\n{self.niter}"
+    def __repr__(self):
+        beta = self.beta if self._beta_noun is None else f"<{' x '.join(str(s) for s in np.shape(self.beta))}> {self._beta_noun}"
+        blocks = [(label, getattr(self, attr)) for label, attr in self._grid] + [("beta", beta), ("niter", self.niter)]
+        return "\n\n".join([self._title] + [f"${label}\n{value}" for label, value in blocks])
 
     def show(self):
         print(repr(self))
+
+
+class ADMM_BP_fit(_DenseFit):                                                # ADMM_BP_fit$show (R/10_admm_bp.R:125-133)
+    _title, _beta_noun = "ADMM Basis Pursuit fitting result", "sparse matrix"
 
 
 class ADMM_BP:
@@ -416,46 +535,20 @@ class ADMM_BP:
         """trace=True also returns the decision trace (fit.trace, layout of include/admm_hip.h ADMM_TRACE_*); state = N > 0 (serial
         solver only) also the iterate dump of the first N decisions (fit.state: (records, 5, p) -- x | z | y | adj_z | adj_y,
         admm_hip_bp_state)."""
-        lib = _lib.load()
-        xp, xmem, xk = as_input(self.x)
-        yp, ymem, yk = as_input(self.y)
-        if xmem != ymem:
-            _stop("x and y must live in the same memory space")
-        o = AdmmOpts(self.maxit, self.eps_abs, self.eps_rel, self.rho)
-        beta = np.zeros(self.p, dtype=np.float64)
-        niter = np.zeros(1, dtype=np.int32)
-        stats = AdmmStats()
-        tr, ntr = _trace_buffers(self.maxit if trace else 0)
         if getattr(self, "nthread", 1) > 1:
             # .Call("admm_parbp", x, y, nthread, list(maxit, eps_abs, eps_rel, rho_ratio = rho)), R/10_admm_bp.R:111-116 -- the
             # symbol the reference never builds; here the column-block sharing solver of admm_amd/csrc/sharing_bp.hip
             with _par_devices(self):
-                check(lib.admm_hip_parbp_traced(xp, yp, self.n, self.p, xmem, int(self.nthread), ctypes.byref(o),
-                                                beta.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                                niter.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), ctypes.byref(stats), *_trace_args(tr, ntr)))
+                beta, niter, stats, tr, st = _dense_call(self, "admm_hip_parbp", (int(self.nthread),), (), 1, None, trace, width=self.p, records_only=True)
         else:
-            sbuf, nst = _state_buffers(state if trace else 0, self.p)
-            check(lib.admm_hip_bp_state(xp, yp, self.n, self.p, xmem, ctypes.byref(o),
-                                        beta.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                        niter.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), ctypes.byref(stats), *_trace_args(tr, ntr),
-                                        *_state_args(sbuf, nst)))
-        fit = ADMM_BP_fit(sp.csc_matrix(beta.reshape(-1, 1)), int(niter[0]), stats.as_dict())   # dgCMatrix p x 1 (BP.cpp:38-43)
-        fit.trace = tr[:ntr.value].copy() if trace else None
-        fit.state = sbuf[:nst.value].copy() if (trace and state and self.nthread <= 1) else None
-        return fit
+            beta, niter, stats, tr, st = _dense_call(self, "admm_hip_bp", (), (), 1, self.p, trace, state, width=self.p, records_only=True)
+        fit = ADMM_BP_fit(sp.csc_matrix(beta.reshape(-1, 1)), int(niter[0]), stats)             # dgCMatrix p x 1 (BP.cpp:38-43)
+        return _with_records(fit, tr, st)
 
 
-class ADMM_LAD_fit:
-    def __init__(self, beta, niter, stats):
-        self.beta = beta            # numeric p+1, intercept first (LAD.cpp:40-45)
-        self.niter = niter
-        self.stats = stats
-
-    def __repr__(self):
-        return f"ADMM LAD fitting result\n\n$beta\n{self.beta}\n\n$niter\n{self.niter}"
-
-    def show(self):
-        print(repr(self))
+class ADMM_LAD_fit(_DenseFit):
+    """beta: numeric p + 1, intercept first (LAD.cpp:40-45)."""
+    _title = "ADMM LAD fitting result"
 
 
 class ADMM_LAD(ADMM_BP):
@@ -467,47 +560,22 @@ class ADMM_LAD(ADMM_BP):
         if n_ != ylen:
             _stop("nrow(x) should be equal to length(y)")
         self.x, self.y, self.n, self.p = x, y, int(n_), int(p_)
-        self.maxit = 10000
-        self.eps_abs = 1e-4
-        self.eps_rel = 1e-4
-        self.rho = 1.0
-        self.intercept = bool(intercept)
+        _lad_defaults(self, intercept)
 
     def fit(self, trace=False, state=0):
         """trace / state as ADMM_BP.fit (the iterate dump has dimension n: admm_hip_lad_state)."""
-        lib = _lib.load()
-        xp, xmem, xk = as_input(self.x)
-        yp, ymem, yk = as_input(self.y)
-        if xmem != ymem:
-            _stop("x and y must live in the same memory space")
-        o = AdmmOpts(self.maxit, self.eps_abs, self.eps_rel, self.rho)
-        beta = np.zeros(self.p + 1, dtype=np.float64)
-        niter = np.zeros(1, dtype=np.int32)
-        stats = AdmmStats()
-        tr, ntr = _trace_buffers(self.maxit if trace else 0)
-        sbuf, nst = _state_buffers(state if trace else 0, self.n)
-        check(lib.admm_hip_lad_state(xp, yp, self.n, self.p, xmem, int(self.intercept), ctypes.byref(o),
-                                     beta.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
-                                     niter.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), ctypes.byref(stats), *_trace_args(tr, ntr),
-                                     *_state_args(sbuf, nst)))
-        fit = ADMM_LAD_fit(beta, int(niter[0]), stats.as_dict())
-        fit.trace = tr[:ntr.value].copy() if trace else None
-        fit.state = sbuf[:nst.value].copy() if (trace and state) else None
-        return fit
+        beta, niter, stats, tr, st = _dense_call(self, "admm_hip_lad", (int(self.intercept),), (), 1, self.n, trace, state, records_only=True)
+        return _with_records(ADMM_LAD_fit(beta, int(niter[0]), stats), tr, st)
 
 
-class ADMM_QuantReg_fit:
+class ADMM_QuantReg_fit(_DenseFit):
+    _title, _grid, _beta_noun = "ADMM quantile regression fitting result", (("tau", "tau"),), "matrix"
+
     def __init__(self, tau, beta, niter, stats):
         self.tau = tau              # numeric ntau
         self.beta = beta            # (p + 1) x ntau, column k = tau[k], intercept first
         self.niter = niter          # integer ntau
         self.stats = stats
-
-    def __repr__(self):
-        return f"ADMM quantile regression fitting result\n\n$tau\n{self.tau}\n\n$beta\n<{self.beta.shape[0]} x {self.beta.shape[1]}> matrix\n\n$niter\n{self.niter}"
-
-    def show(self):
-        print(repr(self))
 
 
 class ADMM_QuantReg(ADMM_LAD):
@@ -515,9 +583,7 @@ class ADMM_QuantReg(ADMM_LAD):
     intercept is fitted (a column of ones), so nrow(x) must exceed ncol(x) + intercept."""
 
     def __init__(self, x, y, tau=0.5, intercept=True, n=None, p=None):
-        n_, p_ = _shape(x, n, p)
-        if n_ <= p_ + (1 if intercept else 0):
-            _stop("nrow(x) must be greater than ncol(x) + 1 (the intercept is fitted)" if intercept else "nrow(x) must be greater than ncol(x)")
+        _fitted_intercept_shape(x, n, p, intercept)
         ADMM_LAD.__init__(self, x, y, intercept, n, p)
         t = np.atleast_1d(np.asarray(tau, dtype=np.float64))
         if t.ndim != 1 or t.size < 1 or t.size > 4096:
@@ -528,34 +594,16 @@ class ADMM_QuantReg(ADMM_LAD):
 
     def fit(self, trace=False, state=0):
         """-> ADMM_QuantReg_fit.  trace / state (as ADMM_LAD.fit, admm_hip_quantreg_state) for a single tau only."""
-        lib = _lib.load()
-        xp, xmem, xk = as_input(self.x)
-        yp, ymem, yk = as_input(self.y)
-        if xmem != ymem:
-            _stop("x and y must live in the same memory space")
         ntau = int(self.tau.size)
         if (trace or state) and ntau != 1:
             _stop("trace and state are recorded for a single tau")
-        o = AdmmOpts(self.maxit, self.eps_abs, self.eps_rel, self.rho)
-        beta = np.zeros((self.p + 1) * ntau, dtype=np.float64)
-        niter = np.zeros(ntau, dtype=np.int32)
-        stats = AdmmStats()
-        bp, np_ = beta.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), niter.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
-        if trace:
-            tr, ntr = _trace_buffers(self.maxit)
-            sbuf, nst = _state_buffers(state, self.n)
-            check(lib.admm_hip_quantreg_state(xp, yp, self.n, self.p, xmem, int(self.intercept), float(self.tau[0]), ctypes.byref(o),
-                                              bp, np_, ctypes.byref(stats), *_trace_args(tr, ntr), *_state_args(sbuf, nst)))
-        else:
-            check(lib.admm_hip_quantreg(xp, yp, self.n, self.p, xmem, int(self.intercept),
-                                        self.tau.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), ntau, ctypes.byref(o), bp, np_, ctypes.byref(stats)))
-        fit = ADMM_QuantReg_fit(self.tau.copy(), beta.reshape(ntau, self.p + 1).T.copy(), niter.copy(), stats.as_dict())
-        fit.trace = tr[:ntr.value].copy() if trace else None
-        fit.state = sbuf[:nst.value].copy() if (trace and state) else None
-        return fit
+        beta, niter, stats, tr, st = _dense_call(self, "admm_hip_quantreg", (int(self.intercept),), (self.tau,), ntau, self.n, trace, state)
+        return _with_records(ADMM_QuantReg_fit(self.tau.copy(), beta.reshape(ntau, self.p + 1).T.copy(), niter.copy(), stats), tr, st)
 
 
-class ADMM_Huber_fit:
+class ADMM_Huber_fit(_DenseFit):
+    _title, _grid, _beta_noun = "ADMM Huber regression fitting result", (("delta", "delta"), ("tau", "tau")), "matrix"
+
     def __init__(self, delta, tau, beta, niter, stats):
         self.delta = delta          # numeric nfit
         self.tau = tau              # numeric nfit
@@ -563,22 +611,13 @@ class ADMM_Huber_fit:
         self.niter = niter          # integer nfit
         self.stats = stats
 
-    def __repr__(self):
-        return (f"ADMM Huber regression fitting result\n\n$delta\n{self.delta}\n\n$tau\n{self.tau}\n\n$beta\n"
-                f"<{self.beta.shape[0]} x {self.beta.shape[1]}> matrix\n\n$niter\n{self.niter}")
-
-    def show(self):
-        print(repr(self))
-
 
 class ADMM_Huber(ADMM_LAD):
     """Huber / expectile regression on LAD's loop (admm_hip_huber): one fit per pair (delta[k], tau[k]), the setup paid once.  delta is in
     the units of y (inf: expectile regression), tau = 0.5 the symmetric Huber loss.  The intercept is fitted as ADMM_QuantReg's."""
 
     def __init__(self, x, y, delta=1.345, tau=0.5, intercept=True, n=None, p=None):
-        n_, p_ = _shape(x, n, p)
-        if n_ <= p_ + (1 if intercept else 0):
-            _stop("nrow(x) must be greater than ncol(x) + 1 (the intercept is fitted)" if intercept else "nrow(x) must be greater than ncol(x)")
+        _fitted_intercept_shape(x, n, p, intercept)
         ADMM_LAD.__init__(self, x, y, intercept, n, p)
         dl = np.atleast_1d(np.asarray(delta, dtype=np.float64))
         t = np.atleast_1d(np.asarray(tau, dtype=np.float64))
@@ -598,45 +637,16 @@ class ADMM_Huber(ADMM_LAD):
 
     def fit(self, trace=False, state=0):
         """-> ADMM_Huber_fit.  trace / state (as ADMM_LAD.fit, admm_hip_huber_state) for a single fit only."""
-        lib = _lib.load()
-        xp, xmem, xk = as_input(self.x)
-        yp, ymem, yk = as_input(self.y)
-        if xmem != ymem:
-            _stop("x and y must live in the same memory space")
         nfit = int(self.tau.size)
         if (trace or state) and nfit != 1:
             _stop("trace and state are recorded for a single fit")
-        o = AdmmOpts(self.maxit, self.eps_abs, self.eps_rel, self.rho)
-        beta = np.zeros((self.p + 1) * nfit, dtype=np.float64)
-        niter = np.zeros(nfit, dtype=np.int32)
-        stats = AdmmStats()
-        dp = ctypes.POINTER(ctypes.c_double)
-        bp, np_ = beta.ctypes.data_as(dp), niter.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
-        if trace:
-            tr, ntr = _trace_buffers(self.maxit)
-            sbuf, nst = _state_buffers(state, self.n)
-            check(lib.admm_hip_huber_state(xp, yp, self.n, self.p, xmem, int(self.intercept), float(self.delta[0]), float(self.tau[0]), ctypes.byref(o),
-                                           bp, np_, ctypes.byref(stats), *_trace_args(tr, ntr), *_state_args(sbuf, nst)))
-        else:
-            check(lib.admm_hip_huber(xp, yp, self.n, self.p, xmem, int(self.intercept), self.delta.ctypes.data_as(dp), self.tau.ctypes.data_as(dp), nfit,
-                                     ctypes.byref(o), bp, np_, ctypes.byref(stats)))
-        fit = ADMM_Huber_fit(self.delta.copy(), self.tau.copy(), beta.reshape(nfit, self.p + 1).T.copy(), niter.copy(), stats.as_dict())
-        fit.trace = tr[:ntr.value].copy() if trace else None
-        fit.state = sbuf[:nst.value].copy() if (trace and state) else None
-        return fit
+        beta, niter, stats, tr, st = _dense_call(self, "admm_hip_huber", (int(self.intercept),), (self.delta, self.tau), nfit, self.n, trace, state)
+        return _with_records(ADMM_Huber_fit(self.delta.copy(), self.tau.copy(), beta.reshape(nfit, self.p + 1).T.copy(), niter.copy(), stats), tr, st)
 
 
-class ADMM_Logit_fit:
-    def __init__(self, beta, niter, stats):
-        self.beta = beta            # numeric p + 1, intercept first
-        self.niter = niter          # maxit + 1: not converged (separable labels end there)
-        self.stats = stats
-
-    def __repr__(self):
-        return f"ADMM logistic regression fitting result\n\n$beta\n{self.beta}\n\n$niter\n{self.niter}"
-
-    def show(self):
-        print(repr(self))
+class ADMM_Logit_fit(_DenseFit):
+    """beta: numeric p + 1, intercept first; niter = maxit + 1: not converged (separable labels end there)."""
+    _title = "ADMM logistic regression fitting result"
 
 
 class ADMM_Logit(ADMM_LAD):
@@ -645,9 +655,7 @@ class ADMM_Logit(ADMM_LAD):
     library."""
 
     def __init__(self, x, y, intercept=True, n=None, p=None):
-        n_, p_ = _shape(x, n, p)
-        if n_ <= p_ + (1 if intercept else 0):
-            _stop("nrow(x) must be greater than ncol(x) + 1 (the intercept is fitted)" if intercept else "nrow(x) must be greater than ncol(x)")
+        _fitted_intercept_shape(x, n, p, intercept)
         if not isinstance(y, DevicePtr):
             y = np.ascontiguousarray(np.asarray(y, dtype=np.float64).ravel())
         ADMM_LAD.__init__(self, x, y, intercept, n, p)
@@ -660,40 +668,13 @@ class ADMM_Logit(ADMM_LAD):
     def fit(self, trace=False, state=0):
         """-> ADMM_Logit_fit.  trace / state as ADMM_LAD.fit (admm_hip_logit_state): record 0 of the iterate dump carries the zero response
         in its x slot and the signs 2 y - 1 in its z slot."""
-        lib = _lib.load()
-        xp, xmem, xk = as_input(self.x)
-        yp, ymem, yk = as_input(self.y)
-        if xmem != ymem:
-            _stop("x and y must live in the same memory space")
-        o = AdmmOpts(self.maxit, self.eps_abs, self.eps_rel, self.rho)
-        beta = np.zeros(self.p + 1, dtype=np.float64)
-        niter = np.zeros(1, dtype=np.int32)
-        stats = AdmmStats()
-        bp, np_ = beta.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), niter.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
-        if trace:
-            tr, ntr = _trace_buffers(self.maxit)
-            sbuf, nst = _state_buffers(state, self.n)
-            check(lib.admm_hip_logit_state(xp, yp, self.n, self.p, xmem, int(self.intercept), ctypes.byref(o), bp, np_, ctypes.byref(stats),
-                                           *_trace_args(tr, ntr), *_state_args(sbuf, nst)))
-        else:
-            check(lib.admm_hip_logit(xp, yp, self.n, self.p, xmem, int(self.intercept), ctypes.byref(o), bp, np_, ctypes.byref(stats)))
-        fit = ADMM_Logit_fit(beta, int(niter[0]), stats.as_dict())
-        fit.trace = tr[:ntr.value].copy() if trace else None
-        fit.state = sbuf[:nst.value].copy() if (trace and state) else None
-        return fit
+        beta, niter, stats, tr, st = _dense_call(self, "admm_hip_logit", (int(self.intercept),), (), 1, self.n, trace, state)
+        return _with_records(ADMM_Logit_fit(beta, int(niter[0]), stats), tr, st)
 
 
-class ADMM_LogitMulti_fit:
-    def __init__(self, beta, niter, stats):
-        self.beta = beta            # (p + 1) x k, column c = label column c, intercept first
-        self.niter = niter          # integer k; maxit + 1: that column has not converged
-        self.stats = stats
-
-    def __repr__(self):
-        return f"ADMM logistic regression fitting result\n\n$beta\n<{self.beta.shape[0]} x {self.beta.shape[1]}> matrix\n\n$niter\n{self.niter}"
-
-    def show(self):
-        print(repr(self))
+class ADMM_LogitMulti_fit(_DenseFit):
+    """beta: (p + 1) x k, column c = label column c, intercept first; niter: integer k, maxit + 1: that column has not converged."""
+    _title, _beta_noun = "ADMM logistic regression fitting result", "matrix"
 
 
 class ADMM_LogitMulti(ADMM_LAD):
@@ -702,48 +683,16 @@ class ADMM_LogitMulti(ADMM_LAD):
     in every column; behind a DevicePtr it is column-major, k is required and the library checks the labels."""
 
     def __init__(self, x, Y, intercept=True, n=None, p=None, k=None):
-        n_, p_ = _shape(x, n, p)
-        if n_ <= p_ + (1 if intercept else 0):
-            _stop("nrow(x) must be greater than ncol(x) + 1 (the intercept is fitted)" if intercept else "nrow(x) must be greater than ncol(x)")
-        if isinstance(Y, DevicePtr):
-            if k is None:
-                _stop("k is required with a DevicePtr")
-            k_ = int(k)
-        else:
-            Y = np.asarray(Y, dtype=np.float64)
-            if Y.ndim == 1:
-                Y = Y[:, None]
-            if Y.ndim != 2:
-                _stop("Y must be a matrix")
-            Y = np.asfortranarray(Y)
-            k_ = Y.shape[1]
-        if k_ < 1:
-            _stop("y must have at least one column")
+        _fitted_intercept_shape(x, n, p, intercept)
+        Y, k_ = _label_matrix(Y, k)
         ADMM_LAD.__init__(self, x, Y, intercept, n, p)
         self.k = k_
-        if not isinstance(Y, DevicePtr):
-            for c in range(k_):
-                col = Y[:, c]
-                if not np.all((col == 0.0) | (col == 1.0)):
-                    _stop(f"column {c} of y: every label must be exactly 0 or 1")
-                if np.all(col == 0.0) or np.all(col == 1.0):
-                    _stop(f"column {c} of y must hold both classes")
+        _binary_columns(Y)
 
     def fit(self):
         """-> ADMM_LogitMulti_fit (there is no trace / state form)."""
-        lib = _lib.load()
-        xp, xmem, xk = as_input(self.x)
-        yp, ymem, yk = as_input(self.y)
-        if xmem != ymem:
-            _stop("x and y must live in the same memory space")
-        o = AdmmOpts(self.maxit, self.eps_abs, self.eps_rel, self.rho)
-        beta = np.zeros((self.p + 1) * self.k, dtype=np.float64)
-        niter = np.zeros(self.k, dtype=np.int32)
-        stats = AdmmStats()
-        check(lib.admm_hip_logit_multi(xp, yp, self.n, self.p, self.k, xmem, int(self.intercept), ctypes.byref(o),
-                                       beta.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), niter.ctypes.data_as(ctypes.POINTER(ctypes.c_int)),
-                                       ctypes.byref(stats)))
-        return ADMM_LogitMulti_fit(beta.reshape((self.p + 1, self.k), order="F"), niter, stats.as_dict())
+        beta, niter, stats, _, _ = _dense_call(self, "admm_hip_logit_multi", (int(self.intercept),), (), self.k, self.n, k=self.k)
+        return ADMM_LogitMulti_fit(beta.reshape((self.p + 1, self.k), order="F"), niter, stats)
 
 
 class ADMM_LogitOvR(ADMM_LogitMulti):
@@ -751,17 +700,8 @@ class ADMM_LogitOvR(ADMM_LogitMulti):
     column c of the fit separates classes[c] from the rest.  No softmax, no calibration: k independent binary fits."""
 
     def __init__(self, x, labels, intercept=True, n=None, p=None):
-        lab = np.asarray(labels)
-        if lab.ndim != 1:
-            _stop("labels must be a vector")
-        if not (np.issubdtype(lab.dtype, np.integer) or np.issubdtype(lab.dtype, np.bool_)):
-            if not (np.issubdtype(lab.dtype, np.floating) and np.all(np.isfinite(lab)) and np.all(lab == np.round(lab))):
-                _stop("labels must be integers")
-            lab = lab.astype(np.int64)
-        classes = np.unique(lab)
-        if classes.size < 2:
-            _stop("labels must hold at least two classes")
-        ADMM_LogitMulti.__init__(self, x, (lab[:, None] == classes[None, :]).astype(np.float64), intercept, n, p)
+        Y, classes = _ovr_indicator(labels)
+        ADMM_LogitMulti.__init__(self, x, Y, intercept, n, p)
         self.classes = classes
 
     def fit(self):
@@ -771,19 +711,26 @@ class ADMM_LogitOvR(ADMM_LogitMulti):
         return fit
 
 
-class ADMM_LogitRidge_fit:
+def _penalised_fit(model, fit_class, entry, grid, trace, state):
+    """fit() of the penalised losses: k label columns times the cells of `grid`, iterates of n + p (the penalty rows behind the data
+    rows).  The grid form returns beta as (p + 1) x k x cells and niter as k x cells, the trace form the vector p + 1 and a scalar."""
+    ncell = int(grid[0].size)
+    beta, niter, stats, tr, st = _dense_call(model, entry, (int(model.intercept),), grid, model.k * ncell, model.n + model.p, trace, state, k=model.k)
+    if trace:
+        fit = fit_class(*(g.copy() for g in grid), beta, int(niter[0]), stats)
+    else:
+        fit = fit_class(*(g.copy() for g in grid), beta.reshape((model.p + 1, model.k, ncell), order="F"), niter.reshape((model.k, ncell), order="F"), stats)
+    return _with_records(fit, tr, st)
+
+
+class ADMM_LogitRidge_fit(_DenseFit):
+    _title, _grid, _beta_noun = "ADMM ridge logistic regression fitting result", (("lambda", "lam"),), "array"
+
     def __init__(self, lam, beta, niter, stats):
         self.lam = lam              # numeric nlambda, in the order given
         self.beta = beta            # (p + 1) x k x nlambda, intercept first          (fit(trace=True): p + 1)
         self.niter = niter          # integer k x nlambda; maxit + 1: not converged   (fit(trace=True): a scalar)
         self.stats = stats
-
-    def __repr__(self):
-        shape = " x ".join(str(s) for s in np.shape(self.beta))
-        return f"ADMM ridge logistic regression fitting result\n\n$lambda\n{self.lam}\n\n$beta\n<{shape}> array\n\n$niter\n{self.niter}"
-
-    def show(self):
-        print(repr(self))
 
 
 class ADMM_LogitRidge(ADMM_LAD):
@@ -797,92 +744,32 @@ class ADMM_LogitRidge(ADMM_LAD):
         n_, p_ = _shape(x, n, p)
         if n_ < 2:
             _stop("nrow(x) must be at least 2")
-        if isinstance(Y, DevicePtr):
-            if k is None:
-                _stop("k is required with a DevicePtr")
-            k_ = int(k)
-        else:
-            Y = np.asarray(Y, dtype=np.float64)
-            if Y.ndim == 1:
-                Y = Y[:, None]
-            if Y.ndim != 2:
-                _stop("Y must be a matrix")
-            Y = np.asfortranarray(Y)
-            k_ = Y.shape[1]
-            if Y.shape[0] != n_:
-                _stop("nrow(x) should be equal to nrow(Y)")
-        if k_ < 1:
-            _stop("y must have at least one column")
+        Y, k_ = _label_matrix(Y, k, n_)
         lm = np.atleast_1d(np.asarray(lam, dtype=np.float64))
         if lm.ndim != 1 or lm.size < 1:
             _stop("lam must hold at least one value")
         if not (np.all(np.isfinite(lm)) and np.all(lm > 0)):
             _stop("every lambda must be finite and positive (lambda = 0 is admm_logit_multi)")
-        if not isinstance(Y, DevicePtr):
-            for c in range(k_):
-                col = Y[:, c]
-                if not np.all((col == 0.0) | (col == 1.0)):
-                    _stop(f"column {c} of y: every label must be exactly 0 or 1")
-                if np.all(col == 0.0) or np.all(col == 1.0):
-                    _stop(f"column {c} of y must hold both classes")
+        _binary_columns(Y)
         self.x, self.y, self.n, self.p, self.k = x, Y, int(n_), int(p_), k_
         self.lam = np.ascontiguousarray(lm)
-        self.maxit = 10000
-        self.eps_abs = 1e-4
-        self.eps_rel = 1e-4
-        self.rho = 1.0
-        self.intercept = bool(intercept)
+        _lad_defaults(self, intercept)
 
     def fit(self, trace=False, state=0):
         """-> ADMM_LogitRidge_fit.  trace / state (admm_hip_logit_ridge_state) for one column and one lambda only: beta is then the
         vector p + 1 and niter a scalar, and the iterate dump has dimension n + p (the ridge rows behind the data rows); its record 0
         carries the zero response in its x slot and [2 y - 1, 0 ... 0] in its z slot."""
-        lib = _lib.load()
-        xp, xmem, xk = as_input(self.x)
-        yp, ymem, yk = as_input(self.y)
-        if xmem != ymem:
-            _stop("x and y must live in the same memory space")
-        nlam = int(self.lam.size)
-        if (trace or state) and (self.k != 1 or nlam != 1):
+        if (trace or state) and (self.k != 1 or self.lam.size != 1):
             _stop("trace and state are recorded for a single label column and a single lambda")
-        o = AdmmOpts(self.maxit, self.eps_abs, self.eps_rel, self.rho)
-        beta = np.zeros((self.p + 1) * self.k * nlam, dtype=np.float64)
-        niter = np.zeros(self.k * nlam, dtype=np.int32)
-        stats = AdmmStats()
-        dp = ctypes.POINTER(ctypes.c_double)
-        bp, np_ = beta.ctypes.data_as(dp), niter.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
-        if trace:
-            tr, ntr = _trace_buffers(self.maxit)
-            sbuf, nst = _state_buffers(state, self.n + self.p)
-            check(lib.admm_hip_logit_ridge_state(xp, yp, self.n, self.p, xmem, int(self.intercept), float(self.lam[0]), ctypes.byref(o), bp, np_,
-                                                 ctypes.byref(stats), *_trace_args(tr, ntr), *_state_args(sbuf, nst)))
-            fit = ADMM_LogitRidge_fit(self.lam.copy(), beta, int(niter[0]), stats.as_dict())
-            fit.trace = tr[:ntr.value].copy()
-            fit.state = sbuf[:nst.value].copy() if state else None
-            return fit
-        check(lib.admm_hip_logit_ridge(xp, yp, self.n, self.p, self.k, xmem, int(self.intercept), self.lam.ctypes.data_as(dp), nlam, ctypes.byref(o), bp, np_,
-                                       ctypes.byref(stats)))
-        fit = ADMM_LogitRidge_fit(self.lam.copy(), beta.reshape((self.p + 1, self.k, nlam), order="F"), niter.reshape((self.k, nlam), order="F"),
-                                  stats.as_dict())
-        fit.trace = fit.state = None
-        return fit
+        return _penalised_fit(self, ADMM_LogitRidge_fit, "admm_hip_logit_ridge", (self.lam,), trace, state)
 
 
 class ADMM_LogitRidgeOvR(ADMM_LogitRidge):
     """One-vs-rest on ADMM_LogitRidge: the indicator matrix of ADMM_LogitOvR, `classes` sorted, column c separates classes[c] from the rest."""
 
     def __init__(self, x, labels, lam, intercept=True, n=None, p=None):
-        lab = np.asarray(labels)
-        if lab.ndim != 1:
-            _stop("labels must be a vector")
-        if not (np.issubdtype(lab.dtype, np.integer) or np.issubdtype(lab.dtype, np.bool_)):
-            if not (np.issubdtype(lab.dtype, np.floating) and np.all(np.isfinite(lab)) and np.all(lab == np.round(lab))):
-                _stop("labels must be integers")
-            lab = lab.astype(np.int64)
-        classes = np.unique(lab)
-        if classes.size < 2:
-            _stop("labels must hold at least two classes")
-        ADMM_LogitRidge.__init__(self, x, (lab[:, None] == classes[None, :]).astype(np.float64), lam, intercept, n, p)
+        Y, classes = _ovr_indicator(labels)
+        ADMM_LogitRidge.__init__(self, x, Y, lam, intercept, n, p)
         self.classes = classes
 
     def fit(self, trace=False, state=0):
@@ -892,21 +779,15 @@ class ADMM_LogitRidgeOvR(ADMM_LogitRidge):
         return fit
 
 
-class ADMM_LogitEnet_fit:
+class ADMM_LogitEnet_fit(_DenseFit):
+    _title, _grid, _beta_noun = "ADMM elastic-net logistic regression fitting result", (("lambda", "lam"), ("alpha", "alpha")), "array"
+
     def __init__(self, lam, alpha, beta, niter, stats):
         self.lam = lam              # numeric ncell, in the order given
         self.alpha = alpha          # numeric ncell: cell l is the pair (lam[l], alpha[l])
         self.beta = beta            # (p + 1) x k x ncell, intercept first            (fit(trace=True): p + 1)
         self.niter = niter          # integer k x ncell; maxit + 1: not converged     (fit(trace=True): a scalar)
         self.stats = stats
-
-    def __repr__(self):
-        shape = " x ".join(str(s) for s in np.shape(self.beta))
-        return (f"ADMM elastic-net logistic regression fitting result\n\n$lambda\n{self.lam}\n\n$alpha\n{self.alpha}\n\n$beta\n<{shape}> array\n\n"
-                f"$niter\n{self.niter}")
-
-    def show(self):
-        print(repr(self))
 
 
 class ADMM_LogitEnet(ADMM_LAD):
@@ -919,26 +800,21 @@ class ADMM_LogitEnet(ADMM_LAD):
     alpha > 0 and asks the device for lambda_1 (admm_hip_logit_enet_lambda_max) when fit() or lambda_one() is called.  Every fit starts
     cold, all of them on one inverse; there is no condition on nrow(x) against ncol(x)."""
 
+    # what a loss on these (lam, alpha) cells names: its entry point, its result, the noun of a column of Y and the two rules below
+    _entry, _fit_class, _column = "admm_hip_logit_enet", ADMM_LogitEnet_fit, "label column"
+
+    def _check_lambda(self, lm, n, p, intercept):
+        if not (np.all(np.isfinite(lm)) and np.all(lm > 0)):
+            _stop("every lambda must be finite and positive")
+
+    def _check_response(self, Y):
+        _binary_columns(Y)
+
     def __init__(self, x, Y, lam=None, alpha=1.0, intercept=True, nlambda=100, lambda_min_ratio=None, n=None, p=None, k=None):
         n_, p_ = _shape(x, n, p)
         if n_ < 2:
             _stop("nrow(x) must be at least 2")
-        if isinstance(Y, DevicePtr):
-            if k is None:
-                _stop("k is required with a DevicePtr")
-            k_ = int(k)
-        else:
-            Y = np.asarray(Y, dtype=np.float64)
-            if Y.ndim == 1:
-                Y = Y[:, None]
-            if Y.ndim != 2:
-                _stop("Y must be a matrix")
-            Y = np.asfortranarray(Y)
-            k_ = Y.shape[1]
-            if Y.shape[0] != n_:
-                _stop("nrow(x) should be equal to nrow(Y)")
-        if k_ < 1:
-            _stop("y must have at least one column")
+        Y, k_ = _label_matrix(Y, k, n_)
         al = np.asarray(alpha, dtype=np.float64)
         if al.ndim > 1 or al.size < 1:
             _stop("alpha must be a scalar or a vector")
@@ -958,41 +834,26 @@ class ADMM_LogitEnet(ADMM_LAD):
             lm = np.atleast_1d(np.asarray(lam, dtype=np.float64))
             if lm.ndim != 1 or lm.size < 1:
                 _stop("lam must hold at least one value")
-            if not (np.all(np.isfinite(lm)) and np.all(lm > 0)):
-                _stop("every lambda must be finite and positive")
+            self._check_lambda(lm, n_, p_, intercept)
             if al.ndim == 1 and al.size != lm.size:
                 _stop("alpha must be a scalar or as long as lam (cells are pairs)")
             self.lam = np.ascontiguousarray(lm)
             self.alpha = np.ascontiguousarray(np.broadcast_to(al, lm.shape), dtype=np.float64)
             self.nlambda, self.lambda_min_ratio = int(lm.size), None
-        if not isinstance(Y, DevicePtr):
-            for c in range(k_):
-                col = Y[:, c]
-                if not np.all((col == 0.0) | (col == 1.0)):
-                    _stop(f"column {c} of y: every label must be exactly 0 or 1")
-                if np.all(col == 0.0) or np.all(col == 1.0):
-                    _stop(f"column {c} of y must hold both classes")
+        self._check_response(Y)
         self.x, self.y, self.n, self.p, self.k = x, Y, int(n_), int(p_), k_
-        self.maxit = 10000
-        self.eps_abs = 1e-4
-        self.eps_rel = 1e-4
-        self.rho = 1.0
-        self.intercept = bool(intercept)
-
-    def _inputs(self):
-        xp, xmem, xk = as_input(self.x)
-        yp, ymem, yk = as_input(self.y)
-        if xmem != ymem:
-            _stop("x and y must live in the same memory space")
-        return xp, yp, xmem, (xk, yk)              # (the last: what keeps converted buffers alive during the call)
+        _lad_defaults(self, intercept)
 
     def lambda_one(self):
         """-> (k,) lambda_1 per label column: max_j |x~_j'(y_c - mean(y_c))| (intercept) or |x~_j'(y_c - 1/2)| (none), on the device.
         For alpha > 0 the coefficients of column c are all zero from lambda_1[c] / alpha on."""
         lib = _lib.load()
-        xp, yp, xmem, keep = self._inputs()
+        xp, xmem, xk = as_input(self.x)
+        yp, ymem, yk = as_input(self.y)                # (xk, yk keep the converted buffers alive during the call)
+        if xmem != ymem:
+            _stop("x and y must live in the same memory space")
         out = np.zeros(self.k, dtype=np.float64)
-        check(lib.admm_hip_logit_enet_lambda_max(xp, yp, self.n, self.p, self.k, xmem, int(self.intercept), out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
+        check(getattr(lib, self._entry + "_lambda_max")(xp, yp, self.n, self.p, self.k, xmem, int(self.intercept), out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
         return out
 
     def _cells(self):
@@ -1006,50 +867,17 @@ class ADMM_LogitEnet(ADMM_LAD):
         """-> ADMM_LogitEnet_fit.  trace / state (admm_hip_logit_enet_state) for one column and one cell only: beta is then the vector
         p + 1 and niter a scalar, and the iterate dump has dimension n + p (the penalty rows behind the data rows); its record 0
         carries the zero response in its x slot and [2 y - 1, 0 ... 0] in its z slot."""
-        lib = _lib.load()
-        xp, yp, xmem, keep = self._inputs()
         if (trace or state) and (self.k != 1 or self.nlambda != 1):
-            _stop("trace and state are recorded for a single label column and a single cell")
-        lam, alpha = self._cells()
-        ncell = int(lam.size)
-        o = AdmmOpts(self.maxit, self.eps_abs, self.eps_rel, self.rho)
-        beta = np.zeros((self.p + 1) * self.k * ncell, dtype=np.float64)
-        niter = np.zeros(self.k * ncell, dtype=np.int32)
-        stats = AdmmStats()
-        dp = ctypes.POINTER(ctypes.c_double)
-        bp, np_ = beta.ctypes.data_as(dp), niter.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
-        if trace:
-            tr, ntr = _trace_buffers(self.maxit)
-            sbuf, nst = _state_buffers(state, self.n + self.p)
-            check(lib.admm_hip_logit_enet_state(xp, yp, self.n, self.p, xmem, int(self.intercept), float(lam[0]), float(alpha[0]), ctypes.byref(o), bp, np_,
-                                                ctypes.byref(stats), *_trace_args(tr, ntr), *_state_args(sbuf, nst)))
-            fit = ADMM_LogitEnet_fit(lam.copy(), alpha.copy(), beta, int(niter[0]), stats.as_dict())
-            fit.trace = tr[:ntr.value].copy()
-            fit.state = sbuf[:nst.value].copy() if state else None
-            return fit
-        check(lib.admm_hip_logit_enet(xp, yp, self.n, self.p, self.k, xmem, int(self.intercept), lam.ctypes.data_as(dp), alpha.ctypes.data_as(dp), ncell,
-                                      ctypes.byref(o), bp, np_, ctypes.byref(stats)))
-        fit = ADMM_LogitEnet_fit(lam.copy(), alpha.copy(), beta.reshape((self.p + 1, self.k, ncell), order="F"), niter.reshape((self.k, ncell), order="F"),
-                                 stats.as_dict())
-        fit.trace = fit.state = None
-        return fit
+            _stop(f"trace and state are recorded for a single {self._column} and a single cell")
+        return _penalised_fit(self, self._fit_class, self._entry, self._cells(), trace, state)        # _cells() may ask the device: after the refusal
 
 
 class ADMM_LogitEnetOvR(ADMM_LogitEnet):
     """One-vs-rest on ADMM_LogitEnet: the indicator matrix of ADMM_LogitOvR, `classes` sorted, column c separates classes[c] from the rest."""
 
     def __init__(self, x, labels, lam=None, alpha=1.0, intercept=True, nlambda=100, lambda_min_ratio=None, n=None, p=None):
-        lab = np.asarray(labels)
-        if lab.ndim != 1:
-            _stop("labels must be a vector")
-        if not (np.issubdtype(lab.dtype, np.integer) or np.issubdtype(lab.dtype, np.bool_)):
-            if not (np.issubdtype(lab.dtype, np.floating) and np.all(np.isfinite(lab)) and np.all(lab == np.round(lab))):
-                _stop("labels must be integers")
-            lab = lab.astype(np.int64)
-        classes = np.unique(lab)
-        if classes.size < 2:
-            _stop("labels must hold at least two classes")
-        ADMM_LogitEnet.__init__(self, x, (lab[:, None] == classes[None, :]).astype(np.float64), lam, alpha, intercept, nlambda, lambda_min_ratio, n, p)
+        Y, classes = _ovr_indicator(labels)
+        ADMM_LogitEnet.__init__(self, x, Y, lam, alpha, intercept, nlambda, lambda_min_ratio, n, p)
         self.classes = classes
 
     def fit(self, trace=False, state=0):
@@ -1059,21 +887,8 @@ class ADMM_LogitEnetOvR(ADMM_LogitEnet):
         return fit
 
 
-class ADMM_Poisson_fit:
-    def __init__(self, lam, alpha, beta, niter, stats):
-        self.lam = lam              # numeric ncell, in the order given
-        self.alpha = alpha          # numeric ncell: cell l is the pair (lam[l], alpha[l])
-        self.beta = beta            # (p + 1) x k x ncell, intercept first            (fit(trace=True): p + 1)
-        self.niter = niter          # integer k x ncell; maxit + 1: not converged     (fit(trace=True): a scalar)
-        self.stats = stats
-
-    def __repr__(self):
-        shape = " x ".join(str(s) for s in np.shape(self.beta))
-        return (f"ADMM Poisson regression fitting result\n\n$lambda\n{self.lam}\n\n$alpha\n{self.alpha}\n\n$beta\n<{shape}> array\n\n"
-                f"$niter\n{self.niter}")
-
-    def show(self):
-        print(repr(self))
+class ADMM_Poisson_fit(ADMM_LogitEnet_fit):
+    _title = "ADMM Poisson regression fitting result"
 
 
 class ADMM_Poisson(ADMM_LogitEnet):
@@ -1086,106 +901,31 @@ class ADMM_Poisson(ADMM_LogitEnet):
     nlambda values log-spaced from max_c lambda_1(c) / alpha down to lambda_min_ratio times that, as ADMM_LogitEnet builds them.  Every
     fit starts cold, all of them on one inverse."""
 
-    def __init__(self, x, Y, lam=None, alpha=1.0, intercept=True, nlambda=100, lambda_min_ratio=None, n=None, p=None, k=None):
-        n_, p_ = _shape(x, n, p)
-        if n_ < 2:
-            _stop("nrow(x) must be at least 2")
-        if isinstance(Y, DevicePtr):
-            if k is None:
-                _stop("k is required with a DevicePtr")
-            k_ = int(k)
-        else:
-            Y = np.asarray(Y, dtype=np.float64)
-            if Y.ndim == 1:
-                Y = Y[:, None]
-            if Y.ndim != 2:
-                _stop("Y must be a matrix")
-            Y = np.asfortranarray(Y)
-            k_ = Y.shape[1]
-            if Y.shape[0] != n_:
-                _stop("nrow(x) should be equal to nrow(Y)")
-        if k_ < 1:
-            _stop("y must have at least one column")
-        al = np.asarray(alpha, dtype=np.float64)
-        if al.ndim > 1 or al.size < 1:
-            _stop("alpha must be a scalar or a vector")
-        if not np.all((al >= 0.0) & (al <= 1.0)):
-            _stop("every alpha must lie in [0, 1]")
-        if lam is None:
-            if al.ndim != 0 or not float(al) > 0.0:
-                _stop("the automatic lambda grid needs one alpha > 0 (alpha = 0 has no lambda_max: pass lam)")
-            if int(nlambda) <= 0:
-                _stop("nlambda must be a positive integer")
-            lmr = (0.01 if n_ < p_ else 0.0001) if lambda_min_ratio is None else float(lambda_min_ratio)
-            if lmr <= 0 or lmr >= 1:
-                _stop("lambda_min_ratio must be within (0, 1)")
-            self.lam, self.alpha = None, np.full(int(nlambda), float(al))
-            self.nlambda, self.lambda_min_ratio = int(nlambda), lmr
-        else:
-            lm = np.atleast_1d(np.asarray(lam, dtype=np.float64))
-            if lm.ndim != 1 or lm.size < 1:
-                _stop("lam must hold at least one value")
-            if not (np.all(np.isfinite(lm)) and np.all(lm >= 0)):
-                _stop("every lambda must be finite and non-negative")
-            if np.any(lm == 0) and not n_ > p_ + int(bool(intercept)):
-                _stop("lambda = 0 needs nrow(x) > ncol(x) + intercept")
-            if al.ndim == 1 and al.size != lm.size:
-                _stop("alpha must be a scalar or as long as lam (cells are pairs)")
-            self.lam = np.ascontiguousarray(lm)
-            self.alpha = np.ascontiguousarray(np.broadcast_to(al, lm.shape), dtype=np.float64)
-            self.nlambda, self.lambda_min_ratio = int(lm.size), None
+    _entry, _fit_class, _column = "admm_hip_poisson", ADMM_Poisson_fit, "count column"
+
+    def _check_lambda(self, lm, n, p, intercept):
+        if not (np.all(np.isfinite(lm)) and np.all(lm >= 0)):
+            _stop("every lambda must be finite and non-negative")
+        if np.any(lm == 0) and not n > p + int(bool(intercept)):
+            _stop("lambda = 0 needs nrow(x) > ncol(x) + intercept")
+
+    def _check_response(self, Y):
         if not isinstance(Y, DevicePtr):
             if not (np.all(np.isfinite(Y)) and np.all(Y >= 0.0)):
                 _stop("every y must be finite and non-negative")
             if not np.all(Y.sum(axis=0) > 0.0):
                 _stop("every column of y must have a positive sum")
-        self.x, self.y, self.n, self.p, self.k = x, Y, int(n_), int(p_), k_
-        self.maxit = 10000
-        self.eps_abs = 1e-4
-        self.eps_rel = 1e-4
-        self.rho = 1.0
-        self.intercept = bool(intercept)
 
     def lambda_one(self):
         """-> (k,) lambda_1 per count column: max_j |x~_j'(y_c - mean(y_c))| (intercept) or |x~_j'(y_c - 1)| (none), on the device.
         For alpha > 0 the coefficients of column c are all zero from lambda_1[c] / alpha on."""
-        lib = _lib.load()
-        xp, yp, xmem, keep = self._inputs()
-        out = np.zeros(self.k, dtype=np.float64)
-        check(lib.admm_hip_poisson_lambda_max(xp, yp, self.n, self.p, self.k, xmem, int(self.intercept), out.ctypes.data_as(ctypes.POINTER(ctypes.c_double))))
-        return out
+        return ADMM_LogitEnet.lambda_one(self)
 
     def fit(self, trace=False, state=0):
         """-> ADMM_Poisson_fit.  trace / state (admm_hip_poisson_state) for one column and one cell only: beta is then the vector p + 1
         and niter a scalar, and the iterate dump has dimension n + p (the penalty rows behind the data rows); its record 0 carries the
         zero response in its x slot and [y, -1 ... -1] in its z slot."""
-        lib = _lib.load()
-        xp, yp, xmem, keep = self._inputs()
-        if (trace or state) and (self.k != 1 or self.nlambda != 1):
-            _stop("trace and state are recorded for a single count column and a single cell")
-        lam, alpha = self._cells()
-        ncell = int(lam.size)
-        o = AdmmOpts(self.maxit, self.eps_abs, self.eps_rel, self.rho)
-        beta = np.zeros((self.p + 1) * self.k * ncell, dtype=np.float64)
-        niter = np.zeros(self.k * ncell, dtype=np.int32)
-        stats = AdmmStats()
-        dp = ctypes.POINTER(ctypes.c_double)
-        bp, np_ = beta.ctypes.data_as(dp), niter.ctypes.data_as(ctypes.POINTER(ctypes.c_int))
-        if trace:
-            tr, ntr = _trace_buffers(self.maxit)
-            sbuf, nst = _state_buffers(state, self.n + self.p)
-            check(lib.admm_hip_poisson_state(xp, yp, self.n, self.p, xmem, int(self.intercept), float(lam[0]), float(alpha[0]), ctypes.byref(o), bp, np_,
-                                             ctypes.byref(stats), *_trace_args(tr, ntr), *_state_args(sbuf, nst)))
-            fit = ADMM_Poisson_fit(lam.copy(), alpha.copy(), beta, int(niter[0]), stats.as_dict())
-            fit.trace = tr[:ntr.value].copy()
-            fit.state = sbuf[:nst.value].copy() if state else None
-            return fit
-        check(lib.admm_hip_poisson(xp, yp, self.n, self.p, self.k, xmem, int(self.intercept), lam.ctypes.data_as(dp), alpha.ctypes.data_as(dp), ncell,
-                                   ctypes.byref(o), bp, np_, ctypes.byref(stats)))
-        fit = ADMM_Poisson_fit(lam.copy(), alpha.copy(), beta.reshape((self.p + 1, self.k, ncell), order="F"), niter.reshape((self.k, ncell), order="F"),
-                               stats.as_dict())
-        fit.trace = fit.state = None
-        return fit
+        return ADMM_LogitEnet.fit(self, trace, state)
 
 
 class LassoPlan:

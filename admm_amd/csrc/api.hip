@@ -27,6 +27,11 @@ static int guarded(F&& f) {
 // The lambda-path arguments every path entry point carries, in the header's order; alpha < 0: the plain Lasso.
 #define PATH_SPEC(alpha) PathSpec{lambda_in, nlambda_in, nlambda_auto, lmin_ratio, standardize, intercept, (alpha), opts}
 #define PATH_OUT PathOut{lambda_out, beta_out, niter_out, stats}
+// What every dense entry point (basis pursuit, LAD and the losses on LAD's loop) writes to, by the header's parameter names: the
+// plain form, with the decision trace, and with the trace and the iterate dump.
+#define DENSE_OUT DenseOut{beta_out, niter_out, stats}
+#define DENSE_OUT_TRACED DenseOut{beta_out, niter_out, stats, {trace_out, trace_cap, ntrace_out}}
+#define DENSE_OUT_STATE DenseOut{beta_out, niter_out, stats, {trace_out, trace_cap, ntrace_out}, {state_out, state_cap, nstate_out}}
 
 static LassoPlan& plan_of(admm_hip_plan* plan) {
     PlanHandle* h = reinterpret_cast<PlanHandle*>(plan);
@@ -109,67 +114,72 @@ int admm_hip_parlasso(const double* x, const double* y, int n, int p, int mem,
 
 int admm_hip_lad(const double* x, const double* y, int n, int p, int mem, int intercept,
                  const admm_opts* opts, double* beta_out, int* niter_out, admm_stats* stats) {
-    return guarded([&] { lad(x, y, n, p, mem, intercept, opts, DenseOut{beta_out, niter_out, stats}); });
+    return guarded([&] { lad(x, y, n, p, mem, intercept, opts, DENSE_OUT); });
 }
 
 int admm_hip_lad_traced(const double* x, const double* y, int n, int p, int mem, int intercept, const admm_opts* opts,
                         double* beta_out, int* niter_out, admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out) {
-    return guarded([&] { lad(x, y, n, p, mem, intercept, opts, DenseOut{beta_out, niter_out, stats, {trace_out, trace_cap, ntrace_out}}); });
+    return guarded([&] { lad(x, y, n, p, mem, intercept, opts, DENSE_OUT_TRACED); });
 }
 
 int admm_hip_lad_state(const double* x, const double* y, int n, int p, int mem, int intercept, const admm_opts* opts,
                        double* beta_out, int* niter_out, admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out,
                        double* state_out, long long state_cap, long long* nstate_out) {
-    return guarded([&] {
-        lad(x, y, n, p, mem, intercept, opts, DenseOut{beta_out, niter_out, stats, {trace_out, trace_cap, ntrace_out}, {state_out, state_cap, nstate_out}});
-    });
+    return guarded([&] { lad(x, y, n, p, mem, intercept, opts, DENSE_OUT_STATE); });
 }
 
 int admm_hip_quantreg(const double* x, const double* y, int n, int p, int mem, int intercept, const double* tau, int ntau,
                       const admm_opts* opts, double* beta_out, int* niter_out, admm_stats* stats) {
-    return guarded([&] { quantreg(x, y, n, p, mem, intercept, tau, ntau, opts, DenseOut{beta_out, niter_out, stats}); });
+    return guarded([&] { quantreg(x, y, n, p, mem, intercept, tau, ntau, opts, DENSE_OUT); });
+}
+
+int admm_hip_quantreg_state(const double* x, const double* y, int n, int p, int mem, int intercept, double tau, const admm_opts* opts,
+                            double* beta_out, int* niter_out, admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out,
+                            double* state_out, long long state_cap, long long* nstate_out) {
+    return guarded([&] { quantreg(x, y, n, p, mem, intercept, &tau, 1, opts, DENSE_OUT_STATE); });
 }
 
 int admm_hip_huber(const double* x, const double* y, int n, int p, int mem, int intercept, const double* delta, const double* tau, int nfit,
                    const admm_opts* opts, double* beta_out, int* niter_out, admm_stats* stats) {
-    return guarded([&] { huber(x, y, n, p, mem, intercept, delta, tau, nfit, opts, DenseOut{beta_out, niter_out, stats}); });
+    return guarded([&] { huber(x, y, n, p, mem, intercept, delta, tau, nfit, opts, DENSE_OUT); });
 }
 
 int admm_hip_huber_state(const double* x, const double* y, int n, int p, int mem, int intercept, double delta, double tau, const admm_opts* opts,
                          double* beta_out, int* niter_out, admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out,
                          double* state_out, long long state_cap, long long* nstate_out) {
-    return guarded([&] {
-        huber(x, y, n, p, mem, intercept, &delta, &tau, 1, opts, DenseOut{beta_out, niter_out, stats, {trace_out, trace_cap, ntrace_out}, {state_out, state_cap, nstate_out}});
-    });
+    return guarded([&] { huber(x, y, n, p, mem, intercept, &delta, &tau, 1, opts, DENSE_OUT_STATE); });
 }
 
 int admm_hip_logit(const double* x, const double* y, int n, int p, int mem, int intercept, const admm_opts* opts, double* beta_out, int* niter_out,
                    admm_stats* stats) {
-    return guarded([&] { logit(x, y, n, p, mem, intercept, opts, DenseOut{beta_out, niter_out, stats}); });
+    return guarded([&] { logit(x, y, n, p, mem, intercept, opts, DENSE_OUT); });
+}
+
+int admm_hip_logit_state(const double* x, const double* y, int n, int p, int mem, int intercept, const admm_opts* opts, double* beta_out, int* niter_out,
+                         admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out, double* state_out, long long state_cap,
+                         long long* nstate_out) {
+    return guarded([&] { logit(x, y, n, p, mem, intercept, opts, DENSE_OUT_STATE); });
 }
 
 int admm_hip_logit_multi(const double* x, const double* y, int n, int p, int k, int mem, int intercept, const admm_opts* opts, double* beta_out,
                          int* niter_out, admm_stats* stats) {
-    return guarded([&] { logit_multi(x, y, n, p, k, mem, intercept, opts, DenseOut{beta_out, niter_out, stats}); });
+    return guarded([&] { logit_multi(x, y, n, p, k, mem, intercept, opts, DENSE_OUT); });
 }
 
 int admm_hip_logit_ridge(const double* x, const double* y, int n, int p, int k, int mem, int intercept, const double* lambda, int nlambda, const admm_opts* opts,
                          double* beta_out, int* niter_out, admm_stats* stats) {
-    return guarded([&] { logit_ridge(x, y, n, p, k, mem, intercept, lambda, nlambda, opts, DenseOut{beta_out, niter_out, stats}); });
+    return guarded([&] { logit_ridge(x, y, n, p, k, mem, intercept, lambda, nlambda, opts, DENSE_OUT); });
 }
 
 int admm_hip_logit_ridge_state(const double* x, const double* y, int n, int p, int mem, int intercept, double lambda, const admm_opts* opts, double* beta_out,
                                int* niter_out, admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out, double* state_out,
                                long long state_cap, long long* nstate_out) {
-    return guarded([&] {
-        logit_ridge(x, y, n, p, 1, mem, intercept, &lambda, 1, opts,
-                    DenseOut{beta_out, niter_out, stats, {trace_out, trace_cap, ntrace_out}, {state_out, state_cap, nstate_out}});
-    });
+    return guarded([&] { logit_ridge(x, y, n, p, 1, mem, intercept, &lambda, 1, opts, DENSE_OUT_STATE); });
 }
 
 int admm_hip_logit_enet(const double* x, const double* y, int n, int p, int k, int mem, int intercept, const double* lambda, const double* alpha, int ncell,
                         const admm_opts* opts, double* beta_out, int* niter_out, admm_stats* stats) {
-    return guarded([&] { logit_enet(x, y, n, p, k, mem, intercept, lambda, alpha, ncell, opts, DenseOut{beta_out, niter_out, stats}); });
+    return guarded([&] { logit_enet(x, y, n, p, k, mem, intercept, lambda, alpha, ncell, opts, DENSE_OUT); });
 }
 
 int admm_hip_logit_enet_lambda_max(const double* x, const double* y, int n, int p, int k, int mem, int intercept, double* out) {
@@ -179,15 +189,12 @@ int admm_hip_logit_enet_lambda_max(const double* x, const double* y, int n, int 
 int admm_hip_logit_enet_state(const double* x, const double* y, int n, int p, int mem, int intercept, double lambda, double alpha, const admm_opts* opts,
                               double* beta_out, int* niter_out, admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out,
                               double* state_out, long long state_cap, long long* nstate_out) {
-    return guarded([&] {
-        logit_enet(x, y, n, p, 1, mem, intercept, &lambda, &alpha, 1, opts,
-                   DenseOut{beta_out, niter_out, stats, {trace_out, trace_cap, ntrace_out}, {state_out, state_cap, nstate_out}});
-    });
+    return guarded([&] { logit_enet(x, y, n, p, 1, mem, intercept, &lambda, &alpha, 1, opts, DENSE_OUT_STATE); });
 }
 
 int admm_hip_poisson(const double* x, const double* y, int n, int p, int k, int mem, int intercept, const double* lambda, const double* alpha, int ncell,
                      const admm_opts* opts, double* beta_out, int* niter_out, admm_stats* stats) {
-    return guarded([&] { poisson(x, y, n, p, k, mem, intercept, lambda, alpha, ncell, opts, DenseOut{beta_out, niter_out, stats}); });
+    return guarded([&] { poisson(x, y, n, p, k, mem, intercept, lambda, alpha, ncell, opts, DENSE_OUT); });
 }
 
 int admm_hip_poisson_lambda_max(const double* x, const double* y, int n, int p, int k, int mem, int intercept, double* out) {
@@ -197,44 +204,23 @@ int admm_hip_poisson_lambda_max(const double* x, const double* y, int n, int p, 
 int admm_hip_poisson_state(const double* x, const double* y, int n, int p, int mem, int intercept, double lambda, double alpha, const admm_opts* opts,
                            double* beta_out, int* niter_out, admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out,
                            double* state_out, long long state_cap, long long* nstate_out) {
-    return guarded([&] {
-        poisson(x, y, n, p, 1, mem, intercept, &lambda, &alpha, 1, opts,
-                DenseOut{beta_out, niter_out, stats, {trace_out, trace_cap, ntrace_out}, {state_out, state_cap, nstate_out}});
-    });
-}
-
-int admm_hip_logit_state(const double* x, const double* y, int n, int p, int mem, int intercept, const admm_opts* opts, double* beta_out, int* niter_out,
-                         admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out, double* state_out, long long state_cap,
-                         long long* nstate_out) {
-    return guarded([&] {
-        logit(x, y, n, p, mem, intercept, opts, DenseOut{beta_out, niter_out, stats, {trace_out, trace_cap, ntrace_out}, {state_out, state_cap, nstate_out}});
-    });
-}
-
-int admm_hip_quantreg_state(const double* x, const double* y, int n, int p, int mem, int intercept, double tau, const admm_opts* opts,
-                            double* beta_out, int* niter_out, admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out,
-                            double* state_out, long long state_cap, long long* nstate_out) {
-    return guarded([&] {
-        quantreg(x, y, n, p, mem, intercept, &tau, 1, opts, DenseOut{beta_out, niter_out, stats, {trace_out, trace_cap, ntrace_out}, {state_out, state_cap, nstate_out}});
-    });
+    return guarded([&] { poisson(x, y, n, p, 1, mem, intercept, &lambda, &alpha, 1, opts, DENSE_OUT_STATE); });
 }
 
 int admm_hip_bp(const double* x, const double* y, int n, int p, int mem,
                 const admm_opts* opts, double* beta_out, int* niter_out, admm_stats* stats) {
-    return guarded([&] { bp(x, y, n, p, mem, opts, DenseOut{beta_out, niter_out, stats}); });
+    return guarded([&] { bp(x, y, n, p, mem, opts, DENSE_OUT); });
 }
 
 int admm_hip_bp_traced(const double* x, const double* y, int n, int p, int mem, const admm_opts* opts,
                        double* beta_out, int* niter_out, admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out) {
-    return guarded([&] { bp(x, y, n, p, mem, opts, DenseOut{beta_out, niter_out, stats, {trace_out, trace_cap, ntrace_out}}); });
+    return guarded([&] { bp(x, y, n, p, mem, opts, DENSE_OUT_TRACED); });
 }
 
 int admm_hip_bp_state(const double* x, const double* y, int n, int p, int mem, const admm_opts* opts,
                       double* beta_out, int* niter_out, admm_stats* stats, double* trace_out, long long trace_cap, long long* ntrace_out,
                       double* state_out, long long state_cap, long long* nstate_out) {
-    return guarded([&] {
-        bp(x, y, n, p, mem, opts, DenseOut{beta_out, niter_out, stats, {trace_out, trace_cap, ntrace_out}, {state_out, state_cap, nstate_out}});
-    });
+    return guarded([&] { bp(x, y, n, p, mem, opts, DENSE_OUT_STATE); });
 }
 
 int admm_hip_dantzig_traced(const double* x, const double* y, int n, int p, int mem,
