@@ -78,6 +78,7 @@ EXPORTS = ["admm_hip_lasso", "admm_hip_enet", "admm_hip_parlasso", "admm_hip_lad
            "admm_hip_logit", "admm_hip_logit_state", "admm_hip_logit_multi", "admm_hip_logit_ridge", "admm_hip_logit_ridge_state",
            "admm_hip_logit_enet", "admm_hip_logit_enet_lambda_max", "admm_hip_logit_enet_state", "admm_hip_test_logit_prox",
            "admm_hip_poisson", "admm_hip_poisson_lambda_max", "admm_hip_poisson_state", "admm_hip_test_poisson_prox",
+           "admm_hip_logit_enet_cv", "admm_hip_logit_enet_cv_state", "admm_hip_poisson_cv", "admm_hip_poisson_cv_state",
            "admm_hip_mtlasso", "admm_hip_mtlasso_plan_create", "admm_hip_test_symv_multi", "admm_hip_test_tall_early_exits",
            "admm_hip_sgl", "admm_hip_sgl_plan_create", "admm_hip_host_sgl_lambda0",
            "admm_hip_boxenet", "admm_hip_boxenet_plan_create", "admm_hip_host_box_lambda0",
@@ -102,17 +103,21 @@ TALL_ONLY = [("admm_hip_grplasso", _GROUP_ARGS, 5), ("admm_hip_sgl", _GROUP_ARGS
 #   array and two record blocks (trace, state); <loss>_lambda_max(x, y, n, p, k, mem, after_mem..., out)
 _RECORDS = [_c_double_p, ctypes.c_longlong, ctypes.POINTER(ctypes.c_longlong)]
 _INT = [ctypes.c_int]          # after mem: the intercept flag (admm_hip_parbp: nthread)
-#         loss           k      after mem  grid arrays         length  _traced  _state  _lambda_max
-DENSE = [("bp",          False, [],        [],                 False,  True,    True,   False),
-         ("parbp",       False, _INT,      [],                 False,  True,    False,  False),
-         ("lad",         False, _INT,      [],                 False,  True,    True,   False),
-         ("quantreg",    False, _INT,      [_c_double_p],      True,   False,   True,   False),
-         ("huber",       False, _INT,      [_c_double_p] * 2,  True,   False,   True,   False),
-         ("logit",       False, _INT,      [],                 False,  False,   True,   False),
-         ("logit_multi", True,  _INT,      [],                 False,  False,   False,  False),
-         ("logit_ridge", True,  _INT,      [_c_double_p],      True,   False,   True,   False),
-         ("logit_enet",  True,  _INT,      [_c_double_p] * 2,  True,   False,   True,   True),
-         ("poisson",     True,  _INT,      [_c_double_p] * 2,  True,   False,   True,   True)]
+#         loss           k      after mem  grid arrays         length  _traced  _state  _lambda_max  _cv
+DENSE = [("bp",          False, [],        [],                 False,  True,    True,   False,       False),
+         ("parbp",       False, _INT,      [],                 False,  True,    False,  False,       False),
+         ("lad",         False, _INT,      [],                 False,  True,    True,   False,       False),
+         ("quantreg",    False, _INT,      [_c_double_p],      True,   False,   True,   False,       False),
+         ("huber",       False, _INT,      [_c_double_p] * 2,  True,   False,   True,   False,       False),
+         ("logit",       False, _INT,      [],                 False,  False,   True,   False,       False),
+         ("logit_multi", True,  _INT,      [],                 False,  False,   False,  False,       False),
+         ("logit_ridge", True,  _INT,      [_c_double_p],      True,   False,   True,   False,       False),
+         ("logit_enet",  True,  _INT,      [_c_double_p] * 2,  True,   False,   True,   True,        True),
+         ("poisson",     True,  _INT,      [_c_double_p] * 2,  True,   False,   True,   True,        True)]
+#   <loss>_cv: the grid form with the folds (fold_id, nfolds) behind `after mem` and the tables cv_mean, cv_se, fold_dev, fold_niter,
+#   fold_beta, idx_min, idx_1se between niter and stats; <loss>_cv_state: the _state form with fold_id, nfolds and the fold held out
+_FOLDS = [_c_int_p, ctypes.c_int]
+_CV_TABLES = [_c_double_p] * 3 + [_c_int_p, _c_double_p, _c_int_p, _c_int_p]
 
 TRACE_FIELDS = 12
 TRACE_COLD, TRACE_CONVERGED, TRACE_ACCELERATE, TRACE_RESTART = -1, 0, 1, 2
@@ -154,7 +159,7 @@ def load():
                                           ctypes.POINTER(AdmmOpts), _c_double_p, _c_float_p, _c_int_p, ctypes.POINTER(AdmmStats)])
     lib.admm_hip_lasso_multi.restype = ctypes.c_int
     dense_out = [ctypes.POINTER(AdmmOpts), _c_double_p, _c_int_p, ctypes.POINTER(AdmmStats)]
-    for loss, has_k, after_mem, grid, count, traced, state, lambda_max in DENSE:
+    for loss, has_k, after_mem, grid, count, traced, state, lambda_max, cv in DENSE:
         head = [_DP, _DP, ctypes.c_int, ctypes.c_int, ctypes.c_int] + after_mem               # x, y, n, p, mem, ...
         head_k = head[:4] + [ctypes.c_int] + head[4:] if has_k else head
         forms = [("", head_k + grid + [ctypes.c_int] * count + dense_out)]
@@ -164,6 +169,9 @@ def load():
             forms.append(("_state", head + [g._type_ for g in grid] + dense_out + _RECORDS * 2))
         if lambda_max:
             forms.append(("_lambda_max", head_k + [_c_double_p]))
+        if cv:
+            forms.append(("_cv", head_k + _FOLDS + grid + [ctypes.c_int] * count + dense_out[:3] + _CV_TABLES + dense_out[3:]))
+            forms.append(("_cv_state", head + _FOLDS + [ctypes.c_int] + [g._type_ for g in grid] + dense_out + _RECORDS * 2))
         for suffix, args in forms:
             fn = getattr(lib, "admm_hip_" + loss + suffix)
             fn.argtypes, fn.restype = args, ctypes.c_int

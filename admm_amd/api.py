@@ -365,13 +365,14 @@ def _state_args(sbuf, nst):
 # ---- the dense builders: basis pursuit, LAD and the losses on LAD's loop.  What they share is written once, here: the call into the
 # library (_dense_call), the argument rules of the builders and the base of the result classes.
 
-def _dense_call(model, entry, lead, grid, nfit, dim, trace=False, state=0, k=None, width=None, records_only=False):
+def _dense_call(model, entry, lead, grid, nfit, dim, trace=False, state=0, k=None, width=None, records_only=False, tables=()):
     """The one path from a dense builder's fit() into the library.  `entry` is admm_hip_<loss>; `lead` its arguments between mem and
     the grid (the intercept flag; nthread for admm_hip_parbp); `grid` the loss's parameter arrays, one fit per entry (k fits where the
     symbol takes `k`); `nfit` the number of fits; `dim` the length of one iterate (None: the symbol has a _traced form only).
     Without trace this calls `entry`(x, y, n, p[, k], mem, lead..., grid arrays..., their length, opts, beta, niter, stats); with
     trace -- and always with records_only: ADMM_BP and ADMM_LAD use no other form -- `entry`_state, which takes the FIRST value of every
     grid array, never k or a length, and then the trace block and the state block (`state` records; ignored without trace).
+    `tables`: further output arrays of the grid form, between niter and stats (the cross-validation tables of <loss>_cv).
     -> (beta: flat float64, nfit times `width` (default p + 1); niter: int32 nfit; stats: dict; trace records or None; state records or None)."""
     lib = _lib.load()
     xp, xmem, xk = as_input(model.x)
@@ -393,8 +394,9 @@ def _dense_call(model, entry, lead, grid, nfit, dim, trace=False, state=0, k=Non
             records += _state_args(sbuf, nst)
         check(getattr(lib, entry + ("_traced" if dim is None else "_state"))(xp, yp, model.n, model.p, xmem, *lead, *(float(g[0]) for g in grid), *out, *records))
     else:
+        ip = ctypes.POINTER(ctypes.c_int)
         check(getattr(lib, entry)(xp, yp, model.n, model.p, *(() if k is None else (k,)), xmem, *lead, *(g.ctypes.data_as(dp) for g in grid),
-                                  *((int(grid[0].size),) if grid else ()), *out))
+                                  *((int(grid[0].size),) if grid else ()), *out[:3], *(t.ctypes.data_as(ip if t.dtype == np.int32 else dp) for t in tables), out[3]))
     # every buffer whose address went into the call -- x and y as converted (xk, yk), the grid arrays, beta, niter and the record buffers -- is
     # a local of this frame and so alive until the call has returned: fit() passes its arrays in, never bare pointers
     return (beta, niter, stats.as_dict(), tr[:ntr.value].copy() if trace else None,
@@ -928,6 +930,92 @@ class ADMM_Poisson(ADMM_LogitEnet):
         return ADMM_LogitEnet.fit(self, trace, state)
 
 
+class ADMM_LogitEnetCV_fit(ADMM_LogitEnet_fit):
+    """The full-data fit (lam, alpha, beta, niter as ADMM_LogitEnet_fit's) and the cross-validation tables: cv_mean, cv_se (k x ncell),
+    fold_dev, fold_niter (nfolds x k x ncell), fold_beta (nfolds x (p + 1) x k x ncell), idx_min, idx_1se (k: cell indices), lambda_min,
+    lambda_1se (k: lam at those cells), fold_id (n).  A fit with trace carries none of them."""
+    _title = "ADMM elastic-net logistic regression cross-validation result"
+
+
+class ADMM_PoissonCV_fit(ADMM_LogitEnetCV_fit):
+    _title = "ADMM Poisson regression cross-validation result"
+
+
+def _cv_folds(model, nfolds, fold_id):
+    """The folds of a cross-validation builder: nfolds within [2, n]; fold_id None (row i in fold i mod nfolds) or n integers in
+    [0, nfolds), every fold present."""
+    nfolds = int(nfolds)
+    if nfolds < 2 or nfolds > model.n:
+        _stop("nfolds must be within [2, nrow(x)]")
+    if fold_id is not None:
+        fold_id = np.asarray(fold_id)
+        if fold_id.shape != (model.n,) or not np.issubdtype(fold_id.dtype, np.integer):
+            _stop("fold_id must hold nrow(x) integers")
+        if fold_id.min() < 0 or fold_id.max() >= nfolds:
+            _stop("fold_id entries must be within [0, nfolds)")
+        if np.unique(fold_id).size != nfolds:
+            _stop("every fold needs at least one held-out row")
+        fold_id = np.ascontiguousarray(fold_id, dtype=np.int32)
+    model.nfolds, model.fold_id = nfolds, fold_id
+
+
+def _cv_fit(model, trace, state, fold):
+    """fit() of the cross-validation builders: <entry>_cv for the grid, <entry>_cv_state for one column, one cell and one fold."""
+    ip = ctypes.POINTER(ctypes.c_int)
+    folds = (None if model.fold_id is None else model.fold_id.ctypes.data_as(ip), model.nfolds)
+    fold = int(fold)
+    if trace or state:
+        if model.k != 1 or model.nlambda != 1:
+            _stop(f"trace and state are recorded for a single {model._column} and a single cell")
+        if fold < -1 or fold >= model.nfolds:
+            _stop("fold must be within [-1, nfolds)")
+    grid = model._cells()
+    ncell, k, p, F = int(grid[0].size), model.k, model.p, model.nfolds
+    if trace:
+        beta, niter, stats, tr, st = _dense_call(model, model._entry + "_cv", (int(model.intercept), *folds, fold), grid, 1, model.n + p, trace, state)
+        return _with_records(model._cv_fit_class(*(g.copy() for g in grid), beta, int(niter[0]), stats), tr, st)
+    tables = [np.zeros(k * ncell), np.zeros(k * ncell), np.zeros(F * k * ncell), np.zeros(F * k * ncell, dtype=np.int32), np.zeros(F * k * ncell * (p + 1)),
+              np.zeros(k, dtype=np.int32), np.zeros(k, dtype=np.int32)]
+    beta, niter, stats, _, _ = _dense_call(model, model._entry + "_cv", (int(model.intercept), *folds), grid, k * ncell, model.n + p, k=k, tables=tables)
+    fit = model._cv_fit_class(*(g.copy() for g in grid), beta.reshape((p + 1, k, ncell), order="F"), niter.reshape((k, ncell), order="F"), stats)
+    fit.cv_mean, fit.cv_se = (t.reshape((k, ncell), order="F") for t in tables[:2])
+    fit.fold_dev, fit.fold_niter = (t.reshape((F, ncell, k)).transpose(0, 2, 1) for t in tables[2:4])
+    fit.fold_beta = tables[4].reshape((F, ncell, k, p + 1)).transpose(0, 3, 2, 1)
+    fit.idx_min, fit.idx_1se = tables[5], tables[6]
+    fit.lambda_min, fit.lambda_1se = fit.lam[fit.idx_min], fit.lam[fit.idx_1se]
+    fit.fold_id = np.arange(model.n, dtype=np.int32) % F if model.fold_id is None else model.fold_id.copy()
+    return _with_records(fit, None, None)
+
+
+class ADMM_LogitEnetCV(ADMM_LogitEnet):
+    """K-fold cross-validation of ADMM_LogitEnet's (column, cell) grid by held-out binomial deviance (admm_hip_logit_enet_cv): all
+    k x ncell x (nfolds + 1) fits on the full-data setup -- a held-out row is a row without loss.  fold_id: None (row i is in fold
+    i mod nfolds) or n integers in [0, nfolds).  The folds use the full-data standardisation; deviance is the only measure."""
+    _cv_fit_class = ADMM_LogitEnetCV_fit
+
+    def __init__(self, x, Y, lam=None, alpha=1.0, nfolds=10, fold_id=None, intercept=True, nlambda=100, lambda_min_ratio=None, n=None, p=None, k=None):
+        ADMM_LogitEnet.__init__(self, x, Y, lam, alpha, intercept, nlambda, lambda_min_ratio, n, p, k)
+        _cv_folds(self, nfolds, fold_id)
+
+    def fit(self, trace=False, state=0, fold=-1):
+        """-> ADMM_LogitEnetCV_fit.  trace / state (admm_hip_logit_enet_cv_state) for one column and one cell only, with `fold` held
+        out (-1: none): record 0's z slot then carries the tags the loop ran with, 2.0 on the held-out rows."""
+        return _cv_fit(self, trace, state, fold)
+
+
+class ADMM_PoissonCV(ADMM_Poisson):
+    """K-fold cross-validation of ADMM_Poisson's grid by held-out Poisson deviance (admm_hip_poisson_cv), as ADMM_LogitEnetCV."""
+    _cv_fit_class = ADMM_PoissonCV_fit
+
+    def __init__(self, x, Y, lam=None, alpha=1.0, nfolds=10, fold_id=None, intercept=True, nlambda=100, lambda_min_ratio=None, n=None, p=None, k=None):
+        ADMM_Poisson.__init__(self, x, Y, lam, alpha, intercept, nlambda, lambda_min_ratio, n, p, k)
+        _cv_folds(self, nfolds, fold_id)
+
+    def fit(self, trace=False, state=0, fold=-1):
+        """-> ADMM_PoissonCV_fit.  trace / state (admm_hip_poisson_cv_state) as ADMM_LogitEnetCV.fit; the held-out tag is -2.0."""
+        return _cv_fit(self, trace, state, fold)
+
+
 class LassoPlan:
     """Prepared problem (admm_hip_lasso_plan_*): setup once, run the lambda path repeatedly.
 
@@ -1070,6 +1158,14 @@ def admm_logit_enet_ovr(x, labels, lam=None, alpha=1.0, intercept=True, nlambda=
 
 def admm_poisson(x, Y, lam=None, alpha=1.0, intercept=True, nlambda=100, lambda_min_ratio=None, **kw):
     return ADMM_Poisson(x, Y, lam, alpha, intercept, nlambda, lambda_min_ratio, **kw)
+
+
+def admm_logit_enet_cv(x, Y, lam=None, alpha=1.0, nfolds=10, fold_id=None, intercept=True, nlambda=100, lambda_min_ratio=None, **kw):
+    return ADMM_LogitEnetCV(x, Y, lam, alpha, nfolds, fold_id, intercept, nlambda, lambda_min_ratio, **kw)
+
+
+def admm_poisson_cv(x, Y, lam=None, alpha=1.0, nfolds=10, fold_id=None, intercept=True, nlambda=100, lambda_min_ratio=None, **kw):
+    return ADMM_PoissonCV(x, Y, lam, alpha, nfolds, fold_id, intercept, nlambda, lambda_min_ratio, **kw)
 
 
 def admm_bp(x, y, **kw):

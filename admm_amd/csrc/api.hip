@@ -207,6 +207,38 @@ int admm_hip_poisson_state(const double* x, const double* y, int n, int p, int m
     return guarded([&] { poisson(x, y, n, p, 1, mem, intercept, &lambda, &alpha, 1, opts, DENSE_OUT_STATE); });
 }
 
+#define GLM_CV_OUT GlmCvOut{cv_mean, cv_se, fold_dev, fold_niter, fold_beta, idx_min, idx_1se}
+
+int admm_hip_logit_enet_cv(const double* x, const double* y, int n, int p, int k, int mem, int intercept, const int* fold_id, int nfolds, const double* lambda,
+                           const double* alpha, int ncell, const admm_opts* opts, double* beta_out, int* niter_out, double* cv_mean, double* cv_se, double* fold_dev,
+                           int* fold_niter, double* fold_beta, int* idx_min, int* idx_1se, admm_stats* stats) {
+    return guarded([&] { glm_cv(false, x, y, n, p, k, mem, intercept, fold_id, nfolds, -2, lambda, alpha, ncell, opts, DENSE_OUT, GLM_CV_OUT); });
+}
+
+int admm_hip_poisson_cv(const double* x, const double* y, int n, int p, int k, int mem, int intercept, const int* fold_id, int nfolds, const double* lambda,
+                        const double* alpha, int ncell, const admm_opts* opts, double* beta_out, int* niter_out, double* cv_mean, double* cv_se, double* fold_dev,
+                        int* fold_niter, double* fold_beta, int* idx_min, int* idx_1se, admm_stats* stats) {
+    return guarded([&] { glm_cv(true, x, y, n, p, k, mem, intercept, fold_id, nfolds, -2, lambda, alpha, ncell, opts, DENSE_OUT, GLM_CV_OUT); });
+}
+
+int admm_hip_logit_enet_cv_state(const double* x, const double* y, int n, int p, int mem, int intercept, const int* fold_id, int nfolds, int fold, double lambda,
+                                 double alpha, const admm_opts* opts, double* beta_out, int* niter_out, admm_stats* stats, double* trace_out, long long trace_cap,
+                                 long long* ntrace_out, double* state_out, long long state_cap, long long* nstate_out) {
+    return guarded([&] {
+        ADMM_REQUIRE(fold >= -1, "fold must be within [-1, nfolds)");
+        glm_cv(false, x, y, n, p, 1, mem, intercept, fold_id, nfolds, fold, &lambda, &alpha, 1, opts, DENSE_OUT_STATE, GlmCvOut{});
+    });
+}
+
+int admm_hip_poisson_cv_state(const double* x, const double* y, int n, int p, int mem, int intercept, const int* fold_id, int nfolds, int fold, double lambda,
+                              double alpha, const admm_opts* opts, double* beta_out, int* niter_out, admm_stats* stats, double* trace_out, long long trace_cap,
+                              long long* ntrace_out, double* state_out, long long state_cap, long long* nstate_out) {
+    return guarded([&] {
+        ADMM_REQUIRE(fold >= -1, "fold must be within [-1, nfolds)");
+        glm_cv(true, x, y, n, p, 1, mem, intercept, fold_id, nfolds, fold, &lambda, &alpha, 1, opts, DENSE_OUT_STATE, GlmCvOut{});
+    });
+}
+
 int admm_hip_bp(const double* x, const double* y, int n, int p, int mem,
                 const admm_opts* opts, double* beta_out, int* niter_out, admm_stats* stats) {
     return guarded([&] { bp(x, y, n, p, mem, opts, DENSE_OUT); });

@@ -80,6 +80,13 @@ void poisson(const double* x, const double* y, int n, int p, int k, int mem, int
              const admm_opts* opts, const DenseOut& out);
 // out[k]: per count column max_j |x~_j'(y_c - mean(y_c))| with the intercept, max_j |x~_j'(y_c - 1)| without it
 void poisson_lambda_max(const double* x, const double* y, int n, int p, int k, int mem, int intercept, double* out);
+// admm_hip_logit_enet_cv / admm_hip_poisson_cv: K-fold cross-validation of the (column, cell) grid on the full-data setup.  fold_id: n
+// host ints in [0, nfolds), or NULL = i mod nfolds.  fold < -1: the grid call -- out: the full-data fit as logit_enet's / poisson's, cv:
+// the tables (k x ncell; fold_*: fold-major, may be NULL; idx_*: k, may be NULL).  fold >= -1: the state form, k = ncell = 1, ONE fit
+// holding out that fold (-1: none); cv is not read.
+struct GlmCvOut { double* cv_mean; double* cv_se; double* fold_dev; int* fold_niter; double* fold_beta; int* idx_min; int* idx_1se; };
+void glm_cv(bool pois, const double* x, const double* y, int n, int p, int k, int mem, int intercept, const int* fold_id, int nfolds, int fold, const double* lambda,
+            const double* alpha, int ncell, const admm_opts* opts, const DenseOut& out, const GlmCvOut& cv);
 void bp(const double* x, const double* y, int n, int p, int mem, const admm_opts* opts, const DenseOut& out);
 // admm_hip_parbp(_traced): over in-process ranks when PAR_DEVICES lists several devices; parbp_dist: this rank's columns of p_total
 void parbp(const double* x, const double* y, int n, int p, int mem, int nthread, const admm_opts* opts, const DenseOut& out);

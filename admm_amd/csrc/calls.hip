@@ -313,8 +313,11 @@ void check_label_columns(const double* y, int n, int k, int mem, std::vector<lon
 // What the grid calls on the LAD loop share behind their own argument checks: LAD's standardisation (always), the caller's ycols
 // columns of y resident on the device for the solver (labels, counts; 0: it needs the standardised response only -- with columns the
 // response the upload standardises, column 0, is replaced by zeros there), every fit's coefficients and iterations out.
+// store: what goes to the caller's coefficient and iteration tables; none: every fit's, in the solver's order.
 using GridSolve = std::function<void(DeviceData<double>&, const double*, QuantResult&, hipStream_t)>;
-void run_lad_grid(const double* x, const double* y, int n, int p, int ycols, int mem, bool icpt, const admm_opts* opts, const GridSolve& solve, const DenseOut& out) {
+using GridStore = std::function<void(const QuantResult&)>;
+void run_lad_grid(const double* x, const double* y, int n, int p, int ycols, int mem, bool icpt, const admm_opts* opts, const GridSolve& solve, const DenseOut& out,
+                  const GridStore& store = nullptr) {
     require_device();
     const double t0 = now_s();
     Stream st;
@@ -325,8 +328,11 @@ void run_lad_grid(const double* x, const double* y, int n, int p, int ycols, int
     begin_result(res.dense, d, out.trace);
     res.dense.state_cap = out.state.cap;
     solve(d, cols.p, res, st.s);
-    std::memcpy(out.beta_out, res.beta.data(), res.beta.size() * sizeof(double));
-    for (size_t k = 0; k < res.niter.size(); ++k) out.niter_out[k] = res.niter[k];
+    if (store) store(res);
+    else {
+        std::memcpy(out.beta_out, res.beta.data(), res.beta.size() * sizeof(double));
+        for (size_t k = 0; k < res.niter.size(); ++k) out.niter_out[k] = res.niter[k];
+    }
     store_state(res.dense, out.state);
     finish_result(res.dense, t0, out.trace, out.stats);
 }
@@ -421,9 +427,8 @@ void logit_ridge(const double* x, const double* y, int n, int p, int k, int mem,
 
 // admm_hip_logit_enet: logit_ridge's call with (lambda, alpha) cells in place of the lambda grid (solve_logit_enet): one fit per
 // (column, cell), all of them on ONE inverse.
-void logit_enet(const double* x, const double* y, int n, int p, int k, int mem, int intercept, const double* lambda, const double* alpha, int ncell,
-                const admm_opts* opts, const DenseOut& out) {
-    const bool icpt = intercept != 0;
+static void check_logit_enet(const double* x, const double* y, int n, int p, int k, int mem, const double* lambda, const double* alpha, int ncell, const admm_opts* opts,
+                             const DenseOut& out) {
     ADMM_REQUIRE(k >= 1, "y must have at least one column");
     ADMM_REQUIRE(lambda != nullptr && alpha != nullptr, "lambda and alpha must not be NULL");
     ADMM_REQUIRE(ncell >= 1, "lambda must have at least one value");
@@ -432,6 +437,11 @@ void logit_enet(const double* x, const double* y, int n, int p, int k, int mem, 
     ADMM_REQUIRE((k == 1 && ncell == 1) || out.trace.cap == 0, "the decision trace is recorded for a single column and a single cell");
     check_dense(x, y, n, p, mem, opts, n >= 2, "nrow(x) must be at least 2", true, out);
     check_label_columns(y, n, k, mem, nullptr);
+}
+void logit_enet(const double* x, const double* y, int n, int p, int k, int mem, int intercept, const double* lambda, const double* alpha, int ncell,
+                const admm_opts* opts, const DenseOut& out) {
+    const bool icpt = intercept != 0;
+    check_logit_enet(x, y, n, p, k, mem, lambda, alpha, ncell, opts, out);
     run_lad_grid(x, y, n, p, k, mem, icpt, opts,
                  [&](DeviceData<double>& d, const double* labels, QuantResult& res, hipStream_t st) { solve_logit_enet(d, icpt, labels, k, lambda, alpha, ncell, *opts, res, st); }, out);
 }
@@ -480,9 +490,8 @@ static void check_count_columns(const double* y, int n, int k, int mem) {
 
 // admm_hip_poisson: logit_enet's call with count columns and the Poisson likelihood (solve_poisson): one fit per (column, cell), all of
 // them on ONE inverse.  lambda = 0 is accepted -- the plain Poisson GLM -- and then needs a design of full column rank by shape.
-void poisson(const double* x, const double* y, int n, int p, int k, int mem, int intercept, const double* lambda, const double* alpha, int ncell,
-             const admm_opts* opts, const DenseOut& out) {
-    const bool icpt = intercept != 0;
+static void check_poisson(const double* x, const double* y, int n, int p, int k, int mem, bool icpt, const double* lambda, const double* alpha, int ncell, const admm_opts* opts,
+                          const DenseOut& out) {
     ADMM_REQUIRE(k >= 1, "y must have at least one column");
     ADMM_REQUIRE(lambda != nullptr && alpha != nullptr, "lambda and alpha must not be NULL");
     ADMM_REQUIRE(ncell >= 1, "lambda must have at least one value");
@@ -496,6 +505,11 @@ void poisson(const double* x, const double* y, int n, int p, int k, int mem, int
     check_dense(x, y, n, p, mem, opts, n >= 2, "nrow(x) must be at least 2", true, out);
     ADMM_REQUIRE(!unpenalised || (long long)n > (long long)p + (icpt ? 1 : 0), "lambda = 0 needs nrow(x) > ncol(x) + intercept");
     check_count_columns(y, n, k, mem);
+}
+void poisson(const double* x, const double* y, int n, int p, int k, int mem, int intercept, const double* lambda, const double* alpha, int ncell,
+             const admm_opts* opts, const DenseOut& out) {
+    const bool icpt = intercept != 0;
+    check_poisson(x, y, n, p, k, mem, icpt, lambda, alpha, ncell, opts, out);
     run_lad_grid(x, y, n, p, k, mem, icpt, opts,
                  [&](DeviceData<double>& d, const double* counts, QuantResult& res, hipStream_t st) { solve_poisson(d, icpt, counts, k, lambda, alpha, ncell, *opts, res, st); }, out);
 }
@@ -525,6 +539,106 @@ void poisson_lambda_max(const double* x, const double* y, int n, int p, int k, i
     }
     logit_enet_lambda_one(d, counts.p, k, mean.data(), lam1.data(), st.s);
     for (int c = 0; c < k; ++c) out[c] = lam1[c];
+}
+
+// admm_hip_logit_enet_cv / admm_hip_poisson_cv (and their _state forms: fold >= -1, one column, one cell): K-fold cross-validation of
+// the (column, cell) grid on ONE setup (solve_glm_cv).  The public call's own checks, then the folds': every fold non-empty, every
+// training set a valid problem of its own in every column.  Nothing is written before every check has passed.
+// Slot 0 of the solver's grid is the full-data fit (out.beta_out, out.niter_out: admm_hip_logit_enet's / admm_hip_poisson's numbers),
+// slot f + 1 fold f's.  cv_mean / cv_se: the unweighted mean over the folds and the sample sd / sqrt(F), admm_hip_lasso_cv's convention.
+void glm_cv(bool pois, const double* x, const double* y, int n, int p, int k, int mem, int intercept, const int* fold_id, int nfolds, int fold, const double* lambda,
+            const double* alpha, int ncell, const admm_opts* opts, const DenseOut& out, const GlmCvOut& cv) {
+    const bool icpt = intercept != 0, grid = fold < -1;
+    if (pois) check_poisson(x, y, n, p, k, mem, icpt, lambda, alpha, ncell, opts, out);
+    else check_logit_enet(x, y, n, p, k, mem, lambda, alpha, ncell, opts, out);
+    ADMM_REQUIRE(!grid || (cv.cv_mean != nullptr && cv.cv_se != nullptr), "cv_mean and cv_se must not be NULL");
+    ADMM_REQUIRE(nfolds >= 2 && nfolds <= n, "nfolds must be within [2, n]");
+    ADMM_REQUIRE(grid || fold < nfolds, "fold must be within [-1, nfolds)");
+    std::vector<int> fid(n), cnt(nfolds, 0);
+    for (int i = 0; i < n; ++i) {
+        fid[i] = fold_id ? fold_id[i] : i % nfolds;
+        ADMM_REQUIRE(fid[i] >= 0 && fid[i] < nfolds, "fold_id entries must be within [0, nfolds)");
+        ++cnt[fid[i]];
+    }
+    int min_tr = n;
+    for (int f = 0; f < nfolds; ++f) {
+        ADMM_REQUIRE(cnt[f] > 0, "every fold needs at least one held-out row");
+        min_tr = std::min(min_tr, n - cnt[f]);
+    }
+    {   // every training set: both classes (logit), a positive count (Poisson), in every column -- on a host copy of y (n x k)
+        std::vector<double> hy;
+        const double* yh = y;
+        if (mem != ADMM_MEM_HOST) {
+            require_device();
+            Stream cs;
+            hy.resize((size_t)n * k);
+            read_back(hy.data(), y, hy.size() * sizeof(double), cs.s);
+            yh = hy.data();
+        }
+        std::vector<long long> in(nfolds);
+        for (int c = 0; c < k; ++c) {
+            long long all = 0;
+            std::fill(in.begin(), in.end(), 0);
+            for (int i = 0; i < n; ++i) if (pois ? yh[(size_t)c * n + i] > 0.0 : yh[(size_t)c * n + i] == 1.0) { ++all; ++in[fid[i]]; }
+            for (int f = 0; f < nfolds; ++f) {
+                const long long tr = all - in[f];
+                if (pois) ADMM_REQUIRE(tr > 0, "column " + std::to_string(c) + " of y has a zero sum over the training rows of fold " + std::to_string(f));
+                else ADMM_REQUIRE(tr > 0 && tr < n - cnt[f], "column " + std::to_string(c) + " of y lacks a class in the training rows of fold " + std::to_string(f));
+            }
+        }
+    }
+    if (pois)
+        for (int l = 0; l < ncell; ++l) ADMM_REQUIRE(lambda[l] != 0.0 || (long long)min_tr > (long long)p + (icpt ? 1 : 0), "lambda = 0 needs more training rows than ncol(x) + intercept in every fold");
+
+    GlmFolds folds;
+    folds.id = &fid; folds.nfolds = nfolds; folds.single = grid ? -2 : fold;
+    std::vector<double> dev;
+    const GridSolve solve = [&](DeviceData<double>& d, const double* cols, QuantResult& res, hipStream_t st) {
+        solve_glm_cv(pois, d, icpt, cols, k, folds, lambda, alpha, ncell, *opts, res, grid ? &dev : nullptr, st);
+    };
+    if (!grid) {                                                 // one fit: run_lad_grid's own store
+        run_lad_grid(x, y, n, p, k, mem, icpt, opts, solve, out);
+        return;
+    }
+    // the solver's fits are cell-major, then slot, then column: slot 0 to the caller's tables, slot f + 1 to fold f's
+    const int nslot = nfolds + 1;
+    const size_t bcol = (size_t)p + 1, npair = (size_t)k * ncell;
+    run_lad_grid(x, y, n, p, k, mem, icpt, opts, solve, out, [&](const QuantResult& res) {
+        for (int l = 0; l < ncell; ++l)
+            for (int s = 0; s < nslot; ++s)
+                for (int c = 0; c < k; ++c) {
+                    const size_t fit = ((size_t)l * nslot + s) * k + c, pair = (size_t)l * k + c;
+                    const double* b = res.beta.data() + fit * bcol;
+                    if (s == 0) {
+                        std::memcpy(out.beta_out + pair * bcol, b, bcol * sizeof(double));
+                        out.niter_out[pair] = res.niter[fit];
+                    } else {
+                        if (cv.fold_beta) std::memcpy(cv.fold_beta + ((size_t)(s - 1) * npair + pair) * bcol, b, bcol * sizeof(double));
+                        if (cv.fold_niter) cv.fold_niter[(size_t)(s - 1) * npair + pair] = res.niter[fit];
+                    }
+                }
+    });
+    if (cv.fold_dev) std::memcpy(cv.fold_dev, dev.data(), dev.size() * sizeof(double));
+    for (size_t q = 0; q < npair; ++q) {
+        double m = 0;
+        for (int f = 0; f < nfolds; ++f) m += dev[(size_t)f * npair + q];
+        m /= nfolds;
+        double v = 0;
+        for (int f = 0; f < nfolds; ++f) { const double e = dev[(size_t)f * npair + q] - m; v += e * e; }
+        cv.cv_mean[q] = m;
+        cv.cv_se[q] = std::sqrt(v / (nfolds - 1) / nfolds);
+    }
+    for (int c = 0; c < k; ++c) {
+        int imin = 0;
+        for (int l = 1; l < ncell; ++l) if (cv.cv_mean[(size_t)l * k + c] < cv.cv_mean[(size_t)imin * k + c]) imin = l;
+        // the one-standard-error rule among the cells of the minimum's alpha: the largest lambda within one standard error
+        const double bound = cv.cv_mean[(size_t)imin * k + c] + cv.cv_se[(size_t)imin * k + c];
+        int i1se = imin;
+        for (int l = 0; l < ncell; ++l)
+            if (alpha[l] == alpha[imin] && lambda[l] > lambda[i1se] && cv.cv_mean[(size_t)l * k + c] <= bound) i1se = l;
+        if (cv.idx_min) cv.idx_min[c] = imin;
+        if (cv.idx_1se) cv.idx_1se[c] = i1se;
+    }
 }
 
 void bp(const double* x, const double* y, int n, int p, int mem, const admm_opts* opts, const DenseOut& out) {

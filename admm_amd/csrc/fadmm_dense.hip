@@ -235,14 +235,29 @@ __device__ __forceinline__ double prox2(double v, double hi, double lo, double d
 // fits carry c_hi = 1.0 (LadProx's default), so the c_hi / rho the serial kernels once formed for them is the same double.  The rows
 // kernels pass a callable that reads LDS on every call: the tag is read again behind the Newton iteration (the barrier below keeps the
 // two reads apart), not held in registers across it.
+// The enet kinds know one more tag, the HELD-OUT data row of a cross-validation fold (admm_hip_logit_enet_cv, admm_hip_poisson_cv): its
+// loss is zero and the prox of the zero function is the identity, z = v.  The fold's fit on the full matrix is then the training rows'
+// problem.  No call but the cross-validation's writes these two values into a tag matrix.
+constexpr double kHeldOutLogitE = 2.0, kHeldOutPoisE = -2.0;
+// A held-out row is no row of the fold's problem: it stays out of the norms ||x||, ||z||, ||y|| the stop thresholds are scaled by (and
+// out of their sqrt(rows): LadProx::live_rows), so a fold's fit stops where the training rows' own loop would measure itself.  Its
+// residuals stay in: r is zero there up to rounding and z - z_old is what the x-update moved.
+template <int PROX>
+__device__ __forceinline__ bool row_held_out(double tag) {
+    if constexpr (PROX == kProxPoisE) return tag == kHeldOutPoisE;
+    else if constexpr (PROX == kProxLogitE) return tag == kHeldOutLogitE;
+    else return false;
+}
 template <int PROX, class TAG>
 __device__ __forceinline__ double row_prox_tagged(double v, TAG tag, double c_hi, double c_lo, double rho) {
 #pragma clang fp contract(off)
     if constexpr (PROX == kProxPoisE) {
-        const double cnt = tag();                                    // >= 0: a data row's count; the marker -1.0: a penalty row
+        const double cnt = tag();                                    // >= 0: a data row's count; the marker -1.0: a penalty row; -2.0: held out
+        if (cnt == kHeldOutPoisE) return v;
         return cnt < 0.0 ? enet2(v, c_hi, c_lo, rho) : pois2(v, cnt, 1.0 / rho);
     } else {
         if (PROX == kProxLogitR && tag() == 0.0) return v * (rho / (1.0 + rho));
+        if (PROX == kProxLogitE && tag() == kHeldOutLogitE) return v;
         if (PROX == kProxLogitE && tag() == 0.0) return enet2(v, c_hi, c_lo, rho);
         const double zs = logit2(tag() * v, 1.0 / rho);              // s logit2(s v, t)
         asm volatile("" ::: "memory");
@@ -441,7 +456,12 @@ struct QuantGrid {
 struct QuantGridZ : QuantGrid {
     double* zpen;                             // [ntau][zrows]
     int zrow0, zrows;
+    const double* sqd;                        // [ntau] sqrt(rows that carry a loss) of every fit (cross-validation folds), or NULL: sqrt(dim) for all
 };
+template <class GRID>
+__device__ __forceinline__ void quant_fit_rows(DenseParams& q, const GRID& G, int fit) {
+    if constexpr (std::is_same<GRID, QuantGridZ>::value) { if (G.sqd != nullptr) q.sqrt_dim = G.sqd[fit]; }
+}
 // slot s: every buffer of slot 0 shifted by s * stride doubles, its pair of control blocks behind slot 0's
 __device__ __forceinline__ DenseParams quant_slot_params(DenseParams q, int s, long long stride) {
     const size_t o = (size_t)s * (size_t)stride;
@@ -475,10 +495,11 @@ quant_head_kernel(DenseParams q0, GRID G, int par) {
     int take = -1;
     bool all_idle = true;
     for (int s = 0; s < G.nslots; ++s) {
-        const DenseParams qs = quant_slot_params(q0, s, G.slot_stride);
+        DenseParams qs = quant_slot_params(q0, s, G.slot_stride);
         const DenseCtl cs = load_ctl_vector(qs.ctl + par);
         if (s == me) in = cs;
         if (cs.done) continue;                                   // idle (uniform)
+        quant_fit_rows(qs, G, cs.pad);
         dense_head_sums(qs, pstage, sums);
         const DenseDecision Ds = dense_decide(qs, cs, sums);
         int tk = -1;
@@ -490,7 +511,7 @@ quant_head_kernel(DenseParams q0, GRID G, int par) {
         G.next[par ^ 1] = next;
         if (all_idle) *q0.done = 1;
     }
-    const DenseParams q = quant_slot_params(q0, me, G.slot_stride);
+    DenseParams q = quant_slot_params(q0, me, G.slot_stride);
     DenseCtl* outp = &q.ctl[par ^ 1];
     if (in.done) {
         if (lead) *outp = in;
@@ -526,6 +547,7 @@ quant_head_kernel(DenseParams q0, GRID G, int par) {
     // the cold start of quantile `take`: what dense_init_kernel + the first head of a single run leave (the stale X'z, X'y of the other
     // parity and the stale partials are multiplied by zero or skipped under `first`, the norm partials are not read)
     const DenseCtl c0 = dense_cold_ctl(G.rho0, take);
+    quant_fit_rows(q, G, take);
     const double zeros[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     const DenseDecision D0 = dense_decide(q, c0, zeros);
     if (lead) *outp = D0.out;
@@ -593,7 +615,7 @@ template <int NPT, bool LANE_NORMS, int PROX>
 __device__ __forceinline__ void lad_row_step(int i, int tid, double x, double dv, const LadRowIn& in, double rho, double pen_hi, double pen_lo, double delta,
                                              double* __restrict__ xo, double* __restrict__ zn_, double* __restrict__ yn_,
                                              double* state, long long state_cap, int total, int dim,
-                                             double* nacc, const double2 (&rv)[NPT], double2 (&az)[NPT], double2 (&ay)[NPT], double zlogit = 0.0) {
+                                             double* nacc, const double2 (&rv)[NPT], double2 (&az)[NPT], double2 (&ay)[NPT], double zlogit = 0.0, bool held = false) {
     double zn, yn;
     {
 #pragma clang fp contract(off)
@@ -604,12 +626,13 @@ __device__ __forceinline__ void lad_row_step(int i, int tid, double x, double dv
         if (LANE_NORMS && tid < 6) {
             const double dz = zn - in.zc, daz = zn - in.ajz;
             const double t = tid == 0 ? rr : (tid == 1 ? dz : (tid == 2 ? daz : (tid == 3 ? x : (tid == 4 ? zn : yn))));
-            nacc[0] += t * t;
+            if (!(kProxKinds[PROX].enet && held && tid >= 3)) nacc[0] += t * t;     // (held: a cross-validation fold's held-out row, row_held_out)
         }
         if (tid == 0) {
             if (!LANE_NORMS) {
                 const double dz = zn - in.zc, daz = zn - in.ajz;
-                nacc[0] += rr * rr; nacc[1] += dz * dz; nacc[2] += daz * daz; nacc[3] += x * x; nacc[4] += zn * zn; nacc[5] += yn * yn;
+                nacc[0] += rr * rr; nacc[1] += dz * dz; nacc[2] += daz * daz;
+                if (!(kProxKinds[PROX].enet && held)) { nacc[3] += x * x; nacc[4] += zn * zn; nacc[5] += yn * yn; }
             }
             xo[i] = x; zn_[i] = zn; yn_[i] = yn;
             if (state != nullptr && total < state_cap) {
@@ -706,7 +729,7 @@ lad_rows_kernel(DenseParams q, int par, const double* __restrict__ Xt, long long
             LadRowIn in;
             in.ajy = uni[buf][R + r]; in.ajz = uni[buf][2 * R + r]; in.zc = uni[buf][3 * R + r];
             lad_row_step<NPT, false, PROX>(i, tid, x, SIGNED ? 0.0 : uni[buf][r], in, rho, pen_hi, pen_lo, delta, q.x, zn_, yn_, q.state, q.state_cap, c.total, q.dim, nacc,
-                                           rv[r], az, ay, read_lane_f64(zl, r));
+                                           rv[r], az, ay, read_lane_f64(zl, r), row_held_out<PROX>(uni[buf][r]));
         }
         buf ^= 1;
     };
@@ -877,8 +900,10 @@ quant_rows_kernel(DenseParams q0, long long slot_stride, const double* __restric
                 LadRowIn in;
                 in.ajy = uni[buf][(NB + NV * s) * R + r]; in.ajz = uni[buf][(NB + 1 + NV * s) * R + r]; in.zc = uni[buf][(NB + 2 + NV * s) * R + r];
                 double zrow = 0.0;
+                bool held = false;
                 if constexpr (LOGIT) zrow = read_lane_f64(zl, s * R + r);
-                lad_row_step<NPT, true, PROX>(i, tid, x, LOGIT ? 0.0 : uni[buf][r], in, rho[s], pen_hi[s], pen_lo[s], delta[s], q0.x + so, zn_, yn_, nullptr, 0, 0, q0.dim, nacc[s], rv[r], az[s], ay[s], zrow);
+                if constexpr (ENET) held = row_held_out<PROX>(uni[buf][(NB + 3 + NV * s) * R + r]);
+                lad_row_step<NPT, true, PROX>(i, tid, x, LOGIT ? 0.0 : uni[buf][r], in, rho[s], pen_hi[s], pen_lo[s], delta[s], q0.x + so, zn_, yn_, nullptr, 0, 0, q0.dim, nacc[s], rv[r], az[s], ay[s], zrow, held);
             }
         }
         buf ^= 1;
@@ -926,11 +951,13 @@ dense_tail_kernel(DenseParams q, int par, double knee) {
         for (int s = 0; s < q.gout_nseg; ++s) g += q.gout[(size_t)s * q.gout_stride + i];
         const double adjy = q.adj_y[i], adjz = q.adj_z[i], zc = zc_[i];
         double x, zn, r;
+        bool held = false;
         if (q.prob == 0) {                        // LAD: x = P_X(vec); z = prox(x - y + adj_y/rho; c_hi/rho, c_lo/rho); r = x - y - z
             x = g;
             const double d = q.data_vec[i];
             if constexpr (kProxKinds[PROX].tagged) {
                 const double tg = q.sgn[i];
+                held = row_held_out<PROX>(tg);
                 zn = row_prox_tagged<PROX>(x - d + adjy / rho, [tg] { return tg; }, q.c_hi, q.c_lo, rho);
             } else zn = prox2<PROX>(x - d + adjy / rho, pen_hi, pen_lo, delta);
             r = x - d - zn;
@@ -941,7 +968,8 @@ dense_tail_kernel(DenseParams q, int par, double knee) {
         }
         const double yn = adjy + rho * r;
         const double dz = zn - zc, daz = zn - adjz;
-        acc[0] += r * r; acc[1] += dz * dz; acc[2] += daz * daz; acc[3] += x * x; acc[4] += zn * zn; acc[5] += yn * yn;
+        acc[0] += r * r; acc[1] += dz * dz; acc[2] += daz * daz;
+        if (!held) { acc[3] += x * x; acc[4] += zn * zn; acc[5] += yn * yn; }
         q.x[i] = x; zn_[i] = zn; yn_[i] = yn;
         if (q.state != nullptr && c.total < q.state_cap) {     // record c.total = the trace record that will judge this iteration
             double* s = q.state + (size_t)c.total * 5 * q.dim;
@@ -1085,6 +1113,7 @@ struct LadProx {
                                                // kProxLogitE: the same; fit k's column is k mod ncols of the matrix at fits[0].signs, and c_hi / c_lo are the penalty rows' constants
                                                // kProxPoisE: the E form's layout with the counts in the signs' place, -1.0 on the penalty rows and the padding
     int ncols = 0;                             // kProxLogitE, kProxPoisE: the label (count) columns of the sign matrix
+    int live_rows = 0;                         // cross-validation folds: the rows that carry a loss (all but the held-out ones), the `rows` of the stop thresholds; 0: all
 };
 
 // M = G0 + lambda D, D = 1 on the first p0 diagonal entries (the user's columns; the intercept's entry is not shifted): one pass, both
@@ -1251,6 +1280,7 @@ struct LadProblem {
         DenseLoop L;
         L.init(n, 0, opts, d.Y.get(), ynorm, st, res.trace_cap, res.state_cap, onepass ? lad_nwg : 0);
         L.q.c_hi = px.c_hi; L.q.c_lo = px.c_lo; L.delta = px.delta; L.prox = px.kind;
+        if (px.live_rows > 0) L.q.sqrt_dim = std::sqrt((double)px.live_rows);
         if (kProxKinds[px.kind].tagged) L.q.sgn = px.signs;
         if (px.kind == kProxHuber && res.state_cap > 0) {       // iterate dump: record 0 also carries the knee as the loop holds it (delta / scaleY), first entry of its z slot
             ADMM_HIP_CHECK(hipMemcpyAsync(L.state.get() + n, &px.delta, sizeof(double), hipMemcpyHostToDevice, st));
@@ -1342,11 +1372,18 @@ struct LadProblem {
         q.c_hi = 1.0; q.c_lo = 1.0;                              // (unused: the slots' constants are chi / clo of their quantile)
         if (kProxKinds[kind].tagged) q.sgn = fits[0].signs;         // the sign matrix: a slot reads the column of the fit it holds
         q.sgn_cols = kProxKinds[kind].enet ? fits[0].ncols : 0;
-        DevBuf<double> zpen_d;
+        DevBuf<double> zpen_d, sqd_d;
         QuantGridZ G{};
         if (kProxKinds[kind].enet) {
             zpen_d.alloc((size_t)ntau * ridge_p0); zpen_d.zero(st);
             G.zpen = zpen_d.get(); G.zrow0 = n0; G.zrows = ridge_p0;
+            if (fits[0].live_rows > 0) {
+                std::vector<double> hs(ntau);
+                for (int k = 0; k < ntau; ++k) hs[k] = std::sqrt((double)fits[k].live_rows);
+                sqd_d.alloc(ntau);
+                write_device(sqd_d.get(), hs.data(), (size_t)ntau * sizeof(double));
+                G.sqd = sqd_d.get();
+            }
         }
         G.nslots = nslots; G.ntau = ntau; G.slot_stride = (long long)stride; G.rho0 = opts.rho;
         G.next = ints.get() + 1; G.idle = ints.get() + 3; G.niter = ints.get() + 3 + nslots; G.rho_fin = rho_fin.get();
@@ -1455,7 +1492,7 @@ static void append_ridge_rows(DeviceData<double>& d, int p0, hipStream_t st) {
 // d: the standardised data (DataStd flag 3 with the intercept, 1 without); with the intercept the loop fits one more column of ones.
 // fits: the grid in the units of the standardised response, all of one prox kind.  What admm_hip_quantreg and admm_hip_huber share:
 // the ones column, the setup, the choice of slots, the loops and the recovery.
-static void run_lad_fits(LadProblem& P, DeviceData<double>& d, int p0, bool intercept, const std::vector<LadProx>& fits, QuantResult& res);
+static void run_lad_fits(LadProblem& P, DeviceData<double>& d, int p0, bool intercept, const std::vector<LadProx>& fits, QuantResult& res, std::vector<double>* coef_std = nullptr);
 static void solve_lad_grid(DeviceData<double>& d, bool intercept, const admm_opts& opts, const std::vector<LadProx>& fits, QuantResult& res, hipStream_t st) {
     const int p0 = d.p;
     if (intercept) append_ones_column(d, st);
@@ -1463,8 +1500,9 @@ static void solve_lad_grid(DeviceData<double>& d, bool intercept, const admm_opt
     P.setup(res.dense.stats);
     run_lad_fits(P, d, p0, intercept, fits, res);
 }
-// the fits of a grid on a problem that is set up (d.p: the loop's columns, p0 of them the user's): the choice of slots, the loops, the recovery
-static void run_lad_fits(LadProblem& P, DeviceData<double>& d, int p0, bool intercept, const std::vector<LadProx>& fits, QuantResult& res) {
+// the fits of a grid on a problem that is set up (d.p: the loop's columns, p0 of them the user's): the choice of slots, the loops, the recovery.
+// coef_std: if given, takes the fits' coefficients on the loop's own (standardised) columns, [fit][d.p], as the recovery reads them.
+static void run_lad_fits(LadProblem& P, DeviceData<double>& d, int p0, bool intercept, const std::vector<LadProx>& fits, QuantResult& res, std::vector<double>* coef_std) {
     const int ntau = (int)fits.size();
     const int n = d.n, p = d.p;
     DenseResult& dr = res.dense;
@@ -1509,6 +1547,7 @@ static void run_lad_fits(LadProblem& P, DeviceData<double>& d, int p0, bool inte
         for (int j = 0; j < p0; ++j) col[j + 1] = out[j];
     }
     d.p = p;
+    if (coef_std != nullptr) *coef_std = std::move(coef);
 }
 
 void solve_quantreg(DeviceData<double>& d, bool intercept, const admm_opts& opts, const double* tau, int ntau, QuantResult& res, hipStream_t st) {
@@ -1621,14 +1660,18 @@ void solve_logit_multi(DeviceData<double>& d, bool intercept, const double* y_de
 // counts: `tags` writes column c of the n0 x ncol labels with leading dimension round_up(d.n, 32) and its own filler behind them), and
 // a response that is no scale.  Returns the tag matrix.
 using TagMatrixKernel = void (*)(const double*, int, int, long long, double*);
-static DevBuf<double> augment_tagged(DeviceData<double>& d, bool intercept, const double* y_dev, int ncol, TagMatrixKernel tags, hipStream_t st) {
-    const int n0 = d.n, p0 = d.p;
+static void augment_rows(DeviceData<double>& d, bool intercept, hipStream_t st) {
+    const int p0 = d.p;
     if (intercept) append_ones_column(d, st);
     append_ridge_rows(d, p0, st);
+    d.scaleY = 1.0; d.meanY = 0.0;
+}
+static DevBuf<double> augment_tagged(DeviceData<double>& d, bool intercept, const double* y_dev, int ncol, TagMatrixKernel tags, hipStream_t st) {
+    const int n0 = d.n;
+    augment_rows(d, intercept, st);
     const long long lds = round_up(d.n, 32);
     DevBuf<double> tag((size_t)lds * ncol);
     hipLaunchKernelGGL(tags, dim3((unsigned)((lds + 255) / 256), std::min(ncol, 65535)), dim3(256), 0, st, y_dev, n0, ncol, lds, tag.get());
-    d.scaleY = 1.0; d.meanY = 0.0;
     return tag;
 }
 
@@ -1677,17 +1720,150 @@ void solve_logit_ridge(DeviceData<double>& d, bool intercept, const double* y_de
 // with c = sqrt(n0) 18 - 66 (tests/test_logit_enet_host.py).  Returned: the penalty rows of the last z over c (exact zeros), the
 // intercept from get_x (run_lad_fits).  res.beta: (p + 1) x ncol x ncell, res.niter: ncol x ncell.
 // (solve_poisson is the same function with another kind and another tag matrix: solve_enet_rows.)
+//
+// Cross-validation (folds != NULL: admm_hip_logit_enet_cv, admm_hip_poisson_cv).  A held-out row is a row whose loss is zero, and the
+// prox of the zero function is the identity (row_prox_tagged's held-out tags): with it a fold's fit on the FULL augmented matrix is the
+// training rows' problem -- the held-out rows' duals vanish after the first iteration and leave the residuals.  So the matrix, its
+// Gram, the inverse, the hat matrix and the transpose are the full-data call's, formed once, and the folds are more COLUMNS of the tag
+// matrix: column s ncol + c is label (count) column c with the rows of slot s's fold tagged held out -- slot 0 holds out nothing (the
+// full-data fit), slot s >= 1 fold s - 1.  The fits run cell-major, then slot, then column, fit (cell nslot + s) ncol + c, so the
+// slotted head's fit mod sgn_cols is the fit's tag column.  folds->single >= -1: one slot only, holding out that fold (-1: none).
+// fold_dev, if given: the held-out deviance of every (fold, cell, column), glm_cv_deviance below.
+template <bool POIS>
+__global__ void __launch_bounds__(256) fold_tag_matrix_kernel(const double* __restrict__ y, int n, int ncol, int ntag, long long lds, const int* __restrict__ fold_id, int held0,
+                                                              double* __restrict__ s) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= lds) return;
+    const int fi = i < n ? fold_id[i] : -1;
+    for (int t = blockIdx.y; t < ntag; t += gridDim.y) {
+        const int c = t % ncol, held = held0 + t / ncol;             // (held -1: nothing held out)
+        double v = POIS ? -1.0 : 0.0;                                // the penalty rows and the padding: as the public calls' matrices
+        if (i < n) {
+            const double yv = y[(size_t)c * n + i];
+            v = held >= 0 && fi == held ? (POIS ? kHeldOutPoisE : kHeldOutLogitE) : (POIS ? yv : (yv == 1.0 ? 1.0 : -1.0));
+        }
+        s[(size_t)t * lds + i] = v;
+    }
+}
+
+// Held-out deviance, in double and the same bits on every run: no atomics, every sum in one fixed order.
+// Rows kernel: one wave per data row, in the order `perm` (the rows sorted by fold, stably); lane = one (cell, column) pair, 64 pairs
+// at a time.  eta = the row of the stored transpose (the standardised columns and the ones column: no second copy of X) times the
+// standardised coefficients of the fit (cell, the ROW's fold, column), which the host lays out as B[fold][column j][pair] so that a
+// wave's loads are contiguous; the row's entries are wave-uniform.  One multiply-add per column, j ascending.  A row is read by one
+// wave, once per 64 pairs.  rowdev: [position in perm][pair].
+template <bool POIS>
+__global__ void __launch_bounds__(256) glm_cv_rowdev_kernel(const double* __restrict__ Xt, long long ldxt, int p, int n, const int* __restrict__ perm,
+                                                            const int* __restrict__ fold_id, const double* __restrict__ B, int npair, int ncol,
+                                                            const double* __restrict__ y, double* __restrict__ rowdev) {
+    const int lane = threadIdx.x & 63;
+    const long long pos = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (pos >= n) return;
+    const int i = perm[pos], f = fold_id[i];
+    const double* xr = Xt + (size_t)i * ldxt;
+    for (int pair0 = 0; pair0 < npair; pair0 += 64) {
+        const int pair = pair0 + lane;
+        if (pair >= npair) break;
+        const double* b = B + (size_t)f * p * npair + pair;
+        double eta = 0.0;
+        for (int j = 0; j < p; ++j) eta = fma(xr[j], b[(size_t)j * npair], eta);
+        const double yv = y[(size_t)(pair % ncol) * n + i];
+        double dev;
+        if (POIS) {
+            const double mu = exp(eta);
+            dev = 2.0 * ((yv > 0.0 ? yv * log(yv / mu) : 0.0) - (yv - mu));
+        } else {
+            const double se = yv == 1.0 ? eta : -eta;                // s eta, s = 2 y - 1
+            dev = 2.0 * (fmax(-se, 0.0) + log1p(exp(-fabs(eta))));
+        }
+        rowdev[(size_t)pos * npair + pair] = dev;
+    }
+}
+// block (pair, f): the mean of rowdev over the positions [off[f], off[f + 1]) of fold f -- thread t adds its positions t, t + 256, ...
+// in order, the 256 sums meet in a fixed tree
+__global__ void __launch_bounds__(256) glm_cv_fold_mean_kernel(const double* __restrict__ rowdev, int npair, const int* __restrict__ off, double* __restrict__ out) {
+    __shared__ double m[256];
+    const int pair = blockIdx.x, f = blockIdx.y;
+    const int lo = off[f], hi = off[f + 1];
+    double s = 0.0;
+    for (int q = lo + (int)threadIdx.x; q < hi; q += 256) s += rowdev[(size_t)q * npair + pair];
+    m[threadIdx.x] = s;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if ((int)threadIdx.x < h) m[threadIdx.x] += m[threadIdx.x + h];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[(size_t)f * npair + pair] = m[0] / (double)(hi - lo);
+}
+// fold_dev[(f ncell + l) ncol + c] = the mean deviance of fold f's rows under the fit (cell l, slot f + 1, column c).  coef: the fits'
+// standardised coefficients [fit][p] (run_lad_fits), p = the loop's columns; fid: the n0 fold ids on the host, fid_dev: on the device.
+static void glm_cv_deviance(bool pois, const LadProblem& P, int p, int n0, const double* y_dev, int ncol, int ncell, const std::vector<int>& fid, const int* fid_dev, int nfolds,
+                            const std::vector<double>& coef, std::vector<double>& fold_dev, hipStream_t st) {
+    const int npair = ncol * ncell, nslot = nfolds + 1;
+    std::vector<int> off(nfolds + 1, 0), perm(n0);
+    for (int i = 0; i < n0; ++i) ++off[fid[i] + 1];
+    for (int f = 0; f < nfolds; ++f) off[f + 1] += off[f];
+    { std::vector<int> at(off.begin(), off.end() - 1); for (int i = 0; i < n0; ++i) perm[at[fid[i]]++] = i; }
+    std::vector<double> hB((size_t)nfolds * p * npair);
+    for (int f = 0; f < nfolds; ++f)
+        for (int l = 0; l < ncell; ++l)
+            for (int c = 0; c < ncol; ++c) {
+                const double* b = coef.data() + (((size_t)l * nslot + f + 1) * ncol + c) * p;
+                for (int j = 0; j < p; ++j) hB[((size_t)f * p + j) * npair + (size_t)l * ncol + c] = b[j];
+            }
+    DevBuf<double> B(hB.size()), rowdev((size_t)n0 * npair), out((size_t)nfolds * npair);
+    DevBuf<int> perm_d(n0), off_d(nfolds + 1);
+    ADMM_HIP_CHECK(hipMemcpyAsync(B.get(), hB.data(), hB.size() * sizeof(double), hipMemcpyHostToDevice, st));
+    ADMM_HIP_CHECK(hipMemcpyAsync(perm_d.get(), perm.data(), perm.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    ADMM_HIP_CHECK(hipMemcpyAsync(off_d.get(), off.data(), off.size() * sizeof(int), hipMemcpyHostToDevice, st));
+    const dim3 grid((unsigned)((n0 + 3) / 4));
+    if (pois) hipLaunchKernelGGL(glm_cv_rowdev_kernel<true>, grid, dim3(256), 0, st, P.Xt.get(), P.ldxt, p, n0, perm_d.get(), fid_dev, B.get(), npair, ncol, y_dev, rowdev.get());
+    else hipLaunchKernelGGL(glm_cv_rowdev_kernel<false>, grid, dim3(256), 0, st, P.Xt.get(), P.ldxt, p, n0, perm_d.get(), fid_dev, B.get(), npair, ncol, y_dev, rowdev.get());
+    for (int f0 = 0; f0 < nfolds; f0 += 65535)                   // (the grid's y extent)
+        hipLaunchKernelGGL(glm_cv_fold_mean_kernel, dim3(npair, std::min(65535, nfolds - f0)), dim3(256), 0, st, rowdev.get(), npair, off_d.get() + f0, out.get() + (size_t)f0 * npair);
+    ADMM_HIP_CHECK(hipGetLastError());
+    fold_dev.assign((size_t)nfolds * npair, 0.0);
+    read_back(fold_dev.data(), out.get(), fold_dev.size() * sizeof(double), st);
+}
+
 static void solve_enet_rows(int kind, TagMatrixKernel tags, DeviceData<double>& d, bool intercept, const double* y_dev, int ncol, const double* lambda, const double* alpha,
-                            int ncell, const admm_opts& opts, QuantResult& res, hipStream_t st) {
+                            int ncell, const admm_opts& opts, QuantResult& res, hipStream_t st, const GlmFolds* folds = nullptr, std::vector<double>* fold_dev = nullptr) {
     const int n0 = d.n, p0 = d.p;
-    const DevBuf<double> tag = augment_tagged(d, intercept, y_dev, ncol, tags, st);
+    const bool pois = kind == kProxPoisE;
+    const int nslot = folds == nullptr || folds->single >= -1 ? 1 : folds->nfolds + 1;
+    const int ntag = ncol * nslot;
+    DevBuf<double> tag;
+    DevBuf<int> fid_d;
+    if (folds == nullptr) {
+        tag = augment_tagged(d, intercept, y_dev, ncol, tags, st);
+    } else {
+        augment_rows(d, intercept, st);
+        fid_d.alloc(n0);
+        ADMM_HIP_CHECK(hipMemcpyAsync(fid_d.get(), folds->id->data(), (size_t)n0 * sizeof(int), hipMemcpyHostToDevice, st));
+        const long long ldt = round_up(d.n, 32);
+        tag.alloc((size_t)ldt * ntag);
+        const dim3 grid((unsigned)((ldt + 255) / 256), std::min(ntag, 65535));
+        const int held0 = nslot == 1 ? folds->single : -1;
+        if (pois) hipLaunchKernelGGL(fold_tag_matrix_kernel<true>, grid, dim3(256), 0, st, y_dev, n0, ncol, ntag, ldt, fid_d.get(), held0, tag.get());
+        else hipLaunchKernelGGL(fold_tag_matrix_kernel<false>, grid, dim3(256), 0, st, y_dev, n0, ncol, ntag, ldt, fid_d.get(), held0, tag.get());
+    }
     const long long lds = round_up(d.n, 32);
     const double c2 = (double)n0, c = std::sqrt(c2);
-    std::vector<LadProx> fits((size_t)ncol * ncell);
+    std::vector<int> live;                                       // per slot: the rows of the loop less the held-out ones
+    if (folds != nullptr) {
+        std::vector<int> cnt(folds->nfolds, 0);
+        for (int i = 0; i < n0; ++i) ++cnt[(*folds->id)[i]];
+        for (int s = 0; s < nslot; ++s) {
+            const int held = nslot == 1 ? folds->single : s - 1;
+            live.push_back(d.n - (held >= 0 ? cnt[held] : 0));
+        }
+    }
+    std::vector<LadProx> fits((size_t)ntag * ncell);
     for (int l = 0; l < ncell; ++l)
-        for (int k = 0; k < ncol; ++k) {
-            LadProx& f = fits[(size_t)l * ncol + k];
-            f.kind = kind; f.ncols = ncol;
+        for (int k = 0; k < ntag; ++k) {
+            LadProx& f = fits[(size_t)l * ntag + k];
+            f.kind = kind; f.ncols = ntag;
+            if (folds != nullptr) f.live_rows = live[k / ncol];
             f.signs = tag.get() + (size_t)k * lds;
             f.c_hi = lambda[l] * alpha[l] / c;
             f.c_lo = lambda[l] * (1.0 - alpha[l]) / c2;
@@ -1695,7 +1871,13 @@ static void solve_enet_rows(int kind, TagMatrixKernel tags, DeviceData<double>& 
     LadProblem P(d, opts, st);
     P.setup_ridge(n0, p0, res.dense.stats);
     P.setup_lambda(c2, res.dense.stats);
-    run_lad_fits(P, d, p0, intercept, fits, res);
+    std::vector<double> coef;
+    run_lad_fits(P, d, p0, intercept, fits, res, fold_dev != nullptr ? &coef : nullptr);
+    if (fold_dev != nullptr) glm_cv_deviance(pois, P, d.p, n0, y_dev, ncol, ncell, *folds->id, fid_d.get(), folds->nfolds, coef, *fold_dev, st);
+}
+void solve_glm_cv(bool pois, DeviceData<double>& d, bool intercept, const double* y_dev, int ncol, const GlmFolds& folds, const double* lambda, const double* alpha, int ncell,
+                  const admm_opts& opts, QuantResult& res, std::vector<double>* fold_dev, hipStream_t st) {
+    solve_enet_rows(pois ? kProxPoisE : kProxLogitE, nullptr, d, intercept, y_dev, ncol, lambda, alpha, ncell, opts, res, st, &folds, folds.single >= -1 ? nullptr : fold_dev);
 }
 void solve_logit_enet(DeviceData<double>& d, bool intercept, const double* y_dev, int ncol, const double* lambda, const double* alpha, int ncell, const admm_opts& opts,
                       QuantResult& res, hipStream_t st) {

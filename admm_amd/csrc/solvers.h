@@ -171,6 +171,19 @@ void logit_enet_lambda_one(const DeviceData<double>& d, const double* y_dev, int
 // device, leading dimension n.  lambda >= 0 (0: the plain GLM, the caller checks n > p + intercept).  res as solve_logit_enet's.
 void solve_poisson(DeviceData<double>& d, bool intercept, const double* y_dev, int ncol, const double* lambda, const double* alpha, int ncell, const admm_opts& opts,
                    QuantResult& res, hipStream_t st);
+// admm_hip_logit_enet_cv / admm_hip_poisson_cv (fadmm_dense.hip): solve_logit_enet / solve_poisson with the folds as further columns of
+// the tag matrix -- a held-out row carries a tag whose prox is the identity, so every fold's fit runs on the full-data matrix, Gram
+// matrix, inverse and transpose.  folds.id: n validated fold ids in [0, nfolds).  Slots: 0 = nothing held out, s >= 1 = fold s - 1;
+// res.beta: (p + 1) x ncol x (nfolds + 1) x ncell, res.niter: ncol x (nfolds + 1) x ncell (cell-major, then slot, then column).
+// fold_dev (may be NULL): nfolds x ncell x ncol, the mean held-out deviance of fold f under its own fit, formed on the device.
+// folds.single >= -1: ONE slot, holding out that fold (-1: none) -- the state forms; no deviance.
+struct GlmFolds {
+    const std::vector<int>* id = nullptr;
+    int nfolds = 0;
+    int single = -2;
+};
+void solve_glm_cv(bool pois, DeviceData<double>& d, bool intercept, const double* y_dev, int ncol, const GlmFolds& folds, const double* lambda, const double* alpha, int ncell,
+                  const admm_opts& opts, QuantResult& res, std::vector<double>* fold_dev, hipStream_t st);
 // one reduction per column of the n x ncol counts on the device: *bad = the entries that are not finite or lie below zero (all columns),
 // sums[c] = column c's sum (ncol host values; the same bits on every run)
 void pois_column_stats(const double* y_dev, int n, int ncol, long long* bad, double* sums, hipStream_t st);

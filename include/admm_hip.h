@@ -419,6 +419,47 @@ ADMM_HIP_API int admm_hip_poisson_state(const double* x, const double* y, int n,
                          const admm_opts* opts, double* beta_out, int* niter_out, admm_stats* stats, double* trace_out, long long trace_cap,
                          long long* ntrace_out, double* state_out, long long state_cap, long long* nstate_out);
 
+/* K-fold cross-validation of admm_hip_logit_enet's / admm_hip_poisson's (column, cell) grid: cv.glmnet for family = "binomial" /
+ * "poisson", by held-out deviance.  A held-out row is a row whose loss is zero, and the prox of the zero function is the identity: a
+ * fold's fit runs on the FULL augmented matrix with its held-out rows tagged (2.0 among the signs, -2.0 among the counts), which is
+ * exactly the training rows' problem.  So the upload, the standardisation, the Gram matrix X'X + n D, the inverse (hat matrix) and the
+ * transpose are the full-data call's, formed ONCE, and the k * ncell * (nfolds + 1) fits are one grid of the loop: cell-major, then
+ * fold slot (0 = nothing held out, f + 1 = fold f), then column; slots (QUANT_SLOTS) refill across all of them.
+ * A fold's stop thresholds are the training rows' too: its held-out rows stay out of the norms that scale them and out of their sqrt(rows).
+ * fold_id[n]: host ints in [0, nfolds), or NULL = i mod nfolds (admm_hip_lasso_cv's default).
+ * beta_out[(p + 1) * k * ncell], niter_out[k * ncell]: the full-data fit, number for number what admm_hip_logit_enet / admm_hip_poisson
+ * return for the same arguments.
+ * fold_dev[nfolds * ncell * k], entry ((f * ncell + l) * k + c): the MEAN deviance of fold f's rows under fold f's fit of (c, l), formed
+ * on the device in double from the standardised coefficients and the matrix the loop holds, eta_i = b0 + x~_i'b --
+ *     binomial: 2 (max(-s eta, 0) + log1p(exp(-|eta|))), s = 2 y - 1;    Poisson: 2 (y log(y / mu) - (y - mu)), mu = exp(eta), 0 log 0 = 0
+ * -- every sum in a fixed order (no atomics): the same bits on every run.  Non-finite values are returned as they are.
+ * cv_mean[k * ncell], cv_se[k * ncell], entry l * k + c: the unweighted mean over the folds and the sample sd over the folds / sqrt(nfolds)
+ * (admm_hip_lasso_cv's convention).  idx_min[k]: per column the cell of the smallest cv_mean (the first on ties).  idx_1se[k]: among the
+ * cells with alpha = alpha[idx_min], the one with the largest lambda whose cv_mean <= cv_mean[idx_min] + cv_se[idx_min].
+ * fold_niter[nfolds * ncell * k], fold_beta[nfolds * ncell * k * (p + 1)]: fold-major, then as niter_out / beta_out.  fold_dev,
+ * fold_niter, fold_beta, idx_min and idx_1se may be NULL.
+ * Refusals (ADMM_ERR_INVALID_ARG, no output touched): the checks of admm_hip_logit_enet / admm_hip_poisson, and nfolds outside [2, n], a
+ * fold_id outside [0, nfolds), an empty fold, a training set that lacks a class (zero sum of counts) in some column, lambda = 0 (Poisson)
+ * with some training set of at most p + intercept rows.
+ * Limits: the folds use the FULL-data standardisation and c^2 = n (lambda means the same in every fold and in the final fit; glmnet
+ * re-standardises per fold); a fold's fit streams all n rows; every fit starts cold; deviance only; no observation weights, no
+ * multi-GPU form, no cross-validation of admm_hip_logit_ridge. */
+ADMM_HIP_API int admm_hip_logit_enet_cv(const double* x, const double* y, int n, int p, int k, int mem, int intercept, const int* fold_id, int nfolds,
+                         const double* lambda, const double* alpha, int ncell, const admm_opts* opts, double* beta_out, int* niter_out, double* cv_mean,
+                         double* cv_se, double* fold_dev, int* fold_niter, double* fold_beta, int* idx_min, int* idx_1se, admm_stats* stats);
+ADMM_HIP_API int admm_hip_poisson_cv(const double* x, const double* y, int n, int p, int k, int mem, int intercept, const int* fold_id, int nfolds,
+                         const double* lambda, const double* alpha, int ncell, const admm_opts* opts, double* beta_out, int* niter_out, double* cv_mean,
+                         double* cv_se, double* fold_dev, int* fold_niter, double* fold_beta, int* idx_min, int* idx_1se, admm_stats* stats);
+/* One column, one cell, one fold of the calls above (fold = -1: nothing held out; the folds' checks are those of the grid call), with the
+ * decision trace and the iterate dump exactly as admm_hip_logit_enet_state / admm_hip_poisson_state: record 0's z slot carries the tags
+ * the loop ran with, the held-out marker (2.0 / -2.0) on the rows of the fold. */
+ADMM_HIP_API int admm_hip_logit_enet_cv_state(const double* x, const double* y, int n, int p, int mem, int intercept, const int* fold_id, int nfolds, int fold,
+                         double lambda, double alpha, const admm_opts* opts, double* beta_out, int* niter_out, admm_stats* stats, double* trace_out,
+                         long long trace_cap, long long* ntrace_out, double* state_out, long long state_cap, long long* nstate_out);
+ADMM_HIP_API int admm_hip_poisson_cv_state(const double* x, const double* y, int n, int p, int mem, int intercept, const int* fold_id, int nfolds, int fold,
+                         double lambda, double alpha, const admm_opts* opts, double* beta_out, int* niter_out, admm_stats* stats, double* trace_out,
+                         long long trace_cap, long long* ntrace_out, double* state_out, long long state_cap, long long* nstate_out);
+
 /* Prepared-problem variant of the Lasso family (the "persistent context" anticipated for a
  * re-fitting caller; the R shim does not need it).  create = everything the reference does
  * before its lambda loop (copy/convert, DataStd, X'y, Gram, Spectra, factorisation:

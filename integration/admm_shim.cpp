@@ -406,6 +406,76 @@ BEGIN_RCPP
 END_RCPP
 }
 
+// K-fold cross-validation of the two calls above by held-out deviance, every fit on the full-data setup (not in the reference;
+// INTEGRATION.md): .Call("admm_logit_enet_cv", x, Y, lambda, alpha, fold_id, nfolds, intercept, opts) -> beta, niter of the full-data fit
+// as admm_logit_enet's; cv_mean, cv_se: k x ncell; fold_dev: (k ncell) x nfolds, row l k + c; idx_min, idx_1se: per column the 1-based
+// cell; lambda_min, lambda_1se.  fold_id: integer(0) = row i in fold (i - 1) mod nfolds, else nrow(x) 0-based fold numbers.
+static SEXP glm_cv_call(decltype(&admm_hip_logit_enet_cv) entry, SEXP x_, SEXP y_, SEXP lambda_, SEXP alpha_, SEXP fold_id_, SEXP nfolds_, SEXP intercept_, SEXP opts_) {
+    NumericMatrix x(x_);
+    NumericMatrix y(y_);
+    NumericVector lambda(lambda_);
+    NumericVector alpha_in(alpha_);
+    IntegerVector fold_id(fold_id_);
+    if (y.nrow() != x.nrow()) Rcpp::stop("nrow(x) should be equal to nrow(Y)");
+    if (fold_id.size() != 0 && fold_id.size() != x.nrow()) Rcpp::stop("fold_id must be empty or as long as nrow(x)");
+    const int ncell = lambda.size(), k = y.ncol(), nfolds = as<int>(nfolds_);
+    if (alpha_in.size() != ncell && alpha_in.size() != 1) Rcpp::stop("alpha must have one value or as many as lambda");
+    if (nfolds < 2) Rcpp::stop("nfolds must be at least 2");
+    NumericVector alpha(ncell);
+    for (int l = 0; l < ncell; ++l) alpha[l] = alpha_in[alpha_in.size() == 1 ? 0 : l];
+    admm_opts o = unpack_opts(opts_);
+    NumericMatrix beta(x.ncol() + 1, k * ncell), cv_mean(k, ncell), cv_se(k, ncell), fold_dev(k * ncell, nfolds);
+    IntegerVector niter(k * ncell), idx_min(k), idx_1se(k);
+    check(entry(x.begin(), y.begin(), x.nrow(), x.ncol(), k, ADMM_MEM_HOST, as<bool>(intercept_), fold_id.size() ? fold_id.begin() : nullptr, nfolds, lambda.begin(),
+                alpha.begin(), ncell, &o, beta.begin(), niter.begin(), cv_mean.begin(), cv_se.begin(), fold_dev.begin(), nullptr, nullptr, idx_min.begin(), idx_1se.begin(),
+                nullptr));
+    NumericVector lambda_min(k), lambda_1se(k);
+    for (int c = 0; c < k; ++c) { lambda_min[c] = lambda[idx_min[c]]; lambda_1se[c] = lambda[idx_1se[c]]; ++idx_min[c]; ++idx_1se[c]; }
+    return List::create(Named("beta") = beta, Named("niter") = niter, Named("lambda") = lambda, Named("alpha") = alpha, Named("cv_mean") = cv_mean, Named("cv_se") = cv_se,
+                        Named("fold_dev") = fold_dev, Named("idx_min") = idx_min, Named("idx_1se") = idx_1se, Named("lambda_min") = lambda_min,
+                        Named("lambda_1se") = lambda_1se);
+}
+RcppExport SEXP admm_logit_enet_cv(SEXP x_, SEXP y_, SEXP lambda_, SEXP alpha_, SEXP fold_id_, SEXP nfolds_, SEXP intercept_, SEXP opts_) {
+BEGIN_RCPP
+    return glm_cv_call(admm_hip_logit_enet_cv, x_, y_, lambda_, alpha_, fold_id_, nfolds_, intercept_, opts_);
+END_RCPP
+}
+RcppExport SEXP admm_poisson_cv(SEXP x_, SEXP y_, SEXP lambda_, SEXP alpha_, SEXP fold_id_, SEXP nfolds_, SEXP intercept_, SEXP opts_) {
+BEGIN_RCPP
+    return glm_cv_call(admm_hip_poisson_cv, x_, y_, lambda_, alpha_, fold_id_, nfolds_, intercept_, opts_);
+END_RCPP
+}
+
+// One vector, one cell and one fold held out (fold = -1: none) with the decision trace, as admm_logit_enet_state / admm_poisson_state:
+// .Call("admm_logit_enet_cv_state", x, y, lambda, alpha, fold_id, nfolds, fold, intercept, opts) -> beta (p + 1), niter, trace, ntrace
+static SEXP glm_cv_state_call(decltype(&admm_hip_logit_enet_cv_state) entry, SEXP x_, SEXP y_, SEXP lambda_, SEXP alpha_, SEXP fold_id_, SEXP nfolds_, SEXP fold_,
+                              SEXP intercept_, SEXP opts_) {
+    NumericMatrix x(x_);
+    NumericVector y(y_);
+    IntegerVector fold_id(fold_id_);
+    if (y.size() != x.nrow()) Rcpp::stop("nrow(x) should be equal to length(y)");
+    if (fold_id.size() != 0 && fold_id.size() != x.nrow()) Rcpp::stop("fold_id must be empty or as long as nrow(x)");
+    admm_opts o = unpack_opts(opts_);
+    NumericVector beta(x.ncol() + 1);
+    int niter = 0;
+    const long long cap = (long long)o.maxit + 2;
+    NumericMatrix trace(ADMM_TRACE_FIELDS, (int)cap);
+    long long ntrace = 0;
+    check(entry(x.begin(), y.begin(), x.nrow(), x.ncol(), ADMM_MEM_HOST, as<bool>(intercept_), fold_id.size() ? fold_id.begin() : nullptr, as<int>(nfolds_), as<int>(fold_),
+                as<double>(lambda_), as<double>(alpha_), &o, beta.begin(), &niter, nullptr, trace.begin(), cap, &ntrace, nullptr, 0, nullptr));
+    return List::create(Named("beta") = beta, Named("niter") = niter, Named("trace") = trace, Named("ntrace") = (double)ntrace);
+}
+RcppExport SEXP admm_logit_enet_cv_state(SEXP x_, SEXP y_, SEXP lambda_, SEXP alpha_, SEXP fold_id_, SEXP nfolds_, SEXP fold_, SEXP intercept_, SEXP opts_) {
+BEGIN_RCPP
+    return glm_cv_state_call(admm_hip_logit_enet_cv_state, x_, y_, lambda_, alpha_, fold_id_, nfolds_, fold_, intercept_, opts_);
+END_RCPP
+}
+RcppExport SEXP admm_poisson_cv_state(SEXP x_, SEXP y_, SEXP lambda_, SEXP alpha_, SEXP fold_id_, SEXP nfolds_, SEXP fold_, SEXP intercept_, SEXP opts_) {
+BEGIN_RCPP
+    return glm_cv_state_call(admm_hip_poisson_cv_state, x_, y_, lambda_, alpha_, fold_id_, nfolds_, fold_, intercept_, opts_);
+END_RCPP
+}
+
 // The symbol R/50_admm_dantzig.R:38 asks for and the reference never builds (src/TODO/Dantzig.cpp:32-99): doubles throughout.
 RcppExport SEXP admm_dantzig(SEXP x_, SEXP y_, SEXP lambda_, SEXP nlambda_, SEXP lmin_ratio_, SEXP standardize_, SEXP intercept_, SEXP opts_) {
 BEGIN_RCPP
